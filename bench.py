@@ -13,12 +13,21 @@ overlapped with backward.  Workload = BASELINE config 2 per GPU: bf16, seq_len 5
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the round brief) with two extra objects:
-  roofline     -- the dominant kernel (by time) of the step, measured live with HIP events recorded on
-                  the launch stream inside the timed region: algorithmic FLOPs / its total duration
-                  against the dense bf16 MFMA peak (2.5 PFLOP/s);
+Prints ONE JSON line on rank 0: `metric` / `value` / `unit` / `ms_per_step` of the K timed steps, plus the phase split
+and loss of those steps.  A plain run does nothing else.  `--full` adds what takes runs of its own after the timed
+region:
+  kernels, roofline -- per-kernel durations and the dominant kernel (by time) of the step, measured with HIP events
+                  recorded on the launch stream around every launch in a re-run of the K steps: algorithmic FLOPs / its
+                  total duration against the dense bf16 MFMA peak (2.5 PFLOP/s); `roofline.traffic` from two child
+                  `rocprofv3 --pmc` runs;
+  optimizer_step_ms -- the fused AdamW + clip that follows an accumulation window;
   cpu_baseline -- the CPU oracle (a port of the reference's CPU path, pinned to it by fixtures) timed
-                  on this box's host cores on a bounded sample of the same workload.
+                  on this box's host cores on a bounded sample of the same workload, with `loss_match` / `grad_match`
+                  of the HIP path on that very sample;
+  comm, grad_sync_ok -- N > 1 (or --force-dist): per-bucket collective times and the cross-rank gradient check.
+
+`--dump-outputs DIR` writes what the last timed step computed (its four losses and a fixed, seeded sample of the student
+gradient) as DIR/*.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -184,6 +193,29 @@ def measure_traffic(symbol, timeout_s=170):
     return out
 
 
+DUMP_PER_TENSOR = 16384
+
+
+def dump_outputs(dirname, student, losses):
+    """What the last timed step hands its caller, as float .npy files: the four losses (float64) and the student
+    gradient in float32 -- every element of a tensor of up to DUMP_PER_TENSOR elements, a fixed seeded sample of that
+    many (sorted indices) of every larger one, tensors in the order of the flat parameter buffer (~13 MB in all)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in zip(("total", "task", "distill", "teacher"), losses):
+        np.save(os.path.join(dirname, f"loss_{name}.npy"), np.array([v], dtype=np.float64))
+    g = torch.Generator().manual_seed(4242)
+    idx = []
+    for off, n, _ in student._slices.values():
+        if n <= DUMP_PER_TENSOR:
+            idx.append(torch.arange(off, off + n))
+        else:
+            idx.append(off + torch.randint(0, n, (DUMP_PER_TENSOR,), generator=g).sort().values)
+    idx = torch.cat(idx).to(student.flat_grad.device)
+    sample = student.flat_grad.index_select(0, idx).float().cpu().numpy()
+    np.save(os.path.join(dirname, "student_grad_sample.npy"), sample)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -226,7 +258,14 @@ def main():
                     help="MEASUREMENT ONLY (not the reported configuration): N idle workgroups (256 threads, 128 registers "
                          "per lane: a communication kernel's footprint) hold a CU slot each during every backward, on a "
                          "stream of their own -- how the backward reacts when RCCL's kernels take CUs (tests/csrc/cu_hog.hip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure per-kernel times / roofline / traffic, the optimizer step, the "
+                         "CPU baseline with loss and gradient match, and (N > 1) the communication report")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the losses and a seeded sample of the student gradient of the last timed step as DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", 0))
     local_rank = int(os.environ.get("LOCAL_RANK", 0))
@@ -359,6 +398,8 @@ def main():
         out = step()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, student, [float(x.detach()) for x in out])
     n_ph = 5
     names = ["student_fwd_teacher_beside", "wait_teacher_topk", "loss_fwd", "backward"]
     phase_ms = [0.0] * 4
@@ -379,7 +420,7 @@ def main():
     # recorded on the launch stream around every launch.  Kept out of the timed region because ~2 000
     # event records per step stretch the step by ~20 % (measured 39.8 vs 32.9 ms) and would understate `value`.
     prof = None
-    if not args.no_prof:
+    if args.full and not args.no_prof:
         student.overlap_dw = False  # one stream only, so that every event pair brackets exactly one kernel
         step(overlap=False)
         barrier()
@@ -393,7 +434,7 @@ def main():
         syms = ops.prof_symbols()
         student.overlap_dw = not args.no_overlap
     comm = None
-    if multi and reducer is not None and reducer.cuda:
+    if args.full and multi and reducer is not None and reducer.cuda:
         # Self-diagnosis of the N > 1 run (its first execution on real xGMI links is the driver's): the same steps again
         # with events on the communication stream around every bucket's collective and around the compute stream's final
         # wait for it (= the communication time NOT hidden under backward).  Outside the timed region.
@@ -432,7 +473,7 @@ def main():
         dt = float(tmax)
     losses = [float(x.detach()) for x in out]
     grad_sync_ok = None
-    if multi:  # after the all-reduce every rank must hold the same averaged gradient
+    if args.full and multi:  # after the all-reduce every rank must hold the same averaged gradient
         cs = student.flat_grad.float().abs().sum().double().reshape(1)
         cs = cs if args.backend == "nccl" else cs.cpu()
         lo, hi = cs.clone(), cs.clone()
@@ -520,29 +561,30 @@ def main():
                             "profiles/r04_gemm_yardstick.json: hipBLASLt / rocBLAS on the same shapes)"}
         if "roofline" in res and world == 1 and not args.no_traffic:
             res["roofline"].update(measure_traffic(res["roofline"]["kernel"]))
-        try:
-            # Not part of the metric (the distillation MICRO-step, repeated gradient_accumulation_steps times per
-            # optimizer step, train.py:336): the fused AdamW + global-norm clip that follows the last micro-step
-            # (HF trainer.py:1778-1796, 2539), measured on the gradients the timed steps left behind, lr = 0.
-            from speech_distill_amd.optim import FlatAdamW
-            opt = FlatAdamW(student, lr=0.0, weight_decay=0.01, clip=1.0)
-            opt.step()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(5):
+        if args.full:
+            try:
+                # Not part of the metric (the distillation MICRO-step, repeated gradient_accumulation_steps times per
+                # optimizer step, train.py:336): the fused AdamW + global-norm clip that follows the last micro-step
+                # (HF trainer.py:1778-1796, 2539), measured on the gradients the timed steps left behind, lr = 0.
+                from speech_distill_amd.optim import FlatAdamW
+                opt = FlatAdamW(student, lr=0.0, weight_decay=0.01, clip=1.0)
                 opt.step()
-            e1.record()
-            torch.cuda.synchronize()
-            res["optimizer_step_ms"] = e0.elapsed_time(e1) / 5
-            del opt
-        except Exception as e:
-            res["optimizer_step_ms"] = repr(e)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(5):
+                    opt.step()
+                e1.record()
+                torch.cuda.synchronize()
+                res["optimizer_step_ms"] = e0.elapsed_time(e1) / 5
+                del opt
+            except Exception as e:
+                res["optimizer_step_ms"] = repr(e)
         if args.experiment_pipeline or args.experiment_cached_rows or args.experiment_cu_hog:
             res["experiment"] = "NOT the reported configuration: " + " ".join(
                 f for f, on in (("--experiment-pipeline", args.experiment_pipeline),
                                 ("--experiment-cached-rows", args.experiment_cached_rows),
                                 (f"--experiment-cu-hog {args.experiment_cu_hog}", args.experiment_cu_hog)) if on)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 cb, sw, tw, cbatch, cout = cpu_baseline(args.cpu_sample_tokens, min(os.cpu_count() or 1, 16))
                 res["cpu_baseline"] = cb

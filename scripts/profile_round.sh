@@ -12,7 +12,7 @@ out=gpurun_out/prof_$tag
 mkdir -p $out
 export TMPDIR=/tmp
 root=$(pwd)
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/default -o run -- python3 $root/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-traffic > $out/default.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/default -o run -- python3 $root/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-traffic > $out/default.log 2>&1
 echo "[profile] default done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/serial -o run -- python3 $root/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-prof --no-overlap --no-traffic > $out/serial.log 2>&1
 echo "[profile] serial done"
