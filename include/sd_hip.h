@@ -158,6 +158,11 @@ int sd_swiglu_bwd(const void* dact, const void* gate_up, void* dgate_up, int M, 
 /* ---- embedding (HF:381) and its deterministic scatter-add backward (dE += scale * rows of dx) */
 int sd_embedding_fwd(const int64_t* ids, const void* E, void* x, int M, int H, int V, void* stream);
 int sd_embedding_bwd(const int64_t* ids, const void* dx, void* dE, int M, int H, int V, float scale, void* stream);
+/* the same scatter-add restricted to ids >= row_lo (0 <= row_lo <= V): rows of dE below row_lo are never read or written,
+ * the others get the sums of sd_embedding_bwd (same increasing-token order, no float atomics).  Stage-1 alignment
+ * (stage1.py:29-73): the embedding gradient is masked to the new speech-token rows [V - num_new_tokens, V). */
+int sd_embedding_bwd_range(const int64_t* ids, const void* dx, void* dE, int M, int H, int V, int row_lo, float scale,
+                           void* stream);
 /* dst [M,H] = 0, then dst[rows[i]] = src[i] (rows unique): un-compacts the gradient of the rows the head kept
  * (inverse of the row gather sd_embedding_fwd(rows, table=x) ; distillation_loss.py:45 `x[valid]` run backwards) */
 int sd_rows_scatter(const void* src, const int64_t* rows, void* dst, int n, int M, int H, void* stream);
@@ -217,6 +222,20 @@ int sd_kdloss_fwd_rows(const void* student_logits, const void* teacher_logits, c
 int sd_kdloss_bwd_rows(const void* student_logits, const void* teacher_logits, const void* top_k_v, const void* top_k_i,
                        const int64_t* row_labels, const void* row_stats, const float* loss_out, const float* grad_total,
                        void* grad_logits, int R, int V, int K, float temperature, float alpha, int dtype, void* stream);
+
+/* ---- causal-LM cross-entropy on selected rows: the Stage-1 loss (stage1.py: TRL SFTTrainer over HF
+ * Qwen3ForCausalLM(labels=...), i.e. HF ForCausalLMLoss -- shift by one, ignore_index -100, reduction "sum" divided by
+ * num_items_in_batch when the Trainer passes it, else the mean over valid rows).  Teacher-free counterpart of
+ * sd_kdloss_*_rows: logits [R,V] (bf16 or fp32 per `dtype`) whose rows the caller already shifted and selected,
+ * row_labels int64 [R] (-100 masks a row).  divisor: fp32 [1] in device memory (nullable = number of valid rows).
+ * loss_out fp32 [4] = {loss, sum of row losses, N valid, divisor used}; a zero divisor gives loss 0 and gradient 0.
+ * row_stats: scratch of sd_celoss_stats_bytes(R) kept from fwd to bwd.  grad_total fp32 [1] nullable (= 1);
+ * grad_logits may alias logits.  fp32 accumulation, fixed reduction order. */
+int64_t sd_celoss_stats_bytes(int R);
+int sd_celoss_fwd_rows(const void* logits, const int64_t* row_labels, const float* divisor, void* row_stats,
+                       float* loss_out, int R, int V, int dtype, void* stream);
+int sd_celoss_bwd_rows(const void* logits, const int64_t* row_labels, const void* row_stats, const float* loss_out,
+                       const float* grad_total, void* grad_logits, int R, int V, int dtype, void* stream);
 
 /* ---- fused AdamW on bf16 params with bf16 state (HF Trainer default optimizer on the bf16 student,
  * train.py:174,331-354; quirk Q5) and the global grad-norm / clip (HF trainer max_grad_norm). */
@@ -347,6 +366,19 @@ int sd_qwen3_backward_rows(const sd_qwen3_dims* d, const sd_qwen3_params* p, con
                            int64_t acts_bytes, void* dlogits, const int64_t* head_rows, int n_head_rows, void* scratch,
                            int64_t scratch_bytes, int B, int T, int accumulate, void* dx0_out,
                            sd_stage_cb on_grads_ready, void* cb_user, void* side_stream, void* stream);
+/* Stage-1 alignment backward (stage1.py:29-73 freeze_model_weights: every decoder weight frozen, the embedding / lm_head
+ * gradients masked to rows >= old_vocab = V - num_new_tokens).  Same arguments as sd_qwen3_backward_rows without dx0_out and
+ * the stage callback, plus grad_row_lo (0 <= grad_row_lo <= V, any value: the < 8 rows before the first multiple of 8 are
+ * handled apart from the aligned GEMM).  Writes ONLY rows [grad_row_lo, V) of g->embed, and of g->lm_head when untied
+ * (SD_BWD_ACCUMULATE adds, otherwise overwrites); never reads or writes the rows below grad_row_lo or any other gradient
+ * buffer (g->layers_host and g->final_norm may be NULL).  Launches the dX chain of the full backward (SD_BWD_RECOMPUTE
+ * honoured), no per-layer weight or gain gradient, the lm_head dW of the new rows beside the lm_head dX on side_stream,
+ * then sd_embedding_bwd_range. */
+int sd_qwen3_backward_embed_rows(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g,
+                                 const int64_t* ids, const int32_t* kv_len, const void* cos_tab, const void* sin_tab,
+                                 void* acts, int64_t acts_bytes, void* dlogits, const int64_t* head_rows, int n_head_rows,
+                                 void* scratch, int64_t scratch_bytes, int B, int T, int accumulate, int grad_row_lo,
+                                 void* side_stream, void* stream);
 
 /* ---- stream placement.  HIP multiplexes streams onto a few hardware queues (4 by default); streams that share a
  * queue never overlap.  Measures, with a `spin_us`-long busy-wait kernel on stream_a and an empty one on stream_b,

@@ -103,11 +103,15 @@ PROTOTYPES = {
     "sd_swiglu_bwd": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "sd_embedding_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "sd_embedding_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    "sd_embedding_bwd_range": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "sd_attn_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _f, _vp]),
     "sd_attn_bwd": (_i, [_vp] * 11 + [_i64] * 7 + [_i, _i, _i, _i, _i, _f, _vp]),
     "sd_attn_bwd2": (_i, [_vp] * 11 + [_i64] * 7 + [_i, _i, _i, _i, _i, _f, _vp, _vp]),
     "sd_logsoftmax_topk": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp]),
     "sd_kdloss_stats_bytes": (_i64, [_i, _i]),
+    "sd_celoss_stats_bytes": (_i64, [_i]),
+    "sd_celoss_fwd_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "sd_celoss_bwd_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "sd_kdloss_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp]),
     "sd_kdloss_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp]),
     "sd_gemm_grouped_tn": (_i, [_vp, _i, _i, _i, _vp]),
@@ -138,6 +142,8 @@ PROTOTYPES = {
                                    _i, _vp]),
     "sd_qwen3_backward_rows": (_i, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(Params), _vp, _vp, _vp, _vp, _vp, _i64,
                                     _vp, _vp, _i, _vp, _i64, _i, _i, _i, _vp, STAGE_CB, _vp, _vp, _vp]),
+    "sd_qwen3_backward_embed_rows": (_i, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(Params), _vp, _vp, _vp, _vp, _vp,
+                                          _i64, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _i, _vp, _vp]),
     "sd_qwen3_backward": (_i, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(Params), _vp, _vp, _vp, _vp, _vp, _i64,
                                _vp, _vp, _i64, _i, _i, _i, _vp, STAGE_CB, _vp, _vp, _vp]),
 }

@@ -427,14 +427,16 @@ __global__ __launch_bounds__(256) void rows_scatter_kernel(const bf16* __restric
 // that id (fixed order) and adds the total to dE[id]; other blocks exit.  No atomics on the gradient, no sort.
 // The later tokens with the same id are found by all 256 threads at once (a bitmap in LDS, walked in increasing token
 // order afterwards) -- every thread scanning all M ids itself cost 83 us at M = 2 048 and grew with M squared.
+// row_lo > 0 (sd_embedding_bwd_range): tokens whose id is below row_lo are skipped before anything else, so rows of dE
+// below row_lo are never read or written; the other rows get exactly the sums of the unrestricted kernel.
 constexpr int EMB_BM_WORDS = 2048;  // bitmap for up to 65 536 tokens; longer batches take the serial scan
 __global__ __launch_bounds__(256) void embedding_bwd_kernel(const int64_t* __restrict__ ids, const bf16* __restrict__ dx,
-                                                            bf16* dE, int M, int H, int V, float scale) {
+                                                            bf16* dE, int M, int H, int V, float scale, int row_lo) {
   __shared__ int first_flag;
   __shared__ unsigned same[EMB_BM_WORDS];
   const int m = blockIdx.x;
   const long id = ids[m];
-  if (id < 0 || id >= V) return;
+  if (id < row_lo || id >= V) return;
   if (threadIdx.x == 0) first_flag = 1;
   __syncthreads();
   for (int i = threadIdx.x; i < m; i += 256)
@@ -715,7 +717,18 @@ extern "C" int sd_embedding_bwd(const int64_t* ids, const void* dx, void* dE, in
                                 void* stream) {
   if (M <= 0 || (H & 7)) return SD_ERR_SHAPE;
   SdProfScope prof(SD_K_EMBED, 6.0 * M * H, ST);
-  hipLaunchKernelGGL(embedding_bwd_kernel, dim3(M), dim3(256), 0, ST, ids, (const bf16*)dx, (bf16*)dE, M, H, V, scale);
+  hipLaunchKernelGGL(embedding_bwd_kernel, dim3(M), dim3(256), 0, ST, ids, (const bf16*)dx, (bf16*)dE, M, H, V, scale, 0);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sd_embedding_bwd_range(const int64_t* ids, const void* dx, void* dE, int M, int H, int V, int row_lo,
+                                      float scale, void* stream) {
+  if (M <= 0 || (H & 7) || row_lo < 0 || row_lo > V) return SD_ERR_SHAPE;
+  SdProfScope prof(SD_K_EMBED, 6.0 * M * H, ST);
+  SD_PROF_LABEL("embedding_bwd_kernel");
+  hipLaunchKernelGGL(embedding_bwd_kernel, dim3(M), dim3(256), 0, ST, ids, (const bf16*)dx, (bf16*)dE, M, H, V, scale,
+                     row_lo);
   SD_CHECK_LAUNCH();
   return 0;
 }

@@ -424,6 +424,162 @@ extern "C" int sd_kdloss_bwd(const void* student_logits, const void* teacher_log
                         grad_logits, B, T, V, K, temperature, alpha, (hipStream_t)stream);
 }
 
+// ---------------------------------------------------------------------------------------- causal-LM cross-entropy
+// Stage-1 alignment loss (stage1.py: TRL SFTTrainer over HF Qwen3ForCausalLM(labels=...), i.e. HF's ForCausalLMLoss:
+// logits.float(), shift by one, cross_entropy(ignore_index=-100, reduction = "sum" / num_items_in_batch when the Trainer
+// passes num_items_in_batch, else "mean")) on rows the caller already shifted and selected -- the teacher-free
+// counterpart of sd_kdloss_*_rows.  Same row streaming as kd_fwd_kernel (PF chunks in flight per thread, unconditional
+// loads), one exponential per logit; per-row stats + a fixed-order single-block finalize: deterministic, no atomics.
+namespace {
+
+struct CeStats {  // 4 floats per row
+  float lse, loss, valid, pad;
+};
+
+template <typename T, int NF>
+__global__ __launch_bounds__(NF) void ce_fwd_kernel(const T* __restrict__ S, const int64_t* __restrict__ labels,
+                                                    CeStats* __restrict__ stats, int V) {
+  __shared__ float sc[32];
+  const int row = blockIdx.x;
+  const long y = labels[row];
+  if (y < 0 || y >= V) {  // -100 (and anything outside the vocabulary) masks the row
+    if (threadIdx.x == 0) stats[row] = CeStats{0.f, 0.f, 0.f, 0.f};
+    return;
+  }
+  const float k1 = 1.4426950408889634f;  // log2(e)
+  const T* s = S + (long)row * V;
+  float m = -INFINITY, s1 = 0.f;
+  constexpr int PF = 4;
+  typedef typename Ld8<T>::Raw Raw;
+  const int stride = NF * 8;
+  Raw sbuf[PF];
+  const int clast = ((V - 1) >> 3) << 3;
+#pragma unroll
+  for (int j = 0; j < PF; ++j) sbuf[j] = Ld8<T>::raw(s + min((int)threadIdx.x * 8 + j * stride, clast));
+  for (int c0 = threadIdx.x * 8; c0 < V; c0 += PF * stride) {
+#pragma unroll
+    for (int j = 0; j < PF; ++j) {
+      const int c = c0 + j * stride;
+      float f[8];
+      Ld8<T>::cvt(sbuf[j], f);
+      sbuf[j] = Ld8<T>::raw(s + min(c + PF * stride, clast));
+      if (c >= V) continue;
+      float cm = f[0];
+#pragma unroll
+      for (int e = 1; e < 8; ++e) cm = fmaxf(cm, f[e]);
+      if (cm > m) {
+        s1 *= __builtin_amdgcn_exp2f((m - cm) * k1);
+        m = cm;
+      }
+      const float mk1 = -m * k1;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s1 += __builtin_amdgcn_exp2f(__builtin_fmaf(f[e], k1, mk1));
+    }
+  }
+  const float M = block_max<NF>(m, sc);
+  s1 = block_sum<NF>(m == -INFINITY ? 0.f : s1 * __expf(m - M), sc);
+  const float lse = M + __logf(s1);
+  if (threadIdx.x == 0) stats[row] = CeStats{lse, lse - (float)s[y], 1.f, 0.f};
+}
+
+// out[0..3] = loss, sum of row losses, N valid rows, divisor used (single block, fixed order)
+__global__ __launch_bounds__(NT) void ce_finalize_kernel(const CeStats* __restrict__ stats, const float* __restrict__ divisor,
+                                                         float* __restrict__ out, int rows) {
+  __shared__ float sc[32];
+  float n = 0.f, sum = 0.f;
+  for (int r = threadIdx.x; r < rows; r += NT) {
+    const CeStats st = stats[r];
+    n += st.valid;
+    sum += st.loss;
+  }
+  n = block_sum<NT>(n, sc);
+  sum = block_sum<NT>(sum, sc);
+  if (threadIdx.x == 0) {
+    const float d = divisor ? divisor[0] : n;
+    out[0] = d != 0.f ? sum / d : 0.f;  // no valid row (or a zero divisor): loss 0, gradient 0
+    out[1] = sum;
+    out[2] = n;
+    out[3] = d;
+  }
+}
+
+// d loss / d s = go (softmax(s) - e_y) / divisor on valid rows, 0 elsewhere.  G may alias S.
+template <typename T>
+__global__ __launch_bounds__(NT) void ce_bwd_kernel(const T* S, const int64_t* __restrict__ labels,
+                                                    const CeStats* __restrict__ stats, const float* __restrict__ loss_out,
+                                                    const float* __restrict__ grad_out, T* G, int V) {
+  const int row = blockIdx.x;
+  const CeStats st = stats[row];
+  T* g = G + (long)row * V;
+  const float d = loss_out[3];
+  if (st.valid == 0.f || d == 0.f) {
+    float z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int c = threadIdx.x * 8; c < V; c += NT * 8) Ld8<T>::store(g + c, z);
+    return;
+  }
+  const float a = (grad_out ? grad_out[0] : 1.f) / d;
+  const long y = labels[row];
+  const T* s = S + (long)row * V;
+  for (int c = threadIdx.x * 8; c < V; c += NT * 8) {
+    float f[8], o[8];
+    Ld8<T>::load(s + c, f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = a * __expf(f[e] - st.lse);
+    if (y >= c && y < c + 8) o[y - c] -= a;
+    Ld8<T>::store(g + c, o);
+  }
+}
+
+int ce_check(const void* S, const int64_t* labels, int R, int V, int dtype) {
+  if (R <= 0 || V <= 0 || !labels) return SD_ERR_SHAPE;
+  if (V & 7) return SD_ERR_ALIGN;
+  if ((uintptr_t)S & 15) return SD_ERR_ALIGN;
+  if (dtype != SD_DTYPE_BF16 && dtype != SD_DTYPE_F32) return SD_ERR_UNSUPPORTED;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int64_t sd_celoss_stats_bytes(int R) { return (int64_t)R * sizeof(CeStats); }
+
+extern "C" int sd_celoss_fwd_rows(const void* logits, const int64_t* row_labels, const float* divisor, void* row_stats,
+                                  float* loss_out, int R, int V, int dtype, void* stream) {
+  if (int e = ce_check(logits, row_labels, R, V, dtype)) return e;
+  hipStream_t st = (hipStream_t)stream;
+  {
+    SdProfScope prof(SD_K_LOSS_FWD, (double)R * V * (dtype == SD_DTYPE_BF16 ? 2 : 4), st);
+    SD_PROF_LABEL("ce_fwd_kernel<%s, 512>", dtype == SD_DTYPE_BF16 ? "__bf16" : "float");
+    if (dtype == SD_DTYPE_BF16)
+      hipLaunchKernelGGL((ce_fwd_kernel<bf16, 512>), dim3(R), dim3(512), 0, st, (const bf16*)logits, row_labels,
+                         (CeStats*)row_stats, V);
+    else
+      hipLaunchKernelGGL((ce_fwd_kernel<float, 512>), dim3(R), dim3(512), 0, st, (const float*)logits, row_labels,
+                         (CeStats*)row_stats, V);
+    SD_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(NT), 0, st, (const CeStats*)row_stats, divisor, loss_out, R);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sd_celoss_bwd_rows(const void* logits, const int64_t* row_labels, const void* row_stats,
+                                  const float* loss_out, const float* grad_total, void* grad_logits, int R, int V, int dtype,
+                                  void* stream) {
+  if (int e = ce_check(logits, row_labels, R, V, dtype)) return e;
+  if ((uintptr_t)grad_logits & 15) return SD_ERR_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  SdProfScope prof(SD_K_LOSS_BWD, (double)R * V * (dtype == SD_DTYPE_BF16 ? 2 : 4) * 2, st);
+  SD_PROF_LABEL("ce_bwd_kernel<%s>", dtype == SD_DTYPE_BF16 ? "__bf16" : "float");
+  if (dtype == SD_DTYPE_BF16)
+    hipLaunchKernelGGL((ce_bwd_kernel<bf16>), dim3(R), dim3(NT), 0, st, (const bf16*)logits, row_labels,
+                       (const CeStats*)row_stats, loss_out, grad_total, (bf16*)grad_logits, V);
+  else
+    hipLaunchKernelGGL((ce_bwd_kernel<float>), dim3(R), dim3(NT), 0, st, (const float*)logits, row_labels,
+                       (const CeStats*)row_stats, loss_out, grad_total, (float*)grad_logits, V);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------------- loss rows
 // distillation_loss.py:31-45: the loss reads position t of sequence b iff t < T-1, labels[b][t+1] != -100 and (with a
 // speech mask) speech_mask[b][t+1] != 0.  One workgroup compacts the flat indices b*T+t of those rows IN ORDER (ballot

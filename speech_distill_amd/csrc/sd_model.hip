@@ -9,6 +9,8 @@
 #include "../../include/sd_hip.h"
 #include "sd_events.h"
 #include "sd_debug.h"
+#include "sd_common.cuh"
+#include "sd_prof.h"
 
 namespace {
 
@@ -163,6 +165,61 @@ bool fold_supported(const sd_qwen3_dims* d) {
   return d->head_dim == 128 && (h % 512) == 0 && h / 128 <= 16 && (d->inter % 64) == 0;
 }
 
+
+// Stage-1 lm_head dW rows [lo, hi) with hi - lo < 8, hi = lo rounded up to 8: the rows the aligned GEMM of
+// sd_qwen3_backward_embed_rows cannot start at (its operands must be 16-byte aligned).  dW[r,:] (+)= sum_k dY[k,r] X[k,:]
+// for k < K in increasing k per wave, the 16 waves' partials summed in wave order: deterministic.  One 16-byte load of dY
+// covers every row of the strip (they share one aligned group of 8 columns).
+constexpr int kStripWaves = 16;
+__global__ __launch_bounds__(1024) void head_dw_strip_kernel(const bf16* __restrict__ dY, const bf16* __restrict__ X,
+                                                             bf16* dW, int lo, int hi, int ldy, int H, int K, int acc) {
+  __shared__ float part[kStripWaves][512];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int c = blockIdx.x * 512 + lane * 8;
+  const int g0 = lo & ~7;
+  float a[8][8];
+#pragma unroll
+  for (int r = 0; r < 8; ++r)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a[r][e] = 0.f;
+  if (c < H) {
+    for (int k = w; k < K; k += kStripWaves) {
+      const bf16x8 y = *(const bf16x8*)(dY + (long)k * ldy + g0);
+      const bf16x8 x = *(const bf16x8*)(X + (long)k * H + c);
+#pragma unroll
+      for (int r = 0; r < 8; ++r)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) a[r][e] += (float)y[r] * (float)x[e];
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {  // (unrolled: a[][] stays in registers)
+    if (r < lo - g0 || r >= hi - g0) continue;  // block-uniform
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 8; ++e) part[w][lane * 8 + e] = a[r][e];
+    __syncthreads();
+    for (int j = threadIdx.x; j < 512; j += 1024) {
+      const int cc = blockIdx.x * 512 + j;
+      if (cc >= H) continue;
+      float t = 0.f;
+      for (int q = 0; q < kStripWaves; ++q) t += part[q][j];
+      bf16* o = dW + (long)(g0 + r) * H + cc;
+      *o = (bf16)(acc ? (float)*o + t : t);
+    }
+  }
+}
+
+int head_dw_strip(const void* dY, const void* X, void* dW, int lo, int hi, int ldy, int H, int K, int acc, void* stream) {
+  if (hi <= lo) return 0;
+  SdProfScope prof(SD_K_GEMM_TN, 2.0 * (hi - lo) * H * K, (hipStream_t)stream);
+  SD_PROF_LABEL("head_dw_strip_kernel");
+  hipLaunchKernelGGL(head_dw_strip_kernel, dim3((H + 511) / 512), dim3(1024), 0, (hipStream_t)stream, (const bf16*)dY,
+                     (const bf16*)X, (bf16*)dW, lo, hi, ldy, H, K, acc);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
 }  // namespace
 
 namespace {
@@ -290,13 +347,17 @@ extern "C" int sd_qwen3_backward(const sd_qwen3_dims* d, const sd_qwen3_params* 
                                 scratch_bytes, B, T, accumulate, dx0_out, on_grads_ready, cb_user, side_stream, stream);
 }
 
-extern "C" int sd_qwen3_backward_rows(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g,
-                                      const int64_t* ids, const int32_t* kv_len, const void* cos_tab, const void* sin_tab,
-                                      void* acts, int64_t acts_bytes, void* dlogits, const int64_t* head_rows,
-                                      int n_head_rows, void* scratch, int64_t scratch_bytes, int B, int T, int accumulate,
-                                      void* dx0_out, sd_stage_cb on_grads_ready, void* cb_user, void* side_stream,
-                                      void* stream) {
+// The student backward.  grad_row_lo < 0: every gradient (sd_qwen3_backward_rows).  grad_row_lo >= 0: Stage-1
+// (sd_qwen3_backward_embed_rows): the same dX chain, no per-layer weight / gain gradient, the lm_head dW over rows
+// [grad_row_lo, V) only and the embedding scatter restricted to ids >= grad_row_lo.
+static int backward_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g, const int64_t* ids,
+                         const int32_t* kv_len, const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes,
+                         void* dlogits, const int64_t* head_rows, int n_head_rows, void* scratch, int64_t scratch_bytes,
+                         int B, int T, int accumulate, void* dx0_out, sd_stage_cb on_grads_ready, void* cb_user,
+                         void* side_stream, void* stream, int grad_row_lo) {
   if (d->head_dim != 128) return SD_ERR_UNSUPPORTED;
+  const bool dw = grad_row_lo < 0;  // per-layer weight and gain gradients wanted
+  if (!dw && (grad_row_lo > d->vocab || dx0_out || on_grads_ready)) return SD_ERR_SHAPE;
   if (head_rows && (n_head_rows <= 0 || n_head_rows > B * T)) return SD_ERR_SHAPE;
   if (B <= 0 || T <= 0 || (accumulate & ~(SD_BWD_ACCUMULATE | SD_BWD_RECOMPUTE))) return SD_ERR_SHAPE;
   Sizes s(d, B, T);
@@ -332,21 +393,39 @@ extern "C" int sd_qwen3_backward_rows(const sd_qwen3_dims* d, const sd_qwen3_par
   const int top = (s.L - 1) & 1;  // buffer set of the last layer (the first one the backward visits)
   SIGNAL(0);  // dlogits (produced on `stream` by the caller) is final: lm_head dW runs beside lm_head dX
   int nsp = 1;
+  if (!dw) {
+    // Stage-1: dW of the new rows only.  The GEMM starts at the first multiple of 8 at or above grad_row_lo (16-byte
+    // aligned operands); the < 8 rows before it take the strip kernel.
+    const int lo = grad_row_lo, lo8 = ((lo + 7) & ~7) < s.V ? ((lo + 7) & ~7) : s.V;
+    const void* xs = head_rows ? (const void*)xn_rows : (const void*)xn_f;
+    const int K = head_rows ? n_head_rows : s.M;
+    void* hs = (ovl & 1) ? wstream : stream;
+    char* gh = (char*)g->lm_head;
+    if (lo8 < s.V)
+      RUN(sd_gemm_bf16((const char*)dlogits + (int64_t)lo8 * 2, xs, gh + (int64_t)lo8 * s.h * 2,
+                       ACC(gh + (int64_t)lo8 * s.h * 2), s.V - lo8, s.h, K, s.V, s.h, s.h, s.h, 1, 1, hs));
+    RUN(head_dw_strip(dlogits, xs, g->lm_head, lo, lo8, s.V, s.h, K, acc, hs));
+  }
   if (head_rows) {
     // dlogits holds only the n_head_rows rows the forward produced; every other row of d(xn_f) is zero
-    RUN(sd_gemm_bf16(dlogits, xn_rows, g->lm_head, ACC(g->lm_head), s.V, s.h, n_head_rows, s.V, s.h, s.h, s.h, 1, 1,
-                     (ovl & 1) ? wstream : stream));
+    if (dw)
+      RUN(sd_gemm_bf16(dlogits, xn_rows, g->lm_head, ACC(g->lm_head), s.V, s.h, n_head_rows, s.V, s.h, s.h, s.h, 1, 1,
+                       (ovl & 1) ? wstream : stream));
     RUN(sd_gemm_bf16_splitk(dlogits, p->lm_head, b.dxb[top], nullptr, n_head_rows, s.h, s.V, s.V, s.h, s.h, 0, 0, 1,
                             b.ws_splitk, b.splitk_bytes, stream));
     RUN(sd_rows_scatter(b.dxb[top], head_rows, b.dxn, n_head_rows, s.M, s.h, stream));
   } else {
-    RUN(sd_gemm_bf16(dlogits, xn_f, g->lm_head, ACC(g->lm_head), s.V, s.h, s.M, s.V, s.h, s.h, s.h, 1, 1,
-                     (ovl & 1) ? wstream : stream));
+    if (dw)
+      RUN(sd_gemm_bf16(dlogits, xn_f, g->lm_head, ACC(g->lm_head), s.V, s.h, s.M, s.V, s.h, s.h, s.h, 1, 1,
+                       (ovl & 1) ? wstream : stream));
     RUN(sd_gemm_bf16_splitk_partial(dlogits, p->lm_head, b.dxn, s.M, s.h, s.V, s.V, s.h, s.h, 0, 1, b.ws_splitk,
                                     b.splitk_bytes, &nsp, stream));
   }
-  if (g->embed != g->lm_head && !acc)
-    if (hipMemsetAsync(g->embed, 0, (size_t)s.V * s.h * 2, (hipStream_t)stream) != hipSuccess) return SD_ERR_WORKSPACE;
+  if (g->embed != g->lm_head && !acc) {
+    const int64_t r0 = dw ? 0 : grad_row_lo;
+    if (hipMemsetAsync((char*)g->embed + r0 * s.h * 2, 0, (size_t)(s.V - r0) * s.h * 2, (hipStream_t)stream) != hipSuccess)
+      return SD_ERR_WORKSPACE;
+  }
   // the norm backward sums the split-K slabs itself (no separate reduce pass)
 #define NORM_BWD(X, W, RSTD, DRES, DX, DW, WS, RS, EV)                                                                   \
   do {                                                                                                                   \
@@ -354,7 +433,8 @@ extern "C" int sd_qwen3_backward_rows(const sd_qwen3_dims* d, const sd_qwen3_par
                                           EV, stream));                                                                  \
     else RUN(sd_rmsnorm_bwd2(b.dxn, X, W, RSTD, DRES, DX, DW, acc, WS, s.M, s.h, RS, EV, stream));                         \
   } while (0)
-  NORM_BWD(x_last, p->final_norm, (const float*)rstd_f, nullptr, b.dxa[top], g->final_norm, b.ws_norm, nullptr, nullptr);
+  NORM_BWD(x_last, p->final_norm, (const float*)rstd_f, nullptr, b.dxa[top], dw ? g->final_norm : nullptr, b.ws_norm, nullptr,
+           nullptr);
   JOIN();
   if (on_grads_ready) on_grads_ready(SD_STAGE_HEAD, cb_user);
   // The four weight gradients of a layer run as ONE persistent grouped launch (sd_gemm_grouped_tn: 926 vs 587 TFLOP/s
@@ -362,7 +442,7 @@ extern "C" int sd_qwen3_backward_rows(const sd_qwen3_dims* d, const sd_qwen3_par
   // the chain of the NEXT layer; that layer joins it (event) before it overwrites the gradient buffer they share,
   // and only then is the finished layer reported to the caller.  SD_OVERLAP_MASK bit 3 = 0 keeps four separate GEMMs
   // launched as their inputs appear.
-  const bool grouped = (ovl & 8) != 0;
+  const bool grouped = dw && (ovl & 8) != 0;
   const bool batch_gains = grouped && (ovl & 16) != 0;  // bit 4: one batched gain-gradient reduce per layer
   int pending = -1;  // layer whose grouped dW is in flight on the side stream
   for (int l = s.L - 1; l >= 0; --l) {
@@ -371,13 +451,14 @@ extern "C" int sd_qwen3_backward_rows(const sd_qwen3_dims* d, const sd_qwen3_par
     char *dxb = b.dxb[P], *dqkv = b.dqkv[P], *dgu = b.dgu[P];
     const LayerActs a = layer_acts(s, base, l, save);
     const sd_qwen3_layer& w = p->layers_host[l];
-    const sd_qwen3_layer& gw = g->layers_host[l];
+    static const sd_qwen3_layer kNoGrads = {};
+    const sd_qwen3_layer& gw = dw ? g->layers_host[l] : kNoGrads;  // Stage-1: g->layers_host may be NULL
     // recompute: this layer's work set was last read by the weight-gradient GEMMs of layer l+2, which `stream` has
     // already waited for (the `pending` join of layer l+1 below)
     if (save == SD_SAVE_LAYER_INPUTS && l != s.L - 1)
       RUN(layer_forward(d, s, a, w, nullptr, true, kv_len, cos_tab, sin_tab, B, T, stream));
     // MLP
-    if (!grouped) {
+    if (!grouped && dw) {
       SIGNAL(0);  // dx_in final
       RUN(sd_gemm_bf16(dx_in, a.act, gw.wdown, ACC(gw.wdown), s.h, s.I, s.M, s.h, s.I, s.I, s.I, 1, 1, wstream));
     }
@@ -391,15 +472,15 @@ extern "C" int sd_qwen3_backward_rows(const sd_qwen3_dims* d, const sd_qwen3_par
         return rc;
       }
     }
-    if (!grouped) SIGNAL(1);  // dgu final
+    if (!grouped && dw) SIGNAL(1);  // dgu final
     RUN(sd_gemm_bf16_splitk_partial(dgu, w.wgu, b.dxn, s.M, s.h, 2 * s.I, 2 * s.I, s.h, s.h, 0, 1, b.ws_splitk,
                                     b.splitk_bytes, &nsp, stream));
-    if (!grouped) RUN(sd_gemm_bf16(dgu, a.xn2, gw.wgu, ACC(gw.wgu), 2 * s.I, s.h, s.M, 2 * s.I, s.h, s.h, s.h, 1, 1, wstream));
+    if (!grouped && dw) RUN(sd_gemm_bf16(dgu, a.xn2, gw.wgu, ACC(gw.wgu), 2 * s.I, s.h, s.M, 2 * s.I, s.h, s.h, s.h, 1, 1, wstream));
     // gain gradients of the layer: the kernels leave per-workgroup partial sums, ONE batched reduce finishes all four
     // (input norm, post-attention norm, q gain, k gain) on the side stream once the layer's last kernel is enqueued
     NORM_BWD(a.x_mid, w.ln2, (const float*)a.rstd2, dx_in, dxb, batch_gains ? nullptr : gw.ln2, b.ws_norm2[P],
-             (ovl & 2) ? side_stream : nullptr, s2 ? (void*)g_ev[8] : nullptr);
-    if (!grouped) SIGNAL(2);  // dxb final
+             ((ovl & 2) && dw) ? side_stream : nullptr, (s2 && dw) ? (void*)g_ev[8] : nullptr);
+    if (!grouped && dw) SIGNAL(2);  // dxb final
     // attention
     // d(attention output) = dxb . Wo with delta = rowsum(dO * O) in the epilogue (one 128-column tile = one head)
     const void* o_for_delta = a.ao;
@@ -409,14 +490,14 @@ extern "C" int sd_qwen3_backward_rows(const sd_qwen3_dims* d, const sd_qwen3_par
       else if (rc) return rc;
       else o_for_delta = nullptr;
     }
-    if (!grouped) RUN(sd_gemm_bf16(dxb, a.ao, gw.wo, ACC(gw.wo), s.h, s.QD, s.M, s.h, s.QD, s.QD, s.QD, 1, 1, wstream));
+    if (!grouped && dw) RUN(sd_gemm_bf16(dxb, a.ao, gw.wo, ACC(gw.wo), s.h, s.QD, s.M, s.h, s.QD, s.QD, s.QD, 1, 1, wstream));
     RUN(sd_attn_bwd2(a.qk, a.qk + (int64_t)s.QD * 2, a.qkv + (int64_t)(s.QD + s.KD) * 2, o_for_delta, b.dao, (const float*)a.lse,
                     (float*)b.delta, b.dqk, b.dqk + (int64_t)s.QD * 2, dqkv + (int64_t)(s.QD + s.KD) * 2, kv_len, s.QK,
                     s.QK, s.QKV, s.QD, s.QK, s.QK, s.QKV, B, T, s.Hq, s.Hkv, 128, scale, (ovl & 4) ? side_stream : nullptr, stream));
     RUN(sd_qknorm_rope_bwd2(b.dqk, a.qkv, w.q_gain, w.k_gain, cos_tab, sin_tab, dqkv, batch_gains ? nullptr : gw.q_gain,
                             batch_gains ? nullptr : gw.k_gain, acc, b.ws_qk[P], s.M, T, s.Hq, s.Hkv, d->eps,
-                            (ovl & 2) ? side_stream : nullptr, s2 ? (void*)g_ev[9] : nullptr, stream));
-    SIGNAL(3);  // dqkv final (and with it dx_in, dgu, dxb of this layer)
+                            ((ovl & 2) && dw) ? side_stream : nullptr, (s2 && dw) ? (void*)g_ev[9] : nullptr, stream));
+    if (dw) SIGNAL(3);  // dqkv final (and with it dx_in, dgu, dxb of this layer)
     if (grouped) {
       sd_gemm_problem pr[4] = {
           {dqkv, a.xn1, gw.wqkv, s.QKV, s.h, s.h, s.QKV, s.h},    // dW_qkv  [QKV,h]  = dqkv^T . xn1
@@ -431,7 +512,7 @@ extern "C" int sd_qwen3_backward_rows(const sd_qwen3_dims* d, const sd_qwen3_par
         return rc;
       }
       if (!batch_gains && s2 && hipEventRecord(g_ev[10 + P], s2) != hipSuccess) return SD_ERR_WORKSPACE;
-    } else {
+    } else if (dw) {
       RUN(sd_gemm_bf16(dqkv, a.xn1, gw.wqkv, ACC(gw.wqkv), s.QKV, s.h, s.M, s.QKV, s.h, s.h, s.h, 1, 1, wstream));
     }
     RUN(sd_gemm_bf16_splitk_partial(dqkv, w.wqkv, b.dxn, s.M, s.h, s.QKV, s.QKV, s.h, s.h, 0, 1, b.ws_splitk,
@@ -439,7 +520,7 @@ extern "C" int sd_qwen3_backward_rows(const sd_qwen3_dims* d, const sd_qwen3_par
     if (grouped) {
       // the previous layer's grouped dW reads the buffer this layer is about to overwrite with its output gradient
       if (pending >= 0 && s2 && hipStreamWaitEvent(s1, g_ev[10 + (pending & 1)], 0) != hipSuccess) return SD_ERR_WORKSPACE;
-    } else {
+    } else if (dw) {
       JOIN();  // the layer's dW GEMMs are done before their inputs are overwritten and before the callback
     }
     NORM_BWD(a.x_in, w.ln1, (const float*)a.rstd1, dxb, dx_out, batch_gains ? nullptr : gw.ln1,
@@ -460,7 +541,7 @@ extern "C" int sd_qwen3_backward_rows(const sd_qwen3_dims* d, const sd_qwen3_par
     if (grouped) {
       if (pending >= 0 && on_grads_ready) on_grads_ready(pending, cb_user);
       pending = l;
-    } else if (on_grads_ready) {
+    } else if (on_grads_ready && dw) {
       on_grads_ready(l, cb_user);
     }
   }
@@ -469,11 +550,32 @@ extern "C" int sd_qwen3_backward_rows(const sd_qwen3_dims* d, const sd_qwen3_par
     if (on_grads_ready) on_grads_ready(pending, cb_user);
   }
   JOIN();  // everything the side stream was given (gain reduces, dQ) before the call returns
-  if (!dx0_out) RUN(sd_embedding_bwd(ids, b.dxa[1], g->embed, s.M, s.h, s.V, 1.0f, stream));
+  if (!dw) RUN(sd_embedding_bwd_range(ids, b.dxa[1], g->embed, s.M, s.h, s.V, grad_row_lo, 1.0f, stream));
+  else if (!dx0_out) RUN(sd_embedding_bwd(ids, b.dxa[1], g->embed, s.M, s.h, s.V, 1.0f, stream));
   if (on_grads_ready) on_grads_ready(SD_STAGE_EMBED, cb_user);
 #undef ACC
 #undef NORM_BWD
 #undef SIGNAL
 #undef JOIN
   return 0;
+}
+
+extern "C" int sd_qwen3_backward_rows(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g,
+                                      const int64_t* ids, const int32_t* kv_len, const void* cos_tab, const void* sin_tab,
+                                      void* acts, int64_t acts_bytes, void* dlogits, const int64_t* head_rows,
+                                      int n_head_rows, void* scratch, int64_t scratch_bytes, int B, int T, int accumulate,
+                                      void* dx0_out, sd_stage_cb on_grads_ready, void* cb_user, void* side_stream,
+                                      void* stream) {
+  return backward_impl(d, p, g, ids, kv_len, cos_tab, sin_tab, acts, acts_bytes, dlogits, head_rows, n_head_rows, scratch,
+                       scratch_bytes, B, T, accumulate, dx0_out, on_grads_ready, cb_user, side_stream, stream, -1);
+}
+
+extern "C" int sd_qwen3_backward_embed_rows(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g,
+                                            const int64_t* ids, const int32_t* kv_len, const void* cos_tab,
+                                            const void* sin_tab, void* acts, int64_t acts_bytes, void* dlogits,
+                                            const int64_t* head_rows, int n_head_rows, void* scratch, int64_t scratch_bytes,
+                                            int B, int T, int accumulate, int grad_row_lo, void* side_stream, void* stream) {
+  if (grad_row_lo < 0) return SD_ERR_SHAPE;
+  return backward_impl(d, p, g, ids, kv_len, cos_tab, sin_tab, acts, acts_bytes, dlogits, head_rows, n_head_rows, scratch,
+                       scratch_bytes, B, T, accumulate, nullptr, nullptr, nullptr, side_stream, stream, grad_row_lo);
 }

@@ -200,6 +200,15 @@ def embedding_bwd(ids, dx, dE, scale=1.0):
     return dE
 
 
+def embedding_bwd_range(ids, dx, dE, row_lo, scale=1.0):
+    """dE[id] += scale * sum of the dx rows carrying id, for ids >= row_lo only (rows below row_lo untouched)."""
+    V, H = dE.shape
+    check(load_lib().sd_embedding_bwd_range(ids.data_ptr(), dx.data_ptr(), dE.data_ptr(), ids.numel(), H, V, int(row_lo),
+                                            float(scale), _stream()),
+          "sd_embedding_bwd_range")
+    return dE
+
+
 # --------------------------------------------------------------------------------------- attention
 def attn_fwd(q, k, v, B, T, Hq, Hkv, kv_len=None):
     """q [B*T, Hq*128], k/v [B*T, Hkv*128] (any row stride, unit column stride)."""
@@ -382,6 +391,45 @@ class KDLossRowsFn(torch.autograd.Function):
                                             stats.data_ptr(), out.data_ptr(), go.data_ptr(), grad.data_ptr(), R, V, K,
                                             temperature, alpha, dt, _stream()), "sd_kdloss_bwd_rows")
         return grad, None, None, None, None, None, None, None
+
+
+class CELossRowsFn(torch.autograd.Function):
+    """Causal-LM cross-entropy on rows the caller already shifted and selected (Stage-1 loss: HF ForCausalLMLoss as the
+    reference's SFTTrainer computes it): logits [R,V] bf16/fp32, row_labels [R] (-100 masks a row), divisor: fp32 [1] device
+    tensor = num_items_in_batch (None = mean over valid rows).  Returns (loss, out fp32[4] = loss, sum, N, divisor)."""
+
+    @staticmethod
+    def forward(ctx, logits, row_labels, divisor, inplace_grad):
+        s = _need(logits, None, "logits")
+        R, V = s.shape
+        dt = _dt(s)
+        lib = load_lib()
+        row_labels = _need(row_labels.to(torch.int64), torch.int64, "row_labels")
+        if divisor is not None:
+            divisor = _need(divisor.to(device=s.device, dtype=torch.float32).reshape(1), torch.float32, "divisor")
+        stats = torch.empty(lib.sd_celoss_stats_bytes(R), dtype=torch.uint8, device=s.device)
+        out = torch.empty(4, dtype=torch.float32, device=s.device)
+        check(lib.sd_celoss_fwd_rows(s.data_ptr(), row_labels.data_ptr(), _p(divisor), stats.data_ptr(), out.data_ptr(), R, V,
+                                     dt, _stream()), "sd_celoss_fwd_rows")
+        ctx.save_for_backward(s, row_labels, stats, out)
+        ctx.cfg = (R, V, dt, bool(inplace_grad))
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, g_total, _g_out):
+        s, row_labels, stats, out = ctx.saved_tensors
+        R, V, dt, inplace = ctx.cfg
+        grad = s if inplace else torch.empty_like(s)
+        go = g_total.to(torch.float32).reshape(1).contiguous()
+        check(load_lib().sd_celoss_bwd_rows(s.data_ptr(), row_labels.data_ptr(), stats.data_ptr(), out.data_ptr(),
+                                            go.data_ptr(), grad.data_ptr(), R, V, dt, _stream()), "sd_celoss_bwd_rows")
+        return grad, None, None, None
+
+
+def celoss_rows(logits, row_labels, divisor=None, inplace_grad=False):
+    """-> (loss 0-d fp32, out fp32[4]); differentiable w.r.t. ``logits`` (see CELossRowsFn)."""
+    return CELossRowsFn.apply(logits, row_labels, divisor, inplace_grad)
 
 
 def left_padded(attention_mask):

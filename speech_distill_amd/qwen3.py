@@ -210,6 +210,9 @@ class HipQwen3ForCausalLM(nn.Module):
         self.fold_norm_gains = True
         self._folded = None  # (flat._version, folded weight buffer, Params, Layers)
         self._lora = None    # lora.LoraState once lora.get_lora_model() has attached an adapter (train.py:180-202)
+        # Stage-1 alignment (stage1.freeze_model_weights, reference stage1.py:29-73): the first vocabulary row whose
+        # embedding / lm_head gradient is kept.  None = normal training (every gradient, labels ignored by forward).
+        self.stage1_row_lo = None
         if init_std:
             self.init_weights(seed, init_std)
 
@@ -518,9 +521,23 @@ class HipQwen3ForCausalLM(nn.Module):
             self._grads_live = True
         return accumulate
 
+    def check_stage1(self):
+        """Stage-1 mode trains the embedding (and an untied lm_head) only: anything else trainable is an inconsistent freeze."""
+        heads = {"model.embed_tokens.weight", "lm_head.weight"}
+        bad = sorted(n for n, p in self._params.items() if p.requires_grad and n not in heads)
+        if bad or self._lora is not None:
+            raise ValueError("Stage-1 mode (stage1_row_lo set by freeze_model_weights) trains only the embedding rows of the "
+                             "new tokens, but " + (f"{len(bad)} body parameters are trainable (e.g. {bad[0]})" if bad else
+                                                   "a LoRA adapter is attached") +
+                             "; call freeze_model_weights again or set model.stage1_row_lo = None")
+        if not 0 <= int(self.stage1_row_lo) <= self.dims.vocab_size:
+            raise ValueError(f"stage1_row_lo {self.stage1_row_lo} outside [0, {self.dims.vocab_size}]")
+
     def _run_backward(self, input_ids, kv_len, acts, dlogits, rows=None, recompute=False):
         lib = load_lib()
         B, T = input_ids.shape
+        if self.stage1_row_lo is not None:
+            return self._run_backward_stage1(input_ids, kv_len, acts, dlogits, rows, recompute)
         accumulate = self._ensure_grads()
         red = getattr(self, "_reducer", None)
         dx0 = None
@@ -552,6 +569,27 @@ class HipQwen3ForCausalLM(nn.Module):
         if self._lora is not None:
             self._lora.grads_stale = True
 
+    def _run_backward_stage1(self, input_ids, kv_len, acts, dlogits, rows, recompute):
+        """sd_qwen3_backward_embed_rows: dX chain only, gradient rows [stage1_row_lo, V) of embed_tokens (+ lm_head)."""
+        self.check_stage1()
+        if getattr(self, "_reducer", None) is not None:
+            raise NotImplementedError("Stage-1 alignment is single-GPU (no data-parallel gradient exchange)")
+        lib = load_lib()
+        B, T = input_ids.shape
+        accumulate = self._ensure_grads()
+        if not dlogits.is_contiguous():
+            dlogits = dlogits.contiguous()
+        cos, sin = self._tables(T, input_ids.device)
+        sbytes = lib.sd_qwen3_bwd_scratch_bytes(C.byref(self._cdims), B, T)
+        scratch = torch.empty(sbytes, dtype=torch.uint8, device=input_ids.device)
+        check(lib.sd_qwen3_backward_embed_rows(C.byref(self._cdims), C.byref(self._cparams), C.byref(self._cgrads),
+                                               input_ids.data_ptr(), _p(kv_len), cos.data_ptr(), sin.data_ptr(),
+                                               acts.data_ptr(), acts.numel(), dlogits.data_ptr(), _p(rows),
+                                               0 if rows is None else rows.numel(), scratch.data_ptr(), sbytes, B, T,
+                                               (BWD_ACCUMULATE if accumulate else 0) | (BWD_RECOMPUTE if recompute else 0),
+                                               int(self.stage1_row_lo), self._side_stream_ptr(input_ids.device), _stream()),
+              "sd_qwen3_backward_embed_rows")
+
     def finalize_grads(self):
         """Called by the optimizer / the clipping hook before they read gradients: a LoRA student projects the
         accumulated weight gradient onto its adapter (dA = s B^T dW, dB = s dW A^T) here, once per optimizer step."""
@@ -565,6 +603,14 @@ class HipQwen3ForCausalLM(nn.Module):
         g = self.flat_grad
         if self._lora is not None:
             return self._lora.optim_segments()
+        if self.stage1_row_lo is not None:
+            # Stage-1: the embedding (+ untied lm_head), matrices, so weight decay applies (HF's groups, stage1.py's adamw_torch)
+            segs = []
+            for name in ("model.embed_tokens.weight", "lm_head.weight"):
+                if name in self._slices:
+                    o, n, _ = self._slices[name]
+                    segs.append(("bf16", self.flat[o:o + n], None if g is None else g[o:o + n], True, None))
+            return segs
         if not split_decay:
             return [("bf16", self.flat, g, True, None)]
         return [("bf16", self.flat[a:b], None if g is None else g[a:b], m, None) for a, b, m in self._decay_runs()]
@@ -593,7 +639,8 @@ class HipQwen3ForCausalLM(nn.Module):
 
     def forward(self, input_ids=None, attention_mask=None, labels=None, logit_rows=None, **kwargs):
         """Returns an object with ``.logits`` [B,T,V] (bf16).  ``labels`` is accepted and ignored: the
-        reference leaves it in ``inputs`` at train.py:54, which only makes HF compute an unused CE.
+        reference leaves it in ``inputs`` at train.py:54, which only makes HF compute an unused CE.  In Stage-1 mode
+        (``stage1_row_lo`` set by ``stage1.freeze_model_weights``) ``labels`` gives ``.loss`` instead: ``_forward_stage1``.
         ``logit_rows`` (int64 [R], flat b*T+t indices, unique): apply the lm_head to those rows only and return
         ``.logits`` [R,V] -- the training step passes the rows the loss reads (``ops.loss_rows``).
         ``concurrent=True`` (keyword): the caller runs another pass beside this one on a second stream (the frozen
@@ -609,16 +656,42 @@ class HipQwen3ForCausalLM(nn.Module):
             am = attention_mask.to(ids.device)
             if am.shape != ids.shape:
                 raise ValueError(f"attention_mask {tuple(am.shape)} != input_ids {tuple(ids.shape)}")
-            if self.validate_padding and not kwargs.get("padding_checked", False) and bool(left_padded(am)):
+            stage1_loss = self.stage1_row_lo is not None and labels is not None  # (ops.loss_rows checks the mask then)
+            if (self.validate_padding and not kwargs.get("padding_checked", False) and not stage1_loss
+                    and bool(left_padded(am))):
                 raise ValueError("attention_mask is not right-padded (a 1 follows a 0): the HIP attention kernels take a "
                                  "valid-prefix length per sequence, as ProcessedDataCollator produces (data.py:280-327)")
             kv_len = am.sum(-1).to(torch.int32).contiguous()
+        if self.stage1_row_lo is not None and labels is not None:
+            return self._forward_stage1(ids, am if attention_mask is not None else None, kv_len, labels, **kwargs)
         if torch.is_grad_enabled() and (self._lora is not None or any(p.requires_grad for p in self._params.values())):
             logits = _DecoderFn.apply(self._anchor, ids, kv_len, self, rows, bool(kwargs.get("concurrent", False)))
         else:
             logits, _ = self._run_forward(ids, kv_len, save=SAVE_NONE, rows=rows,
                                           concurrent=bool(kwargs.get("concurrent", False)))
         return CausalLMOutput(logits=logits)
+
+    def _forward_stage1(self, ids, am, kv_len, labels, num_items_in_batch=None, stage1_inplace_grad=False, **_):
+        """Stage-1 loss (reference stage1.py: SFTTrainer -> HF ForCausalLMLoss): causal-LM cross-entropy over the rows whose
+        next label is not -100, summed and divided by ``num_items_in_batch`` when given (else the mean).  The rows are
+        selected on the GPU (``ops.loss_rows``, the one host read), the lm_head runs on those rows only, and the loss is
+        sd_celoss_*_rows.  ``.logits`` is then [R,V] for the rows ``.logit_rows``.  ``stage1_inplace_grad``: the loss
+        gradient overwrites those logits (the caller does not keep them)."""
+        from .ops import celoss_rows, loss_rows
+        self.check_stage1()
+        rows, row_labels = loss_rows(labels.to(ids.device), right_padded=(am,) if am is not None else ())
+        if rows.numel() == 0:  # nothing to predict: one masked row keeps every launch well-formed (loss 0, gradient 0)
+            rows = torch.zeros(1, dtype=torch.int64, device=ids.device)
+            row_labels = torch.full((1,), -100, dtype=torch.int64, device=ids.device)
+        div = None
+        if num_items_in_batch is not None:
+            div = torch.as_tensor(num_items_in_batch, dtype=torch.float32).to(ids.device).reshape(1)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self._params.values()):
+            logits = _DecoderFn.apply(self._anchor, ids, kv_len, self, rows, False)
+        else:
+            logits, _ = self._run_forward(ids, kv_len, save=SAVE_NONE, rows=rows)
+        loss, _ = celoss_rows(logits, row_labels, div, inplace_grad=bool(stage1_inplace_grad))
+        return CausalLMOutput(loss=loss, logits=logits, logit_rows=rows)
 
     def zero_grad(self, set_to_none: bool = True):
         # keep the flat buffer; the next backward overwrites (accumulate=0) instead of adding

@@ -18,7 +18,81 @@ from .distillation_loss import DistillationLoss
 from .qwen3 import HipQwen3ForCausalLM
 
 
-class DistillationTrainer(Trainer):
+class FlatStudentTrainer(Trainer):
+    """HF Trainer plumbing shared by the trainers of a flat-buffer student (``HipQwen3ForCausalLM``): the data-parallel
+    wrapper, tokens/sec in the training log, the fused optimizer and its one-reduction gradient clip, and
+    ``save_pretrained`` checkpoints.  Subclasses set ``tokens_seen``, ``_tps_mark``, ``_hip_dp`` and ``fused_optimizer``."""
+
+    # ------------------------------------------------------------------------------ HF Trainer plumbing
+    def _wrap_model(self, model, training=True, dataloader=None):
+        """HF trainer.py:1602-1626: a model this hook leaves unwrapped goes through ``accelerator.prepare``, which under
+        torchrun wraps it in torch DDP (the reference's data parallelism) and under ``bf16=True`` wraps ``forward`` to
+        copy every bf16 output to fp32.  Neither fits a flat-gradient model (see ``ddp.HipDataParallel``): its
+        gradients never pass autograd hooks, and its [.,V] logits are consumed as bf16 by the loss kernel.  Such a
+        model is handed to the loop inside ``HipDataParallel`` instead -- the one owner of gradient averaging, with the
+        ``no_sync()`` accelerate looks for on accumulation micro-batches; HF then prepares only the optimizer."""
+        if isinstance(model, ddp.HipDataParallel):
+            return model
+        if ddp.speaks_flat_grad(model):
+            if self._hip_dp is None or self._hip_dp.module is not model:
+                self._hip_dp = ddp.HipDataParallel(model)
+            return self._hip_dp
+        return super()._wrap_model(model, training=training, dataloader=dataloader)
+
+    def log(self, logs, *args, **kwargs):
+        """train.py:107-114 logs the three sub-losses only; SURVEY section 8 f-1 asks the counterpart for tokens/sec.  HF's
+        own training log (the dict with ``loss`` / ``learning_rate``, every ``logging_steps`` optimizer steps, after a
+        ``.item()`` that has drained the GPU) gets ``tokens_per_second``: positions of all ranks' micro-batches since the
+        previous such log over the wall time between the two."""
+        if "loss" in logs and "learning_rate" in logs and self._tps_mark is not None:
+            now = time.perf_counter()
+            t0, n0 = self._tps_mark
+            if now > t0 and self.tokens_seen > n0:
+                logs = dict(logs)
+                logs["tokens_per_second"] = round((self.tokens_seen - n0) * max(1, self.args.world_size) / (now - t0), 1)
+            self._tps_mark = (now, self.tokens_seen)
+        return super().log(logs, *args, **kwargs)
+
+    def _clip_grad_norm(self, model):
+        """HF trainer.py:2535-2539 calls ``clip_grad_norm_`` over ~310 parameter tensors (10 ms of host time per
+        optimizer step with the GPU idle).  With the flat buffers the norm is one reduction, and FlatAdamW folds the
+        clip coefficient into its update; the returned pre-clip norm is the same number HF logs as ``grad_norm``."""
+        core = ddp.unwrap(model)
+        opt = getattr(self.optimizer, "optimizer", self.optimizer)
+        if isinstance(core, HipQwen3ForCausalLM) and core.flat_grad is not None and core.flat_grad.is_cuda:
+            from .optim import FlatAdamW
+            if isinstance(opt, FlatAdamW) and opt.model is core:
+                return opt.grad_norm(self.args.max_grad_norm)
+            core.finalize_grads()
+            ss = torch.zeros(1, dtype=torch.float32, device=core.flat_grad.device)
+            ops.sumsq(core.flat_grad, ss)
+            norm = ss.sqrt().squeeze(0)
+            core.flat_grad.mul_((self.args.max_grad_norm / (norm + 1e-6)).clamp(max=1.0).to(core.flat_grad.dtype))
+            return norm
+        return super()._clip_grad_norm(model)
+
+    def _save(self, output_dir=None, state_dict=None):
+        """HF trainer.py `_save`: a model that is not a PreTrainedModel gets a bare ``model.safetensors``.  The
+        reference's checkpoints (save_strategy="epoch", train.py:341-345) are ``save_pretrained`` directories
+        (``config.json`` + weights, tied head left out) -- write the same for a model that offers it."""
+        core = ddp.unwrap(self.model)
+        if not hasattr(core, "save_pretrained") or isinstance(core, _pretrained_types()):
+            return super()._save(output_dir, state_dict)
+        output_dir = output_dir if output_dir is not None else self.args.output_dir
+        os.makedirs(output_dir, exist_ok=True)
+        core.save_pretrained(output_dir, state_dict=state_dict)
+        if self.processing_class is not None and hasattr(self.processing_class, "save_pretrained"):
+            self.processing_class.save_pretrained(output_dir)
+        torch.save(self.args, os.path.join(output_dir, "training_args.bin"))
+
+    def _flat_adamw(self, core):
+        """FlatAdamW over ``core.optim_segments()`` with the TrainingArguments' AdamW hyper-parameters."""
+        from .optim import FlatAdamW
+        return FlatAdamW(core, lr=self.args.learning_rate, betas=(self.args.adam_beta1, self.args.adam_beta2),
+                         eps=self.args.adam_epsilon, weight_decay=self.args.weight_decay)
+
+
+class DistillationTrainer(FlatStudentTrainer):
     def __init__(self, *args, teacher_model=None, temperature=2.0, alpha=0.5, top_k=100, is_quantized_teacher=False,
                  **kwargs):
         super().__init__(*args, **kwargs)
@@ -56,36 +130,6 @@ class DistillationTrainer(Trainer):
         # by the one-launch FlatAdamW over the flat buffers when the student offers them; set False to keep HF's.
         self.fused_optimizer = True
 
-    # ------------------------------------------------------------------------------ HF Trainer plumbing
-    def _wrap_model(self, model, training=True, dataloader=None):
-        """HF trainer.py:1602-1626: a model this hook leaves unwrapped goes through ``accelerator.prepare``, which under
-        torchrun wraps it in torch DDP (the reference's data parallelism) and under ``bf16=True`` wraps ``forward`` to
-        copy every bf16 output to fp32.  Neither fits a flat-gradient model (see ``ddp.HipDataParallel``): its
-        gradients never pass autograd hooks, and its [.,V] logits are consumed as bf16 by the loss kernel.  Such a
-        model is handed to the loop inside ``HipDataParallel`` instead -- the one owner of gradient averaging, with the
-        ``no_sync()`` accelerate looks for on accumulation micro-batches; HF then prepares only the optimizer."""
-        if isinstance(model, ddp.HipDataParallel):
-            return model
-        if ddp.speaks_flat_grad(model):
-            if self._hip_dp is None or self._hip_dp.module is not model:
-                self._hip_dp = ddp.HipDataParallel(model)
-            return self._hip_dp
-        return super()._wrap_model(model, training=training, dataloader=dataloader)
-
-    def log(self, logs, *args, **kwargs):
-        """train.py:107-114 logs the three sub-losses only; SURVEY section 8 f-1 asks the counterpart for tokens/sec.  HF's
-        own training log (the dict with ``loss`` / ``learning_rate``, every ``logging_steps`` optimizer steps, after a
-        ``.item()`` that has drained the GPU) gets ``tokens_per_second``: positions of all ranks' micro-batches since the
-        previous such log over the wall time between the two."""
-        if "loss" in logs and "learning_rate" in logs and self._tps_mark is not None:
-            now = time.perf_counter()
-            t0, n0 = self._tps_mark
-            if now > t0 and self.tokens_seen > n0:
-                logs = dict(logs)
-                logs["tokens_per_second"] = round((self.tokens_seen - n0) * max(1, self.args.world_size) / (now - t0), 1)
-            self._tps_mark = (now, self.tokens_seen)
-        return super().log(logs, *args, **kwargs)
-
     def create_optimizer(self, model=None):
         """HF trainer.py `create_optimizer(self, model=None)`: TrainingArguments' default is torch AdamW (the reference passes no
         ``optim``, train.py:331-354).  For a flat-buffer student on the GPU the same update -- same hyper-parameters,
@@ -96,9 +140,7 @@ class DistillationTrainer(Trainer):
         default_adamw = str(getattr(self.args.optim, "value", self.args.optim)).startswith("adamw_torch")
         if (self.optimizer is None and self.fused_optimizer and default_adamw and isinstance(core, HipQwen3ForCausalLM)
                 and core.flat.is_cuda and (core._lora is not None or all(p.requires_grad for p in core.parameters()))):
-            from .optim import FlatAdamW
-            self.optimizer = FlatAdamW(core, lr=self.args.learning_rate, betas=(self.args.adam_beta1, self.args.adam_beta2),
-                                       eps=self.args.adam_epsilon, weight_decay=self.args.weight_decay)
+            self.optimizer = self._flat_adamw(core)
             return self.optimizer
         if isinstance(core, HipQwen3ForCausalLM) and core._lora is not None and self.optimizer is None:
             raise NotImplementedError("a LoRA student (lora.py) trains through FlatAdamW only: its adapter gradients are "
@@ -106,38 +148,6 @@ class DistillationTrainer(Trainer):
                                       "TrainingArguments.optim at its adamw_torch default, as the reference does")
         # (HF calls create_optimizer(model) on its delay_optimizer_creation path: FSDP / SageMaker model parallel)
         return super().create_optimizer(model) if model is not None else super().create_optimizer()
-
-    def _clip_grad_norm(self, model):
-        """HF trainer.py:2535-2539 calls ``clip_grad_norm_`` over ~310 parameter tensors (10 ms of host time per
-        optimizer step with the GPU idle).  With the flat buffers the norm is one reduction, and FlatAdamW folds the
-        clip coefficient into its update; the returned pre-clip norm is the same number HF logs as ``grad_norm``."""
-        core = ddp.unwrap(model)
-        opt = getattr(self.optimizer, "optimizer", self.optimizer)
-        if isinstance(core, HipQwen3ForCausalLM) and core.flat_grad is not None and core.flat_grad.is_cuda:
-            from .optim import FlatAdamW
-            if isinstance(opt, FlatAdamW) and opt.model is core:
-                return opt.grad_norm(self.args.max_grad_norm)
-            core.finalize_grads()
-            ss = torch.zeros(1, dtype=torch.float32, device=core.flat_grad.device)
-            ops.sumsq(core.flat_grad, ss)
-            norm = ss.sqrt().squeeze(0)
-            core.flat_grad.mul_((self.args.max_grad_norm / (norm + 1e-6)).clamp(max=1.0).to(core.flat_grad.dtype))
-            return norm
-        return super()._clip_grad_norm(model)
-
-    def _save(self, output_dir=None, state_dict=None):
-        """HF trainer.py `_save`: a model that is not a PreTrainedModel gets a bare ``model.safetensors``.  The
-        reference's checkpoints (save_strategy="epoch", train.py:341-345) are ``save_pretrained`` directories
-        (``config.json`` + weights, tied head left out) -- write the same for a model that offers it."""
-        core = ddp.unwrap(self.model)
-        if not hasattr(core, "save_pretrained") or isinstance(core, _pretrained_types()):
-            return super()._save(output_dir, state_dict)
-        output_dir = output_dir if output_dir is not None else self.args.output_dir
-        os.makedirs(output_dir, exist_ok=True)
-        core.save_pretrained(output_dir, state_dict=state_dict)
-        if self.processing_class is not None and hasattr(self.processing_class, "save_pretrained"):
-            self.processing_class.save_pretrained(output_dir)
-        torch.save(self.args, os.path.join(output_dir, "training_args.bin"))
 
     @staticmethod
     def _rows_key(lab, speech_mask, am, tam):
@@ -408,6 +418,45 @@ class DistillationTrainer(Trainer):
                                 distill_loss.detach().float()]).tolist()
             self.log({"student_loss": vals[0], "teacher_loss": vals[1], "distill_loss": vals[2]})
         return (loss, outputs) if return_outputs else loss
+
+
+class Stage1Trainer(FlatStudentTrainer):
+    """Stage-1 speech-token alignment (reference stage1.py:285-335: TRL SFTTrainer, ``adamw_torch``, ``max_grad_norm`` 1.0)
+    on a model frozen by ``stage1.freeze_model_weights``: plain causal-LM cross-entropy, FlatAdamW over the Stage-1
+    segments (the embedding, + an untied lm_head: HF's decay groups put weight decay on both), the one-reduction clip,
+    tokens/sec in the training log.  Single GPU.  Batches: ``stage1.Stage1Collator`` (input_ids, attention_mask, labels)."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.tokens_seen = 0
+        self._tps_mark = None
+        self._hip_dp = None
+        self.fused_optimizer = True
+        if self.args.world_size > 1:
+            raise NotImplementedError("Stage-1 alignment runs on one GPU (multi-GPU Stage-1 is not implemented)")
+        # compute_loss passes num_items_in_batch to the model itself; HF must then neither drop the count nor divide the
+        # loss by the accumulation steps, whatever its signature probe of the model concluded
+        self.model_accepts_loss_kwargs = True
+
+    def create_optimizer(self, model=None):
+        core = ddp.unwrap(self.model)
+        default_adamw = str(getattr(self.args.optim, "value", self.args.optim)).startswith("adamw_torch")
+        if (self.optimizer is None and self.fused_optimizer and default_adamw and isinstance(core, HipQwen3ForCausalLM)
+                and core.flat.is_cuda and core.stage1_row_lo is not None):
+            core.check_stage1()
+            self.optimizer = self._flat_adamw(core)
+            return self.optimizer
+        return super().create_optimizer(model) if model is not None else super().create_optimizer()
+
+    def compute_loss(self, model, inputs, return_outputs=False, num_items_in_batch=None, **kwargs):
+        ids = inputs["input_ids"]
+        if model.training:
+            self.tokens_seen += ids.numel()
+            if self._tps_mark is None:  # first training micro-batch: the clock of the first tokens/sec figure starts here
+                self._tps_mark = (time.perf_counter(), self.tokens_seen - ids.numel())
+        out = model(input_ids=ids, attention_mask=inputs.get("attention_mask"), labels=inputs["labels"],
+                    num_items_in_batch=num_items_in_batch, stage1_inplace_grad=not return_outputs)
+        return (out["loss"], out) if return_outputs else out["loss"]
 
 
 def _pretrained_types():
