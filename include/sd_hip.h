@@ -185,6 +185,32 @@ int sd_attn_bwd2(const void* q, const void* k, const void* v, const void* o, con
                  int64_t ldo, int64_t lddq, int64_t lddk, int64_t lddv, int B, int T, int Hq, int Hkv, int head_dim,
                  float scale, void* side_stream, void* stream);
 
+/* ---- packed sequences without padding (HF padding-free packing: position_ids restart per document, flash-attn varlen).
+ * The M tokens of a call hold n_seqs documents end to end: document s is the flat tokens [cu_seqlens[s], cu_seqlens[s+1]),
+ * and a token attends to the tokens of its own document from the document start up to itself, to nothing else.
+ * cu_seqlens: int32 [n_seqs + 1] in device memory, non-decreasing, cu_seqlens[0] = 0, cu_seqlens[n_seqs] = M.  Empty
+ * documents are allowed.  Starts and ends are clamped into [0, M]: a malformed array gives wrong numbers, never an access
+ * outside rows [0, M).  max_seqlen: the largest document length (a host-side hint, only used for the profiler's work
+ * estimate).  work: device scratch of sd_varlen_work_bytes(M) bytes (nullable while that is 0, as it is now: the
+ * kernels locate their document by a search in cu_seqlens). */
+typedef struct {
+  const int32_t* cu_seqlens;
+  int n_seqs;
+  int max_seqlen;
+  void* work;
+} sd_varlen;
+int64_t sd_varlen_work_bytes(int M);
+/* sd_attn_fwd / sd_attn_bwd2 over packed documents: the descriptor and M in place of kv_len, B, T; q, k, v, o, dq, dk, dv
+ * [M, ld]; lse and delta fp32 [Hq, M] (one row per head, token-major).  Per document the results are bit-identical to the
+ * padded entries run on that document alone with B = 1, T = its length, and the classic (not software-pipelined) forward. */
+int sd_attn_fwd_varlen(const void* q, const void* k, const void* v, void* o, float* lse, const sd_varlen* vl,
+                       int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int M, int Hq, int Hkv, int head_dim,
+                       float scale, void* stream);
+int sd_attn_bwd_varlen(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
+                       float* delta, void* dq, void* dk, void* dv, const sd_varlen* vl, int64_t ldq, int64_t ldk,
+                       int64_t ldv, int64_t ldo, int64_t lddq, int64_t lddk, int64_t lddv, int M, int Hq, int Hkv,
+                       int head_dim, float scale, void* side_stream, void* stream);
+
 /* ---- teacher log-softmax + top-K (train.py:80-91; extract_teacher_logits.py:114-129).
  * logits [rows, row_stride], first V columns used -> top_v fp16 [rows,K], top_i int32 [rows,K] sorted
  * descending, ties to the lowest index; lse_out fp32 [rows] nullable. */
@@ -379,6 +405,25 @@ int sd_qwen3_backward_embed_rows(const sd_qwen3_dims* d, const sd_qwen3_params* 
                                  void* acts, int64_t acts_bytes, void* dlogits, const int64_t* head_rows, int n_head_rows,
                                  void* scratch, int64_t scratch_bytes, int B, int T, int accumulate, int grad_row_lo,
                                  void* side_stream, void* stream);
+/* The three runner entries over packed documents (sd_varlen above): the _rows entries with the descriptor and M in place
+ * of kv_len, B, T.  ids int64 [M]; head_rows are flat token indices; acts / scratch are sized for B = 1, T = M
+ * (sd_qwen3_acts_bytes(d, 1, M, mode), sd_qwen3_bwd_scratch_bytes(d, 1, M)).  RoPE: cos/sin are PER-TOKEN tables bf16
+ * [M,128] (row m holds the rotary angles of token m's position in its document), read unchanged by the rope consumers
+ * with T = M.  Every forward mode, the recompute bit and the three backwards work as in the padded entries; only the
+ * attention calls differ. */
+int sd_qwen3_forward_varlen(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const sd_varlen* vl,
+                            const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes, void* logits,
+                            const int64_t* head_rows, int n_head_rows, int M, int save_for_backward, void* stream);
+int sd_qwen3_backward_varlen(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g, const int64_t* ids,
+                             const sd_varlen* vl, const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes,
+                             void* dlogits, const int64_t* head_rows, int n_head_rows, void* scratch,
+                             int64_t scratch_bytes, int M, int accumulate, void* dx0_out, sd_stage_cb on_grads_ready,
+                             void* cb_user, void* side_stream, void* stream);
+int sd_qwen3_backward_embed_varlen(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g,
+                                   const int64_t* ids, const sd_varlen* vl, const void* cos_tab, const void* sin_tab,
+                                   void* acts, int64_t acts_bytes, void* dlogits, const int64_t* head_rows,
+                                   int n_head_rows, void* scratch, int64_t scratch_bytes, int M, int accumulate,
+                                   int grad_row_lo, void* side_stream, void* stream);
 
 /* ---- stream placement.  HIP multiplexes streams onto a few hardware queues (4 by default); streams that share a
  * queue never overlap.  Measures, with a `spin_us`-long busy-wait kernel on stream_a and an empty one on stream_b,

@@ -6,7 +6,8 @@ the embedding (and of an untied lm_head) train; every other weight leaves bit-id
 Data: a ``load_from_disk`` directory whose rows carry ``input_ids`` (what the reference's SpeechDistillDatasetProcessor
 produces before it decodes them to text), or a ``text`` column tokenised with the tokenizer in ``--model_path``.  The
 audio-to-token step (s3tokenizer) stays outside, as for scripts/train.py.  Packing: best-fit-decreasing bins of
-``--max_seq_length`` (speech_distill_amd/stage1.py), each document its own right-padded row.
+``--max_seq_length`` (speech_distill_amd/stage1.py), each document its own right-padded row, or with ``--padding_free``
+all documents of a micro-batch in one row without padding (varlen attention).
 
     python scripts/stage1.py --model_path /models/qwen3-0.6b-expanded --dataset_path /data/tokenised \\
         --output_dir /out/stage1 --num_new_tokens 8220
@@ -58,6 +59,9 @@ def parse_args(argv=None):
     p.add_argument("--log_json", default=None, help="(+) write the log history and a summary there")
     p.add_argument("--recompute", default="auto", choices=["auto", "always", "never"],
                    help="(+) what gradient checkpointing does (see scripts/train.py)")
+    p.add_argument("--padding_free", action="store_true", default=False,
+                   help="(+) flatten each micro-batch's documents into one row without padding (position_ids + varlen "
+                        "attention, TRL padding_free) instead of one right-padded row per document")
     return p.parse_args(argv)
 
 
@@ -144,7 +148,7 @@ def main(argv=None):
         dataloader_num_workers=0, report_to=["wandb"] if cfg.use_wandb else [], remove_unused_columns=False,
         label_names=["labels"], max_steps=cfg.max_steps, prediction_loss_only=True)   # stage1.py:291-322
     trainer = Stage1Trainer(model=model, args=args, train_dataset=train, eval_dataset=evals,
-                            data_collator=Stage1Collator(pad_token_id=pad))
+                            data_collator=Stage1Collator(pad_token_id=pad, padding_free=cfg.padding_free))
     def body_checksum():  # every decoder weight + the final norm (untouched by Stage-1)
         return float(torch.cat([model.flat[a:b] for a, b in model.layer_ranges + [model.norm_range]]).double().sum())
     body0, lo = body_checksum(), model.stage1_row_lo

@@ -55,6 +55,10 @@ class LoraTarget(C.Structure):   # include/sd_hip.h SdLoraTarget
                [("out_features", C.c_int32), ("in_features", C.c_int32)]
 
 
+class Varlen(C.Structure):  # include/sd_hip.h sd_varlen (packed documents without padding)
+    _fields_ = [("cu_seqlens", C.c_void_p), ("n_seqs", C.c_int32), ("max_seqlen", C.c_int32), ("work", C.c_void_p)]
+
+
 class Params(C.Structure):
     _fields_ = [("embed", C.c_void_p), ("lm_head", C.c_void_p), ("final_norm", C.c_void_p),
                 ("layers_host", C.POINTER(Layer))]
@@ -107,6 +111,9 @@ PROTOTYPES = {
     "sd_attn_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i, _f, _vp]),
     "sd_attn_bwd": (_i, [_vp] * 11 + [_i64] * 7 + [_i, _i, _i, _i, _i, _f, _vp]),
     "sd_attn_bwd2": (_i, [_vp] * 11 + [_i64] * 7 + [_i, _i, _i, _i, _i, _f, _vp, _vp]),
+    "sd_varlen_work_bytes": (_i64, [_i]),
+    "sd_attn_fwd_varlen": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(Varlen), _i64, _i64, _i64, _i64, _i, _i, _i, _i, _f, _vp]),
+    "sd_attn_bwd_varlen": (_i, [_vp] * 10 + [C.POINTER(Varlen)] + [_i64] * 7 + [_i, _i, _i, _i, _f, _vp, _vp]),
     "sd_logsoftmax_topk": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp]),
     "sd_kdloss_stats_bytes": (_i64, [_i, _i]),
     "sd_celoss_stats_bytes": (_i64, [_i]),
@@ -144,6 +151,12 @@ PROTOTYPES = {
                                     _vp, _vp, _i, _vp, _i64, _i, _i, _i, _vp, STAGE_CB, _vp, _vp, _vp]),
     "sd_qwen3_backward_embed_rows": (_i, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(Params), _vp, _vp, _vp, _vp, _vp,
                                           _i64, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _i, _vp, _vp]),
+    "sd_qwen3_forward_varlen": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, C.POINTER(Varlen), _vp, _vp, _vp, _i64, _vp,
+                                     _vp, _i, _i, _i, _vp]),
+    "sd_qwen3_backward_varlen": (_i, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(Params), _vp, C.POINTER(Varlen), _vp,
+                                      _vp, _vp, _i64, _vp, _vp, _i, _vp, _i64, _i, _i, _vp, STAGE_CB, _vp, _vp, _vp]),
+    "sd_qwen3_backward_embed_varlen": (_i, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(Params), _vp, C.POINTER(Varlen),
+                                            _vp, _vp, _vp, _i64, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _vp, _vp]),
     "sd_qwen3_backward": (_i, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(Params), _vp, _vp, _vp, _vp, _vp, _i64,
                                _vp, _vp, _i64, _i, _i, _i, _vp, STAGE_CB, _vp, _vp, _vp]),
 }

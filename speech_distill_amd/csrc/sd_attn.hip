@@ -188,6 +188,49 @@ SD_DEV AttnWg attn_wg(int id, int npairs, int heads_per_group, int Hkv, int B) {
   return o;
 }
 
+// Packed (varlen) calls: the M tokens of the call hold n documents end to end, document s = flat tokens [cu[s], cu[s+1]),
+// and every kernel below runs per document exactly as it runs per batch row (tok0 = document start, T = klen = its
+// length) when instantiated with VARLEN.  LSE and delta are then [Hq, M].  The tile pairs of document s are numbered
+// from base(s) = cu[s] / 128 + s: a document of L tokens has ceil(L / 128) pairs and base(s+1) - base(s) >= that, so
+// the numbering never overlaps and stays below the host-known bound ceil(M / 128) + n.  A workgroup finds its document
+// by a 64-way search of that (non-decreasing) numbering, one wave-wide load per round, with no scratch and no host
+// synchronisation; a slot past a document's last pair exits at once.  Starts and ends are clamped into [0, M] (end >=
+// start), so a malformed cu_seqlens can give wrong numbers but never an access outside rows [0, M).
+struct VarlenArgs {
+  const int* cu;
+  int n, M;
+};
+struct VarlenDoc { int tok0, len, pair; };  // len == 0: nothing to do for this workgroup
+
+SD_DEV int varlen_start(const VarlenArgs& vl, int s) { return min(max(vl.cu[s], 0), vl.M); }
+
+SD_DEV VarlenDoc varlen_doc(const VarlenArgs& vl, int slot, int lane) {
+  VarlenDoc d = {0, 0, 0};
+  int lo = 0, cnt = vl.n;  // the answer (last s with base(s) <= slot) lies in [lo, lo + cnt)
+  bool found = false;
+  while (cnt > 0) {
+    const int step = (cnt + 63) >> 6;
+    const int s = lo + lane * step;
+    const bool ok = lane * step < cnt && varlen_start(vl, s) / 128 + s <= slot;
+    const unsigned long long bal = __ballot(ok);
+    if (!bal) break;  // round 0 only: slot lies before document 0's first pair
+    const int k = 63 - __clzll(bal);
+    lo += k * step;
+    found = true;
+    if (step == 1) break;
+    cnt = min(step, cnt - k * step);
+  }
+  if (!found) return d;
+  const int start = varlen_start(vl, lo);
+  const int end = max(varlen_start(vl, lo + 1), start);
+  const int pair = slot - (start / 128 + lo);
+  if (pair >= (end - start + 127) / 128) return d;
+  d.tok0 = start;
+  d.len = end - start;
+  d.pair = pair;
+  return d;
+}
+
 #ifdef SD_STAMPS
 // DIAGNOSTIC BUILD ONLY (make stamps): s_memtime at the phase boundaries of workgroup (0,0,0) of attn_fwd_kernel,
 // [wave 0..7][point 0..255] (tests/bench_attn_stamps.py)
@@ -220,15 +263,30 @@ SD_DEV AttnWg attn_wg(int id, int npairs, int heads_per_group, int Hkv, int B) {
 // one tile ahead is less than the L2 latency with all 256 CUs pulling at once, and an iteration cost 3.2 us at T = 512
 // against 0.85 us of MFMA time.)  With two waves per SIMD the DMA issue, LDS reads, MFMAs and softmax VALU of one wave
 // overlap the other's.  The two partial (m, l, O) states of a row block are merged through LDS at the end (fixed order).
+// VARLEN: grid (ceil(M/128) + n) * Hq, one document per workgroup (VarlenArgs above); T is then the call's M on entry.
+// The VarlenArgs travel as a trailing parameter pack, empty for the padded instantiation: its kernel arguments, and with
+// them its code, stay exactly what they were before the varlen instantiation existed.
+template <bool VARLEN, class... VA>
 __global__ __launch_bounds__(512) void attn_fwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ Kp,
                                                        const bf16* __restrict__ Vp, bf16* __restrict__ O,
                                                        float* __restrict__ LSE, const int* __restrict__ kv_len, long ldq,
                                                        long ldk, long ldv, long ldo, int T, int Hq, int Hkv,
-                                                       float scale SD_ATT_STAMP_PARAM) {
+                                                       float scale SD_ATT_STAMP_PARAM, VA... vla) {
   __shared__ __attribute__((aligned(16))) char smem[8 * TILE];  // ring of 4 stages x (K,V)
   const int lane = lane_id(), w8 = wave_id_uniform();
+  const VarlenArgs vl{vla...};
+  AttnWg vwg = {};
+  long vtok0 = 0;
+  if constexpr (VARLEN) {
+    vwg = attn_wg((int)blockIdx.x, (int)gridDim.x / Hq, Hq / Hkv, Hkv, 1);
+    const VarlenDoc dc = varlen_doc(vl, vwg.pair, lane);
+    if (dc.len == 0) return;
+    T = dc.len;
+    vwg.pair = dc.pair;
+    vtok0 = dc.tok0;
+  }
   const int n64 = (T + 63) / 64;
-  const AttnWg wg = attn_wg((int)blockIdx.x, (n64 + 1) / 2, Hq / Hkv, Hkv, (int)gridDim.x / (((n64 + 1) / 2) * Hq));
+  const AttnWg wg = VARLEN ? vwg : attn_wg((int)blockIdx.x, (n64 + 1) / 2, Hq / Hkv, Hkv, (int)gridDim.x / (((n64 + 1) / 2) * Hq));
 #ifdef SD_STAMPS
   const bool stamping = stamps && wg.pair == 0 && wg.member_head == 0 && wg.hkv == 0 && wg.b == 0;
   int sidx = 0;
@@ -245,7 +303,7 @@ __global__ __launch_bounds__(512) void attn_fwd_kernel(const bf16* __restrict__ 
   const int hq = hkv * (Hq / Hkv) + wg.member_head;
   const int q0w = (grp == 0 ? tA : tB) * 64 + 32 * rb;
   const int r = lane & 31, h = lane >> 5;
-  const long tok0 = (long)b * T;
+  const long tok0 = VARLEN ? vtok0 : (long)b * T;
   const bf16* qb = Q + tok0 * ldq + hq * D;
   const bf16* kb = Kp + tok0 * ldk + hkv * D;
   const bf16* vb = Vp + tok0 * ldv + hkv * D;
@@ -421,7 +479,7 @@ __global__ __launch_bounds__(512) void attn_fwd_kernel(const bf16* __restrict__ 
   ATT_STAMP();  // 2+4nkv+1: merged
   if (!active) return;
   store_tile_rows((char*)xo, o, inv, O + (tok0 + q0w) * ldo + hq * D, ldo, T - q0w, lane);
-  if (q < T && h == 0) LSE[((long)b * Hq + hq) * T + q] = m * scale + __logf(l);
+  if (q < T && h == 0) LSE[VARLEN ? (long)hq * vl.M + tok0 + q : ((long)b * Hq + hq) * T + q] = m * scale + __logf(l);
   ATT_STAMP();  // stores issued
 }
 
@@ -695,18 +753,30 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const bf16* __restrict_
 // a group rb = w&1 is the 32-row block and half = (w>>1)&1 splits the K/V tiles (t = 2i + half) through its own double
 // buffer; the two partial dQ^T of a row block are added through LDS at the end in a fixed order.
 // dQ^T[d][q] = scale * sum_key K^T[d][key] dS^T[key][q].
+template <bool VARLEN, class... VA>  // as attn_fwd_kernel
 __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ Kp,
                                                           const bf16* __restrict__ Vp, const bf16* __restrict__ dO,
                                                           const float* __restrict__ LSE, const float* __restrict__ delta,
                                                           bf16* __restrict__ dQ, const int* __restrict__ kv_len, long ldq,
                                                           long ldk, long ldv, long ldo, long lddq, int T, int Hq, int Hkv,
-                                                          float scale) {
+                                                          float scale, VA... vla) {
   __shared__ __attribute__((aligned(16))) char smem[8 * TILE];  // 2 halves x 2 stages x (K,V)
   const int lane = lane_id(), w8 = wave_id_uniform();
+  const VarlenArgs vl{vla...};
+  AttnWg vwg = {};
+  long vtok0 = 0;
+  if constexpr (VARLEN) {
+    vwg = attn_wg((int)blockIdx.x, (int)gridDim.x / Hq, Hq / Hkv, Hkv, 1);
+    const VarlenDoc dc = varlen_doc(vl, vwg.pair, lane);
+    if (dc.len == 0) return;
+    T = dc.len;
+    vwg.pair = dc.pair;
+    vtok0 = dc.tok0;
+  }
   const int grp = w8 >> 2, rb = w8 & 1, half = (w8 >> 1) & 1;
   const int w = grp * 2 + rb;  // 0..3 inside my half: staging share and merge slot
   const int n64 = (T + 63) / 64;
-  const AttnWg wg = attn_wg((int)blockIdx.x, (n64 + 1) / 2, Hq / Hkv, Hkv, (int)gridDim.x / (((n64 + 1) / 2) * Hq));
+  const AttnWg wg = VARLEN ? vwg : attn_wg((int)blockIdx.x, (n64 + 1) / 2, Hq / Hkv, Hkv, (int)gridDim.x / (((n64 + 1) / 2) * Hq));
   const int tA = n64 - 1 - wg.pair, tB = wg.pair;
   const bool active = grp == 0 || tB != tA;
   const int hkv = wg.hkv, b = wg.b;
@@ -714,7 +784,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(const bf16* __restrict
   const int q0w = (grp == 0 ? tA : tB) * 64 + 32 * rb;
   const int r = lane & 31, h = lane >> 5;
   const int klen = kv_len ? max(1, min(kv_len[b], T)) : T;
-  const long tok0 = (long)b * T;
+  const long tok0 = VARLEN ? vtok0 : (long)b * T;
   const bf16* qb = Q + tok0 * ldq + hq * D;
   const bf16* kb = Kp + tok0 * ldk + hkv * D;
   const bf16* vb = Vp + tok0 * ldv + hkv * D;
@@ -728,8 +798,9 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(const bf16* __restrict
     dof[st] = *(const bf16x8*)(dob + (long)qc * ldo + 16 * st + 8 * h);
   }
   const int lim = min(q, klen - 1);
-  const float lse2 = LSE[((long)b * Hq + hq) * T + qc] * LOG2E;
-  const float dl = delta[((long)b * Hq + hq) * T + qc];
+  const long sidx = VARLEN ? (long)hq * vl.M + tok0 + qc : ((long)b * Hq + hq) * T + qc;
+  const float lse2 = LSE[sidx] * LOG2E;
+  const float dl = delta[sidx];
   const float c = scale * LOG2E;
   f32x16 acc[4];
 #pragma unroll
@@ -819,29 +890,41 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(const bf16* __restrict
 // tile strictly one after the other; two independent waves per SIMD overlap those phases.  To fit two waves into the
 // SIMD's 512 registers the two blocks' K and V (128 keys) live in LDS instead of registers (64 KiB), beside a 2-stage
 // (Q, dO) ring (64 KiB): waves 0-3 stage K and the Q tiles, waves 4-7 stage V and the dO tiles.
+template <bool VARLEN, class... VA>  // as attn_fwd_kernel, grid (ceil(M/128) + n) * Hkv
 __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ Kp,
                                                            const bf16* __restrict__ Vp, const bf16* __restrict__ dO,
                                                            const float* __restrict__ LSE, const float* __restrict__ delta,
                                                            bf16* __restrict__ dK, bf16* __restrict__ dV,
                                                            const int* __restrict__ kv_len, long ldq, long ldk, long ldv,
                                                            long ldo, long lddk, long lddv, int T, int Hq, int Hkv,
-                                                           float scale) {
+                                                           float scale, VA... vla) {
   // [K: heavy block 64 rows | light block 64 rows][V: same][stage 0: Q, dO | stage 1: Q, dO | stat[2 stages][lse2|delta][64 q rows]]
   // (ONE __shared__ object: a second one beside an LDS-DMA target makes hipcc drain vmcnt before LDS reads)
   __shared__ __attribute__((aligned(16))) char smem[8 * TILE + 1024];
   const int lane = lane_id(), w8 = wave_id_uniform();
+  const VarlenArgs vl{vla...};
+  AttnWg vwg = {};
+  long vtok0 = 0;
+  if constexpr (VARLEN) {
+    vwg = attn_wg((int)blockIdx.x, (int)gridDim.x / Hkv, 1, Hkv, 1);
+    const VarlenDoc dc = varlen_doc(vl, vwg.pair, lane);
+    if (dc.len == 0) return;
+    T = dc.len;
+    vwg.pair = dc.pair;
+    vtok0 = dc.tok0;
+  }
   const int grp = w8 >> 2, sub = w8 & 1, rh = (w8 >> 1) & 1;  // compute role
   const int sw = w8 & 3;                                       // staging share inside my group of four
   const int G = Hq / Hkv;
   const int n64 = (T + 63) / 64;
-  const AttnWg wg = attn_wg((int)blockIdx.x, (n64 + 1) / 2, 1, Hkv, (int)gridDim.x / (((n64 + 1) / 2) * Hkv));
+  const AttnWg wg = VARLEN ? vwg : attn_wg((int)blockIdx.x, (n64 + 1) / 2, 1, Hkv, (int)gridDim.x / (((n64 + 1) / 2) * Hkv));
   const int hkv = wg.hkv, b = wg.b;
   const int kbA = wg.pair, kbB = n64 - 1 - wg.pair;  // heavy / light key block
   const bool active = grp == 0 || kbB != kbA;                       // odd block count: the middle block has no partner
   const int k0w = (grp == 0 ? kbA : kbB) * 64 + 32 * sub;
   const int r = lane & 31, h = lane >> 5;
   const int klen = kv_len ? max(1, min(kv_len[b], T)) : T;
-  const long tok0 = (long)b * T;
+  const long tok0 = VARLEN ? vtok0 : (long)b * T;
   const int key = k0w + r;  // this lane's key (column of S)
   const bool key_ok = key < klen;  // padded / out-of-range keys receive no probability
   const float c = scale * LOG2E;
@@ -873,7 +956,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const bf16* __restric
     const int hq = hkv * G + itc / per_head;
     int qq = (qt0 + itc % per_head) * 64 + st_i;
     qq = qq < T ? qq : T - 1;
-    const long o = ((long)b * Hq + hq) * T + qq;
+    const long o = VARLEN ? (long)hq * vl.M + tok0 + qq : ((long)b * Hq + hq) * T + qq;
     return st_which ? delta[o] : LSE[o] * LOG2E;
   };
   // one tile = Q rows (waves 0-3) + dO rows (waves 4-7) of query head g, rows qt*64 .. +63
@@ -1003,7 +1086,7 @@ extern "C" int sd_attn_fwd(const void* q, const void* k, const void* v, void* o,
     SD_CHECK_LAUNCH();
     return 0;
   }
-  hipLaunchKernelGGL(attn_fwd_kernel, grid, dim3(512), 0, (hipStream_t)stream, (const bf16*)q,
+  hipLaunchKernelGGL(attn_fwd_kernel<false>, grid, dim3(512), 0, (hipStream_t)stream, (const bf16*)q,
                      (const bf16*)k, (const bf16*)v, (bf16*)o, lse, kv_len, ldq, ldk, ldv, ldo, T, Hq, Hkv, scale SD_ATT_STAMP_ARG);
   SD_CHECK_LAUNCH();
   return 0;
@@ -1033,14 +1116,14 @@ extern "C" int sd_attn_bwd2(const void* q, const void* k, const void* v, const v
   }
   {
     SdProfScope prof2(SD_K_ATTN_BWD_DQ, 3.0 * B * Hq * (double)T * T * D, sq);  // S, dP (recomputed), dQ
-    hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3((((T + 63) / 64 + 1) / 2) * Hq * B), dim3(512), 0, sq, (const bf16*)q, (const bf16*)k,
+    hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, dim3((((T + 63) / 64 + 1) / 2) * Hq * B), dim3(512), 0, sq, (const bf16*)q, (const bf16*)k,
                        (const bf16*)v, (const bf16*)d_o, lse, (const float*)delta, (bf16*)dq, kv_len, ldq, ldk, ldv, ldo,
                        lddq, T, Hq, Hkv, scale);
   }
   SD_CHECK_LAUNCH();
   {
     SdProfScope prof(SD_K_ATTN_BWD_DKV, 4.0 * B * Hq * (double)T * T * D, st);  // S, dP, dV, dK
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel, dim3((((T + 63) / 64 + 1) / 2) * Hkv * B), dim3(512), 0, st, (const bf16*)q,
+    hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, dim3((((T + 63) / 64 + 1) / 2) * Hkv * B), dim3(512), 0, st, (const bf16*)q,
                        (const bf16*)k, (const bf16*)v, (const bf16*)d_o, lse, (const float*)delta, (bf16*)dk, (bf16*)dv,
                        kv_len, ldq, ldk, ldv, ldo, lddk, lddv, T, Hq, Hkv, scale);
   }
@@ -1058,4 +1141,90 @@ extern "C" int sd_attn_bwd(const void* q, const void* k, const void* v, const vo
                            int Hkv, int head_dim, float scale, void* stream) {
   return sd_attn_bwd2(q, k, v, o, d_o, lse, delta, dq, dk, dv, kv_len, ldq, ldk, ldv, ldo, lddq, lddk, lddv, B, T, Hq,
                       Hkv, head_dim, scale, nullptr, stream);
+}
+
+// ------------------------------------------------------------------------------------ packed (varlen) entries
+extern "C" int64_t sd_varlen_work_bytes(int M) { return M < 0 ? SD_ERR_SHAPE : 0; }
+
+namespace {
+
+// validates a descriptor; grid pairs per head = ceil(M/128) + n (VarlenArgs)
+int varlen_check(const sd_varlen* vl, int M, int Hq, int Hkv, long ldq, long ldk, long ldv, long ldo, VarlenArgs* va,
+                 unsigned* pairs) {
+  if (!vl || !vl->cu_seqlens || vl->n_seqs <= 0) return SD_ERR_SHAPE;
+  if (int e = check_common(1, M, Hq, Hkv, ldq, ldk, ldv, ldo)) return e;
+  const long p = (M + 127L) / 128 + vl->n_seqs;
+  if (p * Hq > 0x7fffffffL) return SD_ERR_SHAPE;
+  va->cu = vl->cu_seqlens;
+  va->n = vl->n_seqs;
+  va->M = M;
+  *pairs = (unsigned)p;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int sd_attn_fwd_varlen(const void* q, const void* k, const void* v, void* o, float* lse, const sd_varlen* vl,
+                                  int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int M, int Hq, int Hkv,
+                                  int head_dim, float scale, void* stream) {
+  if (head_dim != D) return SD_ERR_UNSUPPORTED;
+  VarlenArgs va;
+  unsigned pairs;
+  if (int e = varlen_check(vl, M, Hq, Hkv, ldq, ldk, ldv, ldo, &va, &pairs)) return e;
+  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) & 15) return SD_ERR_ALIGN;
+  // work: sum over documents of L^2 <= M * max_seqlen (the bound; the host does not know the lengths)
+  const double ml = vl->max_seqlen > 0 ? (double)(vl->max_seqlen < M ? vl->max_seqlen : M) : (double)M;
+  SdProfScope prof(SD_K_ATTN_FWD, 2.0 * Hq * (double)M * ml * D, (hipStream_t)stream);
+  attn_fwd_kernel<true, VarlenArgs><<<dim3(pairs * Hq), dim3(512), 0, (hipStream_t)stream>>>(
+      (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, lse, nullptr, ldq, ldk, ldv, ldo, M, Hq, Hkv,
+      scale SD_ATT_STAMP_ARG, va);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sd_attn_bwd_varlen(const void* q, const void* k, const void* v, const void* o, const void* d_o,
+                                  const float* lse, float* delta, void* dq, void* dk, void* dv, const sd_varlen* vl,
+                                  int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddq, int64_t lddk,
+                                  int64_t lddv, int M, int Hq, int Hkv, int head_dim, float scale, void* side_stream,
+                                  void* stream) {
+  if (head_dim != D) return SD_ERR_UNSUPPORTED;
+  VarlenArgs va;
+  unsigned pairs;
+  if (int e = varlen_check(vl, M, Hq, Hkv, ldq, ldk, ldv, ldo, &va, &pairs)) return e;
+  if ((lddq | lddk | lddv) & 7) return SD_ERR_ALIGN;
+  hipStream_t st = (hipStream_t)stream, s2 = (hipStream_t)side_stream;
+  SdEventLease lease;
+  if (s2 && !(lease.set = sd_lease_events())) return SD_ERR_WORKSPACE;
+  hipEvent_t* g_attn_ev = lease.set ? lease.set->ev : nullptr;
+  const long total = (long)M * Hq;
+  if (o) {  // per token: one row of M tokens is exactly the [Hq, M] layout of the packed LSE / delta
+    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, st, (const bf16*)d_o,
+                       (const bf16*)o, delta, ldo, M, Hq, total);
+    SD_CHECK_LAUNCH();
+  }
+  hipStream_t sq = s2 ? s2 : st;
+  if (s2) {
+    if (hipEventRecord(g_attn_ev[0], st) != hipSuccess || hipStreamWaitEvent(s2, g_attn_ev[0], 0) != hipSuccess)
+      return SD_ERR_WORKSPACE;
+  }
+  const double ml = vl->max_seqlen > 0 ? (double)(vl->max_seqlen < M ? vl->max_seqlen : M) : (double)M;
+  {
+    SdProfScope prof2(SD_K_ATTN_BWD_DQ, 3.0 * Hq * (double)M * ml * D, sq);
+    attn_bwd_dq_kernel<true, VarlenArgs><<<dim3(pairs * Hq), dim3(512), 0, sq>>>(
+        (const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)d_o, lse, (const float*)delta, (bf16*)dq, nullptr,
+        ldq, ldk, ldv, ldo, lddq, M, Hq, Hkv, scale, va);
+  }
+  SD_CHECK_LAUNCH();
+  {
+    SdProfScope prof(SD_K_ATTN_BWD_DKV, 4.0 * Hq * (double)M * ml * D, st);
+    attn_bwd_dkv_kernel<true, VarlenArgs><<<dim3(pairs * Hkv), dim3(512), 0, st>>>(
+        (const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)d_o, lse, (const float*)delta, (bf16*)dk, (bf16*)dv,
+        nullptr, ldq, ldk, ldv, ldo, lddk, lddv, M, Hq, Hkv, scale, va);
+  }
+  SD_CHECK_LAUNCH();
+  if (s2) {
+    if (hipEventRecord(g_attn_ev[1], s2) != hipSuccess || hipStreamWaitEvent(st, g_attn_ev[1], 0) != hipSuccess)
+      return SD_ERR_WORKSPACE;
+  }
+  return 0;
 }

@@ -103,13 +103,23 @@ LayerActs layer_acts(const Sizes& s, char* base, int l, int save) {
   return a;
 }
 
+// The layer's attention: per batch row (kv_len: right padding), or per packed document when vl is given (B = 1, T = M)
+int layer_attn_fwd(const Sizes& s, const LayerActs& a, const int32_t* kv_len, const sd_varlen* vl, int B, int T,
+                   void* stream) {
+  const float scale = 0.08838834764831845f;  // 128^-1/2
+  if (vl)
+    return sd_attn_fwd_varlen(a.qk, a.qk + (int64_t)s.QD * 2, a.qkv + (int64_t)(s.QD + s.KD) * 2, a.ao, (float*)a.lse, vl,
+                              s.QK, s.QK, s.QKV, s.QD, s.M, s.Hq, s.Hkv, 128, scale, stream);
+  return sd_attn_fwd(a.qk, a.qk + (int64_t)s.QD * 2, a.qkv + (int64_t)(s.QD + s.KD) * 2, a.ao, (float*)a.lse, kv_len,
+                     s.QK, s.QK, s.QKV, s.QD, B, T, s.Hq, s.Hkv, 128, scale, stream);
+}
+
 // One decoder layer (HF modeling_qwen3.py:227-250): a.x_in -> x_out, every intermediate into `a`.  x_out == nullptr
 // stops after the SwiGLU (the backward's recompute does not need the layer output again); keep_gu: gate|up is kept
 // for the backward.
 int layer_forward(const sd_qwen3_dims* d, const Sizes& s, const LayerActs& a, const sd_qwen3_layer& w, char* x_out,
-                  bool keep_gu, const int32_t* kv_len, const void* cos_tab, const void* sin_tab, int B, int T,
-                  void* stream) {
-  const float scale = 0.08838834764831845f;  // 128^-1/2
+                  bool keep_gu, const int32_t* kv_len, const sd_varlen* vl, const void* cos_tab, const void* sin_tab,
+                  int B, int T, void* stream) {
   RUN(sd_rmsnorm_fwd(a.x_in, w.ln1, a.xn1, (float*)a.rstd1, s.M, s.h, d->eps, stream));
   // q|k|v projection with q/k-norm + RoPE in the GEMM epilogue (one head = one 128-column tile)
   int rc = sd_gemm_qkv_rope(a.xn1, w.wqkv, a.qkv, a.qk, w.q_gain, w.k_gain, cos_tab, sin_tab, s.M, T, s.Hq, s.Hkv, s.h,
@@ -120,8 +130,7 @@ int layer_forward(const sd_qwen3_dims* d, const Sizes& s, const LayerActs& a, co
   } else if (rc) {
     return rc;
   }
-  RUN(sd_attn_fwd(a.qk, a.qk + (int64_t)s.QD * 2, a.qkv + (int64_t)(s.QD + s.KD) * 2, a.ao, (float*)a.lse, kv_len,
-                  s.QK, s.QK, s.QKV, s.QD, B, T, s.Hq, s.Hkv, 128, scale, stream));
+  RUN(layer_attn_fwd(s, a, kv_len, vl, B, T, stream));
   RUN(sd_gemm_bf16(a.ao, w.wo, a.x_mid, a.x_in, s.M, s.h, s.QD, s.QD, s.QD, s.h, s.h, 0, 0, stream));
   RUN(sd_rmsnorm_fwd(a.x_mid, w.ln2, a.xn2, (float*)a.rstd2, s.M, s.h, d->eps, stream));
   // gate|up projection: SwiGLU runs in the GEMM epilogue when gate|up need not be kept (no backward follows:
@@ -146,13 +155,11 @@ int layer_forward(const sd_qwen3_dims* d, const Sizes& s, const LayerActs& a, co
 // (from the embedding or the previous layer's down projection); ssq_mid: scratch for those of a.x_mid; ssq_next
 // (nullable): where the down projection leaves those of x_out for the next layer.  w.ln1 / w.ln2 are not read.
 int layer_forward_folded(const sd_qwen3_dims* d, const Sizes& s, const LayerActs& a, const sd_qwen3_layer& w, char* x_out,
-                         const int32_t* kv_len, const void* cos_tab, const void* sin_tab, int B, int T, const float* ssq_in,
-                         float* ssq_mid, float* ssq_next, void* stream) {
-  const float scale = 0.08838834764831845f;
+                         const int32_t* kv_len, const sd_varlen* vl, const void* cos_tab, const void* sin_tab, int B, int T,
+                         const float* ssq_in, float* ssq_mid, float* ssq_next, void* stream) {
   RUN(sd_gemm_qkv_rope_rs(a.x_in, w.wqkv, a.qkv, a.qk, w.q_gain, w.k_gain, cos_tab, sin_tab, ssq_in, s.M, T, s.Hq, s.Hkv,
                           s.h, d->eps, stream));
-  RUN(sd_attn_fwd(a.qk, a.qk + (int64_t)s.QD * 2, a.qkv + (int64_t)(s.QD + s.KD) * 2, a.ao, (float*)a.lse, kv_len,
-                  s.QK, s.QK, s.QKV, s.QD, B, T, s.Hq, s.Hkv, 128, scale, stream));
+  RUN(layer_attn_fwd(s, a, kv_len, vl, B, T, stream));
   RUN(sd_gemm_bf16_ssq(a.ao, w.wo, a.x_mid, a.x_in, ssq_mid, s.M, s.h, s.QD, s.QD, s.QD, s.h, s.h, stream));
   RUN(sd_gemm_swiglu_rs(a.x_mid, w.wgu, nullptr, a.act, ssq_mid, d->eps, s.M, s.I, s.h, stream));
   if (ssq_next) RUN(sd_gemm_bf16_ssq(a.act, w.wdown, x_out, a.x_mid, ssq_next, s.M, s.h, s.I, s.I, s.I, s.h, s.h, stream));
@@ -279,10 +286,10 @@ extern "C" int sd_qwen3_forward(const sd_qwen3_dims* d, const sd_qwen3_params* p
                                stream);
 }
 
-extern "C" int sd_qwen3_forward_rows(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
-                                     const int32_t* kv_len, const void* cos_tab, const void* sin_tab, void* acts,
-                                     int64_t acts_bytes, void* logits, const int64_t* head_rows, int n_head_rows, int B,
-                                     int T, int save, void* stream) {
+// The forward of every entry: per batch row (kv_len), or per packed document when vl is given (B = 1, T = M)
+static int forward_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* kv_len,
+                        const sd_varlen* vl, const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes,
+                        void* logits, const int64_t* head_rows, int n_head_rows, int B, int T, int save, void* stream) {
   if (d->head_dim != 128) return SD_ERR_UNSUPPORTED;
   if (B <= 0 || T <= 0) return SD_ERR_SHAPE;
   if (head_rows && (n_head_rows <= 0 || n_head_rows > B * T)) return SD_ERR_SHAPE;
@@ -320,10 +327,11 @@ extern "C" int sd_qwen3_forward_rows(const sd_qwen3_dims* d, const sd_qwen3_para
     if (save) x_out = (l + 1 < s.L) ? layer_acts(s, base, l + 1, save).x_in : x_last;
     else x_out = (l + 1 < s.L) ? ((x_cur == pong) ? base : pong) : x_last;
     if (folded)
-      RUN(layer_forward_folded(d, s, a, p->layers_host[l], x_out, kv_len, cos_tab, sin_tab, B, T, ssq_a, ssq_b,
+      RUN(layer_forward_folded(d, s, a, p->layers_host[l], x_out, kv_len, vl, cos_tab, sin_tab, B, T, ssq_a, ssq_b,
                                l + 1 < s.L ? ssq_a : nullptr, stream));
     else
-      RUN(layer_forward(d, s, a, p->layers_host[l], x_out, save != SD_SAVE_NONE, kv_len, cos_tab, sin_tab, B, T, stream));
+      RUN(layer_forward(d, s, a, p->layers_host[l], x_out, save != SD_SAVE_NONE, kv_len, vl, cos_tab, sin_tab, B, T,
+                        stream));
     x_cur = x_out;
   }
   RUN(sd_rmsnorm_fwd(x_last, p->final_norm, xn_f, (float*)rstd_f, s.M, s.h, d->eps, stream));
@@ -336,6 +344,23 @@ extern "C" int sd_qwen3_forward_rows(const sd_qwen3_dims* d, const sd_qwen3_para
     RUN(sd_gemm_bf16(xn_f, p->lm_head, logits, nullptr, s.M, s.V, s.h, s.h, s.h, s.V, 0, 0, 0, stream));
   }
   return 0;
+}
+
+extern "C" int sd_qwen3_forward_rows(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
+                                     const int32_t* kv_len, const void* cos_tab, const void* sin_tab, void* acts,
+                                     int64_t acts_bytes, void* logits, const int64_t* head_rows, int n_head_rows, int B,
+                                     int T, int save, void* stream) {
+  return forward_impl(d, p, ids, kv_len, nullptr, cos_tab, sin_tab, acts, acts_bytes, logits, head_rows, n_head_rows, B, T,
+                      save, stream);
+}
+
+extern "C" int sd_qwen3_forward_varlen(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
+                                       const sd_varlen* vl, const void* cos_tab, const void* sin_tab, void* acts,
+                                       int64_t acts_bytes, void* logits, const int64_t* head_rows, int n_head_rows, int M,
+                                       int save, void* stream) {
+  if (!vl) return SD_ERR_SHAPE;
+  return forward_impl(d, p, ids, nullptr, vl, cos_tab, sin_tab, acts, acts_bytes, logits, head_rows, n_head_rows, 1, M,
+                      save, stream);
 }
 
 extern "C" int sd_qwen3_backward(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g,
@@ -351,7 +376,7 @@ extern "C" int sd_qwen3_backward(const sd_qwen3_dims* d, const sd_qwen3_params* 
 // (sd_qwen3_backward_embed_rows): the same dX chain, no per-layer weight / gain gradient, the lm_head dW over rows
 // [grad_row_lo, V) only and the embedding scatter restricted to ids >= grad_row_lo.
 static int backward_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g, const int64_t* ids,
-                         const int32_t* kv_len, const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes,
+                         const int32_t* kv_len, const sd_varlen* vl, const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes,
                          void* dlogits, const int64_t* head_rows, int n_head_rows, void* scratch, int64_t scratch_bytes,
                          int B, int T, int accumulate, void* dx0_out, sd_stage_cb on_grads_ready, void* cb_user,
                          void* side_stream, void* stream, int grad_row_lo) {
@@ -456,7 +481,7 @@ static int backward_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const
     // recompute: this layer's work set was last read by the weight-gradient GEMMs of layer l+2, which `stream` has
     // already waited for (the `pending` join of layer l+1 below)
     if (save == SD_SAVE_LAYER_INPUTS && l != s.L - 1)
-      RUN(layer_forward(d, s, a, w, nullptr, true, kv_len, cos_tab, sin_tab, B, T, stream));
+      RUN(layer_forward(d, s, a, w, nullptr, true, kv_len, vl, cos_tab, sin_tab, B, T, stream));
     // MLP
     if (!grouped && dw) {
       SIGNAL(0);  // dx_in final
@@ -491,9 +516,15 @@ static int backward_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const
       else o_for_delta = nullptr;
     }
     if (!grouped && dw) RUN(sd_gemm_bf16(dxb, a.ao, gw.wo, ACC(gw.wo), s.h, s.QD, s.M, s.h, s.QD, s.QD, s.QD, 1, 1, wstream));
-    RUN(sd_attn_bwd2(a.qk, a.qk + (int64_t)s.QD * 2, a.qkv + (int64_t)(s.QD + s.KD) * 2, o_for_delta, b.dao, (const float*)a.lse,
-                    (float*)b.delta, b.dqk, b.dqk + (int64_t)s.QD * 2, dqkv + (int64_t)(s.QD + s.KD) * 2, kv_len, s.QK,
-                    s.QK, s.QKV, s.QD, s.QK, s.QK, s.QKV, B, T, s.Hq, s.Hkv, 128, scale, (ovl & 4) ? side_stream : nullptr, stream));
+    if (vl)
+      RUN(sd_attn_bwd_varlen(a.qk, a.qk + (int64_t)s.QD * 2, a.qkv + (int64_t)(s.QD + s.KD) * 2, o_for_delta, b.dao,
+                             (const float*)a.lse, (float*)b.delta, b.dqk, b.dqk + (int64_t)s.QD * 2,
+                             dqkv + (int64_t)(s.QD + s.KD) * 2, vl, s.QK, s.QK, s.QKV, s.QD, s.QK, s.QK, s.QKV, s.M, s.Hq,
+                             s.Hkv, 128, scale, (ovl & 4) ? side_stream : nullptr, stream));
+    else
+      RUN(sd_attn_bwd2(a.qk, a.qk + (int64_t)s.QD * 2, a.qkv + (int64_t)(s.QD + s.KD) * 2, o_for_delta, b.dao, (const float*)a.lse,
+                      (float*)b.delta, b.dqk, b.dqk + (int64_t)s.QD * 2, dqkv + (int64_t)(s.QD + s.KD) * 2, kv_len, s.QK,
+                      s.QK, s.QKV, s.QD, s.QK, s.QK, s.QKV, B, T, s.Hq, s.Hkv, 128, scale, (ovl & 4) ? side_stream : nullptr, stream));
     RUN(sd_qknorm_rope_bwd2(b.dqk, a.qkv, w.q_gain, w.k_gain, cos_tab, sin_tab, dqkv, batch_gains ? nullptr : gw.q_gain,
                             batch_gains ? nullptr : gw.k_gain, acc, b.ws_qk[P], s.M, T, s.Hq, s.Hkv, d->eps,
                             ((ovl & 2) && dw) ? side_stream : nullptr, (s2 && dw) ? (void*)g_ev[9] : nullptr, stream));
@@ -566,8 +597,8 @@ extern "C" int sd_qwen3_backward_rows(const sd_qwen3_dims* d, const sd_qwen3_par
                                       int n_head_rows, void* scratch, int64_t scratch_bytes, int B, int T, int accumulate,
                                       void* dx0_out, sd_stage_cb on_grads_ready, void* cb_user, void* side_stream,
                                       void* stream) {
-  return backward_impl(d, p, g, ids, kv_len, cos_tab, sin_tab, acts, acts_bytes, dlogits, head_rows, n_head_rows, scratch,
-                       scratch_bytes, B, T, accumulate, dx0_out, on_grads_ready, cb_user, side_stream, stream, -1);
+  return backward_impl(d, p, g, ids, kv_len, nullptr, cos_tab, sin_tab, acts, acts_bytes, dlogits, head_rows, n_head_rows,
+                       scratch, scratch_bytes, B, T, accumulate, dx0_out, on_grads_ready, cb_user, side_stream, stream, -1);
 }
 
 extern "C" int sd_qwen3_backward_embed_rows(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g,
@@ -576,6 +607,28 @@ extern "C" int sd_qwen3_backward_embed_rows(const sd_qwen3_dims* d, const sd_qwe
                                             const int64_t* head_rows, int n_head_rows, void* scratch, int64_t scratch_bytes,
                                             int B, int T, int accumulate, int grad_row_lo, void* side_stream, void* stream) {
   if (grad_row_lo < 0) return SD_ERR_SHAPE;
-  return backward_impl(d, p, g, ids, kv_len, cos_tab, sin_tab, acts, acts_bytes, dlogits, head_rows, n_head_rows, scratch,
-                       scratch_bytes, B, T, accumulate, nullptr, nullptr, nullptr, side_stream, stream, grad_row_lo);
+  return backward_impl(d, p, g, ids, kv_len, nullptr, cos_tab, sin_tab, acts, acts_bytes, dlogits, head_rows, n_head_rows,
+                       scratch, scratch_bytes, B, T, accumulate, nullptr, nullptr, nullptr, side_stream, stream, grad_row_lo);
+}
+
+extern "C" int sd_qwen3_backward_varlen(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g,
+                                        const int64_t* ids, const sd_varlen* vl, const void* cos_tab, const void* sin_tab,
+                                        void* acts, int64_t acts_bytes, void* dlogits, const int64_t* head_rows,
+                                        int n_head_rows, void* scratch, int64_t scratch_bytes, int M, int accumulate,
+                                        void* dx0_out, sd_stage_cb on_grads_ready, void* cb_user, void* side_stream,
+                                        void* stream) {
+  if (!vl) return SD_ERR_SHAPE;
+  return backward_impl(d, p, g, ids, nullptr, vl, cos_tab, sin_tab, acts, acts_bytes, dlogits, head_rows, n_head_rows,
+                       scratch, scratch_bytes, 1, M, accumulate, dx0_out, on_grads_ready, cb_user, side_stream, stream, -1);
+}
+
+extern "C" int sd_qwen3_backward_embed_varlen(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g,
+                                              const int64_t* ids, const sd_varlen* vl, const void* cos_tab,
+                                              const void* sin_tab, void* acts, int64_t acts_bytes, void* dlogits,
+                                              const int64_t* head_rows, int n_head_rows, void* scratch,
+                                              int64_t scratch_bytes, int M, int accumulate, int grad_row_lo,
+                                              void* side_stream, void* stream) {
+  if (!vl || grad_row_lo < 0) return SD_ERR_SHAPE;
+  return backward_impl(d, p, g, ids, nullptr, vl, cos_tab, sin_tab, acts, acts_bytes, dlogits, head_rows, n_head_rows,
+                       scratch, scratch_bytes, 1, M, accumulate, nullptr, nullptr, nullptr, side_stream, stream, grad_row_lo);
 }

@@ -235,6 +235,68 @@ def attn_bwd(q, k, v, o, do, lse, B, T, Hq, Hkv, kv_len=None, delta=None):
     return dq, dk, dv
 
 
+def varlen_desc(cu_seqlens, max_seqlen=0, work=None):
+    """include/sd_hip.h sd_varlen over a device int32 ``cu_seqlens`` [n+1] (the caller keeps the tensors alive)."""
+    _need(cu_seqlens, torch.int32, "cu_seqlens")
+    if cu_seqlens.dim() != 1 or cu_seqlens.numel() < 2:
+        raise ValueError("cu_seqlens must be a 1-D tensor of n_seqs + 1 offsets")
+    from ._lib import Varlen
+    return Varlen(cu_seqlens.data_ptr(), cu_seqlens.numel() - 1, int(max_seqlen), _p(work))
+
+
+def attn_fwd_varlen(q, k, v, cu_seqlens, Hq, Hkv, max_seqlen=0, o=None, lse=None):
+    """Packed documents (sd_attn_fwd_varlen): q [M, Hq*128], k/v [M, Hkv*128] (any row stride, unit column stride), document
+    s = rows [cu_seqlens[s], cu_seqlens[s+1]).  Returns o [M, Hq*128] and lse fp32 [Hq, M]; ``o`` / ``lse`` may be given
+    (``o`` with any row stride)."""
+    M = q.shape[0]
+    if o is None:
+        o = torch.empty(M, Hq * 128, dtype=torch.bfloat16, device=q.device)
+    if lse is None:
+        lse = torch.empty(Hq, M, dtype=torch.float32, device=q.device)
+    desc = varlen_desc(cu_seqlens, max_seqlen)
+    check(load_lib().sd_attn_fwd_varlen(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), lse.data_ptr(), C.byref(desc),
+                                        q.stride(0), k.stride(0), v.stride(0), o.stride(0), M, Hq, Hkv, 128, 128 ** -0.5,
+                                        _stream()), "sd_attn_fwd_varlen")
+    return o, lse
+
+
+def attn_bwd_varlen(q, k, v, o, do, lse, cu_seqlens, Hq, Hkv, max_seqlen=0, delta=None, dq=None, dk=None, dv=None):
+    """Backward of ``attn_fwd_varlen`` (sd_attn_bwd_varlen); o = None: ``delta`` [Hq, M] already holds rowsum(dO * O).
+    ``dq`` / ``dk`` / ``dv`` may be given (any row stride); only rows [0, M) of the head columns are written."""
+    if o is None and delta is None:
+        raise ValueError("attn_bwd_varlen: either o or a precomputed delta")
+    M = q.shape[0]
+    if o is not None and M > 1 and o.stride(0) != do.stride(0):
+        raise ValueError("attn_bwd_varlen: o and do share one row stride (ldo)")
+    if delta is None:
+        delta = torch.empty_like(lse)
+    dq = torch.zeros(M, Hq * 128, dtype=torch.bfloat16, device=q.device) if dq is None else dq
+    dk = torch.zeros(M, Hkv * 128, dtype=torch.bfloat16, device=q.device) if dk is None else dk
+    dv = torch.zeros(M, Hkv * 128, dtype=torch.bfloat16, device=q.device) if dv is None else dv
+    desc = varlen_desc(cu_seqlens, max_seqlen)
+    check(load_lib().sd_attn_bwd_varlen(q.data_ptr(), k.data_ptr(), v.data_ptr(), _p(o), do.data_ptr(), lse.data_ptr(),
+                                        delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), C.byref(desc),
+                                        q.stride(0), k.stride(0), v.stride(0), do.stride(0), dq.stride(0), dk.stride(0),
+                                        dv.stride(0), M, Hq, Hkv, 128, 128 ** -0.5, None, _stream()), "sd_attn_bwd_varlen")
+    return dq, dk, dv
+
+
+def packed_segments(position_ids):
+    """Document boundaries of packed rows by HF's rule (transformers masking_utils.find_packed_sequence_indices): a new
+    document wherever ``position_ids[b, t] != position_ids[b, t-1] + 1``, and at every row start (rows never share a
+    document).  position_ids [B, T] (any device) -> (cu_seqlens int64 [n+1] on the host over the B*T flattened tokens,
+    largest position, smallest position): ONE host read."""
+    pos = position_ids.to(torch.int64)
+    if pos.dim() != 2 or pos.numel() == 0:
+        raise ValueError(f"position_ids must be [batch, seq_len], got {tuple(position_ids.shape)}")
+    start = torch.ones_like(pos, dtype=torch.bool)
+    start[:, 1:] = pos[:, 1:] != pos[:, :-1] + 1
+    host = torch.cat([start.reshape(-1).to(torch.int64), pos.max().reshape(1), pos.min().reshape(1)]).cpu()
+    M = pos.numel()
+    starts = torch.nonzero(host[:M]).reshape(-1)
+    return torch.cat([starts, torch.tensor([M])]), int(host[M]), int(host[M + 1])
+
+
 # ------------------------------------------------------------------------------------ top-K / loss
 def logsoftmax_topk(logits, k, vocab_size=None):
     """train.py:80-91: logits[..., :vocab] -> log_softmax -> topk(k) -> (fp16 values, int32 indices)."""

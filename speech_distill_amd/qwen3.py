@@ -26,6 +26,22 @@ from ._lib import check, load_lib
 from .ops import _need, _p, _stream, left_padded, rope_tables  # noqa: F401  (left_padded is re-exported)
 
 
+class PackedBatch:
+    """One call's packed documents (padding-free packing, HF ``position_ids`` without ``attention_mask``): the int32
+    ``cu_seqlens`` on the device, the C descriptor (include/sd_hip.h sd_varlen) and the per-token RoPE tables (row m =
+    the angles of token m's position).  Kept by the autograd function for the backward."""
+
+    def __init__(self, cu_host, cos, sin, device):
+        from . import ops
+        self.M, self.n = int(cu_host[-1]), cu_host.numel() - 1
+        self.max_seqlen = int((cu_host[1:] - cu_host[:-1]).max())
+        self.cu = cu_host.to(torch.int32).to(device)
+        nb = load_lib().sd_varlen_work_bytes(self.M)
+        self.work = torch.empty(nb, dtype=torch.uint8, device=device) if nb > 0 else None
+        self.desc = ops.varlen_desc(self.cu, self.max_seqlen, self.work)
+        self.cos, self.sin = cos, sin
+
+
 @dataclass
 class Qwen3Dims:
     vocab_size: int
@@ -106,18 +122,20 @@ BWD_ACCUMULATE, BWD_RECOMPUTE = 1, 2              # SD_BWD_*
 
 class _DecoderFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, anchor, input_ids, kv_len, model, rows, concurrent=False):
-        save = SAVE_LAYER_INPUTS if model._wants_recompute(*input_ids.shape, input_ids.device) else SAVE_ALL
-        logits, acts = model._run_forward(input_ids, kv_len, save=save, rows=rows, concurrent=concurrent)
+    def forward(ctx, anchor, input_ids, kv_len, model, rows, concurrent=False, packed=None):
+        shape = (1, packed.M) if packed is not None else input_ids.shape
+        save = SAVE_LAYER_INPUTS if model._wants_recompute(*shape, input_ids.device) else SAVE_ALL
+        logits, acts = model._run_forward(input_ids, kv_len, save=save, rows=rows, concurrent=concurrent, packed=packed)
         ctx.model, ctx.acts, ctx.ids, ctx.kv_len, ctx.rows, ctx.save = model, acts, input_ids, kv_len, rows, save
+        ctx.packed = packed
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
         ctx.model._run_backward(ctx.ids, ctx.kv_len, ctx.acts, dlogits, rows=ctx.rows,
-                                recompute=ctx.save == SAVE_LAYER_INPUTS)
-        ctx.acts = None
-        return torch.zeros((), device=dlogits.device), None, None, None, None, None
+                                recompute=ctx.save == SAVE_LAYER_INPUTS, packed=ctx.packed)
+        ctx.acts = ctx.packed = None
+        return torch.zeros((), device=dlogits.device), None, None, None, None, None, None
 
 
 class HipQwen3ForCausalLM(nn.Module):
@@ -450,6 +468,41 @@ class HipQwen3ForCausalLM(nn.Module):
             self._rope[key] = rope_tables(T, device, self.dims.rope_theta)
         return self._rope[key]
 
+    def _packed(self, ids, position_ids, cu_seq_lens_q=None, cu_seq_lens_k=None):
+        """PackedBatch of a packed call (HF padding-free packing): the segments come from ``cu_seq_lens_q`` when given
+        (it must then equal ``cu_seq_lens_k``), else from ``position_ids`` by HF's rule (``ops.packed_segments``); ``B > 1``
+        rows are flattened.  RoPE uses the given positions, which need not start at 0.  Everything is checked before any
+        launch, on one host read."""
+        from .ops import packed_segments
+        pos = position_ids.to(ids.device)
+        if pos.dtype not in (torch.int32, torch.int64) or tuple(pos.shape) != tuple(ids.shape):
+            raise ValueError(f"position_ids must be an integer tensor shaped like input_ids {tuple(ids.shape)}, "
+                             f"got {pos.dtype} {tuple(pos.shape)}")
+        M = ids.numel()
+        if cu_seq_lens_q is not None:
+            cu = cu_seq_lens_q
+            if cu_seq_lens_k is not None and (cu_seq_lens_k.shape != cu.shape or
+                                              not torch.equal(cu_seq_lens_k.to(cu.device), cu)):
+                raise ValueError("cu_seq_lens_k differs from cu_seq_lens_q: packed causal attention takes one set of segments")
+            if cu.dtype not in (torch.int32, torch.int64) or cu.dim() != 1 or cu.numel() < 2:
+                raise ValueError(f"cu_seq_lens_q must be a 1-D int32 tensor of n_seqs + 1 offsets, got {cu.dtype} "
+                                 f"{tuple(cu.shape)}")
+            host = torch.cat([cu.to(device=pos.device, dtype=torch.int64), pos.max().reshape(1).to(torch.int64),
+                              pos.min().reshape(1).to(torch.int64)]).cpu()
+            cu_host, pmax, pmin = host[:-2], int(host[-2]), int(host[-1])
+            if int(cu_host[0]) != 0 or int(cu_host[-1]) != M or bool((cu_host[1:] < cu_host[:-1]).any()):
+                raise ValueError(f"cu_seq_lens_q must rise from 0 to the token count {M}, got {cu_host.tolist()[:8]}...")
+        else:
+            cu_host, pmax, pmin = packed_segments(pos)
+        if pmin < 0:
+            raise ValueError("position_ids must be non-negative")
+        n = 64
+        while n <= pmax:
+            n *= 2
+        cos, sin = self._tables(n, ids.device)
+        flat = pos.reshape(-1).to(torch.int64)
+        return PackedBatch(cu_host, cos[flat].contiguous(), sin[flat].contiguous(), ids.device)
+
     @torch.no_grad()
     def _folded_params(self):
         """C parameter struct whose wqkv / wgu point at W diag(g) (g = the RMSNorm gain in front of the projection,
@@ -481,11 +534,11 @@ class HipQwen3ForCausalLM(nn.Module):
         self._folded = (ver, buf, params, layers)
         return params
 
-    def _run_forward(self, input_ids, kv_len, save, rows=None, concurrent=False):
+    def _run_forward(self, input_ids, kv_len, save, rows=None, concurrent=False, packed=None):
         lib = load_lib()
         B, T = input_ids.shape
         dev = input_ids.device
-        cos, sin = self._tables(T, dev)
+        cos, sin = (packed.cos, packed.sin) if packed is not None else self._tables(T, dev)
         cparams = self._cparams
         if self._lora is not None:
             self._lora.ensure_merged()   # W_eff = W_res + s B A, rebuilt only after A / B have changed
@@ -493,12 +546,19 @@ class HipQwen3ForCausalLM(nn.Module):
             folded = self._folded_params()
             if folded is not None:
                 cparams, save = folded, SAVE_NONE_FOLDED
-        nbytes = lib.sd_qwen3_acts_bytes(C.byref(self._cdims), B, T, int(save))
+        nbytes = lib.sd_qwen3_acts_bytes(C.byref(self._cdims), *((1, packed.M) if packed is not None else (B, T)), int(save))
         acts = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         if rows is None:
             logits = torch.empty(B, T, self.dims.vocab_size, dtype=torch.bfloat16, device=dev)
         else:
             logits = torch.empty(rows.numel(), self.dims.vocab_size, dtype=torch.bfloat16, device=dev)
+        if packed is not None:  # one row of B*T tokens, attention per document
+            check(lib.sd_qwen3_forward_varlen(C.byref(self._cdims), C.byref(cparams), input_ids.data_ptr(),
+                                              C.byref(packed.desc), cos.data_ptr(), sin.data_ptr(), acts.data_ptr(), nbytes,
+                                              logits.data_ptr(), _p(rows), 0 if rows is None else rows.numel(), packed.M,
+                                              int(save) | (FWD_CONCURRENT if concurrent else 0), _stream()),
+                  "sd_qwen3_forward_varlen")
+            return logits, acts
         check(lib.sd_qwen3_forward_rows(C.byref(self._cdims), C.byref(cparams), input_ids.data_ptr(), _p(kv_len),
                                         cos.data_ptr(), sin.data_ptr(), acts.data_ptr(), nbytes, logits.data_ptr(),
                                         _p(rows), 0 if rows is None else rows.numel(), B, T,
@@ -533,11 +593,11 @@ class HipQwen3ForCausalLM(nn.Module):
         if not 0 <= int(self.stage1_row_lo) <= self.dims.vocab_size:
             raise ValueError(f"stage1_row_lo {self.stage1_row_lo} outside [0, {self.dims.vocab_size}]")
 
-    def _run_backward(self, input_ids, kv_len, acts, dlogits, rows=None, recompute=False):
+    def _run_backward(self, input_ids, kv_len, acts, dlogits, rows=None, recompute=False, packed=None):
         lib = load_lib()
         B, T = input_ids.shape
         if self.stage1_row_lo is not None:
-            return self._run_backward_stage1(input_ids, kv_len, acts, dlogits, rows, recompute)
+            return self._run_backward_stage1(input_ids, kv_len, acts, dlogits, rows, recompute, packed)
         accumulate = self._ensure_grads()
         red = getattr(self, "_reducer", None)
         dx0 = None
@@ -551,25 +611,32 @@ class HipQwen3ForCausalLM(nn.Module):
                 red.set_embedding_exchange(input_ids.reshape(-1), dx0, self.flat_grad[eo:eo + en].view(eshape))
         if not dlogits.is_contiguous():
             dlogits = dlogits.contiguous()
-        cos, sin = self._tables(T, input_ids.device)
-        sbytes = lib.sd_qwen3_bwd_scratch_bytes(C.byref(self._cdims), B, T)
+        cos, sin = (packed.cos, packed.sin) if packed is not None else self._tables(T, input_ids.device)
+        sbytes = lib.sd_qwen3_bwd_scratch_bytes(C.byref(self._cdims), *((1, packed.M) if packed is not None else (B, T)))
         scratch = torch.empty(sbytes, dtype=torch.uint8, device=input_ids.device)
         user_cb = self._stage_cb
         cb = _lib.STAGE_CB((lambda stage, _u: user_cb(stage)) if user_cb else 0)
-        check(lib.sd_qwen3_backward_rows(C.byref(self._cdims), C.byref(self._cparams), C.byref(self._cgrads),
-                                         input_ids.data_ptr(), _p(kv_len), cos.data_ptr(), sin.data_ptr(),
-                                         acts.data_ptr(), acts.numel(), dlogits.data_ptr(), _p(rows),
-                                         0 if rows is None else rows.numel(), scratch.data_ptr(), sbytes, B, T,
-                                         (BWD_ACCUMULATE if accumulate else 0) | (BWD_RECOMPUTE if recompute else 0),
-                                         _p(dx0), cb, None, self._side_stream_ptr(input_ids.device),
-                                         _stream()),
-              "sd_qwen3_backward_rows")
+        flags = (BWD_ACCUMULATE if accumulate else 0) | (BWD_RECOMPUTE if recompute else 0)
+        if packed is not None:
+            check(lib.sd_qwen3_backward_varlen(C.byref(self._cdims), C.byref(self._cparams), C.byref(self._cgrads),
+                                               input_ids.data_ptr(), C.byref(packed.desc), cos.data_ptr(), sin.data_ptr(),
+                                               acts.data_ptr(), acts.numel(), dlogits.data_ptr(), _p(rows),
+                                               0 if rows is None else rows.numel(), scratch.data_ptr(), sbytes, packed.M,
+                                               flags, _p(dx0), cb, None, self._side_stream_ptr(input_ids.device), _stream()),
+                  "sd_qwen3_backward_varlen")
+        else:
+            check(lib.sd_qwen3_backward_rows(C.byref(self._cdims), C.byref(self._cparams), C.byref(self._cgrads),
+                                             input_ids.data_ptr(), _p(kv_len), cos.data_ptr(), sin.data_ptr(),
+                                             acts.data_ptr(), acts.numel(), dlogits.data_ptr(), _p(rows),
+                                             0 if rows is None else rows.numel(), scratch.data_ptr(), sbytes, B, T, flags,
+                                             _p(dx0), cb, None, self._side_stream_ptr(input_ids.device), _stream()),
+                  "sd_qwen3_backward_rows")
         if red is not None:
             red.finish()
         if self._lora is not None:
             self._lora.grads_stale = True
 
-    def _run_backward_stage1(self, input_ids, kv_len, acts, dlogits, rows, recompute):
+    def _run_backward_stage1(self, input_ids, kv_len, acts, dlogits, rows, recompute, packed=None):
         """sd_qwen3_backward_embed_rows: dX chain only, gradient rows [stage1_row_lo, V) of embed_tokens (+ lm_head)."""
         self.check_stage1()
         if getattr(self, "_reducer", None) is not None:
@@ -579,15 +646,24 @@ class HipQwen3ForCausalLM(nn.Module):
         accumulate = self._ensure_grads()
         if not dlogits.is_contiguous():
             dlogits = dlogits.contiguous()
-        cos, sin = self._tables(T, input_ids.device)
-        sbytes = lib.sd_qwen3_bwd_scratch_bytes(C.byref(self._cdims), B, T)
+        sbytes = lib.sd_qwen3_bwd_scratch_bytes(C.byref(self._cdims), *((1, packed.M) if packed is not None else (B, T)))
         scratch = torch.empty(sbytes, dtype=torch.uint8, device=input_ids.device)
+        flags = (BWD_ACCUMULATE if accumulate else 0) | (BWD_RECOMPUTE if recompute else 0)
+        if packed is not None:
+            check(lib.sd_qwen3_backward_embed_varlen(C.byref(self._cdims), C.byref(self._cparams), C.byref(self._cgrads),
+                                                     input_ids.data_ptr(), C.byref(packed.desc), packed.cos.data_ptr(),
+                                                     packed.sin.data_ptr(), acts.data_ptr(), acts.numel(), dlogits.data_ptr(),
+                                                     _p(rows), 0 if rows is None else rows.numel(), scratch.data_ptr(),
+                                                     sbytes, packed.M, flags, int(self.stage1_row_lo),
+                                                     self._side_stream_ptr(input_ids.device), _stream()),
+                  "sd_qwen3_backward_embed_varlen")
+            return
+        cos, sin = self._tables(T, input_ids.device)
         check(lib.sd_qwen3_backward_embed_rows(C.byref(self._cdims), C.byref(self._cparams), C.byref(self._cgrads),
                                                input_ids.data_ptr(), _p(kv_len), cos.data_ptr(), sin.data_ptr(),
                                                acts.data_ptr(), acts.numel(), dlogits.data_ptr(), _p(rows),
                                                0 if rows is None else rows.numel(), scratch.data_ptr(), sbytes, B, T,
-                                               (BWD_ACCUMULATE if accumulate else 0) | (BWD_RECOMPUTE if recompute else 0),
-                                               int(self.stage1_row_lo), self._side_stream_ptr(input_ids.device), _stream()),
+                                               flags, int(self.stage1_row_lo), self._side_stream_ptr(input_ids.device), _stream()),
               "sd_qwen3_backward_embed_rows")
 
     def finalize_grads(self):
@@ -637,14 +713,22 @@ class HipQwen3ForCausalLM(nn.Module):
             self._side_stream = ops.concurrent_stream(device, "dw")
         return self._side_stream.cuda_stream
 
-    def forward(self, input_ids=None, attention_mask=None, labels=None, logit_rows=None, **kwargs):
+    def forward(self, input_ids=None, attention_mask=None, labels=None, logit_rows=None, position_ids=None, **kwargs):
         """Returns an object with ``.logits`` [B,T,V] (bf16).  ``labels`` is accepted and ignored: the
         reference leaves it in ``inputs`` at train.py:54, which only makes HF compute an unused CE.  In Stage-1 mode
         (``stage1_row_lo`` set by ``stage1.freeze_model_weights``) ``labels`` gives ``.loss`` instead: ``_forward_stage1``.
         ``logit_rows`` (int64 [R], flat b*T+t indices, unique): apply the lm_head to those rows only and return
         ``.logits`` [R,V] -- the training step passes the rows the loss reads (``ops.loss_rows``).
         ``concurrent=True`` (keyword): the caller runs another pass beside this one on a second stream (the frozen
-        teacher beside the student, as DistillationTrainer does): SD_FWD_CONCURRENT, launches sized for a shared GPU."""
+        teacher beside the student, as DistillationTrainer does): SD_FWD_CONCURRENT, launches sized for a shared GPU.
+
+        Packed documents (HF padding-free packing: ``DataCollatorWithFlattening``, TRL ``padding_free``), exactly when HF
+        Qwen3 packs: ``position_ids`` given and ``attention_mask`` None.  The documents are the segments of
+        ``cu_seq_lens_q`` (HF's ``FlashAttentionKwargs``; ``cu_seq_lens_k`` must equal it) or, without it, the runs of
+        consecutive ``position_ids`` (a new document wherever ``pos[t] != pos[t-1] + 1`` and at every row start); rows of
+        ``B > 1`` are flattened.  No token attends across a document boundary (varlen attention kernels) and RoPE uses the
+        given positions.  With an ``attention_mask``, ``position_ids`` are ignored (positions 0..T-1 per right-padded
+        row), as before."""
         ids = _need(input_ids.to(torch.int64), torch.int64, "input_ids")
         rows = None
         if logit_rows is not None:
@@ -662,16 +746,24 @@ class HipQwen3ForCausalLM(nn.Module):
                 raise ValueError("attention_mask is not right-padded (a 1 follows a 0): the HIP attention kernels take a "
                                  "valid-prefix length per sequence, as ProcessedDataCollator produces (data.py:280-327)")
             kv_len = am.sum(-1).to(torch.int32).contiguous()
+        packed = None
+        if attention_mask is None and position_ids is not None:
+            packed = self._packed(ids, position_ids, kwargs.get("cu_seq_lens_q"), kwargs.get("cu_seq_lens_k"))
+        elif attention_mask is None and kwargs.get("cu_seq_lens_q") is not None:
+            raise ValueError("cu_seq_lens_q without position_ids: packed documents need their positions (HF packs only "
+                             "when position_ids is given and attention_mask is None)")
         if self.stage1_row_lo is not None and labels is not None:
-            return self._forward_stage1(ids, am if attention_mask is not None else None, kv_len, labels, **kwargs)
+            return self._forward_stage1(ids, am if attention_mask is not None else None, kv_len, labels, packed=packed,
+                                        **kwargs)
         if torch.is_grad_enabled() and (self._lora is not None or any(p.requires_grad for p in self._params.values())):
-            logits = _DecoderFn.apply(self._anchor, ids, kv_len, self, rows, bool(kwargs.get("concurrent", False)))
+            logits = _DecoderFn.apply(self._anchor, ids, kv_len, self, rows, bool(kwargs.get("concurrent", False)), packed)
         else:
             logits, _ = self._run_forward(ids, kv_len, save=SAVE_NONE, rows=rows,
-                                          concurrent=bool(kwargs.get("concurrent", False)))
+                                          concurrent=bool(kwargs.get("concurrent", False)), packed=packed)
         return CausalLMOutput(logits=logits)
 
-    def _forward_stage1(self, ids, am, kv_len, labels, num_items_in_batch=None, stage1_inplace_grad=False, **_):
+    def _forward_stage1(self, ids, am, kv_len, labels, num_items_in_batch=None, stage1_inplace_grad=False, packed=None,
+                        **_):
         """Stage-1 loss (reference stage1.py: SFTTrainer -> HF ForCausalLMLoss): causal-LM cross-entropy over the rows whose
         next label is not -100, summed and divided by ``num_items_in_batch`` when given (else the mean).  The rows are
         selected on the GPU (``ops.loss_rows``, the one host read), the lm_head runs on those rows only, and the loss is
@@ -687,9 +779,9 @@ class HipQwen3ForCausalLM(nn.Module):
         if num_items_in_batch is not None:
             div = torch.as_tensor(num_items_in_batch, dtype=torch.float32).to(ids.device).reshape(1)
         if torch.is_grad_enabled() and any(p.requires_grad for p in self._params.values()):
-            logits = _DecoderFn.apply(self._anchor, ids, kv_len, self, rows, False)
+            logits = _DecoderFn.apply(self._anchor, ids, kv_len, self, rows, False, packed)
         else:
-            logits, _ = self._run_forward(ids, kv_len, save=SAVE_NONE, rows=rows)
+            logits, _ = self._run_forward(ids, kv_len, save=SAVE_NONE, rows=rows, packed=packed)
         loss, _ = celoss_rows(logits, row_labels, div, inplace_grad=bool(stage1_inplace_grad))
         return CausalLMOutput(loss=loss, logits=logits, logit_rows=rows)
 

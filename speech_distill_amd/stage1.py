@@ -6,8 +6,10 @@ expanded vocabulary that belong to the new speech tokens, with plain causal-LM c
   On a ``HipQwen3ForCausalLM`` the mask is not a hook: the model records ``stage1_row_lo = old_vocab`` and its backward
   (``sd_qwen3_backward_embed_rows``) never computes the body's weight gradients nor writes the rows below it.
 * ``pack_bfd`` / ``Stage1Collator`` -- TRL ``packing=True`` restated: best-fit-decreasing bins of ``max_seq_length``
-  tokens; each document of a bin is its own right-padded row, so attention and RoPE positions restart per document as in
-  padding-free packing (the cost is padding instead of a varlen kernel).  The bin order and the boundary convention (the
+  tokens.  By default each document of a bin is its own right-padded row, so attention and RoPE positions restart per
+  document at the cost of padding; ``padding_free=True`` gives what TRL trains on under flash-attention: the documents
+  flattened into one row with ``position_ids`` restarting per document and the flash-attn varlen keys, run by the varlen
+  attention kernels with no padding at all.  The bin order and the boundary convention (the
   last token of a document predicts nothing, as with HF ``DataCollatorWithFlattening``) are an UNPINNED restatement of
   trl 0.26.2 (requirements.txt), which is not available to test against.
 * ``Stage1Trainer`` (speech_distill_amd.trainer) -- the SFTTrainer's role: HF Trainer + FlatAdamW over the Stage-1 segments.
@@ -106,11 +108,20 @@ class Stage1Collator:
     ``pad_to_multiple_of``): ``input_ids`` (pad ``pad_token_id``), ``attention_mask``, ``labels`` = ids with -100 at the
     first position of every document and at the padding (HF DataCollatorWithFlattening's labels; after the causal
     shift the last token of a document predicts nothing).  Features: ``{"documents": [[ids], ...]}`` (one bin) or
-    ``{"input_ids": [ids]}`` (one unpacked document)."""
+    ``{"input_ids": [ids]}`` (one unpacked document).
 
-    def __init__(self, pad_token_id=0, pad_to_multiple_of=None):
+    ``padding_free=True``: the documents of the batch's bins (bins in batch order, documents in bin order) flattened into
+    ONE row with no padding: ``input_ids`` and ``labels`` [1, M], ``position_ids`` restarting at 0 per document,
+    ``cu_seq_lens_q`` / ``_k`` (int32 [n+1]) and ``max_length_q`` / ``_k`` (int) -- exactly what
+    ``transformers.DataCollatorWithFlattening(return_flash_attn_kwargs=True, separator_id=-100)`` returns, and no
+    ``attention_mask`` (HipQwen3ForCausalLM then runs the varlen attention)."""
+
+    def __init__(self, pad_token_id=0, pad_to_multiple_of=None, padding_free=False):
+        if padding_free and pad_to_multiple_of:
+            raise ValueError("Stage1Collator: pad_to_multiple_of pads rows, and padding_free has none to pad")
         self.pad_token_id = pad_token_id
         self.pad_to_multiple_of = pad_to_multiple_of
+        self.padding_free = padding_free
 
     def __call__(self, features: List[Dict[str, Any]]) -> Dict[str, torch.Tensor]:
         docs = []
@@ -119,6 +130,8 @@ class Stage1Collator:
         docs = [list(d) for d in docs if len(d) > 0]
         if not docs:
             raise ValueError("Stage1Collator: empty batch")
+        if self.padding_free:
+            return self._flatten(docs)
         w = max(len(d) for d in docs)
         m = self.pad_to_multiple_of
         if m:
@@ -132,3 +145,17 @@ class Stage1Collator:
             am[r, :len(d)] = 1
             labels[r, 1:len(d)] = t[1:]
         return {"input_ids": ids, "attention_mask": am, "labels": labels}
+
+    @staticmethod
+    def _flatten(docs):
+        ids, labels, pos, cu = [], [], [], [0]
+        for d in docs:
+            ids += d
+            labels += [-100] + d[1:]
+            pos += range(len(d))
+            cu.append(cu[-1] + len(d))
+        longest = max(len(d) for d in docs)
+        cu_t = torch.tensor(cu, dtype=torch.int32)
+        return {"input_ids": torch.tensor([ids], dtype=torch.long), "labels": torch.tensor([labels], dtype=torch.long),
+                "position_ids": torch.tensor([pos], dtype=torch.long), "cu_seq_lens_q": cu_t, "cu_seq_lens_k": cu_t.clone(),
+                "max_length_q": longest, "max_length_k": longest}

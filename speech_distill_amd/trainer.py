@@ -424,7 +424,10 @@ class Stage1Trainer(FlatStudentTrainer):
     """Stage-1 speech-token alignment (reference stage1.py:285-335: TRL SFTTrainer, ``adamw_torch``, ``max_grad_norm`` 1.0)
     on a model frozen by ``stage1.freeze_model_weights``: plain causal-LM cross-entropy, FlatAdamW over the Stage-1
     segments (the embedding, + an untied lm_head: HF's decay groups put weight decay on both), the one-reduction clip,
-    tokens/sec in the training log.  Single GPU.  Batches: ``stage1.Stage1Collator`` (input_ids, attention_mask, labels)."""
+    tokens/sec in the training log.  Single GPU.  Batches: ``stage1.Stage1Collator`` (input_ids, attention_mask, labels; or,
+    with ``padding_free=True``, input_ids, labels, position_ids and the flash-attn varlen keys, passed through)."""
+
+    PACKED_KEYS = ("position_ids", "cu_seq_lens_q", "cu_seq_lens_k", "max_length_q", "max_length_k")
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -454,8 +457,9 @@ class Stage1Trainer(FlatStudentTrainer):
             self.tokens_seen += ids.numel()
             if self._tps_mark is None:  # first training micro-batch: the clock of the first tokens/sec figure starts here
                 self._tps_mark = (time.perf_counter(), self.tokens_seen - ids.numel())
+        packed = {k: inputs[k] for k in self.PACKED_KEYS if inputs.get(k) is not None}
         out = model(input_ids=ids, attention_mask=inputs.get("attention_mask"), labels=inputs["labels"],
-                    num_items_in_batch=num_items_in_batch, stage1_inplace_grad=not return_outputs)
+                    num_items_in_batch=num_items_in_batch, stage1_inplace_grad=not return_outputs, **packed)
         return (out["loss"], out) if return_outputs else out["loss"]
 
 
