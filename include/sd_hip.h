@@ -425,6 +425,55 @@ int sd_qwen3_backward_embed_varlen(const sd_qwen3_dims* d, const sd_qwen3_params
                                    int n_head_rows, void* scratch, int64_t scratch_bytes, int M, int accumulate,
                                    int grad_row_lo, void* side_stream, void* stream);
 
+/* ---- MXFP8 frozen teacher (train.py:60-69, 155-169: the teacher is loaded once, frozen, and only ever run forward; the
+ * reference offers it in 8 bit through bitsandbytes, train.py:155-162 -- this is the format gfx950 has hardware for, not
+ * bitsandbytes').  OCP Microscaling FP8: e4m3fn elements, one E8M0 scale byte per 32 consecutive elements along K.
+ * For a block of bf16 values x: amax = max |x|; e = floor(log2(amax)) - 8 clamped to [-127, 127] (amax == 0: e = -127);
+ * scale byte = e + 127; q = RNE_e4m3fn(clamp(x * 2^-e, -448, 448)); value = float(q) * 2^e.  NaN / Inf inputs are outside
+ * the contract.  Every quantisation takes bf16-rounded values, also inside a GEMM epilogue.
+ *   sd_mxfp8_quant: x bf16 [M,K] (row stride ldx elements) -> q e4m3 [M,K] + scale E8M0 [M,K/32]; rstd (nullable) fp32 [M]
+ *     = rsqrt(mean(x^2) + eps) of the same row (HF:59-64: the RMSNorm statistic, applied as the consuming GEMM's row scale).
+ *     K % 128 == 0.
+ *   sd_gemm_mxfp8 (HF:252-254, 279, 83): C bf16 [M,N] = bf16(rowscale[m] * (A . B^T) + R), A [M,K] and B [N,K] (torch
+ *     weight layout) both MXFP8, fp32 accumulation on v_mfma_scale_f32_16x16x128_f8f6f4; rowscale fp32 [M] and R bf16
+ *     [M,N] (may alias C) nullable.  K % 128 == 0, N % 32 == 0.
+ *   sd_gemm_mxfp8_swiglu (HF:81-83): wgu = [gate rows | up rows] [2I,K]; g, u = bf16(rowscale * (A . W^T)),
+ *     act = bf16(silu(g) * u) exactly as sd_swiglu_fwd computes it, written ONLY as MXFP8: act_q [M,I], act_scale [M,I/32]
+ *     (equals sd_gemm_mxfp8 + sd_swiglu_fwd + sd_mxfp8_quant bit for bit; the bf16 act is never stored).  I % 128 == 0. */
+int sd_mxfp8_quant(const void* x, int64_t ldx, void* q, void* scale, float* rstd, float eps, int M, int K, void* stream);
+int sd_gemm_mxfp8(const void* a_q, const void* a_scale, const void* b_q, const void* b_scale, void* C, const void* R,
+                  const float* rowscale, int M, int N, int K, int64_t ldc, int64_t ldr, void* stream);
+int sd_gemm_mxfp8_swiglu(const void* a_q, const void* a_scale, const void* wgu_q, const void* wgu_scale,
+                         const float* rowscale, void* act_q, void* act_scale, int M, int I, int K, void* stream);
+
+/* The decoder runner at that precision: inference only.  Per layer the four projections carry the RMSNorm gain in front
+ * of them folded in (bf16(W[n][k] * g[k]), as SD_SAVE_NONE_FOLDED does) and are then quantised by sd_mxfp8_quant; the
+ * residual stream, attention, q/k-norm + RoPE, the final RMSNorm, embedding and lm_head stay bf16.
+ * Launches per layer: quant(x)+rstd, q|k|v GEMM, sd_qknorm_rope_fwd, attention, quant(ao), o GEMM + residual,
+ * quant(x_mid)+rstd, gate|up GEMM + SwiGLU -> MXFP8, down GEMM + residual.
+ * sd_qwen3_mx_supported: head_dim 128, hidden and inter multiples of 128.  `flags`: 0 or SD_FWD_CONCURRENT.  The other
+ * arguments are those of sd_qwen3_forward_rows / sd_qwen3_forward_varlen; acts of sd_qwen3_mx_acts_bytes(d, B, T)
+ * (B = 1, T = M for the packed entry). */
+typedef struct {
+  void *wqkv_q, *wqkv_scale, *wo_q, *wo_scale, *wgu_q, *wgu_scale, *wdown_q, *wdown_scale; /* e4m3 [N,K] + E8M0 [N,K/32] */
+  void *q_gain, *k_gain;                                                                    /* bf16 [128] */
+} sd_qwen3_layer_mx;
+typedef struct {
+  void* embed;      /* bf16 [V,h] */
+  void* lm_head;    /* bf16 [V,h]; == embed when tied */
+  void* final_norm; /* bf16 [h] */
+  const sd_qwen3_layer_mx* layers_host; /* HOST array of `layers` entries holding DEVICE pointers */
+} sd_qwen3_params_mx;
+int sd_qwen3_mx_supported(const sd_qwen3_dims* d);
+int64_t sd_qwen3_mx_acts_bytes(const sd_qwen3_dims* d, int B, int T);
+int sd_qwen3_forward_mx(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids, const int32_t* kv_len,
+                        const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes, void* logits,
+                        const int64_t* head_rows, int n_head_rows, int B, int T, int flags, void* stream);
+int sd_qwen3_forward_mx_varlen(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids,
+                               const sd_varlen* vl, const void* cos_tab, const void* sin_tab, void* acts,
+                               int64_t acts_bytes, void* logits, const int64_t* head_rows, int n_head_rows, int M,
+                               int flags, void* stream);
+
 /* ---- stream placement.  HIP multiplexes streams onto a few hardware queues (4 by default); streams that share a
  * queue never overlap.  Measures, with a `spin_us`-long busy-wait kernel on stream_a and an empty one on stream_b,
  * whether work on b runs while a is busy: *overlap = 1/0.  Synchronises both streams (a calibration call, made once

@@ -58,7 +58,7 @@ def nested_column(arrays, arrow_type, max_chunk_elems=1 << 30):
     return pa.chunked_array(chunks)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--teacher_model_path", required=True)   # extract_teacher_logits.py:154
     ap.add_argument("--dataset_path", required=True)
@@ -76,13 +76,20 @@ def main():
     ap.add_argument("--speech_eos", default="<|semantic_token_end|>")
     ap.add_argument("--pad_token", default="<|semantic_token_end|>")
     ap.add_argument("--pad_token_id", type=int, default=153478, help="(+) when the model directory holds no tokenizer")
-    cfg = ap.parse_args()
+    ap.add_argument("--teacher_precision", choices=("bf16", "mxfp8"), default="bf16",
+                    help="(+) mxfp8: the frozen teacher's decoder projections run as MXFP8 GEMMs (lm_head stays bf16)")
+    return ap.parse_args(argv)
+
+
+def main():
+    cfg = parse_args()
     from datasets import DatasetDict, load_from_disk
     import speech_distill_amd as sda
     from speech_distill_amd.collator import ProcessedDataCollator
     dev = torch.device("cuda:0")
     teacher = sda.HipQwen3ForCausalLM.from_pretrained(cfg.teacher_model_path, device=dev)       # :28-40
     teacher.eval().requires_grad_(False)
+    teacher.set_inference_precision(cfg.teacher_precision)   # (+)
     ds = load_from_disk(cfg.dataset_path)
     if isinstance(ds, DatasetDict):
         ds = ds[cfg.dataset_split]

@@ -62,9 +62,12 @@ def parse_args():
     p.add_argument("--pad_token_id", type=int, default=153478, help="(+) when --student_model holds no tokenizer")
     p.add_argument("--speech_bos_id", type=int, default=None, help="(+) id of <|semantic_token_start|> when no tokenizer dir")
     # train.py:585-594: a quantised teacher switches the trainer to DENSE distillation (train.py:74-79).  Here the
-    # teacher always stays bf16 in HBM (3.5 GB of 288); the flags keep their effect on the loss
+    # teacher always stays bf16 in HBM (3.5 GB of 288) under these two flags; they keep their effect on the loss
     p.add_argument("--load_teacher_in_4bit", action="store_true")
     p.add_argument("--load_teacher_in_8bit", action="store_true")
+    p.add_argument("--teacher_precision", choices=("bf16", "mxfp8"), default="bf16",
+                   help="(+) this build's 8-bit teacher: mxfp8 runs the frozen teacher's decoder projections as MXFP8 GEMMs "
+                        "(OCP Microscaling FP8, not bitsandbytes' int8); lm_head, attention and the residual stream stay bf16")
     # LoRA (train.py:180-202, :470-487): speech_distill_amd/lora.py, merged-weight form
     p.add_argument("--use_lora", action="store_true")
     p.add_argument("--lora_r", type=int, default=32)
@@ -122,6 +125,7 @@ def main():
     torch.cuda.set_device(dev)
     student, teacher = build_models(cfg, dev)
     teacher.eval().requires_grad_(False)               # train.py:165-169
+    teacher.set_inference_precision(cfg.teacher_precision)   # (+)
     if cfg.use_lora:                                   # train.py:180-203
         from speech_distill_amd import lora
         print("Applying LoRA to student model...")

@@ -59,6 +59,16 @@ class Varlen(C.Structure):  # include/sd_hip.h sd_varlen (packed documents witho
     _fields_ = [("cu_seqlens", C.c_void_p), ("n_seqs", C.c_int32), ("max_seqlen", C.c_int32), ("work", C.c_void_p)]
 
 
+class LayerMx(C.Structure):  # include/sd_hip.h sd_qwen3_layer_mx
+    _fields_ = [(n, C.c_void_p) for n in ("wqkv_q", "wqkv_scale", "wo_q", "wo_scale", "wgu_q", "wgu_scale", "wdown_q",
+                                          "wdown_scale", "q_gain", "k_gain")]
+
+
+class ParamsMx(C.Structure):  # include/sd_hip.h sd_qwen3_params_mx
+    _fields_ = [("embed", C.c_void_p), ("lm_head", C.c_void_p), ("final_norm", C.c_void_p),
+                ("layers_host", C.POINTER(LayerMx))]
+
+
 class Params(C.Structure):
     _fields_ = [("embed", C.c_void_p), ("lm_head", C.c_void_p), ("final_norm", C.c_void_p),
                 ("layers_host", C.POINTER(Layer))]
@@ -159,6 +169,15 @@ PROTOTYPES = {
                                             _vp, _vp, _vp, _i64, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _vp, _vp]),
     "sd_qwen3_backward": (_i, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(Params), _vp, _vp, _vp, _vp, _vp, _i64,
                                _vp, _vp, _i64, _i, _i, _i, _vp, STAGE_CB, _vp, _vp, _vp]),
+    "sd_mxfp8_quant": (_i, [_vp, _i64, _vp, _vp, _vp, _f, _i, _i, _vp]),
+    "sd_gemm_mxfp8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i64, _vp]),
+    "sd_gemm_mxfp8_swiglu": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "sd_qwen3_mx_supported": (_i, [C.POINTER(Dims)]),
+    "sd_qwen3_mx_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
+    "sd_qwen3_forward_mx": (_i, [C.POINTER(Dims), C.POINTER(ParamsMx), _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i,
+                                 _i, _vp]),
+    "sd_qwen3_forward_mx_varlen": (_i, [C.POINTER(Dims), C.POINTER(ParamsMx), _vp, C.POINTER(Varlen), _vp, _vp, _vp, _i64,
+                                        _vp, _vp, _i, _i, _i, _vp]),
 }
 
 

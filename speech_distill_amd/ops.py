@@ -714,3 +714,53 @@ def gemm_qkv_rope_rs(x, wqkv_folded, q_gain, k_gain, cos, sin, ssq, T, Hq, Hkv, 
     check(load_lib().sd_gemm_qkv_rope_rs(_p(x), _p(wqkv_folded), qkv.data_ptr(), qk.data_ptr(), _p(q_gain), _p(k_gain),
                                          _p(cos), _p(sin), _p(ssq), M, T, Hq, Hkv, K, eps, _stream()), "sd_gemm_qkv_rope_rs")
     return qkv, qk
+
+
+# ---- MXFP8 frozen teacher (include/sd_hip.h "MXFP8 frozen teacher"): e4m3fn elements + one E8M0 scale byte per 32 along K
+def mxfp8_quant(x, want_rstd=False, eps=1e-6):
+    """bf16 [M,K] (rows may be strided) -> (q uint8 [M,K] holding e4m3fn, scale uint8 [M,K/32] holding E8M0[, rstd fp32 [M]])."""
+    if not x.is_cuda:
+        raise RuntimeError("speech_distill_amd: x must be a GPU tensor (no CPU fallback)")
+    if x.dtype != torch.bfloat16 or x.dim() != 2 or x.stride(1) != 1:
+        raise TypeError("mxfp8_quant: expected a 2-D bf16 tensor with unit column stride")
+    M, K = x.shape
+    q = torch.empty(M, K, dtype=torch.uint8, device=x.device)
+    s = torch.empty(M, K // 32, dtype=torch.uint8, device=x.device)
+    rstd = torch.empty(M, dtype=torch.float32, device=x.device) if want_rstd else None
+    check(load_lib().sd_mxfp8_quant(x.data_ptr(), x.stride(0), q.data_ptr(), s.data_ptr(), _p(rstd), eps, M, K, _stream()),
+          "sd_mxfp8_quant")
+    return (q, s, rstd) if want_rstd else (q, s)
+
+
+def gemm_mxfp8(a_q, a_scale, b_q, b_scale, rowscale=None, residual=None, out=None):
+    """bf16 [M,N] = bf16(rowscale[m] * (A . B^T) + residual); A [M,K], B [N,K] as (e4m3 bytes, E8M0 scale bytes)."""
+    for t, n in ((a_q, "a_q"), (a_scale, "a_scale"), (b_q, "b_q"), (b_scale, "b_scale")):
+        _need(t, torch.uint8, n)
+    M, K = a_q.shape
+    N = b_q.shape[0]
+    if b_q.shape[1] != K or tuple(a_scale.shape) != (M, K // 32) or tuple(b_scale.shape) != (N, K // 32):
+        raise ValueError("gemm_mxfp8: operand / scale shapes do not match")
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=a_q.device)
+    r = None if residual is None else _need(residual, torch.bfloat16, "residual")
+    rs = None if rowscale is None else _need(rowscale, torch.float32, "rowscale")
+    check(load_lib().sd_gemm_mxfp8(a_q.data_ptr(), a_scale.data_ptr(), b_q.data_ptr(), b_scale.data_ptr(), out.data_ptr(),
+                                   _p(r), _p(rs), M, N, K, out.stride(0), 0 if r is None else r.stride(0), _stream()),
+          "sd_gemm_mxfp8")
+    return out
+
+
+def gemm_mxfp8_swiglu(a_q, a_scale, wgu_q, wgu_scale, rowscale=None):
+    """(act_q, act_scale): the MXFP8 image of bf16(silu(g) * u), g | u = bf16(rowscale * (A . Wgu^T)); no bf16 act."""
+    for t, n in ((a_q, "a_q"), (a_scale, "a_scale"), (wgu_q, "wgu_q"), (wgu_scale, "wgu_scale")):
+        _need(t, torch.uint8, n)
+    M, K = a_q.shape
+    I = wgu_q.shape[0] // 2
+    if wgu_q.shape[1] != K or tuple(a_scale.shape) != (M, K // 32) or tuple(wgu_scale.shape) != (2 * I, K // 32):
+        raise ValueError("gemm_mxfp8_swiglu: operand / scale shapes do not match")
+    act_q = torch.empty(M, I, dtype=torch.uint8, device=a_q.device)
+    act_s = torch.empty(M, I // 32, dtype=torch.uint8, device=a_q.device)
+    rs = None if rowscale is None else _need(rowscale, torch.float32, "rowscale")
+    check(load_lib().sd_gemm_mxfp8_swiglu(a_q.data_ptr(), a_scale.data_ptr(), wgu_q.data_ptr(), wgu_scale.data_ptr(), _p(rs),
+                                          act_q.data_ptr(), act_s.data_ptr(), M, I, K, _stream()), "sd_gemm_mxfp8_swiglu")
+    return act_q, act_s

@@ -227,6 +227,10 @@ class HipQwen3ForCausalLM(nn.Module):
         # the folded copies are rebuilt whenever the flat parameter buffer has been written to (version counter).
         self.fold_norm_gains = True
         self._folded = None  # (flat._version, folded weight buffer, Params, Layers)
+        # Opt-in inference precision of a FROZEN model (set_inference_precision): "mxfp8" runs the four projections of
+        # every decoder layer as MXFP8 x MXFP8 GEMMs on weights quantised once (sd_qwen3_forward_mx).
+        self.inference_precision = "bf16"
+        self._mx = None      # (ParamsMx, LayerMx array, the quantised weight tensors they point into)
         self._lora = None    # lora.LoraState once lora.get_lora_model() has attached an adapter (train.py:180-202)
         # Stage-1 alignment (stage1.freeze_model_weights, reference stage1.py:29-73): the first vocabulary row whose
         # embedding / lm_head gradient is kept.  None = normal training (every gradient, labels ignored by forward).
@@ -238,6 +242,7 @@ class HipQwen3ForCausalLM(nn.Module):
     def _apply(self, fn, recurse=True):
         """``.to(device)`` / ``.cuda()`` (HF Trainer moves the model to ``args.device``): move the FLAT buffers and
         re-point the HF-named parameters at them, so they stay views of one buffer.  Other dtypes are refused."""
+        self._mx = None  # the quantised teacher weights live on the old device / belong to the old buffer
         new_flat = fn(self.flat)
         if new_flat.dtype != torch.bfloat16:
             raise TypeError("HipQwen3ForCausalLM holds bf16 parameters (train.py:174 loads the student in bf16)")
@@ -298,6 +303,7 @@ class HipQwen3ForCausalLM(nn.Module):
     @torch.no_grad()
     def init_weights(self, seed=0, std=0.02):
         """HF default init: N(0, std) matrices, unit norm gains; one CPU generator -> same on every rank."""
+        self._mx = None
         g = torch.Generator().manual_seed(seed)
         for name, p in self._params.items():
             if p.dim() == 1:
@@ -312,6 +318,7 @@ class HipQwen3ForCausalLM(nn.Module):
     @torch.no_grad()
     def load_hf_state_dict(self, sd):
         """Copy tensors from a dict with HF key names (fp32 or bf16, any device)."""
+        self._mx = None
         for name, p in self._params.items():
             if name == "lm_head.weight" and name not in sd:
                 continue
@@ -343,6 +350,7 @@ class HipQwen3ForCausalLM(nn.Module):
         ``_IncompatibleKeys``; a tied ``lm_head.weight`` is neither required nor, when present, unexpected
         (it must then equal the embedding, which is what gets loaded)."""
         from torch.nn.modules.module import _IncompatibleKeys
+        self._mx = None
         if self._lora is not None:
             return self._lora.load_state_dict(state_dict, strict)
         tied = self._tied_head_key()
@@ -534,7 +542,97 @@ class HipQwen3ForCausalLM(nn.Module):
         self._folded = (ver, buf, params, layers)
         return params
 
+    # ------------------------------------------------------------------------- MXFP8 inference (frozen teacher)
+    def _check_mx(self):
+        if self._lora is not None:
+            raise ValueError('inference precision "mxfp8" is for a frozen model; this one carries a LoRA adapter')
+        if any(p.requires_grad for p in self._params.values()):
+            raise ValueError('inference precision "mxfp8" is for a frozen model (call requires_grad_(False) first): '
+                             "its weights are quantised once, trainable parameters would go stale")
+        if not load_lib().sd_qwen3_mx_supported(C.byref(self._cdims)):
+            raise ValueError('inference precision "mxfp8" needs head_dim 128 and hidden_size, intermediate_size multiples '
+                             f"of 128 (got hidden {self.dims.hidden_size}, intermediate {self.dims.intermediate_size})")
+
+    def set_inference_precision(self, precision):
+        """"bf16" (default) or "mxfp8": how the no-grad forward of this FROZEN model runs its decoder projections.
+        "mxfp8" (the teacher's 8-bit mode of this build; a different format from bitsandbytes' LLM.int8()): q|k|v, o,
+        gate|up and down run as MXFP8 x MXFP8 -> fp32 GEMMs (OCP Microscaling FP8: e4m3 elements, one power-of-two scale per
+        32 along K) on weights quantised once; the residual stream, attention, q/k-norm + RoPE, the final norm, the
+        embedding and the lm_head stay bf16.  The quantised weights are dropped by ``.to()``, ``load_state_dict``,
+        ``load_hf_state_dict``, ``init_weights`` and this call; a frozen model's parameters are not expected to be written
+        any other way."""
+        if precision not in ("bf16", "mxfp8"):
+            raise ValueError(f'inference precision must be "bf16" or "mxfp8", got {precision!r}')
+        if precision == "mxfp8":
+            self._check_mx()
+        self.inference_precision = precision
+        self._mx = None
+        return self
+
+    @torch.no_grad()
+    def _mx_params(self):
+        """sd_qwen3_params_mx of this model: per layer bf16(W diag(g)) exactly as ``_folded_params`` folds, then
+        sd_mxfp8_quant; built once and kept until invalidated."""
+        self._check_mx()
+        if self._mx is not None and self._mx[2][0].device == self.flat.device:
+            return self._mx[0]
+        from . import ops
+        d = self.dims
+        h, I = d.hidden_size, d.intermediate_size
+        nq, ng = (d.q_dim + 2 * d.kv_dim) * h, 2 * I * h
+        keep = []
+        layers = (_lib.LayerMx * d.num_hidden_layers)()
+        base = self.flat.data_ptr()
+
+        def quant(t):
+            q, s = ops.mxfp8_quant(t)
+            keep.extend((q, s))
+            return q.data_ptr(), s.data_ptr()
+        for l in range(d.num_hidden_layers):
+            p = f"model.layers.{l}."
+            o, _, _ = self._slices[p + "self_attn.q_proj.weight"]
+            wqkv = self.flat[o:o + nq].view(-1, h)       # q | k | v rows are contiguous in the flat layout
+            o, _, _ = self._slices[p + "mlp.gate_proj.weight"]
+            wgu = self.flat[o:o + ng].view(-1, h)        # gate | up likewise
+            fq = (wqkv.float() * self._params[p + "input_layernorm.weight"].float()[None, :]).to(torch.bfloat16)
+            fg = (wgu.float() * self._params[p + "post_attention_layernorm.weight"].float()[None, :]).to(torch.bfloat16)
+            layers[l].wqkv_q, layers[l].wqkv_scale = quant(fq)
+            layers[l].wgu_q, layers[l].wgu_scale = quant(fg)
+            layers[l].wo_q, layers[l].wo_scale = quant(self._params[p + "self_attn.o_proj.weight"].data)
+            layers[l].wdown_q, layers[l].wdown_scale = quant(self._params[p + "mlp.down_proj.weight"].data)
+            layers[l].q_gain = base + self._slices[p + "self_attn.q_norm.weight"][0] * 2
+            layers[l].k_gain = base + self._slices[p + "self_attn.k_norm.weight"][0] * 2
+        params = _lib.ParamsMx()
+        params.embed, params.lm_head, params.final_norm = self._cparams.embed, self._cparams.lm_head, self._cparams.final_norm
+        params.layers_host = C.cast(layers, C.POINTER(_lib.LayerMx))
+        self._mx = (params, layers, keep)
+        return params
+
+    def _run_forward_mx(self, input_ids, kv_len, rows, concurrent, packed):
+        lib = load_lib()
+        B, T = input_ids.shape
+        dev = input_ids.device
+        cos, sin = (packed.cos, packed.sin) if packed is not None else self._tables(T, dev)
+        params = self._mx_params()
+        nbytes = lib.sd_qwen3_mx_acts_bytes(C.byref(self._cdims), *((1, packed.M) if packed is not None else (B, T)))
+        acts = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        n_rows = 0 if rows is None else rows.numel()
+        logits = torch.empty(*((B, T) if rows is None else (n_rows,)), self.dims.vocab_size, dtype=torch.bfloat16, device=dev)
+        flags = FWD_CONCURRENT if concurrent else 0
+        if packed is not None:
+            check(lib.sd_qwen3_forward_mx_varlen(C.byref(self._cdims), C.byref(params), input_ids.data_ptr(),
+                                                 C.byref(packed.desc), cos.data_ptr(), sin.data_ptr(), acts.data_ptr(), nbytes,
+                                                 logits.data_ptr(), _p(rows), n_rows, packed.M, flags, _stream()),
+                  "sd_qwen3_forward_mx_varlen")
+        else:
+            check(lib.sd_qwen3_forward_mx(C.byref(self._cdims), C.byref(params), input_ids.data_ptr(), _p(kv_len),
+                                          cos.data_ptr(), sin.data_ptr(), acts.data_ptr(), nbytes, logits.data_ptr(), _p(rows),
+                                          n_rows, B, T, flags, _stream()), "sd_qwen3_forward_mx")
+        return logits, acts
+
     def _run_forward(self, input_ids, kv_len, save, rows=None, concurrent=False, packed=None):
+        if save == SAVE_NONE and self.inference_precision == "mxfp8":
+            return self._run_forward_mx(input_ids, kv_len, rows, concurrent, packed)
         lib = load_lib()
         B, T = input_ids.shape
         dev = input_ids.device
