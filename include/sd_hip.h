@@ -169,7 +169,15 @@ int sd_rows_scatter(const void* src, const int64_t* rows, void* dst, int n, int 
 
 /* ---- causal GQA flash attention, head_dim 128 (flash_attn via train.py:160,177; maths HF:185-207).
  * q [B*T, ldq] head hq at column hq*128; k, v likewise per kv head; o [B*T, ldo]; lse fp32 [B,Hq,T].
- * kv_len (int32 [B], nullable): keys >= kv_len[b] are masked (right padding). */
+ * kv_len (int32 [B], nullable): keys >= kv_len[b] are masked (right padding).  Pinned by tests/test_gpu_attn_edges.py:
+ *   - kv_len[b] is clamped to [1, T] (0 or a negative value behaves as 1: key 0 stays visible; NULL is T);
+ *   - masked key rows of k and v may hold any FINITE values: they change no output bit.  Not NaN / inf: masked
+ *     probabilities are exact zeros that still go through the P.V product, and 0 * inf is NaN;
+ *   - query rows >= kv_len[b] are computed like any other row (they attend to the keys < kv_len[b]): o, lse and dq are
+ *     written for all B*T rows;
+ *   - dk and dv rows >= kv_len[b] are written, as zeros;
+ *   - every output element of the head columns of rows [0, B*T) is stored (outputs need no zero fill), nothing else is;
+ *   - the backward reads o and d_o with ONE row stride, ldo. */
 int sd_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* kv_len, int64_t ldq,
                 int64_t ldk, int64_t ldv, int64_t ldo, int B, int T, int Hq, int Hkv, int head_dim, float scale,
                 void* stream);

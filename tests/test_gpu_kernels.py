@@ -4,6 +4,9 @@ golden fixtures generated from the reference, and a plain fp32/fp64 torch statem
 Tolerances (stated per test): bf16 kernels are compared with an fp64 evaluation of the SAME bf16
 inputs; one bf16 rounding of the output is 2^-9 relative (3.9e-3 max), so max-norm bounds are a few
 times that and rms bounds ~2e-3.  Integer-valued inputs must come out exact.
+Exception: oracle.qwen3.attention takes its softmax in fp32 whatever the input type (the goldens pin that), so
+test_attention_fwd_bwd compares with fp64 matrix products around an fp32 softmax; the attention reference that is fp64
+throughout is tests/attn_ref.py (tests/test_gpu_attn_edges.py).
 """
 import glob
 import os
@@ -643,6 +646,8 @@ def test_embedding_bwd_many_duplicates_fixed_order(ops):
                                             (1, 512, 4, 2, False), (1, 40, 2, 1, False), (2, 200, 8, 4, True),
                                             (3, 72, 8, 8, True), (4, 330, 4, 2, False)])
 def test_attention_fwd_bwd(ops, O, B, T, Hq, Hkv, pad):
+    """Against oracle.qwen3.attention on double inputs: fp64 products, but its softmax runs in fp32 (not an fp64 evaluation;
+    one norm over the whole tensor -- the per-row, fp64-throughout comparison is tests/test_gpu_attn_edges.py)."""
     g = torch.Generator().manual_seed(T + Hq)
     M = B * T
     q, k, v = (bf(torch.randn(M, h * 128, generator=g)) for h in (Hq, Hkv, Hkv))
