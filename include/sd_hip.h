@@ -482,6 +482,88 @@ int sd_qwen3_forward_mx_varlen(const sd_qwen3_dims* d, const sd_qwen3_params_mx*
                                int64_t acts_bytes, void* logits, const int64_t* head_rows, int n_head_rows, int M,
                                int flags, void* stream);
 
+/* ---- KV-cache generation (the reference's inference engine: soulxpodcast/engine/llm_engine.py:37-76 decodes one token per
+ * step over a KV cache with the sampling recipe of soulxpodcast/config.py:107-118 and the repetition-aware rule of
+ * soulxpodcast/models/modules/sampler.py:136-189; the attention maths is HF:185-207 for a single query row).
+ * Cache: ONE caller-owned bf16 buffer [L][2][B][cap][Hkv*128] of sd_kvcache_bytes(d, B, cap) bytes -- per layer a K plane
+ * then a V plane, each [B][cap][Hkv*128] with rows in the [token][kv head * 128] layout sd_attn_fwd reads.  head_dim 128
+ * only (SD_ERR_UNSUPPORTED otherwise).  The entries below take the two planes of one layer.  Device-side lengths and
+ * positions are clamped before any address is formed: nothing is read or written outside [0, cap) of a cache row. */
+int64_t sd_kvcache_bytes(const sd_qwen3_dims* d, int B, int cap);
+/* prefill sink (HF:252-257 outputs kept as past_key_values): for t < kv_len[b] (clamped to [0, T]; NULL = T) copies the
+ * normalised + rotated K of qk [B*T,(Hq+Hkv)*128] and the raw V of qkv [B*T,(Hq+2Hkv)*128] into slot t; writes nothing
+ * else.  T <= cap. */
+int sd_kvcache_store(const void* qk, const void* qkv, void* k_plane, void* v_plane, const int32_t* kv_len, int B, int T,
+                     int cap, int Hq, int Hkv, void* stream);
+/* rows[b] = b*T + clamp(kv_len[b], 1, T) - 1 (int64 [B]; kv_len NULL = T): the last valid row of every right-padded
+ * sequence, i.e. the row whose logits predict the first new token (HF generate reads logits[:, -1] of a left-padded
+ * batch, sampler.py:136). */
+int sd_last_rows(const int32_t* kv_len, int64_t* rows, int B, int T, void* stream);
+/* decode twin of sd_qknorm_rope_fwd (HF:252-257) for ONE new token per sequence: qkv [B,(Hq+2Hkv)*128] raw; cos/sin bf16
+ * [cap,128]; pos int32 [B] (device) = tokens already cached = the new token's position.  q_out [B,Hq*128] gets the
+ * normalised + rotated q, cache slot pos[b] the normalised + rotated K and the raw V; q and K are bit-identical to
+ * sd_qknorm_rope_fwd at that position.  A row with pos[b] outside [0, cap) writes nothing to the cache (its q_out row is
+ * rotated by the clamped position). */
+int sd_qknorm_rope_append(const void* qkv, const void* q_gain, const void* k_gain, const void* cos_tab, const void* sin_tab,
+                          const int32_t* pos, void* q_out, void* k_plane, void* v_plane, int B, int cap, int Hq, int Hkv,
+                          float eps, void* stream);
+/* single-token attention over the cache (HF:185-207 with one query row; flash-decoding split-KV): q [B,Hq*128], o
+ * [B,Hq*128] bf16, lse fp32 [B,Hq] nullable (natural log).  Sequence b attends to keys [0, n), n = len[b] + len_add
+ * clamped to [0, min(cap, max_len)]; len int32 [B] in device memory.  n == 0: a zero row (lse -inf).
+ * Two launches: every (partition of 256 keys, kv head, sequence) with a visible key writes fp32 partials (max, sum, 128
+ * accumulators per query head of the group) to `workspace` (sd_attn_decode_workspace_bytes(B, Hq, cap)); the second merges
+ * the partitions of a row in increasing index order.  max_len: a HOST upper bound of every n (longest prompt + steps
+ * taken) that sizes the grid.  Partition size and merge order are fixed, so the output bits depend on n and the data
+ * only -- not on cap, max_len or the number of partitions launched.  Cache slots >= n may hold any finite values: they
+ * are never read.  Hq / Hkv in {1, 2, 4}. */
+int64_t sd_attn_decode_workspace_bytes(int B, int Hq, int cap);
+int sd_attn_decode(const void* q, const void* k_plane, const void* v_plane, void* o, float* lse, const int32_t* len,
+                   int len_add, void* workspace, int64_t workspace_bytes, int B, int cap, int max_len, int Hq, int Hkv,
+                   int head_dim, float scale, void* stream);
+/* one sampling step for B rows (sampler.py:136-189; HF logits_process.py in generate's order):
+ *   1 repetition penalty over the row's GENERATED tokens seq[b, prompt_len[b] .. len[b]) only, each distinct token once:
+ *     score < 0 ? score * p : score / p;   2 EOS = -inf while fewer than min_new_tokens were generated;   3 / temperature;
+ *   4 top-k (1..128; the indices come from sd_logsoftmax_topk over the processed fp32 row, the scores are gathered from
+ *     that row);   5 top-p on the renormalised top-k distribution: walking up from the smallest probability a candidate
+ *     is dropped while the cumulative mass is <= 1 - top_p, the largest always stays;   6 inverse-CDF draw over the
+ *     survivors in descending order (ties: lowest index first) with the caller's uniform.
+ *   do_sample = 0: arg-max of the processed scores, ties to the lowest index.
+ *   use_ras (sampler.py:142-148): a candidate is drawn with u[b,0]; if it occurs at least ras_min_count - 1 times in the
+ *     last win_size tokens of seq[b, 0 .. len[b]) (prompt included; ras_min_count = ceil(win_size * tau_r), so that
+ *     count + 1 >= win_size * tau_r) the token is drawn with u[b,1] from softmax(RAW logits) over the whole vocabulary,
+ *     else with u[b,1] from the processed distribution.  Without use_ras the draw uses u[b,1].
+ *   top_k = 0 (only with top_p = 1 and no RAS): the whole processed row is the distribution.  Full-vocabulary draws walk
+ *     the vocabulary in index order: fp32 sums in blocks of 1024 columns, a scan of the block sums, a scan in the block.
+ * logits bf16 [B, row_stride] (V columns used, never written); uniforms fp32 [B,2] in [0,1); seq int64 [B,cap];
+ * prompt_len, len int32 [B]; finished uint8 [B].  An unfinished row gets its token at seq[b, len[b]], len[b] += 1,
+ * next_out[b] = token, pos_out[b] = its index, finished[b] = 1 on EOS (or when the row is full).  A finished row gets
+ * next_out[b] = pad_token_id and nothing else changes.  eos_token_id < 0: none. */
+typedef struct {
+  int32_t do_sample, top_k, use_ras, win_size, ras_min_count, min_new_tokens, eos_token_id, pad_token_id;
+  float temperature, top_p, repetition_penalty, pad_;
+} sd_sample_params;
+int64_t sd_sample_workspace_bytes(int B, int V);
+int sd_sample_step(const void* logits, int64_t row_stride, const float* uniforms, int64_t* seq, const int32_t* prompt_len,
+                   int32_t* len, uint8_t* finished, int64_t* next_out, int32_t* pos_out, void* workspace,
+                   int64_t workspace_bytes, const sd_sample_params* sp, int B, int V, int cap, void* stream);
+/* The runner over the cache (unfolded bf16 weights only).
+ * sd_qwen3_prefill: the SD_SAVE_NONE forward of sd_qwen3_forward_rows with sd_kvcache_store after each layer's q|k|v step
+ *   and the lm_head on the last valid row of each sequence (sd_last_rows, on the device): logits bf16 [B,V], bit-identical
+ *   to sd_qwen3_forward_rows on those rows.  cos/sin [T,128]; acts of sd_qwen3_prefill_acts_bytes(d, B, T); T <= cap.
+ * sd_qwen3_decode_step: ids int64 [B] (device: the sampler's next_out), pos int32 [B] (device: the sampler's pos_out, the
+ *   tokens already cached per row), max_len = host upper bound of every pos[b] + 1; cos/sin [cap,128].  Per layer: RMSNorm,
+ *   q|k|v GEMM, sd_qknorm_rope_append, sd_attn_decode (len = pos + 1), o GEMM + residual, RMSNorm, gate|up + SwiGLU
+ *   (sd_gemm_swiglu, else GEMM + sd_swiglu_fwd), down GEMM + residual; then the final norm and the lm_head:
+ *   logits bf16 [B,V].  acts of sd_qwen3_decode_acts_bytes(d, B, cap). */
+int64_t sd_qwen3_prefill_acts_bytes(const sd_qwen3_dims* d, int B, int T);
+int sd_qwen3_prefill(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* kv_len,
+                     const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes, void* cache,
+                     int64_t cache_bytes, int cap, void* logits, int B, int T, void* stream);
+int64_t sd_qwen3_decode_acts_bytes(const sd_qwen3_dims* d, int B, int cap);
+int sd_qwen3_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* pos,
+                         int max_len, const void* cos_tab, const void* sin_tab, void* cache, int64_t cache_bytes, int cap,
+                         void* acts, int64_t acts_bytes, void* logits, int B, void* stream);
+
 /* ---- stream placement.  HIP multiplexes streams onto a few hardware queues (4 by default); streams that share a
  * queue never overlap.  Measures, with a `spin_us`-long busy-wait kernel on stream_a and an empty one on stream_b,
  * whether work on b runs while a is busy: *overlap = 1/0.  Synchronises both streams (a calibration call, made once

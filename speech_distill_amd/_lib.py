@@ -69,6 +69,12 @@ class ParamsMx(C.Structure):  # include/sd_hip.h sd_qwen3_params_mx
                 ("layers_host", C.POINTER(LayerMx))]
 
 
+class SampleParams(C.Structure):  # include/sd_hip.h sd_sample_params
+    _fields_ = [(n, C.c_int32) for n in ("do_sample", "top_k", "use_ras", "win_size", "ras_min_count", "min_new_tokens",
+                                         "eos_token_id", "pad_token_id")] + \
+               [(n, C.c_float) for n in ("temperature", "top_p", "repetition_penalty", "pad_")]
+
+
 class Params(C.Structure):
     _fields_ = [("embed", C.c_void_p), ("lm_head", C.c_void_p), ("final_norm", C.c_void_p),
                 ("layers_host", C.POINTER(Layer))]
@@ -176,6 +182,21 @@ PROTOTYPES = {
     "sd_qwen3_mx_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
     "sd_qwen3_forward_mx": (_i, [C.POINTER(Dims), C.POINTER(ParamsMx), _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i,
                                  _i, _vp]),
+    "sd_kvcache_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
+    "sd_kvcache_store": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "sd_last_rows": (_i, [_vp, _vp, _i, _i, _vp]),
+    "sd_qknorm_rope_append": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
+    "sd_attn_decode_workspace_bytes": (_i64, [_i, _i, _i]),
+    "sd_attn_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _i, _i, _i, _f, _vp]),
+    "sd_sample_workspace_bytes": (_i64, [_i, _i]),
+    "sd_sample_step": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(SampleParams), _i, _i, _i,
+                            _vp]),
+    "sd_qwen3_prefill_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
+    "sd_qwen3_prefill": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i, _vp, _i, _i,
+                              _vp]),
+    "sd_qwen3_decode_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
+    "sd_qwen3_decode_step": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _i, _vp, _vp, _vp, _i64, _i, _vp, _i64, _vp,
+                                  _i, _vp]),
     "sd_qwen3_forward_mx_varlen": (_i, [C.POINTER(Dims), C.POINTER(ParamsMx), _vp, C.POINTER(Varlen), _vp, _vp, _vp, _i64,
                                         _vp, _vp, _i, _i, _i, _vp]),
 }

@@ -1,0 +1,627 @@
+// KV-cache generation for gfx950: cache store / append, single-token (decode) attention, and the on-GPU sampler.
+//
+// What the reference runs for this (its inference engine, not the training path):
+//   soulxpodcast/engine/llm_engine.py:37-76 ... the decode loop over a KV cache (vLLM / HF generate underneath)
+//   soulxpodcast/config.py:107-118 ............. SamplingParams (temperature 0.6, top-k 100, top-p 0.9, repetition penalty
+//                                                1.25, min/max tokens, RAS window 25 / threshold 0.2)
+//   soulxpodcast/models/modules/sampler.py:136-189 the HF sampling loop with repetition-aware sampling (VALL-E 2)
+// and, inside HF, transformers/generation/logits_process.py (RepetitionPenalty, MinNewTokensLength, Temperature, TopK,
+// TopP) whose arithmetic the sampler restates.
+//
+// Cache layout: one caller-owned bf16 buffer [L][2][B][cap][Hkv*128] (K plane, V plane per layer); a row is
+// [kv head][128], the layout the attention kernels read.  Every kernel below clamps the device-side lengths it is handed
+// into [0, cap] before it forms an address: no access leaves [0, cap) of a cache row whatever those arrays hold.
+// All stores are ordinary vector stores from plain C++.
+#include <math.h>
+#include <stdlib.h>
+#include "sd_common.cuh"
+#include "../../include/sd_hip.h"
+#include "sd_prof.h"
+
+#define ST ((hipStream_t)stream)
+
+namespace {
+
+constexpr int kPart = 256;  // keys per split-KV partition (fixed: the output bits must not depend on a launch choice)
+constexpr int kRec = 132;   // floats of one partial record: max, sum, 2 pad, 128 accumulators (16-byte aligned rows)
+constexpr float kNegBig = -1.0e30f;  // "no key yet": finite, so that max - max never forms inf - inf
+
+SD_DEV void unpack8(bf16x8 v, float* f) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) f[e] = (float)v[e];
+}
+SD_DEV bf16x8 pack8(const float* f) {
+  bf16x8 v;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] = (bf16)f[e];
+  return v;
+}
+SD_DEV bf16x8 zero8() {
+  bf16x8 v;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] = (bf16)0.f;
+  return v;
+}
+SD_DEV int clampi(int x, int lo, int hi) { return x < lo ? lo : (x > hi ? hi : x); }
+
+// ------------------------------------------------------------------------------------------- cache store (prefill)
+// One thread per 16 bytes of a K or V row of the layer: rows t < kv_len[b] go to cache slot t, nothing else is written.
+__global__ __launch_bounds__(256) void kvcache_store_kernel(const bf16* __restrict__ qk, const bf16* __restrict__ qkv,
+                                                            bf16* __restrict__ kp, bf16* __restrict__ vp,
+                                                            const int32_t* __restrict__ kv_len, int B, int T, int cap,
+                                                            int Hq, int Hkv) {
+  const int cpr = Hkv * 16;  // 16-byte chunks per row
+  const long total = 2l * B * T * cpr;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int c = (int)(idx % cpr);
+  const long r = idx / cpr;
+  const int which = (int)(r / ((long)B * T));  // 0 = K, 1 = V
+  const int m = (int)(r % ((long)B * T));
+  const int b = m / T, t = m % T;
+  const int lim = T < cap ? T : cap;
+  const int n = kv_len ? clampi(kv_len[b], 0, lim) : lim;
+  if (t >= n) return;
+  const long dst = ((long)b * cap + t) * (Hkv * 128) + c * 8;
+  if (which == 0) *(bf16x8*)(kp + dst) = *(const bf16x8*)(qk + (long)m * (Hq + Hkv) * 128 + Hq * 128 + c * 8);
+  else *(bf16x8*)(vp + dst) = *(const bf16x8*)(qkv + (long)m * (Hq + 2 * Hkv) * 128 + (Hq + Hkv) * 128 + c * 8);
+}
+
+// last valid row of every sequence: rows[b] = b*T + clamp(kv_len[b], 1, T) - 1 (the clamp of sd_attn_fwd)
+__global__ void last_rows_kernel(const int32_t* __restrict__ kv_len, int64_t* __restrict__ rows, int B, int T) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int n = kv_len ? clampi(kv_len[b], 1, T) : T;
+  rows[b] = (int64_t)b * T + n - 1;
+}
+
+// ------------------------------------------------------------------------------- q/k norm + RoPE + append (decode)
+// The arithmetic of qknorm_rope_fwd_kernel (sd_elementwise.hip), statement for statement, for ONE token per sequence
+// whose position is pos[b]: q goes to q_out, k and the raw v into cache slot pos[b].  A head vector of 128 bf16 is owned
+// by 16 lanes; every lane runs the norm / rotation (the DPP row operations want whole rows active), the head kind only
+// picks the store.
+__global__ __launch_bounds__(256) void qknorm_rope_append_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ qw,
+                                                                 const bf16* __restrict__ kw, const bf16* __restrict__ cosb,
+                                                                 const bf16* __restrict__ sinb,
+                                                                 const int32_t* __restrict__ pos, bf16* __restrict__ q_out,
+                                                                 bf16* __restrict__ kp, bf16* __restrict__ vp, int B,
+                                                                 int cap, int Hq, int Hkv, float eps) {
+  const int lane = lane_id();
+  const int sub = lane >> 4, j = lane & 15;
+  const int nh = Hq + 2 * Hkv;
+  const long total = (long)B * nh;
+  const long idx = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + sub;
+  const bool ok = idx < total;
+  const long id = ok ? idx : total - 1;
+  const int b = (int)(id / nh), hh = (int)(id % nh);
+  const int p = pos[b];
+  const bool inb = p >= 0 && p < cap;
+  const int t = clampi(p, 0, cap - 1);
+  const bf16x8 raw = *(const bf16x8*)(qkv + (long)b * nh * 128 + hh * 128 + j * 8);
+  float f[8], g[8], cs[8], sn[8];
+  unpack8(raw, f);
+  float ss = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) ss += f[e] * f[e];
+  ss = row16_sum(ss);
+  const float rs = rsqrtf(ss * (1.f / 128.f) + eps);
+  unpack8(*(const bf16x8*)((hh < Hq ? qw : kw) + j * 8), g);
+  unpack8(*(const bf16x8*)(cosb + (long)t * 128 + j * 8), cs);
+  unpack8(*(const bf16x8*)(sinb + (long)t * 128 + j * 8), sn);
+  float o[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float n = (float)(bf16)(g[e] * (float)(bf16)(f[e] * rs));  // normed value as HF holds it (bf16)
+    const float pr = row16_xor8(n);
+    const float rot = (j < 8) ? -pr : pr;
+    o[e] = n * cs[e] + rot * sn[e];
+  }
+  if (!ok) return;
+  const long slot = ((long)b * cap + t) * (Hkv * 128);
+  if (hh < Hq) *(bf16x8*)(q_out + (long)b * Hq * 128 + hh * 128 + j * 8) = pack8(o);
+  else if (hh < Hq + Hkv) { if (inb) *(bf16x8*)(kp + slot + (hh - Hq) * 128 + j * 8) = pack8(o); }
+  else if (inb) *(bf16x8*)(vp + slot + (hh - Hq - Hkv) * 128 + j * 8) = raw;
+}
+
+// ------------------------------------------------------------------------------------------------ decode attention
+// Phase 1.  One workgroup = (partition of 256 keys, kv head, sequence), serving the G query heads of the group.  A key
+// row (128 bf16 = 256 bytes) is read by a 16-lane group with one 16-byte load per lane, straight into registers; the 16
+// groups of the workgroup take keys base + 16 i + group, 4 keys per trip with the 8 loads of the trip issued together.
+// Scores: fp32 FMAs on the vector ALU, summed over the 16 lanes by DPP; the online softmax (log2 domain) and the 8 V
+// columns a lane owns stay in registers per group, and the 16 group states are merged in group order through LDS.
+// Keys >= n are never loaded and get probability exactly 0.
+template <int G>
+__global__ __launch_bounds__(256) void attn_decode_part_kernel(const bf16* __restrict__ q, const bf16* __restrict__ kp,
+                                                               const bf16* __restrict__ vp, float* __restrict__ ws,
+                                                               const int32_t* __restrict__ len, int len_add, int cap,
+                                                               int max_len, int Hq, int Hkv, int pstride,
+                                                               float scale_log2) {
+  __shared__ __attribute__((aligned(16))) float sh[16][G][kRec];
+  const int p = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
+  const int n = clampi(len[b] + len_add, 0, cap < max_len ? cap : max_len);
+  if (p * kPart >= n) return;  // block-uniform: this partition holds no visible key
+  const int lane = lane_id(), j = lane & 15;
+  const int sg = (threadIdx.x >> 6) * 4 + (lane >> 4);
+  const int KD = Hkv * 128;
+  float qf[G][8], m[G], l[G], acc[G][8];
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    unpack8(*(const bf16x8*)(q + (long)b * Hq * 128 + (hk * G + g) * 128 + j * 8), qf[g]);
+    m[g] = kNegBig;
+    l[g] = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[g][e] = 0.f;
+  }
+  const long off = (long)b * cap * KD + hk * 128 + j * 8;
+  const bf16* kb = kp + off;
+  const bf16* vb = vp + off;
+  for (int it = 0; it < 16; it += 4) {
+    if (p * kPart + it * 16 >= n) break;  // block-uniform
+    bf16x8 kv[4], vv[4];
+    bool okk[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int key = p * kPart + (it + u) * 16 + sg;
+      okk[u] = key < n;
+      kv[u] = zero8();
+      vv[u] = zero8();
+      if (okk[u]) {
+        kv[u] = *(const bf16x8*)(kb + (long)key * KD);
+        vv[u] = *(const bf16x8*)(vb + (long)key * KD);
+      }
+    }
+    float s[G][4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      float kf[8];
+      unpack8(kv[u], kf);
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        float d = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) d += qf[g][e] * kf[e];
+        d = row16_sum(d);
+        s[g][u] = okk[u] ? d * scale_log2 : -INFINITY;
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const float mn = fmaxf(fmaxf(m[g], fmaxf(s[g][0], s[g][1])), fmaxf(s[g][2], s[g][3]));
+      const float c = exp2f(m[g] - mn);
+      l[g] *= c;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[g][e] *= c;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const float pu = exp2f(s[g][u] - mn);  // masked key: exp2(-inf) = 0
+        float vf[8];
+        unpack8(vv[u], vf);
+        l[g] += pu;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[g][e] += pu * vf[e];
+      }
+      m[g] = mn;
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    if (j == 0) { sh[sg][g][0] = m[g]; sh[sg][g][1] = l[g]; }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sh[sg][g][4 + j * 8 + e] = acc[g][e];
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < G * 128; i += 256) {
+    const int g = i >> 7, c = i & 127;
+    float M = sh[0][g][0];
+    for (int x = 1; x < 16; ++x) M = fmaxf(M, sh[x][g][0]);
+    float L = 0.f, A = 0.f;
+    for (int x = 0; x < 16; ++x) {  // group order: fixed
+      const float w = exp2f(sh[x][g][0] - M);
+      L += sh[x][g][1] * w;
+      A += sh[x][g][4 + c] * w;
+    }
+    float* rec = ws + (((long)b * Hq + hk * G + g) * pstride + p) * kRec;
+    rec[4 + c] = A;
+    if (c == 0) { rec[0] = M; rec[1] = L; }
+  }
+}
+
+// Phase 2.  One workgroup per (query head, sequence), one thread per output column: the partitions [0, ceil(n/256)) are
+// merged in increasing index order.  n == 0: a zero row, LSE = -inf.
+__global__ __launch_bounds__(128) void attn_decode_merge_kernel(const float* __restrict__ ws, bf16* __restrict__ o,
+                                                                float* __restrict__ lse, const int32_t* __restrict__ len,
+                                                                int len_add, int cap, int max_len, int Hq, int pstride) {
+  const int h = blockIdx.x, b = blockIdx.y, c = threadIdx.x;
+  const int n = clampi(len[b] + len_add, 0, cap < max_len ? cap : max_len);
+  const int np = (n + kPart - 1) / kPart;
+  float M = kNegBig, L = 0.f, A = 0.f;
+  const float* rec = ws + ((long)b * Hq + h) * pstride * kRec;
+  for (int p = 0; p < np; ++p, rec += kRec) {
+    const float mp = rec[0], lp = rec[1], ap = rec[4 + c];
+    const float mn = fmaxf(M, mp);
+    const float c0 = exp2f(M - mn), c1 = exp2f(mp - mn);
+    L = L * c0 + lp * c1;
+    A = A * c0 + ap * c1;
+    M = mn;
+  }
+  o[((long)b * Hq + h) * 128 + c] = (bf16)(np > 0 ? A / L : 0.f);
+  if (lse && c == 0) lse[(long)b * Hq + h] = np > 0 ? (M + log2f(L)) * 0.6931471805599453f : -INFINITY;
+}
+
+// --------------------------------------------------------------------------------------------------------- sampler
+struct SampleArgs {
+  const bf16* logits;   // raw [B, ld]
+  long ld;
+  float* proc;          // processed scores fp32 [B, V] (penalty + EOS suppression; temperature is applied by readers)
+  const int32_t* top_i; // [B, K] indices of the K largest processed scores, descending, ties to the lowest index
+  float* bpart;         // [B, nblk, 2] block max / block sum of the full-vocabulary draw
+  int32_t* flag;        // [B] 1 = the row's token comes from the full-vocabulary draw
+  const float* u;       // [B, 2]
+  int64_t* seq;         // [B, cap]
+  const int32_t* prompt_len;
+  int32_t* len;
+  uint8_t* finished;
+  int64_t* next_out;
+  int32_t* pos_out;
+  int B, V, cap, K, nblk;
+  sd_sample_params sp;
+};
+
+SD_DEV void row_bounds(const SampleArgs& a, int b, int* n, int* np) {
+  *n = clampi(a.len[b], 0, a.cap);
+  *np = clampi(a.prompt_len[b], 0, *n);
+}
+
+// The token of an unfinished row: appended at seq[b, len], len advanced, EOS sets finished.  A full row finishes.
+SD_DEV void commit(const SampleArgs& a, int b, long tok) {
+  const int L = clampi(a.len[b], 0, a.cap);
+  if (L >= a.cap) {
+    a.next_out[b] = a.sp.pad_token_id;
+    a.pos_out[b] = a.cap - 1;
+    a.finished[b] = 1;
+    return;
+  }
+  a.seq[(long)b * a.cap + L] = tok;
+  a.len[b] = L + 1;
+  a.next_out[b] = tok;
+  a.pos_out[b] = L;
+  if (a.sp.eos_token_id >= 0 && tok == a.sp.eos_token_id) a.finished[b] = 1;
+}
+
+// Step 1 + 2 of the chain (HF RepetitionPenaltyLogitsProcessor fed the generated ids, MinNewTokensLength): the raw row is
+// copied to fp32, then every GENERATED token's column gets raw < 0 ? raw * p : raw / p.  The penalty reads the raw row
+// and writes the copy, so a token that occurs twice is written twice with the same value: "each distinct token once".
+// grid (slices, B): a workgroup owns a contiguous slice of columns and applies the tokens that fall into it.
+__global__ __launch_bounds__(1024) void sample_scores_kernel(SampleArgs a, int per) {
+  const int b = blockIdx.y;
+  if (a.finished[b]) return;
+  const int c0 = blockIdx.x * per, c1 = min(a.V, c0 + per);
+  const bf16* raw = a.logits + (long)b * a.ld;
+  float* out = a.proc + (long)b * a.V;
+  for (int c = c0 + threadIdx.x * 8; c < c1; c += 1024 * 8) {
+    float f[8];
+    unpack8(*(const bf16x8*)(raw + c), f);
+    *(f32x4*)(out + c) = f32x4{f[0], f[1], f[2], f[3]};
+    *(f32x4*)(out + c + 4) = f32x4{f[4], f[5], f[6], f[7]};
+  }
+  __syncthreads();
+  int n, np;
+  row_bounds(a, b, &n, &np);
+  const float pen = a.sp.repetition_penalty;
+  if (pen != 1.0f)
+    for (int i = np + threadIdx.x; i < n; i += 1024) {
+      const long tok = a.seq[(long)b * a.cap + i];
+      if (tok >= c0 && tok < c1) {
+        const float r = (float)raw[tok];
+        out[tok] = r < 0.f ? r * pen : r / pen;
+      }
+    }
+  __syncthreads();
+  const int eos = a.sp.eos_token_id;
+  if (threadIdx.x == 0 && eos >= c0 && eos < c1 && n - np < a.sp.min_new_tokens) out[eos] = -INFINITY;
+}
+
+// Steps 3-6 on the top-K candidates, one workgroup per row; thread 0 walks the <= 128 candidates in descending order.
+// Temperature: score / T.  Top-p (HF TopPLogitsWarper on the top-k survivors): walking up from the smallest
+// probability, a candidate is dropped while the cumulative mass is <= 1 - top_p; the largest always stays.
+// Draw: the first candidate whose cumulative mass (descending order, renormalised over the survivors) exceeds u.
+__global__ __launch_bounds__(128) void sample_pick_kernel(SampleArgs a) {
+  __shared__ float e_s[128];
+  __shared__ int id_s[128];
+  const int b = blockIdx.x, K = a.K;
+  int n, np;
+  row_bounds(a, b, &n, &np);
+  if (a.finished[b]) {
+    if (threadIdx.x == 0) {
+      a.next_out[b] = a.sp.pad_token_id;
+      a.pos_out[b] = n > 0 ? n - 1 : 0;
+      a.flag[b] = 0;
+    }
+    return;
+  }
+  if (K == 0) {  // no top-k: the whole processed row is the distribution (sample_full_*)
+    if (threadIdx.x == 0) a.flag[b] = 1;
+    return;
+  }
+  if (threadIdx.x < K) {
+    const int id = clampi(a.top_i[(long)b * K + threadIdx.x], 0, a.V - 1);
+    id_s[threadIdx.x] = id;
+    e_s[threadIdx.x] = a.proc[(long)b * a.V + id] / a.sp.temperature;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  if (!a.sp.do_sample) {
+    a.flag[b] = 0;
+    commit(a, b, id_s[0]);
+    return;
+  }
+  const float mx = e_s[0];
+  float Z = 0.f;
+  for (int k = 0; k < K; ++k) {
+    e_s[k] = expf(e_s[k] - mx);
+    Z += e_s[k];
+  }
+  int keep = K;
+  if (a.sp.top_p < 1.0f) {
+    const float drop = 1.0f - a.sp.top_p;
+    float cum = 0.f;
+    while (keep > 1) {
+      cum += e_s[keep - 1] / Z;
+      if (!(cum <= drop)) break;
+      --keep;
+    }
+  }
+  float Zk = 0.f;
+  for (int k = 0; k < keep; ++k) Zk += e_s[k];
+  auto draw = [&](float u) {
+    const float target = u * Zk;
+    float c = 0.f;
+    for (int k = 0; k < keep; ++k) {
+      c += e_s[k];
+      if (target < c) return k;
+    }
+    return keep - 1;
+  };
+  if (a.sp.use_ras) {
+    const int cand = id_s[draw(a.u[2 * b])];
+    int cnt = 0;
+    const int w0 = n - a.sp.win_size > 0 ? n - a.sp.win_size : 0;
+    for (int i = w0; i < n; ++i) cnt += a.seq[(long)b * a.cap + i] == cand;
+    if (cnt + 1 >= a.sp.ras_min_count) {  // the final draw is from softmax(raw logits): sample_full_*
+      a.flag[b] = 1;
+      return;
+    }
+  }
+  a.flag[b] = 0;
+  commit(a, b, id_s[draw(a.u[2 * b + 1])]);
+}
+
+// Full-vocabulary draw, pass 1: per block of 1024 columns the maximum and the sum of exp(x - block max), fp32, for the
+// rows whose flag is set.  x = value / temp (the raw bf16 row with temp 1, or the processed fp32 row).
+template <typename T>
+__global__ __launch_bounds__(256) void sample_full_partial_kernel(SampleArgs a, const T* __restrict__ src, long ld,
+                                                                  float temp) {
+  __shared__ float red[32];
+  const int b = blockIdx.y;
+  if (!a.flag[b]) return;
+  const int c0 = blockIdx.x * 1024 + threadIdx.x * 4;
+  float x[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) x[e] = c0 + e < a.V ? (float)src[(long)b * ld + c0 + e] / temp : -INFINITY;
+  const float bm = block_max<256>(fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])), red);
+  float s = 0.f;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) s += x[e] == -INFINITY ? 0.f : expf(x[e] - bm);
+  s = block_sum<256>(s, red);
+  if (threadIdx.x == 0) {
+    a.bpart[((long)b * a.nblk + blockIdx.x) * 2] = bm;
+    a.bpart[((long)b * a.nblk + blockIdx.x) * 2 + 1] = s;
+  }
+}
+
+// Pass 2: scan the block sums (thread 0, block order) to the block that holds u * Z, then scan that block's 1024 columns
+// in column order and take the first whose cumulative mass exceeds the target.
+template <typename T>
+__global__ __launch_bounds__(1024) void sample_full_pick_kernel(SampleArgs a, const T* __restrict__ src, long ld,
+                                                                float temp) {
+  __shared__ float red[32];
+  __shared__ float wsum[16];
+  __shared__ float sel_base, sel_target, sel_M;
+  __shared__ int sel_blk, first_hit;
+  const int b = blockIdx.x, t = threadIdx.x;
+  if (!a.flag[b]) return;
+  const float* bp = a.bpart + (long)b * a.nblk * 2;
+  float mx = -INFINITY;
+  for (int i = t; i < a.nblk; i += 1024) mx = fmaxf(mx, bp[2 * i]);
+  mx = block_max<1024>(mx, red);
+  if (t == 0) {
+    float Z = 0.f;
+    for (int i = 0; i < a.nblk; ++i) Z += bp[2 * i] == -INFINITY ? 0.f : bp[2 * i + 1] * expf(bp[2 * i] - mx);
+    const float target = a.u[2 * b + 1] * Z;
+    float c = 0.f, base = 0.f;
+    int blk = a.nblk - 1;  // rounding may leave the target at or past Z: the last block then
+    for (int i = 0; i < a.nblk; ++i) {
+      const float s = bp[2 * i] == -INFINITY ? 0.f : bp[2 * i + 1] * expf(bp[2 * i] - mx);
+      base = c;
+      if (target < c + s) { blk = i; break; }
+      c += s;
+    }
+    sel_blk = blk; sel_base = base; sel_target = target; sel_M = mx;
+    first_hit = 1024;
+  }
+  __syncthreads();
+  const int col = sel_blk * 1024 + t;
+  float x = col < a.V ? (float)src[(long)b * ld + col] / temp : -INFINITY;
+  const float e = x == -INFINITY ? 0.f : expf(x - sel_M);
+  float incl = e;  // inclusive scan over the 1024 threads: wave scan, then the wave totals in wave order
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float v = __shfl_up(incl, o, 64);
+    if ((t & 63) >= o) incl += v;
+  }
+  if ((t & 63) == 63) wsum[t >> 6] = incl;
+  __syncthreads();
+  float before = sel_base;
+  for (int w = 0; w < (t >> 6); ++w) before += wsum[w];
+  const bool hit = e > 0.f && sel_target < before + incl;
+  if (hit) atomicMin(&first_hit, t);
+  __syncthreads();
+  if (t == 0) {
+    int pick = first_hit;
+    if (pick >= 1024) {  // rounding left the target past the block's last column: its last column inside the vocabulary
+      pick = a.V - 1 - sel_blk * 1024;
+      pick = pick > 1023 ? 1023 : pick;
+    }
+    commit(a, b, (long)sel_blk * 1024 + pick);
+  }
+}
+
+int64_t sample_ws_layout(int B, int V, int64_t* o_topi, int64_t* o_topv, int64_t* o_bpart, int64_t* o_flag) {
+  auto al = [](int64_t x) { return (x + 255) & ~(int64_t)255; };
+  int64_t p = al((int64_t)B * V * 4);
+  *o_topi = p; p += al((int64_t)B * 128 * 4);
+  *o_topv = p; p += al((int64_t)B * 128 * 2);
+  *o_bpart = p; p += al((int64_t)B * ((V + 1023) / 1024) * 8);
+  *o_flag = p; p += al((int64_t)B * 4);
+  return p;
+}
+
+}  // namespace
+
+extern "C" int64_t sd_kvcache_bytes(const sd_qwen3_dims* d, int B, int cap) {
+  if (!d || d->head_dim != 128) return SD_ERR_UNSUPPORTED;
+  if (B <= 0 || cap <= 0) return SD_ERR_SHAPE;
+  return (int64_t)d->layers * 2 * B * cap * d->n_kv * 128 * 2;
+}
+
+extern "C" int sd_kvcache_store(const void* qk, const void* qkv, void* k_plane, void* v_plane, const int32_t* kv_len, int B,
+                                int T, int cap, int Hq, int Hkv, void* stream) {
+  if (B <= 0 || T <= 0 || cap <= 0 || T > cap || Hq <= 0 || Hkv <= 0) return SD_ERR_SHAPE;
+  const long total = 2l * B * T * Hkv * 16;
+  SdProfScope prof(SD_K_MISC, 2.0 * total * 16, ST);
+  SD_PROF_LABEL("kvcache_store_kernel");
+  hipLaunchKernelGGL(kvcache_store_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ST, (const bf16*)qk,
+                     (const bf16*)qkv, (bf16*)k_plane, (bf16*)v_plane, kv_len, B, T, cap, Hq, Hkv);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sd_last_rows(const int32_t* kv_len, int64_t* rows, int B, int T, void* stream) {
+  if (B <= 0 || T <= 0 || !rows) return SD_ERR_SHAPE;
+  hipLaunchKernelGGL(last_rows_kernel, dim3((B + 63) / 64), dim3(64), 0, ST, kv_len, rows, B, T);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sd_qknorm_rope_append(const void* qkv, const void* q_gain, const void* k_gain, const void* cos_tab,
+                                     const void* sin_tab, const int32_t* pos, void* q_out, void* k_plane, void* v_plane,
+                                     int B, int cap, int Hq, int Hkv, float eps, void* stream) {
+  if (B <= 0 || cap <= 0 || Hq <= 0 || Hkv <= 0 || !pos) return SD_ERR_SHAPE;
+  const long items = (long)B * (Hq + 2 * Hkv);
+  SdProfScope prof(SD_K_MISC, 4.0 * items * 128, ST);
+  SD_PROF_LABEL("qknorm_rope_append_kernel");
+  hipLaunchKernelGGL(qknorm_rope_append_kernel, dim3((unsigned)((items + 15) / 16)), dim3(256), 0, ST, (const bf16*)qkv,
+                     (const bf16*)q_gain, (const bf16*)k_gain, (const bf16*)cos_tab, (const bf16*)sin_tab, pos,
+                     (bf16*)q_out, (bf16*)k_plane, (bf16*)v_plane, B, cap, Hq, Hkv, eps);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int64_t sd_attn_decode_workspace_bytes(int B, int Hq, int cap) {
+  if (B <= 0 || Hq <= 0 || cap <= 0) return SD_ERR_SHAPE;
+  return (int64_t)B * Hq * ((cap + kPart - 1) / kPart) * kRec * 4;
+}
+
+extern "C" int sd_attn_decode(const void* q, const void* k_plane, const void* v_plane, void* o, float* lse,
+                              const int32_t* len, int len_add, void* workspace, int64_t workspace_bytes, int B, int cap,
+                              int max_len, int Hq, int Hkv, int head_dim, float scale, void* stream) {
+  if (head_dim != 128) return SD_ERR_UNSUPPORTED;
+  if (B <= 0 || cap <= 0 || max_len <= 0 || Hq <= 0 || Hkv <= 0 || (Hq % Hkv) || !len) return SD_ERR_SHAPE;
+  const int G = Hq / Hkv;
+  if (G != 1 && G != 2 && G != 4) return SD_ERR_UNSUPPORTED;
+  if (B > 65535 || Hkv > 65535) return SD_ERR_SHAPE;
+  if (workspace_bytes < sd_attn_decode_workspace_bytes(B, Hq, cap) || !workspace) return SD_ERR_WORKSPACE;
+  if (max_len > cap) max_len = cap;
+  const int pstride = (cap + kPart - 1) / kPart, np = (max_len + kPart - 1) / kPart;
+  const float sl2 = scale * 1.4426950408889634f;
+  {
+    // K and V rows of max_len keys per (sequence, kv head), read once
+    SdProfScope prof(SD_K_MISC, 2.0 * B * Hkv * 256.0 * max_len, ST);
+    SD_PROF_LABEL("attn_decode_part_kernel<%d>", G);
+#define SD_DEC_GO(G_)                                                                                                 \
+  hipLaunchKernelGGL((attn_decode_part_kernel<G_>), dim3(np, Hkv, B), dim3(256), 0, ST, (const bf16*)q,               \
+                     (const bf16*)k_plane, (const bf16*)v_plane, (float*)workspace, len, len_add, cap, max_len, Hq, Hkv, \
+                     pstride, sl2)
+    if (G == 1) SD_DEC_GO(1); else if (G == 2) SD_DEC_GO(2); else SD_DEC_GO(4);
+#undef SD_DEC_GO
+    SD_CHECK_LAUNCH();
+  }
+  SdProfScope prof(SD_K_MISC, (double)B * Hq * np * kRec * 4, ST);
+  SD_PROF_LABEL("attn_decode_merge_kernel");
+  hipLaunchKernelGGL(attn_decode_merge_kernel, dim3(Hq, B), dim3(128), 0, ST, (const float*)workspace, (bf16*)o, lse, len,
+                     len_add, cap, max_len, Hq, pstride);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int64_t sd_sample_workspace_bytes(int B, int V) {
+  if (B <= 0 || V <= 0) return SD_ERR_SHAPE;
+  int64_t a, b, c, d;
+  return sample_ws_layout(B, V, &a, &b, &c, &d);
+}
+
+extern "C" int sd_sample_step(const void* logits, int64_t row_stride, const float* uniforms, int64_t* seq,
+                              const int32_t* prompt_len, int32_t* len, uint8_t* finished, int64_t* next_out,
+                              int32_t* pos_out, void* workspace, int64_t workspace_bytes, const sd_sample_params* sp, int B,
+                              int V, int cap, void* stream) {
+  if (!sp || !logits || !uniforms || !seq || !prompt_len || !len || !finished || !next_out || !pos_out) return SD_ERR_SHAPE;
+  if (B <= 0 || B > 65535 || V <= 0 || cap <= 0 || row_stride < V) return SD_ERR_SHAPE;
+  if ((V & 7) || (row_stride & 7) || ((uintptr_t)logits & 15) || ((uintptr_t)workspace & 15)) return SD_ERR_ALIGN;
+  if (sp->top_k < 0 || sp->top_k > 128 || sp->top_k > V) return SD_ERR_SHAPE;
+  if (sp->pad_token_id < 0 || sp->pad_token_id >= V || sp->eos_token_id >= V) return SD_ERR_SHAPE;
+  if (sp->do_sample && (!(sp->temperature > 0.f) || !(sp->top_p > 0.f) || !(sp->repetition_penalty > 0.f))) return SD_ERR_SHAPE;
+  // the top-p rule and RAS need the sorted top-k candidates
+  if (sp->do_sample && sp->top_k == 0 && (sp->top_p < 1.0f || sp->use_ras)) return SD_ERR_UNSUPPORTED;
+  if (sp->use_ras && (sp->win_size <= 0 || sp->ras_min_count <= 0)) return SD_ERR_SHAPE;
+  int64_t o_topi, o_topv, o_bpart, o_flag;
+  if (workspace_bytes < sample_ws_layout(B, V, &o_topi, &o_topv, &o_bpart, &o_flag) || !workspace) return SD_ERR_WORKSPACE;
+  char* ws = (char*)workspace;
+  SampleArgs a;
+  a.logits = (const bf16*)logits; a.ld = row_stride; a.proc = (float*)ws; a.top_i = (const int32_t*)(ws + o_topi);
+  a.bpart = (float*)(ws + o_bpart); a.flag = (int32_t*)(ws + o_flag); a.u = uniforms; a.seq = seq;
+  a.prompt_len = prompt_len; a.len = len; a.finished = finished; a.next_out = next_out; a.pos_out = pos_out;
+  a.B = B; a.V = V; a.cap = cap; a.K = sp->do_sample ? sp->top_k : 1; a.nblk = (V + 1023) / 1024; a.sp = *sp;
+  {
+    SdProfScope prof(SD_K_MISC, 6.0 * B * V, ST);
+    SD_PROF_LABEL("sample_scores_kernel");
+    const int slices = 8, per = ((V + slices - 1) / slices + 7) & ~7;
+    hipLaunchKernelGGL(sample_scores_kernel, dim3(slices, B), dim3(1024), 0, ST, a, per);
+    SD_CHECK_LAUNCH();
+  }
+  if (a.K > 0) {
+    const int rc = sd_logsoftmax_topk(a.proc, ws + o_topv, ws + o_topi, nullptr, B, V, V, a.K, SD_DTYPE_F32, stream);
+    if (rc) return rc;
+  }
+  {
+    SdProfScope prof(SD_K_MISC, 8.0 * B * 128, ST);
+    SD_PROF_LABEL("sample_pick_kernel");
+    hipLaunchKernelGGL(sample_pick_kernel, dim3(B), dim3(128), 0, ST, a);
+    SD_CHECK_LAUNCH();
+  }
+  if (!sp->do_sample || (a.K > 0 && !sp->use_ras)) return 0;
+  SdProfScope prof(SD_K_MISC, 2.0 * B * V, ST);
+  SD_PROF_LABEL("sample_full_kernels");
+  if (a.K == 0) {  // the processed row at the caller's temperature
+    hipLaunchKernelGGL((sample_full_partial_kernel<float>), dim3(a.nblk, B), dim3(256), 0, ST, a, (const float*)a.proc,
+                       (long)V, sp->temperature);
+    SD_CHECK_LAUNCH();
+    hipLaunchKernelGGL((sample_full_pick_kernel<float>), dim3(B), dim3(1024), 0, ST, a, (const float*)a.proc, (long)V,
+                       sp->temperature);
+  } else {  // RAS fallback: softmax of the raw logits
+    hipLaunchKernelGGL((sample_full_partial_kernel<bf16>), dim3(a.nblk, B), dim3(256), 0, ST, a, a.logits, a.ld, 1.0f);
+    SD_CHECK_LAUNCH();
+    hipLaunchKernelGGL((sample_full_pick_kernel<bf16>), dim3(B), dim3(1024), 0, ST, a, a.logits, a.ld, 1.0f);
+  }
+  SD_CHECK_LAUNCH();
+  return 0;
+}

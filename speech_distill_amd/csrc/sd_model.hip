@@ -114,12 +114,21 @@ int layer_attn_fwd(const Sizes& s, const LayerActs& a, const int32_t* kv_len, co
                      s.QK, s.QK, s.QKV, s.QD, B, T, s.Hq, s.Hkv, 128, scale, stream);
 }
 
+// Where a prefill leaves the keys and values of its layers: the cache [L][2][B][cap][Hkv*128] of sd_kvcache_bytes
+struct KvSink {
+  char* cache;
+  int cap;
+  char* plane(const Sizes& s, int B, int l, int which) const {
+    return cache + ((int64_t)l * 2 + which) * B * cap * s.KD * 2;
+  }
+};
+
 // One decoder layer (HF modeling_qwen3.py:227-250): a.x_in -> x_out, every intermediate into `a`.  x_out == nullptr
 // stops after the SwiGLU (the backward's recompute does not need the layer output again); keep_gu: gate|up is kept
-// for the backward.
+// for the backward.  sink (sd_qwen3_prefill): the layer's K / V rows below kv_len also go to planes l of the cache.
 int layer_forward(const sd_qwen3_dims* d, const Sizes& s, const LayerActs& a, const sd_qwen3_layer& w, char* x_out,
                   bool keep_gu, const int32_t* kv_len, const sd_varlen* vl, const void* cos_tab, const void* sin_tab,
-                  int B, int T, void* stream) {
+                  int B, int T, void* stream, const KvSink* sink = nullptr, int l = 0) {
   RUN(sd_rmsnorm_fwd(a.x_in, w.ln1, a.xn1, (float*)a.rstd1, s.M, s.h, d->eps, stream));
   // q|k|v projection with q/k-norm + RoPE in the GEMM epilogue (one head = one 128-column tile)
   int rc = sd_gemm_qkv_rope(a.xn1, w.wqkv, a.qkv, a.qk, w.q_gain, w.k_gain, cos_tab, sin_tab, s.M, T, s.Hq, s.Hkv, s.h,
@@ -130,6 +139,9 @@ int layer_forward(const sd_qwen3_dims* d, const Sizes& s, const LayerActs& a, co
   } else if (rc) {
     return rc;
   }
+  if (sink)
+    RUN(sd_kvcache_store(a.qk, a.qkv, sink->plane(s, B, l, 0), sink->plane(s, B, l, 1), kv_len, B, T, sink->cap, s.Hq,
+                         s.Hkv, stream));
   RUN(layer_attn_fwd(s, a, kv_len, vl, B, T, stream));
   RUN(sd_gemm_bf16(a.ao, w.wo, a.x_mid, a.x_in, s.M, s.h, s.QD, s.QD, s.QD, s.h, s.h, 0, 0, stream));
   RUN(sd_rmsnorm_fwd(a.x_mid, w.ln2, a.xn2, (float*)a.rstd2, s.M, s.h, d->eps, stream));
@@ -289,9 +301,11 @@ extern "C" int sd_qwen3_forward(const sd_qwen3_dims* d, const sd_qwen3_params* p
 // The forward of every entry: per batch row (kv_len), or per packed document when vl is given (B = 1, T = M)
 static int forward_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* kv_len,
                         const sd_varlen* vl, const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes,
-                        void* logits, const int64_t* head_rows, int n_head_rows, int B, int T, int save, void* stream) {
+                        void* logits, const int64_t* head_rows, int n_head_rows, int B, int T, int save, void* stream,
+                        const KvSink* sink = nullptr) {
   if (d->head_dim != 128) return SD_ERR_UNSUPPORTED;
   if (B <= 0 || T <= 0) return SD_ERR_SHAPE;
+  if (sink && (vl || (save & ~SD_FWD_CONCURRENT) != SD_SAVE_NONE)) return SD_ERR_SHAPE;
   if (head_rows && (n_head_rows <= 0 || n_head_rows > B * T)) return SD_ERR_SHAPE;
   Sizes s(d, B, T);
   const bool concurrent = (save & SD_FWD_CONCURRENT) != 0;
@@ -331,7 +345,7 @@ static int forward_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const 
                                l + 1 < s.L ? ssq_a : nullptr, stream));
     else
       RUN(layer_forward(d, s, a, p->layers_host[l], x_out, save != SD_SAVE_NONE, kv_len, vl, cos_tab, sin_tab, B, T,
-                        stream));
+                        stream, sink, l));
     x_cur = x_out;
   }
   RUN(sd_rmsnorm_fwd(x_last, p->final_norm, xn_f, (float*)rstd_f, s.M, s.h, d->eps, stream));
@@ -631,4 +645,90 @@ extern "C" int sd_qwen3_backward_embed_varlen(const sd_qwen3_dims* d, const sd_q
   if (!vl || grad_row_lo < 0) return SD_ERR_SHAPE;
   return backward_impl(d, p, g, ids, nullptr, vl, cos_tab, sin_tab, acts, acts_bytes, dlogits, head_rows, n_head_rows,
                        scratch, scratch_bytes, 1, M, accumulate, nullptr, nullptr, nullptr, side_stream, stream, grad_row_lo);
+}
+
+// ------------------------------------------------------------------------------------------ KV-cache generation
+// (engine/llm_engine.py:37-76: prefill the prompt once, then one token per step over the cache)
+extern "C" int64_t sd_qwen3_prefill_acts_bytes(const sd_qwen3_dims* d, int B, int T) {
+  const int64_t base = sd_qwen3_acts_bytes(d, B, T, SD_SAVE_NONE);
+  return base < 0 ? base : al(base) + al((int64_t)B * 8);  // + the head rows (int64 [B])
+}
+
+extern "C" int sd_qwen3_prefill(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* kv_len,
+                                const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes, void* cache,
+                                int64_t cache_bytes, int cap, void* logits, int B, int T, void* stream) {
+  if (d->head_dim != 128) return SD_ERR_UNSUPPORTED;
+  if (B <= 0 || T <= 0 || cap < T || !logits || !cache) return SD_ERR_SHAPE;
+  if (acts_bytes < sd_qwen3_prefill_acts_bytes(d, B, T) || cache_bytes < sd_kvcache_bytes(d, B, cap)) return SD_ERR_WORKSPACE;
+  const int64_t base = al(sd_qwen3_acts_bytes(d, B, T, SD_SAVE_NONE));
+  int64_t* rows = (int64_t*)((char*)acts + base);
+  RUN(sd_last_rows(kv_len, rows, B, T, stream));
+  const KvSink sink = {(char*)cache, cap};
+  return forward_impl(d, p, ids, kv_len, nullptr, cos_tab, sin_tab, acts, base, logits, rows, B, B, T, SD_SAVE_NONE, stream,
+                      &sink);
+}
+
+namespace {
+struct DecodeActs {
+  char *x, *x_mid, *xn, *qkv, *q, *ao, *gu, *act, *ws;
+  int64_t ws_bytes, total;
+  DecodeActs(const sd_qwen3_dims* d, int B, int cap, char* p) {
+    const Sizes s(d, B, 1);
+    char* p0 = p;
+    x = p; p += s.x;
+    x_mid = p; p += s.x;
+    xn = p; p += s.x;
+    qkv = p; p += s.qkv;
+    q = p; p += s.ao;
+    ao = p; p += s.ao;
+    gu = p; p += s.gu;
+    act = p; p += s.act;
+    ws_bytes = sd_attn_decode_workspace_bytes(B, s.Hq, cap);
+    ws = p; p += al(ws_bytes);
+    total = p - p0;
+  }
+};
+}  // namespace
+
+extern "C" int64_t sd_qwen3_decode_acts_bytes(const sd_qwen3_dims* d, int B, int cap) {
+  if (!d || d->head_dim != 128) return SD_ERR_UNSUPPORTED;
+  if (B <= 0 || cap <= 0) return SD_ERR_SHAPE;
+  return DecodeActs(d, B, cap, nullptr).total;
+}
+
+extern "C" int sd_qwen3_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
+                                    const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab, void* cache,
+                                    int64_t cache_bytes, int cap, void* acts, int64_t acts_bytes, void* logits, int B,
+                                    void* stream) {
+  if (d->head_dim != 128) return SD_ERR_UNSUPPORTED;
+  if (B <= 0 || cap <= 0 || max_len <= 0 || !ids || !pos || !logits || !cache) return SD_ERR_SHAPE;
+  const Sizes s(d, B, 1);
+  const DecodeActs a(d, B, cap, (char*)acts);
+  if (acts_bytes < a.total || cache_bytes < sd_kvcache_bytes(d, B, cap)) return SD_ERR_WORKSPACE;
+  const KvSink kv = {(char*)cache, cap};
+  const float scale = 0.08838834764831845f;  // 128^-1/2
+  RUN(sd_embedding_fwd(ids, p->embed, a.x, B, s.h, s.V, stream));
+  for (int l = 0; l < s.L; ++l) {
+    const sd_qwen3_layer& w = p->layers_host[l];
+    char *kp = kv.plane(s, B, l, 0), *vp = kv.plane(s, B, l, 1);
+    RUN(sd_rmsnorm_fwd(a.x, w.ln1, a.xn, nullptr, B, s.h, d->eps, stream));
+    RUN(sd_gemm_bf16(a.xn, w.wqkv, a.qkv, nullptr, B, s.QKV, s.h, s.h, s.h, s.QKV, 0, 0, 0, stream));
+    RUN(sd_qknorm_rope_append(a.qkv, w.q_gain, w.k_gain, cos_tab, sin_tab, pos, a.q, kp, vp, B, cap, s.Hq, s.Hkv, d->eps,
+                              stream));
+    RUN(sd_attn_decode(a.q, kp, vp, a.ao, nullptr, pos, 1, a.ws, a.ws_bytes, B, cap, max_len, s.Hq, s.Hkv, 128, scale,
+                       stream));
+    RUN(sd_gemm_bf16(a.ao, w.wo, a.x_mid, a.x, B, s.h, s.QD, s.QD, s.QD, s.h, s.h, 0, 0, stream));
+    RUN(sd_rmsnorm_fwd(a.x_mid, w.ln2, a.xn, nullptr, B, s.h, d->eps, stream));
+    const int rc = sd_gemm_swiglu(a.xn, w.wgu, nullptr, a.act, B, s.I, s.h, stream);
+    if (rc == SD_ERR_UNSUPPORTED) {
+      RUN(sd_gemm_bf16(a.xn, w.wgu, a.gu, nullptr, B, 2 * s.I, s.h, s.h, s.h, 2 * s.I, 0, 0, 0, stream));
+      RUN(sd_swiglu_fwd(a.gu, a.act, B, s.I, stream));
+    } else if (rc) {
+      return rc;
+    }
+    RUN(sd_gemm_bf16(a.act, w.wdown, a.x, a.x_mid, B, s.h, s.I, s.I, s.I, s.h, s.h, 0, 0, stream));
+  }
+  RUN(sd_rmsnorm_fwd(a.x, p->final_norm, a.xn, nullptr, B, s.h, d->eps, stream));
+  RUN(sd_gemm_bf16(a.xn, p->lm_head, logits, nullptr, B, s.V, s.h, s.h, s.h, s.V, 0, 0, 0, stream));
+  return 0;
 }

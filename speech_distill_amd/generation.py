@@ -1,0 +1,179 @@
+"""KV-cache generation for ``HipQwen3ForCausalLM``: prefill, one-token decode steps and the on-GPU sampler.
+
+What the reference does for this lives in its inference engine: the decode loop of soulxpodcast/engine/llm_engine.py:37-76,
+the ``SamplingParams`` of soulxpodcast/config.py:107-118 and the HF sampling loop with repetition-aware sampling of
+soulxpodcast/models/modules/sampler.py:136-189.  Here the whole step stays on the GPU: the sampler (sd_sample_step) appends
+the token to a device-resident sequence buffer and hands its output straight to the next decode step
+(sd_qwen3_decode_step); the host reads the ``finished`` flags once every ``sync_every`` steps and nothing else.
+
+Prompts are right-padded (as everywhere in this package): row b's first new token takes position ``kv_len[b]`` and the
+pad slots are never cached, so no row ever attends to them.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+
+from . import _lib
+from ._lib import check, load_lib
+from .ops import _need, _stream, left_padded, sample_params, sample_step
+
+REFERENCE_SAMPLING = dict(do_sample=True, temperature=0.6, top_k=100, top_p=0.9, repetition_penalty=1.25, use_ras=True,
+                          win_size=25, tau_r=0.2)  # soulxpodcast/config.py:107-118
+DEFAULT_CACHE_CAPACITY = 32768  # positions; Qwen3's max_position_embeddings when the config does not say
+
+
+def cache_capacity(model):
+    """Most positions (prompt + new tokens) a generation may hold: ``model.kv_cache_capacity`` when set, else the
+    config's ``max_position_embeddings``."""
+    cap = getattr(model, "kv_cache_capacity", None) or getattr(model.config, "max_position_embeddings", None)
+    return int(cap or DEFAULT_CACHE_CAPACITY)
+
+
+class Decoder:
+    """The KV cache [L][2][B][cap][Hkv*128] (bf16) of one batch, the activation buffers of the two runner entries, and the
+    calls themselves.  ``prefill`` fills the cache from right-padded prompts and returns the logits of each row's last
+    valid token; ``step`` takes one token per row at position ``pos[b]`` (= tokens already cached) and returns the next
+    logits [B,V]."""
+
+    def __init__(self, model, B, cap):
+        if model.inference_precision != "bf16":
+            raise NotImplementedError('generate() decodes with the unfolded bf16 weights; this model runs "'
+                                      f'{model.inference_precision}" (set_inference_precision("bf16") first)')
+        self.model, self.B, self.cap = model, int(B), int(cap)
+        lib = load_lib()
+        dev = model.flat.device
+        _need(model.flat, torch.bfloat16, "model parameters")
+        d = model._cdims
+        nb = lib.sd_kvcache_bytes(C.byref(d), self.B, self.cap)
+        check(min(nb, 0), "sd_kvcache_bytes")
+        self.cache = torch.empty(nb, dtype=torch.uint8, device=dev)
+        self.step_acts = torch.empty(lib.sd_qwen3_decode_acts_bytes(C.byref(d), self.B, self.cap), dtype=torch.uint8,
+                                     device=dev)
+        self.cos, self.sin = model._tables(self.cap, dev)
+        self.logits = torch.empty(self.B, model.dims.vocab_size, dtype=torch.bfloat16, device=dev)
+
+    def planes(self, layer):
+        """(K, V) views [B, cap, Hkv*128] of one layer's cache planes."""
+        kd = self.model.dims.kv_dim
+        n = self.B * self.cap * kd
+        flat = self.cache.view(torch.bfloat16)
+        k = flat[(2 * layer) * n:(2 * layer + 1) * n].view(self.B, self.cap, kd)
+        v = flat[(2 * layer + 1) * n:(2 * layer + 2) * n].view(self.B, self.cap, kd)
+        return k, v
+
+    def _params(self):
+        if self.model._lora is not None:
+            self.model._lora.ensure_merged()   # the decoder reads the merged weights
+        return self.model._cparams
+
+    @torch.no_grad()
+    def prefill(self, ids, kv_len=None):
+        lib, m = load_lib(), self.model
+        _need(ids, torch.int64, "input_ids")
+        B, T = ids.shape
+        if B != self.B or T > self.cap:
+            raise ValueError(f"prefill of {tuple(ids.shape)} into a cache for {self.B} rows of {self.cap} positions")
+        nb = lib.sd_qwen3_prefill_acts_bytes(C.byref(m._cdims), B, T)
+        acts = torch.empty(nb, dtype=torch.uint8, device=ids.device)
+        check(lib.sd_qwen3_prefill(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(),
+                                   0 if kv_len is None else kv_len.data_ptr(), self.cos.data_ptr(), self.sin.data_ptr(),
+                                   acts.data_ptr(), nb, self.cache.data_ptr(), self.cache.numel(), self.cap,
+                                   self.logits.data_ptr(), B, T, _stream()), "sd_qwen3_prefill")
+        return self.logits
+
+    @torch.no_grad()
+    def step(self, ids, pos, max_len):
+        """ids int64 [B], pos int32 [B] (device); max_len: host upper bound of every pos[b] + 1."""
+        lib, m = load_lib(), self.model
+        _need(ids, torch.int64, "ids"), _need(pos, torch.int32, "pos")
+        if ids.numel() != self.B or pos.numel() != self.B:
+            raise ValueError(f"decode step wants {self.B} tokens and positions")
+        check(lib.sd_qwen3_decode_step(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(), pos.data_ptr(),
+                                       int(max_len), self.cos.data_ptr(), self.sin.data_ptr(), self.cache.data_ptr(),
+                                       self.cache.numel(), self.cap, self.step_acts.data_ptr(), self.step_acts.numel(),
+                                       self.logits.data_ptr(), self.B, _stream()), "sd_qwen3_decode_step")
+        return self.logits
+
+
+def _check_args(model, B, T, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p, repetition_penalty,
+                use_ras, win_size, tau_r, sync_every):
+    if max_new_tokens < 1:
+        raise ValueError(f"max_new_tokens must be at least 1, got {max_new_tokens}")
+    if top_k < 0 or top_k > 128:
+        raise ValueError(f"top_k must be in 0..128 (the sampler keeps at most 128 candidates), got {top_k}")
+    cap = cache_capacity(model)
+    if T + max_new_tokens > cap:
+        raise ValueError(f"prompt length {T} + max_new_tokens {max_new_tokens} exceeds the KV-cache capacity {cap}")
+    if model.inference_precision != "bf16":
+        raise NotImplementedError('generate() decodes with the unfolded bf16 weights; this model runs "'
+                                  f'{model.inference_precision}" (set_inference_precision("bf16") first)')
+    if min_new_tokens < 0 or sync_every < 1:
+        raise ValueError("min_new_tokens must be >= 0 and sync_every >= 1")
+    if do_sample:
+        if not temperature > 0 or not 0 < top_p <= 1 or not repetition_penalty > 0:
+            raise ValueError("sampling needs temperature > 0, 0 < top_p <= 1 and repetition_penalty > 0")
+        if top_k == 0 and (top_p < 1 or use_ras):
+            raise ValueError("top_p < 1 and use_ras work on the sorted top-k candidates: give top_k in 1..128")
+        if use_ras and (win_size < 1 or not tau_r > 0):
+            raise ValueError("use_ras needs win_size >= 1 and tau_r > 0")
+
+
+@torch.no_grad()
+def generate(model, input_ids, attention_mask=None, max_new_tokens=20, min_new_tokens=0, do_sample=True, temperature=1.0,
+             top_k=0, top_p=1.0, repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, use_ras=False, win_size=25,
+             tau_r=0.2, seed=None, sync_every=16):
+    """See ``HipQwen3ForCausalLM.generate``."""
+    if input_ids.dim() != 2:
+        raise ValueError(f"input_ids must be [B,T], got {tuple(input_ids.shape)}")
+    B, T = input_ids.shape
+    _check_args(model, B, T, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p, repetition_penalty,
+                use_ras, win_size, tau_r, sync_every)
+    V = model.dims.vocab_size
+    pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
+    if not 0 <= pad < V or (eos_token_id is not None and not 0 <= eos_token_id < V):
+        raise ValueError(f"pad / eos token ids must lie in [0, {V})")
+    ids = _need(input_ids.to(torch.int64), torch.int64, "input_ids")
+    dev = ids.device
+    if attention_mask is not None:
+        am = attention_mask.to(dev)
+        if am.shape != ids.shape:
+            raise ValueError(f"attention_mask {tuple(am.shape)} != input_ids {tuple(ids.shape)}")
+        kv_len = am.sum(-1).to(torch.int32).contiguous()
+        bad, shortest = torch.stack([left_padded(am).to(torch.int32).reshape(()), kv_len.min()]).tolist()  # one host read
+        if bad:
+            raise ValueError("attention_mask is not right-padded (a 1 follows a 0): the HIP attention kernels take a "
+                             "valid-prefix length per sequence, as ProcessedDataCollator produces (data.py:280-327)")
+        if shortest < 1:
+            raise ValueError("every prompt needs at least one token")
+        valid = am.to(torch.bool)
+    else:
+        kv_len = torch.full((B,), T, dtype=torch.int32, device=dev)
+        valid = None
+    cap = (T + max_new_tokens + 255) // 256 * 256   # whole attention partitions; the output bits do not depend on it
+    dec = Decoder(model, B, cap)
+    seq = torch.full((B, cap), pad, dtype=torch.int64, device=dev)
+    seq[:, :T] = ids if valid is None else torch.where(valid, ids, torch.full_like(ids, pad))
+    lens, finished = kv_len.clone(), torch.zeros(B, dtype=torch.uint8, device=dev)
+    nxt = torch.empty(B, dtype=torch.int64, device=dev)
+    pos = torch.empty(B, dtype=torch.int32, device=dev)
+    sp = sample_params(do_sample, temperature, top_k, top_p, repetition_penalty, min_new_tokens, eos_token_id, pad, use_ras,
+                       win_size, tau_r)
+    ws = torch.empty(load_lib().sd_sample_workspace_bytes(B, V), dtype=torch.uint8, device=dev)
+    gen = None
+    if seed is not None:
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(int(seed))
+    u = torch.rand(max_new_tokens, B, 2, generator=gen, device=dev, dtype=torch.float32)  # every step's uniforms, one launch
+    logits = dec.prefill(ids, kv_len)
+    for step in range(max_new_tokens):
+        sample_step(logits, u[step], seq, kv_len, lens, finished, sp, workspace=ws, next_out=nxt, pos_out=pos)
+        if step + 1 == max_new_tokens:
+            break
+        if (step + 1) % sync_every == 0 and bool(finished.all()):   # the only host read of the loop
+            break
+        logits = dec.step(nxt, pos, T + step + 1)
+    # row b's new tokens sit at seq[b, kv_len[b] ...]; slots never written still hold pad
+    cols = kv_len.to(torch.int64)[:, None] + torch.arange(max_new_tokens, device=dev)[None, :]
+    return torch.cat([ids, seq.gather(1, cols)], dim=1)

@@ -764,3 +764,89 @@ def gemm_mxfp8_swiglu(a_q, a_scale, wgu_q, wgu_scale, rowscale=None):
     check(load_lib().sd_gemm_mxfp8_swiglu(a_q.data_ptr(), a_scale.data_ptr(), wgu_q.data_ptr(), wgu_scale.data_ptr(), _p(rs),
                                           act_q.data_ptr(), act_s.data_ptr(), M, I, K, _stream()), "sd_gemm_mxfp8_swiglu")
     return act_q, act_s
+
+
+# ------------------------------------------------------------------------------------ KV-cache generation
+def kvcache_store(qk, qkv, k_plane, v_plane, kv_len, B, T, Hq, Hkv):
+    """Prefill sink (sd_kvcache_store): K of ``qk`` [B*T,(Hq+Hkv)*128] and V of ``qkv`` [B*T,(Hq+2Hkv)*128] -> slots
+    t < kv_len[b] of the planes [B, cap, Hkv*128]."""
+    _need(qk, torch.bfloat16, "qk"), _need(qkv, torch.bfloat16, "qkv")
+    _need(k_plane, torch.bfloat16, "k_plane"), _need(v_plane, torch.bfloat16, "v_plane")
+    check(load_lib().sd_kvcache_store(qk.data_ptr(), qkv.data_ptr(), k_plane.data_ptr(), v_plane.data_ptr(), _p(kv_len), B, T,
+                                      k_plane.shape[1], Hq, Hkv, _stream()), "sd_kvcache_store")
+
+
+def last_rows(kv_len, B, T, device=None):
+    """int64 [B]: flat index b*T + clamp(kv_len[b], 1, T) - 1 of the last valid row of every right-padded sequence."""
+    rows = torch.empty(B, dtype=torch.int64, device=kv_len.device if kv_len is not None else device)
+    check(load_lib().sd_last_rows(_p(kv_len), rows.data_ptr(), B, T, _stream()), "sd_last_rows")
+    return rows
+
+
+def qknorm_rope_append(qkv, q_gain, k_gain, cos, sin, pos, k_plane, v_plane, Hq, Hkv, eps=1e-6):
+    """Decode twin of qknorm_rope_fwd for one token per sequence at position pos[b] (int32, device): returns q
+    [B,Hq*128]; K (normalised, rotated) and raw V go to slot pos[b] of the planes [B, cap, Hkv*128]."""
+    _need(qkv, torch.bfloat16, "qkv"), _need(pos, torch.int32, "pos")
+    _need(k_plane, torch.bfloat16, "k_plane"), _need(v_plane, torch.bfloat16, "v_plane")
+    B, cap = qkv.shape[0], k_plane.shape[1]
+    if cos.shape[0] < cap:
+        raise ValueError(f"rope tables hold {cos.shape[0]} positions, the cache {cap}")
+    q = torch.empty(B, Hq * 128, dtype=torch.bfloat16, device=qkv.device)
+    check(load_lib().sd_qknorm_rope_append(qkv.data_ptr(), q_gain.data_ptr(), k_gain.data_ptr(), cos.data_ptr(),
+                                           sin.data_ptr(), pos.data_ptr(), q.data_ptr(), k_plane.data_ptr(),
+                                           v_plane.data_ptr(), B, cap, Hq, Hkv, eps, _stream()), "sd_qknorm_rope_append")
+    return q
+
+
+def attn_decode(q, k_plane, v_plane, lens, Hq, Hkv, max_len=None, len_add=0, want_lse=False, workspace=None):
+    """Single-token attention over the cache planes [B, cap, Hkv*128]: q [B,Hq*128], lens int32 [B] (device); row b attends
+    to keys [0, lens[b] + len_add).  max_len: host upper bound of those counts (default cap).  -> o [B,Hq*128] (, lse [B,Hq])."""
+    _need(q, torch.bfloat16, "q"), _need(lens, torch.int32, "lens")
+    _need(k_plane, torch.bfloat16, "k_plane"), _need(v_plane, torch.bfloat16, "v_plane")
+    lib = load_lib()
+    B, cap = q.shape[0], k_plane.shape[1]
+    nb = lib.sd_attn_decode_workspace_bytes(B, Hq, cap)
+    if workspace is None:
+        workspace = torch.empty(max(nb, 16), dtype=torch.uint8, device=q.device)
+    o = torch.empty(B, Hq * 128, dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty(B, Hq, dtype=torch.float32, device=q.device) if want_lse else None
+    check(lib.sd_attn_decode(q.data_ptr(), k_plane.data_ptr(), v_plane.data_ptr(), o.data_ptr(), _p(lse), lens.data_ptr(),
+                             int(len_add), workspace.data_ptr(), workspace.numel(), B, cap,
+                             cap if max_len is None else int(max_len), Hq, Hkv, 128, 128 ** -0.5, _stream()),
+          "sd_attn_decode")
+    return (o, lse) if want_lse else o
+
+
+def sample_params(do_sample=True, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, min_new_tokens=0,
+                  eos_token_id=None, pad_token_id=0, use_ras=False, win_size=25, tau_r=0.2):
+    """include/sd_hip.h sd_sample_params.  The RAS threshold is handed over as an integer count: count + 1 >= win_size *
+    tau_r (sampler.py:146-147, evaluated in double as Python does) <=> count + 1 >= ceil(win_size * tau_r)."""
+    import math
+    from ._lib import SampleParams
+    return SampleParams(int(bool(do_sample)), int(top_k), int(bool(use_ras)), int(win_size),
+                        max(1, math.ceil(win_size * tau_r)), int(min_new_tokens),
+                        -1 if eos_token_id is None else int(eos_token_id), int(pad_token_id), float(temperature),
+                        float(top_p), float(repetition_penalty), 0.0)
+
+
+def sample_step(logits, uniforms, seq, prompt_len, lens, finished, params, workspace=None, next_out=None, pos_out=None):
+    """One sampling step (sd_sample_step) on logits bf16 [B,V] with uniforms fp32 [B,2]; updates seq int64 [B,cap], lens
+    int32 [B] and finished uint8 [B] in place.  -> (next token int64 [B], its position int32 [B])."""
+    _need(logits, torch.bfloat16, "logits"), _need(uniforms, torch.float32, "uniforms"), _need(seq, torch.int64, "seq")
+    _need(prompt_len, torch.int32, "prompt_len"), _need(lens, torch.int32, "lens"), _need(finished, torch.uint8, "finished")
+    lib = load_lib()
+    B, V = logits.shape
+    if uniforms.shape != (B, 2) or seq.shape[0] != B:
+        raise ValueError("sample_step: uniforms must be [B,2] and seq [B,cap]")
+    nb = lib.sd_sample_workspace_bytes(B, V)
+    if workspace is None:
+        workspace = torch.empty(nb, dtype=torch.uint8, device=logits.device)
+    if next_out is None:
+        next_out = torch.empty(B, dtype=torch.int64, device=logits.device)
+    if pos_out is None:
+        pos_out = torch.empty(B, dtype=torch.int32, device=logits.device)
+    check(lib.sd_sample_step(logits.data_ptr(), logits.stride(0), uniforms.data_ptr(), seq.data_ptr(), prompt_len.data_ptr(),
+                             lens.data_ptr(), finished.data_ptr(), next_out.data_ptr(), pos_out.data_ptr(),
+                             workspace.data_ptr(), workspace.numel(), C.byref(params), B, V, seq.shape[1], _stream()),
+          "sd_sample_step")
+    return next_out, pos_out
