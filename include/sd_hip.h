@@ -11,7 +11,7 @@
  *     16-byte aligned, leading dimensions are in ELEMENTS and multiples of 8;
  *   - `stream` is a hipStream_t (torch's current stream); launchers never allocate device memory and never
  *     synchronise; scratch comes from the caller (see *_workspace_bytes).  Process state reachable from THIS header is
- *     limited to: (1) a pool of timing-disabled hipEvent_t sets, leased per sd_qwen3_backward* / sd_attn_bwd2 call and per
+ *     limited to: (1) a pool of timing-disabled hipEvent_t sets, leased per sd_qwen3_backward / sd_attn_bwd2 call and per
  *     device (two concurrent backward calls never share an event); (2) the sd_prof_* accumulators (only between
  *     sd_prof_begin/end).  The library never reads the environment.  Measurement and test switches (forced kernel variants,
  *     A/B thresholds, the CU budget of a multi-GPU run) are a separate interface, include/sd_hip_debug.h;
@@ -332,7 +332,7 @@ typedef struct {
   const sd_qwen3_layer* layers_host; /* HOST array of `layers` entries holding DEVICE pointers */
 } sd_qwen3_params;
 
-/* What a forward keeps in `acts` (the `save_for_backward` argument below):
+/* What a forward keeps in `acts` (the low bits of the `mode` argument below):
  *   SD_SAVE_NONE          inference (the frozen teacher): one layer's buffers + a ping-pong residual stream;
  *   SD_SAVE_ALL           every activation the backward reads, for all layers (default training mode);
  *   SD_SAVE_LAYER_INPUTS  layer-granular recompute = what `gradient_checkpointing_enable()` means in HF
@@ -349,7 +349,7 @@ typedef struct {
 #define SD_SAVE_ALL 1
 #define SD_SAVE_LAYER_INPUTS 2
 #define SD_SAVE_NONE_FOLDED 3
-/* OR-ed into `save` of sd_qwen3_forward(_rows): the caller runs ANOTHER pass beside this one on a second stream (the frozen
+/* OR-ed into `mode` of sd_qwen3_forward: the caller runs ANOTHER pass beside this one on a second stream (the frozen
  * teacher beside the student's forward, train.py:60-69 vs :54).  Launches are then sized for CU-time per FLOP instead of
  * for covering every CU on their own (larger tiles on fewer workgroups for the N = hidden projections); results agree with
  * the unflagged pass to bf16 rounding.  Without a second stream the flag costs time: leave it off for a pass that runs alone. */
@@ -359,79 +359,69 @@ int sd_qwen3_fold_supported(const sd_qwen3_dims* d);
 int64_t sd_qwen3_acts_bytes(const sd_qwen3_dims* d, int B, int T, int save_for_backward);
 int64_t sd_qwen3_bwd_scratch_bytes(const sd_qwen3_dims* d, int B, int T);
 
-/* ids int64 [B,T]; kv_len int32 [B] nullable; cos/sin bf16 [T,128]; acts: caller buffer of
- * sd_qwen3_acts_bytes; logits bf16 [B*T, V] out (nullable: stop after the final norm);
- * hidden_out bf16 [B*T,h] nullable */
-int sd_qwen3_forward(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* kv_len,
-                     const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes, void* logits, int B, int T,
-                     int save_for_backward, void* stream);
-/* same, with the lm_head applied only to the rows listed in head_rows (int64 [n_head_rows], flat b*T+t indices,
- * unique, device memory; NULL = all rows): logits is then bf16 [n_head_rows, V].  The training step needs only the
- * rows whose shifted label is not -100 (distillation_loss.py:37-45); HF computes all of them (train.py:54-55). */
-int sd_qwen3_forward_rows(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* kv_len,
-                          const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes, void* logits,
-                          const int64_t* head_rows, int n_head_rows, int B, int T, int save_for_backward, void* stream);
-/* g: same structure as p but holding gradient buffers (bf16, same shapes); dlogits bf16 [B*T,V];
- * accumulate: bit set of SD_BWD_ACCUMULATE (add to the gradient buffers: gradient accumulation; otherwise overwrite)
- * and SD_BWD_RECOMPUTE (`acts` was written by a forward with SD_SAVE_LAYER_INPUTS).
+/* One call's tokens, the same descriptor for a forward and for the backward of that forward.
+ *   padded: ids int64 [B,T]; kv_len int32 [B] nullable (right padding); cos/sin bf16 [T,128];
+ *   packed: vl given (sd_varlen above), then kv_len = NULL, B = 1, T = M: ids int64 [M], attention per document, and
+ *     cos/sin are PER-TOKEN tables bf16 [M,128] (row m holds the rotary angles of token m's position in its document),
+ *     read unchanged by the rope consumers.  acts / scratch are sized for B = 1, T = M.  Only the attention calls differ.
+ *   head_rows (int64 [n_head_rows], flat b*T+t indices, unique, device memory; NULL = every row): the lm_head runs on
+ *     those rows only, logits and dlogits are then bf16 [n_head_rows, V].  The training step needs only the rows whose
+ *     shifted label is not -100 (distillation_loss.py:37-45); HF computes all of them (train.py:54-55).
+ * SD_ERR_SHAPE: a NULL batch, B or T <= 0, vl together with kv_len or with B != 1, n_head_rows outside [1, B*T]. */
+typedef struct {
+  const int64_t* ids;
+  const int32_t* kv_len;
+  const sd_varlen* vl;
+  const void *cos_tab, *sin_tab;
+  const int64_t* head_rows;
+  int32_t n_head_rows, B, T, pad_;
+} sd_qwen3_batch;
+/* acts: caller buffer of sd_qwen3_acts_bytes(d, B, T, mode); logits bf16 [B*T, V] or [n_head_rows, V] out (nullable:
+ * stop after the final norm); mode = SD_SAVE_* | SD_FWD_CONCURRENT, anything else is SD_ERR_SHAPE. */
+int sd_qwen3_forward(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_batch* batch, void* acts,
+                     int64_t acts_bytes, void* logits, int mode, void* stream);
+/* Backward of a forward made with the same batch.  g: same structure as p but holding gradient buffers (bf16, same
+ * shapes); dlogits bf16, shaped like the forward's logits; scratch of sd_qwen3_bwd_scratch_bytes(d, B, T).  Options
+ * (all-zero = the plain full backward on one stream):
+ * flags: SD_BWD_ACCUMULATE (add to the gradient buffers: gradient accumulation; otherwise overwrite), SD_BWD_RECOMPUTE
+ *   (`acts` was written by a forward with SD_SAVE_LAYER_INPUTS), SD_BWD_EMBED_ONLY; any other bit is SD_ERR_SHAPE.
  * on_grads_ready (nullable) is called ON THE HOST, from inside this call, each time the kernels that
- * finish one group of gradients have been enqueued on `stream`: stage = SD_STAGE_HEAD (lm_head dW
- * + final norm, before any layer), layer index L-1..0 (that layer's 8 tensors), SD_STAGE_EMBED (the
- * embedding scatter-add, last).  A data-parallel caller records an event there and starts that
- * bucket's RCCL all-reduce on a second stream, overlapping it with the rest of backward.
+ *   finish one group of gradients have been enqueued on `stream`: stage = SD_STAGE_HEAD (lm_head dW
+ *   + final norm, before any layer), layer index L-1..0 (that layer's 8 tensors), SD_STAGE_EMBED (the
+ *   embedding scatter-add, last).  A data-parallel caller records an event there and starts that
+ *   bucket's RCCL all-reduce on a second stream, overlapping it with the rest of backward.
  * side_stream (nullable hipStream_t): when given, the weight-gradient GEMMs of a layer (dW = dY^T X, which
- * nothing else in the layer depends on) are launched there and overlap the dX chain on `stream`; ordering
- * is by HIP events, `stream` has waited for all of them when the call returns (and before each callback).
+ *   nothing else in the layer depends on) are launched there and overlap the dX chain on `stream`; ordering
+ *   is by HIP events, `stream` has waited for all of them when the call returns (and before each callback).
  * dx0_out (nullable, bf16 [B*T,h]): when given, the gradient w.r.t. the embedding OUTPUT is written there and
- * the local embedding scatter-add is skipped -- the data-parallel caller then reduces the dense (lm_head)
- * part of the tied gradient early and exchanges only the B*T touched rows (ddp.py). */
+ *   the local embedding scatter-add is skipped -- the data-parallel caller then reduces the dense (lm_head)
+ *   part of the tied gradient early and exchanges only the B*T touched rows (ddp.py).
+ * SD_BWD_EMBED_ONLY: the Stage-1 alignment backward (stage1.py:29-73 freeze_model_weights: every decoder weight frozen,
+ *   the embedding / lm_head gradients masked to rows >= old_vocab = V - num_new_tokens).  grad_row_lo (read only with
+ *   this flag; 0 <= grad_row_lo <= V, any value: the < 8 rows before the first multiple of 8 are handled apart from the
+ *   aligned GEMM); dx0_out or on_grads_ready with it is SD_ERR_SHAPE.  Writes ONLY rows [grad_row_lo, V) of g->embed, and
+ *   of g->lm_head when untied; never reads or writes the rows below grad_row_lo or any other gradient buffer
+ *   (g->layers_host and g->final_norm may be NULL).  Launches the dX chain of the full backward (SD_BWD_RECOMPUTE
+ *   honoured), no per-layer weight or gain gradient, the lm_head dW of the new rows beside the lm_head dX on side_stream,
+ *   then sd_embedding_bwd_range. */
 #define SD_STAGE_HEAD (-1)
 #define SD_STAGE_EMBED (-2)
 #define SD_BWD_ACCUMULATE 1
 #define SD_BWD_RECOMPUTE 2
+#define SD_BWD_EMBED_ONLY 4
 typedef void (*sd_stage_cb)(int stage, void* user);
-int sd_qwen3_backward(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g, const int64_t* ids,
-                      const int32_t* kv_len, const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes,
-                      void* dlogits, void* scratch, int64_t scratch_bytes, int B, int T, int accumulate,
-                      void* dx0_out, sd_stage_cb on_grads_ready, void* cb_user, void* side_stream, void* stream);
-/* same for a forward made by sd_qwen3_forward_rows with the same head_rows: dlogits is bf16 [n_head_rows, V] */
-int sd_qwen3_backward_rows(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g, const int64_t* ids,
-                           const int32_t* kv_len, const void* cos_tab, const void* sin_tab, void* acts,
-                           int64_t acts_bytes, void* dlogits, const int64_t* head_rows, int n_head_rows, void* scratch,
-                           int64_t scratch_bytes, int B, int T, int accumulate, void* dx0_out,
-                           sd_stage_cb on_grads_ready, void* cb_user, void* side_stream, void* stream);
-/* Stage-1 alignment backward (stage1.py:29-73 freeze_model_weights: every decoder weight frozen, the embedding / lm_head
- * gradients masked to rows >= old_vocab = V - num_new_tokens).  Same arguments as sd_qwen3_backward_rows without dx0_out and
- * the stage callback, plus grad_row_lo (0 <= grad_row_lo <= V, any value: the < 8 rows before the first multiple of 8 are
- * handled apart from the aligned GEMM).  Writes ONLY rows [grad_row_lo, V) of g->embed, and of g->lm_head when untied
- * (SD_BWD_ACCUMULATE adds, otherwise overwrites); never reads or writes the rows below grad_row_lo or any other gradient
- * buffer (g->layers_host and g->final_norm may be NULL).  Launches the dX chain of the full backward (SD_BWD_RECOMPUTE
- * honoured), no per-layer weight or gain gradient, the lm_head dW of the new rows beside the lm_head dX on side_stream,
- * then sd_embedding_bwd_range. */
-int sd_qwen3_backward_embed_rows(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g,
-                                 const int64_t* ids, const int32_t* kv_len, const void* cos_tab, const void* sin_tab,
-                                 void* acts, int64_t acts_bytes, void* dlogits, const int64_t* head_rows, int n_head_rows,
-                                 void* scratch, int64_t scratch_bytes, int B, int T, int accumulate, int grad_row_lo,
-                                 void* side_stream, void* stream);
-/* The three runner entries over packed documents (sd_varlen above): the _rows entries with the descriptor and M in place
- * of kv_len, B, T.  ids int64 [M]; head_rows are flat token indices; acts / scratch are sized for B = 1, T = M
- * (sd_qwen3_acts_bytes(d, 1, M, mode), sd_qwen3_bwd_scratch_bytes(d, 1, M)).  RoPE: cos/sin are PER-TOKEN tables bf16
- * [M,128] (row m holds the rotary angles of token m's position in its document), read unchanged by the rope consumers
- * with T = M.  Every forward mode, the recompute bit and the three backwards work as in the padded entries; only the
- * attention calls differ. */
-int sd_qwen3_forward_varlen(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const sd_varlen* vl,
-                            const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes, void* logits,
-                            const int64_t* head_rows, int n_head_rows, int M, int save_for_backward, void* stream);
-int sd_qwen3_backward_varlen(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g, const int64_t* ids,
-                             const sd_varlen* vl, const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes,
-                             void* dlogits, const int64_t* head_rows, int n_head_rows, void* scratch,
-                             int64_t scratch_bytes, int M, int accumulate, void* dx0_out, sd_stage_cb on_grads_ready,
-                             void* cb_user, void* side_stream, void* stream);
-int sd_qwen3_backward_embed_varlen(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g,
-                                   const int64_t* ids, const sd_varlen* vl, const void* cos_tab, const void* sin_tab,
-                                   void* acts, int64_t acts_bytes, void* dlogits, const int64_t* head_rows,
-                                   int n_head_rows, void* scratch, int64_t scratch_bytes, int M, int accumulate,
-                                   int grad_row_lo, void* side_stream, void* stream);
+typedef struct {
+  int32_t flags;
+  int32_t grad_row_lo;
+  void* dx0_out;
+  sd_stage_cb on_grads_ready;
+  void* cb_user;
+  void* side_stream;
+} sd_qwen3_bwd_opts;
+int sd_qwen3_backward(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g,
+                      const sd_qwen3_batch* batch, void* acts, int64_t acts_bytes, void* dlogits, void* scratch,
+                      int64_t scratch_bytes, const sd_qwen3_bwd_opts* opts, void* stream);
+/* ABI 2 folded the _rows, _varlen, _embed_rows and _embed_varlen twins of these entries into the batch and the options. */
 
 /* ---- MXFP8 frozen teacher (train.py:60-69, 155-169: the teacher is loaded once, frozen, and only ever run forward; the
  * reference offers it in 8 bit through bitsandbytes, train.py:155-162 -- this is the format gfx950 has hardware for, not
@@ -460,8 +450,7 @@ int sd_gemm_mxfp8_swiglu(const void* a_q, const void* a_scale, const void* wgu_q
  * Launches per layer: quant(x)+rstd, q|k|v GEMM, sd_qknorm_rope_fwd, attention, quant(ao), o GEMM + residual,
  * quant(x_mid)+rstd, gate|up GEMM + SwiGLU -> MXFP8, down GEMM + residual.
  * sd_qwen3_mx_supported: head_dim 128, hidden and inter multiples of 128.  `flags`: 0 or SD_FWD_CONCURRENT.  The other
- * arguments are those of sd_qwen3_forward_rows / sd_qwen3_forward_varlen; acts of sd_qwen3_mx_acts_bytes(d, B, T)
- * (B = 1, T = M for the packed entry). */
+ * arguments are those of sd_qwen3_forward; acts of sd_qwen3_mx_acts_bytes(d, B, T). */
 typedef struct {
   void *wqkv_q, *wqkv_scale, *wo_q, *wo_scale, *wgu_q, *wgu_scale, *wdown_q, *wdown_scale; /* e4m3 [N,K] + E8M0 [N,K/32] */
   void *q_gain, *k_gain;                                                                    /* bf16 [128] */
@@ -474,13 +463,8 @@ typedef struct {
 } sd_qwen3_params_mx;
 int sd_qwen3_mx_supported(const sd_qwen3_dims* d);
 int64_t sd_qwen3_mx_acts_bytes(const sd_qwen3_dims* d, int B, int T);
-int sd_qwen3_forward_mx(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids, const int32_t* kv_len,
-                        const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes, void* logits,
-                        const int64_t* head_rows, int n_head_rows, int B, int T, int flags, void* stream);
-int sd_qwen3_forward_mx_varlen(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids,
-                               const sd_varlen* vl, const void* cos_tab, const void* sin_tab, void* acts,
-                               int64_t acts_bytes, void* logits, const int64_t* head_rows, int n_head_rows, int M,
-                               int flags, void* stream);
+int sd_qwen3_forward_mx(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const sd_qwen3_batch* batch, void* acts,
+                        int64_t acts_bytes, void* logits, int flags, void* stream);
 
 /* ---- KV-cache generation (the reference's inference engine: soulxpodcast/engine/llm_engine.py:37-76 decodes one token per
  * step over a KV cache with the sampling recipe of soulxpodcast/config.py:107-118 and the repetition-aware rule of
@@ -547,9 +531,9 @@ int sd_sample_step(const void* logits, int64_t row_stride, const float* uniforms
                    int32_t* len, uint8_t* finished, int64_t* next_out, int32_t* pos_out, void* workspace,
                    int64_t workspace_bytes, const sd_sample_params* sp, int B, int V, int cap, void* stream);
 /* The runner over the cache (unfolded bf16 weights only).
- * sd_qwen3_prefill: the SD_SAVE_NONE forward of sd_qwen3_forward_rows with sd_kvcache_store after each layer's q|k|v step
+ * sd_qwen3_prefill: the SD_SAVE_NONE forward of sd_qwen3_forward with sd_kvcache_store after each layer's q|k|v step
  *   and the lm_head on the last valid row of each sequence (sd_last_rows, on the device): logits bf16 [B,V], bit-identical
- *   to sd_qwen3_forward_rows on those rows.  cos/sin [T,128]; acts of sd_qwen3_prefill_acts_bytes(d, B, T); T <= cap.
+ *   to sd_qwen3_forward with those head_rows.  cos/sin [T,128]; acts of sd_qwen3_prefill_acts_bytes(d, B, T); T <= cap.
  * sd_qwen3_decode_step: ids int64 [B] (device: the sampler's next_out), pos int32 [B] (device: the sampler's pos_out, the
  *   tokens already cached per row), max_len = host upper bound of every pos[b] + 1; cos/sin [cap,128].  Per layer: RMSNorm,
  *   q|k|v GEMM, sd_qknorm_rope_append, sd_attn_decode (len = pos + 1), o GEMM + residual, RMSNorm, gate|up + SwiGLU

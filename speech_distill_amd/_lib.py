@@ -80,12 +80,25 @@ class Params(C.Structure):
                 ("layers_host", C.POINTER(Layer))]
 
 
+ABI_VERSION = 2        # what sd_abi_version() of the library these prototypes were written for returns
 SUMSQ_PARTIALS = 2048  # include/sd_hip.h SD_SUMSQ_PARTIALS
 
 KINDS = ["gemm_nt", "gemm_nn", "gemm_tn", "attn_fwd", "attn_bwd_dkv", "attn_bwd_dq", "loss_fwd", "loss_bwd", "topk",
          "rmsnorm", "qknorm_rope", "swiglu", "embedding", "optim", "misc", "gemm_nt_stag"]
 
 STAGE_CB = C.CFUNCTYPE(None, C.c_int, C.c_void_p)
+
+
+class Batch(C.Structure):  # include/sd_hip.h sd_qwen3_batch
+    _fields_ = [("ids", C.c_void_p), ("kv_len", C.c_void_p), ("vl", C.POINTER(Varlen)), ("cos_tab", C.c_void_p),
+                ("sin_tab", C.c_void_p), ("head_rows", C.c_void_p), ("n_head_rows", C.c_int32), ("B", C.c_int32),
+                ("T", C.c_int32), ("pad_", C.c_int32)]
+
+
+class BwdOpts(C.Structure):  # include/sd_hip.h sd_qwen3_bwd_opts
+    _fields_ = [("flags", C.c_int32), ("grad_row_lo", C.c_int32), ("dx0_out", C.c_void_p), ("on_grads_ready", STAGE_CB),
+                ("cb_user", C.c_void_p), ("side_stream", C.c_void_p)]
+
 
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 # name -> (restype, argtypes); must list every symbol include/sd_hip.h declares (tests check this)
@@ -160,28 +173,15 @@ PROTOTYPES = {
     "sd_prof_symbols": (_i64, [_vp, _i64]),
     "sd_qwen3_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i, _i]),
     "sd_qwen3_bwd_scratch_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
-    "sd_qwen3_forward": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i, _i, _i, _vp]),
-    "sd_qwen3_forward_rows": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i,
-                                   _i, _vp]),
-    "sd_qwen3_backward_rows": (_i, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(Params), _vp, _vp, _vp, _vp, _vp, _i64,
-                                    _vp, _vp, _i, _vp, _i64, _i, _i, _i, _vp, STAGE_CB, _vp, _vp, _vp]),
-    "sd_qwen3_backward_embed_rows": (_i, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(Params), _vp, _vp, _vp, _vp, _vp,
-                                          _i64, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _i, _vp, _vp]),
-    "sd_qwen3_forward_varlen": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, C.POINTER(Varlen), _vp, _vp, _vp, _i64, _vp,
-                                     _vp, _i, _i, _i, _vp]),
-    "sd_qwen3_backward_varlen": (_i, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(Params), _vp, C.POINTER(Varlen), _vp,
-                                      _vp, _vp, _i64, _vp, _vp, _i, _vp, _i64, _i, _i, _vp, STAGE_CB, _vp, _vp, _vp]),
-    "sd_qwen3_backward_embed_varlen": (_i, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(Params), _vp, C.POINTER(Varlen),
-                                            _vp, _vp, _vp, _i64, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _vp, _vp]),
-    "sd_qwen3_backward": (_i, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(Params), _vp, _vp, _vp, _vp, _vp, _i64,
-                               _vp, _vp, _i64, _i, _i, _i, _vp, STAGE_CB, _vp, _vp, _vp]),
+    "sd_qwen3_forward": (_i, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(Batch), _vp, _i64, _vp, _i, _vp]),
+    "sd_qwen3_backward": (_i, [C.POINTER(Dims), C.POINTER(Params), C.POINTER(Params), C.POINTER(Batch), _vp, _i64, _vp,
+                               _vp, _i64, C.POINTER(BwdOpts), _vp]),
     "sd_mxfp8_quant": (_i, [_vp, _i64, _vp, _vp, _vp, _f, _i, _i, _vp]),
     "sd_gemm_mxfp8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i64, _vp]),
     "sd_gemm_mxfp8_swiglu": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "sd_qwen3_mx_supported": (_i, [C.POINTER(Dims)]),
     "sd_qwen3_mx_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
-    "sd_qwen3_forward_mx": (_i, [C.POINTER(Dims), C.POINTER(ParamsMx), _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i,
-                                 _i, _vp]),
+    "sd_qwen3_forward_mx": (_i, [C.POINTER(Dims), C.POINTER(ParamsMx), C.POINTER(Batch), _vp, _i64, _vp, _i, _vp]),
     "sd_kvcache_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
     "sd_kvcache_store": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "sd_last_rows": (_i, [_vp, _vp, _i, _i, _vp]),
@@ -197,8 +197,6 @@ PROTOTYPES = {
     "sd_qwen3_decode_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
     "sd_qwen3_decode_step": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _i, _vp, _vp, _vp, _i64, _i, _vp, _i64, _vp,
                                   _i, _vp]),
-    "sd_qwen3_forward_mx_varlen": (_i, [C.POINTER(Dims), C.POINTER(ParamsMx), _vp, C.POINTER(Varlen), _vp, _vp, _vp, _i64,
-                                        _vp, _vp, _i, _i, _i, _vp]),
 }
 
 
@@ -213,6 +211,9 @@ def load_lib():
             f"{path} not found: build it with `make -C speech_distill_amd/csrc` (hipcc --offload-arch=gfx950). "
             "speech_distill_amd has no CPU fallback.")
     lib = C.CDLL(path)
+    if lib.sd_abi_version() != ABI_VERSION:   # before any prototype is bound: a stale build fails here, not at a symbol
+        raise SdHipError(f"{path} has ABI version {lib.sd_abi_version()}, this package is written for {ABI_VERSION}: "
+                         "rebuild it with `make -C speech_distill_amd/csrc`")
     for name, (res, args) in list(PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = res, args

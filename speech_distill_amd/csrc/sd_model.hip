@@ -11,17 +11,13 @@
 #include "sd_debug.h"
 #include "sd_common.cuh"
 #include "sd_prof.h"
+#include "sd_runner.h"
 
 namespace {
 
-inline int64_t al(int64_t x) { return (x + 255) & ~(int64_t)255; }
-
-struct Sizes {
-  int M, h, I, QD, KD, QKV, QK, V, L, Hq, Hkv;
+struct Sizes : SdShape {
   int64_t x, rstd, qkv, qk, ao, lse, gu, act;
-  Sizes(const sd_qwen3_dims* d, int B, int T) {
-    M = B * T; h = d->hidden; I = d->inter; Hq = d->n_q; Hkv = d->n_kv;
-    QD = Hq * d->head_dim; KD = Hkv * d->head_dim; QKV = QD + 2 * KD; QK = QD + KD; V = d->vocab; L = d->layers;
+  Sizes(const sd_qwen3_dims* d, int B, int T) : SdShape(d, B, T) {
     x = al((int64_t)M * h * 2); rstd = al((int64_t)M * 4); qkv = al((int64_t)M * QKV * 2); qk = al((int64_t)M * QK * 2);
     ao = al((int64_t)M * QD * 2); lse = al((int64_t)B * Hq * T * 4); gu = al((int64_t)M * 2 * I * 2);
     act = al((int64_t)M * I * 2);
@@ -93,25 +89,12 @@ struct BwdScratch {
   }
 };
 
-#define RUN(call) do { int e__ = (call); if (e__) return e__; } while (0)
-
 // where layer l's buffers live in `acts` for a training forward (SD_SAVE_ALL / SD_SAVE_LAYER_INPUTS)
 LayerActs layer_acts(const Sizes& s, char* base, int l, int save) {
   if (save == SD_SAVE_ALL) return carve(s, base + (int64_t)l * s.per_layer());
   LayerActs a = carve(s, base + (int64_t)s.L * s.x + (int64_t)(l & 1) * s.per_layer());
   a.x_in = base + (int64_t)l * s.x;
   return a;
-}
-
-// The layer's attention: per batch row (kv_len: right padding), or per packed document when vl is given (B = 1, T = M)
-int layer_attn_fwd(const Sizes& s, const LayerActs& a, const int32_t* kv_len, const sd_varlen* vl, int B, int T,
-                   void* stream) {
-  const float scale = 0.08838834764831845f;  // 128^-1/2
-  if (vl)
-    return sd_attn_fwd_varlen(a.qk, a.qk + (int64_t)s.QD * 2, a.qkv + (int64_t)(s.QD + s.KD) * 2, a.ao, (float*)a.lse, vl,
-                              s.QK, s.QK, s.QKV, s.QD, s.M, s.Hq, s.Hkv, 128, scale, stream);
-  return sd_attn_fwd(a.qk, a.qk + (int64_t)s.QD * 2, a.qkv + (int64_t)(s.QD + s.KD) * 2, a.ao, (float*)a.lse, kv_len,
-                     s.QK, s.QK, s.QKV, s.QD, B, T, s.Hq, s.Hkv, 128, scale, stream);
 }
 
 // Where a prefill leaves the keys and values of its layers: the cache [L][2][B][cap][Hkv*128] of sd_kvcache_bytes
@@ -127,8 +110,9 @@ struct KvSink {
 // stops after the SwiGLU (the backward's recompute does not need the layer output again); keep_gu: gate|up is kept
 // for the backward.  sink (sd_qwen3_prefill): the layer's K / V rows below kv_len also go to planes l of the cache.
 int layer_forward(const sd_qwen3_dims* d, const Sizes& s, const LayerActs& a, const sd_qwen3_layer& w, char* x_out,
-                  bool keep_gu, const int32_t* kv_len, const sd_varlen* vl, const void* cos_tab, const void* sin_tab,
-                  int B, int T, void* stream, const KvSink* sink = nullptr, int l = 0) {
+                  bool keep_gu, const sd_qwen3_batch& bt, void* stream, const KvSink* sink = nullptr, int l = 0) {
+  const int B = bt.B, T = bt.T;
+  const void *cos_tab = bt.cos_tab, *sin_tab = bt.sin_tab;
   RUN(sd_rmsnorm_fwd(a.x_in, w.ln1, a.xn1, (float*)a.rstd1, s.M, s.h, d->eps, stream));
   // q|k|v projection with q/k-norm + RoPE in the GEMM epilogue (one head = one 128-column tile)
   int rc = sd_gemm_qkv_rope(a.xn1, w.wqkv, a.qkv, a.qk, w.q_gain, w.k_gain, cos_tab, sin_tab, s.M, T, s.Hq, s.Hkv, s.h,
@@ -140,9 +124,9 @@ int layer_forward(const sd_qwen3_dims* d, const Sizes& s, const LayerActs& a, co
     return rc;
   }
   if (sink)
-    RUN(sd_kvcache_store(a.qk, a.qkv, sink->plane(s, B, l, 0), sink->plane(s, B, l, 1), kv_len, B, T, sink->cap, s.Hq,
+    RUN(sd_kvcache_store(a.qk, a.qkv, sink->plane(s, B, l, 0), sink->plane(s, B, l, 1), bt.kv_len, B, T, sink->cap, s.Hq,
                          s.Hkv, stream));
-  RUN(layer_attn_fwd(s, a, kv_len, vl, B, T, stream));
+  RUN(sd_layer_attn_fwd(s, bt, a.qk, a.qkv, a.ao, a.lse, stream));
   RUN(sd_gemm_bf16(a.ao, w.wo, a.x_mid, a.x_in, s.M, s.h, s.QD, s.QD, s.QD, s.h, s.h, 0, 0, stream));
   RUN(sd_rmsnorm_fwd(a.x_mid, w.ln2, a.xn2, (float*)a.rstd2, s.M, s.h, d->eps, stream));
   // gate|up projection: SwiGLU runs in the GEMM epilogue when gate|up need not be kept (no backward follows:
@@ -167,11 +151,10 @@ int layer_forward(const sd_qwen3_dims* d, const Sizes& s, const LayerActs& a, co
 // (from the embedding or the previous layer's down projection); ssq_mid: scratch for those of a.x_mid; ssq_next
 // (nullable): where the down projection leaves those of x_out for the next layer.  w.ln1 / w.ln2 are not read.
 int layer_forward_folded(const sd_qwen3_dims* d, const Sizes& s, const LayerActs& a, const sd_qwen3_layer& w, char* x_out,
-                         const int32_t* kv_len, const sd_varlen* vl, const void* cos_tab, const void* sin_tab, int B, int T,
-                         const float* ssq_in, float* ssq_mid, float* ssq_next, void* stream) {
-  RUN(sd_gemm_qkv_rope_rs(a.x_in, w.wqkv, a.qkv, a.qk, w.q_gain, w.k_gain, cos_tab, sin_tab, ssq_in, s.M, T, s.Hq, s.Hkv,
-                          s.h, d->eps, stream));
-  RUN(layer_attn_fwd(s, a, kv_len, vl, B, T, stream));
+                         const sd_qwen3_batch& bt, const float* ssq_in, float* ssq_mid, float* ssq_next, void* stream) {
+  RUN(sd_gemm_qkv_rope_rs(a.x_in, w.wqkv, a.qkv, a.qk, w.q_gain, w.k_gain, bt.cos_tab, bt.sin_tab, ssq_in, s.M, bt.T, s.Hq,
+                          s.Hkv, s.h, d->eps, stream));
+  RUN(sd_layer_attn_fwd(s, bt, a.qk, a.qkv, a.ao, a.lse, stream));
   RUN(sd_gemm_bf16_ssq(a.ao, w.wo, a.x_mid, a.x_in, ssq_mid, s.M, s.h, s.QD, s.QD, s.QD, s.h, s.h, stream));
   RUN(sd_gemm_swiglu_rs(a.x_mid, w.wgu, nullptr, a.act, ssq_mid, d->eps, s.M, s.I, s.h, stream));
   if (ssq_next) RUN(sd_gemm_bf16_ssq(a.act, w.wdown, x_out, a.x_mid, ssq_next, s.M, s.h, s.I, s.I, s.I, s.h, s.h, stream));
@@ -185,8 +168,8 @@ bool fold_supported(const sd_qwen3_dims* d) {
 }
 
 
-// Stage-1 lm_head dW rows [lo, hi) with hi - lo < 8, hi = lo rounded up to 8: the rows the aligned GEMM of
-// sd_qwen3_backward_embed_rows cannot start at (its operands must be 16-byte aligned).  dW[r,:] (+)= sum_k dY[k,r] X[k,:]
+// Stage-1 lm_head dW rows [lo, hi) with hi - lo < 8, hi = lo rounded up to 8: the rows at which the aligned GEMM of
+// the SD_BWD_EMBED_ONLY backward cannot start (its operands must be 16-byte aligned).  dW[r,:] (+)= sum_k dY[k,r] X[k,:]
 // for k < K in increasing k per wave, the 16 waves' partials summed in wave order: deterministic.  One 16-byte load of dY
 // covers every row of the strip (they share one aligned group of 8 columns).
 constexpr int kStripWaves = 16;
@@ -273,7 +256,7 @@ void sd_return_events(SdEventSet* s) {
   g_ev_free.push_back(s);
 }
 
-extern "C" int sd_abi_version(void) { return 1; }
+extern "C" int sd_abi_version(void) { return 2; }
 
 extern "C" int sd_qwen3_fold_supported(const sd_qwen3_dims* d) { return d && fold_supported(d) ? 1 : 0; }
 
@@ -291,22 +274,13 @@ extern "C" int64_t sd_qwen3_bwd_scratch_bytes(const sd_qwen3_dims* d, int B, int
   return b.total;
 }
 
-extern "C" int sd_qwen3_forward(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
-                                const int32_t* kv_len, const void* cos_tab, const void* sin_tab, void* acts,
-                                int64_t acts_bytes, void* logits, int B, int T, int save, void* stream) {
-  return sd_qwen3_forward_rows(d, p, ids, kv_len, cos_tab, sin_tab, acts, acts_bytes, logits, nullptr, 0, B, T, save,
-                               stream);
-}
-
-// The forward of every entry: per batch row (kv_len), or per packed document when vl is given (B = 1, T = M)
-static int forward_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* kv_len,
-                        const sd_varlen* vl, const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes,
-                        void* logits, const int64_t* head_rows, int n_head_rows, int B, int T, int save, void* stream,
-                        const KvSink* sink = nullptr) {
+// The forward of both entries: per batch row (kv_len), or per packed document when bt->vl is given (B = 1, T = M)
+static int forward_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_batch* bt, void* acts,
+                        int64_t acts_bytes, void* logits, int save, void* stream, const KvSink* sink) {
   if (d->head_dim != 128) return SD_ERR_UNSUPPORTED;
-  if (B <= 0 || T <= 0) return SD_ERR_SHAPE;
-  if (sink && (vl || (save & ~SD_FWD_CONCURRENT) != SD_SAVE_NONE)) return SD_ERR_SHAPE;
-  if (head_rows && (n_head_rows <= 0 || n_head_rows > B * T)) return SD_ERR_SHAPE;
+  RUN(sd_batch_check(bt));
+  const int B = bt->B, T = bt->T;
+  if (sink && (bt->vl || (save & ~SD_FWD_CONCURRENT) != SD_SAVE_NONE)) return SD_ERR_SHAPE;
   Sizes s(d, B, T);
   const bool concurrent = (save & SD_FWD_CONCURRENT) != 0;
   save &= ~SD_FWD_CONCURRENT;
@@ -329,8 +303,8 @@ static int forward_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const 
   float* ssq_b = (float*)(tail + s.tail() + s.ssq());
 
   char* x_cur = save ? layer_acts(s, base, 0, save).x_in : base;
-  if (folded) RUN(sd_embedding_fwd_ssq(ids, p->embed, x_cur, ssq_a, s.M, s.h, s.V, stream));
-  else RUN(sd_embedding_fwd(ids, p->embed, x_cur, s.M, s.h, s.V, stream));
+  if (folded) RUN(sd_embedding_fwd_ssq(bt->ids, p->embed, x_cur, ssq_a, s.M, s.h, s.V, stream));
+  else RUN(sd_embedding_fwd(bt->ids, p->embed, x_cur, s.M, s.h, s.V, stream));
   for (int l = 0; l < s.L; ++l) {
     LayerActs a = save ? layer_acts(s, base, l, save) : carve(s, base);
     a.x_in = x_cur;
@@ -341,64 +315,41 @@ static int forward_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const 
     if (save) x_out = (l + 1 < s.L) ? layer_acts(s, base, l + 1, save).x_in : x_last;
     else x_out = (l + 1 < s.L) ? ((x_cur == pong) ? base : pong) : x_last;
     if (folded)
-      RUN(layer_forward_folded(d, s, a, p->layers_host[l], x_out, kv_len, vl, cos_tab, sin_tab, B, T, ssq_a, ssq_b,
-                               l + 1 < s.L ? ssq_a : nullptr, stream));
+      RUN(layer_forward_folded(d, s, a, p->layers_host[l], x_out, *bt, ssq_a, ssq_b, l + 1 < s.L ? ssq_a : nullptr,
+                               stream));
     else
-      RUN(layer_forward(d, s, a, p->layers_host[l], x_out, save != SD_SAVE_NONE, kv_len, vl, cos_tab, sin_tab, B, T,
-                        stream, sink, l));
+      RUN(layer_forward(d, s, a, p->layers_host[l], x_out, save != SD_SAVE_NONE, *bt, stream, sink, l));
     x_cur = x_out;
   }
-  RUN(sd_rmsnorm_fwd(x_last, p->final_norm, xn_f, (float*)rstd_f, s.M, s.h, d->eps, stream));
-  if (logits && head_rows) {
-    // lm_head only for the rows the loss will read (HF computes all B*T rows, train.py:54-55; the rows whose shifted
-    // label is -100 never reach the loss, distillation_loss.py:37-45)
-    RUN(sd_embedding_fwd(head_rows, xn_f, xn_rows, n_head_rows, s.h, s.M, stream));
-    RUN(sd_gemm_bf16(xn_rows, p->lm_head, logits, nullptr, n_head_rows, s.V, s.h, s.h, s.h, s.V, 0, 0, 0, stream));
-  } else if (logits) {
-    RUN(sd_gemm_bf16(xn_f, p->lm_head, logits, nullptr, s.M, s.V, s.h, s.h, s.h, s.V, 0, 0, 0, stream));
-  }
-  return 0;
+  return sd_head_fwd(d, s, *bt, x_last, p->final_norm, p->lm_head, rstd_f, xn_f, xn_rows, logits, stream);
 }
 
-extern "C" int sd_qwen3_forward_rows(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
-                                     const int32_t* kv_len, const void* cos_tab, const void* sin_tab, void* acts,
-                                     int64_t acts_bytes, void* logits, const int64_t* head_rows, int n_head_rows, int B,
-                                     int T, int save, void* stream) {
-  return forward_impl(d, p, ids, kv_len, nullptr, cos_tab, sin_tab, acts, acts_bytes, logits, head_rows, n_head_rows, B, T,
-                      save, stream);
+extern "C" int sd_qwen3_forward(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_batch* batch, void* acts,
+                                int64_t acts_bytes, void* logits, int mode, void* stream) {
+  return forward_impl(d, p, batch, acts, acts_bytes, logits, mode, stream, nullptr);
 }
 
-extern "C" int sd_qwen3_forward_varlen(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
-                                       const sd_varlen* vl, const void* cos_tab, const void* sin_tab, void* acts,
-                                       int64_t acts_bytes, void* logits, const int64_t* head_rows, int n_head_rows, int M,
-                                       int save, void* stream) {
-  if (!vl) return SD_ERR_SHAPE;
-  return forward_impl(d, p, ids, nullptr, vl, cos_tab, sin_tab, acts, acts_bytes, logits, head_rows, n_head_rows, 1, M,
-                      save, stream);
-}
-
+// The student backward.  Without SD_BWD_EMBED_ONLY: every gradient.  With it (Stage-1): the same dX chain, no per-layer
+// weight / gain gradient, the lm_head dW over rows [grad_row_lo, V) only and the embedding scatter restricted to
+// ids >= grad_row_lo.
 extern "C" int sd_qwen3_backward(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g,
-                                 const int64_t* ids, const int32_t* kv_len, const void* cos_tab, const void* sin_tab,
-                                 void* acts, int64_t acts_bytes, void* dlogits, void* scratch, int64_t scratch_bytes, int B,
-                                 int T, int accumulate, void* dx0_out, sd_stage_cb on_grads_ready, void* cb_user,
-                                 void* side_stream, void* stream) {
-  return sd_qwen3_backward_rows(d, p, g, ids, kv_len, cos_tab, sin_tab, acts, acts_bytes, dlogits, nullptr, 0, scratch,
-                                scratch_bytes, B, T, accumulate, dx0_out, on_grads_ready, cb_user, side_stream, stream);
-}
-
-// The student backward.  grad_row_lo < 0: every gradient (sd_qwen3_backward_rows).  grad_row_lo >= 0: Stage-1
-// (sd_qwen3_backward_embed_rows): the same dX chain, no per-layer weight / gain gradient, the lm_head dW over rows
-// [grad_row_lo, V) only and the embedding scatter restricted to ids >= grad_row_lo.
-static int backward_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g, const int64_t* ids,
-                         const int32_t* kv_len, const sd_varlen* vl, const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes,
-                         void* dlogits, const int64_t* head_rows, int n_head_rows, void* scratch, int64_t scratch_bytes,
-                         int B, int T, int accumulate, void* dx0_out, sd_stage_cb on_grads_ready, void* cb_user,
-                         void* side_stream, void* stream, int grad_row_lo) {
+                                 const sd_qwen3_batch* bt, void* acts, int64_t acts_bytes, void* dlogits, void* scratch,
+                                 int64_t scratch_bytes, const sd_qwen3_bwd_opts* opts, void* stream) {
   if (d->head_dim != 128) return SD_ERR_UNSUPPORTED;
-  const bool dw = grad_row_lo < 0;  // per-layer weight and gain gradients wanted
-  if (!dw && (grad_row_lo > d->vocab || dx0_out || on_grads_ready)) return SD_ERR_SHAPE;
-  if (head_rows && (n_head_rows <= 0 || n_head_rows > B * T)) return SD_ERR_SHAPE;
-  if (B <= 0 || T <= 0 || (accumulate & ~(SD_BWD_ACCUMULATE | SD_BWD_RECOMPUTE))) return SD_ERR_SHAPE;
+  RUN(sd_batch_check(bt));
+  if (!opts) return SD_ERR_SHAPE;
+  const sd_qwen3_bwd_opts& o = *opts;
+  const int accumulate = o.flags & ~SD_BWD_EMBED_ONLY, grad_row_lo = o.grad_row_lo;
+  const bool dw = !(o.flags & SD_BWD_EMBED_ONLY);  // per-layer weight and gain gradients wanted
+  void *const dx0_out = o.dx0_out, *const cb_user = o.cb_user, *const side_stream = o.side_stream;
+  const sd_stage_cb on_grads_ready = o.on_grads_ready;
+  const int64_t *const ids = bt->ids, *const head_rows = bt->head_rows;
+  const int32_t* const kv_len = bt->kv_len;
+  const sd_varlen* const vl = bt->vl;
+  const void *const cos_tab = bt->cos_tab, *const sin_tab = bt->sin_tab;
+  const int n_head_rows = bt->n_head_rows, B = bt->B, T = bt->T;
+  if (!dw && (grad_row_lo < 0 || grad_row_lo > d->vocab || dx0_out || on_grads_ready)) return SD_ERR_SHAPE;
+  if (accumulate & ~(SD_BWD_ACCUMULATE | SD_BWD_RECOMPUTE)) return SD_ERR_SHAPE;
   Sizes s(d, B, T);
   // SD_BWD_RECOMPUTE: `acts` came from a forward with SD_SAVE_LAYER_INPUTS; each layer's forward is run again from its
   // saved input right before its backward (the last layer's buffers are still those of the forward itself)
@@ -407,7 +358,6 @@ static int backward_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const
   BwdScratch b(s, (char*)scratch);
   if (scratch_bytes < b.total) return SD_ERR_WORKSPACE;
   char* base = (char*)acts;
-  const float scale = 0.08838834764831845f;
   char* tail = base + s.body(save);
   char* x_last = tail;
   char* rstd_f = tail + s.x;
@@ -495,7 +445,7 @@ static int backward_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const
     // recompute: this layer's work set was last read by the weight-gradient GEMMs of layer l+2, which `stream` has
     // already waited for (the `pending` join of layer l+1 below)
     if (save == SD_SAVE_LAYER_INPUTS && l != s.L - 1)
-      RUN(layer_forward(d, s, a, w, nullptr, true, kv_len, vl, cos_tab, sin_tab, B, T, stream));
+      RUN(layer_forward(d, s, a, w, nullptr, true, *bt, stream));
     // MLP
     if (!grouped && dw) {
       SIGNAL(0);  // dx_in final
@@ -530,15 +480,15 @@ static int backward_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const
       else o_for_delta = nullptr;
     }
     if (!grouped && dw) RUN(sd_gemm_bf16(dxb, a.ao, gw.wo, ACC(gw.wo), s.h, s.QD, s.M, s.h, s.QD, s.QD, s.QD, 1, 1, wstream));
+    const SdQkv f(s, a.qk, a.qkv), df(s, b.dqk, dqkv);
     if (vl)
-      RUN(sd_attn_bwd_varlen(a.qk, a.qk + (int64_t)s.QD * 2, a.qkv + (int64_t)(s.QD + s.KD) * 2, o_for_delta, b.dao,
-                             (const float*)a.lse, (float*)b.delta, b.dqk, b.dqk + (int64_t)s.QD * 2,
-                             dqkv + (int64_t)(s.QD + s.KD) * 2, vl, s.QK, s.QK, s.QKV, s.QD, s.QK, s.QK, s.QKV, s.M, s.Hq,
-                             s.Hkv, 128, scale, (ovl & 4) ? side_stream : nullptr, stream));
+      RUN(sd_attn_bwd_varlen(f.q, f.k, f.v, o_for_delta, b.dao, (const float*)a.lse, (float*)b.delta, df.q, df.k, df.v, vl,
+                             s.QK, s.QK, s.QKV, s.QD, s.QK, s.QK, s.QKV, s.M, s.Hq, s.Hkv, 128, kSdAttnScale,
+                             (ovl & 4) ? side_stream : nullptr, stream));
     else
-      RUN(sd_attn_bwd2(a.qk, a.qk + (int64_t)s.QD * 2, a.qkv + (int64_t)(s.QD + s.KD) * 2, o_for_delta, b.dao, (const float*)a.lse,
-                      (float*)b.delta, b.dqk, b.dqk + (int64_t)s.QD * 2, dqkv + (int64_t)(s.QD + s.KD) * 2, kv_len, s.QK,
-                      s.QK, s.QKV, s.QD, s.QK, s.QK, s.QKV, B, T, s.Hq, s.Hkv, 128, scale, (ovl & 4) ? side_stream : nullptr, stream));
+      RUN(sd_attn_bwd2(f.q, f.k, f.v, o_for_delta, b.dao, (const float*)a.lse, (float*)b.delta, df.q, df.k, df.v, kv_len,
+                       s.QK, s.QK, s.QKV, s.QD, s.QK, s.QK, s.QKV, B, T, s.Hq, s.Hkv, 128, kSdAttnScale,
+                       (ovl & 4) ? side_stream : nullptr, stream));
     RUN(sd_qknorm_rope_bwd2(b.dqk, a.qkv, w.q_gain, w.k_gain, cos_tab, sin_tab, dqkv, batch_gains ? nullptr : gw.q_gain,
                             batch_gains ? nullptr : gw.k_gain, acc, b.ws_qk[P], s.M, T, s.Hq, s.Hkv, d->eps,
                             ((ovl & 2) && dw) ? side_stream : nullptr, (s2 && dw) ? (void*)g_ev[9] : nullptr, stream));
@@ -605,48 +555,6 @@ static int backward_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const
   return 0;
 }
 
-extern "C" int sd_qwen3_backward_rows(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g,
-                                      const int64_t* ids, const int32_t* kv_len, const void* cos_tab, const void* sin_tab,
-                                      void* acts, int64_t acts_bytes, void* dlogits, const int64_t* head_rows,
-                                      int n_head_rows, void* scratch, int64_t scratch_bytes, int B, int T, int accumulate,
-                                      void* dx0_out, sd_stage_cb on_grads_ready, void* cb_user, void* side_stream,
-                                      void* stream) {
-  return backward_impl(d, p, g, ids, kv_len, nullptr, cos_tab, sin_tab, acts, acts_bytes, dlogits, head_rows, n_head_rows,
-                       scratch, scratch_bytes, B, T, accumulate, dx0_out, on_grads_ready, cb_user, side_stream, stream, -1);
-}
-
-extern "C" int sd_qwen3_backward_embed_rows(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g,
-                                            const int64_t* ids, const int32_t* kv_len, const void* cos_tab,
-                                            const void* sin_tab, void* acts, int64_t acts_bytes, void* dlogits,
-                                            const int64_t* head_rows, int n_head_rows, void* scratch, int64_t scratch_bytes,
-                                            int B, int T, int accumulate, int grad_row_lo, void* side_stream, void* stream) {
-  if (grad_row_lo < 0) return SD_ERR_SHAPE;
-  return backward_impl(d, p, g, ids, kv_len, nullptr, cos_tab, sin_tab, acts, acts_bytes, dlogits, head_rows, n_head_rows,
-                       scratch, scratch_bytes, B, T, accumulate, nullptr, nullptr, nullptr, side_stream, stream, grad_row_lo);
-}
-
-extern "C" int sd_qwen3_backward_varlen(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g,
-                                        const int64_t* ids, const sd_varlen* vl, const void* cos_tab, const void* sin_tab,
-                                        void* acts, int64_t acts_bytes, void* dlogits, const int64_t* head_rows,
-                                        int n_head_rows, void* scratch, int64_t scratch_bytes, int M, int accumulate,
-                                        void* dx0_out, sd_stage_cb on_grads_ready, void* cb_user, void* side_stream,
-                                        void* stream) {
-  if (!vl) return SD_ERR_SHAPE;
-  return backward_impl(d, p, g, ids, nullptr, vl, cos_tab, sin_tab, acts, acts_bytes, dlogits, head_rows, n_head_rows,
-                       scratch, scratch_bytes, 1, M, accumulate, dx0_out, on_grads_ready, cb_user, side_stream, stream, -1);
-}
-
-extern "C" int sd_qwen3_backward_embed_varlen(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g,
-                                              const int64_t* ids, const sd_varlen* vl, const void* cos_tab,
-                                              const void* sin_tab, void* acts, int64_t acts_bytes, void* dlogits,
-                                              const int64_t* head_rows, int n_head_rows, void* scratch,
-                                              int64_t scratch_bytes, int M, int accumulate, int grad_row_lo,
-                                              void* side_stream, void* stream) {
-  if (!vl || grad_row_lo < 0) return SD_ERR_SHAPE;
-  return backward_impl(d, p, g, ids, nullptr, vl, cos_tab, sin_tab, acts, acts_bytes, dlogits, head_rows, n_head_rows,
-                       scratch, scratch_bytes, 1, M, accumulate, nullptr, nullptr, nullptr, side_stream, stream, grad_row_lo);
-}
-
 // ------------------------------------------------------------------------------------------ KV-cache generation
 // (engine/llm_engine.py:37-76: prefill the prompt once, then one token per step over the cache)
 extern "C" int64_t sd_qwen3_prefill_acts_bytes(const sd_qwen3_dims* d, int B, int T) {
@@ -664,8 +572,8 @@ extern "C" int sd_qwen3_prefill(const sd_qwen3_dims* d, const sd_qwen3_params* p
   int64_t* rows = (int64_t*)((char*)acts + base);
   RUN(sd_last_rows(kv_len, rows, B, T, stream));
   const KvSink sink = {(char*)cache, cap};
-  return forward_impl(d, p, ids, kv_len, nullptr, cos_tab, sin_tab, acts, base, logits, rows, B, B, T, SD_SAVE_NONE, stream,
-                      &sink);
+  const sd_qwen3_batch bt = {ids, kv_len, nullptr, cos_tab, sin_tab, rows, B, B, T, 0};
+  return forward_impl(d, p, &bt, acts, base, logits, SD_SAVE_NONE, stream, &sink);
 }
 
 namespace {
@@ -706,7 +614,6 @@ extern "C" int sd_qwen3_decode_step(const sd_qwen3_dims* d, const sd_qwen3_param
   const DecodeActs a(d, B, cap, (char*)acts);
   if (acts_bytes < a.total || cache_bytes < sd_kvcache_bytes(d, B, cap)) return SD_ERR_WORKSPACE;
   const KvSink kv = {(char*)cache, cap};
-  const float scale = 0.08838834764831845f;  // 128^-1/2
   RUN(sd_embedding_fwd(ids, p->embed, a.x, B, s.h, s.V, stream));
   for (int l = 0; l < s.L; ++l) {
     const sd_qwen3_layer& w = p->layers_host[l];
@@ -715,7 +622,7 @@ extern "C" int sd_qwen3_decode_step(const sd_qwen3_dims* d, const sd_qwen3_param
     RUN(sd_gemm_bf16(a.xn, w.wqkv, a.qkv, nullptr, B, s.QKV, s.h, s.h, s.h, s.QKV, 0, 0, 0, stream));
     RUN(sd_qknorm_rope_append(a.qkv, w.q_gain, w.k_gain, cos_tab, sin_tab, pos, a.q, kp, vp, B, cap, s.Hq, s.Hkv, d->eps,
                               stream));
-    RUN(sd_attn_decode(a.q, kp, vp, a.ao, nullptr, pos, 1, a.ws, a.ws_bytes, B, cap, max_len, s.Hq, s.Hkv, 128, scale,
+    RUN(sd_attn_decode(a.q, kp, vp, a.ao, nullptr, pos, 1, a.ws, a.ws_bytes, B, cap, max_len, s.Hq, s.Hkv, 128, kSdAttnScale,
                        stream));
     RUN(sd_gemm_bf16(a.ao, w.wo, a.x_mid, a.x, B, s.h, s.QD, s.QD, s.QD, s.h, s.h, 0, 0, stream));
     RUN(sd_rmsnorm_fwd(a.x_mid, w.ln2, a.xn, nullptr, B, s.h, d->eps, stream));

@@ -16,6 +16,7 @@
 #include "sd_debug.h"
 #include "sd_common.cuh"
 #include "sd_prof.h"
+#include "sd_runner.h"
 
 namespace {
 
@@ -372,15 +373,10 @@ extern "C" int sd_gemm_mxfp8_swiglu(const void* a_q, const void* a_scale, const 
 // ------------------------------------------------------------------------------------------ the decoder runner
 namespace {
 
-inline int64_t al(int64_t x) { return (x + 255) & ~(int64_t)255; }
-
-struct MxActs {
-  int M, h, I, QD, KD, QKV, QK, V, L, Hq, Hkv;
+struct MxActs : SdShape {
   char *x_a, *x_b, *x_mid, *xq, *xs, *rstd, *qkv, *qk, *ao, *lse, *aoq, *aos, *actq, *acts, *rstd_f, *xn_f, *xn_rows;
   int64_t total;
-  MxActs(const sd_qwen3_dims* d, int B, int T, char* p) {
-    M = B * T; h = d->hidden; I = d->inter; Hq = d->n_q; Hkv = d->n_kv;
-    QD = Hq * 128; KD = Hkv * 128; QKV = QD + 2 * KD; QK = QD + KD; V = d->vocab; L = d->layers;
+  MxActs(const sd_qwen3_dims* d, int B, int T, char* p) : SdShape(d, B, T) {
     char* p0 = p;
     auto take = [&](int64_t n) { char* r = p; p += al(n); return r; };
     const int64_t x = (int64_t)M * h * 2;
@@ -401,53 +397,6 @@ bool mx_supported(const sd_qwen3_dims* d) {
          d->n_q > 0 && d->n_kv > 0;
 }
 
-#define RUN(call) do { int e__ = (call); if (e__) return e__; } while (0)
-
-int forward_mx_impl(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids, const int32_t* kv_len,
-                    const sd_varlen* vl, const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes,
-                    void* logits, const int64_t* head_rows, int n_head_rows, int B, int T, int flags, void* stream) {
-  if (!d || !p || !mx_supported(d)) return SD_ERR_UNSUPPORTED;
-  if (B <= 0 || T <= 0 || (flags & ~SD_FWD_CONCURRENT)) return SD_ERR_SHAPE;
-  if (head_rows && (n_head_rows <= 0 || n_head_rows > B * T)) return SD_ERR_SHAPE;
-  MxActs a(d, B, T, (char*)acts);
-  if (acts_bytes < a.total) return SD_ERR_WORKSPACE;
-  SdSharedGpuScope shared((flags & SD_FWD_CONCURRENT) ? 1 : 0);  // read by the bf16 GEMM dispatch (lm_head)
-  const float scale = 0.08838834764831845f;                       // 128^-1/2
-  const int M = a.M, h = a.h;
-  char* x_cur = a.x_a;
-  RUN(sd_embedding_fwd(ids, p->embed, x_cur, M, h, a.V, stream));
-  for (int l = 0; l < a.L; ++l) {
-    const sd_qwen3_layer_mx& w = p->layers_host[l];
-    char* x_out = x_cur == a.x_a ? a.x_b : a.x_a;
-    // input RMSNorm folded: its gain is in wqkv, its row statistic is the q|k|v GEMM's row scale (HF:59-64, 252-254)
-    RUN(sd_mxfp8_quant(x_cur, h, a.xq, a.xs, (float*)a.rstd, d->eps, M, h, stream));
-    RUN(sd_gemm_mxfp8(a.xq, a.xs, w.wqkv_q, w.wqkv_scale, a.qkv, nullptr, (const float*)a.rstd, M, a.QKV, h, a.QKV, 0,
-                      stream));
-    RUN(sd_qknorm_rope_fwd(a.qkv, w.q_gain, w.k_gain, cos_tab, sin_tab, a.qk, M, T, a.Hq, a.Hkv, d->eps, stream));
-    if (vl)
-      RUN(sd_attn_fwd_varlen(a.qk, a.qk + (int64_t)a.QD * 2, a.qkv + (int64_t)(a.QD + a.KD) * 2, a.ao, (float*)a.lse, vl,
-                             a.QK, a.QK, a.QKV, a.QD, M, a.Hq, a.Hkv, 128, scale, stream));
-    else
-      RUN(sd_attn_fwd(a.qk, a.qk + (int64_t)a.QD * 2, a.qkv + (int64_t)(a.QD + a.KD) * 2, a.ao, (float*)a.lse, kv_len,
-                      a.QK, a.QK, a.QKV, a.QD, B, T, a.Hq, a.Hkv, 128, scale, stream));
-    RUN(sd_mxfp8_quant(a.ao, a.QD, a.aoq, a.aos, nullptr, 0.f, M, a.QD, stream));
-    RUN(sd_gemm_mxfp8(a.aoq, a.aos, w.wo_q, w.wo_scale, a.x_mid, x_cur, nullptr, M, h, a.QD, h, h, stream));
-    // post-attention RMSNorm folded into wgu the same way (HF:59-64, 81-83)
-    RUN(sd_mxfp8_quant(a.x_mid, h, a.xq, a.xs, (float*)a.rstd, d->eps, M, h, stream));
-    RUN(sd_gemm_mxfp8_swiglu(a.xq, a.xs, w.wgu_q, w.wgu_scale, (const float*)a.rstd, a.actq, a.acts, M, a.I, h, stream));
-    RUN(sd_gemm_mxfp8(a.actq, a.acts, w.wdown_q, w.wdown_scale, x_out, a.x_mid, nullptr, M, h, a.I, h, h, stream));
-    x_cur = x_out;
-  }
-  RUN(sd_rmsnorm_fwd(x_cur, p->final_norm, a.xn_f, (float*)a.rstd_f, M, h, d->eps, stream));
-  if (logits && head_rows) {
-    RUN(sd_embedding_fwd(head_rows, a.xn_f, a.xn_rows, n_head_rows, h, M, stream));
-    RUN(sd_gemm_bf16(a.xn_rows, p->lm_head, logits, nullptr, n_head_rows, a.V, h, h, h, a.V, 0, 0, 0, stream));
-  } else if (logits) {
-    RUN(sd_gemm_bf16(a.xn_f, p->lm_head, logits, nullptr, M, a.V, h, h, h, a.V, 0, 0, 0, stream));
-  }
-  return 0;
-}
-
 }  // namespace
 
 extern "C" int sd_qwen3_mx_supported(const sd_qwen3_dims* d) { return d && mx_supported(d) ? 1 : 0; }
@@ -458,19 +407,34 @@ extern "C" int64_t sd_qwen3_mx_acts_bytes(const sd_qwen3_dims* d, int B, int T) 
   return MxActs(d, B, T, nullptr).total;
 }
 
-extern "C" int sd_qwen3_forward_mx(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids,
-                                   const int32_t* kv_len, const void* cos_tab, const void* sin_tab, void* acts,
-                                   int64_t acts_bytes, void* logits, const int64_t* head_rows, int n_head_rows, int B, int T,
-                                   int flags, void* stream) {
-  return forward_mx_impl(d, p, ids, kv_len, nullptr, cos_tab, sin_tab, acts, acts_bytes, logits, head_rows, n_head_rows, B,
-                         T, flags, stream);
-}
-
-extern "C" int sd_qwen3_forward_mx_varlen(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids,
-                                          const sd_varlen* vl, const void* cos_tab, const void* sin_tab, void* acts,
-                                          int64_t acts_bytes, void* logits, const int64_t* head_rows, int n_head_rows, int M,
-                                          int flags, void* stream) {
-  if (!vl) return SD_ERR_SHAPE;
-  return forward_mx_impl(d, p, ids, nullptr, vl, cos_tab, sin_tab, acts, acts_bytes, logits, head_rows, n_head_rows, 1, M,
-                         flags, stream);
+extern "C" int sd_qwen3_forward_mx(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const sd_qwen3_batch* bt, void* acts,
+                                   int64_t acts_bytes, void* logits, int flags, void* stream) {
+  if (!d || !p || !mx_supported(d)) return SD_ERR_UNSUPPORTED;
+  RUN(sd_batch_check(bt));
+  if (flags & ~SD_FWD_CONCURRENT) return SD_ERR_SHAPE;
+  const int B = bt->B, T = bt->T;
+  MxActs a(d, B, T, (char*)acts);
+  if (acts_bytes < a.total) return SD_ERR_WORKSPACE;
+  SdSharedGpuScope shared((flags & SD_FWD_CONCURRENT) ? 1 : 0);  // read by the bf16 GEMM dispatch (lm_head)
+  const int M = a.M, h = a.h;
+  char* x_cur = a.x_a;
+  RUN(sd_embedding_fwd(bt->ids, p->embed, x_cur, M, h, a.V, stream));
+  for (int l = 0; l < a.L; ++l) {
+    const sd_qwen3_layer_mx& w = p->layers_host[l];
+    char* x_out = x_cur == a.x_a ? a.x_b : a.x_a;
+    // input RMSNorm folded: its gain is in wqkv, its row statistic is the q|k|v GEMM's row scale (HF:59-64, 252-254)
+    RUN(sd_mxfp8_quant(x_cur, h, a.xq, a.xs, (float*)a.rstd, d->eps, M, h, stream));
+    RUN(sd_gemm_mxfp8(a.xq, a.xs, w.wqkv_q, w.wqkv_scale, a.qkv, nullptr, (const float*)a.rstd, M, a.QKV, h, a.QKV, 0,
+                      stream));
+    RUN(sd_qknorm_rope_fwd(a.qkv, w.q_gain, w.k_gain, bt->cos_tab, bt->sin_tab, a.qk, M, T, a.Hq, a.Hkv, d->eps, stream));
+    RUN(sd_layer_attn_fwd(a, *bt, a.qk, a.qkv, a.ao, a.lse, stream));
+    RUN(sd_mxfp8_quant(a.ao, a.QD, a.aoq, a.aos, nullptr, 0.f, M, a.QD, stream));
+    RUN(sd_gemm_mxfp8(a.aoq, a.aos, w.wo_q, w.wo_scale, a.x_mid, x_cur, nullptr, M, h, a.QD, h, h, stream));
+    // post-attention RMSNorm folded into wgu the same way (HF:59-64, 81-83)
+    RUN(sd_mxfp8_quant(a.x_mid, h, a.xq, a.xs, (float*)a.rstd, d->eps, M, h, stream));
+    RUN(sd_gemm_mxfp8_swiglu(a.xq, a.xs, w.wgu_q, w.wgu_scale, (const float*)a.rstd, a.actq, a.acts, M, a.I, h, stream));
+    RUN(sd_gemm_mxfp8(a.actq, a.acts, w.wdown_q, w.wdown_scale, x_out, a.x_mid, nullptr, M, h, a.I, h, h, stream));
+    x_cur = x_out;
+  }
+  return sd_head_fwd(d, a, *bt, x_cur, p->final_norm, p->lm_head, a.rstd_f, a.xn_f, a.xn_rows, logits, stream);
 }

@@ -117,24 +117,25 @@ class CausalLMOutput(dict):
 
 SAVE_NONE, SAVE_ALL, SAVE_LAYER_INPUTS, SAVE_NONE_FOLDED = 0, 1, 2, 3  # include/sd_hip.h SD_SAVE_*
 FWD_CONCURRENT = 0x100                            # SD_FWD_CONCURRENT
-BWD_ACCUMULATE, BWD_RECOMPUTE = 1, 2              # SD_BWD_*
+BWD_ACCUMULATE, BWD_RECOMPUTE, BWD_EMBED_ONLY = 1, 2, 4   # SD_BWD_*
 
 
 class _DecoderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, input_ids, kv_len, model, rows, concurrent=False, packed=None):
-        shape = (1, packed.M) if packed is not None else input_ids.shape
+        batch, shape = model._batch(input_ids, kv_len, rows, packed)
         save = SAVE_LAYER_INPUTS if model._wants_recompute(*shape, input_ids.device) else SAVE_ALL
-        logits, acts = model._run_forward(input_ids, kv_len, save=save, rows=rows, concurrent=concurrent, packed=packed)
+        logits, acts = model._run_forward(input_ids, kv_len, save=save, rows=rows, concurrent=concurrent, packed=packed,
+                                          batch=batch)
         ctx.model, ctx.acts, ctx.ids, ctx.kv_len, ctx.rows, ctx.save = model, acts, input_ids, kv_len, rows, save
-        ctx.packed = packed
+        ctx.packed, ctx.batch = packed, batch
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
         ctx.model._run_backward(ctx.ids, ctx.kv_len, ctx.acts, dlogits, rows=ctx.rows,
-                                recompute=ctx.save == SAVE_LAYER_INPUTS, packed=ctx.packed)
-        ctx.acts = ctx.packed = None
+                                recompute=ctx.save == SAVE_LAYER_INPUTS, packed=ctx.packed, batch=ctx.batch)
+        ctx.acts = ctx.packed = ctx.batch = None
         return torch.zeros((), device=dlogits.device), None, None, None, None, None, None
 
 
@@ -511,6 +512,18 @@ class HipQwen3ForCausalLM(nn.Module):
         flat = pos.reshape(-1).to(torch.int64)
         return PackedBatch(cu_host, cos[flat].contiguous(), sin[flat].contiguous(), ids.device)
 
+    def _fold_layer(self, l):
+        """bf16(W diag(g)) of layer l's q|k|v and gate|up projections, g = the RMSNorm gain in front of each."""
+        d, p = self.dims, f"model.layers.{l}."
+        h = d.hidden_size
+        out = []
+        for first, n, gain in (("self_attn.q_proj", (d.q_dim + 2 * d.kv_dim) * h, "input_layernorm"),
+                               ("mlp.gate_proj", 2 * d.intermediate_size * h, "post_attention_layernorm")):
+            o = self._slices[p + first + ".weight"][0]
+            w = self.flat[o:o + n].view(-1, h)   # q | k | v (gate | up) rows are contiguous in the flat layout
+            out.append((w.float() * self._params[p + gain + ".weight"].float()[None, :]).to(torch.bfloat16))
+        return out
+
     @torch.no_grad()
     def _folded_params(self):
         """C parameter struct whose wqkv / wgu point at W diag(g) (g = the RMSNorm gain in front of the projection,
@@ -528,15 +541,10 @@ class HipQwen3ForCausalLM(nn.Module):
         buf = torch.empty(d.num_hidden_layers * (nq + ng), dtype=torch.bfloat16, device=self.flat.device)
         params, layers = self._c_struct(self.flat)
         for l in range(d.num_hidden_layers):
-            p = f"model.layers.{l}."
-            o, _, _ = self._slices[p + "self_attn.q_proj.weight"]
-            wqkv = self.flat[o:o + nq].view(-1, h)       # q | k | v rows are contiguous in the flat layout
-            o, _, _ = self._slices[p + "mlp.gate_proj.weight"]
-            wgu = self.flat[o:o + ng].view(-1, h)        # gate | up likewise
             base = l * (nq + ng)
-            fq, fg = buf[base:base + nq].view(-1, h), buf[base + nq:base + nq + ng].view(-1, h)
-            fq.copy_(wqkv.float() * self._params[p + "input_layernorm.weight"].float()[None, :])
-            fg.copy_(wgu.float() * self._params[p + "post_attention_layernorm.weight"].float()[None, :])
+            fq, fg = self._fold_layer(l)
+            buf[base:base + nq].copy_(fq.view(-1))
+            buf[base + nq:base + nq + ng].copy_(fg.view(-1))
             layers[l].wqkv = buf.data_ptr() + base * 2
             layers[l].wgu = buf.data_ptr() + (base + nq) * 2
         self._folded = (ver, buf, params, layers)
@@ -578,8 +586,6 @@ class HipQwen3ForCausalLM(nn.Module):
             return self._mx[0]
         from . import ops
         d = self.dims
-        h, I = d.hidden_size, d.intermediate_size
-        nq, ng = (d.q_dim + 2 * d.kv_dim) * h, 2 * I * h
         keep = []
         layers = (_lib.LayerMx * d.num_hidden_layers)()
         base = self.flat.data_ptr()
@@ -590,12 +596,7 @@ class HipQwen3ForCausalLM(nn.Module):
             return q.data_ptr(), s.data_ptr()
         for l in range(d.num_hidden_layers):
             p = f"model.layers.{l}."
-            o, _, _ = self._slices[p + "self_attn.q_proj.weight"]
-            wqkv = self.flat[o:o + nq].view(-1, h)       # q | k | v rows are contiguous in the flat layout
-            o, _, _ = self._slices[p + "mlp.gate_proj.weight"]
-            wgu = self.flat[o:o + ng].view(-1, h)        # gate | up likewise
-            fq = (wqkv.float() * self._params[p + "input_layernorm.weight"].float()[None, :]).to(torch.bfloat16)
-            fg = (wgu.float() * self._params[p + "post_attention_layernorm.weight"].float()[None, :]).to(torch.bfloat16)
+            fq, fg = self._fold_layer(l)
             layers[l].wqkv_q, layers[l].wqkv_scale = quant(fq)
             layers[l].wgu_q, layers[l].wgu_scale = quant(fg)
             layers[l].wo_q, layers[l].wo_scale = quant(self._params[p + "self_attn.o_proj.weight"].data)
@@ -608,35 +609,31 @@ class HipQwen3ForCausalLM(nn.Module):
         self._mx = (params, layers, keep)
         return params
 
-    def _run_forward_mx(self, input_ids, kv_len, rows, concurrent, packed):
-        lib = load_lib()
-        B, T = input_ids.shape
-        dev = input_ids.device
-        cos, sin = (packed.cos, packed.sin) if packed is not None else self._tables(T, dev)
-        params = self._mx_params()
-        nbytes = lib.sd_qwen3_mx_acts_bytes(C.byref(self._cdims), *((1, packed.M) if packed is not None else (B, T)))
-        acts = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        n_rows = 0 if rows is None else rows.numel()
-        logits = torch.empty(*((B, T) if rows is None else (n_rows,)), self.dims.vocab_size, dtype=torch.bfloat16, device=dev)
-        flags = FWD_CONCURRENT if concurrent else 0
-        if packed is not None:
-            check(lib.sd_qwen3_forward_mx_varlen(C.byref(self._cdims), C.byref(params), input_ids.data_ptr(),
-                                                 C.byref(packed.desc), cos.data_ptr(), sin.data_ptr(), acts.data_ptr(), nbytes,
-                                                 logits.data_ptr(), _p(rows), n_rows, packed.M, flags, _stream()),
-                  "sd_qwen3_forward_mx_varlen")
-        else:
-            check(lib.sd_qwen3_forward_mx(C.byref(self._cdims), C.byref(params), input_ids.data_ptr(), _p(kv_len),
-                                          cos.data_ptr(), sin.data_ptr(), acts.data_ptr(), nbytes, logits.data_ptr(), _p(rows),
-                                          n_rows, B, T, flags, _stream()), "sd_qwen3_forward_mx")
-        return logits, acts
+    def _batch(self, input_ids, kv_len, rows, packed):
+        """include/sd_hip.h sd_qwen3_batch of one call and the (B, T) that size its buffers: (1, M) for packed documents.
+        Built once per forward and kept by the autograd function for the backward; ``keep`` holds what it points to."""
+        B, T = input_ids.shape if packed is None else (1, packed.M)
+        cos, sin = self._tables(T, input_ids.device) if packed is None else (packed.cos, packed.sin)
+        b = _lib.Batch(input_ids.data_ptr(), _p(kv_len) if packed is None else 0,
+                       None if packed is None else C.pointer(packed.desc), cos.data_ptr(), sin.data_ptr(), _p(rows),
+                       0 if rows is None else rows.numel(), B, T, 0)
+        b.keep = (input_ids, kv_len, rows, packed, cos, sin)
+        return b, (B, T)
 
-    def _run_forward(self, input_ids, kv_len, save, rows=None, concurrent=False, packed=None):
-        if save == SAVE_NONE and self.inference_precision == "mxfp8":
-            return self._run_forward_mx(input_ids, kv_len, rows, concurrent, packed)
+    def _run_forward(self, input_ids, kv_len, save, rows=None, concurrent=False, packed=None, batch=None):
         lib = load_lib()
-        B, T = input_ids.shape
+        if batch is None:
+            batch, _ = self._batch(input_ids, kv_len, rows, packed)
         dev = input_ids.device
-        cos, sin = (packed.cos, packed.sin) if packed is not None else self._tables(T, dev)
+        shape = input_ids.shape if rows is None else (rows.numel(),)
+        logits = torch.empty(*shape, self.dims.vocab_size, dtype=torch.bfloat16, device=dev)
+        mode = FWD_CONCURRENT if concurrent else 0
+        if save == SAVE_NONE and self.inference_precision == "mxfp8":
+            nbytes = lib.sd_qwen3_mx_acts_bytes(C.byref(self._cdims), batch.B, batch.T)
+            acts = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            check(lib.sd_qwen3_forward_mx(C.byref(self._cdims), C.byref(self._mx_params()), C.byref(batch), acts.data_ptr(),
+                                          nbytes, logits.data_ptr(), mode, _stream()), "sd_qwen3_forward_mx")
+            return logits, acts
         cparams = self._cparams
         if self._lora is not None:
             self._lora.ensure_merged()   # W_eff = W_res + s B A, rebuilt only after A / B have changed
@@ -644,24 +641,10 @@ class HipQwen3ForCausalLM(nn.Module):
             folded = self._folded_params()
             if folded is not None:
                 cparams, save = folded, SAVE_NONE_FOLDED
-        nbytes = lib.sd_qwen3_acts_bytes(C.byref(self._cdims), *((1, packed.M) if packed is not None else (B, T)), int(save))
+        nbytes = lib.sd_qwen3_acts_bytes(C.byref(self._cdims), batch.B, batch.T, int(save))
         acts = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        if rows is None:
-            logits = torch.empty(B, T, self.dims.vocab_size, dtype=torch.bfloat16, device=dev)
-        else:
-            logits = torch.empty(rows.numel(), self.dims.vocab_size, dtype=torch.bfloat16, device=dev)
-        if packed is not None:  # one row of B*T tokens, attention per document
-            check(lib.sd_qwen3_forward_varlen(C.byref(self._cdims), C.byref(cparams), input_ids.data_ptr(),
-                                              C.byref(packed.desc), cos.data_ptr(), sin.data_ptr(), acts.data_ptr(), nbytes,
-                                              logits.data_ptr(), _p(rows), 0 if rows is None else rows.numel(), packed.M,
-                                              int(save) | (FWD_CONCURRENT if concurrent else 0), _stream()),
-                  "sd_qwen3_forward_varlen")
-            return logits, acts
-        check(lib.sd_qwen3_forward_rows(C.byref(self._cdims), C.byref(cparams), input_ids.data_ptr(), _p(kv_len),
-                                        cos.data_ptr(), sin.data_ptr(), acts.data_ptr(), nbytes, logits.data_ptr(),
-                                        _p(rows), 0 if rows is None else rows.numel(), B, T,
-                                        int(save) | (FWD_CONCURRENT if concurrent else 0), _stream()),
-              "sd_qwen3_forward_rows")
+        check(lib.sd_qwen3_forward(C.byref(self._cdims), C.byref(cparams), C.byref(batch), acts.data_ptr(), nbytes,
+                                   logits.data_ptr(), int(save) | mode, _stream()), "sd_qwen3_forward")
         return logits, acts
 
     def _ensure_grads(self):
@@ -691,78 +674,49 @@ class HipQwen3ForCausalLM(nn.Module):
         if not 0 <= int(self.stage1_row_lo) <= self.dims.vocab_size:
             raise ValueError(f"stage1_row_lo {self.stage1_row_lo} outside [0, {self.dims.vocab_size}]")
 
-    def _run_backward(self, input_ids, kv_len, acts, dlogits, rows=None, recompute=False, packed=None):
+    def _run_backward(self, input_ids, kv_len, acts, dlogits, rows=None, recompute=False, packed=None, batch=None):
+        """sd_qwen3_backward.  Stage-1 (``stage1_row_lo`` set): SD_BWD_EMBED_ONLY, the dX chain only and the gradient rows
+        [stage1_row_lo, V) of embed_tokens (+ lm_head).  ``batch``: the descriptor its forward built; the autograd function
+        must pass it (no host work is repeated per step), a direct caller may leave it None and it is rebuilt here."""
         lib = load_lib()
-        B, T = input_ids.shape
-        if self.stage1_row_lo is not None:
-            return self._run_backward_stage1(input_ids, kv_len, acts, dlogits, rows, recompute, packed)
-        accumulate = self._ensure_grads()
+        dev = input_ids.device
+        stage1 = self.stage1_row_lo is not None
         red = getattr(self, "_reducer", None)
-        dx0 = None
-        if red is not None:
+        if stage1:
+            self.check_stage1()
+            if red is not None:
+                raise NotImplementedError("Stage-1 alignment is single-GPU (no data-parallel gradient exchange)")
+        accumulate = self._ensure_grads()
+        opts = _lib.BwdOpts((BWD_ACCUMULATE if accumulate else 0) | (BWD_RECOMPUTE if recompute else 0))
+        opts.side_stream = self._side_stream_ptr(dev)
+        if stage1:
+            opts.flags |= BWD_EMBED_ONLY
+            opts.grad_row_lo = int(self.stage1_row_lo)
+        elif red is not None:
             red.begin_step()
             if red.wants_split_embedding():
                 # tied embedding/lm_head gradient: the dense lm_head part is all-reduced at the START of
                 # backward; only the B*T rows touched by the embedding lookup are exchanged at the end
-                dx0 = torch.empty(B * T, self.dims.hidden_size, dtype=torch.bfloat16, device=input_ids.device)
+                dx0 = torch.empty(input_ids.numel(), self.dims.hidden_size, dtype=torch.bfloat16, device=dev)
                 eo, en, eshape = self._slices["model.embed_tokens.weight"]
                 red.set_embedding_exchange(input_ids.reshape(-1), dx0, self.flat_grad[eo:eo + en].view(eshape))
+                opts.dx0_out = dx0.data_ptr()
+        user_cb = self._stage_cb
+        if user_cb and not stage1:
+            opts.on_grads_ready = _lib.STAGE_CB(lambda stage, _u: user_cb(stage))  # (opts keeps the thunk alive)
         if not dlogits.is_contiguous():
             dlogits = dlogits.contiguous()
-        cos, sin = (packed.cos, packed.sin) if packed is not None else self._tables(T, input_ids.device)
-        sbytes = lib.sd_qwen3_bwd_scratch_bytes(C.byref(self._cdims), *((1, packed.M) if packed is not None else (B, T)))
-        scratch = torch.empty(sbytes, dtype=torch.uint8, device=input_ids.device)
-        user_cb = self._stage_cb
-        cb = _lib.STAGE_CB((lambda stage, _u: user_cb(stage)) if user_cb else 0)
-        flags = (BWD_ACCUMULATE if accumulate else 0) | (BWD_RECOMPUTE if recompute else 0)
-        if packed is not None:
-            check(lib.sd_qwen3_backward_varlen(C.byref(self._cdims), C.byref(self._cparams), C.byref(self._cgrads),
-                                               input_ids.data_ptr(), C.byref(packed.desc), cos.data_ptr(), sin.data_ptr(),
-                                               acts.data_ptr(), acts.numel(), dlogits.data_ptr(), _p(rows),
-                                               0 if rows is None else rows.numel(), scratch.data_ptr(), sbytes, packed.M,
-                                               flags, _p(dx0), cb, None, self._side_stream_ptr(input_ids.device), _stream()),
-                  "sd_qwen3_backward_varlen")
-        else:
-            check(lib.sd_qwen3_backward_rows(C.byref(self._cdims), C.byref(self._cparams), C.byref(self._cgrads),
-                                             input_ids.data_ptr(), _p(kv_len), cos.data_ptr(), sin.data_ptr(),
-                                             acts.data_ptr(), acts.numel(), dlogits.data_ptr(), _p(rows),
-                                             0 if rows is None else rows.numel(), scratch.data_ptr(), sbytes, B, T, flags,
-                                             _p(dx0), cb, None, self._side_stream_ptr(input_ids.device), _stream()),
-                  "sd_qwen3_backward_rows")
+        if batch is None:
+            batch, _ = self._batch(input_ids, kv_len, rows, packed)
+        sbytes = lib.sd_qwen3_bwd_scratch_bytes(C.byref(self._cdims), batch.B, batch.T)
+        scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
+        check(lib.sd_qwen3_backward(C.byref(self._cdims), C.byref(self._cparams), C.byref(self._cgrads), C.byref(batch),
+                                    acts.data_ptr(), acts.numel(), dlogits.data_ptr(), scratch.data_ptr(), sbytes,
+                                    C.byref(opts), _stream()), "sd_qwen3_backward")
         if red is not None:
             red.finish()
         if self._lora is not None:
             self._lora.grads_stale = True
-
-    def _run_backward_stage1(self, input_ids, kv_len, acts, dlogits, rows, recompute, packed=None):
-        """sd_qwen3_backward_embed_rows: dX chain only, gradient rows [stage1_row_lo, V) of embed_tokens (+ lm_head)."""
-        self.check_stage1()
-        if getattr(self, "_reducer", None) is not None:
-            raise NotImplementedError("Stage-1 alignment is single-GPU (no data-parallel gradient exchange)")
-        lib = load_lib()
-        B, T = input_ids.shape
-        accumulate = self._ensure_grads()
-        if not dlogits.is_contiguous():
-            dlogits = dlogits.contiguous()
-        sbytes = lib.sd_qwen3_bwd_scratch_bytes(C.byref(self._cdims), *((1, packed.M) if packed is not None else (B, T)))
-        scratch = torch.empty(sbytes, dtype=torch.uint8, device=input_ids.device)
-        flags = (BWD_ACCUMULATE if accumulate else 0) | (BWD_RECOMPUTE if recompute else 0)
-        if packed is not None:
-            check(lib.sd_qwen3_backward_embed_varlen(C.byref(self._cdims), C.byref(self._cparams), C.byref(self._cgrads),
-                                                     input_ids.data_ptr(), C.byref(packed.desc), packed.cos.data_ptr(),
-                                                     packed.sin.data_ptr(), acts.data_ptr(), acts.numel(), dlogits.data_ptr(),
-                                                     _p(rows), 0 if rows is None else rows.numel(), scratch.data_ptr(),
-                                                     sbytes, packed.M, flags, int(self.stage1_row_lo),
-                                                     self._side_stream_ptr(input_ids.device), _stream()),
-                  "sd_qwen3_backward_embed_varlen")
-            return
-        cos, sin = self._tables(T, input_ids.device)
-        check(lib.sd_qwen3_backward_embed_rows(C.byref(self._cdims), C.byref(self._cparams), C.byref(self._cgrads),
-                                               input_ids.data_ptr(), _p(kv_len), cos.data_ptr(), sin.data_ptr(),
-                                               acts.data_ptr(), acts.numel(), dlogits.data_ptr(), _p(rows),
-                                               0 if rows is None else rows.numel(), scratch.data_ptr(), sbytes, B, T,
-                                               flags, int(self.stage1_row_lo), self._side_stream_ptr(input_ids.device), _stream()),
-              "sd_qwen3_backward_embed_rows")
 
     def finalize_grads(self):
         """Called by the optimizer / the clipping hook before they read gradients: a LoRA student projects the

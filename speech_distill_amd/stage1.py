@@ -4,7 +4,8 @@ expanded vocabulary that belong to the new speech tokens, with plain causal-LM c
 * ``freeze_model_weights(model, num_new_tokens)`` -- the reference's name and signature (stage1.py:29-93): every weight
   frozen except the input / output embeddings, whose gradients are masked to rows >= ``old_vocab = V - num_new_tokens``.
   On a ``HipQwen3ForCausalLM`` the mask is not a hook: the model records ``stage1_row_lo = old_vocab`` and its backward
-  (``sd_qwen3_backward_embed_rows``) never computes the body's weight gradients nor writes the rows below it.
+  (``sd_qwen3_backward`` with ``SD_BWD_EMBED_ONLY``) never computes the body's weight gradients nor writes the rows
+  below it.
 * ``pack_bfd`` / ``Stage1Collator`` -- TRL ``packing=True`` restated: best-fit-decreasing bins of ``max_seq_length``
   tokens.  By default each document of a bin is its own right-padded row, so attention and RoPE positions restart per
   document at the cost of padding; ``padding_free=True`` gives what TRL trains on under flash-attention: the documents

@@ -29,7 +29,7 @@ def test_header_symbols_are_exported_and_bound():
     for name in sorted(declared):
         assert hasattr(lib, name), f"{name} declared in include/sd_hip.h but not exported by libsd_hip.so"
     assert set(_lib.PROTOTYPES) == declared, (set(_lib.PROTOTYPES) ^ declared)
-    assert sda.load_lib().sd_abi_version() == 1
+    assert sda.load_lib().sd_abi_version() == 2
 
 
 def test_workspace_queries_run_without_gpu():
@@ -48,6 +48,57 @@ def test_workspace_queries_run_without_gpu():
     assert infer < folded <= infer + 2 * (4 * 512 * 64 + 256)
     assert lib.sd_kdloss_stats_bytes(4, 512) == 4 * 512 * 32
     assert lib.sd_gemm_splitk_plan(2048, 1024, 159488) > 1 and lib.sd_gemm_splitk_plan(2048, 6144, 1024) == 1
+
+
+def test_runner_entries_refuse_invalid_descriptors_before_any_launch():
+    """The three runner entries validate the batch descriptor, the mode / flag bits, the options and the workspace sizes
+    before anything touches the device, so the codes come back on a machine without one."""
+    import speech_distill_amd as sda
+    from speech_distill_amd import _lib
+    lib = sda.load_lib()
+    V = 640
+    d = ctypes.byref(_lib.Dims(V, 256, 512, 2, 4, 2, 128, 1, 1e-6, 0))
+    p, g, pmx = ctypes.byref(_lib.Params()), ctypes.byref(_lib.Params()), ctypes.byref(_lib.ParamsMx())
+    SHAPE, WORKSPACE, BIG = -1, -5, 1 << 40
+    vl = ctypes.pointer(_lib.Varlen(0x1000, 1, 8, None))
+
+    def batch(kv_len=None, vl=None, rows=None, n_rows=0, B=2, T=8):
+        return ctypes.byref(_lib.Batch(0x1000, kv_len, vl, 0x1000, 0x1000, rows, n_rows, B, T, 0))
+
+    def fwd(b, mode=0, acts_bytes=BIG):
+        return lib.sd_qwen3_forward(d, p, b, 0x1000, acts_bytes, 0x1000, mode, None)
+
+    def fwd_mx(b, flags=0, acts_bytes=BIG):
+        return lib.sd_qwen3_forward_mx(d, pmx, b, 0x1000, acts_bytes, 0x1000, flags, None)
+
+    def bwd(b, opts=None, acts_bytes=BIG, scratch_bytes=BIG):
+        o = ctypes.byref(opts or _lib.BwdOpts())    # all-zero options: the plain full backward
+        return lib.sd_qwen3_backward(d, p, g, b, 0x1000, acts_bytes, 0x1000, 0x1000, scratch_bytes, o, None)
+
+    for call in (fwd, fwd_mx, bwd):
+        assert call(None) == SHAPE                                     # NULL batch
+        assert call(batch(B=0)) == SHAPE and call(batch(T=0)) == SHAPE
+        assert call(batch(kv_len=0x1000, vl=vl, B=1)) == SHAPE         # packed documents carry no kv_len
+        assert call(batch(vl=vl, B=2)) == SHAPE                        # ... and are one row
+        assert call(batch(rows=0x1000, n_rows=0)) == SHAPE
+        assert call(batch(rows=0x1000, n_rows=2 * 8 + 1)) == SHAPE
+        assert call(batch(), acts_bytes=0) == WORKSPACE
+        assert call(batch(vl=vl, B=1), acts_bytes=0) == WORKSPACE      # a valid packed descriptor gets as far
+        assert call(batch(rows=0x1000, n_rows=16), acts_bytes=0) == WORKSPACE
+    assert fwd(batch(), mode=4) == SHAPE and fwd(batch(), mode=0x200) == SHAPE   # unknown mode / flag bit
+    assert fwd(batch(), mode=1 | 0x100, acts_bytes=0) == WORKSPACE               # SD_SAVE_ALL | SD_FWD_CONCURRENT is known
+    assert fwd_mx(batch(), flags=1) == SHAPE and fwd_mx(batch(), flags=0x100, acts_bytes=0) == WORKSPACE
+    assert bwd(batch(), _lib.BwdOpts(8)) == SHAPE
+    assert lib.sd_qwen3_backward(d, p, g, batch(), 0x1000, BIG, 0x1000, 0x1000, BIG, None, None) == SHAPE   # NULL options
+    assert bwd(batch(), _lib.BwdOpts(1 | 2 | 4), acts_bytes=0) == WORKSPACE
+    assert bwd(batch(), scratch_bytes=0) == WORKSPACE
+    # SD_BWD_EMBED_ONLY (4) takes neither a stage callback nor dx0_out, and grad_row_lo in [0, V]
+    cb = _lib.STAGE_CB(lambda stage, user: None)
+    assert bwd(batch(), _lib.BwdOpts(4, 0, None, cb)) == SHAPE
+    assert bwd(batch(), _lib.BwdOpts(4, 0, 0x1000)) == SHAPE
+    assert bwd(batch(), _lib.BwdOpts(4, V + 1)) == SHAPE and bwd(batch(), _lib.BwdOpts(4, -1)) == SHAPE
+    assert bwd(batch(), _lib.BwdOpts(4, V), acts_bytes=0) == WORKSPACE
+    assert bwd(batch(), _lib.BwdOpts(0, V + 1), acts_bytes=0) == WORKSPACE       # grad_row_lo is read only with the flag
 
 
 def test_cpu_tensors_are_rejected_not_routed_to_a_fallback():

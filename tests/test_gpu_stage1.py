@@ -1,5 +1,5 @@
 """-m gpu: Stage-1 speech-token alignment on the MI355X (reference stage1.py): the cross-entropy row kernels, the
-range-restricted embedding scatter, the embedding-only backward runner (sd_qwen3_backward_embed_rows), a HIP Stage-1
+range-restricted embedding scatter, the embedding-only backward runner (sd_qwen3_backward with SD_BWD_EMBED_ONLY), a HIP Stage-1
 step against fixture G6, and scripts/stage1.py end to end."""
 import ctypes as C
 import json
@@ -105,7 +105,7 @@ def _model(sda, dims, seed=0):
 def _run(sda, m, ids, am, rows, dlogits, row_lo, save, acc, grads_flat, full=False):
     """One forward (save mode) + one backward into grads_flat (a flat buffer) -> None."""
     from speech_distill_amd import qwen3 as Qm
-    from speech_distill_amd._lib import check, load_lib
+    from speech_distill_amd._lib import STAGE_CB, Batch, BwdOpts, check, load_lib
     from speech_distill_amd.ops import _stream
     lib = load_lib()
     B, T = ids.shape
@@ -116,15 +116,15 @@ def _run(sda, m, ids, am, rows, dlogits, row_lo, save, acc, grads_flat, full=Fal
     sbytes = lib.sd_qwen3_bwd_scratch_bytes(C.byref(m._cdims), B, T)
     scratch = torch.empty(sbytes, dtype=torch.uint8, device=ids.device)
     flags = (Qm.BWD_ACCUMULATE if acc else 0) | (Qm.BWD_RECOMPUTE if save == Qm.SAVE_LAYER_INPUTS else 0)
-    common = (C.byref(m._cdims), C.byref(m._cparams), C.byref(cg), ids.data_ptr(), kv_len.data_ptr(), cos.data_ptr(),
-              sin.data_ptr(), acts.data_ptr(), acts.numel(), dlogits.data_ptr(), rows.data_ptr(), rows.numel(),
-              scratch.data_ptr(), sbytes, B, T, flags)
+    batch = Batch(ids.data_ptr(), kv_len.data_ptr(), None, cos.data_ptr(), sin.data_ptr(), rows.data_ptr(), rows.numel(),
+                  B, T, 0)
     side = m._side_stream_ptr(ids.device)
-    if full:
-        from speech_distill_amd._lib import STAGE_CB
-        check(lib.sd_qwen3_backward_rows(*common, None, STAGE_CB(0), None, side, _stream()), "sd_qwen3_backward_rows")
-    else:
-        check(lib.sd_qwen3_backward_embed_rows(*common, row_lo, side, _stream()), "sd_qwen3_backward_embed_rows")
+    # the two option sets: the plain full backward, and the embedding-only one from row_lo
+    opts = BwdOpts(flags, 0, None, STAGE_CB(0), None, side) if full else BwdOpts(flags | Qm.BWD_EMBED_ONLY, row_lo,
+                                                                                None, STAGE_CB(0), None, side)
+    check(lib.sd_qwen3_backward(C.byref(m._cdims), C.byref(m._cparams), C.byref(cg), C.byref(batch), acts.data_ptr(),
+                                acts.numel(), dlogits.data_ptr(), scratch.data_ptr(), sbytes, C.byref(opts), _stream()),
+          "sd_qwen3_backward")
     torch.cuda.synchronize()
 
 

@@ -17,7 +17,7 @@ from conftest import ROOT
 
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 NEW = ["sd_mxfp8_quant", "sd_gemm_mxfp8", "sd_gemm_mxfp8_swiglu", "sd_qwen3_mx_supported", "sd_qwen3_mx_acts_bytes",
-       "sd_qwen3_forward_mx", "sd_qwen3_forward_mx_varlen"]
+       "sd_qwen3_forward_mx"]
 
 
 def test_mx_ref_follows_the_format_rule():
@@ -103,7 +103,7 @@ def test_abi_additions_are_declared_exported_and_bound():
     assert lib.sd_qwen3_mx_supported(ctypes.byref(odd)) == 0 and lib.sd_qwen3_mx_acts_bytes(ctypes.byref(odd), 4, 512) < 0
     t = cd(Qwen3Dims.teacher_17b())
     assert lib.sd_qwen3_acts_bytes(ctypes.byref(t), 4, 512, 4) < 0  # still no fifth SD_SAVE_* mode
-    assert lib.sd_abi_version() == 1
+    assert lib.sd_abi_version() == 2
 
 
 def _load_script(name):
