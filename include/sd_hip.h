@@ -538,7 +538,16 @@ int sd_sample_step(const void* logits, int64_t row_stride, const float* uniforms
  *   tokens already cached per row), max_len = host upper bound of every pos[b] + 1; cos/sin [cap,128].  Per layer: RMSNorm,
  *   q|k|v GEMM, sd_qknorm_rope_append, sd_attn_decode (len = pos + 1), o GEMM + residual, RMSNorm, gate|up + SwiGLU
  *   (sd_gemm_swiglu, else GEMM + sd_swiglu_fwd), down GEMM + residual; then the final norm and the lm_head:
- *   logits bf16 [B,V].  acts of sd_qwen3_decode_acts_bytes(d, B, cap). */
+ *   logits bf16 [B,V].  acts of sd_qwen3_decode_acts_bytes(d, B, cap).
+ * sd_qwen3_decode_step_flags: the same step with flags = 0.  SD_DECODE_SKINNY (B <= SD_GEMV_MAX_M): every projection is a
+ *   weight-streaming GEMV and the norms and the SwiGLU ride in them -- per layer sd_gemv_bf16(norm_gain = ln1) for q|k|v,
+ *   sd_qknorm_rope_append, sd_attn_decode, sd_gemv_bf16(r = x) for o, sd_gemv_swiglu(norm_gain = ln2), sd_gemv_bf16(r =
+ *   x_mid) for down (7 launches instead of 9), then ONE launch for the final norm + lm_head.  In that mode row b of the
+ *   logits depends on row b's token, position and cache only (not on B or the other rows).  When any GEMV of the step
+ *   would refuse its shape (B > 16, hidden > 4096, ...) the WHOLE step runs the unflagged sequence, so a step's arithmetic
+ *   is one of two kinds, never a mixture.  An unknown flag bit is SD_ERR_SHAPE before any launch.
+ * Both entries return SD_ERR_SHAPE for a NULL d or p. */
+#define SD_DECODE_SKINNY 1
 int64_t sd_qwen3_prefill_acts_bytes(const sd_qwen3_dims* d, int B, int T);
 int sd_qwen3_prefill(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* kv_len,
                      const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes, void* cache,
@@ -547,6 +556,30 @@ int64_t sd_qwen3_decode_acts_bytes(const sd_qwen3_dims* d, int B, int cap);
 int sd_qwen3_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* pos,
                          int max_len, const void* cos_tab, const void* sin_tab, void* cache, int64_t cache_bytes, int cap,
                          void* acts, int64_t acts_bytes, void* logits, int B, void* stream);
+int sd_qwen3_decode_step_flags(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* pos,
+                               int max_len, const void* cos_tab, const void* sin_tab, void* cache, int64_t cache_bytes,
+                               int cap, void* acts, int64_t acts_bytes, void* logits, int B, int flags, void* stream);
+
+/* ---- weight-streaming GEMV for decode (M = batch <= 16): the projections of HF:239-262 (q/k/v, o), HF:81-83 (MLP) and the
+ * lm_head for one token per sequence, with the RMSNorm of HF:59-64 and the SwiGLU of HF:81-83 fused in.  bf16 operands,
+ * fp32 accumulation, nothing transposed: w is [N,K] with K contiguous.
+ * sd_gemv_bf16: y[M,N] = xn[M,K] . w[N,K]^T (+ r[M,N]), one rounding: bf16(acc + float(r)).  xn = x, or
+ *   RMSNorm(x; norm_gain, eps) when norm_gain != NULL -- bit-identical to sd_rmsnorm_fwd into a bf16 buffer followed by
+ *   sd_gemv_bf16 without a norm.
+ * sd_gemv_swiglu: act[M,I] = silu(xn Wg^T) * (xn Wu^T), wgu = [gate rows | up rows] [2I,K] -- bit-identical to
+ *   sd_gemv_bf16 with N = 2I into a bf16 gate|up buffer followed by sd_swiglu_fwd.
+ * The bits of y[m,n] depend on x[m,:], w[n,:], r[m,n], norm_gain, eps and K only: not on M, the other rows, N or the grid
+ * (every element is reduced over K in one fixed order, no atomics).  Weights are read once, 16 bytes per lane,
+ * non-temporal, with no LDS staging.  y may be r (an element's residual is read by the thread that stores it, before the
+ * store); y must not overlap x or w: every workgroup reads all of x while others already store.
+ * Supported: 1 <= M <= SD_GEMV_MAX_M, N >= 1, K % 8 == 0, K <= 8192 (<= 4096 with a norm, the limit of sd_rmsnorm_fwd),
+ * ld* >= the row length, x / w / norm_gain rows 16-byte aligned; anything else that is sane is SD_ERR_UNSUPPORTED, M <= 0
+ * or a NULL x / w / y is SD_ERR_SHAPE.  Both are decided before any launch. */
+#define SD_GEMV_MAX_M 16
+int sd_gemv_bf16(const void* x, const void* w, void* y, const void* r, const void* norm_gain, float eps, int M, int N, int K,
+                 int64_t ldx, int64_t ldw, int64_t ldy, int64_t ldr, void* stream);
+int sd_gemv_swiglu(const void* x, const void* wgu, void* act, const void* norm_gain, float eps, int M, int I, int K,
+                   void* stream);
 
 /* ---- stream placement.  HIP multiplexes streams onto a few hardware queues (4 by default); streams that share a
  * queue never overlap.  Measures, with a `spin_us`-long busy-wait kernel on stream_a and an empty one on stream_b,

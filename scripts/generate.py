@@ -42,6 +42,8 @@ def parse_args(argv=None):
     p.add_argument("--greedy", action="store_true", help="arg-max instead of sampling")
     p.add_argument("--seed", type=int, default=None)
     p.add_argument("--sync_every", type=int, default=16)
+    p.add_argument("--decode_kernels", choices=("tile", "skinny"), default="tile",
+                   help="skinny: weight-streaming GEMV kernels for the decode step (batch_size <= 16)")
     return p.parse_args(argv)
 
 
@@ -83,7 +85,8 @@ def main(argv=None):
                                  min_new_tokens=args.min_tokens, do_sample=not args.greedy, temperature=args.temperature,
                                  top_k=args.top_k, top_p=args.top_p, repetition_penalty=args.repetition_penalty,
                                  eos_token_id=args.stop_token_id, pad_token_id=pad, use_ras=not args.no_ras,
-                                 win_size=args.win_size, tau_r=args.tau_r, seed=args.seed, sync_every=args.sync_every)
+                                 win_size=args.win_size, tau_r=args.tau_r, seed=args.seed, sync_every=args.sync_every,
+                                 decode_kernels=args.decode_kernels)
             torch.cuda.synchronize()
             elapsed += time.perf_counter() - t0
             new = res[:, T:].cpu().tolist()

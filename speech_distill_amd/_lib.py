@@ -197,6 +197,10 @@ PROTOTYPES = {
     "sd_qwen3_decode_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
     "sd_qwen3_decode_step": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _i, _vp, _vp, _vp, _i64, _i, _vp, _i64, _vp,
                                   _i, _vp]),
+    "sd_qwen3_decode_step_flags": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _i, _vp, _vp, _vp, _i64, _i, _vp, _i64,
+                                        _vp, _i, _i, _vp]),
+    "sd_gemv_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i64, _i64, _i64, _i64, _vp]),
+    "sd_gemv_swiglu": (_i, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp]),
 }
 
 

@@ -604,17 +604,51 @@ extern "C" int64_t sd_qwen3_decode_acts_bytes(const sd_qwen3_dims* d, int B, int
   return DecodeActs(d, B, cap, nullptr).total;
 }
 
-extern "C" int sd_qwen3_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
-                                    const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab, void* cache,
-                                    int64_t cache_bytes, int cap, void* acts, int64_t acts_bytes, void* logits, int B,
-                                    void* stream) {
+namespace {
+// true when every GEMV of a skinny step accepts its shape: decided for the whole step before the first launch
+bool skinny_step_ok(const sd_qwen3_params* p, const Sizes& s, const DecodeActs& a, const void* logits, int B) {
+  bool ok = sd_gemv_check(a.x, p->lm_head, logits, nullptr, p->final_norm, B, s.V, s.h, s.h, s.h, s.V, 0) == 0;
+  for (int l = 0; ok && l < s.L; ++l) {
+    const sd_qwen3_layer& w = p->layers_host[l];
+    ok = sd_gemv_check(a.x, w.wqkv, a.qkv, nullptr, w.ln1, B, s.QKV, s.h, s.h, s.h, s.QKV, 0) == 0 &&
+         sd_gemv_check(a.ao, w.wo, a.x_mid, a.x, nullptr, B, s.h, s.QD, s.QD, s.QD, s.h, s.h) == 0 &&
+         sd_gemv_check(a.x_mid, w.wgu, a.act, nullptr, w.ln2, B, s.I, s.h, s.h, s.h, s.I, 0) == 0 &&
+         sd_gemv_check(a.act, w.wdown, a.x, a.x_mid, nullptr, B, s.h, s.I, s.I, s.I, s.h, s.h) == 0;
+  }
+  return ok;
+}
+}  // namespace
+
+extern "C" int sd_qwen3_decode_step_flags(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
+                                          const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab,
+                                          void* cache, int64_t cache_bytes, int cap, void* acts, int64_t acts_bytes,
+                                          void* logits, int B, int flags, void* stream) {
+  if (flags & ~SD_DECODE_SKINNY) return SD_ERR_SHAPE;
+  if (!d || !p) return SD_ERR_SHAPE;
   if (d->head_dim != 128) return SD_ERR_UNSUPPORTED;
   if (B <= 0 || cap <= 0 || max_len <= 0 || !ids || !pos || !logits || !cache) return SD_ERR_SHAPE;
   const Sizes s(d, B, 1);
   const DecodeActs a(d, B, cap, (char*)acts);
   if (acts_bytes < a.total || cache_bytes < sd_kvcache_bytes(d, B, cap)) return SD_ERR_WORKSPACE;
   const KvSink kv = {(char*)cache, cap};
+  const bool skinny = (flags & SD_DECODE_SKINNY) && skinny_step_ok(p, s, a, logits, B);
   RUN(sd_embedding_fwd(ids, p->embed, a.x, B, s.h, s.V, stream));
+  if (skinny) {
+    for (int l = 0; l < s.L; ++l) {
+      const sd_qwen3_layer& w = p->layers_host[l];
+      char *kp = kv.plane(s, B, l, 0), *vp = kv.plane(s, B, l, 1);
+      RUN(sd_gemv_bf16(a.x, w.wqkv, a.qkv, nullptr, w.ln1, d->eps, B, s.QKV, s.h, s.h, s.h, s.QKV, 0, stream));
+      RUN(sd_qknorm_rope_append(a.qkv, w.q_gain, w.k_gain, cos_tab, sin_tab, pos, a.q, kp, vp, B, cap, s.Hq, s.Hkv, d->eps,
+                                stream));
+      RUN(sd_attn_decode(a.q, kp, vp, a.ao, nullptr, pos, 1, a.ws, a.ws_bytes, B, cap, max_len, s.Hq, s.Hkv, 128,
+                         kSdAttnScale, stream));
+      RUN(sd_gemv_bf16(a.ao, w.wo, a.x_mid, a.x, nullptr, 0.f, B, s.h, s.QD, s.QD, s.QD, s.h, s.h, stream));
+      RUN(sd_gemv_swiglu(a.x_mid, w.wgu, a.act, w.ln2, d->eps, B, s.I, s.h, stream));
+      RUN(sd_gemv_bf16(a.act, w.wdown, a.x, a.x_mid, nullptr, 0.f, B, s.h, s.I, s.I, s.I, s.h, s.h, stream));
+    }
+    RUN(sd_gemv_bf16(a.x, p->lm_head, logits, nullptr, p->final_norm, d->eps, B, s.V, s.h, s.h, s.h, s.V, 0, stream));
+    return 0;
+  }
   for (int l = 0; l < s.L; ++l) {
     const sd_qwen3_layer& w = p->layers_host[l];
     char *kp = kv.plane(s, B, l, 0), *vp = kv.plane(s, B, l, 1);
@@ -638,4 +672,12 @@ extern "C" int sd_qwen3_decode_step(const sd_qwen3_dims* d, const sd_qwen3_param
   RUN(sd_rmsnorm_fwd(a.x, p->final_norm, a.xn, nullptr, B, s.h, d->eps, stream));
   RUN(sd_gemm_bf16(a.xn, p->lm_head, logits, nullptr, B, s.V, s.h, s.h, s.h, s.V, 0, 0, 0, stream));
   return 0;
+}
+
+extern "C" int sd_qwen3_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
+                                    const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab, void* cache,
+                                    int64_t cache_bytes, int cap, void* acts, int64_t acts_bytes, void* logits, int B,
+                                    void* stream) {
+  return sd_qwen3_decode_step_flags(d, p, ids, pos, max_len, cos_tab, sin_tab, cache, cache_bytes, cap, acts, acts_bytes,
+                                    logits, B, 0, stream);
 }

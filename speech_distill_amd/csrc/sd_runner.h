@@ -9,6 +9,12 @@ static inline int64_t al(int64_t x) { return (x + 255) & ~(int64_t)255; }
 
 constexpr float kSdAttnScale = 0.08838834764831845f;  // 128^-1/2
 
+// sd_gemv.hip: the checks of sd_gemv_bf16 / sd_gemv_swiglu without a launch (0, or the code the entry would return).  The
+// skinny decode step asks them for every projection before its first launch.  Internal: not exported from the library.
+__attribute__((visibility("hidden"))) int sd_gemv_check(const void* x, const void* w, const void* y, const void* r,
+                                                        const void* norm_gain, int M, int N, int K, int64_t ldx,
+                                                        int64_t ldw, int64_t ldy, int64_t ldr);
+
 // the shape ints every runner derives from the dims and the batch
 struct SdShape {
   int M, h, I, QD, KD, QKV, QK, V, L, Hq, Hkv;

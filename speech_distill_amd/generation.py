@@ -21,6 +21,7 @@ from .ops import _need, _stream, left_padded, sample_params, sample_step
 
 REFERENCE_SAMPLING = dict(do_sample=True, temperature=0.6, top_k=100, top_p=0.9, repetition_penalty=1.25, use_ras=True,
                           win_size=25, tau_r=0.2)  # soulxpodcast/config.py:107-118
+DECODE_KERNELS = ("tile", "skinny")
 DEFAULT_CACHE_CAPACITY = 32768  # positions; Qwen3's max_position_embeddings when the config does not say
 
 
@@ -31,13 +32,22 @@ def cache_capacity(model):
     return int(cap or DEFAULT_CACHE_CAPACITY)
 
 
+def _check_decode_kernels(decode_kernels):
+    if decode_kernels not in DECODE_KERNELS:
+        raise ValueError(f"decode_kernels must be one of {DECODE_KERNELS}, got {decode_kernels!r}")
+
+
 class Decoder:
     """The KV cache [L][2][B][cap][Hkv*128] (bf16) of one batch, the activation buffers of the two runner entries, and the
     calls themselves.  ``prefill`` fills the cache from right-padded prompts and returns the logits of each row's last
     valid token; ``step`` takes one token per row at position ``pos[b]`` (= tokens already cached) and returns the next
-    logits [B,V]."""
+    logits [B,V].  ``decode_kernels``: "tile" runs the step's projections on the training tile GEMMs; "skinny" (B <= 16)
+    streams the weights through the GEMV kernels with the norms and the SwiGLU fused in (SD_DECODE_SKINNY) -- a row's
+    logits then do not depend on the batch around it.  A step whose shapes the GEMV kernels refuse runs the tile sequence."""
 
-    def __init__(self, model, B, cap):
+    def __init__(self, model, B, cap, decode_kernels="tile"):
+        _check_decode_kernels(decode_kernels)
+        self.flags = 1 if decode_kernels == "skinny" else 0   # include/sd_hip.h SD_DECODE_SKINNY
         if model.inference_precision != "bf16":
             raise NotImplementedError('generate() decodes with the unfolded bf16 weights; this model runs "'
                                       f'{model.inference_precision}" (set_inference_precision("bf16") first)')
@@ -90,15 +100,17 @@ class Decoder:
         _need(ids, torch.int64, "ids"), _need(pos, torch.int32, "pos")
         if ids.numel() != self.B or pos.numel() != self.B:
             raise ValueError(f"decode step wants {self.B} tokens and positions")
-        check(lib.sd_qwen3_decode_step(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(), pos.data_ptr(),
-                                       int(max_len), self.cos.data_ptr(), self.sin.data_ptr(), self.cache.data_ptr(),
-                                       self.cache.numel(), self.cap, self.step_acts.data_ptr(), self.step_acts.numel(),
-                                       self.logits.data_ptr(), self.B, _stream()), "sd_qwen3_decode_step")
+        check(lib.sd_qwen3_decode_step_flags(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(), pos.data_ptr(),
+                                             int(max_len), self.cos.data_ptr(), self.sin.data_ptr(), self.cache.data_ptr(),
+                                             self.cache.numel(), self.cap, self.step_acts.data_ptr(),
+                                             self.step_acts.numel(), self.logits.data_ptr(), self.B, self.flags, _stream()),
+              "sd_qwen3_decode_step_flags")
         return self.logits
 
 
 def _check_args(model, B, T, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p, repetition_penalty,
-                use_ras, win_size, tau_r, sync_every):
+                use_ras, win_size, tau_r, sync_every, decode_kernels="tile"):
+    _check_decode_kernels(decode_kernels)
     if max_new_tokens < 1:
         raise ValueError(f"max_new_tokens must be at least 1, got {max_new_tokens}")
     if top_k < 0 or top_k > 128:
@@ -123,13 +135,13 @@ def _check_args(model, B, T, max_new_tokens, min_new_tokens, do_sample, temperat
 @torch.no_grad()
 def generate(model, input_ids, attention_mask=None, max_new_tokens=20, min_new_tokens=0, do_sample=True, temperature=1.0,
              top_k=0, top_p=1.0, repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, use_ras=False, win_size=25,
-             tau_r=0.2, seed=None, sync_every=16):
+             tau_r=0.2, seed=None, sync_every=16, decode_kernels="tile"):
     """See ``HipQwen3ForCausalLM.generate``."""
     if input_ids.dim() != 2:
         raise ValueError(f"input_ids must be [B,T], got {tuple(input_ids.shape)}")
     B, T = input_ids.shape
     _check_args(model, B, T, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p, repetition_penalty,
-                use_ras, win_size, tau_r, sync_every)
+                use_ras, win_size, tau_r, sync_every, decode_kernels)
     V = model.dims.vocab_size
     pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
     if not 0 <= pad < V or (eos_token_id is not None and not 0 <= eos_token_id < V):
@@ -152,7 +164,7 @@ def generate(model, input_ids, attention_mask=None, max_new_tokens=20, min_new_t
         kv_len = torch.full((B,), T, dtype=torch.int32, device=dev)
         valid = None
     cap = (T + max_new_tokens + 255) // 256 * 256   # whole attention partitions; the output bits do not depend on it
-    dec = Decoder(model, B, cap)
+    dec = Decoder(model, B, cap, decode_kernels)
     seq = torch.full((B, cap), pad, dtype=torch.int64, device=dev)
     seq[:, :T] = ids if valid is None else torch.where(valid, ids, torch.full_like(ids, pad))
     lens, finished = kv_len.clone(), torch.zeros(B, dtype=torch.uint8, device=dev)

@@ -664,6 +664,54 @@ def gemm_swiglu(x, wgu, save_gu=True):
     return act, gu
 
 
+# ---- weight-streaming GEMV for decode (include/sd_hip.h "weight-streaming GEMV"): M = batch <= 16
+def _rows2d(t, name):
+    if not t.is_cuda:
+        raise RuntimeError(f"speech_distill_amd: {name} must be a GPU tensor (no CPU fallback)")
+    if t.dtype != torch.bfloat16 or t.dim() != 2 or t.stride(1) != 1:
+        raise TypeError(f"{name}: expected a 2-D bf16 tensor with unit column stride")
+    return t
+
+
+def gemv_bf16(x, w, residual=None, norm_gain=None, eps=1e-6, out=None):
+    """y [M,N] = xn [M,K] @ w[N,K]^T (+ residual), xn = x or RMSNorm(x; norm_gain, eps); 1 <= M <= 16.  x, w, residual and
+    out may have strided rows.  The bits of y[m,n] depend on row m, weight row n and K only."""
+    _rows2d(x, "x"), _rows2d(w, "w")
+    M, K = x.shape
+    N, Kw = w.shape
+    if Kw != K:
+        raise ValueError(f"gemv_bf16: contraction mismatch {K} vs {Kw}")
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
+    _rows2d(out, "out")
+    if out.shape != (M, N) or (residual is not None and _rows2d(residual, "residual").shape != (M, N)):
+        raise ValueError("gemv_bf16: out / residual must be [M,N]")
+    if norm_gain is not None and _need(norm_gain, torch.bfloat16, "norm_gain").numel() != K:
+        raise ValueError(f"norm_gain must hold K = {K} elements, got {norm_gain.numel()}")
+    check(load_lib().sd_gemv_bf16(x.data_ptr(), w.data_ptr(), out.data_ptr(), _p(residual), _p(norm_gain), float(eps), M, N,
+                                  K, x.stride(0), w.stride(0), out.stride(0),
+                                  0 if residual is None else residual.stride(0), _stream()), "sd_gemv_bf16")
+    return out
+
+
+def gemv_swiglu(x, wgu, norm_gain=None, eps=1e-6):
+    """act [M,I] = silu(xn Wg^T) * (xn Wu^T) with wgu = [gate rows | up rows] [2I,K]; 1 <= M <= 16.  Equals
+    swiglu_fwd(gemv_bf16(x, wgu, norm_gain=...)) bit for bit."""
+    _need(x, torch.bfloat16, "x"), _need(wgu, torch.bfloat16, "wgu")
+    if x.dim() != 2 or wgu.dim() != 2:
+        raise ValueError(f"gemv_swiglu: x must be [M,K] and wgu [2I,K], got {tuple(x.shape)} and {tuple(wgu.shape)}")
+    M, K = x.shape
+    I = wgu.shape[0] // 2
+    if wgu.shape != (2 * I, K):
+        raise ValueError(f"gemv_swiglu: wgu must be [2I,{K}], got {tuple(wgu.shape)}")
+    if norm_gain is not None and _need(norm_gain, torch.bfloat16, "norm_gain").numel() != K:
+        raise ValueError(f"norm_gain must hold K = {K} elements, got {norm_gain.numel()}")
+    act = torch.empty(M, I, dtype=torch.bfloat16, device=x.device)
+    check(load_lib().sd_gemv_swiglu(x.data_ptr(), wgu.data_ptr(), act.data_ptr(), _p(norm_gain), float(eps), M, I, K,
+                                    _stream()), "sd_gemv_swiglu")
+    return act
+
+
 def gemm_qkv_rope(x, wqkv, q_gain, k_gain, cos, sin, T, Hq, Hkv, eps=1e-6):
     """raw q|k|v and RMS-normalised + RoPE-rotated q|k in one launch."""
     M, K = x.shape

@@ -839,7 +839,7 @@ class HipQwen3ForCausalLM(nn.Module):
 
     def generate(self, input_ids, attention_mask=None, max_new_tokens=20, min_new_tokens=0, do_sample=True,
                  temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, eos_token_id=None, pad_token_id=None,
-                 use_ras=False, win_size=25, tau_r=0.2, seed=None, sync_every=16):
+                 use_ras=False, win_size=25, tau_r=0.2, seed=None, sync_every=16, decode_kernels="tile"):
         """Decode ``max_new_tokens`` tokens per row over a KV cache (generation.py; the reference's engine:
         soulxpodcast/engine/llm_engine.py:37-76 with sampler.py:136-189).  Returns int64 [B, T + max_new_tokens]: the given
         ``input_ids`` followed by the new tokens in columns T..., ``pad_token_id`` (default: ``eos_token_id``, else 0) after
@@ -850,15 +850,18 @@ class HipQwen3ForCausalLM(nn.Module):
         arg-max; ``use_ras`` adds repetition-aware sampling (window ``win_size``, threshold ``tau_r``).  ``top_k=0`` samples
         the whole vocabulary and allows neither ``top_p < 1`` nor ``use_ras``.  ``seed`` fixes the uniforms.  The loop runs
         under no_grad on the current stream; the host reads the finished flags once every ``sync_every`` steps, and the
-        tokens do not depend on that number.
+        tokens do not depend on that number.  ``decode_kernels``: "tile" (default) runs the step's projections on the tile
+        GEMMs; "skinny" streams the weights through the GEMV kernels for batches of up to 16 rows, with the norms and the
+        SwiGLU fused in: a row's tokens then equal those of the row generated alone.
 
-        Raises before any launch: ValueError when T + max_new_tokens exceeds the cache capacity (``kv_cache_capacity`` or
-        the config's ``max_position_embeddings``), when ``top_k > 128`` or when the mask is not right-padded;
+        Raises before any launch: ValueError for another ``decode_kernels``, when T + max_new_tokens exceeds the cache
+        capacity (``kv_cache_capacity`` or the config's ``max_position_embeddings``), when ``top_k > 128`` or when the mask is not right-padded;
         NotImplementedError for a model set to "mxfp8" (the decoder reads the unfolded bf16 weights; a LoRA student's merged
         weights are those); RuntimeError for CPU tensors."""
         from .generation import generate
         return generate(self, input_ids, attention_mask, max_new_tokens, min_new_tokens, do_sample, temperature, top_k,
-                        top_p, repetition_penalty, eos_token_id, pad_token_id, use_ras, win_size, tau_r, seed, sync_every)
+                        top_p, repetition_penalty, eos_token_id, pad_token_id, use_ras, win_size, tau_r, seed, sync_every,
+                        decode_kernels)
 
     def zero_grad(self, set_to_none: bool = True):
         # keep the flat buffer; the next backward overwrites (accumulate=0) instead of adding
