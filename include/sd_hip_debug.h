@@ -56,6 +56,15 @@ int sd_debug_set(const char* key, int64_t value);
 int64_t sd_debug_get(const char* key);
 /* newline-separated list of the keys; returns the bytes needed (cap too small: nothing written) */
 int sd_debug_keys(char* buf, int cap);
+/* What sd_gemm_* would launch for this call under the current switches, without launching: writes
+ * "<kernel symbol exactly as SD_PROF_LABEL prints it>\t<grid_x>\t<grid_y>\t<block>\t<gm>" and returns the bytes needed,
+ * or a negative SD_ERR_* (cap too small: nothing written).  epi_kind: 0, or 3 SwiGLU (epi_I = I), 4 q/k-norm + RoPE,
+ * 5 SwiGLU backward, 6 delta (the fused entry points; anything else is SD_ERR_SHAPE).  The folded-RMSNorm forms
+ * (sd_gemm_swiglu_rs: ssq != NULL keeps the 256x256 kernel away) cannot be asked for: the plan is that of ssq == NULL.
+ * splits: 0 = sd_gemm_bf16 (no workspace), >= 1 = the slice count of a sd_gemm_bf16_splitk call (workspace given, also
+ * when the split-K plan is 1).  cus: CU count to plan for (a machine without a GPU passes 256). */
+int sd_debug_gemm_plan(int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int trans_a, int trans_b,
+                       int epi_kind, int has_residual, int splits, int epi_I, int shared_gpu, int cus, char* buf, int cap);
 
 #ifdef __cplusplus
 }

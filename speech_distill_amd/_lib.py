@@ -108,6 +108,7 @@ DEBUG_PROTOTYPES = {
     "sd_debug_set": (_i, [_cp, _i64]),
     "sd_debug_get": (_i64, [_cp]),
     "sd_debug_keys": (_i, [_vp, _i]),
+    "sd_debug_gemm_plan": (_i, [_i, _i, _i, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i]),
 }
 PROTOTYPES = {
     "sd_abi_version": (_i, []),
@@ -250,6 +251,24 @@ def debug_set(key: str, value: int):
 
 def debug_get(key: str) -> int:
     return int(load_lib().sd_debug_get(key.encode()))
+
+
+def gemm_plan(M, N, K, trans_a=False, trans_b=False, *, lda=None, ldb=None, ldc=None, epi_kind=0, residual=False,
+              split_k=False, epi_I=0, shared_gpu=False, cus=256):
+    """include/sd_hip_debug.h sd_debug_gemm_plan: what the GEMM dispatch would launch under the current switches, nothing
+    launched (no GPU needed): {"symbol", "grid_x", "grid_y", "block", "gm"}.  Leading dimensions default to contiguous
+    operands; split_k: the call goes through sd_gemm_bf16_splitk with its own slice count, as ops.gemm(split_k=True) does."""
+    lib = load_lib()
+    lda = (M if trans_a else K) if lda is None else lda
+    ldb = (N if trans_b else K) if ldb is None else ldb
+    splits = lib.sd_gemm_splitk_plan(M, N, K) if split_k else 0
+    buf = C.create_string_buffer(160)
+    rc = lib.sd_debug_gemm_plan(M, N, K, lda, ldb, N if ldc is None else ldc, int(trans_a), int(trans_b), epi_kind,
+                                int(residual), splits, epi_I, int(shared_gpu), cus, buf, len(buf))
+    if rc < 0:
+        raise SdHipError(f"sd_debug_gemm_plan failed: {ERRORS.get(rc, rc)}")
+    sym, *nums = buf.value.decode().split("\t")
+    return dict(zip(("grid_x", "grid_y", "block", "gm"), map(int, nums)), symbol=sym)
 
 
 def gemm_force_variant(bm: int, nst: int):

@@ -23,9 +23,12 @@
 // as fp32 and written out in full 16-byte row pieces with the epilogue fused (+ residual / accumulate).  Split-K
 // (contraction over the vocabulary): every K slice writes an fp32 slab; a reduce kernel -- or the consumer itself
 // (sd_rmsnorm_bwd_slabs) -- sums the slabs in a fixed order.
+#include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include "sd_common.cuh"
 #include "../../include/sd_hip.h"
+#include "../../include/sd_hip_debug.h"
 #include "sd_prof.h"
 #include "sd_debug.h"
 
@@ -1481,176 +1484,56 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 #ifdef SD_STAMPS
 void* g_stamp_buffer = nullptr;  // diagnostic build: device buffer for the phase stamps of gemm_pstag_kernel
 #endif
+// ---- Host side.  gemm_plan() decides kernel, tile and grid of a call; it is pure (reads its two arguments and kGemmTable)
+// and sd_debug_gemm_plan prints its answer without a GPU (tests/test_gemm_plan_cpu.py).  launch_plan() only launches.
+struct GemmTableEntry { int ta, tb, epi, M, N, K, bm, nst, flags; };
+const GemmTableEntry kGemmTable[] = {
+#include "sd_gemm_table.inc"
+};
+
+enum GemmKernel { K_BF16, K_STAG, K_PSTAG, K_P256 };
+struct GemmQuery {
+  int M, N, K; long lda, ldb; bool ta, tb;
+  int epi_kind;           // 0, or 3..6: the fused epilogue of the entry point
+  bool has_r, has_slabs;  // residual given; split-K workspace given (also when the split-K plan is a single slice)
+  int splits, epi_I; bool epi_ssq_in;  // EpiArgs::I and ssq_in != NULL: what the 256 x 256 choice reads of the epilogue
+  bool shared_gpu; int cus;            // t_sd_shared_gpu of the caller; device_cus() (0 = unknown)
+};
+struct GemmPlan {
+  int rc;  // 0, or SD_ERR_UNSUPPORTED: a fused epilogue without descriptor staging
+  GemmKernel kernel; int bm, nst, epi; bool ta, tb, fast, pair;  // the template arguments (nst 9 = the staggered family)
+  // launch shape and tile arguments; gemm_p256_kernel: its own t_m, t_n and group in tiles_m, tiles_n, gm
+  int grid_x, grid_y, block, gm, per, tiles_m, tiles_n;
+};
+
 // Measurement switches live in g_sd_debug (sd_debug.h, set through include/sd_hip_debug.h); defaults = product behaviour.
 // gemm_cu_budget (multi-GPU runs): the persistent kernels of the BACKWARD (grouped weight gradients, lm_head weight
 // gradient) take one workgroup per CU for their whole duration; when RCCL's reduction kernels hold c CUs meanwhile, c
 // workgroups start only after others have finished and the launch takes up to twice as long (measured with
 // bench.py --experiment-cu-hog 16: +22 % / +70 %).  A budget of 256 - c keeps every workgroup resident from the start.
-// Default (knob 0): when the backward runs them on its side stream beside the dX chain (t_sd_shared_gpu, set by the
+// Default (knob 0): when the backward runs them on its side stream beside the dX chain (shared_gpu, set by the
 // runner), three quarters of the CUs -- the chain's kernels then always find CUs instead of queueing behind a launch
 // that holds every one of them for 70-550 us: 19.51 -> 19.31 ms per config-2 step and half the run-to-run spread
 // (tests/bench_knob_ab.py gemm.cu_budget 0 192, alternating in one process; 224 / 160 / 128 measured no better).
 // Only for 1 536 .. 3 072 tokens per launch (K of a weight-gradient GEMM): measured -0.16 / -0.20 / -0.19 ms at 1 536 /
 // 2 048 / 3 072 tokens, +-0.0 at 1 024, +0.1 at 512, and +0.57 / +1.3 ms at 4 096 / 8 192, where the chain's own kernels
 // fill the chip for long stretches and the budget only slows the weight gradients.  Knob -1: one workgroup per CU always.
-static int cu_budget(int cus, int tokens) {
-  if (g_sd_debug.gemm_cu_budget > 0) return g_sd_debug.gemm_cu_budget & ~7;
+int cu_budget(int cus, int tokens, bool shared_gpu, const SdDebug& d) {
+  if (d.gemm_cu_budget > 0) return d.gemm_cu_budget & ~7;
   const bool in_range = tokens >= 1536 && tokens <= 3072;
-  return (g_sd_debug.gemm_cu_budget == 0 && t_sd_shared_gpu && in_range) ? ((cus * 3 / 4) & ~7) : 0;
-}
-thread_local bool g_skip_reduce = false;  // set by sd_gemm_bf16_splitk_partial around its dispatch
-
-template <int BM, int NST, bool TA, bool TB>
-int launch(const void* A, const void* B, void* C, const void* R, float* slabs, int splits, int M, int N, int K, long lda,
-           long ldb, long ldc, long ldr, int epi_kind, const EpiArgs& ea, hipStream_t st, int tflags) {
-  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
-  const int kt_all = (K + BK - 1) / BK;
-  const int per = (kt_all + splits - 1) / splits;
-  dim3 grid(tiles_m * tiles_n, splits), block(BM == 256 ? 512 : 256);
-  // descriptor-based staging needs every k >= K to read as zero in at least one operand (transposed
-  // operands get that from the hardware range check; two K-contiguous ones need K % 64 == 0) and 31-bit offsets
-  const long bytes_a = (TA ? ((long)(K - 1) * lda + M) : ((long)(M - 1) * lda + K)) * 2;
-  const long bytes_b = (TB ? ((long)(K - 1) * ldb + N) : ((long)(N - 1) * ldb + K)) * 2;
-  const long span = ((long)kt_all + 6) * BK * 2 * (TA ? lda : 1) + bytes_a;
-  const long span_b = ((long)kt_all + 6) * BK * 2 * (TB ? ldb : 1) + bytes_b;
-  // persistent kernel: one workgroup per CU (a multiple of 8 so that every workgroup stays on its XCD's tile run)
-  static const int all_cus = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return 0;
-    return cus & ~7;
-  }();
-  // tflags: what the measured table (sd_gemm_table.inc) asks for this very shape: 1 no persistent kernel, 2 no 256x256
-  // kernel, 4 the 256x256 kernel whatever the tile count
-  const int persist_grid = (g_sd_debug.gemm_no_persist || (tflags & 1)) ? 0 : all_cus;
-  const bool p256_ok = !g_sd_debug.gemm_no_p256 && !(tflags & 2);
-  const bool p256_pair = !g_sd_debug.gemm_p256_unpaired;
-  // Measured (tests/bench_p256.py, MI355X): the 256 x 256 kernel ties the 256 x 128 one on the lm_head class (544 vs
-  // 557 us student, 924 vs 929 us teacher) and loses on gate|up (114 vs 93 us teacher, 37.6 vs 36.3 us student): both
-  // settle at ~0.9 us per staged K-step whatever the bytes of the step, i.e. the loop is paced by the latency of the
-  // operand stream at the LDS-limited prefetch depth, not by L2 -> LDS bandwidth per FLOP.  So only the vocabulary-wide
-  // GEMMs take it.  gemm.p256_min_tiles (sd_hip_debug.h) lowers the threshold for measurements / tests.
-  const int p256_min_tiles = (tflags & 4) ? 1 : g_sd_debug.gemm_p256_min_tiles;
-  const int gm_env = g_sd_debug.gemm_group_m;
-  int gm = gm_env > 0 ? gm_env : (BM == 256 ? 4 : 8);
-  if (gm > tiles_m) gm = tiles_m;
-  const bool fast = !g_sd_debug.gemm_checked_staging && (TA || TB || (K % BK) == 0) && span < 0x7fffffffL && span_b < 0x7fffffffL;
-#ifdef SD_STAMPS
-#define SD_STAMP_ARGS() EpiArgs ea_st = ea; ea_st.cos_t = (const bf16*)g_stamp_buffer
-#define SD_STAMP_EA ea_st
-#else
-#define SD_STAMP_ARGS() do { } while (0)
-#define SD_STAMP_EA ea
-#endif
-#define SD_GEMM_GO(EPI)                                                                                              \
-  do {                                                                                                               \
-    if constexpr (BM == 256 && NST == 9 && !TA && !TB && (EPI == 0 || EPI == 3)) {                                   \
-      /* many-column forward GEMMs: 256 x 256 tiles when they still fill >= 70 % of the CUs' rounds */               \
-      const int t_m = (M + 255) / 256, t_n = (EPI == 3) ? (ea.I + 127) / 128 : (N + 255) / 256, nt2 = t_m * t_n;       \
-      const int rounds = persist_grid > 0 ? (nt2 + persist_grid - 1) / persist_grid : 0;                              \
-      if (splits == 1 && !R && !ea.ssq_in && p256_ok && persist_grid > 0 && (K % P2_BK) == 0 &&                         \
-          (EPI != 3 || (ea.I % 128) == 0) &&                                                                          \
-          (N % 8) == 0 && nt2 >= p256_min_tiles && 10 * nt2 >= 7 * rounds * persist_grid && span < 0x7fffffffL &&      \
-          span_b < 0x7fffffffL) {                                                                                     \
-        const int grid2 = nt2 > persist_grid ? persist_grid : nt2;                                                    \
-        if (p256_pair && (K % (2 * P2_BK)) == 0) {                                                                    \
-          SD_PROF_LABEL("gemm_p256_kernel<%d, true>", EPI);                                                           \
-          hipLaunchKernelGGL((gemm_p256_kernel<EPI, true>), dim3(grid2), dim3(512), 0, st, (const bf16*)A,             \
-                             (const bf16*)B, (bf16*)C, M, N, K, lda, ldb, ldc, t_m, t_n, t_m < 8 ? t_m : 8, ea);        \
-        } else {                                                                                                       \
-          SD_PROF_LABEL("gemm_p256_kernel<%d, false>", EPI);                                                          \
-          hipLaunchKernelGGL((gemm_p256_kernel<EPI, false>), dim3(grid2), dim3(512), 0, st, (const bf16*)A,            \
-                             (const bf16*)B, (bf16*)C, M, N, K, lda, ldb, ldc, t_m, t_n, t_m < 8 ? t_m : 8, ea);        \
-        }                                                                                                              \
-        break;                                                                                                         \
-      }                                                                                                                \
-    }                                                                                                                  \
-    if constexpr (BM == 256 && NST == 9 && (EPI == 0 || EPI == 3)) {                                                 \
-      if (splits == 1 && tiles_m * tiles_n > persist_grid && persist_grid > 0) {                                       \
-        SD_PROF_LABEL("gemm_pstag_kernel<4, %s, %s, %d>", TA ? "true" : "false", TB ? "true" : "false", EPI);          \
-        SD_STAMP_ARGS();                                                                                               \
-        /* weight gradients (TA): the backward's persistent launches honour the CU budget of a multi-GPU run */       \
-        const int cb = cu_budget(persist_grid, K);                                                                     \
-        int pg = (TA && cb > 0 && cb < persist_grid) ? cb : persist_grid;                                              \
-        if (!TA && g_sd_debug.gemm_fwd_cu_budget > 0 && t_sd_shared_gpu && g_sd_debug.gemm_fwd_cu_budget < pg)         \
-          pg = g_sd_debug.gemm_fwd_cu_budget & ~7; /* (measurement) forward persistent launches beside another stream */ \
-        if (!TA && g_sd_debug.gemm_persist_balance) { /* (measurement) equal tiles per workgroup */                    \
-          const int nt = tiles_m * tiles_n, rounds = (nt + persist_grid - 1) / persist_grid;                           \
-          pg = (((nt + rounds - 1) / rounds) + 7) & ~7;                                                                \
-          if (pg > persist_grid) pg = persist_grid;                                                                    \
-        }                                                                                                              \
-        hipLaunchKernelGGL((gemm_pstag_kernel<4, TA, TB, EPI>), dim3(pg), dim3(768), 0, st, (const bf16*)A,            \
-                           (const bf16*)B, (bf16*)C, (const bf16*)R, M, N, K, lda, ldb, ldc, ldr, tiles_m, tiles_n,    \
-                           gm, SD_STAMP_EA);                                                                           \
-        break;                                                                                                         \
-      }                                                                                                                \
-    }                                                                                                                  \
-    if constexpr (BM == 256 && NST == 9) {                                                                           \
-      SD_PROF_LABEL("gemm_stag_kernel<%s, %s, %d>", TA ? "true" : "false", TB ? "true" : "false", EPI);                \
-      hipLaunchKernelGGL((gemm_stag_kernel<TA, TB, EPI>), grid, block, 0, st, (const bf16*)A, (const bf16*)B,          \
-                         (bf16*)C, (const bf16*)R, slabs, M, N, K, lda, ldb, ldc, ldr, tiles_m, tiles_n, per, gm, ea); \
-    } else if (fast || EPI >= 3) {                                                                                   \
-      SD_PROF_LABEL("gemm_bf16_kernel<%d, %d, %s, %s, %d, true>", BM, (NST == 9 ? 3 : NST), TA ? "true" : "false",     \
-                    TB ? "true" : "false", EPI);                                                                       \
-      hipLaunchKernelGGL((gemm_bf16_kernel<BM, (NST == 9 ? 3 : NST), TA, TB, EPI, true>), grid, block, 0, st,          \
-                         (const bf16*)A, (const bf16*)B, (bf16*)C, (const bf16*)R, slabs, M, N, K, lda, ldb, ldc, ldr, \
-                         tiles_m, tiles_n, per, gm, ea);                                                             \
-    } else                                                                                                           \
-      hipLaunchKernelGGL((gemm_bf16_kernel<BM, (NST == 9 ? 3 : NST), TA, TB, (EPI >= 3 ? 0 : EPI), false>), grid,      \
-                         block, 0, st, (const bf16*)A, (const bf16*)B, (bf16*)C, (const bf16*)R, slabs, M, N, K, lda,  \
-                         ldb, ldc, ldr, tiles_m, tiles_n, per, gm, ea);                                              \
-  } while (0)
-  if constexpr (!TA && !TB) {
-    if (epi_kind == 3) { if (!fast) return SD_ERR_UNSUPPORTED; SD_GEMM_GO(3); SD_CHECK_LAUNCH(); return 0; }
-    if (epi_kind == 4) { if (!fast) return SD_ERR_UNSUPPORTED; SD_GEMM_GO(4); SD_CHECK_LAUNCH(); return 0; }
-  }
-  if constexpr (!TA && TB) {
-    if (epi_kind == 5) { if (!fast) return SD_ERR_UNSUPPORTED; SD_GEMM_GO(5); SD_CHECK_LAUNCH(); return 0; }
-    if (epi_kind == 6) { if (!fast || splits != 1) return SD_ERR_UNSUPPORTED; SD_GEMM_GO(6); SD_CHECK_LAUNCH(); return 0; }
-  }
-  if (splits > 1) SD_GEMM_GO(2);
-  else if (R) SD_GEMM_GO(1);
-  else SD_GEMM_GO(0);
-#undef SD_GEMM_GO
-  SD_CHECK_LAUNCH();
-  if (splits > 1 && !g_skip_reduce) {
-    const long n8 = (long)M * N / 8;
-    const int nb = (int)((n8 + 255) / 256 < 2048 ? (n8 + 255) / 256 : 2048);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(nb), dim3(256), 0, st, (const float*)slabs, (bf16*)C, (const bf16*)R, M,
-                       N, ldc, ldr, splits);
-    SD_CHECK_LAUNCH();
-  }
-  return 0;
+  return (d.gemm_cu_budget == 0 && shared_gpu && in_range) ? ((cus * 3 / 4) & ~7) : 0;
 }
 
-struct GemmTableEntry { int ta, tb, epi, M, N, K, bm, nst, flags; };
-const GemmTableEntry kGemmTable[] = {
-#include "sd_gemm_table.inc"
-};
-
-int check_args(const void* A, const void* B, const void* C, const void* R, int M, int N, int K, int64_t lda, int64_t ldb,
-               int64_t ldc, int64_t ldr, int trans_a, int trans_b) {
-  if (M <= 0 || N <= 0 || K <= 0) return SD_ERR_SHAPE;
-  if ((lda | ldb | ldc | (R ? ldr : 0)) & 7) return SD_ERR_ALIGN;
-  if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)R) & 15) return SD_ERR_ALIGN;
-  if (N & 7) return SD_ERR_ALIGN;
-  if ((!trans_a || !trans_b) && (K & 7)) return SD_ERR_ALIGN;
-  if (trans_a && (M & 7)) return SD_ERR_ALIGN;
-  return 0;
-}
-
-
-int dispatch(const void* A, const void* B, void* C, const void* R, float* slabs, int splits, int M, int N, int K,
-             long lda, long ldb, long ldc, long ldr, int ta, int tb, hipStream_t st, int epi_kind = 0,
-             const EpiArgs* eap = nullptr) {
-  const EpiArgs ea = eap ? *eap : EpiArgs{};
-  // Picked from tests/bench_shapes.py --tune --cold on MI355X (weight operand HBM-cold, as in the real step
-  // where every layer streams its own weights).  NT/NN read weights: latency-bound on HBM misses, so large
-  // tiles / deeper rings win whenever the grid still covers the 256 CUs; TN (dW) reads two warm activations.
+GemmPlan gemm_plan(const GemmQuery& q, const SdDebug& d) {
+  const int M = q.M, N = q.N, K = q.K, splits = q.splits, epi_kind = q.epi_kind;
+  const bool ta = q.ta, tb = q.tb;
+  // 1. Tile heuristic per layout.  Picked from tests/bench_shapes.py --tune --cold on MI355X (weight operand HBM-cold,
+  // as in the real step where every layer streams its own weights).  NT/NN read weights: latency-bound on HBM misses, so
+  // large tiles / deeper rings win whenever the grid still covers the 256 CUs; TN (dW) reads two warm activations.
   const long tiles256 = (long)((M + 255) / 256) * ((N + BN - 1) / BN) * splits;
   const long tiles128 = (long)((M + 127) / 128) * ((N + BN - 1) / BN) * splits;
   const long blocks64 = (long)((M + 63) / 64) * ((N + BN - 1) / BN) * splits;
-  int bm, nst;
+  int bm, nst, tflags = 0;
   if (!ta && !tb) {  // forward linear
     if (tiles256 >= 256) { bm = 256; nst = 9; }  // 9 = the staggered two-half kernel (gemm_stag_kernel)
     else if (tiles128 >= 256) { bm = 128; nst = 3; }
@@ -1665,25 +1548,25 @@ int dispatch(const void* A, const void* B, void* C, const void* R, float* slabs,
     else if (tiles128 >= 256) { bm = 128; nst = 3; }
     else { bm = 64; nst = 3; }
   } else {  // TN: dW = dY^T . X (two warm activations)
-    const long tn_stag_min = g_sd_debug.gemm_tn_stag_min;
-    if (tiles256 >= tn_stag_min) { bm = 256; nst = 9; }
+    if (tiles256 >= (long)d.gemm_tn_stag_min) { bm = 256; nst = 9; }
     else if (tiles128 >= 320) { bm = 128; nst = 2; }
     else { bm = 64; nst = blocks64 <= 320 ? 3 : 2; }
   }
-  // Dispatch by measurement (round 4): the GEMM calls of the distillation step at the BASELINE config 2 / 4 / 5 shapes were
-  // timed under every variant (tests/bench_tune.py -> profiles/r04_gemm_tune.json -> scripts/make_gemm_table.py); where a
-  // variant beat the heuristic above by >= 2 % the table names it.  Any other shape keeps the heuristic.
-  int tflags = 0;
-  if (!g_sd_debug.gemm_no_table && !g_sd_debug.gemm_force_bm) {
-    const int key_epi = epi_kind ? epi_kind : (slabs ? 2 : (R ? 1 : 0));
+  // 2. Dispatch by measurement (round 4): the GEMM calls of the distillation step at the BASELINE config 2 / 4 / 5 shapes
+  // were timed under every variant (tests/bench_tune.py -> profiles/r04_gemm_tune.json -> scripts/make_gemm_table.py);
+  // where a variant beat the heuristic above by >= 2 % the table names it.  Any other shape keeps the heuristic.
+  // tflags: what the table asks for this very shape: 1 no persistent kernel, 2 no 256x256 kernel, 4 the 256x256 kernel
+  // whatever the tile count
+  if (!d.gemm_no_table && !d.gemm_force_bm) {
+    const int key_epi = epi_kind ? epi_kind : (q.has_slabs ? 2 : (q.has_r ? 1 : 0));
     for (const GemmTableEntry& e : kGemmTable)
       if (e.M == M && e.N == N && e.K == K && e.ta == ta && e.tb == tb && e.epi == key_epi) {
         if (e.bm) { bm = e.bm; nst = e.nst; tflags = e.flags; }
         break;
       }
   }
-  if (g_sd_debug.gemm_force_bm) { bm = g_sd_debug.gemm_force_bm; nst = g_sd_debug.gemm_force_nst; }
-  // A pass that shares the GPU with a second stream (SD_FWD_CONCURRENT: the frozen teacher beside the student's forward)
+  if (d.gemm_force_bm) { bm = d.gemm_force_bm; nst = d.gemm_force_nst; }  // 3. the forced variant of tests / benchmarks
+  // 4. A pass that shares the GPU with a second stream (SD_FWD_CONCURRENT: the frozen teacher beside the student's forward)
   // is not served by tiles chosen to cover all 256 CUs: what counts then is CU-time per FLOP, and the other stream fills
   // whatever this launch leaves free.  The forward GEMMs that end in a residual add (o / down projections: N = hidden,
   // 256 tiles of 64 x 128 for the student, of 128 x 128 for the teacher) take the next tile up -- half as many workgroups
@@ -1692,45 +1575,199 @@ int dispatch(const void* A, const void* B, void* C, const void* R, float* slabs,
   // the tile that covers the chip still yields >= 192 workgroups (>= 96 after the step up): -0.46 / -0.50 / -0.85 / -0.32 ms
   // per step at 1 536 / 2 048 / 3 072 / 4 096 tokens, +-0.0 at 1 024 (128 -> 64 workgroups), +0.35 ms at 512 (64 -> 32).
   const long tiles_now = (long)((M + bm - 1) / bm) * ((N + BN - 1) / BN);
-  const int bump = g_sd_debug.gemm_fwd_bump > 0 ? g_sd_debug.gemm_fwd_bump
-                   : (g_sd_debug.gemm_fwd_bump == 0 && t_sd_shared_gpu && tiles_now >= 192 ? 3 : 0);
-  if (bump && !ta && !tb && R && !slabs && epi_kind <= 1) {
+  const int bump = d.gemm_fwd_bump > 0 ? d.gemm_fwd_bump : (d.gemm_fwd_bump == 0 && q.shared_gpu && tiles_now >= 192 ? 3 : 0);
+  if (bump && !ta && !tb && q.has_r && !q.has_slabs && epi_kind <= 1) {
     if (bm == 64 && (bump & 16)) { bm = 256; nst = 9; }
     else if (bm == 64 && (bump & 1)) { bm = 128; nst = (bump & 32) ? 2 : 3; }
     else if (bm == 128 && (bump & 2)) { bm = 256; nst = 9; }
     else if (bm == 128 && (bump & 64)) { nst = 2; }   // (measurement) 64 KiB of LDS: two workgroups per CU
   }
-  if ((bump & 12) && !ta && tb && !slabs && splits == 1) {    // (measurement only) the same for the dX GEMMs
+  if ((bump & 12) && !ta && tb && !q.has_slabs && splits == 1) {    // (measurement only) the same for the dX GEMMs
     if (bm == 64 && (bump & 4)) { bm = 128; nst = 3; }
     else if (bm == 128 && (bump & 8)) { bm = 256; nst = 9; }
   }
-  // the staggered kernel only has the descriptor staging path
-  bool stag_ok = !g_sd_debug.gemm_checked_staging && (ta || tb || (K % BK) == 0) &&
-                       ((long)K * (ta ? lda : 1) + (long)M * (ta ? 1 : lda)) * 2 < 0x70000000L &&
-                       ((long)K * (tb ? ldb : 1) + (long)N * (tb ? 1 : ldb)) * 2 < 0x70000000L;
+  // 5. Descriptor-based staging needs every k >= K to read as zero in at least one operand (transposed operands get that
+  // from the hardware range check; two K-contiguous ones need K % 64 == 0) and 31-bit offsets.  Two forms of that test:
+  const bool desc_k_ok = !d.gemm_checked_staging && (ta || tb || (K % BK) == 0);
+  // stag_ok guards gemm_stag_kernel and gemm_pstag_kernel, which only have the descriptor path: without it 256x9 -> 256x3
+  const bool stag_ok = desc_k_ok && ((long)K * (ta ? q.lda : 1) + (long)M * (ta ? 1 : q.lda)) * 2 < 0x70000000L &&
+                       ((long)K * (tb ? q.ldb : 1) + (long)N * (tb ? 1 : q.ldb)) * 2 < 0x70000000L;
   if (nst == 9 && (!stag_ok || bm != 256)) nst = 3;
-  SdProfScope prof(ta ? SD_K_GEMM_TN : (tb ? SD_K_GEMM_NN : ((bm == 256 && nst == 9) ? SD_K_GEMM_NT_STAG : SD_K_GEMM_NT)),
-                   2.0 * M * N * K, st);
-#define SD_GO(BM_, NST_, TA_, TB_) \
-  return launch<BM_, NST_, TA_, TB_>(A, B, C, R, slabs, splits, M, N, K, lda, ldb, ldc, ldr, epi_kind, ea, st, tflags)
-#define SD_PICK(TA_, TB_)                                   \
-  do {                                                      \
-    if (bm == 256 && nst == 9 && stag_ok) SD_GO(256, 9, TA_, TB_); \
-    if (bm == 256 && nst == 2) SD_GO(256, 2, TA_, TB_);     \
-    if (bm == 256) SD_GO(256, 3, TA_, TB_);                 \
-    if (bm == 64 && nst == 2) SD_GO(64, 2, TA_, TB_);       \
-    if (bm == 64 && nst == 3) SD_GO(64, 3, TA_, TB_);       \
-    if (bm == 64) SD_GO(64, 4, TA_, TB_);                   \
-    if (nst == 2) SD_GO(128, 2, TA_, TB_);                  \
-    if (nst == 4) SD_GO(128, 4, TA_, TB_);                  \
-    SD_GO(128, 3, TA_, TB_);                                \
+  // the tiles that exist: 256 x {9, 2, 3}, 64 x {2, 3, 4}, 128 x {2, 4, 3}; anything else takes the last of its row
+  bm = bm == 256 || bm == 64 ? bm : 128;
+  if (bm == 256) nst = (nst == 9 || nst == 2) ? nst : 3;
+  else if (bm == 64) nst = (nst == 2 || nst == 3) ? nst : 4;
+  else nst = (nst == 2 || nst == 4) ? nst : 3;
+  const int tiles_m = (M + bm - 1) / bm, tiles_n = (N + BN - 1) / BN, kt_all = (K + BK - 1) / BK;
+  const int gm = d.gemm_group_m > 0 ? d.gemm_group_m : (bm == 256 ? 4 : 8);
+  GemmPlan p{};
+  p.kernel = (bm == 256 && nst == 9) ? K_STAG : K_BF16;
+  p.bm = bm; p.nst = nst; p.ta = ta; p.tb = tb;
+  p.grid_x = tiles_m * tiles_n; p.grid_y = splits; p.block = bm == 256 ? 512 : 256;
+  p.gm = gm < tiles_m ? gm : tiles_m; p.per = (kt_all + splits - 1) / splits; p.tiles_m = tiles_m; p.tiles_n = tiles_n;
+  // 6. fast guards gemm_bf16_kernel<..., true> (else its pointer-staging form <..., false>), every fused epilogue
+  // (EPI >= 3, which has no pointer-staging form) and, through its two span tests, gemm_p256_kernel
+  const long bytes_a = (ta ? ((long)(K - 1) * q.lda + M) : ((long)(M - 1) * q.lda + K)) * 2;
+  const long bytes_b = (tb ? ((long)(K - 1) * q.ldb + N) : ((long)(N - 1) * q.ldb + K)) * 2;
+  const bool span_ok = ((long)kt_all + 6) * BK * 2 * (ta ? q.lda : 1) + bytes_a < 0x7fffffffL &&
+                       ((long)kt_all + 6) * BK * 2 * (tb ? q.ldb : 1) + bytes_b < 0x7fffffffL;
+  p.fast = desc_k_ok && span_ok;
+  const bool fused = !ta && (tb ? (epi_kind == 5 || epi_kind == 6) : (epi_kind == 3 || epi_kind == 4));
+  p.epi = fused ? epi_kind : (splits > 1 ? 2 : (q.has_r ? 1 : 0));
+  if (fused && (!p.fast || (epi_kind == 6 && splits != 1))) p.rc = SD_ERR_UNSUPPORTED;
+  // 7. persistent kernels (256 x 9, plain or SwiGLU epilogue, unsplit): one workgroup per CU
+  const int persist_grid = (d.gemm_no_persist || (tflags & 1)) ? 0 : q.cus;
+  if (p.rc || p.kernel != K_STAG || (p.epi != 0 && p.epi != 3) || splits != 1 || persist_grid <= 0) return p;
+  // 8. many-column forward GEMMs: 256 x 256 tiles when they still fill >= 70 % of the CUs' rounds.
+  // Measured (tests/bench_p256.py, MI355X): the 256 x 256 kernel ties the 256 x 128 one on the lm_head class (544 vs
+  // 557 us student, 924 vs 929 us teacher) and loses on gate|up (114 vs 93 us teacher, 37.6 vs 36.3 us student): both
+  // settle at ~0.9 us per staged K-step whatever the bytes of the step, i.e. the loop is paced by the latency of the
+  // operand stream at the LDS-limited prefetch depth, not by L2 -> LDS bandwidth per FLOP.  So only the vocabulary-wide
+  // GEMMs take it.  gemm.p256_min_tiles (sd_hip_debug.h) lowers the threshold for measurements / tests.
+  const int t_m = (M + 255) / 256, t_n = (p.epi == 3) ? (q.epi_I + 127) / 128 : (N + 255) / 256, nt2 = t_m * t_n;
+  const int rounds = (nt2 + persist_grid - 1) / persist_grid;
+  const int p256_min_tiles = (tflags & 4) ? 1 : d.gemm_p256_min_tiles;
+  if (!ta && !tb && !q.has_r && !q.epi_ssq_in && !d.gemm_no_p256 && !(tflags & 2) && (K % P2_BK) == 0 &&
+      (p.epi != 3 || (q.epi_I % 128) == 0) && (N % 8) == 0 && nt2 >= p256_min_tiles &&
+      10 * nt2 >= 7 * rounds * persist_grid && span_ok) {
+    p.kernel = K_P256; p.pair = !d.gemm_p256_unpaired && (K % (2 * P2_BK)) == 0;
+    p.grid_x = nt2 > persist_grid ? persist_grid : nt2; p.block = 512;
+    p.tiles_m = t_m; p.tiles_n = t_n; p.gm = t_m < 8 ? t_m : 8;
+    return p;
+  }
+  // 9. the persistent 256 x 128 kernel once there are more tiles than CUs
+  if (tiles_m * tiles_n <= persist_grid) return p;
+  p.kernel = K_PSTAG; p.block = 768;
+  // weight gradients (TA): the backward's persistent launches honour the CU budget of a multi-GPU run
+  const int cb = cu_budget(persist_grid, K, q.shared_gpu, d);
+  p.grid_x = (ta && cb > 0 && cb < persist_grid) ? cb : persist_grid;
+  if (!ta && d.gemm_fwd_cu_budget > 0 && q.shared_gpu && d.gemm_fwd_cu_budget < p.grid_x)
+    p.grid_x = d.gemm_fwd_cu_budget & ~7;  // (measurement) forward persistent launches beside another stream
+  if (!ta && d.gemm_persist_balance) {  // (measurement) equal tiles per workgroup
+    const int nt = tiles_m * tiles_n, rounds_nt = (nt + persist_grid - 1) / persist_grid;
+    p.grid_x = (((nt + rounds_nt - 1) / rounds_nt) + 7) & ~7;
+    if (p.grid_x > persist_grid) p.grid_x = persist_grid;
+  }
+  return p;
+}
+
+// the kernel symbol as rocprofv3 prints it: bench.py and the tests match on these strings
+const char* plan_symbol(const GemmPlan& p, char (&s)[96]) {
+  const char *ta = p.ta ? "true" : "false", *tb = p.tb ? "true" : "false";
+  const char* last = (p.kernel == K_P256 ? p.pair : p.fast) ? "true" : "false";
+  switch (p.kernel) {
+    case K_P256: snprintf(s, sizeof s, "gemm_p256_kernel<%d, %s>", p.epi, last); break;
+    case K_PSTAG: snprintf(s, sizeof s, "gemm_pstag_kernel<4, %s, %s, %d>", ta, tb, p.epi); break;
+    case K_STAG: snprintf(s, sizeof s, "gemm_stag_kernel<%s, %s, %d>", ta, tb, p.epi); break;
+    default: snprintf(s, sizeof s, "gemm_bf16_kernel<%d, %d, %s, %s, %d, %s>", p.bm, p.nst, ta, tb, p.epi, last);
+  }
+  return s;
+}
+
+struct GemmOperands {
+  const bf16 *A, *B; bf16* C; const bf16* R; float* slabs;
+  int M, N, K; long lda, ldb, ldc, ldr;
+};
+
+// One (layout, epilogue): the plan's kernel, tile and staging form -> the template instantiation.  No decisions here;
+// SD_ERR_UNSUPPORTED = not a plan that gemm_plan produces.
+template <bool TA, bool TB, int EPI>
+int launch_inst(const GemmPlan& p, const GemmOperands& o, const EpiArgs& ea, hipStream_t st) {
+  const dim3 grid(p.grid_x, p.grid_y), block(p.block);
+#define SD_LAUNCH(KERNEL, ...)                                                                \
+  do {                                                                                        \
+    hipLaunchKernelGGL(KERNEL, grid, block, 0, st, o.A, o.B, o.C, __VA_ARGS__);               \
+    SD_CHECK_LAUNCH();                                                                        \
+    return 0;                                                                                 \
   } while (0)
-  if (!ta && !tb) SD_PICK(false, false);
-  if (!ta && tb) SD_PICK(false, true);
-  if (ta && tb) SD_PICK(true, true);
-  SD_PICK(true, false);
-#undef SD_PICK
-#undef SD_GO
+#define SD_SHAPE_ARGS o.M, o.N, o.K, o.lda, o.ldb, o.ldc
+#define SD_TILE_ARGS o.R, o.slabs, SD_SHAPE_ARGS, o.ldr, p.tiles_m, p.tiles_n, p.per, p.gm, ea
+#define SD_BF16_CASE(BM, NST)                                                                         \
+  case BM * 16 + NST:                                                                                 \
+    if (p.fast) SD_LAUNCH((gemm_bf16_kernel<BM, NST, TA, TB, EPI, true>), SD_TILE_ARGS);               \
+    if constexpr (EPI < 3) SD_LAUNCH((gemm_bf16_kernel<BM, NST, TA, TB, EPI, false>), SD_TILE_ARGS);    \
+    break;
+  if (p.kernel == K_P256) {
+    if constexpr (!TA && !TB && (EPI == 0 || EPI == 3)) {
+      if (p.pair) SD_LAUNCH((gemm_p256_kernel<EPI, true>), SD_SHAPE_ARGS, p.tiles_m, p.tiles_n, p.gm, ea);
+      SD_LAUNCH((gemm_p256_kernel<EPI, false>), SD_SHAPE_ARGS, p.tiles_m, p.tiles_n, p.gm, ea);
+    }
+  } else if (p.kernel == K_PSTAG) {
+    if constexpr (EPI == 0 || EPI == 3)
+      SD_LAUNCH((gemm_pstag_kernel<4, TA, TB, EPI>), o.R, SD_SHAPE_ARGS, o.ldr, p.tiles_m, p.tiles_n, p.gm, ea);
+  } else if (p.kernel == K_STAG) {
+    SD_LAUNCH((gemm_stag_kernel<TA, TB, EPI>), SD_TILE_ARGS);
+  } else {
+    switch (p.bm * 16 + p.nst) {
+      SD_BF16_CASE(256, 2) SD_BF16_CASE(256, 3) SD_BF16_CASE(64, 2) SD_BF16_CASE(64, 3)
+      SD_BF16_CASE(64, 4) SD_BF16_CASE(128, 2) SD_BF16_CASE(128, 3) SD_BF16_CASE(128, 4)
+    }
+  }
+  return SD_ERR_UNSUPPORTED;
+#undef SD_BF16_CASE
+#undef SD_TILE_ARGS
+#undef SD_SHAPE_ARGS
+#undef SD_LAUNCH
+}
+
+int launch_plan(const GemmPlan& p, const GemmOperands& o, const EpiArgs& ea, hipStream_t st) {
+  char sym[96];
+  SD_PROF_LABEL("%s", plan_symbol(p, sym));
+#define SD_INST(TA, TB, EPI) case (TA * 2 + TB) * 8 + EPI: return launch_inst<TA, TB, EPI>(p, o, ea, st);
+  switch ((p.ta * 2 + p.tb) * 8 + p.epi) {  // plain / residual / split-K in every layout; 3, 4 only NT; 5, 6 only NN
+    SD_INST(false, false, 0) SD_INST(false, false, 1) SD_INST(false, false, 2) SD_INST(false, false, 3)
+    SD_INST(false, false, 4)
+    SD_INST(false, true, 0) SD_INST(false, true, 1) SD_INST(false, true, 2) SD_INST(false, true, 5) SD_INST(false, true, 6)
+    SD_INST(true, false, 0) SD_INST(true, false, 1) SD_INST(true, false, 2)
+    SD_INST(true, true, 0) SD_INST(true, true, 1) SD_INST(true, true, 2)
+  }
+#undef SD_INST
+  return SD_ERR_UNSUPPORTED;
+}
+
+int check_args(const void* A, const void* B, const void* C, const void* R, int M, int N, int K, int64_t lda, int64_t ldb,
+               int64_t ldc, int64_t ldr, int trans_a, int trans_b) {
+  if (M <= 0 || N <= 0 || K <= 0) return SD_ERR_SHAPE;
+  if ((lda | ldb | ldc | (R ? ldr : 0)) & 7) return SD_ERR_ALIGN;
+  if (((uintptr_t)A | (uintptr_t)B | (uintptr_t)C | (uintptr_t)R) & 15) return SD_ERR_ALIGN;
+  if (N & 7) return SD_ERR_ALIGN;
+  if ((!trans_a || !trans_b) && (K & 7)) return SD_ERR_ALIGN;
+  if (trans_a && (M & 7)) return SD_ERR_ALIGN;
+  return 0;
+}
+
+// CUs of the current device, rounded down to a multiple of 8 (every persistent workgroup stays on its XCD's tile run);
+// 0 = unknown.  Asked on every call: the current device may change between calls.
+int device_cus() {
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    return 0;
+  return cus & ~7;
+}
+
+// reduce: a split-K launch is followed by splitk_reduce_kernel (false: the caller's consumer sums the slabs itself)
+int dispatch(const void* A, const void* B, void* C, const void* R, float* slabs, int splits, bool reduce, int M, int N, int K,
+             long lda, long ldb, long ldc, long ldr, int ta, int tb, hipStream_t st, int epi_kind = 0,
+             const EpiArgs* eap = nullptr) {
+  EpiArgs ea = eap ? *eap : EpiArgs{};
+  const GemmQuery q{M, N, K, lda, ldb, ta != 0, tb != 0, epi_kind, R != nullptr, slabs != nullptr, splits, ea.I,
+                    ea.ssq_in != nullptr, t_sd_shared_gpu != 0, device_cus()};
+  const GemmPlan p = gemm_plan(q, g_sd_debug);
+  SdProfScope prof(ta ? SD_K_GEMM_TN : (tb ? SD_K_GEMM_NN : (p.nst == 9 ? SD_K_GEMM_NT_STAG : SD_K_GEMM_NT)),
+                   2.0 * M * N * K, st);
+  if (p.rc) return p.rc;
+#ifdef SD_STAMPS
+  if (p.kernel == K_PSTAG) ea.cos_t = (const bf16*)g_stamp_buffer;  // diagnostic build: its epilogues do not read cos_t
+#endif
+  const GemmOperands o{(const bf16*)A, (const bf16*)B, (bf16*)C, (const bf16*)R, slabs, M, N, K, lda, ldb, ldc, ldr};
+  if (int e = launch_plan(p, o, ea, st)) return e;
+  if (splits > 1 && reduce) {
+    const long n8 = (long)M * N / 8;
+    const int nb = (int)((n8 + 255) / 256 < 2048 ? (n8 + 255) / 256 : 2048);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(nb), dim3(256), 0, st, slabs, o.C, o.R, M, N, ldc, ldr, splits);
+    SD_CHECK_LAUNCH();
+  }
+  return 0;
 }
 
 }  // namespace
@@ -1738,12 +1775,28 @@ int dispatch(const void* A, const void* B, void* C, const void* R, float* slabs,
 extern "C" int sd_gemm_bf16(const void* A, const void* B, void* C, const void* R, int M, int N, int K, int64_t lda,
                             int64_t ldb, int64_t ldc, int64_t ldr, int trans_a, int trans_b, void* stream) {
   if (int e = check_args(A, B, C, R, M, N, K, lda, ldb, ldc, ldr, trans_a, trans_b)) return e;
-  return dispatch(A, B, C, R, nullptr, 1, M, N, K, lda, ldb, ldc, ldr, trans_a, trans_b, (hipStream_t)stream);
+  return dispatch(A, B, C, R, nullptr, 1, true, M, N, K, lda, ldb, ldc, ldr, trans_a, trans_b, (hipStream_t)stream);
 }
 
 #ifdef SD_STAMPS
 extern "C" void sd_debug_stamp_buffer(void* p) { g_stamp_buffer = p; }
 #endif
+
+// include/sd_hip_debug.h: the plan of a call as text, nothing launched
+extern "C" int sd_debug_gemm_plan(int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int trans_a, int trans_b,
+                                  int epi_kind, int has_residual, int splits, int epi_I, int shared_gpu, int cus, char* buf,
+                                  int cap) {
+  if (M <= 0 || N <= 0 || K <= 0 || epi_kind < 0 || epi_kind > 6 || epi_kind == 1 || epi_kind == 2) return SD_ERR_SHAPE;
+  const GemmQuery q{M, N, K, lda, ldb, trans_a != 0, trans_b != 0, epi_kind, has_residual != 0, splits >= 1,
+                    splits < 1 ? 1 : splits, epi_I, false, shared_gpu != 0, cus & ~7};
+  const GemmPlan p = gemm_plan(q, g_sd_debug);
+  if (p.rc) return p.rc;
+  char sym[96], line[160];
+  const int need =
+      snprintf(line, sizeof line, "%s\t%d\t%d\t%d\t%d", plan_symbol(p, sym), p.grid_x, p.grid_y, p.block, p.gm) + 1;
+  if (buf && cap >= need) memcpy(buf, line, need);  // cap too small: nothing written, as sd_debug_keys
+  return need;
+}
 
 extern "C" int sd_gemm_splitk_plan(int M, int N, int K) {
   // The kernels are bound by the L2 -> LDS rate, i.e. by FLOP per staged byte, i.e. by tile area: a GEMM whose
@@ -1782,7 +1835,7 @@ extern "C" int sd_gemm_bf16_splitk(const void* A, const void* B, void* C, const 
   int s = sd_gemm_splitk_plan(M, N, K);
   if (s > 1 && (workspace == nullptr || workspace_bytes < (int64_t)s * M * N * 4)) s = 1;
   if (s > 1 && ((uintptr_t)workspace & 15)) return SD_ERR_ALIGN;
-  return dispatch(A, B, C, R, (float*)workspace, s, M, N, K, lda, ldb, ldc, ldr, trans_a, trans_b, (hipStream_t)stream);
+  return dispatch(A, B, C, R, (float*)workspace, s, true, M, N, K, lda, ldb, ldc, ldr, trans_a, trans_b, (hipStream_t)stream);
 }
 
 // Split-K GEMM that leaves its `*nsplit_out` fp32 slabs [nsplit][M][N] un-reduced in `workspace` for a consumer that
@@ -1795,11 +1848,8 @@ extern "C" int sd_gemm_bf16_splitk_partial(const void* A, const void* B, void* C
   if (s > 1 && (workspace == nullptr || workspace_bytes < (int64_t)s * M * N * 4)) s = 1;
   if (s > 1 && ((uintptr_t)workspace & 15)) return SD_ERR_ALIGN;
   *nsplit_out = s;
-  g_skip_reduce = true;
-  const int rc = dispatch(A, B, C, nullptr, (float*)workspace, s, M, N, K, lda, ldb, ldc, 0, trans_a, trans_b,
-                          (hipStream_t)stream);
-  g_skip_reduce = false;
-  return rc;
+  return dispatch(A, B, C, nullptr, (float*)workspace, s, false, M, N, K, lda, ldb, ldc, 0, trans_a, trans_b,
+                  (hipStream_t)stream);
 }
 
 // Weight gradients of one layer in one persistent launch: C_p [M_p,N_p] = A_p^T . B_p for p < n <= 4, A_p [K,M_p]
@@ -1825,12 +1875,9 @@ extern "C" int sd_gemm_grouped_tn(const sd_gemm_problem* probs, int n, int K, in
   }
   for (int p = n; p <= 4; ++p) ga.start[p] = start;
   ga.n = n;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-    return SD_ERR_UNSUPPORTED;
-  cus &= ~7;
+  int cus = device_cus();
   if (cus <= 0) return SD_ERR_UNSUPPORTED;
-  if (const int cb = cu_budget(cus, K); cb > 0 && cb < cus) cus = cb;
+  if (const int cb = cu_budget(cus, K, t_sd_shared_gpu != 0, g_sd_debug); cb > 0 && cb < cus) cus = cb;
   SdProfScope prof(SD_K_GEMM_TN, flops, (hipStream_t)stream);
   SD_PROF_LABEL("gemm_pgroup_tn_kernel<%s>", accumulate ? "true" : "false");
   // (sharing the DMA issue with the compute waves, gemm_pstag_kernel's +3 %, was measured 2-4 % SLOWER here -- 73.5-74.6 vs
@@ -1856,7 +1903,7 @@ extern "C" int sd_gemm_swiglu_bwd(const void* dy, const void* wdown, const void*
   ea.I = I;
   ea.g0 = (const bf16*)gate_up;
   // NN: C[M,I] = dy[M,H] . W[H,I]; C itself (d act) is not written: the epilogue needs a non-null C only for alignment checks
-  return dispatch(dy, wdown, dgate_up, nullptr, nullptr, 1, M, I, H, H, I, I, 0, 0, 1, (hipStream_t)stream, 5, &ea);
+  return dispatch(dy, wdown, dgate_up, nullptr, nullptr, 1, false, M, I, H, H, I, I, 0, 0, 1, (hipStream_t)stream, 5, &ea);
 }
 
 // o-projection dX with delta = rowsum(dO * O) per (token, head) in its epilogue (the flash-attention backward's row
@@ -1873,7 +1920,7 @@ extern "C" int sd_gemm_odx_delta(const void* dy, const void* wo, void* d_ao, con
   ea.T = T;
   ea.Hq = Hq;
   const int QD = Hq * 128;
-  return dispatch(dy, wo, d_ao, nullptr, nullptr, 1, M, QD, H, H, QD, QD, 0, 0, 1, (hipStream_t)stream, 6, &ea);
+  return dispatch(dy, wo, d_ao, nullptr, nullptr, 1, false, M, QD, H, H, QD, QD, 0, 0, 1, (hipStream_t)stream, 6, &ea);
 }
 
 // ---- folded RMSNorm (the frozen teacher's inference forward, sd_hip.h SD_SAVE_NONE_FOLDED): the norm's gain lives in the
@@ -1889,7 +1936,7 @@ extern "C" int sd_gemm_bf16_ssq(const void* A, const void* B, void* C, const voi
   EpiArgs ea{};
   ea.ssq_out = ssq_out;
   ea.ssq_n = N / 128;
-  return dispatch(A, B, C, R, nullptr, 1, M, N, K, lda, ldb, ldc, ldr, 0, 0, (hipStream_t)stream, 0, &ea);
+  return dispatch(A, B, C, R, nullptr, 1, false, M, N, K, lda, ldb, ldc, ldr, 0, 0, (hipStream_t)stream, 0, &ea);
 }
 
 // gate|up projection with SwiGLU fused into the epilogue (HF:81-83): act [M,I] = silu(x Wg^T) * (x Wu^T);
@@ -1905,7 +1952,7 @@ static int gemm_swiglu_impl(const void* x, const void* wgu, void* gu_out, void* 
   ea.ld2 = I;
   ea.I = I;
   if (ssq) { ea.ssq_in = ssq; ea.ssq_n = K / 128; ea.inv_h = 1.f / (float)K; ea.eps_rs = eps; }
-  return dispatch(x, wgu, gu_out, nullptr, nullptr, 1, M, 2 * I, K, K, K, 2 * I, 0, 0, 0, (hipStream_t)stream, 3, &ea);
+  return dispatch(x, wgu, gu_out, nullptr, nullptr, 1, false, M, 2 * I, K, K, K, 2 * I, 0, 0, 0, (hipStream_t)stream, 3, &ea);
 }
 extern "C" int sd_gemm_swiglu(const void* x, const void* wgu, void* gu_out, void* act_out, int M, int I, int K,
                               void* stream) {
@@ -1953,5 +2000,5 @@ static int gemm_qkv_rope_impl(const void* x, const void* wqkv, void* qkv_out, vo
   ea.Hkv = Hkv;
   ea.eps = eps;
   const int N = (Hq + 2 * Hkv) * 128;
-  return dispatch(x, wqkv, qkv_out, nullptr, nullptr, 1, M, N, K, K, K, N, 0, 0, 0, (hipStream_t)stream, 4, &ea);
+  return dispatch(x, wqkv, qkv_out, nullptr, nullptr, 1, false, M, N, K, K, K, N, 0, 0, 0, (hipStream_t)stream, 4, &ea);
 }

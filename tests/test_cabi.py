@@ -152,7 +152,7 @@ def test_debug_interface_is_separate_documented_and_complete():
             assert "getenv" not in open(os.path.join(ROOT, "speech_distill_amd", "csrc", f)).read(), f
     dbg = open(os.path.join(ROOT, "include", "sd_hip_debug.h")).read()
     declared = set(re.findall(r"\b(sd_debug_[a-z_]+)\s*\(", re.sub(r"/\*.*?\*/", "", dbg, flags=re.S)))
-    assert declared == set(_lib.DEBUG_PROTOTYPES) == {"sd_debug_set", "sd_debug_get", "sd_debug_keys"}
+    assert declared == set(_lib.DEBUG_PROTOTYPES) == {"sd_debug_set", "sd_debug_get", "sd_debug_keys", "sd_debug_gemm_plan"}
     lib = sda.load_lib()
     n = lib.sd_debug_keys(None, 0)
     buf = ctypes.create_string_buffer(n)

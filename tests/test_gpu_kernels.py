@@ -488,6 +488,64 @@ def test_gemm_split_k(ops):
     assert torch.equal(got, again)
 
 
+# name, (M, N, K), ta, tb, residual, split_k, switches, the kernel gemm_plan() picks for it on 256 CUs.
+# Two cases come from a case list that named the wrong kernel for them (forced 256 x 9 NT at K = 200 as the staggered
+# kernel, K = 96 on the 256 x 256 shape as its unpaired form): with two K-contiguous operands and K % 64 != 0 there is no
+# descriptor staging, so both take gemm_bf16_kernel<256, 3, ..., false>.  They stay, with that expectation, and
+# stag_nn_residual / p256_unpaired reach the two kernels that were meant.
+_FORCE_STAG = {"gemm.force_bm": 256, "gemm.force_nst": 9}
+_P256_SHAPE = (3584, 3328, 64)  # 14 x 26 = 364 tiles of 256 x 128 (> 256 CUs); 14 x 13 = 182 of 256 x 256 (>= 70 % of a round)
+GEMM_PLAN_CASES = [
+    ("bf16_64_nt", (200, 136, 72), False, False, False, False, {}, "gemm_bf16_kernel<64, 4, false, false, 0, false>"),
+    ("bf16_64_nn", (200, 136, 72), False, True, False, False, {}, "gemm_bf16_kernel<64, 3, false, true, 0, true>"),
+    ("bf16_64_tn", (200, 136, 72), True, True, False, False, {}, "gemm_bf16_kernel<64, 3, true, true, 0, true>"),
+    ("bf16_64_ta", (200, 136, 72), True, False, False, False, {}, "gemm_bf16_kernel<64, 3, true, false, 0, true>"),
+    # forced (256, 9) with two K-contiguous operands and K % 64 != 0 has no descriptor staging: the 3-stage ring, pointer form
+    ("forced_stag_nt_residual", (520, 264, 200), False, False, True, False, _FORCE_STAG, "gemm_bf16_kernel<256, 3, false, false, 1, false>"),
+    ("stag_nn_residual", (520, 264, 200), False, True, True, False, _FORCE_STAG, "gemm_stag_kernel<false, true, 1>"),
+    ("pstag", _P256_SHAPE, False, False, False, False, {"gemm.no_p256": 1}, "gemm_pstag_kernel<4, false, false, 0>"),
+    ("p256_paired", _P256_SHAPE, False, False, False, False, {"gemm.p256_min_tiles": 150}, "gemm_p256_kernel<0, true>"),
+    ("p256_unpaired", _P256_SHAPE, False, False, False, False, {"gemm.p256_min_tiles": 150, "gemm.p256_unpaired": 1},
+     "gemm_p256_kernel<0, false>"),
+    # K = 96 on the same shape: K % 64 != 0 again, so neither staggered nor 256 x 256 (whose unpaired form only the switch reaches)
+    ("p256_shape_k96", (3584, 3328, 96), False, False, False, False, {"gemm.p256_min_tiles": 150},
+     "gemm_bf16_kernel<256, 3, false, false, 0, false>"),
+    ("split_k", (256, 1024, 6144), False, True, False, True, {}, "gemm_stag_kernel<false, true, 2>"),
+]
+
+
+def test_gemm_launches_what_gemm_plan_says(ops):
+    """`_lib.gemm_plan` (sd_debug_gemm_plan: the dispatch's own gemm_plan(), nothing launched) names the kernel that the same
+    call then launches, for the smallest case of every kernel family, and that launch is exact on integer data (fp64
+    reference rounded to bf16; |sum| <= 9 * 6144 is exact in fp32, also through the split-K slabs and their reduce)."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    g = torch.Generator().manual_seed(12)
+    data = {}
+    try:
+        for name, (M, N, K), ta, tb, res, sk, switches, kernel in GEMM_PLAN_CASES:
+            _lib.debug_set("reset", 0)
+            for k, v in switches.items():
+                _lib.debug_set(k, v)
+            if (M, N, K, ta, tb, res) not in data:
+                a = torch.randint(-3, 4, (K, M) if ta else (M, K), generator=g).float()
+                b = torch.randint(-3, 4, (K, N) if tb else (N, K), generator=g).float()
+                r = torch.randint(-3, 4, (M, N), generator=g).float() if res else None
+                data[(M, N, K, ta, tb, res)] = (to_dev(bf(a)), to_dev(bf(b)), None if r is None else to_dev(bf(r)),
+                                                _gemm_ref(a, b, ta, tb, r).float().bfloat16().float())
+            a, b, r, ref = data[(M, N, K, ta, tb, res)]
+            want = _lib.gemm_plan(M, N, K, ta, tb, residual=res, split_k=sk, cus=cus)
+            ops.prof_begin()
+            got = ops.gemm(a, b, ta, tb, residual=r, split_k=sk)
+            ops.prof_end()
+            assert [s for s in ops.prof_symbols() if s.startswith("gemm_")] == [want["symbol"]], name
+            if cus == 256:
+                assert want["symbol"] == kernel, name
+            assert torch.equal(got.float().cpu(), ref), name
+    finally:
+        _lib.debug_set("reset", 0)
+        _lib.debug_set("gemm.p256_min_tiles", 150)  # the module fixture's setting
+
+
 def test_gemm_accumulate_in_place(ops):
     g = torch.Generator().manual_seed(5)
     a, b = bf(torch.randn(160, 256, generator=g)), bf(torch.randn(160, 136, generator=g))
