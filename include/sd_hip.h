@@ -504,6 +504,28 @@ int64_t sd_attn_decode_workspace_bytes(int B, int Hq, int cap);
 int sd_attn_decode(const void* q, const void* k_plane, const void* v_plane, void* o, float* lse, const int32_t* len,
                    int len_add, void* workspace, int64_t workspace_bytes, int B, int cap, int max_len, int Hq, int Hkv,
                    int head_dim, float scale, void* stream);
+/* sd_kvcache_store at an offset (the sink of a block of T new tokens behind a live cache, soulxpodcast.py:378-380): row
+ * (b, t) with t < new_len[b] goes to slot past[b] + t; writes nothing else.  past, new_len int32 [B] (device), clamped
+ * before any address is formed: past to [0, cap], new_len to [0, min(T, cap - past)]. */
+int sd_kvcache_store_at(const void* qk, const void* qkv, void* k_plane, void* v_plane, const int32_t* past,
+                        const int32_t* new_len, int B, int T, int cap, int Hq, int Hkv, void* stream);
+/* causal attention of a block of T new query rows per sequence, at positions past[b] + t, over the keys already in the
+ * cache plus the block itself (HF:185-207 with past_key_values; what a turn of soulxpodcast.py:378-380, a chunk of a
+ * chunked prefill or a speculative verify step runs).  q, o [B*T, ld] bf16, head hq at column hq*128; k_plane, v_plane
+ * one layer's planes [B][cap][Hkv*128], which already hold the block's own K / V at slots past[b] .. past[b] +
+ * new_len[b] - 1 (sd_kvcache_store_at runs first); lse fp32 [B,Hq,T], natural log, nullable; past, new_len int32 [B]
+ * (device), clamped as in sd_kvcache_store_at.  Row (b,t) sees keys [0, min(past[b] + t + 1, past[b] + new_len[b])); rows
+ * t >= new_len[b] are padding, computed over that capped key set and stored like any other (as sd_attn_fwd does for rows
+ * >= kv_len); a row with no visible key is zeros with lse = -inf.  Every head column of all B*T rows of o is stored,
+ * nothing else is written; slots >= past[b] + new_len[b] are never read and may hold anything finite.
+ * The bits of o[b,t,h,:] and lse[b,h,t] depend on that row's query, its position past[b] + t and the visible K / V rows
+ * only: not on how the sequence was split into past and block, nor on T, B, cap, the other rows or the grid (key tiles
+ * are anchored at cache slot 0, every row's online softmax is private to it, a masked key has probability exactly 0 and
+ * stays out of the row maximum; no atomics, no split over keys).  head_dim 128 and Hq / Hkv in {1, 2, 4}; anything else
+ * that is sane is SD_ERR_UNSUPPORTED, a NULL pointer (lse apart), T <= 0 or cap <= 0 SD_ERR_SHAPE, both before any launch. */
+int sd_attn_extend(const void* q, const void* k_plane, const void* v_plane, void* o, float* lse, const int32_t* past,
+                   const int32_t* new_len, int64_t ldq, int64_t ldo, int B, int T, int cap, int Hq, int Hkv, int head_dim,
+                   float scale, void* stream);
 /* one sampling step for B rows (sampler.py:136-189; HF logits_process.py in generate's order):
  *   1 repetition penalty over the row's GENERATED tokens seq[b, prompt_len[b] .. len[b]) only, each distinct token once:
  *     score < 0 ? score * p : score / p;   2 EOS = -inf while fewer than min_new_tokens were generated;   3 / temperature;
@@ -546,12 +568,25 @@ int sd_sample_step(const void* logits, int64_t row_stride, const float* uniforms
  *   logits depends on row b's token, position and cache only (not on B or the other rows).  When any GEMV of the step
  *   would refuse its shape (B > 16, hidden > 4096, ...) the WHOLE step runs the unflagged sequence, so a step's arithmetic
  *   is one of two kinds, never a mixture.  An unknown flag bit is SD_ERR_SHAPE before any launch.
- * Both entries return SD_ERR_SHAPE for a NULL d or p. */
+ * sd_qwen3_extend (soulxpodcast.py:342,378-380: ONE DynamicCache handed to llm.generate for every turn, each turn feeding
+ *   only the tokens the cache has not seen; llm_engine.py:91 enable_prefix_caching): the SD_SAVE_NONE forward over a block
+ *   of T right-padded NEW tokens per row, ids int64 [B*T], behind past[b] cached positions.  Token (b,t) takes position
+ *   past[b] + t (cos/sin [cap,128]; the rows are gathered on the device, positions clamped to cap - 1; q and K are
+ *   bit-identical to sd_qknorm_rope_fwd at that position), sd_kvcache_store_at follows each layer's q|k|v step and
+ *   sd_attn_extend stands where sd_attn_fwd does.  The lm_head runs on row b*T + clamp(new_len[b], 1, T) - 1: logits bf16
+ *   [B,V].  past, new_len int32 [B] (device), clamped as in sd_attn_extend; acts of sd_qwen3_extend_acts_bytes(d, B, T);
+ *   T <= cap.  Argument checks as sd_qwen3_prefill (SD_ERR_SHAPE, SD_ERR_WORKSPACE, SD_ERR_UNSUPPORTED; Hq / Hkv outside
+ *   {1, 2, 4} is SD_ERR_UNSUPPORTED), all before the first launch.
+ * The three step / extend entries return SD_ERR_SHAPE for a NULL d or p. */
 #define SD_DECODE_SKINNY 1
 int64_t sd_qwen3_prefill_acts_bytes(const sd_qwen3_dims* d, int B, int T);
 int sd_qwen3_prefill(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* kv_len,
                      const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes, void* cache,
                      int64_t cache_bytes, int cap, void* logits, int B, int T, void* stream);
+int64_t sd_qwen3_extend_acts_bytes(const sd_qwen3_dims* d, int B, int T);
+int sd_qwen3_extend(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* past,
+                    const int32_t* new_len, const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes,
+                    void* cache, int64_t cache_bytes, int cap, void* logits, int B, int T, void* stream);
 int64_t sd_qwen3_decode_acts_bytes(const sd_qwen3_dims* d, int B, int cap);
 int sd_qwen3_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* pos,
                          int max_len, const void* cos_tab, const void* sin_tab, void* cache, int64_t cache_bytes, int cap,

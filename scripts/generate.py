@@ -8,8 +8,12 @@ penalty 1.25, min 8 / max 3000 new tokens, stop token 151675, repetition-aware s
 
     python scripts/generate.py /out/checkpoint-1000 prompts.jsonl --output generated.jsonl
 
-``prompts.jsonl``: one JSON object per line with ``input_ids`` (a list of token ids), or a bare list.  The output holds,
-per prompt, ``{"index", "prompt_len", "generated_ids"}`` with the ids up to and including the stop token.
+``prompts.jsonl``: one JSON object per line with ``input_ids`` (a list of token ids), or a bare list.  An object may carry
+``"turns": [[ids], [ids], ...]`` instead: a dialogue whose turns are generated one after the other over ONE live KV cache
+(``model.start_session``; the reference's dialogue loop, soulxpodcast/models/soulxpodcast.py:339-386) -- turn n feeds only
+its own text behind the history the cache already holds.  The dialogues of a batch take their turns together, so prompts
+are batched by turn count.  The output holds, per prompt and turn, ``{"index", "turn", "prompt_len", "generated_ids"}``
+with the ids up to and including the stop token.
 """
 import argparse
 import json
@@ -48,6 +52,7 @@ def parse_args(argv=None):
 
 
 def read_prompts(path):
+    """One dialogue per line, as a list of turns (each a non-empty list of token ids); a plain prompt is one turn."""
     out = []
     with open(path) as f:
         for line in f:
@@ -55,47 +60,77 @@ def read_prompts(path):
             if not line:
                 continue
             row = json.loads(line)
-            ids = row["input_ids"] if isinstance(row, dict) else row
-            if not ids:
+            if isinstance(row, dict) and "turns" in row:
+                turns = row["turns"]
+                if not turns:
+                    raise ValueError(f"{path}: a dialogue without turns")
+            else:
+                turns = [row["input_ids"] if isinstance(row, dict) else row]
+            if any(not ids for ids in turns):
                 raise ValueError(f"{path}: an empty prompt")
-            out.append([int(t) for t in ids])
+            out.append([[int(t) for t in ids] for ids in turns])
     return out
+
+
+def batches_by_turn_count(dialogues, batch_size):
+    """[(indices, dialogues)] with at most ``batch_size`` dialogues of EQUAL turn count each (a dialogue with fewer turns
+    would sit the later ones out), in order of first appearance."""
+    groups = {}
+    for i, d in enumerate(dialogues):
+        groups.setdefault(len(d), []).append(i)
+    out = []
+    for idx in groups.values():
+        for s in range(0, len(idx), batch_size):
+            part = idx[s:s + batch_size]
+            out.append((part, [dialogues[i] for i in part]))
+    return out
+
+
+def right_pad(rows, pad):
+    T = max(len(r) for r in rows)
+    ids = torch.full((len(rows), T), pad, dtype=torch.int64)
+    mask = torch.zeros(len(rows), T, dtype=torch.int64)
+    for i, r in enumerate(rows):
+        ids[i, :len(r)] = torch.tensor(r)
+        mask[i, :len(r)] = 1
+    return ids, mask
 
 
 def main(argv=None):
     args = parse_args(argv)
     import speech_distill_amd as sda
+    from speech_distill_amd.generation import cache_capacity
     model = sda.HipQwen3ForCausalLM.from_pretrained(args.checkpoint, device="cuda").eval()
-    prompts = read_prompts(args.prompts)
+    dialogues = read_prompts(args.prompts)
     pad = args.pad_token_id if args.pad_token_id is not None else args.stop_token_id
     dev = model.flat.device
     n_new, elapsed = 0, 0.0
     with open(args.output, "w") as out:
-        for s in range(0, len(prompts), args.batch_size):
-            chunk = prompts[s:s + args.batch_size]
-            T = max(len(p) for p in chunk)
-            ids = torch.full((len(chunk), T), pad, dtype=torch.int64)
-            mask = torch.zeros(len(chunk), T, dtype=torch.int64)
-            for i, p in enumerate(chunk):   # right padding
-                ids[i, :len(p)] = torch.tensor(p)
-                mask[i, :len(p)] = 1
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            res = model.generate(ids.to(dev), attention_mask=mask.to(dev), max_new_tokens=args.max_tokens,
-                                 min_new_tokens=args.min_tokens, do_sample=not args.greedy, temperature=args.temperature,
-                                 top_k=args.top_k, top_p=args.top_p, repetition_penalty=args.repetition_penalty,
-                                 eos_token_id=args.stop_token_id, pad_token_id=pad, use_ras=not args.no_ras,
-                                 win_size=args.win_size, tau_r=args.tau_r, seed=args.seed, sync_every=args.sync_every,
-                                 decode_kernels=args.decode_kernels)
-            torch.cuda.synchronize()
-            elapsed += time.perf_counter() - t0
-            new = res[:, T:].cpu().tolist()
-            for i, row in enumerate(new):
-                if args.stop_token_id in row:
-                    row = row[:row.index(args.stop_token_id) + 1]
-                n_new += len(row)
-                out.write(json.dumps({"index": s + i, "prompt_len": len(chunk[i]), "generated_ids": row}) + "\n")
-    print(f"{len(prompts)} prompts, {n_new} new tokens in {elapsed:.2f} s: {n_new / max(elapsed, 1e-9):.1f} tokens/s "
+        for index, chunk in batches_by_turn_count(dialogues, args.batch_size):
+            n_turns = len(chunk[0])
+            need = max(sum(len(t) for t in d) for d in chunk) + n_turns * args.max_tokens
+            if need > cache_capacity(model):
+                raise ValueError(f"a dialogue of {need} positions exceeds the KV-cache capacity {cache_capacity(model)}")
+            sess = model.start_session(len(chunk), (need + 255) // 256 * 256, decode_kernels=args.decode_kernels)
+            for turn in range(n_turns):
+                ids, mask = right_pad([d[turn] for d in chunk], pad)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                res = sess.generate(ids.to(dev), attention_mask=mask.to(dev), max_new_tokens=args.max_tokens,
+                                    min_new_tokens=args.min_tokens, do_sample=not args.greedy,
+                                    temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
+                                    repetition_penalty=args.repetition_penalty, eos_token_id=args.stop_token_id,
+                                    pad_token_id=pad, use_ras=not args.no_ras, win_size=args.win_size, tau_r=args.tau_r,
+                                    seed=None if args.seed is None else args.seed + turn, sync_every=args.sync_every)
+                torch.cuda.synchronize()
+                elapsed += time.perf_counter() - t0
+                for i, row in enumerate(res.cpu().tolist()):
+                    if args.stop_token_id in row:
+                        row = row[:row.index(args.stop_token_id) + 1]
+                    n_new += len(row)
+                    out.write(json.dumps({"index": index[i], "turn": turn, "prompt_len": len(chunk[i][turn]),
+                                          "generated_ids": row}) + "\n")
+    print(f"{len(dialogues)} prompts, {n_new} new tokens in {elapsed:.2f} s: {n_new / max(elapsed, 1e-9):.1f} tokens/s "
           f"-> {args.output}")
 
 

@@ -185,6 +185,8 @@ PROTOTYPES = {
     "sd_qwen3_forward_mx": (_i, [C.POINTER(Dims), C.POINTER(ParamsMx), C.POINTER(Batch), _vp, _i64, _vp, _i, _vp]),
     "sd_kvcache_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
     "sd_kvcache_store": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "sd_kvcache_store_at": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "sd_attn_extend": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _i, _f, _vp]),
     "sd_last_rows": (_i, [_vp, _vp, _i, _i, _vp]),
     "sd_qknorm_rope_append": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     "sd_attn_decode_workspace_bytes": (_i64, [_i, _i, _i]),
@@ -195,6 +197,9 @@ PROTOTYPES = {
     "sd_qwen3_prefill_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
     "sd_qwen3_prefill": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i, _vp, _i, _i,
                               _vp]),
+    "sd_qwen3_extend_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
+    "sd_qwen3_extend": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i, _vp, _i,
+                             _i, _vp]),
     "sd_qwen3_decode_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
     "sd_qwen3_decode_step": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _i, _vp, _vp, _vp, _i64, _i, _vp, _i64, _vp,
                                   _i, _vp]),

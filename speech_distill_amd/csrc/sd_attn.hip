@@ -1228,3 +1228,171 @@ extern "C" int sd_attn_bwd_varlen(const void* q, const void* k, const void* v, c
   }
   return 0;
 }
+
+// ------------------------------------------------------------------------------------------ extend
+// Causal attention of a block of T new query rows per sequence, at positions past[b] + t, over a live KV cache: the keys
+// already cached plus the block's own (stored into the planes before this call).  The decomposition of attn_fwd_kernel
+// (S^T = K Q^T, a lane owns one query row, O^T = V^T P^T, one swizzled LDS image, LDS-DMA), arranged for the cache:
+//   grid (ceil(T/64), Hkv, B), 128 G threads (G = Hq / Hkv).  A workgroup owns one 64-row query tile of one sequence and
+//   ALL G query heads of one kv head: wave w serves head hkv*G + (w >> 1), rows 32 (w & 1) .. + 31 of the tile, and every
+//   wave takes all 64 keys of a K/V tile, so a tile is staged once for the whole group (two stages of (K,V), 64 KiB).
+//   K/V tiles come from the cache plane (row stride Hkv*128) and are ANCHORED AT CACHE SLOT 0: tile i is slots 64 i ..
+//   64 i + 63 whatever past is, and the loop stops at the tile of the workgroup's last visible key.
+// Bit contract (tests/test_gpu_attn_extend.py): o and lse of a row depend on its query, its position and the visible
+// K / V rows only.  A row's running (m, l, O) live in its own lane pair; the online softmax steps over the same absolute
+// tiles however the sequence was split into past and block; a masked key gets the score -1e30 BEFORE the row maximum and
+// therefore probability exactly 0 (exp2 underflows; key 0 is visible to every row that sees anything, so the maximum is
+// a real score from the first tile on); a tile that lies wholly above a row's diagonal changes nothing for that row
+// (alpha = 1, p = 0), which is why a wave may skip it or compute it.  No atomics, no split over keys.
+// Slots >= past + new_len are outside the buffer descriptor of the stream: they read as zeros and are masked.
+namespace {
+template <int G>
+__global__ __launch_bounds__(128 * G) void attn_extend_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ Kp,
+                                                              const bf16* __restrict__ Vp, bf16* __restrict__ O,
+                                                              float* __restrict__ LSE, const int* __restrict__ past_p,
+                                                              const int* __restrict__ new_p, long ldq, long ldo, int T,
+                                                              int cap, int Hq, int Hkv, float scale) {
+  constexpr int NW = 2 * G;    // waves
+  constexpr int NP = 16 / NW;  // 1 KiB pieces of a tile each wave stages
+  __shared__ __attribute__((aligned(16))) char smem[4 * TILE];  // 2 stages x (K,V); then a store image per wave
+  const int lane = lane_id(), w = wave_id_uniform();
+  const int qt = blockIdx.x, hkv = blockIdx.y, b = blockIdx.z;
+  // clamped before any address is formed
+  const int past = min(max(past_p[b], 0), cap);
+  const int nnew = min(max(new_p[b], 0), min(T, cap - past));
+  const int kv_end = past + nnew;  // <= cap: keys [0, kv_end) exist
+  const int hq = hkv * G + (w >> 1);
+  const int t0w = qt * 64 + 32 * (w & 1);  // first block row of this wave
+  const int r = lane & 31, h = lane >> 5;
+  const int t = t0w + r;  // this lane's row of the block
+  const int tc = t < T ? t : T - 1;
+  bf16* orow = O + ((long)b * T + t0w) * ldo + hq * D;
+  float* lrow = LSE ? LSE + ((long)b * Hq + hq) * T : nullptr;
+  char* img = smem + w * 8192;
+
+  f32x16 o[4];
+#pragma unroll
+  for (int db = 0; db < 4; ++db)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) o[db][e] = 0.f;
+  if (kv_end == 0) {  // workgroup-uniform: no row of this sequence sees a key
+    store_tile_rows(img, o, 0.f, orow, ldo, T - t0w, lane);
+    if (lrow && t < T && h == 0) lrow[t] = -INFINITY;
+    return;
+  }
+  const int kv_hi = min(past + qt * 64 + 64, kv_end);  // one past the last key any row of the tile sees
+  const int nkv = (kv_hi + 63) >> 6;
+  const int wave_hi = min(past + t0w + 32, kv_end);    // the same for this wave's 32 rows
+  const int lim = min(past + t, kv_end - 1);           // keys > lim are masked for this row (lim >= 0)
+  const int KD = Hkv * D;
+  TileDma<NP> kd, vd;
+  kd.init(Kp + (long)b * cap * KD + hkv * D, KD, kv_end, w, lane);
+  vd.init(Vp + (long)b * cap * KD + hkv * D, KD, kv_end, w, lane);
+  kd.issue(0, smem, w);
+  vd.issue(0, smem + TILE, w);
+  bf16x8 qf[8];
+  {
+    const bf16* qp = Q + ((long)b * T + tc) * ldq + hq * D + 8 * h;
+#pragma unroll
+    for (int st = 0; st < 8; ++st) qf[st] = *(const bf16x8*)(qp + 16 * st);
+  }
+  float m = NEG, l = 0.f;
+  const float c = scale * LOG2E;
+
+  auto tile = [&](int i, int stage) {
+    const char* ks = smem + stage * 2 * TILE;
+    const char* vs = ks + TILE;
+    f32x16 s[2];
+#pragma unroll
+    for (int kh = 0; kh < 2; ++kh) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) s[kh][e] = 0.f;
+#pragma unroll
+      for (int st = 0; st < 8; ++st) s[kh] = mfma32(row_frag(ks, 32 * kh, st, lane), qf[st], s[kh]);
+    }
+    const int k0 = i * 64;
+    // wave-uniform: the tile touches a diagonal of mine or the end of the keys (computed from ABSOLUTE positions: the
+    // diagonal falls mid-tile whenever past % 64 != 0)
+    const bool need_mask = __builtin_amdgcn_readfirstlane((int)((k0 + 63 > past + t0w) || (k0 + 63 >= kv_end))) != 0;
+    if (need_mask) {
+#pragma unroll
+      for (int kh = 0; kh < 2; ++kh)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) s[kh][e] = (k0 + 32 * kh + acc_row(e, h)) > lim ? NEG : s[kh][e];
+    }
+    float mx = fmaxf(s[0][0], s[1][0]);
+#pragma unroll
+    for (int e = 1; e < 16; ++e) mx = fmaxf(fmaxf(mx, s[0][e]), s[1][e]);
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float mn = fmaxf(m, mx);
+    const float alpha = __builtin_amdgcn_exp2f((m - mn) * c);
+    m = mn;
+    const float mnc = -mn * c;
+    float rs = 0.f;
+#pragma unroll
+    for (int kh = 0; kh < 2; ++kh)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kh][e], c, mnc));
+        s[kh][e] = p;
+        rs += p;
+      }
+    l = l * alpha + rs;
+    if (__any(alpha != 1.f)) {
+#pragma unroll
+      for (int db = 0; db < 4; ++db)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) o[db][e] *= alpha;
+    }
+#pragma unroll
+    for (int ss = 0; ss < 4; ++ss) {  // 16 keys per step
+      bf16x8 vt[4];
+      tr_frag4(vs, 16 * ss, lane, vt);
+      const bf16x8 pf = acc_frag(s[ss >> 1], ss & 1);
+#pragma unroll
+      for (int db = 0; db < 4; ++db) o[db] = mfma32(vt[db], pf, o[db]);
+    }
+  };
+  for (int i = 0; i < nkv; ++i) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // my share of tile i (and, the first time, my Q rows)
+    __builtin_amdgcn_s_barrier();  // everybody's share of tile i has landed; everybody is done reading tile i-1
+    asm volatile("" ::: "memory");
+    if (i + 1 < nkv) {
+      char* nx = smem + ((i + 1) & 1) * 2 * TILE;
+      kd.issue((i + 1) * 64, nx, w);
+      vd.issue((i + 1) * 64, nx + TILE, w);
+    }
+    if (i * 64 < wave_hi) tile(i, i & 1);  // wave-uniform
+  }
+  __syncthreads();  // nothing is in flight (the last iteration issued nothing); the ring becomes the store images
+  l += __shfl_xor(l, 32, 64);
+  store_tile_rows(img, o, 1.f / l, orow, ldo, T - t0w, lane);
+  if (lrow && t < T && h == 0) lrow[t] = m * scale + __logf(l);
+}
+}  // namespace
+
+extern "C" int sd_attn_extend(const void* q, const void* k_plane, const void* v_plane, void* o, float* lse,
+                              const int32_t* past, const int32_t* new_len, int64_t ldq, int64_t ldo, int B, int T, int cap,
+                              int Hq, int Hkv, int head_dim, float scale, void* stream) {
+  if (!q || !k_plane || !v_plane || !o || !past || !new_len) return SD_ERR_SHAPE;
+  if (B <= 0 || T <= 0 || cap <= 0 || Hq <= 0 || Hkv <= 0 || (Hq % Hkv) || head_dim <= 0) return SD_ERR_SHAPE;
+  if (head_dim != D) return SD_ERR_UNSUPPORTED;
+  const int G = Hq / Hkv;
+  if (G != 1 && G != 2 && G != 4) return SD_ERR_UNSUPPORTED;
+  if (ldq < (int64_t)Hq * D || ldo < (int64_t)Hq * D) return SD_ERR_SHAPE;
+  if ((ldq | ldo) & 7) return SD_ERR_ALIGN;
+  if (((uintptr_t)q | (uintptr_t)k_plane | (uintptr_t)v_plane | (uintptr_t)o) & 15) return SD_ERR_ALIGN;
+  // a cache row of one sequence is addressed with 32-bit byte offsets; the grid's y and z are 16-bit
+  if ((int64_t)cap * Hkv * D * 2 >= ((int64_t)1 << 31) || T > (1 << 30) || B > 65535 || Hkv > 65535) return SD_ERR_UNSUPPORTED;
+  SdProfScope prof(SD_K_ATTN_FWD, 4.0 * B * Hq * (double)T * cap * D, (hipStream_t)stream);  // upper bound: every key
+  SD_PROF_LABEL("attn_extend_kernel<%d>", G);
+  const dim3 grid((T + 63) / 64, Hkv, B);
+#define SD_EXT_GO(G_)                                                                                                \
+  hipLaunchKernelGGL((attn_extend_kernel<G_>), grid, dim3(128 * G_), 0, (hipStream_t)stream, (const bf16*)q,         \
+                     (const bf16*)k_plane, (const bf16*)v_plane, (bf16*)o, lse, past, new_len, (long)ldq, (long)ldo, T, \
+                     cap, Hq, Hkv, scale)
+  if (G == 1) SD_EXT_GO(1); else if (G == 2) SD_EXT_GO(2); else SD_EXT_GO(4);
+#undef SD_EXT_GO
+  SD_CHECK_LAUNCH();
+  return 0;
+}

@@ -17,6 +17,7 @@
 #include "sd_common.cuh"
 #include "../../include/sd_hip.h"
 #include "sd_prof.h"
+#include "sd_runner.h"
 
 #define ST ((hipStream_t)stream)
 
@@ -65,6 +66,49 @@ __global__ __launch_bounds__(256) void kvcache_store_kernel(const bf16* __restri
   const long dst = ((long)b * cap + t) * (Hkv * 128) + c * 8;
   if (which == 0) *(bf16x8*)(kp + dst) = *(const bf16x8*)(qk + (long)m * (Hq + Hkv) * 128 + Hq * 128 + c * 8);
   else *(bf16x8*)(vp + dst) = *(const bf16x8*)(qkv + (long)m * (Hq + 2 * Hkv) * 128 + (Hq + Hkv) * 128 + c * 8);
+}
+
+// The same sink at an offset (a block of T new tokens behind past[b] cached ones): row t < new_len[b] goes to slot
+// past[b] + t, nothing else is written.  past is clamped to [0, cap], new_len to [0, min(T, cap - past)] first.
+__global__ __launch_bounds__(256) void kvcache_store_at_kernel(const bf16* __restrict__ qk, const bf16* __restrict__ qkv,
+                                                               bf16* __restrict__ kp, bf16* __restrict__ vp,
+                                                               const int32_t* __restrict__ past,
+                                                               const int32_t* __restrict__ new_len, int B, int T, int cap,
+                                                               int Hq, int Hkv) {
+  const int cpr = Hkv * 16;  // 16-byte chunks per row
+  const long total = 2l * B * T * cpr;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int c = (int)(idx % cpr);
+  const long r = idx / cpr;
+  const int which = (int)(r / ((long)B * T));  // 0 = K, 1 = V
+  const int m = (int)(r % ((long)B * T));
+  const int b = m / T, t = m % T;
+  const int p0 = clampi(past[b], 0, cap);
+  const int room = cap - p0;
+  const int n = clampi(new_len[b], 0, T < room ? T : room);
+  if (t >= n) return;
+  const long dst = ((long)b * cap + p0 + t) * (Hkv * 128) + c * 8;
+  if (which == 0) *(bf16x8*)(kp + dst) = *(const bf16x8*)(qk + (long)m * (Hq + Hkv) * 128 + Hq * 128 + c * 8);
+  else *(bf16x8*)(vp + dst) = *(const bf16x8*)(qkv + (long)m * (Hq + 2 * Hkv) * 128 + (Hq + Hkv) * 128 + c * 8);
+}
+
+// cos / sin rows of the positions past[b] + t (clamped to [0, cap - 1]) of a block of T tokens per sequence, gathered
+// into [B*T, 128] tables: the q/k-norm + RoPE step then takes row m of them for token m.  One thread per 16 bytes.
+__global__ __launch_bounds__(256) void rope_rows_at_kernel(const bf16* __restrict__ cosb, const bf16* __restrict__ sinb,
+                                                           const int32_t* __restrict__ past, bf16* __restrict__ cos_out,
+                                                           bf16* __restrict__ sin_out, int B, int T, int cap) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= 2l * B * T * 16) return;
+  const int c = (int)(idx & 15);
+  const long r = idx >> 4;
+  const int which = (int)(r / ((long)B * T));
+  const int m = (int)(r % ((long)B * T));
+  const int b = m / T, t = m % T;
+  const long p = (long)clampi(past[b], 0, cap) + t;
+  const long pos = p < cap - 1 ? p : cap - 1;
+  if (which == 0) *(bf16x8*)(cos_out + (long)m * 128 + c * 8) = *(const bf16x8*)(cosb + pos * 128 + c * 8);
+  else *(bf16x8*)(sin_out + (long)m * 128 + c * 8) = *(const bf16x8*)(sinb + pos * 128 + c * 8);
 }
 
 // last valid row of every sequence: rows[b] = b*T + clamp(kv_len[b], 1, T) - 1 (the clamp of sd_attn_fwd)
@@ -502,6 +546,32 @@ extern "C" int sd_kvcache_store(const void* qk, const void* qkv, void* k_plane, 
   SD_PROF_LABEL("kvcache_store_kernel");
   hipLaunchKernelGGL(kvcache_store_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ST, (const bf16*)qk,
                      (const bf16*)qkv, (bf16*)k_plane, (bf16*)v_plane, kv_len, B, T, cap, Hq, Hkv);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sd_kvcache_store_at(const void* qk, const void* qkv, void* k_plane, void* v_plane, const int32_t* past,
+                                   const int32_t* new_len, int B, int T, int cap, int Hq, int Hkv, void* stream) {
+  if (B <= 0 || T <= 0 || cap <= 0 || Hq <= 0 || Hkv <= 0 || !qk || !qkv || !k_plane || !v_plane || !past || !new_len)
+    return SD_ERR_SHAPE;
+  const long total = 2l * B * T * Hkv * 16;
+  SdProfScope prof(SD_K_MISC, 2.0 * total * 16, ST);
+  SD_PROF_LABEL("kvcache_store_at_kernel");
+  hipLaunchKernelGGL(kvcache_store_at_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ST, (const bf16*)qk,
+                     (const bf16*)qkv, (bf16*)k_plane, (bf16*)v_plane, past, new_len, B, T, cap, Hq, Hkv);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+// internal (sd_runner.h): the gathered RoPE tables of sd_qwen3_extend
+int sd_rope_rows_at(const void* cos_tab, const void* sin_tab, const int32_t* past, void* cos_out, void* sin_out, int B,
+                    int T, int cap, void* stream) {
+  if (B <= 0 || T <= 0 || cap <= 0 || !cos_tab || !sin_tab || !past || !cos_out || !sin_out) return SD_ERR_SHAPE;
+  const long total = 2l * B * T * 16;
+  SdProfScope prof(SD_K_MISC, 2.0 * total * 16, ST);
+  SD_PROF_LABEL("rope_rows_at_kernel");
+  hipLaunchKernelGGL(rope_rows_at_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ST, (const bf16*)cos_tab,
+                     (const bf16*)sin_tab, past, (bf16*)cos_out, (bf16*)sin_out, B, T, cap);
   SD_CHECK_LAUNCH();
   return 0;
 }

@@ -101,6 +101,8 @@ LayerActs layer_acts(const Sizes& s, char* base, int l, int save) {
 struct KvSink {
   char* cache;
   int cap;
+  // sd_qwen3_extend: the block's rows go behind past[b] cached ones and attend over the cache (nullptr: a prefill)
+  const int32_t *past = nullptr, *new_len = nullptr;
   char* plane(const Sizes& s, int B, int l, int which) const {
     return cache + ((int64_t)l * 2 + which) * B * cap * s.KD * 2;
   }
@@ -109,24 +111,35 @@ struct KvSink {
 // One decoder layer (HF modeling_qwen3.py:227-250): a.x_in -> x_out, every intermediate into `a`.  x_out == nullptr
 // stops after the SwiGLU (the backward's recompute does not need the layer output again); keep_gu: gate|up is kept
 // for the backward.  sink (sd_qwen3_prefill): the layer's K / V rows below kv_len also go to planes l of the cache.
+// sink->past (sd_qwen3_extend): bt's cos/sin tables hold one row per TOKEN (sd_rope_rows_at), the K / V rows t <
+// new_len[b] go to slots past[b] + t and the attention is sd_attn_extend over the planes.
 int layer_forward(const sd_qwen3_dims* d, const Sizes& s, const LayerActs& a, const sd_qwen3_layer& w, char* x_out,
                   bool keep_gu, const sd_qwen3_batch& bt, void* stream, const KvSink* sink = nullptr, int l = 0) {
   const int B = bt.B, T = bt.T;
   const void *cos_tab = bt.cos_tab, *sin_tab = bt.sin_tab;
+  const bool extend = sink && sink->past;
+  const int Trope = extend ? s.M : T;  // per-token tables: row m of them belongs to token m
   RUN(sd_rmsnorm_fwd(a.x_in, w.ln1, a.xn1, (float*)a.rstd1, s.M, s.h, d->eps, stream));
   // q|k|v projection with q/k-norm + RoPE in the GEMM epilogue (one head = one 128-column tile)
-  int rc = sd_gemm_qkv_rope(a.xn1, w.wqkv, a.qkv, a.qk, w.q_gain, w.k_gain, cos_tab, sin_tab, s.M, T, s.Hq, s.Hkv, s.h,
-                            d->eps, stream);
+  int rc = sd_gemm_qkv_rope(a.xn1, w.wqkv, a.qkv, a.qk, w.q_gain, w.k_gain, cos_tab, sin_tab, s.M, Trope, s.Hq, s.Hkv,
+                            s.h, d->eps, stream);
   if (rc == SD_ERR_UNSUPPORTED) {
     RUN(sd_gemm_bf16(a.xn1, w.wqkv, a.qkv, nullptr, s.M, s.QKV, s.h, s.h, s.h, s.QKV, 0, 0, 0, stream));
-    RUN(sd_qknorm_rope_fwd(a.qkv, w.q_gain, w.k_gain, cos_tab, sin_tab, a.qk, s.M, T, s.Hq, s.Hkv, d->eps, stream));
+    RUN(sd_qknorm_rope_fwd(a.qkv, w.q_gain, w.k_gain, cos_tab, sin_tab, a.qk, s.M, Trope, s.Hq, s.Hkv, d->eps, stream));
   } else if (rc) {
     return rc;
   }
-  if (sink)
-    RUN(sd_kvcache_store(a.qk, a.qkv, sink->plane(s, B, l, 0), sink->plane(s, B, l, 1), bt.kv_len, B, T, sink->cap, s.Hq,
-                         s.Hkv, stream));
-  RUN(sd_layer_attn_fwd(s, bt, a.qk, a.qkv, a.ao, a.lse, stream));
+  if (extend) {
+    char *kp = sink->plane(s, B, l, 0), *vp = sink->plane(s, B, l, 1);
+    RUN(sd_kvcache_store_at(a.qk, a.qkv, kp, vp, sink->past, sink->new_len, B, T, sink->cap, s.Hq, s.Hkv, stream));
+    RUN(sd_attn_extend(a.qk, kp, vp, a.ao, nullptr, sink->past, sink->new_len, s.QK, s.QD, B, T, sink->cap, s.Hq, s.Hkv,
+                       128, kSdAttnScale, stream));
+  } else {
+    if (sink)
+      RUN(sd_kvcache_store(a.qk, a.qkv, sink->plane(s, B, l, 0), sink->plane(s, B, l, 1), bt.kv_len, B, T, sink->cap, s.Hq,
+                           s.Hkv, stream));
+    RUN(sd_layer_attn_fwd(s, bt, a.qk, a.qkv, a.ao, a.lse, stream));
+  }
   RUN(sd_gemm_bf16(a.ao, w.wo, a.x_mid, a.x_in, s.M, s.h, s.QD, s.QD, s.QD, s.h, s.h, 0, 0, stream));
   RUN(sd_rmsnorm_fwd(a.x_mid, w.ln2, a.xn2, (float*)a.rstd2, s.M, s.h, d->eps, stream));
   // gate|up projection: SwiGLU runs in the GEMM epilogue when gate|up need not be kept (no backward follows:
@@ -573,6 +586,40 @@ extern "C" int sd_qwen3_prefill(const sd_qwen3_dims* d, const sd_qwen3_params* p
   RUN(sd_last_rows(kv_len, rows, B, T, stream));
   const KvSink sink = {(char*)cache, cap};
   const sd_qwen3_batch bt = {ids, kv_len, nullptr, cos_tab, sin_tab, rows, B, B, T, 0};
+  return forward_impl(d, p, &bt, acts, base, logits, SD_SAVE_NONE, stream, &sink);
+}
+
+// Carrying on from a live cache (soulxpodcast.py:342,378-380: one DynamicCache handed to llm.generate turn after turn, each
+// turn feeding only the tokens the cache has not seen).  acts: the prefill's set, then the head rows and the gathered
+// cos / sin rows of the block.
+extern "C" int64_t sd_qwen3_extend_acts_bytes(const sd_qwen3_dims* d, int B, int T) {
+  if (!d) return SD_ERR_SHAPE;
+  const int64_t base = sd_qwen3_prefill_acts_bytes(d, B, T);
+  return base < 0 ? base : al(base) + 2 * al((int64_t)B * T * 128 * 2);
+}
+
+extern "C" int sd_qwen3_extend(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* past,
+                               const int32_t* new_len, const void* cos_tab, const void* sin_tab, void* acts,
+                               int64_t acts_bytes, void* cache, int64_t cache_bytes, int cap, void* logits, int B, int T,
+                               void* stream) {
+  if (!d || !p) return SD_ERR_SHAPE;
+  if (d->head_dim != 128) return SD_ERR_UNSUPPORTED;
+  if (B <= 0 || T <= 0 || cap < T || !ids || !past || !new_len || !cos_tab || !sin_tab || !acts || !logits || !cache)
+    return SD_ERR_SHAPE;
+  if (d->n_kv <= 0 || d->n_q % d->n_kv) return SD_ERR_SHAPE;
+  const int G = d->n_q / d->n_kv;
+  if (G != 1 && G != 2 && G != 4) return SD_ERR_UNSUPPORTED;
+  if (acts_bytes < sd_qwen3_extend_acts_bytes(d, B, T) || cache_bytes < sd_kvcache_bytes(d, B, cap)) return SD_ERR_WORKSPACE;
+  const int64_t base = al(sd_qwen3_acts_bytes(d, B, T, SD_SAVE_NONE));
+  int64_t* rows = (int64_t*)((char*)acts + base);
+  char* cos_rows = (char*)acts + al(sd_qwen3_prefill_acts_bytes(d, B, T));
+  char* sin_rows = cos_rows + al((int64_t)B * T * 128 * 2);
+  RUN(sd_last_rows(new_len, rows, B, T, stream));
+  RUN(sd_rope_rows_at(cos_tab, sin_tab, past, cos_rows, sin_rows, B, T, cap, stream));
+  KvSink sink = {(char*)cache, cap};
+  sink.past = past;
+  sink.new_len = new_len;
+  const sd_qwen3_batch bt = {ids, nullptr, nullptr, cos_rows, sin_rows, rows, B, B, T, 0};
   return forward_impl(d, p, &bt, acts, base, logits, SD_SAVE_NONE, stream, &sink);
 }
 

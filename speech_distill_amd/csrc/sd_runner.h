@@ -15,6 +15,13 @@ __attribute__((visibility("hidden"))) int sd_gemv_check(const void* x, const voi
                                                         const void* norm_gain, int M, int N, int K, int64_t ldx,
                                                         int64_t ldw, int64_t ldy, int64_t ldr);
 
+// sd_decode.hip: cos / sin rows of the positions past[b] + t (clamped to [0, cap - 1]) gathered into [B*T,128] tables, on
+// the device.  sd_qwen3_extend runs its q/k-norm + RoPE step on them with one "sequence" of B*T rows, the way the packed
+// forward feeds per-token positions.  Internal: not exported from the library.
+__attribute__((visibility("hidden"))) int sd_rope_rows_at(const void* cos_tab, const void* sin_tab, const int32_t* past,
+                                                          void* cos_out, void* sin_out, int B, int T, int cap,
+                                                          void* stream);
+
 // the shape ints every runner derives from the dims and the batch
 struct SdShape {
   int M, h, I, QD, KD, QKV, QK, V, L, Hq, Hkv;

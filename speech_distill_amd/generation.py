@@ -8,6 +8,10 @@ the token to a device-resident sequence buffer and hands its output straight to 
 
 Prompts are right-padded (as everywhere in this package): row b's first new token takes position ``kv_len[b]`` and the
 pad slots are never cached, so no row ever attends to them.
+
+``GenerationSession`` keeps the cache and the token buffer alive between calls, the way the reference's dialogue loop
+hands one ``DynamicCache`` to ``llm.generate`` for every turn (soulxpodcast/models/soulxpodcast.py:342,378-380): a turn
+feeds only the tokens the cache has not seen (sd_qwen3_extend).  ``generate`` is a one-turn session.
 """
 from __future__ import annotations
 
@@ -94,6 +98,25 @@ class Decoder:
         return self.logits
 
     @torch.no_grad()
+    def extend(self, ids, past, new_len):
+        """A block of right-padded NEW tokens ids int64 [B,T] behind ``past[b]`` cached positions (int32 [B], device):
+        tokens t < new_len[b] take positions past[b] + t and go into the cache; returns the logits [B,V] of each row's
+        last new token (sd_qwen3_extend)."""
+        lib, m = load_lib(), self.model
+        _need(ids, torch.int64, "input_ids"), _need(past, torch.int32, "past"), _need(new_len, torch.int32, "new_len")
+        B, T = ids.shape
+        if B != self.B or T < 1 or T > self.cap or past.numel() != B or new_len.numel() != B:
+            raise ValueError(f"extend of {tuple(ids.shape)} into a cache for {self.B} rows of {self.cap} positions")
+        nb = lib.sd_qwen3_extend_acts_bytes(C.byref(m._cdims), B, T)
+        check(min(nb, 0), "sd_qwen3_extend_acts_bytes")
+        acts = torch.empty(nb, dtype=torch.uint8, device=ids.device)
+        check(lib.sd_qwen3_extend(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(), past.data_ptr(),
+                                  new_len.data_ptr(), self.cos.data_ptr(), self.sin.data_ptr(), acts.data_ptr(), nb,
+                                  self.cache.data_ptr(), self.cache.numel(), self.cap, self.logits.data_ptr(), B, T,
+                                  _stream()), "sd_qwen3_extend")
+        return self.logits
+
+    @torch.no_grad()
     def step(self, ids, pos, max_len):
         """ids int64 [B], pos int32 [B] (device); max_len: host upper bound of every pos[b] + 1."""
         lib, m = load_lib(), self.model
@@ -109,14 +132,16 @@ class Decoder:
 
 
 def _check_args(model, B, T, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p, repetition_penalty,
-                use_ras, win_size, tau_r, sync_every, decode_kernels="tile"):
+                use_ras, win_size, tau_r, sync_every, decode_kernels="tile", model_capacity=True):
+    """``model_capacity``: also hold T + max_new_tokens against ``cache_capacity(model)`` (a session holds its own
+    lengths against its own capacity instead)."""
     _check_decode_kernels(decode_kernels)
     if max_new_tokens < 1:
         raise ValueError(f"max_new_tokens must be at least 1, got {max_new_tokens}")
     if top_k < 0 or top_k > 128:
         raise ValueError(f"top_k must be in 0..128 (the sampler keeps at most 128 candidates), got {top_k}")
     cap = cache_capacity(model)
-    if T + max_new_tokens > cap:
+    if model_capacity and T + max_new_tokens > cap:
         raise ValueError(f"prompt length {T} + max_new_tokens {max_new_tokens} exceeds the KV-cache capacity {cap}")
     if model.inference_precision != "bf16":
         raise NotImplementedError('generate() decodes with the unfolded bf16 weights; this model runs "'
@@ -132,60 +157,181 @@ def _check_args(model, B, T, max_new_tokens, min_new_tokens, do_sample, temperat
             raise ValueError("use_ras needs win_size >= 1 and tau_r > 0")
 
 
+class GenerationSession:
+    """A live generation: ONE cache of ``capacity`` positions per row, the device buffers ``seq`` int64 [B,capacity] (each
+    row's whole sequence), ``len`` int32 [B] (tokens in it) and ``cached`` int32 [B] (positions whose K / V the cache
+    holds), kept across calls (soulxpodcast.py:342: one DynamicCache; :378-380: every turn continues it).
+
+    A turn (``generate``) writes the right-padded new tokens behind each row's sequence, runs sd_qwen3_extend over each
+    row's uncached suffix ``seq[b, cached[b]:len[b]]``, and then runs the sampler / decode-step loop with ``prompt_len =
+    len``: the repetition penalty and ``min_new_tokens`` count from the turn's start (the reference passes the whole
+    history as the prompt), the RAS window looks at the last ``win_size`` tokens of the whole sequence.  After a turn every
+    row's last sampled token is in ``seq`` but not in the cache (``cached = len - 1``): that covers an EOS too, whose slot
+    the loop keeps rewriting with the pad token's K / V.  The next turn's suffix starts with that token, exactly as HF
+    feeds it.  The host knows the suffix is {0 or 1} + T_in columns wide without a read.  ``extend`` appends and caches
+    without sampling and leaves nothing uncached.
+
+    When nothing is cached in any row (a new session, or after ``reset()`` of all rows) the turn's first pass is
+    sd_qwen3_prefill, so a one-turn session returns ``model.generate``'s tokens bit for bit.
+
+    The host keeps an upper bound of the lengths (old bound + T_in + max_new_tokens) and reads the true lengths only when
+    that bound would pass ``capacity``.  ``decode_kernels="skinny"``: the decode STEPS are batch-invariant; the extend pass
+    runs the tile GEMMs at M = B * T, so a row equals the row generated alone within a turn's decode steps only."""
+
+    def __init__(self, model, batch_size, capacity=None, decode_kernels="tile"):
+        self.model, self.B = model, int(batch_size)
+        self.capacity = int(capacity) if capacity is not None else cache_capacity(model)
+        if self.B < 1 or self.capacity < 1:
+            raise ValueError(f"a session needs batch_size >= 1 and capacity >= 1, got {batch_size}, {capacity}")
+        self.decoder = Decoder(model, self.B, self.capacity, decode_kernels)
+        dev = model.flat.device
+        self.seq = torch.zeros(self.B, self.capacity, dtype=torch.int64, device=dev)
+        self.len = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self.cached = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self._fresh, self._pending, self._bound = True, False, 0
+
+    def lengths(self):
+        """int32 [B] (device): tokens in each row's sequence."""
+        return self.len.clone()
+
+    def tokens(self):
+        """List of B 1-D int64 tensors: each row's whole sequence so far (one host read of the lengths)."""
+        return [self.seq[b, :n].clone() for b, n in enumerate(self.len.tolist())]
+
+    def reset(self, rows=None):
+        """Forget the sequences of ``rows`` (all rows when None): their ``len`` and ``cached`` become 0.  The mechanism of
+        the reference's history rebuild (soulxpodcast.py:346-373); the policy itself is the caller's."""
+        if rows is None:
+            self.len.zero_(), self.cached.zero_()
+            self._fresh, self._pending, self._bound = True, False, 0
+            return
+        idx = torch.as_tensor(rows, dtype=torch.int64, device=self.len.device).reshape(-1)
+        self.len[idx] = 0
+        self.cached[idx] = 0
+
+    def _take(self, input_ids, attention_mask, max_new_tokens, sampling):
+        """Every check of a turn (one host read at most), then the new tokens go behind the sequences and the uncached
+        suffixes through the model.  -> logits [B,V]."""
+        if input_ids.dim() != 2:
+            raise ValueError(f"input_ids must be [B,T], got {tuple(input_ids.shape)}")
+        B, T = input_ids.shape
+        if B != self.B:
+            raise ValueError(f"this session holds {self.B} rows, got a batch of {B}")
+        ids = _need(input_ids.to(torch.int64), torch.int64, "input_ids")
+        dev = ids.device
+        am = None
+        if attention_mask is not None:
+            am = attention_mask.to(dev)
+            if am.shape != ids.shape:
+                raise ValueError(f"attention_mask {tuple(am.shape)} != input_ids {tuple(ids.shape)}")
+            n_in = am.sum(-1).to(torch.int32).contiguous()
+        else:
+            n_in = torch.full((B,), T, dtype=torch.int32, device=dev)
+        W = (1 if self._pending else 0) + T    # columns of the widest uncached suffix
+        bound = self._bound + T + max_new_tokens
+        if W < 1:
+            raise ValueError("every prompt needs at least one token")
+        new_len = self.len + n_in
+        if W > self.capacity:
+            raise ValueError(f"{W} new positions exceed the session's KV-cache capacity {self.capacity}")
+        if am is not None or T == 0 or bound > self.capacity:
+            bad = left_padded(am).to(torch.int32).reshape(()) if am is not None and T > 0 else new_len.min() * 0
+            bad, shortest, fewest, longest = torch.stack([bad, new_len.min(), (new_len - self.cached).min(),
+                                                          new_len.max()]).tolist()   # the one host read
+            if bad:
+                raise ValueError("attention_mask is not right-padded (a 1 follows a 0): the HIP attention kernels take a "
+                                 "valid-prefix length per sequence, as ProcessedDataCollator produces (data.py:280-327)")
+            if shortest < 1:
+                raise ValueError("every prompt needs at least one token")
+            if sampling and fewest < 1:
+                raise ValueError("a row has no uncached token to continue from: give every row at least one token")
+            bound = min(bound, longest + max_new_tokens)
+            if longest + max_new_tokens > self.capacity:
+                raise ValueError(f"sequence length {longest} + max_new_tokens {max_new_tokens} exceeds the session's "
+                                 f"KV-cache capacity {self.capacity}")
+        # ---- nothing was launched on the session's state up to here
+        col = torch.arange(self.capacity, device=dev, dtype=torch.int32)[None, :]
+        if T > 0:
+            j = col - self.len[:, None]
+            mine = (j >= 0) & (j < n_in[:, None])
+            self.seq = torch.where(mine, ids.gather(1, j.clamp(0, T - 1).to(torch.int64)), self.seq)
+        if self._fresh:
+            logits = self.decoder.prefill(ids, n_in)
+        else:
+            cols = (self.cached[:, None] + col[:, :W]).clamp(max=self.capacity - 1).to(torch.int64)
+            logits = self.decoder.extend(self.seq.gather(1, cols).contiguous(), self.cached, (new_len - self.cached).contiguous())
+        self.len = new_len.contiguous()
+        self.cached = self.len.clone()
+        self._fresh, self._pending, self._bound = False, False, bound - max_new_tokens
+        return logits
+
+    @torch.no_grad()
+    def extend(self, input_ids, attention_mask=None):
+        """Append right-padded tokens to the rows and cache them, without sampling.  Returns bf16 [B,V]: the logits of
+        each row's last token (a copy).  A row whose mask is empty sits the call out; its logits row is then meaningless."""
+        return self._take(input_ids, attention_mask, 0, False).clone()
+
+    @torch.no_grad()
+    def generate(self, input_ids, attention_mask=None, max_new_tokens=20, min_new_tokens=0, do_sample=True, temperature=1.0,
+                 top_k=0, top_p=1.0, repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, use_ras=False,
+                 win_size=25, tau_r=0.2, seed=None, sync_every=16):
+        """One turn: the sampling arguments of ``HipQwen3ForCausalLM.generate``.  Returns the NEW tokens only, int64
+        [B, max_new_tokens], ``pad_token_id`` after a row's EOS.  Every error is raised before anything is launched on the
+        session's state."""
+        model, B = self.model, self.B
+        T = input_ids.shape[1] if input_ids.dim() == 2 else 0
+        _check_args(model, B, T, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p, repetition_penalty,
+                    use_ras, win_size, tau_r, sync_every, model_capacity=False)
+        V = model.dims.vocab_size
+        pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
+        if not 0 <= pad < V or (eos_token_id is not None and not 0 <= eos_token_id < V):
+            raise ValueError(f"pad / eos token ids must lie in [0, {V})")
+        logits = self._take(input_ids, attention_mask, max_new_tokens, True)
+        dev = self.seq.device
+        dec, cap = self.decoder, self.capacity
+        # slots behind a row's sequence read as pad (the output gathers them for a row that stops early)
+        col = torch.arange(cap, device=dev, dtype=torch.int32)[None, :]
+        self.seq = torch.where(col < self.len[:, None], self.seq, torch.full_like(self.seq, pad))
+        start, lens = self.len.clone(), self.len
+        finished = torch.zeros(B, dtype=torch.uint8, device=dev)
+        nxt = torch.empty(B, dtype=torch.int64, device=dev)
+        pos = torch.empty(B, dtype=torch.int32, device=dev)
+        sp = sample_params(do_sample, temperature, top_k, top_p, repetition_penalty, min_new_tokens, eos_token_id, pad,
+                           use_ras, win_size, tau_r)
+        ws = torch.empty(load_lib().sd_sample_workspace_bytes(B, V), dtype=torch.uint8, device=dev)
+        gen = None
+        if seed is not None:
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(int(seed))
+        u = torch.rand(max_new_tokens, B, 2, generator=gen, device=dev, dtype=torch.float32)  # every step's uniforms, one launch
+        base = self._bound    # host upper bound of every row's length before the first new token
+        for step in range(max_new_tokens):
+            sample_step(logits, u[step], self.seq, start, lens, finished, sp, workspace=ws, next_out=nxt, pos_out=pos)
+            if step + 1 == max_new_tokens:
+                break
+            if (step + 1) % sync_every == 0 and bool(finished.all()):   # the only host read of the loop
+                break
+            logits = dec.step(nxt, pos, base + step + 1)
+        # every row's last sampled token (an EOS included: its slot holds the pad steps' K / V) is not in the cache
+        self.cached = lens - 1
+        self._pending, self._bound = True, base + max_new_tokens
+        # row b's new tokens sit at seq[b, start[b] ...]; slots never written still hold pad
+        cols = start.to(torch.int64)[:, None] + torch.arange(max_new_tokens, device=dev)[None, :]
+        return self.seq.gather(1, cols)
+
+
 @torch.no_grad()
 def generate(model, input_ids, attention_mask=None, max_new_tokens=20, min_new_tokens=0, do_sample=True, temperature=1.0,
              top_k=0, top_p=1.0, repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, use_ras=False, win_size=25,
              tau_r=0.2, seed=None, sync_every=16, decode_kernels="tile"):
-    """See ``HipQwen3ForCausalLM.generate``."""
+    """See ``HipQwen3ForCausalLM.generate``: a one-turn ``GenerationSession``."""
     if input_ids.dim() != 2:
         raise ValueError(f"input_ids must be [B,T], got {tuple(input_ids.shape)}")
     B, T = input_ids.shape
     _check_args(model, B, T, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p, repetition_penalty,
                 use_ras, win_size, tau_r, sync_every, decode_kernels)
-    V = model.dims.vocab_size
-    pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
-    if not 0 <= pad < V or (eos_token_id is not None and not 0 <= eos_token_id < V):
-        raise ValueError(f"pad / eos token ids must lie in [0, {V})")
-    ids = _need(input_ids.to(torch.int64), torch.int64, "input_ids")
-    dev = ids.device
-    if attention_mask is not None:
-        am = attention_mask.to(dev)
-        if am.shape != ids.shape:
-            raise ValueError(f"attention_mask {tuple(am.shape)} != input_ids {tuple(ids.shape)}")
-        kv_len = am.sum(-1).to(torch.int32).contiguous()
-        bad, shortest = torch.stack([left_padded(am).to(torch.int32).reshape(()), kv_len.min()]).tolist()  # one host read
-        if bad:
-            raise ValueError("attention_mask is not right-padded (a 1 follows a 0): the HIP attention kernels take a "
-                             "valid-prefix length per sequence, as ProcessedDataCollator produces (data.py:280-327)")
-        if shortest < 1:
-            raise ValueError("every prompt needs at least one token")
-        valid = am.to(torch.bool)
-    else:
-        kv_len = torch.full((B,), T, dtype=torch.int32, device=dev)
-        valid = None
     cap = (T + max_new_tokens + 255) // 256 * 256   # whole attention partitions; the output bits do not depend on it
-    dec = Decoder(model, B, cap, decode_kernels)
-    seq = torch.full((B, cap), pad, dtype=torch.int64, device=dev)
-    seq[:, :T] = ids if valid is None else torch.where(valid, ids, torch.full_like(ids, pad))
-    lens, finished = kv_len.clone(), torch.zeros(B, dtype=torch.uint8, device=dev)
-    nxt = torch.empty(B, dtype=torch.int64, device=dev)
-    pos = torch.empty(B, dtype=torch.int32, device=dev)
-    sp = sample_params(do_sample, temperature, top_k, top_p, repetition_penalty, min_new_tokens, eos_token_id, pad, use_ras,
-                       win_size, tau_r)
-    ws = torch.empty(load_lib().sd_sample_workspace_bytes(B, V), dtype=torch.uint8, device=dev)
-    gen = None
-    if seed is not None:
-        gen = torch.Generator(device=dev)
-        gen.manual_seed(int(seed))
-    u = torch.rand(max_new_tokens, B, 2, generator=gen, device=dev, dtype=torch.float32)  # every step's uniforms, one launch
-    logits = dec.prefill(ids, kv_len)
-    for step in range(max_new_tokens):
-        sample_step(logits, u[step], seq, kv_len, lens, finished, sp, workspace=ws, next_out=nxt, pos_out=pos)
-        if step + 1 == max_new_tokens:
-            break
-        if (step + 1) % sync_every == 0 and bool(finished.all()):   # the only host read of the loop
-            break
-        logits = dec.step(nxt, pos, T + step + 1)
-    # row b's new tokens sit at seq[b, kv_len[b] ...]; slots never written still hold pad
-    cols = kv_len.to(torch.int64)[:, None] + torch.arange(max_new_tokens, device=dev)[None, :]
-    return torch.cat([ids, seq.gather(1, cols)], dim=1)
+    sess = GenerationSession(model, B, cap, decode_kernels)
+    new = sess.generate(input_ids, attention_mask, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p,
+                        repetition_penalty, eos_token_id, pad_token_id, use_ras, win_size, tau_r, seed, sync_every)
+    return torch.cat([input_ids.to(torch.int64), new], dim=1)

@@ -824,6 +824,32 @@ def kvcache_store(qk, qkv, k_plane, v_plane, kv_len, B, T, Hq, Hkv):
                                       k_plane.shape[1], Hq, Hkv, _stream()), "sd_kvcache_store")
 
 
+def kvcache_store_at(qk, qkv, k_plane, v_plane, past, new_len, B, T, Hq, Hkv):
+    """sd_kvcache_store_at: rows t < new_len[b] of a block of T tokens per sequence -> slots past[b] + t of the planes."""
+    _need(qk, torch.bfloat16, "qk"), _need(qkv, torch.bfloat16, "qkv")
+    _need(k_plane, torch.bfloat16, "k_plane"), _need(v_plane, torch.bfloat16, "v_plane")
+    _need(past, torch.int32, "past"), _need(new_len, torch.int32, "new_len")
+    check(load_lib().sd_kvcache_store_at(qk.data_ptr(), qkv.data_ptr(), k_plane.data_ptr(), v_plane.data_ptr(),
+                                         past.data_ptr(), new_len.data_ptr(), B, T, k_plane.shape[1], Hq, Hkv, _stream()),
+          "sd_kvcache_store_at")
+
+
+def attn_extend(q, k_plane, v_plane, past, new_len, T, Hq, Hkv, want_lse=True):
+    """sd_attn_extend: q [B*T, Hq*128] (any row stride), planes [B, cap, Hkv*128] that already hold the block's K / V at
+    slots past[b] .. past[b] + new_len[b] - 1; past, new_len int32 [B] (device).  -> o [B*T, Hq*128] (, lse [B,Hq,T])."""
+    _need(k_plane, torch.bfloat16, "k_plane"), _need(v_plane, torch.bfloat16, "v_plane")
+    _need(past, torch.int32, "past"), _need(new_len, torch.int32, "new_len")
+    if not q.is_cuda:
+        raise RuntimeError("speech_distill_amd: q must be a GPU tensor (no CPU fallback)")
+    B, cap = k_plane.shape[0], k_plane.shape[1]
+    o = torch.empty(B * T, Hq * 128, dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty(B, Hq, T, dtype=torch.float32, device=q.device) if want_lse else None
+    check(load_lib().sd_attn_extend(q.data_ptr(), k_plane.data_ptr(), v_plane.data_ptr(), o.data_ptr(), _p(lse),
+                                    past.data_ptr(), new_len.data_ptr(), q.stride(0), o.stride(0), B, T, cap, Hq, Hkv, 128,
+                                    128 ** -0.5, _stream()), "sd_attn_extend")
+    return (o, lse) if want_lse else o
+
+
 def last_rows(kv_len, B, T, device=None):
     """int64 [B]: flat index b*T + clamp(kv_len[b], 1, T) - 1 of the last valid row of every right-padded sequence."""
     rows = torch.empty(B, dtype=torch.int64, device=kv_len.device if kv_len is not None else device)

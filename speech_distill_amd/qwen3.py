@@ -863,6 +863,16 @@ class HipQwen3ForCausalLM(nn.Module):
                         top_p, repetition_penalty, eos_token_id, pad_token_id, use_ras, win_size, tau_r, seed, sync_every,
                         decode_kernels)
 
+    def start_session(self, batch_size, capacity=None, decode_kernels="tile"):
+        """A ``GenerationSession`` (generation.py): multi-turn generation over ONE live KV cache of ``capacity`` positions
+        per row (default: ``cache_capacity(self)``), as the reference's dialogue loop keeps one ``DynamicCache`` across
+        turns (soulxpodcast/models/soulxpodcast.py:342,378-380).  ``sess.generate(ids, mask, ...)`` takes a turn and returns
+        its new tokens, ``sess.extend(ids, mask)`` appends without sampling (chunked prefill), ``sess.reset(rows)`` forgets
+        rows.  With ``decode_kernels="skinny"`` only the decode steps of a turn are batch-invariant: the extend pass runs the
+        tile GEMMs.  NotImplementedError for a model set to "mxfp8"."""
+        from .generation import GenerationSession
+        return GenerationSession(self, batch_size, capacity, decode_kernels)
+
     def zero_grad(self, set_to_none: bool = True):
         # keep the flat buffer; the next backward overwrites (accumulate=0) instead of adding
         self._grads_live = False
