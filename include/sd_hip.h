@@ -595,6 +595,69 @@ int sd_qwen3_decode_step_flags(const sd_qwen3_dims* d, const sd_qwen3_params* p,
                                int max_len, const void* cos_tab, const void* sin_tab, void* cache, int64_t cache_bytes,
                                int cap, void* acts, int64_t acts_bytes, void* logits, int B, int flags, void* stream);
 
+/* ---- paged KV cache (the reference's engine runs vLLM with enable_prefix_caching=True, soulxpodcast/engine/
+ * llm_engine.py:91: a block-paged cache whose blocks requests with a common prefix share).  Opt-in twins of the cache
+ * entries above; the contiguous entries and their bits are unchanged.
+ * Page: SD_KV_PAGE = 256 positions, fixed -- one sd_attn_decode partition and four 64-key sd_attn_extend tiles, so a
+ *   partition or a tile never straddles a page and the paged kernels walk the same keys in the same order as their twins.
+ * Pool: ONE caller-owned bf16 buffer [L][2][n_pages][256][Hkv*128] of sd_kvpool_bytes(d, n_pages) bytes -- per layer a K
+ *   pool plane then a V pool plane, each [n_pages][256][Hkv*128], rows as in the contiguous planes (K normalised + rotated,
+ *   V raw).  The kernel entries take the two pool planes of one layer.
+ * Page table: int32 [B][max_pages] in device memory, one for all layers: entry i of row b is the physical page holding
+ *   positions 256 i .. 256 i + 255 of that row; the row's logical capacity is cap = max_pages * 256.
+ * Rules: entries of logical pages a row does not reach are never read ("slots >= n are never read"); an entry that IS read
+ *   and lies outside [0, n_pages) is a caller error -- no access leaves the pool: a store through it is skipped, a load
+ *   through it arrives from page 0 (decode) or as zeros (extend), and that row's result is unspecified.  Device-side
+ *   lengths and positions are clamped into [0, cap] first, as in the twins.
+ * Bit contract: for ANY assignment of physical pages, o / lse / q_out and the rows gathered back through the table are
+ *   bit-identical to the twin run on a contiguous cache holding the same rows.
+ * Each entry mirrors its twin with (k_pool, v_pool, table, max_pages, n_pages) where the twin takes (k_plane, v_plane,
+ *   cap); argument checks return the twin's codes before any launch, and a NULL table, max_pages <= 0 or n_pages <= 0 is
+ *   SD_ERR_SHAPE.  sd_attn_decode_paged: workspace of sd_attn_decode_workspace_bytes(B, Hq, max_pages * 256); the
+ *   workgroup of partition p reads table[b][p] once, after the "no visible key" exit. */
+#define SD_KV_PAGE 256
+int64_t sd_kvpool_bytes(const sd_qwen3_dims* d, int n_pages);
+int sd_kvcache_store_paged(const void* qk, const void* qkv, void* k_pool, void* v_pool, const int32_t* table, int max_pages,
+                           int n_pages, const int32_t* kv_len, int B, int T, int Hq, int Hkv, void* stream);
+int sd_kvcache_store_at_paged(const void* qk, const void* qkv, void* k_pool, void* v_pool, const int32_t* table,
+                              int max_pages, int n_pages, const int32_t* past, const int32_t* new_len, int B, int T, int Hq,
+                              int Hkv, void* stream);
+int sd_qknorm_rope_append_paged(const void* qkv, const void* q_gain, const void* k_gain, const void* cos_tab,
+                                const void* sin_tab, const int32_t* pos, void* q_out, void* k_pool, void* v_pool,
+                                const int32_t* table, int max_pages, int n_pages, int B, int Hq, int Hkv, float eps,
+                                void* stream);
+int sd_attn_decode_paged(const void* q, const void* k_pool, const void* v_pool, const int32_t* table, int max_pages,
+                         int n_pages, void* o, float* lse, const int32_t* len, int len_add, void* workspace,
+                         int64_t workspace_bytes, int B, int max_len, int Hq, int Hkv, int head_dim, float scale,
+                         void* stream);
+int sd_attn_extend_paged(const void* q, const void* k_pool, const void* v_pool, const int32_t* table, int max_pages,
+                         int n_pages, void* o, float* lse, const int32_t* past, const int32_t* new_len, int64_t ldq,
+                         int64_t ldo, int B, int T, int Hq, int Hkv, int head_dim, float scale, void* stream);
+/* The runner over a paged cache (llm_engine.py:91): the launches of sd_qwen3_prefill / sd_qwen3_extend /
+ * sd_qwen3_decode_step_flags in the same order with only the five cache kernels swapped for their paged twins, so the
+ * logits are bit-identical.  kv: the pool, its size in bytes, the table [B][max_pages] and the two counts; cap =
+ * max_pages * 256 wherever the twin takes cap (cos/sin [cap,128], T <= cap, the *_acts_bytes).  A NULL kv, pool or table,
+ * n_pages <= 0 or max_pages <= 0 is SD_ERR_SHAPE, pool_bytes < sd_kvpool_bytes(d, n_pages) SD_ERR_WORKSPACE, an unknown
+ * flag bit SD_ERR_SHAPE; everything else as the twin; every check runs before the first launch. */
+typedef struct {
+  void* pool;
+  int64_t pool_bytes;
+  const int32_t* table;
+  int32_t n_pages, max_pages;
+} sd_kv_pages;
+int64_t sd_qwen3_prefill_paged_acts_bytes(const sd_qwen3_dims* d, int B, int T);
+int sd_qwen3_prefill_paged(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* kv_len,
+                           const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes, const sd_kv_pages* kv,
+                           void* logits, int B, int T, void* stream);
+int64_t sd_qwen3_extend_paged_acts_bytes(const sd_qwen3_dims* d, int B, int T);
+int sd_qwen3_extend_paged(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* past,
+                          const int32_t* new_len, const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes,
+                          const sd_kv_pages* kv, void* logits, int B, int T, void* stream);
+int64_t sd_qwen3_decode_step_paged_acts_bytes(const sd_qwen3_dims* d, int B, int max_pages);
+int sd_qwen3_decode_step_paged(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* pos,
+                               int max_len, const void* cos_tab, const void* sin_tab, const sd_kv_pages* kv, void* acts,
+                               int64_t acts_bytes, void* logits, int B, int flags, void* stream);
+
 /* ---- weight-streaming GEMV for decode (M = batch <= 16): the projections of HF:239-262 (q/k/v, o), HF:81-83 (MLP) and the
  * lm_head for one token per sequence, with the RMSNorm of HF:59-64 and the SwiGLU of HF:81-83 fused in.  bf16 operands,
  * fp32 accumulation, nothing transposed: w is [N,K] with K contiguous.

@@ -48,6 +48,10 @@ def parse_args(argv=None):
     p.add_argument("--sync_every", type=int, default=16)
     p.add_argument("--decode_kernels", choices=("tile", "skinny"), default="tile",
                    help="skinny: weight-streaming GEMV kernels for the decode step (batch_size <= 16)")
+    p.add_argument("--kv_pool_pages", type=int, default=0,
+                   help="0: every batch reserves a contiguous KV cache for its worst case.  N > 0: every batch's session "
+                        "draws pages of 256 positions from ONE pool of N pages, turn by turn (the paged cache of the "
+                        "reference's engine, llm_engine.py:91); the tokens are the same")
     return p.parse_args(argv)
 
 
@@ -105,13 +109,14 @@ def main(argv=None):
     pad = args.pad_token_id if args.pad_token_id is not None else args.stop_token_id
     dev = model.flat.device
     n_new, elapsed = 0, 0.0
+    pool = model.kv_page_pool(args.kv_pool_pages) if args.kv_pool_pages > 0 else None
     with open(args.output, "w") as out:
         for index, chunk in batches_by_turn_count(dialogues, args.batch_size):
             n_turns = len(chunk[0])
             need = max(sum(len(t) for t in d) for d in chunk) + n_turns * args.max_tokens
             if need > cache_capacity(model):
                 raise ValueError(f"a dialogue of {need} positions exceeds the KV-cache capacity {cache_capacity(model)}")
-            sess = model.start_session(len(chunk), (need + 255) // 256 * 256, decode_kernels=args.decode_kernels)
+            sess = model.start_session(len(chunk), (need + 255) // 256 * 256, decode_kernels=args.decode_kernels, pool=pool)
             for turn in range(n_turns):
                 ids, mask = right_pad([d[turn] for d in chunk], pad)
                 torch.cuda.synchronize()
@@ -130,6 +135,7 @@ def main(argv=None):
                     n_new += len(row)
                     out.write(json.dumps({"index": index[i], "turn": turn, "prompt_len": len(chunk[i][turn]),
                                           "generated_ids": row}) + "\n")
+            sess.close()    # a paged session hands its pages back to the pool for the next batch
     print(f"{len(dialogues)} prompts, {n_new} new tokens in {elapsed:.2f} s: {n_new / max(elapsed, 1e-9):.1f} tokens/s "
           f"-> {args.output}")
 

@@ -75,6 +75,11 @@ class SampleParams(C.Structure):  # include/sd_hip.h sd_sample_params
                [(n, C.c_float) for n in ("temperature", "top_p", "repetition_penalty", "pad_")]
 
 
+class KvPages(C.Structure):  # include/sd_hip.h sd_kv_pages (the paged KV cache of the runner entries)
+    _fields_ = [("pool", C.c_void_p), ("pool_bytes", C.c_int64), ("table", C.c_void_p), ("n_pages", C.c_int32),
+                ("max_pages", C.c_int32)]
+
+
 class Params(C.Structure):
     _fields_ = [("embed", C.c_void_p), ("lm_head", C.c_void_p), ("final_norm", C.c_void_p),
                 ("layers_host", C.POINTER(Layer))]
@@ -205,6 +210,21 @@ PROTOTYPES = {
                                   _i, _vp]),
     "sd_qwen3_decode_step_flags": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _i, _vp, _vp, _vp, _i64, _i, _vp, _i64,
                                         _vp, _i, _i, _vp]),
+    "sd_kvpool_bytes": (_i64, [C.POINTER(Dims), _i]),
+    "sd_kvcache_store_paged": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp]),
+    "sd_kvcache_store_at_paged": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "sd_qknorm_rope_append_paged": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp]),
+    "sd_attn_decode_paged": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _i, _i, _f, _vp]),
+    "sd_attn_extend_paged": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _f, _vp]),
+    "sd_qwen3_prefill_paged_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
+    "sd_qwen3_prefill_paged": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(KvPages),
+                                    _vp, _i, _i, _vp]),
+    "sd_qwen3_extend_paged_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
+    "sd_qwen3_extend_paged": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                   C.POINTER(KvPages), _vp, _i, _i, _vp]),
+    "sd_qwen3_decode_step_paged_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
+    "sd_qwen3_decode_step_paged": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _i, _vp, _vp, C.POINTER(KvPages), _vp,
+                                        _i64, _vp, _i, _i, _vp]),
     "sd_gemv_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i64, _i64, _i64, _i64, _vp]),
     "sd_gemv_swiglu": (_i, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp]),
 }

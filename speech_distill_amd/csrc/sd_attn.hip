@@ -55,6 +55,13 @@ struct TileDma {
       voff[i] = (int)(((long)row * ld + ((s ^ f_swz(row)) * 8)) * 2);
     }
   }
+  // the same per-lane offsets over another slice (a page of a paged cache): scalar work only.  rows <= 0: every load
+  // arrives as zeros
+  SD_DEV void rebase(const bf16* g, int rows) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)g, 0, rows > 0 ? (int)(((rows - 1) * row_bytes) + D * 2) : 0, 0x00020000);
+#endif
+  }
   SD_DEV void issue(int row0, char* lds, int w) const {
 #if defined(__HIP_DEVICE_COMPILE__)
     const int soff = (int)(row0 * row_bytes);
@@ -1245,13 +1252,26 @@ extern "C" int sd_attn_bwd_varlen(const void* q, const void* k, const void* v, c
 // a real score from the first tile on); a tile that lies wholly above a row's diagonal changes nothing for that row
 // (alpha = 1, p = 0), which is why a wave may skip it or compute it.  No atomics, no split over keys.
 // Slots >= past + new_len are outside the buffer descriptor of the stream: they read as zeros and are masked.
+// Paged (llm_engine.py:91; the page table travels as a trailing parameter pack, empty for the contiguous instantiation,
+// whose arguments and code stay what they were): a page is four tiles, so a tile never straddles one.  The buffer
+// descriptor is rebuilt per page -- base = the page's first row for this kv head, min(256, kv_end - 256 page_index)
+// records, so the slots >= kv_end still arrive as zeros -- from a page number held in scalar registers, which is
+// fetched one page (four tiles) ahead of the DMA that needs it.  Tile order, masks, online softmax and stores are untouched.
 namespace {
-template <int G>
+static_assert(SD_KV_PAGE % 64 == 0, "a 64-key tile must not straddle a page");
+struct ExtPageArgs {
+  const int* table;  // int32 [B][max_pages]
+  int max_pages, n_pages;
+};
+template <int G, class... PG>
 __global__ __launch_bounds__(128 * G) void attn_extend_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ Kp,
                                                               const bf16* __restrict__ Vp, bf16* __restrict__ O,
                                                               float* __restrict__ LSE, const int* __restrict__ past_p,
                                                               const int* __restrict__ new_p, long ldq, long ldo, int T,
-                                                              int cap, int Hq, int Hkv, float scale) {
+                                                              int cap, int Hq, int Hkv, float scale, PG... pga) {
+  constexpr bool PAGED = sizeof...(PG) > 0;
+  constexpr int TPP = SD_KV_PAGE / 64;  // tiles per page
+  const ExtPageArgs pg{pga...};
   constexpr int NW = 2 * G;    // waves
   constexpr int NP = 16 / NW;  // 1 KiB pieces of a tile each wave stages
   __shared__ __attribute__((aligned(16))) char smem[4 * TILE];  // 2 stages x (K,V); then a store image per wave
@@ -1286,8 +1306,39 @@ __global__ __launch_bounds__(128 * G) void attn_extend_kernel(const bf16* __rest
   const int lim = min(past + t, kv_end - 1);           // keys > lim are masked for this row (lim >= 0)
   const int KD = Hkv * D;
   TileDma<NP> kd, vd;
-  kd.init(Kp + (long)b * cap * KD + hkv * D, KD, kv_end, w, lane);
-  vd.init(Vp + (long)b * cap * KD + hkv * D, KD, kv_end, w, lane);
+  // paged: logical page pi of this row -> its descriptors; pages visited hold a visible key, so pi < max_pages
+  // The table entry comes by a VECTOR buffer load (every lane the same address; the descriptor covers this row of the
+  // table): its arrival is then counted by vmcnt, which the loop waits on for the tile DMA anyway, so a look-ahead
+  // fetch needs no wait of its own (a scalar load shares its counter with the LDS reads of the tile in flight).  The
+  // value is made uniform by readfirstlane where a descriptor is built from it.
+  auto page_no = [&](int pi) -> int {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (PAGED) {
+      const __amdgpu_buffer_rsrc_t trs = __builtin_amdgcn_make_buffer_rsrc(
+          (void*)(pg.table + (long)b * pg.max_pages), 0, pg.max_pages * 4, 0x00020000);
+      return (int)__builtin_amdgcn_raw_buffer_load_b32(trs, pi * 4, 0, 0);
+    }
+#endif
+    return 0;
+  };
+  auto set_page = [&](int pi, int page_v) {
+    const int page = __builtin_amdgcn_readfirstlane(page_v);
+    const bool ok = page >= 0 && page < pg.n_pages;
+    const long first = ((long)(ok ? page : 0) * SD_KV_PAGE) * KD + hkv * D;
+    const int rows = ok ? min(SD_KV_PAGE, kv_end - SD_KV_PAGE * pi) : 0;
+    kd.rebase(Kp + first, rows);
+    vd.rebase(Vp + first, rows);
+  };
+  int page_nx = 0;  // the page of the NEXT page boundary the stream crosses
+  if constexpr (PAGED) {
+    kd.init(Kp + hkv * D, KD, 1, w, lane);
+    vd.init(Vp + hkv * D, KD, 1, w, lane);
+    set_page(0, page_no(0));
+    if (nkv > TPP) page_nx = page_no(1);
+  } else {
+    kd.init(Kp + (long)b * cap * KD + hkv * D, KD, kv_end, w, lane);
+    vd.init(Vp + (long)b * cap * KD + hkv * D, KD, kv_end, w, lane);
+  }
   kd.issue(0, smem, w);
   vd.issue(0, smem + TILE, w);
   bf16x8 qf[8];
@@ -1359,8 +1410,18 @@ __global__ __launch_bounds__(128 * G) void attn_extend_kernel(const bf16* __rest
     asm volatile("" ::: "memory");
     if (i + 1 < nkv) {
       char* nx = smem + ((i + 1) & 1) * 2 * TILE;
-      kd.issue((i + 1) * 64, nx, w);
-      vd.issue((i + 1) * 64, nx + TILE, w);
+      if constexpr (PAGED) {
+        const int pi = (i + 1) / TPP;
+        if ((i + 1) % TPP == 0) {  // tile i + 1 opens page pi: its number was fetched when page pi - 1 was opened
+          set_page(pi, page_nx);
+          if ((pi + 1) * TPP < nkv) page_nx = page_no(pi + 1);
+        }
+        kd.issue(((i + 1) % TPP) * 64, nx, w);
+        vd.issue(((i + 1) % TPP) * 64, nx + TILE, w);
+      } else {
+        kd.issue((i + 1) * 64, nx, w);
+        vd.issue((i + 1) * 64, nx + TILE, w);
+      }
     }
     if (i * 64 < wave_hi) tile(i, i & 1);  // wave-uniform
   }
@@ -1391,6 +1452,38 @@ extern "C" int sd_attn_extend(const void* q, const void* k_plane, const void* v_
   hipLaunchKernelGGL((attn_extend_kernel<G_>), grid, dim3(128 * G_), 0, (hipStream_t)stream, (const bf16*)q,         \
                      (const bf16*)k_plane, (const bf16*)v_plane, (bf16*)o, lse, past, new_len, (long)ldq, (long)ldo, T, \
                      cap, Hq, Hkv, scale)
+  if (G == 1) SD_EXT_GO(1); else if (G == 2) SD_EXT_GO(2); else SD_EXT_GO(4);
+#undef SD_EXT_GO
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+// The paged twin (llm_engine.py:91): the twin's checks with cap = max_pages * 256, the same grid.
+extern "C" int sd_attn_extend_paged(const void* q, const void* k_pool, const void* v_pool, const int32_t* table,
+                                    int max_pages, int n_pages, void* o, float* lse, const int32_t* past,
+                                    const int32_t* new_len, int64_t ldq, int64_t ldo, int B, int T, int Hq, int Hkv,
+                                    int head_dim, float scale, void* stream) {
+  if (!q || !k_pool || !v_pool || !o || !past || !new_len || !table) return SD_ERR_SHAPE;
+  if (B <= 0 || T <= 0 || max_pages <= 0 || n_pages <= 0 || Hq <= 0 || Hkv <= 0 || (Hq % Hkv) || head_dim <= 0)
+    return SD_ERR_SHAPE;
+  if (head_dim != D) return SD_ERR_UNSUPPORTED;
+  const int G = Hq / Hkv;
+  if (G != 1 && G != 2 && G != 4) return SD_ERR_UNSUPPORTED;
+  if (ldq < (int64_t)Hq * D || ldo < (int64_t)Hq * D) return SD_ERR_SHAPE;
+  if ((ldq | ldo) & 7) return SD_ERR_ALIGN;
+  if (((uintptr_t)q | (uintptr_t)k_pool | (uintptr_t)v_pool | (uintptr_t)o) & 15) return SD_ERR_ALIGN;
+  // a PAGE is addressed with 32-bit byte offsets; cap = max_pages * 256 must fit an int; the grid's y and z are 16-bit
+  if ((int64_t)SD_KV_PAGE * Hkv * D * 2 >= ((int64_t)1 << 31) || max_pages > (1 << 22) || T > (1 << 30) || B > 65535 ||
+      Hkv > 65535)
+    return SD_ERR_UNSUPPORTED;
+  const int cap = max_pages * SD_KV_PAGE;
+  SdProfScope prof(SD_K_ATTN_FWD, 4.0 * B * Hq * (double)T * cap * D, (hipStream_t)stream);  // upper bound: every key
+  SD_PROF_LABEL("attn_extend_kernel<%d, paged>", G);
+  const dim3 grid((T + 63) / 64, Hkv, B);
+#define SD_EXT_GO(G_)                                                                                                  \
+  hipLaunchKernelGGL((attn_extend_kernel<G_, const int*, int, int>), grid, dim3(128 * G_), 0, (hipStream_t)stream,     \
+                     (const bf16*)q, (const bf16*)k_pool, (const bf16*)v_pool, (bf16*)o, lse, past, new_len, (long)ldq, \
+                     (long)ldo, T, cap, Hq, Hkv, scale, (const int*)table, max_pages, n_pages)
   if (G == 1) SD_EXT_GO(1); else if (G == 2) SD_EXT_GO(2); else SD_EXT_GO(4);
 #undef SD_EXT_GO
   SD_CHECK_LAUNCH();

@@ -12,6 +12,11 @@
 // [kv head][128], the layout the attention kernels read.  Every kernel below clamps the device-side lengths it is handed
 // into [0, cap] before it forms an address: no access leaves [0, cap) of a cache row whatever those arrays hold.
 // All stores are ordinary vector stores from plain C++.
+//
+// Paged form (llm_engine.py:91, vLLM's paged cache with enable_prefix_caching): the planes become pool planes
+// [n_pages][256][Hkv*128] and slot s of row b lives at page table[b][s >> 8], row s & 255 (include/sd_hip.h).  The four
+// cache kernels below take the page table as a TRAILING PARAMETER PACK, empty for the contiguous instantiation: its
+// kernel arguments, and with them its code, stay exactly what they were before the paged instantiation existed.
 #include <math.h>
 #include <stdlib.h>
 #include "sd_common.cuh"
@@ -45,12 +50,26 @@ SD_DEV bf16x8 zero8() {
 }
 SD_DEV int clampi(int x, int lo, int hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
+static_assert(SD_KV_PAGE == kPart, "a page is one decode partition");
+struct PageArgs {
+  const int32_t* table;  // int32 [B][max_pages]
+  int max_pages, n_pages;
+};
+// Element offset of slot s (0 <= s < max_pages * 256) of row b in a pool plane.  false: the table entry lies outside the
+// pool, and the caller must not store through it.
+SD_DEV bool page_slot(const PageArgs& pg, int b, int s, int KD, long* off) {
+  const int page = pg.table[(long)b * pg.max_pages + (s >> 8)];
+  *off = ((long)page * SD_KV_PAGE + (s & (SD_KV_PAGE - 1))) * KD;
+  return page >= 0 && page < pg.n_pages;
+}
+
 // ------------------------------------------------------------------------------------------- cache store (prefill)
 // One thread per 16 bytes of a K or V row of the layer: rows t < kv_len[b] go to cache slot t, nothing else is written.
+template <class... PG>
 __global__ __launch_bounds__(256) void kvcache_store_kernel(const bf16* __restrict__ qk, const bf16* __restrict__ qkv,
                                                             bf16* __restrict__ kp, bf16* __restrict__ vp,
                                                             const int32_t* __restrict__ kv_len, int B, int T, int cap,
-                                                            int Hq, int Hkv) {
+                                                            int Hq, int Hkv, PG... pga) {
   const int cpr = Hkv * 16;  // 16-byte chunks per row
   const long total = 2l * B * T * cpr;
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -63,18 +82,23 @@ __global__ __launch_bounds__(256) void kvcache_store_kernel(const bf16* __restri
   const int lim = T < cap ? T : cap;
   const int n = kv_len ? clampi(kv_len[b], 0, lim) : lim;
   if (t >= n) return;
-  const long dst = ((long)b * cap + t) * (Hkv * 128) + c * 8;
+  long dst = ((long)b * cap + t) * (Hkv * 128) + c * 8;
+  if constexpr (sizeof...(PG) > 0) {
+    if (!page_slot(PageArgs{pga...}, b, t, Hkv * 128, &dst)) return;
+    dst += c * 8;
+  }
   if (which == 0) *(bf16x8*)(kp + dst) = *(const bf16x8*)(qk + (long)m * (Hq + Hkv) * 128 + Hq * 128 + c * 8);
   else *(bf16x8*)(vp + dst) = *(const bf16x8*)(qkv + (long)m * (Hq + 2 * Hkv) * 128 + (Hq + Hkv) * 128 + c * 8);
 }
 
 // The same sink at an offset (a block of T new tokens behind past[b] cached ones): row t < new_len[b] goes to slot
 // past[b] + t, nothing else is written.  past is clamped to [0, cap], new_len to [0, min(T, cap - past)] first.
+template <class... PG>
 __global__ __launch_bounds__(256) void kvcache_store_at_kernel(const bf16* __restrict__ qk, const bf16* __restrict__ qkv,
                                                                bf16* __restrict__ kp, bf16* __restrict__ vp,
                                                                const int32_t* __restrict__ past,
                                                                const int32_t* __restrict__ new_len, int B, int T, int cap,
-                                                               int Hq, int Hkv) {
+                                                               int Hq, int Hkv, PG... pga) {
   const int cpr = Hkv * 16;  // 16-byte chunks per row
   const long total = 2l * B * T * cpr;
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -88,7 +112,11 @@ __global__ __launch_bounds__(256) void kvcache_store_at_kernel(const bf16* __res
   const int room = cap - p0;
   const int n = clampi(new_len[b], 0, T < room ? T : room);
   if (t >= n) return;
-  const long dst = ((long)b * cap + p0 + t) * (Hkv * 128) + c * 8;
+  long dst = ((long)b * cap + p0 + t) * (Hkv * 128) + c * 8;
+  if constexpr (sizeof...(PG) > 0) {
+    if (!page_slot(PageArgs{pga...}, b, p0 + t, Hkv * 128, &dst)) return;
+    dst += c * 8;
+  }
   if (which == 0) *(bf16x8*)(kp + dst) = *(const bf16x8*)(qk + (long)m * (Hq + Hkv) * 128 + Hq * 128 + c * 8);
   else *(bf16x8*)(vp + dst) = *(const bf16x8*)(qkv + (long)m * (Hq + 2 * Hkv) * 128 + (Hq + Hkv) * 128 + c * 8);
 }
@@ -124,12 +152,13 @@ __global__ void last_rows_kernel(const int32_t* __restrict__ kv_len, int64_t* __
 // whose position is pos[b]: q goes to q_out, k and the raw v into cache slot pos[b].  A head vector of 128 bf16 is owned
 // by 16 lanes; every lane runs the norm / rotation (the DPP row operations want whole rows active), the head kind only
 // picks the store.
+template <class... PG>
 __global__ __launch_bounds__(256) void qknorm_rope_append_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ qw,
                                                                  const bf16* __restrict__ kw, const bf16* __restrict__ cosb,
                                                                  const bf16* __restrict__ sinb,
                                                                  const int32_t* __restrict__ pos, bf16* __restrict__ q_out,
                                                                  bf16* __restrict__ kp, bf16* __restrict__ vp, int B,
-                                                                 int cap, int Hq, int Hkv, float eps) {
+                                                                 int cap, int Hq, int Hkv, float eps, PG... pga) {
   const int lane = lane_id();
   const int sub = lane >> 4, j = lane & 15;
   const int nh = Hq + 2 * Hkv;
@@ -139,7 +168,7 @@ __global__ __launch_bounds__(256) void qknorm_rope_append_kernel(const bf16* __r
   const long id = ok ? idx : total - 1;
   const int b = (int)(id / nh), hh = (int)(id % nh);
   const int p = pos[b];
-  const bool inb = p >= 0 && p < cap;
+  bool inb = p >= 0 && p < cap;
   const int t = clampi(p, 0, cap - 1);
   const bf16x8 raw = *(const bf16x8*)(qkv + (long)b * nh * 128 + hh * 128 + j * 8);
   float f[8], g[8], cs[8], sn[8];
@@ -161,7 +190,10 @@ __global__ __launch_bounds__(256) void qknorm_rope_append_kernel(const bf16* __r
     o[e] = n * cs[e] + rot * sn[e];
   }
   if (!ok) return;
-  const long slot = ((long)b * cap + t) * (Hkv * 128);
+  long slot = ((long)b * cap + t) * (Hkv * 128);
+  if constexpr (sizeof...(PG) > 0) {
+    if (hh >= Hq && inb) inb = page_slot(PageArgs{pga...}, b, t, Hkv * 128, &slot);
+  }
   if (hh < Hq) *(bf16x8*)(q_out + (long)b * Hq * 128 + hh * 128 + j * 8) = pack8(o);
   else if (hh < Hq + Hkv) { if (inb) *(bf16x8*)(kp + slot + (hh - Hq) * 128 + j * 8) = pack8(o); }
   else if (inb) *(bf16x8*)(vp + slot + (hh - Hq - Hkv) * 128 + j * 8) = raw;
@@ -174,12 +206,13 @@ __global__ __launch_bounds__(256) void qknorm_rope_append_kernel(const bf16* __r
 // Scores: fp32 FMAs on the vector ALU, summed over the 16 lanes by DPP; the online softmax (log2 domain) and the 8 V
 // columns a lane owns stay in registers per group, and the 16 group states are merged in group order through LDS.
 // Keys >= n are never loaded and get probability exactly 0.
-template <int G>
+// Paged: the partition IS a page; the workgroup reads table[b][p] once (uniform: a scalar load), after the early exit.
+template <int G, class... PG>
 __global__ __launch_bounds__(256) void attn_decode_part_kernel(const bf16* __restrict__ q, const bf16* __restrict__ kp,
                                                                const bf16* __restrict__ vp, float* __restrict__ ws,
                                                                const int32_t* __restrict__ len, int len_add, int cap,
                                                                int max_len, int Hq, int Hkv, int pstride,
-                                                               float scale_log2) {
+                                                               float scale_log2, PG... pga) {
   __shared__ __attribute__((aligned(16))) float sh[16][G][kRec];
   const int p = blockIdx.x, hk = blockIdx.y, b = blockIdx.z;
   const int n = clampi(len[b] + len_add, 0, cap < max_len ? cap : max_len);
@@ -196,7 +229,12 @@ __global__ __launch_bounds__(256) void attn_decode_part_kernel(const bf16* __res
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[g][e] = 0.f;
   }
-  const long off = (long)b * cap * KD + hk * 128 + j * 8;
+  long off = (long)b * cap * KD + hk * 128 + j * 8;
+  if constexpr (sizeof...(PG) > 0) {
+    const PageArgs pg{pga...};
+    const int page = clampi(pg.table[(long)b * pg.max_pages + p], 0, pg.n_pages - 1);  // p < max_pages: p * 256 < n <= cap
+    off = ((long)page - p) * kPart * KD + hk * 128 + j * 8;  // key = p * 256 + r below lands on row r of the page
+  }
   const bf16* kb = kp + off;
   const bf16* vb = vp + off;
   for (int it = 0; it < 16; it += 4) {
@@ -544,7 +582,7 @@ extern "C" int sd_kvcache_store(const void* qk, const void* qkv, void* k_plane, 
   const long total = 2l * B * T * Hkv * 16;
   SdProfScope prof(SD_K_MISC, 2.0 * total * 16, ST);
   SD_PROF_LABEL("kvcache_store_kernel");
-  hipLaunchKernelGGL(kvcache_store_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ST, (const bf16*)qk,
+  hipLaunchKernelGGL(kvcache_store_kernel<>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ST, (const bf16*)qk,
                      (const bf16*)qkv, (bf16*)k_plane, (bf16*)v_plane, kv_len, B, T, cap, Hq, Hkv);
   SD_CHECK_LAUNCH();
   return 0;
@@ -557,8 +595,46 @@ extern "C" int sd_kvcache_store_at(const void* qk, const void* qkv, void* k_plan
   const long total = 2l * B * T * Hkv * 16;
   SdProfScope prof(SD_K_MISC, 2.0 * total * 16, ST);
   SD_PROF_LABEL("kvcache_store_at_kernel");
-  hipLaunchKernelGGL(kvcache_store_at_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ST, (const bf16*)qk,
+  hipLaunchKernelGGL(kvcache_store_at_kernel<>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ST, (const bf16*)qk,
                      (const bf16*)qkv, (bf16*)k_plane, (bf16*)v_plane, past, new_len, B, T, cap, Hq, Hkv);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- paged twins of the two stores (llm_engine.py:91): same checks, same grid, the table in the trailing pack
+extern "C" int64_t sd_kvpool_bytes(const sd_qwen3_dims* d, int n_pages) {
+  if (!d || d->head_dim != 128) return SD_ERR_UNSUPPORTED;
+  if (n_pages <= 0) return SD_ERR_SHAPE;
+  return (int64_t)d->layers * 2 * n_pages * SD_KV_PAGE * d->n_kv * 128 * 2;
+}
+
+extern "C" int sd_kvcache_store_paged(const void* qk, const void* qkv, void* k_pool, void* v_pool, const int32_t* table,
+                                      int max_pages, int n_pages, const int32_t* kv_len, int B, int T, int Hq, int Hkv,
+                                      void* stream) {
+  if (!table || max_pages <= 0 || n_pages <= 0 || max_pages > (1 << 22)) return SD_ERR_SHAPE;
+  const int cap = max_pages * SD_KV_PAGE;
+  if (B <= 0 || T <= 0 || T > cap || Hq <= 0 || Hkv <= 0 || !qk || !qkv || !k_pool || !v_pool) return SD_ERR_SHAPE;
+  const long total = 2l * B * T * Hkv * 16;
+  SdProfScope prof(SD_K_MISC, 2.0 * total * 16, ST);
+  SD_PROF_LABEL("kvcache_store_kernel<paged>");
+  hipLaunchKernelGGL((kvcache_store_kernel<const int32_t*, int, int>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
+                     ST, (const bf16*)qk, (const bf16*)qkv, (bf16*)k_pool, (bf16*)v_pool, kv_len, B, T, cap, Hq, Hkv, table,
+                     max_pages, n_pages);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sd_kvcache_store_at_paged(const void* qk, const void* qkv, void* k_pool, void* v_pool, const int32_t* table,
+                                         int max_pages, int n_pages, const int32_t* past, const int32_t* new_len, int B,
+                                         int T, int Hq, int Hkv, void* stream) {
+  if (!table || max_pages <= 0 || n_pages <= 0 || max_pages > (1 << 22)) return SD_ERR_SHAPE;
+  if (B <= 0 || T <= 0 || Hq <= 0 || Hkv <= 0 || !qk || !qkv || !k_pool || !v_pool || !past || !new_len) return SD_ERR_SHAPE;
+  const long total = 2l * B * T * Hkv * 16;
+  SdProfScope prof(SD_K_MISC, 2.0 * total * 16, ST);
+  SD_PROF_LABEL("kvcache_store_at_kernel<paged>");
+  hipLaunchKernelGGL((kvcache_store_at_kernel<const int32_t*, int, int>), dim3((unsigned)((total + 255) / 256)), dim3(256),
+                     0, ST, (const bf16*)qk, (const bf16*)qkv, (bf16*)k_pool, (bf16*)v_pool, past, new_len, B, T,
+                     max_pages * SD_KV_PAGE, Hq, Hkv, table, max_pages, n_pages);
   SD_CHECK_LAUNCH();
   return 0;
 }
@@ -590,9 +666,26 @@ extern "C" int sd_qknorm_rope_append(const void* qkv, const void* q_gain, const 
   const long items = (long)B * (Hq + 2 * Hkv);
   SdProfScope prof(SD_K_MISC, 4.0 * items * 128, ST);
   SD_PROF_LABEL("qknorm_rope_append_kernel");
-  hipLaunchKernelGGL(qknorm_rope_append_kernel, dim3((unsigned)((items + 15) / 16)), dim3(256), 0, ST, (const bf16*)qkv,
+  hipLaunchKernelGGL(qknorm_rope_append_kernel<>, dim3((unsigned)((items + 15) / 16)), dim3(256), 0, ST, (const bf16*)qkv,
                      (const bf16*)q_gain, (const bf16*)k_gain, (const bf16*)cos_tab, (const bf16*)sin_tab, pos,
                      (bf16*)q_out, (bf16*)k_plane, (bf16*)v_plane, B, cap, Hq, Hkv, eps);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sd_qknorm_rope_append_paged(const void* qkv, const void* q_gain, const void* k_gain, const void* cos_tab,
+                                           const void* sin_tab, const int32_t* pos, void* q_out, void* k_pool, void* v_pool,
+                                           const int32_t* table, int max_pages, int n_pages, int B, int Hq, int Hkv,
+                                           float eps, void* stream) {
+  if (!table || max_pages <= 0 || n_pages <= 0 || max_pages > (1 << 22)) return SD_ERR_SHAPE;
+  if (B <= 0 || Hq <= 0 || Hkv <= 0 || !pos || !qkv || !q_out || !k_pool || !v_pool) return SD_ERR_SHAPE;
+  const long items = (long)B * (Hq + 2 * Hkv);
+  SdProfScope prof(SD_K_MISC, 4.0 * items * 128, ST);
+  SD_PROF_LABEL("qknorm_rope_append_kernel<paged>");
+  hipLaunchKernelGGL((qknorm_rope_append_kernel<const int32_t*, int, int>), dim3((unsigned)((items + 15) / 16)), dim3(256),
+                     0, ST, (const bf16*)qkv, (const bf16*)q_gain, (const bf16*)k_gain, (const bf16*)cos_tab,
+                     (const bf16*)sin_tab, pos, (bf16*)q_out, (bf16*)k_pool, (bf16*)v_pool, B, max_pages * SD_KV_PAGE, Hq,
+                     Hkv, eps, table, max_pages, n_pages);
   SD_CHECK_LAUNCH();
   return 0;
 }
@@ -622,6 +715,41 @@ extern "C" int sd_attn_decode(const void* q, const void* k_plane, const void* v_
   hipLaunchKernelGGL((attn_decode_part_kernel<G_>), dim3(np, Hkv, B), dim3(256), 0, ST, (const bf16*)q,               \
                      (const bf16*)k_plane, (const bf16*)v_plane, (float*)workspace, len, len_add, cap, max_len, Hq, Hkv, \
                      pstride, sl2)
+    if (G == 1) SD_DEC_GO(1); else if (G == 2) SD_DEC_GO(2); else SD_DEC_GO(4);
+#undef SD_DEC_GO
+    SD_CHECK_LAUNCH();
+  }
+  SdProfScope prof(SD_K_MISC, (double)B * Hq * np * kRec * 4, ST);
+  SD_PROF_LABEL("attn_decode_merge_kernel");
+  hipLaunchKernelGGL(attn_decode_merge_kernel, dim3(Hq, B), dim3(128), 0, ST, (const float*)workspace, (bf16*)o, lse, len,
+                     len_add, cap, max_len, Hq, pstride);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+// The paged twin (llm_engine.py:91): phase 1 reads its page from the table, phase 2 and the workspace are the twin's.
+extern "C" int sd_attn_decode_paged(const void* q, const void* k_pool, const void* v_pool, const int32_t* table,
+                                    int max_pages, int n_pages, void* o, float* lse, const int32_t* len, int len_add,
+                                    void* workspace, int64_t workspace_bytes, int B, int max_len, int Hq, int Hkv,
+                                    int head_dim, float scale, void* stream) {
+  if (head_dim != 128) return SD_ERR_UNSUPPORTED;
+  if (!table || max_pages <= 0 || n_pages <= 0 || max_pages > (1 << 22)) return SD_ERR_SHAPE;
+  if (B <= 0 || max_len <= 0 || Hq <= 0 || Hkv <= 0 || (Hq % Hkv) || !len || !q || !k_pool || !v_pool || !o) return SD_ERR_SHAPE;
+  const int G = Hq / Hkv;
+  if (G != 1 && G != 2 && G != 4) return SD_ERR_UNSUPPORTED;
+  if (B > 65535 || Hkv > 65535) return SD_ERR_SHAPE;
+  const int cap = max_pages * SD_KV_PAGE;
+  if (workspace_bytes < sd_attn_decode_workspace_bytes(B, Hq, cap) || !workspace) return SD_ERR_WORKSPACE;
+  if (max_len > cap) max_len = cap;
+  const int pstride = max_pages, np = (max_len + kPart - 1) / kPart;
+  const float sl2 = scale * 1.4426950408889634f;
+  {
+    SdProfScope prof(SD_K_MISC, 2.0 * B * Hkv * 256.0 * max_len, ST);
+    SD_PROF_LABEL("attn_decode_part_kernel<%d, paged>", G);
+#define SD_DEC_GO(G_)                                                                                                  \
+  hipLaunchKernelGGL((attn_decode_part_kernel<G_, const int32_t*, int, int>), dim3(np, Hkv, B), dim3(256), 0, ST,      \
+                     (const bf16*)q, (const bf16*)k_pool, (const bf16*)v_pool, (float*)workspace, len, len_add, cap,   \
+                     max_len, Hq, Hkv, pstride, sl2, table, max_pages, n_pages)
     if (G == 1) SD_DEC_GO(1); else if (G == 2) SD_DEC_GO(2); else SD_DEC_GO(4);
 #undef SD_DEC_GO
     SD_CHECK_LAUNCH();

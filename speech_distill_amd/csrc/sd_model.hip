@@ -98,15 +98,65 @@ LayerActs layer_acts(const Sizes& s, char* base, int l, int save) {
 }
 
 // Where a prefill leaves the keys and values of its layers: the cache [L][2][B][cap][Hkv*128] of sd_kvcache_bytes
+// -- or, in the paged form (table != nullptr; llm_engine.py:91), the pool [L][2][n_pages][256][Hkv*128] of
+// sd_kvpool_bytes: cache is then the pool's base, cap = max_pages * 256, and plane() gives the layer's pool planes.  The
+// five cache kernels are reached through the members below, which pick the contiguous entry or its paged twin.
 struct KvSink {
   char* cache;
   int cap;
   // sd_qwen3_extend: the block's rows go behind past[b] cached ones and attend over the cache (nullptr: a prefill)
   const int32_t *past = nullptr, *new_len = nullptr;
+  const int32_t* table = nullptr;
+  int n_pages = 0, max_pages = 0;
   char* plane(const Sizes& s, int B, int l, int which) const {
+    if (table) return cache + ((int64_t)l * 2 + which) * n_pages * SD_KV_PAGE * s.KD * 2;
     return cache + ((int64_t)l * 2 + which) * B * cap * s.KD * 2;
   }
+  int store(const Sizes& s, int l, const void* qk, const void* qkv, const int32_t* kv_len, int B, int T, void* stream) const {
+    char *kp = plane(s, B, l, 0), *vp = plane(s, B, l, 1);
+    if (table) return sd_kvcache_store_paged(qk, qkv, kp, vp, table, max_pages, n_pages, kv_len, B, T, s.Hq, s.Hkv, stream);
+    return sd_kvcache_store(qk, qkv, kp, vp, kv_len, B, T, cap, s.Hq, s.Hkv, stream);
+  }
+  // store_at + attention of an extend block
+  int extend(const Sizes& s, int l, const void* qk, const void* qkv, void* ao, int B, int T, void* stream) const {
+    char *kp = plane(s, B, l, 0), *vp = plane(s, B, l, 1);
+    if (table) {
+      RUN(sd_kvcache_store_at_paged(qk, qkv, kp, vp, table, max_pages, n_pages, past, new_len, B, T, s.Hq, s.Hkv, stream));
+      return sd_attn_extend_paged(qk, kp, vp, table, max_pages, n_pages, ao, nullptr, past, new_len, s.QK, s.QD, B, T, s.Hq,
+                                  s.Hkv, 128, kSdAttnScale, stream);
+    }
+    RUN(sd_kvcache_store_at(qk, qkv, kp, vp, past, new_len, B, T, cap, s.Hq, s.Hkv, stream));
+    return sd_attn_extend(qk, kp, vp, ao, nullptr, past, new_len, s.QK, s.QD, B, T, cap, s.Hq, s.Hkv, 128, kSdAttnScale,
+                          stream);
+  }
+  // append + attention of a decode step
+  int step(const Sizes& s, int l, const sd_qwen3_layer& w, const void* qkv, void* q, void* ao, const void* cos_tab,
+           const void* sin_tab, const int32_t* pos, void* ws, int64_t ws_bytes, int B, int max_len, float eps,
+           void* stream) const {
+    char *kp = plane(s, B, l, 0), *vp = plane(s, B, l, 1);
+    if (table) {
+      RUN(sd_qknorm_rope_append_paged(qkv, w.q_gain, w.k_gain, cos_tab, sin_tab, pos, q, kp, vp, table, max_pages, n_pages,
+                                      B, s.Hq, s.Hkv, eps, stream));
+      return sd_attn_decode_paged(q, kp, vp, table, max_pages, n_pages, ao, nullptr, pos, 1, ws, ws_bytes, B, max_len, s.Hq,
+                                  s.Hkv, 128, kSdAttnScale, stream);
+    }
+    RUN(sd_qknorm_rope_append(qkv, w.q_gain, w.k_gain, cos_tab, sin_tab, pos, q, kp, vp, B, cap, s.Hq, s.Hkv, eps, stream));
+    return sd_attn_decode(q, kp, vp, ao, nullptr, pos, 1, ws, ws_bytes, B, cap, max_len, s.Hq, s.Hkv, 128, kSdAttnScale,
+                          stream);
+  }
 };
+
+// the checked arguments of the paged runner entries -> a KvSink over the pool (0, or the code to return)
+int paged_sink(const sd_qwen3_dims* d, const sd_kv_pages* kv, KvSink* sink) {
+  if (!kv || !kv->pool || !kv->table || kv->n_pages <= 0 || kv->max_pages <= 0 || kv->max_pages > (1 << 22))
+    return SD_ERR_SHAPE;
+  if (kv->pool_bytes < sd_kvpool_bytes(d, kv->n_pages)) return SD_ERR_WORKSPACE;
+  *sink = KvSink{(char*)kv->pool, kv->max_pages * SD_KV_PAGE};
+  sink->table = kv->table;
+  sink->n_pages = kv->n_pages;
+  sink->max_pages = kv->max_pages;
+  return 0;
+}
 
 // One decoder layer (HF modeling_qwen3.py:227-250): a.x_in -> x_out, every intermediate into `a`.  x_out == nullptr
 // stops after the SwiGLU (the backward's recompute does not need the layer output again); keep_gu: gate|up is kept
@@ -130,14 +180,9 @@ int layer_forward(const sd_qwen3_dims* d, const Sizes& s, const LayerActs& a, co
     return rc;
   }
   if (extend) {
-    char *kp = sink->plane(s, B, l, 0), *vp = sink->plane(s, B, l, 1);
-    RUN(sd_kvcache_store_at(a.qk, a.qkv, kp, vp, sink->past, sink->new_len, B, T, sink->cap, s.Hq, s.Hkv, stream));
-    RUN(sd_attn_extend(a.qk, kp, vp, a.ao, nullptr, sink->past, sink->new_len, s.QK, s.QD, B, T, sink->cap, s.Hq, s.Hkv,
-                       128, kSdAttnScale, stream));
+    RUN(sink->extend(s, l, a.qk, a.qkv, a.ao, B, T, stream));
   } else {
-    if (sink)
-      RUN(sd_kvcache_store(a.qk, a.qkv, sink->plane(s, B, l, 0), sink->plane(s, B, l, 1), bt.kv_len, B, T, sink->cap, s.Hq,
-                           s.Hkv, stream));
+    if (sink) RUN(sink->store(s, l, a.qk, a.qkv, bt.kv_len, B, T, stream));
     RUN(sd_layer_attn_fwd(s, bt, a.qk, a.qkv, a.ao, a.lse, stream));
   }
   RUN(sd_gemm_bf16(a.ao, w.wo, a.x_mid, a.x_in, s.M, s.h, s.QD, s.QD, s.QD, s.h, s.h, 0, 0, stream));
@@ -623,6 +668,57 @@ extern "C" int sd_qwen3_extend(const sd_qwen3_dims* d, const sd_qwen3_params* p,
   return forward_impl(d, p, &bt, acts, base, logits, SD_SAVE_NONE, stream, &sink);
 }
 
+// The two block entries over a page pool (llm_engine.py:91): the twins' launches with the paged sinks.
+extern "C" int64_t sd_qwen3_prefill_paged_acts_bytes(const sd_qwen3_dims* d, int B, int T) {
+  return sd_qwen3_prefill_acts_bytes(d, B, T);
+}
+
+extern "C" int sd_qwen3_prefill_paged(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
+                                      const int32_t* kv_len, const void* cos_tab, const void* sin_tab, void* acts,
+                                      int64_t acts_bytes, const sd_kv_pages* kv, void* logits, int B, int T, void* stream) {
+  if (!d || !p) return SD_ERR_SHAPE;
+  if (d->head_dim != 128) return SD_ERR_UNSUPPORTED;
+  KvSink sink = {};
+  RUN(paged_sink(d, kv, &sink));
+  if (B <= 0 || T <= 0 || sink.cap < T || !logits || !ids || !acts) return SD_ERR_SHAPE;
+  if (acts_bytes < sd_qwen3_prefill_acts_bytes(d, B, T)) return SD_ERR_WORKSPACE;
+  const int64_t base = al(sd_qwen3_acts_bytes(d, B, T, SD_SAVE_NONE));
+  int64_t* rows = (int64_t*)((char*)acts + base);
+  RUN(sd_last_rows(kv_len, rows, B, T, stream));
+  const sd_qwen3_batch bt = {ids, kv_len, nullptr, cos_tab, sin_tab, rows, B, B, T, 0};
+  return forward_impl(d, p, &bt, acts, base, logits, SD_SAVE_NONE, stream, &sink);
+}
+
+extern "C" int64_t sd_qwen3_extend_paged_acts_bytes(const sd_qwen3_dims* d, int B, int T) {
+  return sd_qwen3_extend_acts_bytes(d, B, T);
+}
+
+extern "C" int sd_qwen3_extend_paged(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
+                                     const int32_t* past, const int32_t* new_len, const void* cos_tab, const void* sin_tab,
+                                     void* acts, int64_t acts_bytes, const sd_kv_pages* kv, void* logits, int B, int T,
+                                     void* stream) {
+  if (!d || !p) return SD_ERR_SHAPE;
+  if (d->head_dim != 128) return SD_ERR_UNSUPPORTED;
+  KvSink sink = {};
+  RUN(paged_sink(d, kv, &sink));
+  if (B <= 0 || T <= 0 || sink.cap < T || !ids || !past || !new_len || !cos_tab || !sin_tab || !acts || !logits)
+    return SD_ERR_SHAPE;
+  if (d->n_kv <= 0 || d->n_q % d->n_kv) return SD_ERR_SHAPE;
+  const int G = d->n_q / d->n_kv;
+  if (G != 1 && G != 2 && G != 4) return SD_ERR_UNSUPPORTED;
+  if (acts_bytes < sd_qwen3_extend_acts_bytes(d, B, T)) return SD_ERR_WORKSPACE;
+  const int64_t base = al(sd_qwen3_acts_bytes(d, B, T, SD_SAVE_NONE));
+  int64_t* rows = (int64_t*)((char*)acts + base);
+  char* cos_rows = (char*)acts + al(sd_qwen3_prefill_acts_bytes(d, B, T));
+  char* sin_rows = cos_rows + al((int64_t)B * T * 128 * 2);
+  RUN(sd_last_rows(new_len, rows, B, T, stream));
+  RUN(sd_rope_rows_at(cos_tab, sin_tab, past, cos_rows, sin_rows, B, T, sink.cap, stream));
+  sink.past = past;
+  sink.new_len = new_len;
+  const sd_qwen3_batch bt = {ids, nullptr, nullptr, cos_rows, sin_rows, rows, B, B, T, 0};
+  return forward_impl(d, p, &bt, acts, base, logits, SD_SAVE_NONE, stream, &sink);
+}
+
 namespace {
 struct DecodeActs {
   char *x, *x_mid, *xn, *qkv, *q, *ao, *gu, *act, *ws;
@@ -666,6 +762,13 @@ bool skinny_step_ok(const sd_qwen3_params* p, const Sizes& s, const DecodeActs& 
 }
 }  // namespace
 
+namespace {
+// the launches of a decode step over either kind of cache; every argument was checked by the entry
+int decode_step_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* pos, int max_len,
+                     const void* cos_tab, const void* sin_tab, const KvSink& kv, const Sizes& s, const DecodeActs& a,
+                     void* logits, int B, int flags, void* stream);
+}  // namespace
+
 extern "C" int sd_qwen3_decode_step_flags(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
                                           const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab,
                                           void* cache, int64_t cache_bytes, int cap, void* acts, int64_t acts_bytes,
@@ -678,17 +781,45 @@ extern "C" int sd_qwen3_decode_step_flags(const sd_qwen3_dims* d, const sd_qwen3
   const DecodeActs a(d, B, cap, (char*)acts);
   if (acts_bytes < a.total || cache_bytes < sd_kvcache_bytes(d, B, cap)) return SD_ERR_WORKSPACE;
   const KvSink kv = {(char*)cache, cap};
+  return decode_step_impl(d, p, ids, pos, max_len, cos_tab, sin_tab, kv, s, a, logits, B, flags, stream);
+}
+
+// sd_qwen3_decode_step_paged (llm_engine.py:91): the same launches over a page pool
+extern "C" int64_t sd_qwen3_decode_step_paged_acts_bytes(const sd_qwen3_dims* d, int B, int max_pages) {
+  if (max_pages <= 0 || max_pages > (1 << 22)) return SD_ERR_SHAPE;
+  return sd_qwen3_decode_acts_bytes(d, B, max_pages * SD_KV_PAGE);
+}
+
+extern "C" int sd_qwen3_decode_step_paged(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
+                                          const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab,
+                                          const sd_kv_pages* kvp, void* acts, int64_t acts_bytes, void* logits, int B,
+                                          int flags, void* stream) {
+  if (flags & ~SD_DECODE_SKINNY) return SD_ERR_SHAPE;
+  if (!d || !p) return SD_ERR_SHAPE;
+  if (d->head_dim != 128) return SD_ERR_UNSUPPORTED;
+  if (B <= 0 || max_len <= 0 || !ids || !pos || !logits || !acts) return SD_ERR_SHAPE;
+  if (d->n_kv <= 0 || d->n_q % d->n_kv) return SD_ERR_SHAPE;
+  const int G = d->n_q / d->n_kv;
+  if (G != 1 && G != 2 && G != 4) return SD_ERR_UNSUPPORTED;
+  KvSink kv = {};
+  RUN(paged_sink(d, kvp, &kv));
+  const Sizes s(d, B, 1);
+  const DecodeActs a(d, B, kv.cap, (char*)acts);
+  if (acts_bytes < a.total) return SD_ERR_WORKSPACE;
+  return decode_step_impl(d, p, ids, pos, max_len, cos_tab, sin_tab, kv, s, a, logits, B, flags, stream);
+}
+
+namespace {
+int decode_step_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* pos, int max_len,
+                     const void* cos_tab, const void* sin_tab, const KvSink& kv, const Sizes& s, const DecodeActs& a,
+                     void* logits, int B, int flags, void* stream) {
   const bool skinny = (flags & SD_DECODE_SKINNY) && skinny_step_ok(p, s, a, logits, B);
   RUN(sd_embedding_fwd(ids, p->embed, a.x, B, s.h, s.V, stream));
   if (skinny) {
     for (int l = 0; l < s.L; ++l) {
       const sd_qwen3_layer& w = p->layers_host[l];
-      char *kp = kv.plane(s, B, l, 0), *vp = kv.plane(s, B, l, 1);
       RUN(sd_gemv_bf16(a.x, w.wqkv, a.qkv, nullptr, w.ln1, d->eps, B, s.QKV, s.h, s.h, s.h, s.QKV, 0, stream));
-      RUN(sd_qknorm_rope_append(a.qkv, w.q_gain, w.k_gain, cos_tab, sin_tab, pos, a.q, kp, vp, B, cap, s.Hq, s.Hkv, d->eps,
-                                stream));
-      RUN(sd_attn_decode(a.q, kp, vp, a.ao, nullptr, pos, 1, a.ws, a.ws_bytes, B, cap, max_len, s.Hq, s.Hkv, 128,
-                         kSdAttnScale, stream));
+      RUN(kv.step(s, l, w, a.qkv, a.q, a.ao, cos_tab, sin_tab, pos, a.ws, a.ws_bytes, B, max_len, d->eps, stream));
       RUN(sd_gemv_bf16(a.ao, w.wo, a.x_mid, a.x, nullptr, 0.f, B, s.h, s.QD, s.QD, s.QD, s.h, s.h, stream));
       RUN(sd_gemv_swiglu(a.x_mid, w.wgu, a.act, w.ln2, d->eps, B, s.I, s.h, stream));
       RUN(sd_gemv_bf16(a.act, w.wdown, a.x, a.x_mid, nullptr, 0.f, B, s.h, s.I, s.I, s.I, s.h, s.h, stream));
@@ -698,13 +829,9 @@ extern "C" int sd_qwen3_decode_step_flags(const sd_qwen3_dims* d, const sd_qwen3
   }
   for (int l = 0; l < s.L; ++l) {
     const sd_qwen3_layer& w = p->layers_host[l];
-    char *kp = kv.plane(s, B, l, 0), *vp = kv.plane(s, B, l, 1);
     RUN(sd_rmsnorm_fwd(a.x, w.ln1, a.xn, nullptr, B, s.h, d->eps, stream));
     RUN(sd_gemm_bf16(a.xn, w.wqkv, a.qkv, nullptr, B, s.QKV, s.h, s.h, s.h, s.QKV, 0, 0, 0, stream));
-    RUN(sd_qknorm_rope_append(a.qkv, w.q_gain, w.k_gain, cos_tab, sin_tab, pos, a.q, kp, vp, B, cap, s.Hq, s.Hkv, d->eps,
-                              stream));
-    RUN(sd_attn_decode(a.q, kp, vp, a.ao, nullptr, pos, 1, a.ws, a.ws_bytes, B, cap, max_len, s.Hq, s.Hkv, 128, kSdAttnScale,
-                       stream));
+    RUN(kv.step(s, l, w, a.qkv, a.q, a.ao, cos_tab, sin_tab, pos, a.ws, a.ws_bytes, B, max_len, d->eps, stream));
     RUN(sd_gemm_bf16(a.ao, w.wo, a.x_mid, a.x, B, s.h, s.QD, s.QD, s.QD, s.h, s.h, 0, 0, stream));
     RUN(sd_rmsnorm_fwd(a.x_mid, w.ln2, a.xn, nullptr, B, s.h, d->eps, stream));
     const int rc = sd_gemm_swiglu(a.xn, w.wgu, nullptr, a.act, B, s.I, s.h, stream);
@@ -720,6 +847,7 @@ extern "C" int sd_qwen3_decode_step_flags(const sd_qwen3_dims* d, const sd_qwen3
   RUN(sd_gemm_bf16(a.xn, p->lm_head, logits, nullptr, B, s.V, s.h, s.h, s.h, s.V, 0, 0, 0, stream));
   return 0;
 }
+}  // namespace
 
 extern "C" int sd_qwen3_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
                                     const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab, void* cache,

@@ -12,6 +12,10 @@ pad slots are never cached, so no row ever attends to them.
 ``GenerationSession`` keeps the cache and the token buffer alive between calls, the way the reference's dialogue loop
 hands one ``DynamicCache`` to ``llm.generate`` for every turn (soulxpodcast/models/soulxpodcast.py:342,378-380): a turn
 feeds only the tokens the cache has not seen (sd_qwen3_extend).  ``generate`` is a one-turn session.
+
+A session given a ``PagePool`` (paged.py; the reference's engine runs vLLM's paged cache with prefix caching,
+soulxpodcast/engine/llm_engine.py:91) keeps no cache buffer: it owns a page table and takes pages of 256 positions from
+the pool at the start of every turn.  Its tokens are the contiguous session's, bit for bit.
 """
 from __future__ import annotations
 
@@ -22,6 +26,7 @@ import torch
 from . import _lib
 from ._lib import check, load_lib
 from .ops import _need, _stream, left_padded, sample_params, sample_step
+from .paged import PAGE, PageTable, pages_for
 
 REFERENCE_SAMPLING = dict(do_sample=True, temperature=0.6, top_k=100, top_p=0.9, repetition_penalty=1.25, use_ras=True,
                           win_size=25, tau_r=0.2)  # soulxpodcast/config.py:107-118
@@ -47,9 +52,14 @@ class Decoder:
     valid token; ``step`` takes one token per row at position ``pos[b]`` (= tokens already cached) and returns the next
     logits [B,V].  ``decode_kernels``: "tile" runs the step's projections on the training tile GEMMs; "skinny" (B <= 16)
     streams the weights through the GEMV kernels with the norms and the SwiGLU fused in (SD_DECODE_SKINNY) -- a row's
-    logits then do not depend on the batch around it.  A step whose shapes the GEMV kernels refuse runs the tile sequence."""
+    logits then do not depend on the batch around it.  A step whose shapes the GEMV kernels refuse runs the tile sequence.
 
-    def __init__(self, model, B, cap, decode_kernels="tile"):
+    ``pool`` (a ``PagePool``): the paged form (llm_engine.py:91).  No cache buffer; the decoder owns a device page table
+    int32 [B, ceil(cap / 256)] and its host mirror ``pages`` (a ``PageTable``), ``cap`` becomes that many whole pages, and
+    the three calls run the paged runner entries, whose logits are bit-identical.  Whoever drives the calls by hand makes
+    the rows own their pages first (``reserve``); ``gather`` stands in for ``planes``."""
+
+    def __init__(self, model, B, cap, decode_kernels="tile", pool=None):
         _check_decode_kernels(decode_kernels)
         self.flags = 1 if decode_kernels == "skinny" else 0   # include/sd_hip.h SD_DECODE_SKINNY
         if model.inference_precision != "bf16":
@@ -60,16 +70,68 @@ class Decoder:
         dev = model.flat.device
         _need(model.flat, torch.bfloat16, "model parameters")
         d = model._cdims
-        nb = lib.sd_kvcache_bytes(C.byref(d), self.B, self.cap)
-        check(min(nb, 0), "sd_kvcache_bytes")
-        self.cache = torch.empty(nb, dtype=torch.uint8, device=dev)
+        self.pool, self.pages = pool, None
+        if pool is not None:
+            if pool.model is not model:
+                raise ValueError("the page pool belongs to another model")
+            if self.B < 1 or self.cap < 1:
+                raise ValueError(f"a decoder needs B >= 1 and cap >= 1, got {B}, {cap}")
+            self.max_pages = pages_for(self.cap)
+            self.cap = self.max_pages * PAGE
+            self.pages = PageTable(pool.alloc, self.B, self.max_pages)
+            self.table = torch.full((self.B, self.max_pages), -1, dtype=torch.int32, device=dev)
+            self._kvp = _lib.KvPages(pool.buffer.data_ptr(), pool.buffer.numel(), self.table.data_ptr(), pool.n_pages,
+                                     self.max_pages)   # include/sd_hip.h sd_kv_pages: fixed for the decoder's life
+            self.cache = None
+        else:
+            nb = lib.sd_kvcache_bytes(C.byref(d), self.B, self.cap)
+            check(min(nb, 0), "sd_kvcache_bytes")
+            self.cache = torch.empty(nb, dtype=torch.uint8, device=dev)
         self.step_acts = torch.empty(lib.sd_qwen3_decode_acts_bytes(C.byref(d), self.B, self.cap), dtype=torch.uint8,
                                      device=dev)
         self.cos, self.sin = model._tables(self.cap, dev)
         self.logits = torch.empty(self.B, model.dims.vocab_size, dtype=torch.bfloat16, device=dev)
 
+    # ---- paged form
+    def upload(self):
+        """Send the table rows that changed on the host to the device table, on the launch stream (ahead of the first
+        kernel that needs them)."""
+        rows = sorted(self.pages.dirty)
+        if rows:
+            host = torch.tensor([self.pages.entries(b) for b in rows], dtype=torch.int32)
+            self.table[torch.tensor(rows, dtype=torch.int64, device=self.table.device)] = host.to(self.table.device)
+            self.pages.dirty.clear()
+
+    def reserve(self, lengths):
+        """Every row owns pages for ``lengths[b]`` positions (a host list).  ValueError, and nothing taken, when the pool
+        cannot cover it."""
+        self.pages.reserve([int(n) for n in lengths])
+        self.upload()
+
+    def gather(self, layer, b, n):
+        """Copies (K, V) [n, Hkv*128] of row b's first ``n`` cached rows of one layer, through the table."""
+        pg = self.pages.rows[b][:pages_for(n)]
+        if len(pg) < pages_for(n):
+            raise ValueError(f"row {b} owns {len(self.pages.rows[b])} pages, fewer than {n} positions need")
+        idx = torch.tensor(pg, dtype=torch.int64, device=self.table.device)
+        k, v = self.pool.planes(layer)
+        return k[idx].flatten(0, 1)[:n].clone(), v[idx].flatten(0, 1)[:n].clone()
+
+    def close(self):
+        """Give every page back to the pool (host bookkeeping only)."""
+        if self.pages is not None:
+            self.pages.release()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
     def planes(self, layer):
         """(K, V) views [B, cap, Hkv*128] of one layer's cache planes."""
+        if self.pool is not None:
+            raise ValueError("a paged decoder has no planes of its own: use gather(layer, b, n)")
         kd = self.model.dims.kv_dim
         n = self.B * self.cap * kd
         flat = self.cache.view(torch.bfloat16)
@@ -91,6 +153,12 @@ class Decoder:
             raise ValueError(f"prefill of {tuple(ids.shape)} into a cache for {self.B} rows of {self.cap} positions")
         nb = lib.sd_qwen3_prefill_acts_bytes(C.byref(m._cdims), B, T)
         acts = torch.empty(nb, dtype=torch.uint8, device=ids.device)
+        if self.pool is not None:
+            check(lib.sd_qwen3_prefill_paged(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(),
+                                             0 if kv_len is None else kv_len.data_ptr(), self.cos.data_ptr(),
+                                             self.sin.data_ptr(), acts.data_ptr(), nb, C.byref(self._kvp),
+                                             self.logits.data_ptr(), B, T, _stream()), "sd_qwen3_prefill_paged")
+            return self.logits
         check(lib.sd_qwen3_prefill(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(),
                                    0 if kv_len is None else kv_len.data_ptr(), self.cos.data_ptr(), self.sin.data_ptr(),
                                    acts.data_ptr(), nb, self.cache.data_ptr(), self.cache.numel(), self.cap,
@@ -110,6 +178,12 @@ class Decoder:
         nb = lib.sd_qwen3_extend_acts_bytes(C.byref(m._cdims), B, T)
         check(min(nb, 0), "sd_qwen3_extend_acts_bytes")
         acts = torch.empty(nb, dtype=torch.uint8, device=ids.device)
+        if self.pool is not None:
+            check(lib.sd_qwen3_extend_paged(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(), past.data_ptr(),
+                                            new_len.data_ptr(), self.cos.data_ptr(), self.sin.data_ptr(), acts.data_ptr(), nb,
+                                            C.byref(self._kvp), self.logits.data_ptr(), B, T, _stream()),
+                  "sd_qwen3_extend_paged")
+            return self.logits
         check(lib.sd_qwen3_extend(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(), past.data_ptr(),
                                   new_len.data_ptr(), self.cos.data_ptr(), self.sin.data_ptr(), acts.data_ptr(), nb,
                                   self.cache.data_ptr(), self.cache.numel(), self.cap, self.logits.data_ptr(), B, T,
@@ -123,6 +197,12 @@ class Decoder:
         _need(ids, torch.int64, "ids"), _need(pos, torch.int32, "pos")
         if ids.numel() != self.B or pos.numel() != self.B:
             raise ValueError(f"decode step wants {self.B} tokens and positions")
+        if self.pool is not None:
+            check(lib.sd_qwen3_decode_step_paged(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(), pos.data_ptr(),
+                                                 int(max_len), self.cos.data_ptr(), self.sin.data_ptr(), C.byref(self._kvp),
+                                                 self.step_acts.data_ptr(), self.step_acts.numel(), self.logits.data_ptr(),
+                                                 self.B, self.flags, _stream()), "sd_qwen3_decode_step_paged")
+            return self.logits
         check(lib.sd_qwen3_decode_step_flags(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(), pos.data_ptr(),
                                              int(max_len), self.cos.data_ptr(), self.sin.data_ptr(), self.cache.data_ptr(),
                                              self.cache.numel(), self.cap, self.step_acts.data_ptr(),
@@ -176,14 +256,25 @@ class GenerationSession:
 
     The host keeps an upper bound of the lengths (old bound + T_in + max_new_tokens) and reads the true lengths only when
     that bound would pass ``capacity``.  ``decode_kernels="skinny"``: the decode STEPS are batch-invariant; the extend pass
-    runs the tile GEMMs at M = B * T, so a row equals the row generated alone within a turn's decode steps only."""
+    runs the tile GEMMs at M = B * T, so a row equals the row generated alone within a turn's decode steps only.
 
-    def __init__(self, model, batch_size, capacity=None, decode_kernels="tile"):
+    ``pool`` (a ``PagePool``; llm_engine.py:91): the paged session.  It holds no cache buffer but a page table, and several
+    sessions may share one pool.  Allocation rule: a paged session ALWAYS takes its one host read at the start of a turn,
+    and that read also carries the per-row lengths.  There the host first gives back the pages a row no longer needs (whole
+    pages past its true length, left over from the previous turn's worst case), then gives every row pages for ``len[b] +
+    n_in[b] + max_new_tokens`` positions and uploads the changed table rows on the launch stream ahead of the first kernel.
+    Inside the decode loop no table changes and no extra host read happens.  A pool that cannot cover the turn raises
+    ValueError before anything is launched on the session's state, and no page has then changed hands.  ``reset`` releases
+    the rows' pages, ``trim()`` releases the worst-case leftovers on demand, ``fork(rows)`` continues rows in a new
+    session that shares their full pages, ``close()`` (also run when the session is dropped) releases everything."""
+
+    def __init__(self, model, batch_size, capacity=None, decode_kernels="tile", pool=None):
         self.model, self.B = model, int(batch_size)
         self.capacity = int(capacity) if capacity is not None else cache_capacity(model)
         if self.B < 1 or self.capacity < 1:
             raise ValueError(f"a session needs batch_size >= 1 and capacity >= 1, got {batch_size}, {capacity}")
-        self.decoder = Decoder(model, self.B, self.capacity, decode_kernels)
+        self.pool, self.decode_kernels = pool, decode_kernels
+        self.decoder = Decoder(model, self.B, self.capacity, decode_kernels, pool=pool)
         dev = model.flat.device
         self.seq = torch.zeros(self.B, self.capacity, dtype=torch.int64, device=dev)
         self.len = torch.zeros(self.B, dtype=torch.int32, device=dev)
@@ -204,10 +295,63 @@ class GenerationSession:
         if rows is None:
             self.len.zero_(), self.cached.zero_()
             self._fresh, self._pending, self._bound = True, False, 0
+            if self.pool is not None:
+                self.decoder.pages.release()
+                self.decoder.upload()
             return
         idx = torch.as_tensor(rows, dtype=torch.int64, device=self.len.device).reshape(-1)
         self.len[idx] = 0
         self.cached[idx] = 0
+        if self.pool is not None:
+            self.decoder.pages.release(sorted(set(torch.as_tensor(rows).reshape(-1).tolist())))
+            self.decoder.upload()
+
+    def trim(self):
+        """Paged sessions: give back every row's whole pages past its true length (the leftovers of the last turn's
+        worst case), with one host read of the lengths.  The next turn does this by itself."""
+        if self.pool is None:
+            raise ValueError("trim() is for sessions over a page pool")
+        self.decoder.pages.trim(self.len.tolist())
+        self.decoder.upload()
+
+    def close(self):
+        """Release the session's pages (paged sessions; a no-op otherwise).  The session holds nothing afterwards."""
+        if self.pool is not None:
+            self.decoder.close()
+            self.len.zero_(), self.cached.zero_()
+            self._fresh, self._pending, self._bound = True, False, 0
+
+    def __del__(self):
+        try:
+            if self.pool is not None:
+                self.decoder.close()
+        except Exception:
+            pass
+
+    def fork(self, rows):
+        """A new session on the same pool whose row i continues this session's row ``rows[i]`` (repeats allowed: ``fork([0]
+        * 8)`` gives 8 continuations of row 0), with one host read of the source lengths.  Pages wholly below ``cached[src]``
+        are shared -- a row only writes at positions >= cached[b], so nobody writes there again; the page that holds
+        position ``cached[src]`` is copied across all layers when that position does not start a page.  ``seq``, ``len``,
+        ``cached`` and the session flags are copied.  ValueError on a contiguous session, or when the pool lacks the pages
+        for the copies (nothing has changed then)."""
+        if self.pool is None:
+            raise ValueError("fork() is for sessions over a page pool (start_session(..., pool=pool))")
+        rows = [int(r) for r in rows]
+        if not rows or min(rows) < 0 or max(rows) >= self.B:
+            raise ValueError(f"fork rows must lie in [0, {self.B}), got {rows}")
+        new = GenerationSession.__new__(GenerationSession)
+        new.model, new.B, new.capacity, new.pool, new.decode_kernels = self.model, len(rows), self.capacity, self.pool, \
+            self.decode_kernels
+        new.decoder = Decoder(self.model, new.B, self.capacity, self.decode_kernels, pool=self.pool)
+        cached = self.cached.tolist()   # the one host read
+        new.decoder.pages, copies = self.decoder.pages.fork(rows, cached)   # raises before anything changed
+        self.pool.copy_pages(copies)
+        new.decoder.upload()
+        idx = torch.tensor(rows, dtype=torch.int64, device=self.len.device)
+        new.seq, new.len, new.cached = self.seq[idx].clone(), self.len[idx].clone(), self.cached[idx].clone()
+        new._fresh, new._pending, new._bound = self._fresh, self._pending, self._bound
+        return new
 
     def _take(self, input_ids, attention_mask, max_new_tokens, sampling):
         """Every check of a turn (one host read at most), then the new tokens go behind the sequences and the uncached
@@ -234,10 +378,14 @@ class GenerationSession:
         new_len = self.len + n_in
         if W > self.capacity:
             raise ValueError(f"{W} new positions exceed the session's KV-cache capacity {self.capacity}")
-        if am is not None or T == 0 or bound > self.capacity:
+        paged = self.pool is not None
+        if paged or am is not None or T == 0 or bound > self.capacity:
             bad = left_padded(am).to(torch.int32).reshape(()) if am is not None and T > 0 else new_len.min() * 0
-            bad, shortest, fewest, longest = torch.stack([bad, new_len.min(), (new_len - self.cached).min(),
-                                                          new_len.max()]).tolist()   # the one host read
+            head = torch.stack([bad, new_len.min(), (new_len - self.cached).min(), new_len.max()])
+            if paged:   # the read also carries the per-row lengths
+                head = torch.cat([head, self.len, new_len])
+            host = head.tolist()   # the one host read
+            bad, shortest, fewest, longest = host[:4]
             if bad:
                 raise ValueError("attention_mask is not right-padded (a 1 follows a 0): the HIP attention kernels take a "
                                  "valid-prefix length per sequence, as ProcessedDataCollator produces (data.py:280-327)")
@@ -249,6 +397,9 @@ class GenerationSession:
             if longest + max_new_tokens > self.capacity:
                 raise ValueError(f"sequence length {longest} + max_new_tokens {max_new_tokens} exceeds the session's "
                                  f"KV-cache capacity {self.capacity}")
+            if paged:   # give back last turn's leftovers, take this turn's worst case: ValueError changes nothing
+                self.decoder.pages.admit(host[4:4 + B], [n + max_new_tokens for n in host[4 + B:]])
+                self.decoder.upload()
         # ---- nothing was launched on the session's state up to here
         col = torch.arange(self.capacity, device=dev, dtype=torch.int32)[None, :]
         if T > 0:

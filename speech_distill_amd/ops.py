@@ -891,6 +891,81 @@ def attn_decode(q, k_plane, v_plane, lens, Hq, Hkv, max_len=None, len_add=0, wan
     return (o, lse) if want_lse else o
 
 
+# ---- paged twins (soulxpodcast/engine/llm_engine.py:91): pool planes [n_pages, 256, Hkv*128], table int32 [B, max_pages]
+def _paged_args(k_pool, v_pool, table):
+    _need(k_pool, torch.bfloat16, "k_pool"), _need(v_pool, torch.bfloat16, "v_pool"), _need(table, torch.int32, "table")
+    if k_pool.dim() != 3 or k_pool.shape[1] != 256 or v_pool.shape != k_pool.shape or table.dim() != 2:
+        raise ValueError(f"pool planes must be [n_pages, 256, Hkv*128] and the table [B, max_pages], got "
+                         f"{tuple(k_pool.shape)}, {tuple(v_pool.shape)}, {tuple(table.shape)}")
+    return k_pool.data_ptr(), v_pool.data_ptr(), table.data_ptr(), table.shape[1], k_pool.shape[0]
+
+
+def kvcache_store_paged(qk, qkv, k_pool, v_pool, table, kv_len, B, T, Hq, Hkv):
+    """sd_kvcache_store_paged: ``kvcache_store`` through a page table; slot t of row b is row t & 255 of page
+    table[b, t >> 8]."""
+    _need(qk, torch.bfloat16, "qk"), _need(qkv, torch.bfloat16, "qkv")
+    kp, vp, tp, max_pages, n_pages = _paged_args(k_pool, v_pool, table)
+    check(load_lib().sd_kvcache_store_paged(qk.data_ptr(), qkv.data_ptr(), kp, vp, tp, max_pages, n_pages, _p(kv_len), B, T,
+                                            Hq, Hkv, _stream()), "sd_kvcache_store_paged")
+
+
+def kvcache_store_at_paged(qk, qkv, k_pool, v_pool, table, past, new_len, B, T, Hq, Hkv):
+    """sd_kvcache_store_at_paged: ``kvcache_store_at`` through a page table."""
+    _need(qk, torch.bfloat16, "qk"), _need(qkv, torch.bfloat16, "qkv")
+    _need(past, torch.int32, "past"), _need(new_len, torch.int32, "new_len")
+    kp, vp, tp, max_pages, n_pages = _paged_args(k_pool, v_pool, table)
+    check(load_lib().sd_kvcache_store_at_paged(qk.data_ptr(), qkv.data_ptr(), kp, vp, tp, max_pages, n_pages,
+                                               past.data_ptr(), new_len.data_ptr(), B, T, Hq, Hkv, _stream()),
+          "sd_kvcache_store_at_paged")
+
+
+def attn_extend_paged(q, k_pool, v_pool, table, past, new_len, T, Hq, Hkv, want_lse=True):
+    """sd_attn_extend_paged: ``attn_extend`` over pool planes and a page table; the same bits."""
+    _need(past, torch.int32, "past"), _need(new_len, torch.int32, "new_len")
+    kp, vp, tp, max_pages, n_pages = _paged_args(k_pool, v_pool, table)
+    if not q.is_cuda:
+        raise RuntimeError("speech_distill_amd: q must be a GPU tensor (no CPU fallback)")
+    B = table.shape[0]
+    o = torch.empty(B * T, Hq * 128, dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty(B, Hq, T, dtype=torch.float32, device=q.device) if want_lse else None
+    check(load_lib().sd_attn_extend_paged(q.data_ptr(), kp, vp, tp, max_pages, n_pages, o.data_ptr(), _p(lse),
+                                          past.data_ptr(), new_len.data_ptr(), q.stride(0), o.stride(0), B, T, Hq, Hkv, 128,
+                                          128 ** -0.5, _stream()), "sd_attn_extend_paged")
+    return (o, lse) if want_lse else o
+
+
+def qknorm_rope_append_paged(qkv, q_gain, k_gain, cos, sin, pos, k_pool, v_pool, table, Hq, Hkv, eps=1e-6):
+    """sd_qknorm_rope_append_paged: ``qknorm_rope_append`` whose K / V go to slot pos[b] through a page table."""
+    _need(qkv, torch.bfloat16, "qkv"), _need(pos, torch.int32, "pos")
+    kp, vp, tp, max_pages, n_pages = _paged_args(k_pool, v_pool, table)
+    B = qkv.shape[0]
+    if cos.shape[0] < max_pages * 256:
+        raise ValueError(f"rope tables hold {cos.shape[0]} positions, the page table {max_pages * 256}")
+    q = torch.empty(B, Hq * 128, dtype=torch.bfloat16, device=qkv.device)
+    check(load_lib().sd_qknorm_rope_append_paged(qkv.data_ptr(), q_gain.data_ptr(), k_gain.data_ptr(), cos.data_ptr(),
+                                                 sin.data_ptr(), pos.data_ptr(), q.data_ptr(), kp, vp, tp, max_pages,
+                                                 n_pages, B, Hq, Hkv, eps, _stream()), "sd_qknorm_rope_append_paged")
+    return q
+
+
+def attn_decode_paged(q, k_pool, v_pool, table, lens, Hq, Hkv, max_len=None, len_add=0, want_lse=False, workspace=None):
+    """sd_attn_decode_paged: ``attn_decode`` over pool planes and a page table; the same bits."""
+    _need(q, torch.bfloat16, "q"), _need(lens, torch.int32, "lens")
+    kp, vp, tp, max_pages, n_pages = _paged_args(k_pool, v_pool, table)
+    lib = load_lib()
+    B, cap = q.shape[0], max_pages * 256
+    nb = lib.sd_attn_decode_workspace_bytes(B, Hq, cap)
+    if workspace is None:
+        workspace = torch.empty(max(nb, 16), dtype=torch.uint8, device=q.device)
+    o = torch.empty(B, Hq * 128, dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty(B, Hq, dtype=torch.float32, device=q.device) if want_lse else None
+    check(lib.sd_attn_decode_paged(q.data_ptr(), kp, vp, tp, max_pages, n_pages, o.data_ptr(), _p(lse), lens.data_ptr(),
+                                   int(len_add), workspace.data_ptr(), workspace.numel(), B,
+                                   cap if max_len is None else int(max_len), Hq, Hkv, 128, 128 ** -0.5, _stream()),
+          "sd_attn_decode_paged")
+    return (o, lse) if want_lse else o
+
+
 def sample_params(do_sample=True, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, min_new_tokens=0,
                   eos_token_id=None, pad_token_id=0, use_ras=False, win_size=25, tau_r=0.2):
     """include/sd_hip.h sd_sample_params.  The RAS threshold is handed over as an integer count: count + 1 >= win_size *

@@ -863,15 +863,32 @@ class HipQwen3ForCausalLM(nn.Module):
                         top_p, repetition_penalty, eos_token_id, pad_token_id, use_ras, win_size, tau_r, seed, sync_every,
                         decode_kernels)
 
-    def start_session(self, batch_size, capacity=None, decode_kernels="tile"):
+    def start_session(self, batch_size, capacity=None, decode_kernels="tile", pool=None):
         """A ``GenerationSession`` (generation.py): multi-turn generation over ONE live KV cache of ``capacity`` positions
         per row (default: ``cache_capacity(self)``), as the reference's dialogue loop keeps one ``DynamicCache`` across
         turns (soulxpodcast/models/soulxpodcast.py:342,378-380).  ``sess.generate(ids, mask, ...)`` takes a turn and returns
         its new tokens, ``sess.extend(ids, mask)`` appends without sampling (chunked prefill), ``sess.reset(rows)`` forgets
         rows.  With ``decode_kernels="skinny"`` only the decode steps of a turn are batch-invariant: the extend pass runs the
-        tile GEMMs.  NotImplementedError for a model set to "mxfp8"."""
+        tile GEMMs.  NotImplementedError for a model set to "mxfp8".
+
+        ``pool`` (a ``PagePool`` of ``kv_page_pool``): the session keeps no cache buffer of its own; it owns a page table
+        and takes pages of 256 positions from the pool turn by turn (paged.py; the reference's engine runs vLLM's paged
+        cache, soulxpodcast/engine/llm_engine.py:91).  Several sessions may share one pool; ``sess.fork(rows)``,
+        ``sess.trim()`` and ``sess.close()`` exist for such sessions.  The tokens are those of the contiguous session, bit
+        for bit.  Sampling n answers to one prompt with one prefill::
+
+            s = model.start_session(1, pool=pool); s.extend(prompt[:, :-1])
+            n = s.fork([0] * 8); out = n.generate(prompt[:, -1:].expand(8, 1), ...)
+        """
         from .generation import GenerationSession
-        return GenerationSession(self, batch_size, capacity, decode_kernels)
+        return GenerationSession(self, batch_size, capacity, decode_kernels, pool=pool)
+
+    def kv_page_pool(self, n_pages, order=None):
+        """A ``PagePool`` (paged.py) of ``n_pages`` pages of 256 positions for this model's paged sessions
+        (``start_session(..., pool=pool)``); ``order``: an optional permutation of the page numbers, the order in which
+        free pages are handed out.  One page costs ``pool.bytes_per_page`` = L * 2 * 256 * Hkv * 128 * 2 bytes."""
+        from .paged import PagePool
+        return PagePool(self, n_pages, order)
 
     def zero_grad(self, set_to_none: bool = True):
         # keep the flat buffer; the next backward overwrites (accumulate=0) instead of adding
