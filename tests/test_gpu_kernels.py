@@ -272,7 +272,7 @@ def test_folded_rmsnorm_pieces(ops, O, H):
 
 
 @pytest.mark.parametrize("K", [64, 128, 192, 1088])
-@pytest.mark.parametrize("ta,tb", [(False, False), (False, True), (True, True)])
+@pytest.mark.parametrize("ta,tb", [(False, False), (False, True), (True, False), (True, True)])
 def test_gemm_persistent_kernel(ops, ta, tb, K):
     """more 256x128 tiles than CUs -> the persistent staggered kernel: one K stream across tile boundaries (K of 1, 2,
     3 and 17 steps per tile), ragged M and N edges, register epilogue; must equal the one-tile-per-workgroup kernel
