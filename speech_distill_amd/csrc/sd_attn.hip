@@ -1106,10 +1106,9 @@ extern "C" int sd_attn_bwd2(const void* q, const void* k, const void* v, const v
   if (head_dim != D) return SD_ERR_UNSUPPORTED;
   if (int e = check_common(B, T, Hq, Hkv, ldq, ldk, ldv, ldo)) return e;
   if ((lddq | lddk | lddv) & 7) return SD_ERR_ALIGN;
-  hipStream_t st = (hipStream_t)stream, s2 = (hipStream_t)side_stream;
-  SdEventLease lease;  // this call's events (per call, per device)
-  if (s2 && !(lease.set = sd_lease_events())) return SD_ERR_WORKSPACE;
-  hipEvent_t* g_attn_ev = lease.set ? lease.set->ev : nullptr;
+  SdStreamOrder ord;  // this call's events (per call, per device)
+  if (int e = ord.init(stream, side_stream)) return e;
+  hipStream_t st = ord.main, s2 = ord.side;
   const long total = (long)B * T * Hq;
   if (o) {  // o == NULL: `delta` already holds rowsum(dO * O) (sd_gemm_odx_delta)
     hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, st, (const bf16*)d_o,
@@ -1117,10 +1116,7 @@ extern "C" int sd_attn_bwd2(const void* q, const void* k, const void* v, const v
     SD_CHECK_LAUNCH();
   }
   hipStream_t sq = s2 ? s2 : st;  // stream of the dQ kernel
-  if (s2) {
-    if (hipEventRecord(g_attn_ev[0], st) != hipSuccess || hipStreamWaitEvent(s2, g_attn_ev[0], 0) != hipSuccess)
-      return SD_ERR_WORKSPACE;
-  }
+  if (int e = ord.side_waits_for_main(kEvAttnInputs)) return e;
   {
     SdProfScope prof2(SD_K_ATTN_BWD_DQ, 3.0 * B * Hq * (double)T * T * D, sq);  // S, dP (recomputed), dQ
     hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, dim3((((T + 63) / 64 + 1) / 2) * Hq * B), dim3(512), 0, sq, (const bf16*)q, (const bf16*)k,
@@ -1135,11 +1131,7 @@ extern "C" int sd_attn_bwd2(const void* q, const void* k, const void* v, const v
                        kv_len, ldq, ldk, ldv, ldo, lddk, lddv, T, Hq, Hkv, scale);
   }
   SD_CHECK_LAUNCH();
-  if (s2) {
-    if (hipEventRecord(g_attn_ev[1], s2) != hipSuccess || hipStreamWaitEvent(st, g_attn_ev[1], 0) != hipSuccess)
-      return SD_ERR_WORKSPACE;
-  }
-  return 0;
+  return ord.main_waits_for_side(kEvAttnDq);
 }
 
 extern "C" int sd_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
@@ -1199,10 +1191,9 @@ extern "C" int sd_attn_bwd_varlen(const void* q, const void* k, const void* v, c
   unsigned pairs;
   if (int e = varlen_check(vl, M, Hq, Hkv, ldq, ldk, ldv, ldo, &va, &pairs)) return e;
   if ((lddq | lddk | lddv) & 7) return SD_ERR_ALIGN;
-  hipStream_t st = (hipStream_t)stream, s2 = (hipStream_t)side_stream;
-  SdEventLease lease;
-  if (s2 && !(lease.set = sd_lease_events())) return SD_ERR_WORKSPACE;
-  hipEvent_t* g_attn_ev = lease.set ? lease.set->ev : nullptr;
+  SdStreamOrder ord;  // this call's events (per call, per device)
+  if (int e = ord.init(stream, side_stream)) return e;
+  hipStream_t st = ord.main, s2 = ord.side;
   const long total = (long)M * Hq;
   if (o) {  // per token: one row of M tokens is exactly the [Hq, M] layout of the packed LSE / delta
     hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, st, (const bf16*)d_o,
@@ -1210,10 +1201,7 @@ extern "C" int sd_attn_bwd_varlen(const void* q, const void* k, const void* v, c
     SD_CHECK_LAUNCH();
   }
   hipStream_t sq = s2 ? s2 : st;
-  if (s2) {
-    if (hipEventRecord(g_attn_ev[0], st) != hipSuccess || hipStreamWaitEvent(s2, g_attn_ev[0], 0) != hipSuccess)
-      return SD_ERR_WORKSPACE;
-  }
+  if (int e = ord.side_waits_for_main(kEvAttnInputs)) return e;
   const double ml = vl->max_seqlen > 0 ? (double)(vl->max_seqlen < M ? vl->max_seqlen : M) : (double)M;
   {
     SdProfScope prof2(SD_K_ATTN_BWD_DQ, 3.0 * Hq * (double)M * ml * D, sq);
@@ -1229,11 +1217,7 @@ extern "C" int sd_attn_bwd_varlen(const void* q, const void* k, const void* v, c
         nullptr, ldq, ldk, ldv, ldo, lddk, lddv, M, Hq, Hkv, scale, va);
   }
   SD_CHECK_LAUNCH();
-  if (s2) {
-    if (hipEventRecord(g_attn_ev[1], s2) != hipSuccess || hipStreamWaitEvent(st, g_attn_ev[1], 0) != hipSuccess)
-      return SD_ERR_WORKSPACE;
-  }
-  return 0;
+  return ord.main_waits_for_side(kEvAttnDq);
 }
 
 // ------------------------------------------------------------------------------------------ extend

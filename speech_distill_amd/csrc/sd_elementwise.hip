@@ -14,6 +14,7 @@
 #include "../../include/sd_hip.h"
 #include "sd_prof.h"
 #include "sd_debug.h"
+#include "sd_events.h"
 
 namespace {
 
@@ -536,8 +537,7 @@ static int rmsnorm_bwd_any(const void* dy, const float* dy_slabs, int nsplit, co
   hipStream_t rs = ST;
   if (reduce_stream && event) {
     rs = (hipStream_t)reduce_stream;
-    if (hipEventRecord((hipEvent_t)event, ST) != hipSuccess || hipStreamWaitEvent(rs, (hipEvent_t)event, 0) != hipSuccess)
-      return SD_ERR_WORKSPACE;
+    if (int e = sd_order_after(ST, rs, (hipEvent_t)event)) return e;
   }
   hipLaunchKernelGGL(colsum_reduce_kernel, dim3((H + 31) / 32), dim3(256), 0, rs, (const float*)workspace, (bf16*)dw,
                      nb, H, H, accumulate_dw);
@@ -641,8 +641,7 @@ extern "C" int sd_qknorm_rope_bwd2(const void* dqk, const void* qkv, const void*
   hipStream_t rs = ST;
   if (reduce_stream && event) {
     rs = (hipStream_t)reduce_stream;
-    if (hipEventRecord((hipEvent_t)event, ST) != hipSuccess || hipStreamWaitEvent(rs, (hipEvent_t)event, 0) != hipSuccess)
-      return SD_ERR_WORKSPACE;
+    if (int e = sd_order_after(ST, rs, (hipEvent_t)event)) return e;
   }
   hipLaunchKernelGGL(colsum_reduce_kernel, dim3(4), dim3(256), 0, rs, (const float*)workspace, (bf16*)dq_gain, nb, 128,
                      256, accumulate_dw);

@@ -39,19 +39,11 @@ struct LayerActs {
 };
 
 LayerActs carve(const Sizes& s, char* p) {
+  auto take = [&](int64_t n) { char* q = p; p += n; return q; };  // the next n bytes of the caller's buffer
   LayerActs a;
-  a.x_in = p; p += s.x;
-  a.rstd1 = p; p += s.rstd;
-  a.xn1 = p; p += s.x;
-  a.qkv = p; p += s.qkv;
-  a.qk = p; p += s.qk;
-  a.ao = p; p += s.ao;
-  a.lse = p; p += s.lse;
-  a.x_mid = p; p += s.x;
-  a.rstd2 = p; p += s.rstd;
-  a.xn2 = p; p += s.x;
-  a.gu = p; p += s.gu;
-  a.act = p; p += s.act;
+  a.x_in = take(s.x); a.rstd1 = take(s.rstd); a.xn1 = take(s.x); a.qkv = take(s.qkv); a.qk = take(s.qk);
+  a.ao = take(s.ao); a.lse = take(s.lse); a.x_mid = take(s.x); a.rstd2 = take(s.rstd); a.xn2 = take(s.x);
+  a.gu = take(s.gu); a.act = take(s.act);
   return a;
 }
 
@@ -63,29 +55,24 @@ struct BwdScratch {
   char *dxn, *dqk, *dao, *delta, *dact, *ws_norm, *ws_splitk;
   int64_t total, splitk_bytes;
   BwdScratch(const Sizes& s, char* p) {
-    char* p0 = p;
+    int64_t off = 0;  // (p == nullptr: a size query, no address is formed)
+    auto take = [&](int64_t n) { char* q = p ? p + off : nullptr; off += n; return q; };
+    const int64_t norm_ws = al(sd_rmsnorm_bwd_workspace_bytes(s.M, s.h));
     for (int i = 0; i < 2; ++i) {
-      dxa[i] = p; p += s.x;
-      dxb[i] = p; p += s.x;
-      dqkv[i] = p; p += s.qkv;
-      dgu[i] = p; p += s.gu;
-      ws_norm2[i] = p; p += al(sd_rmsnorm_bwd_workspace_bytes(s.M, s.h));
-      ws_qk[i] = p; p += al(sd_qknorm_rope_bwd_workspace_bytes(s.M, s.Hq, s.Hkv));
-      ws_norm1[i] = p; p += al(sd_rmsnorm_bwd_workspace_bytes(s.M, s.h));
+      dxa[i] = take(s.x); dxb[i] = take(s.x); dqkv[i] = take(s.qkv); dgu[i] = take(s.gu);
+      ws_norm2[i] = take(norm_ws);
+      ws_qk[i] = take(al(sd_qknorm_rope_bwd_workspace_bytes(s.M, s.Hq, s.Hkv)));
+      ws_norm1[i] = take(norm_ws);
     }
-    dxn = p; p += s.x;
-    dqk = p; p += s.qk;
-    dao = p; p += s.ao;
-    delta = p; p += s.lse;
-    dact = p; p += s.act;
-    ws_norm = p; p += al(sd_rmsnorm_bwd_workspace_bytes(s.M, s.h));
+    dxn = take(s.x); dqk = take(s.qk); dao = take(s.ao); delta = take(s.lse); dact = take(s.act);
+    ws_norm = take(norm_ws);
     splitk_bytes = sd_gemm_splitk_workspace_bytes(s.M, s.h, s.V);
     for (int k : {s.QKV, 2 * s.I, s.QD, s.I}) {
       const int64_t b1 = sd_gemm_splitk_workspace_bytes(s.M, s.h, k);
       splitk_bytes = b1 > splitk_bytes ? b1 : splitk_bytes;
     }
-    ws_splitk = p; p += al(splitk_bytes);
-    total = p - p0;
+    ws_splitk = take(al(splitk_bytes));
+    total = off;
   }
 };
 
@@ -146,17 +133,25 @@ struct KvSink {
   }
 };
 
+// the query heads per kv head the cache attention kernels serve (0, or the code to return)
+int gqa_check(const sd_qwen3_dims* d) {
+  if (d->n_kv <= 0 || d->n_q % d->n_kv) return SD_ERR_SHAPE;
+  const int G = d->n_q / d->n_kv;
+  return G != 1 && G != 2 && G != 4 ? SD_ERR_UNSUPPORTED : 0;
+}
+
 // the checked arguments of the paged runner entries -> a KvSink over the pool (0, or the code to return)
 int paged_sink(const sd_qwen3_dims* d, const sd_kv_pages* kv, KvSink* sink) {
   if (!kv || !kv->pool || !kv->table || kv->n_pages <= 0 || kv->max_pages <= 0 || kv->max_pages > (1 << 22))
     return SD_ERR_SHAPE;
   if (kv->pool_bytes < sd_kvpool_bytes(d, kv->n_pages)) return SD_ERR_WORKSPACE;
-  *sink = KvSink{(char*)kv->pool, kv->max_pages * SD_KV_PAGE};
-  sink->table = kv->table;
-  sink->n_pages = kv->n_pages;
-  sink->max_pages = kv->max_pages;
+  *sink = KvSink{(char*)kv->pool, kv->max_pages * SD_KV_PAGE, nullptr, nullptr, kv->table, kv->n_pages, kv->max_pages};
   return 0;
 }
+
+// "The fused entry, or the two-kernel form when it answers SD_ERR_UNSUPPORTED": rc is what the fused entry returned
+template <class F>
+int fused_or(int rc, F two_kernel_form) { return rc == SD_ERR_UNSUPPORTED ? two_kernel_form() : rc; }
 
 // One decoder layer (HF modeling_qwen3.py:227-250): a.x_in -> x_out, every intermediate into `a`.  x_out == nullptr
 // stops after the SwiGLU (the backward's recompute does not need the layer output again); keep_gu: gate|up is kept
@@ -171,14 +166,11 @@ int layer_forward(const sd_qwen3_dims* d, const Sizes& s, const LayerActs& a, co
   const int Trope = extend ? s.M : T;  // per-token tables: row m of them belongs to token m
   RUN(sd_rmsnorm_fwd(a.x_in, w.ln1, a.xn1, (float*)a.rstd1, s.M, s.h, d->eps, stream));
   // q|k|v projection with q/k-norm + RoPE in the GEMM epilogue (one head = one 128-column tile)
-  int rc = sd_gemm_qkv_rope(a.xn1, w.wqkv, a.qkv, a.qk, w.q_gain, w.k_gain, cos_tab, sin_tab, s.M, Trope, s.Hq, s.Hkv,
-                            s.h, d->eps, stream);
-  if (rc == SD_ERR_UNSUPPORTED) {
+  RUN(fused_or(sd_gemm_qkv_rope(a.xn1, w.wqkv, a.qkv, a.qk, w.q_gain, w.k_gain, cos_tab, sin_tab, s.M, Trope, s.Hq, s.Hkv, s.h,
+                                d->eps, stream), [&] {
     RUN(sd_gemm_bf16(a.xn1, w.wqkv, a.qkv, nullptr, s.M, s.QKV, s.h, s.h, s.h, s.QKV, 0, 0, 0, stream));
-    RUN(sd_qknorm_rope_fwd(a.qkv, w.q_gain, w.k_gain, cos_tab, sin_tab, a.qk, s.M, Trope, s.Hq, s.Hkv, d->eps, stream));
-  } else if (rc) {
-    return rc;
-  }
+    return sd_qknorm_rope_fwd(a.qkv, w.q_gain, w.k_gain, cos_tab, sin_tab, a.qk, s.M, Trope, s.Hq, s.Hkv, d->eps, stream);
+  }));
   if (extend) {
     RUN(sink->extend(s, l, a.qk, a.qkv, a.ao, B, T, stream));
   } else {
@@ -190,15 +182,13 @@ int layer_forward(const sd_qwen3_dims* d, const Sizes& s, const LayerActs& a, co
   // gate|up projection: SwiGLU runs in the GEMM epilogue when gate|up need not be kept (no backward follows:
   // the frozen teacher).  With the 2*I-wide store as well the fused epilogue is no faster than the separate
   // elementwise pass (tests/bench_fused.py), so the student keeps the two-kernel form.
-  rc = (keep_gu && !g_sd_debug.model_fuse_student_swiglu)
-           ? SD_ERR_UNSUPPORTED
-           : sd_gemm_swiglu(a.xn2, w.wgu, keep_gu ? a.gu : nullptr, a.act, s.M, s.I, s.h, stream);
-  if (rc == SD_ERR_UNSUPPORTED) {
+  const int rc = (keep_gu && !g_sd_debug.model_fuse_student_swiglu)
+                     ? SD_ERR_UNSUPPORTED
+                     : sd_gemm_swiglu(a.xn2, w.wgu, keep_gu ? a.gu : nullptr, a.act, s.M, s.I, s.h, stream);
+  RUN(fused_or(rc, [&] {
     RUN(sd_gemm_bf16(a.xn2, w.wgu, a.gu, nullptr, s.M, 2 * s.I, s.h, s.h, s.h, 2 * s.I, 0, 0, 0, stream));
-    RUN(sd_swiglu_fwd(a.gu, a.act, s.M, s.I, stream));
-  } else if (rc) {
-    return rc;
-  }
+    return sd_swiglu_fwd(a.gu, a.act, s.M, s.I, stream);
+  }));
   if (!x_out) return 0;
   RUN(sd_gemm_bf16(a.act, w.wdown, x_out, a.x_mid, s.M, s.h, s.I, s.I, s.I, s.h, s.h, 0, 0, stream));
   return 0;
@@ -280,11 +270,287 @@ int head_dw_strip(const void* dY, const void* X, void* dW, int lo, int hi, int l
   return 0;
 }
 
-}  // namespace
+// what lies behind the layers' buffers in `acts`: written by the head of every forward, read again by the backward
+struct Tail {
+  char *x_last, *rstd_f, *xn_f, *xn_rows;  // (xn_rows: the head rows gathered)
+  Tail(const Sizes& s, char* p) : x_last(p), rstd_f(p + s.x), xn_f(rstd_f + s.rstd), xn_rows(xn_f + s.x) {}
+};
 
-namespace {
+// ------------------------------------------------------------------------------------------------ the student backward
+// The context of one sd_qwen3_backward call and the steps over it.  `stream` ("main") carries the dX chain; weight-gradient
+// GEMMs and gain reduces go to the side stream when the caller gives one, ordered by the events of sd_events.h (SdBwdEvent).
+struct Bwd {
+  const sd_qwen3_dims* d;
+  const sd_qwen3_params *p, *g;
+  const sd_qwen3_batch& bt;
+  const sd_qwen3_bwd_opts& o;
+  const Sizes& s;
+  const BwdScratch& b;
+  char* acts; int save;  // the forward's activations, kept in mode `save`
+  void *dlogits, *stream;
+  Tail tail{s, acts + s.body(save)};
+  void* wstream = o.side_stream ? o.side_stream : stream;  // where weight-gradient GEMMs go
+  int acc = (o.flags & SD_BWD_ACCUMULATE) ? 1 : 0;         // add to the gradient buffers
+  bool dw = !(o.flags & SD_BWD_EMBED_ONLY);                // per-layer weight and gain gradients wanted (false: Stage-1)
+  // A/B switch for measurements ("model.overlap_mask", sd_hip_debug.h; default all on): bit0 lm_head dW, bit1 gain
+  // reduces, bit2 attention dQ beside the main stream; bit3 the layer's four dW as one grouped launch (else `separate`:
+  // four GEMMs launched as their inputs appear); bit4 one batched gain-gradient reduce per layer
+  int ovl = g_sd_debug.model_overlap_mask;
+  bool head_dw_beside = ovl & 1, gains_beside = (ovl & 2) && dw, dq_beside = ovl & 4, grouped = dw && (ovl & 8),
+       separate = dw && !grouped, batch_gains = grouped && (ovl & 16);
+  SdStreamOrder ord;
+  int nsp = 1;       // live split-K slab count: what the last sd_gemm_bf16_splitk_partial left for the next norm backward
+  int pending = -1;  // layer whose grouped dW is in flight on the side stream (hand_over, layer_dx_out, bwd_drain)
+  const void* accp(const void* ptr) const { return acc ? ptr : nullptr; }  // the residual operand of an accumulating GEMM
+  void ready(int stage) const { if (o.on_grads_ready) o.on_grads_ready(stage, o.cb_user); }
+};
+
+// One layer's view of the context.  The buffers the weight-gradient GEMMs read exist twice (BwdScratch), used by parity P.
+static const sd_qwen3_layer kNoGrads = {};
+enum { kDwQkv, kDwGu, kDwDown, kDwO };
+struct BwdLayer {
+  const Bwd& c;
+  int l, P = l & 1;
+  char *dx_in = c.b.dxa[P], *dx_out = (l == 0 && c.o.dx0_out) ? (char*)c.o.dx0_out : c.b.dxa[P ^ 1];
+  char *dxb = c.b.dxb[P], *dqkv = c.b.dqkv[P], *dgu = c.b.dgu[P];
+  LayerActs a = layer_acts(c.s, c.acts, l, c.save);
+  const sd_qwen3_layer &w = c.p->layers_host[l], &gw = c.dw ? c.g->layers_host[l] : kNoGrads;  // Stage-1: g->layers_host may be NULL
+  // the layer's weight gradients dW [M,N] (+)= dY^T . X over the s.M tokens, in grouped-launch order
+  sd_gemm_problem pr[4] = {
+      {dqkv, a.xn1, gw.wqkv, c.s.QKV, c.s.h, c.s.h, c.s.QKV, c.s.h},    // dW_qkv  [QKV,h]  = dqkv^T . xn1
+      {dgu, a.xn2, gw.wgu, 2 * c.s.I, c.s.h, c.s.h, 2 * c.s.I, c.s.h},  // dW_gu   [2I,h]   = dgu^T  . xn2
+      {dx_in, a.act, gw.wdown, c.s.h, c.s.I, c.s.I, c.s.h, c.s.I},      // dW_down [h,I]    = dx_in^T . act
+      {dxb, a.ao, gw.wo, c.s.h, c.s.QD, c.s.QD, c.s.h, c.s.QD}};        // dW_o    [h,QD]   = dxb^T  . ao
+};
+
+// RMSNorm backward of the gradient in b.dxn, or of the split-K slabs its producer left (c.nsp > 1: summed in the kernel)
+int norm_bwd(const Bwd& c, const void* x, const void* w, const char* rstd, const void* dres, void* dx, void* dwp, void* ws,
+             void* rs, void* ev) {
+  if (c.nsp > 1)
+    return sd_rmsnorm_bwd_slabs((const float*)c.b.ws_splitk, c.nsp, x, w, (const float*)rstd, dres, dx, dwp, c.acc, ws, c.s.M,
+                                c.s.h, rs, ev, c.stream);
+  return sd_rmsnorm_bwd2(c.b.dxn, x, w, (const float*)rstd, dres, dx, dwp, c.acc, ws, c.s.M, c.s.h, rs, ev, c.stream);
+}
+
+// one weight gradient as a plain TN GEMM over K rows
+int dw_gemm(const Bwd& c, const sd_gemm_problem& q, int K, void* stream) {
+  return sd_gemm_bf16(q.A, q.B, q.C, c.accp(q.C), q.M, q.N, K, q.lda, q.ldb, q.ldc, q.ldc, 1, 1, stream);
+}
+// The separate-GEMM schedule launches each weight gradient as soon as its input is final: main says so (`ev`, see
+// SdBwdEvent), the side stream waits, the GEMM follows there.  In the other schedules both are no-ops.
+int input_final(const Bwd& c, int ev) { return c.separate ? c.ord.side_waits_for_main(ev) : 0; }
+int dw_separate(const Bwd& c, const sd_gemm_problem& q) { return c.separate ? dw_gemm(c, q, c.s.M, c.wstream) : 0; }
+
+// lm_head: dxn = dlogits . W ; dW (+)= dlogits^T . xn_f ; then the final norm's backward -> the last layer's dx_in
+int bwd_head(Bwd& c) {
+  const Sizes& s = c.s; const BwdScratch& b = c.b;
+  const int top = (s.L - 1) & 1;  // buffer set of the last layer (the first one the backward visits)
+  // dlogits (produced on main by the caller) is final: lm_head dW runs beside lm_head dX
+  RUN(c.ord.side_waits_for_main(kEvGradIn));
+  // with head rows, dlogits holds only the n_head_rows rows the forward produced; every other row of d(xn_f) is zero
+  const void* xs = c.bt.head_rows ? c.tail.xn_rows : c.tail.xn_f;
+  const int K = c.bt.head_rows ? c.bt.n_head_rows : s.M;
+  void* hs = c.head_dw_beside ? c.wstream : c.stream;
+  auto head_dw = [&](int r0) {  // dW rows [r0, V) (+)= dlogits[:, r0:]^T . xs
+    char* gh = (char*)c.g->lm_head + (int64_t)r0 * s.h * 2;
+    return dw_gemm(c, {(const char*)c.dlogits + (int64_t)r0 * 2, xs, gh, s.V, s.h, s.h, s.V - r0, s.h}, K, hs);
+  };
+  if (c.dw) {
+    RUN(head_dw(0));
+  } else {
+    // Stage-1: dW of the new rows only.  The GEMM starts at the first multiple of 8 at or above grad_row_lo (16-byte
+    // aligned operands); the < 8 rows before it take the strip kernel.
+    const int lo = c.o.grad_row_lo, lo8 = ((lo + 7) & ~7) < s.V ? ((lo + 7) & ~7) : s.V;
+    if (lo8 < s.V) RUN(head_dw(lo8));
+    RUN(head_dw_strip(c.dlogits, xs, c.g->lm_head, lo, lo8, s.V, s.h, K, c.acc, hs));
+  }
+  if (c.bt.head_rows) {
+    RUN(sd_gemm_bf16_splitk(c.dlogits, c.p->lm_head, b.dxb[top], nullptr, K, s.h, s.V, s.V, s.h, s.h, 0, 0, 1, b.ws_splitk,
+                            b.splitk_bytes, c.stream));
+    RUN(sd_rows_scatter(b.dxb[top], c.bt.head_rows, b.dxn, K, s.M, s.h, c.stream));
+  } else {
+    RUN(sd_gemm_bf16_splitk_partial(c.dlogits, c.p->lm_head, b.dxn, s.M, s.h, s.V, s.V, s.h, s.h, 0, 1, b.ws_splitk,
+                                    b.splitk_bytes, &c.nsp, c.stream));
+  }
+  if (c.g->embed != c.g->lm_head && !c.acc) {
+    const int64_t r0 = c.dw ? 0 : c.o.grad_row_lo;
+    if (hipMemsetAsync((char*)c.g->embed + r0 * s.h * 2, 0, (size_t)(s.V - r0) * s.h * 2, (hipStream_t)c.stream) != hipSuccess)
+      return SD_ERR_WORKSPACE;
+  }
+  RUN(norm_bwd(c, c.tail.x_last, c.p->final_norm, c.tail.rstd_f, nullptr, b.dxa[top], c.dw ? c.g->final_norm : nullptr,
+               b.ws_norm, nullptr, nullptr));
+  RUN(c.ord.main_waits_for_side(kEvSideDrained));  // the lm_head dW is enqueued and joined before it is reported
+  c.ready(SD_STAGE_HEAD);
+  return 0;
+}
+
+// The layer's dX chain from dx_in down to d(q|k|v): MLP, post-attention norm, o projection, attention, q/k-norm + RoPE
+int layer_dx(Bwd& c, const BwdLayer& y) {
+  const Sizes& s = c.s; const BwdScratch& b = c.b; const LayerActs& a = y.a;
+  // recompute: this work set was last read by the dW GEMMs of layer l+2, which main has waited for (layer l+1's join)
+  if (c.save == SD_SAVE_LAYER_INPUTS && y.l != s.L - 1) RUN(layer_forward(c.d, s, a, y.w, nullptr, true, c.bt, c.stream));
+  RUN(input_final(c, kEvGradIn));
+  RUN(dw_separate(c, y.pr[kDwDown]));
+  // d(act) = dx_in . W_down with the SwiGLU backward in the epilogue: d(act) itself never reaches HBM
+  RUN(fused_or(sd_gemm_swiglu_bwd(y.dx_in, y.w.wdown, a.gu, y.dgu, s.M, s.I, s.h, c.stream), [&] {
+    RUN(sd_gemm_bf16(y.dx_in, y.w.wdown, b.dact, nullptr, s.M, s.I, s.h, s.h, s.I, s.I, 0, 0, 1, c.stream));
+    return sd_swiglu_bwd(b.dact, a.gu, y.dgu, s.M, s.I, c.stream);
+  }));
+  RUN(input_final(c, kEvDgu));
+  RUN(sd_gemm_bf16_splitk_partial(y.dgu, y.w.wgu, b.dxn, s.M, s.h, 2 * s.I, 2 * s.I, s.h, s.h, 0, 1, b.ws_splitk,
+                                  b.splitk_bytes, &c.nsp, c.stream));
+  RUN(dw_separate(c, y.pr[kDwGu]));
+  // gain gradient: reduced from the kernel's partial sums beside the main stream (lent event), or left to gain_reduce
+  RUN(norm_bwd(c, a.x_mid, y.w.ln2, a.rstd2, y.dx_in, y.dxb, c.batch_gains ? nullptr : y.gw.ln2, b.ws_norm2[y.P],
+               c.gains_beside ? c.o.side_stream : nullptr, c.dw ? c.ord.event(kEvLentNorm) : nullptr));
+  RUN(input_final(c, kEvDxb));
+  // d(attention output) = dxb . Wo with delta = rowsum(dO * O) in the epilogue (one 128-column tile = one head)
+  const void* o_for_delta = nullptr;
+  RUN(fused_or(sd_gemm_odx_delta(y.dxb, y.w.wo, b.dao, a.ao, s.QD, (float*)b.delta, s.M, c.bt.T, s.Hq, s.h, c.stream), [&] {
+    o_for_delta = a.ao;
+    return sd_gemm_bf16(y.dxb, y.w.wo, b.dao, nullptr, s.M, s.QD, s.h, s.h, s.QD, s.QD, 0, 0, 1, c.stream);
+  }));
+  RUN(dw_separate(c, y.pr[kDwO]));
+  const SdQkv f(s, a.qk, a.qkv), df(s, b.dqk, y.dqkv);
+  void* dq_stream = c.dq_beside ? c.o.side_stream : nullptr;
+  if (c.bt.vl)
+    RUN(sd_attn_bwd_varlen(f.q, f.k, f.v, o_for_delta, b.dao, (const float*)a.lse, (float*)b.delta, df.q, df.k, df.v, c.bt.vl,
+                           s.QK, s.QK, s.QKV, s.QD, s.QK, s.QK, s.QKV, s.M, s.Hq, s.Hkv, 128, kSdAttnScale, dq_stream,
+                           c.stream));
+  else
+    RUN(sd_attn_bwd2(f.q, f.k, f.v, o_for_delta, b.dao, (const float*)a.lse, (float*)b.delta, df.q, df.k, df.v, c.bt.kv_len,
+                     s.QK, s.QK, s.QKV, s.QD, s.QK, s.QK, s.QKV, c.bt.B, c.bt.T, s.Hq, s.Hkv, 128, kSdAttnScale, dq_stream,
+                     c.stream));
+  void *dq_gain = c.batch_gains ? nullptr : y.gw.q_gain, *dk_gain = c.batch_gains ? nullptr : y.gw.k_gain;
+  return sd_qknorm_rope_bwd2(b.dqk, a.qkv, y.w.q_gain, y.w.k_gain, c.bt.cos_tab, c.bt.sin_tab, y.dqkv, dq_gain, dk_gain, c.acc,
+                             b.ws_qk[y.P], s.M, c.bt.T, s.Hq, s.Hkv, c.d->eps, c.gains_beside ? c.o.side_stream : nullptr,
+                             c.dw ? c.ord.event(kEvLentQkNorm) : nullptr, c.stream);
+}
+
+// The layer's weight gradients, now that d(q|k|v) -- and with it dx_in, dgu, dxb of this layer -- is final.  Grouped: all
+// four as ONE persistent launch (sd_gemm_grouped_tn: 926 vs 587 TFLOP/s for four separate launches) on the side stream,
+// i.e. under the dX chain of the NEXT layer.  Separate: the last of the four GEMMs, the others are already enqueued.
+int layer_dw(const Bwd& c, const BwdLayer& y) {
+  if (!c.dw) return 0;
+  RUN(c.ord.side_waits_for_main(kEvDqkv));
+  if (!c.grouped) return dw_gemm(c, y.pr[kDwQkv], c.s.M, c.wstream);
+  RUN(fused_or(sd_gemm_grouped_tn(y.pr, 4, c.s.M, c.acc, c.wstream), [&] {
+    for (const sd_gemm_problem& q : y.pr) RUN(dw_gemm(c, q, c.s.M, c.wstream));
+    return 0;
+  }));
+  // the layer is finished on the side stream here, unless its batched gain reduce is still to come (gain_reduce)
+  return c.batch_gains ? 0 : c.ord.record_on_side(kEvLayerDone + y.P);
+}
+
+// d(q|k|v) -> dx_out: q|k|v projection dX, then the input norm's backward.  dx_out of layer l is dx_in of layer l+1, so
+// main first waits for the dW GEMMs that still read it: grouped, the launch of layer l+1 (`pending`, by the event it
+// recorded); separate, this layer's own four (dx_in, dgu, dxb, dqkv are reused too), done before the callback as well.
+int layer_dx_out(Bwd& c, const BwdLayer& y) {
+  const Sizes& s = c.s;
+  RUN(sd_gemm_bf16_splitk_partial(y.dqkv, y.w.wqkv, c.b.dxn, s.M, s.h, s.QKV, s.QKV, s.h, s.h, 0, 1, c.b.ws_splitk,
+                                  c.b.splitk_bytes, &c.nsp, c.stream));
+  if (c.grouped && c.pending >= 0) RUN(c.ord.main_waits_for_record(kEvLayerDone + (c.pending & 1)));
+  if (c.separate) RUN(c.ord.main_waits_for_side(kEvSideDrained));
+  return norm_bwd(c, y.a.x_in, y.w.ln1, y.a.rstd1, y.dxb, y.dx_out, c.batch_gains ? nullptr : y.gw.ln1,
+                  c.batch_gains ? c.b.ws_norm1[y.P] : c.b.ws_norm, nullptr, nullptr);
+}
+
+// batch_gains: ONE reduce finishes the layer's four gain gradients on the side stream, behind the layer's grouped dW
+int gain_reduce(const Bwd& c, const BwdLayer& y) {
+  if (!c.batch_gains) return 0;
+  const Sizes& s = c.s;
+  RUN(c.ord.side_waits_for_main(kEvGainPartials));  // the last partials (input norm) are enqueued on main
+  const int nb_n = sd_rmsnorm_bwd_partial_rows(s.M, s.h), nb_q = sd_qknorm_rope_bwd_partial_rows(s.M, s.Hq, s.Hkv);
+  const sd_colsum_problem cp[4] = {{(const float*)c.b.ws_norm2[y.P], y.gw.ln2, nb_n, s.h, s.h, c.acc},
+                                   {(const float*)c.b.ws_norm1[y.P], y.gw.ln1, nb_n, s.h, s.h, c.acc},
+                                   {(const float*)c.b.ws_qk[y.P], y.gw.q_gain, nb_q, 128, 256, c.acc},
+                                   {(const float*)c.b.ws_qk[y.P] + 128, y.gw.k_gain, nb_q, 128, 256, c.acc}};
+  RUN(sd_colsum_reduce_batch(cp, 4, c.wstream));
+  return c.ord.record_on_side(kEvLayerDone + y.P);  // now covers the weight AND the gain gradients of the layer
+}
+
+// Reports finished layers to the caller.  A grouped layer is still in flight when its chain ends: it becomes `pending` and
+// is reported by the next layer, which has made main wait for it (layer_dx_out) (layer 0: by bwd_drain).
+void hand_over(Bwd& c, int l) {
+  if (!c.grouped) { if (c.dw) c.ready(l); return; }
+  if (c.pending >= 0) c.ready(c.pending);
+  c.pending = l;
+}
+
+int bwd_drain(Bwd& c) {
+  if (c.grouped && c.pending >= 0) {
+    RUN(c.ord.main_waits_for_record(kEvLayerDone + (c.pending & 1)));  // layer 0's grouped dW, before it is reported
+    c.ready(c.pending);
+  }
+  return c.ord.main_waits_for_side(kEvSideDrained);  // all the side stream was given (gain reduces, dQ), before the call returns
+}
+
+struct DecodeActs {
+  char *x, *x_mid, *xn, *qkv, *q, *ao, *gu, *act, *ws;
+  int64_t ws_bytes, total;
+  DecodeActs(const sd_qwen3_dims* d, int B, int cap, char* p) {
+    const Sizes s(d, B, 1);
+    int64_t off = 0;  // (p == nullptr: a size query, no address is formed)
+    auto take = [&](int64_t n) { char* q = p ? p + off : nullptr; off += n; return q; };
+    x = take(s.x); x_mid = take(s.x); xn = take(s.x); qkv = take(s.qkv); q = take(s.ao); ao = take(s.ao);
+    gu = take(s.gu); act = take(s.act);
+    ws_bytes = sd_attn_decode_workspace_bytes(B, s.Hq, cap);
+    ws = take(al(ws_bytes));
+    total = off;
+  }
+};
+
+// true when every GEMV of a skinny step accepts its shape: decided for the whole step before the first launch
+bool skinny_step_ok(const sd_qwen3_params* p, const Sizes& s, const DecodeActs& a, const void* logits, int B) {
+  bool ok = sd_gemv_check(a.x, p->lm_head, logits, nullptr, p->final_norm, B, s.V, s.h, s.h, s.h, s.V, 0) == 0;
+  for (int l = 0; ok && l < s.L; ++l) {
+    const sd_qwen3_layer& w = p->layers_host[l];
+    ok = sd_gemv_check(a.x, w.wqkv, a.qkv, nullptr, w.ln1, B, s.QKV, s.h, s.h, s.h, s.QKV, 0) == 0 &&
+         sd_gemv_check(a.ao, w.wo, a.x_mid, a.x, nullptr, B, s.h, s.QD, s.QD, s.QD, s.h, s.h) == 0 &&
+         sd_gemv_check(a.x_mid, w.wgu, a.act, nullptr, w.ln2, B, s.I, s.h, s.h, s.h, s.I, 0) == 0 &&
+         sd_gemv_check(a.act, w.wdown, a.x, a.x_mid, nullptr, B, s.h, s.I, s.I, s.I, s.h, s.h) == 0;
+  }
+  return ok;
+}
+
+// the launches of a decode step over either kind of cache; every argument was checked by the entry
+int decode_step_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* pos, int max_len,
+                     const void* cos_tab, const void* sin_tab, const KvSink& kv, const Sizes& s, const DecodeActs& a,
+                     void* logits, int B, int flags, void* stream) {
+  const bool skinny = (flags & SD_DECODE_SKINNY) && skinny_step_ok(p, s, a, logits, B);
+  RUN(sd_embedding_fwd(ids, p->embed, a.x, B, s.h, s.V, stream));
+  if (skinny) {
+    for (int l = 0; l < s.L; ++l) {
+      const sd_qwen3_layer& w = p->layers_host[l];
+      RUN(sd_gemv_bf16(a.x, w.wqkv, a.qkv, nullptr, w.ln1, d->eps, B, s.QKV, s.h, s.h, s.h, s.QKV, 0, stream));
+      RUN(kv.step(s, l, w, a.qkv, a.q, a.ao, cos_tab, sin_tab, pos, a.ws, a.ws_bytes, B, max_len, d->eps, stream));
+      RUN(sd_gemv_bf16(a.ao, w.wo, a.x_mid, a.x, nullptr, 0.f, B, s.h, s.QD, s.QD, s.QD, s.h, s.h, stream));
+      RUN(sd_gemv_swiglu(a.x_mid, w.wgu, a.act, w.ln2, d->eps, B, s.I, s.h, stream));
+      RUN(sd_gemv_bf16(a.act, w.wdown, a.x, a.x_mid, nullptr, 0.f, B, s.h, s.I, s.I, s.I, s.h, s.h, stream));
+    }
+    return sd_gemv_bf16(a.x, p->lm_head, logits, nullptr, p->final_norm, d->eps, B, s.V, s.h, s.h, s.h, s.V, 0, stream);
+  }
+  for (int l = 0; l < s.L; ++l) {
+    const sd_qwen3_layer& w = p->layers_host[l];
+    RUN(sd_rmsnorm_fwd(a.x, w.ln1, a.xn, nullptr, B, s.h, d->eps, stream));
+    RUN(sd_gemm_bf16(a.xn, w.wqkv, a.qkv, nullptr, B, s.QKV, s.h, s.h, s.h, s.QKV, 0, 0, 0, stream));
+    RUN(kv.step(s, l, w, a.qkv, a.q, a.ao, cos_tab, sin_tab, pos, a.ws, a.ws_bytes, B, max_len, d->eps, stream));
+    RUN(sd_gemm_bf16(a.ao, w.wo, a.x_mid, a.x, B, s.h, s.QD, s.QD, s.QD, s.h, s.h, 0, 0, stream));
+    RUN(sd_rmsnorm_fwd(a.x_mid, w.ln2, a.xn, nullptr, B, s.h, d->eps, stream));
+    RUN(fused_or(sd_gemm_swiglu(a.xn, w.wgu, nullptr, a.act, B, s.I, s.h, stream), [&] {
+      RUN(sd_gemm_bf16(a.xn, w.wgu, a.gu, nullptr, B, 2 * s.I, s.h, s.h, s.h, 2 * s.I, 0, 0, 0, stream));
+      return sd_swiglu_fwd(a.gu, a.act, B, s.I, stream);
+    }));
+    RUN(sd_gemm_bf16(a.act, w.wdown, a.x, a.x_mid, B, s.h, s.I, s.I, s.I, s.h, s.h, 0, 0, stream));
+  }
+  RUN(sd_rmsnorm_fwd(a.x, p->final_norm, a.xn, nullptr, B, s.h, d->eps, stream));
+  return sd_gemm_bf16(a.xn, p->lm_head, logits, nullptr, B, s.V, s.h, s.h, s.h, s.V, 0, 0, 0, stream);
+}
+
+// the event pool of sd_events.h
 std::mutex g_ev_mu;
 std::vector<SdEventSet*> g_ev_free;
+
 }  // namespace
 
 SdEventSet* sd_lease_events() {
@@ -351,14 +617,10 @@ static int forward_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const 
   }
   if (acts_bytes < sd_qwen3_acts_bytes(d, B, T, save)) return SD_ERR_WORKSPACE;
   char* base = (char*)acts;
-  char* tail = base + s.body(save);
-  char* x_last = tail;
-  char* rstd_f = tail + s.x;
-  char* xn_f = rstd_f + s.rstd;
-  char* xn_rows = xn_f + s.x;
+  const Tail t(s, base + s.body(save));
   char* pong = base + s.per_layer();  // inference only
-  float* ssq_a = (float*)(tail + s.tail());  // folded inference only
-  float* ssq_b = (float*)(tail + s.tail() + s.ssq());
+  float* ssq_a = (float*)(t.x_last + s.tail());  // folded inference only
+  float* ssq_b = (float*)(t.x_last + s.tail() + s.ssq());
 
   char* x_cur = save ? layer_acts(s, base, 0, save).x_in : base;
   if (folded) RUN(sd_embedding_fwd_ssq(bt->ids, p->embed, x_cur, ssq_a, s.M, s.h, s.V, stream));
@@ -370,8 +632,8 @@ static int forward_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const 
     const int lim = save ? g_sd_debug.model_shared_layers_train : g_sd_debug.model_shared_layers;
     SdSharedGpuScope shared(concurrent && (lim < 0 || l < lim) ? 1 : 0);
     char* x_out;
-    if (save) x_out = (l + 1 < s.L) ? layer_acts(s, base, l + 1, save).x_in : x_last;
-    else x_out = (l + 1 < s.L) ? ((x_cur == pong) ? base : pong) : x_last;
+    if (save) x_out = (l + 1 < s.L) ? layer_acts(s, base, l + 1, save).x_in : t.x_last;
+    else x_out = (l + 1 < s.L) ? ((x_cur == pong) ? base : pong) : t.x_last;
     if (folded)
       RUN(layer_forward_folded(d, s, a, p->layers_host[l], x_out, *bt, ssq_a, ssq_b, l + 1 < s.L ? ssq_a : nullptr,
                                stream));
@@ -379,7 +641,7 @@ static int forward_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const 
       RUN(layer_forward(d, s, a, p->layers_host[l], x_out, save != SD_SAVE_NONE, *bt, stream, sink, l));
     x_cur = x_out;
   }
-  return sd_head_fwd(d, s, *bt, x_last, p->final_norm, p->lm_head, rstd_f, xn_f, xn_rows, logits, stream);
+  return sd_head_fwd(d, s, *bt, t.x_last, p->final_norm, p->lm_head, t.rstd_f, t.xn_f, t.xn_rows, logits, stream);
 }
 
 extern "C" int sd_qwen3_forward(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_batch* batch, void* acts,
@@ -387,9 +649,8 @@ extern "C" int sd_qwen3_forward(const sd_qwen3_dims* d, const sd_qwen3_params* p
   return forward_impl(d, p, batch, acts, acts_bytes, logits, mode, stream, nullptr);
 }
 
-// The student backward.  Without SD_BWD_EMBED_ONLY: every gradient.  With it (Stage-1): the same dX chain, no per-layer
-// weight / gain gradient, the lm_head dW over rows [grad_row_lo, V) only and the embedding scatter restricted to
-// ids >= grad_row_lo.
+// The student backward: checks, context, head, layers, drain, embedding.  With SD_BWD_EMBED_ONLY (Stage-1): the same dX
+// chain, no per-layer gradient, the lm_head dW over rows [grad_row_lo, V) and the embedding scatter of ids >= grad_row_lo.
 extern "C" int sd_qwen3_backward(const sd_qwen3_dims* d, const sd_qwen3_params* p, const sd_qwen3_params* g,
                                  const sd_qwen3_batch* bt, void* acts, int64_t acts_bytes, void* dlogits, void* scratch,
                                  int64_t scratch_bytes, const sd_qwen3_bwd_opts* opts, void* stream) {
@@ -397,223 +658,54 @@ extern "C" int sd_qwen3_backward(const sd_qwen3_dims* d, const sd_qwen3_params* 
   RUN(sd_batch_check(bt));
   if (!opts) return SD_ERR_SHAPE;
   const sd_qwen3_bwd_opts& o = *opts;
-  const int accumulate = o.flags & ~SD_BWD_EMBED_ONLY, grad_row_lo = o.grad_row_lo;
-  const bool dw = !(o.flags & SD_BWD_EMBED_ONLY);  // per-layer weight and gain gradients wanted
-  void *const dx0_out = o.dx0_out, *const cb_user = o.cb_user, *const side_stream = o.side_stream;
-  const sd_stage_cb on_grads_ready = o.on_grads_ready;
-  const int64_t *const ids = bt->ids, *const head_rows = bt->head_rows;
-  const int32_t* const kv_len = bt->kv_len;
-  const sd_varlen* const vl = bt->vl;
-  const void *const cos_tab = bt->cos_tab, *const sin_tab = bt->sin_tab;
-  const int n_head_rows = bt->n_head_rows, B = bt->B, T = bt->T;
-  if (!dw && (grad_row_lo < 0 || grad_row_lo > d->vocab || dx0_out || on_grads_ready)) return SD_ERR_SHAPE;
-  if (accumulate & ~(SD_BWD_ACCUMULATE | SD_BWD_RECOMPUTE)) return SD_ERR_SHAPE;
-  Sizes s(d, B, T);
+  if ((o.flags & SD_BWD_EMBED_ONLY) && (o.grad_row_lo < 0 || o.grad_row_lo > d->vocab || o.dx0_out || o.on_grads_ready))
+    return SD_ERR_SHAPE;
+  if (o.flags & ~(SD_BWD_EMBED_ONLY | SD_BWD_ACCUMULATE | SD_BWD_RECOMPUTE)) return SD_ERR_SHAPE;
+  const Sizes s(d, bt->B, bt->T);
   // SD_BWD_RECOMPUTE: `acts` came from a forward with SD_SAVE_LAYER_INPUTS; each layer's forward is run again from its
   // saved input right before its backward (the last layer's buffers are still those of the forward itself)
-  const int save = (accumulate & SD_BWD_RECOMPUTE) ? SD_SAVE_LAYER_INPUTS : SD_SAVE_ALL;
-  if (acts_bytes < sd_qwen3_acts_bytes(d, B, T, save)) return SD_ERR_WORKSPACE;
-  BwdScratch b(s, (char*)scratch);
+  const int save = (o.flags & SD_BWD_RECOMPUTE) ? SD_SAVE_LAYER_INPUTS : SD_SAVE_ALL;
+  if (acts_bytes < sd_qwen3_acts_bytes(d, bt->B, bt->T, save)) return SD_ERR_WORKSPACE;
+  const BwdScratch b(s, (char*)scratch);
   if (scratch_bytes < b.total) return SD_ERR_WORKSPACE;
-  char* base = (char*)acts;
-  char* tail = base + s.body(save);
-  char* x_last = tail;
-  char* rstd_f = tail + s.x;
-  char* xn_f = rstd_f + s.rstd;
-  char* xn_rows = xn_f + s.x;
-  const int acc = (accumulate & SD_BWD_ACCUMULATE) ? 1 : 0;
-#define ACC(ptr) (acc ? (const void*)(ptr) : (const void*)nullptr)
-  // A/B switch for measurements ("model.overlap_mask", sd_hip_debug.h): bit0 lm_head dW, bit1 gain reduces, bit2 attention
-  // dQ, bit3 grouped per-layer dW, bit4 batched per-layer gain reduce (default all on)
-  const int ovl = g_sd_debug.model_overlap_mask;
-  hipStream_t s1 = (hipStream_t)stream, s2 = (hipStream_t)side_stream;
-  SdEventLease lease;
-  if (s2 && !(lease.set = sd_lease_events())) return SD_ERR_WORKSPACE;
-  hipEvent_t* g_ev = lease.set ? lease.set->ev : nullptr;  // this call's events
-  void* wstream = s2 ? side_stream : stream;  // where weight-gradient GEMMs go
-  SdSharedGpuScope shared(s2 ? 1 : 0);  // two streams share the GPU: the persistent dW launches leave CUs to the dX chain
-  // main -> side: "this buffer is final"; side -> main: "this layer's dW GEMMs have read their inputs"
-#define SIGNAL(i) do { if (s2) { if (hipEventRecord(g_ev[i], s1) != hipSuccess || hipStreamWaitEvent(s2, g_ev[i], 0) != hipSuccess) return SD_ERR_WORKSPACE; } } while (0)
-#define JOIN() do { if (s2) { if (hipEventRecord(g_ev[7], s2) != hipSuccess || hipStreamWaitEvent(s1, g_ev[7], 0) != hipSuccess) return SD_ERR_WORKSPACE; } } while (0)
-
-  // lm_head: dxn = dlogits . W ; dW (+)= dlogits^T . xn_f
-  const int top = (s.L - 1) & 1;  // buffer set of the last layer (the first one the backward visits)
-  SIGNAL(0);  // dlogits (produced on `stream` by the caller) is final: lm_head dW runs beside lm_head dX
-  int nsp = 1;
-  if (!dw) {
-    // Stage-1: dW of the new rows only.  The GEMM starts at the first multiple of 8 at or above grad_row_lo (16-byte
-    // aligned operands); the < 8 rows before it take the strip kernel.
-    const int lo = grad_row_lo, lo8 = ((lo + 7) & ~7) < s.V ? ((lo + 7) & ~7) : s.V;
-    const void* xs = head_rows ? (const void*)xn_rows : (const void*)xn_f;
-    const int K = head_rows ? n_head_rows : s.M;
-    void* hs = (ovl & 1) ? wstream : stream;
-    char* gh = (char*)g->lm_head;
-    if (lo8 < s.V)
-      RUN(sd_gemm_bf16((const char*)dlogits + (int64_t)lo8 * 2, xs, gh + (int64_t)lo8 * s.h * 2,
-                       ACC(gh + (int64_t)lo8 * s.h * 2), s.V - lo8, s.h, K, s.V, s.h, s.h, s.h, 1, 1, hs));
-    RUN(head_dw_strip(dlogits, xs, g->lm_head, lo, lo8, s.V, s.h, K, acc, hs));
-  }
-  if (head_rows) {
-    // dlogits holds only the n_head_rows rows the forward produced; every other row of d(xn_f) is zero
-    if (dw)
-      RUN(sd_gemm_bf16(dlogits, xn_rows, g->lm_head, ACC(g->lm_head), s.V, s.h, n_head_rows, s.V, s.h, s.h, s.h, 1, 1,
-                       (ovl & 1) ? wstream : stream));
-    RUN(sd_gemm_bf16_splitk(dlogits, p->lm_head, b.dxb[top], nullptr, n_head_rows, s.h, s.V, s.V, s.h, s.h, 0, 0, 1,
-                            b.ws_splitk, b.splitk_bytes, stream));
-    RUN(sd_rows_scatter(b.dxb[top], head_rows, b.dxn, n_head_rows, s.M, s.h, stream));
-  } else {
-    if (dw)
-      RUN(sd_gemm_bf16(dlogits, xn_f, g->lm_head, ACC(g->lm_head), s.V, s.h, s.M, s.V, s.h, s.h, s.h, 1, 1,
-                       (ovl & 1) ? wstream : stream));
-    RUN(sd_gemm_bf16_splitk_partial(dlogits, p->lm_head, b.dxn, s.M, s.h, s.V, s.V, s.h, s.h, 0, 1, b.ws_splitk,
-                                    b.splitk_bytes, &nsp, stream));
-  }
-  if (g->embed != g->lm_head && !acc) {
-    const int64_t r0 = dw ? 0 : grad_row_lo;
-    if (hipMemsetAsync((char*)g->embed + r0 * s.h * 2, 0, (size_t)(s.V - r0) * s.h * 2, (hipStream_t)stream) != hipSuccess)
-      return SD_ERR_WORKSPACE;
-  }
-  // the norm backward sums the split-K slabs itself (no separate reduce pass)
-#define NORM_BWD(X, W, RSTD, DRES, DX, DW, WS, RS, EV)                                                                   \
-  do {                                                                                                                   \
-    if (nsp > 1) RUN(sd_rmsnorm_bwd_slabs((const float*)b.ws_splitk, nsp, X, W, RSTD, DRES, DX, DW, acc, WS, s.M, s.h, RS, \
-                                          EV, stream));                                                                  \
-    else RUN(sd_rmsnorm_bwd2(b.dxn, X, W, RSTD, DRES, DX, DW, acc, WS, s.M, s.h, RS, EV, stream));                         \
-  } while (0)
-  NORM_BWD(x_last, p->final_norm, (const float*)rstd_f, nullptr, b.dxa[top], dw ? g->final_norm : nullptr, b.ws_norm, nullptr,
-           nullptr);
-  JOIN();
-  if (on_grads_ready) on_grads_ready(SD_STAGE_HEAD, cb_user);
-  // The four weight gradients of a layer run as ONE persistent grouped launch (sd_gemm_grouped_tn: 926 vs 587 TFLOP/s
-  // for four separate launches) on the side stream once the layer's dX chain has produced their inputs, i.e. under
-  // the chain of the NEXT layer; that layer joins it (event) before it overwrites the gradient buffer they share,
-  // and only then is the finished layer reported to the caller.  SD_OVERLAP_MASK bit 3 = 0 keeps four separate GEMMs
-  // launched as their inputs appear.
-  const bool grouped = dw && (ovl & 8) != 0;
-  const bool batch_gains = grouped && (ovl & 16) != 0;  // bit 4: one batched gain-gradient reduce per layer
-  int pending = -1;  // layer whose grouped dW is in flight on the side stream
+  Bwd c{d, p, g, *bt, o, s, b, (char*)acts, save, dlogits, stream};
+  RUN(c.ord.init(stream, o.side_stream));  // leases this call's events when there is a side stream
+  SdSharedGpuScope shared(c.ord.side ? 1 : 0);  // two streams share the GPU: the persistent dW launches leave CUs to the dX chain
+  RUN(bwd_head(c));
   for (int l = s.L - 1; l >= 0; --l) {
-    const int P = l & 1;
-    char *dx_in = b.dxa[P], *dx_out = (l == 0 && dx0_out) ? (char*)dx0_out : b.dxa[P ^ 1];
-    char *dxb = b.dxb[P], *dqkv = b.dqkv[P], *dgu = b.dgu[P];
-    const LayerActs a = layer_acts(s, base, l, save);
-    const sd_qwen3_layer& w = p->layers_host[l];
-    static const sd_qwen3_layer kNoGrads = {};
-    const sd_qwen3_layer& gw = dw ? g->layers_host[l] : kNoGrads;  // Stage-1: g->layers_host may be NULL
-    // recompute: this layer's work set was last read by the weight-gradient GEMMs of layer l+2, which `stream` has
-    // already waited for (the `pending` join of layer l+1 below)
-    if (save == SD_SAVE_LAYER_INPUTS && l != s.L - 1)
-      RUN(layer_forward(d, s, a, w, nullptr, true, *bt, stream));
-    // MLP
-    if (!grouped && dw) {
-      SIGNAL(0);  // dx_in final
-      RUN(sd_gemm_bf16(dx_in, a.act, gw.wdown, ACC(gw.wdown), s.h, s.I, s.M, s.h, s.I, s.I, s.I, 1, 1, wstream));
-    }
-    // d(act) = dx_in . W_down with the SwiGLU backward in the epilogue: d(act) itself never reaches HBM
-    {
-      const int rc = sd_gemm_swiglu_bwd(dx_in, w.wdown, a.gu, dgu, s.M, s.I, s.h, stream);
-      if (rc == SD_ERR_UNSUPPORTED) {
-        RUN(sd_gemm_bf16(dx_in, w.wdown, b.dact, nullptr, s.M, s.I, s.h, s.h, s.I, s.I, 0, 0, 1, stream));
-        RUN(sd_swiglu_bwd(b.dact, a.gu, dgu, s.M, s.I, stream));
-      } else if (rc) {
-        return rc;
-      }
-    }
-    if (!grouped && dw) SIGNAL(1);  // dgu final
-    RUN(sd_gemm_bf16_splitk_partial(dgu, w.wgu, b.dxn, s.M, s.h, 2 * s.I, 2 * s.I, s.h, s.h, 0, 1, b.ws_splitk,
-                                    b.splitk_bytes, &nsp, stream));
-    if (!grouped && dw) RUN(sd_gemm_bf16(dgu, a.xn2, gw.wgu, ACC(gw.wgu), 2 * s.I, s.h, s.M, 2 * s.I, s.h, s.h, s.h, 1, 1, wstream));
-    // gain gradients of the layer: the kernels leave per-workgroup partial sums, ONE batched reduce finishes all four
-    // (input norm, post-attention norm, q gain, k gain) on the side stream once the layer's last kernel is enqueued
-    NORM_BWD(a.x_mid, w.ln2, (const float*)a.rstd2, dx_in, dxb, batch_gains ? nullptr : gw.ln2, b.ws_norm2[P],
-             ((ovl & 2) && dw) ? side_stream : nullptr, (s2 && dw) ? (void*)g_ev[8] : nullptr);
-    if (!grouped && dw) SIGNAL(2);  // dxb final
-    // attention
-    // d(attention output) = dxb . Wo with delta = rowsum(dO * O) in the epilogue (one 128-column tile = one head)
-    const void* o_for_delta = a.ao;
-    {
-      const int rc = sd_gemm_odx_delta(dxb, w.wo, b.dao, a.ao, s.QD, (float*)b.delta, s.M, T, s.Hq, s.h, stream);
-      if (rc == SD_ERR_UNSUPPORTED) RUN(sd_gemm_bf16(dxb, w.wo, b.dao, nullptr, s.M, s.QD, s.h, s.h, s.QD, s.QD, 0, 0, 1, stream));
-      else if (rc) return rc;
-      else o_for_delta = nullptr;
-    }
-    if (!grouped && dw) RUN(sd_gemm_bf16(dxb, a.ao, gw.wo, ACC(gw.wo), s.h, s.QD, s.M, s.h, s.QD, s.QD, s.QD, 1, 1, wstream));
-    const SdQkv f(s, a.qk, a.qkv), df(s, b.dqk, dqkv);
-    if (vl)
-      RUN(sd_attn_bwd_varlen(f.q, f.k, f.v, o_for_delta, b.dao, (const float*)a.lse, (float*)b.delta, df.q, df.k, df.v, vl,
-                             s.QK, s.QK, s.QKV, s.QD, s.QK, s.QK, s.QKV, s.M, s.Hq, s.Hkv, 128, kSdAttnScale,
-                             (ovl & 4) ? side_stream : nullptr, stream));
-    else
-      RUN(sd_attn_bwd2(f.q, f.k, f.v, o_for_delta, b.dao, (const float*)a.lse, (float*)b.delta, df.q, df.k, df.v, kv_len,
-                       s.QK, s.QK, s.QKV, s.QD, s.QK, s.QK, s.QKV, B, T, s.Hq, s.Hkv, 128, kSdAttnScale,
-                       (ovl & 4) ? side_stream : nullptr, stream));
-    RUN(sd_qknorm_rope_bwd2(b.dqk, a.qkv, w.q_gain, w.k_gain, cos_tab, sin_tab, dqkv, batch_gains ? nullptr : gw.q_gain,
-                            batch_gains ? nullptr : gw.k_gain, acc, b.ws_qk[P], s.M, T, s.Hq, s.Hkv, d->eps,
-                            ((ovl & 2) && dw) ? side_stream : nullptr, (s2 && dw) ? (void*)g_ev[9] : nullptr, stream));
-    if (dw) SIGNAL(3);  // dqkv final (and with it dx_in, dgu, dxb of this layer)
-    if (grouped) {
-      sd_gemm_problem pr[4] = {
-          {dqkv, a.xn1, gw.wqkv, s.QKV, s.h, s.h, s.QKV, s.h},    // dW_qkv  [QKV,h]  = dqkv^T . xn1
-          {dgu, a.xn2, gw.wgu, 2 * s.I, s.h, s.h, 2 * s.I, s.h},  // dW_gu   [2I,h]   = dgu^T  . xn2
-          {dx_in, a.act, gw.wdown, s.h, s.I, s.I, s.h, s.I},      // dW_down [h,I]    = dx_in^T . act
-          {dxb, a.ao, gw.wo, s.h, s.QD, s.QD, s.h, s.QD}};        // dW_o    [h,QD]   = dxb^T  . ao
-      const int rc = sd_gemm_grouped_tn(pr, 4, s.M, acc, wstream);
-      if (rc == SD_ERR_UNSUPPORTED) {
-        for (const sd_gemm_problem& q : pr)
-          RUN(sd_gemm_bf16(q.A, q.B, q.C, acc ? q.C : nullptr, q.M, q.N, s.M, q.lda, q.ldb, q.ldc, q.ldc, 1, 1, wstream));
-      } else if (rc) {
-        return rc;
-      }
-      if (!batch_gains && s2 && hipEventRecord(g_ev[10 + P], s2) != hipSuccess) return SD_ERR_WORKSPACE;
-    } else if (dw) {
-      RUN(sd_gemm_bf16(dqkv, a.xn1, gw.wqkv, ACC(gw.wqkv), s.QKV, s.h, s.M, s.QKV, s.h, s.h, s.h, 1, 1, wstream));
-    }
-    RUN(sd_gemm_bf16_splitk_partial(dqkv, w.wqkv, b.dxn, s.M, s.h, s.QKV, s.QKV, s.h, s.h, 0, 1, b.ws_splitk,
-                                    b.splitk_bytes, &nsp, stream));
-    if (grouped) {
-      // the previous layer's grouped dW reads the buffer this layer is about to overwrite with its output gradient
-      if (pending >= 0 && s2 && hipStreamWaitEvent(s1, g_ev[10 + (pending & 1)], 0) != hipSuccess) return SD_ERR_WORKSPACE;
-    } else if (dw) {
-      JOIN();  // the layer's dW GEMMs are done before their inputs are overwritten and before the callback
-    }
-    NORM_BWD(a.x_in, w.ln1, (const float*)a.rstd1, dxb, dx_out, batch_gains ? nullptr : gw.ln1,
-             batch_gains ? b.ws_norm1[P] : b.ws_norm, nullptr, nullptr);
-    if (batch_gains) {
-      // the side stream (after this layer's grouped dW) waits for the partials, reduces, and only then marks the
-      // layer finished: the event below now covers the weight AND the gain gradients of layer l
-      if (s2 && (hipEventRecord(g_ev[6], s1) != hipSuccess || hipStreamWaitEvent(s2, g_ev[6], 0) != hipSuccess))
-        return SD_ERR_WORKSPACE;
-      const int nb_n = sd_rmsnorm_bwd_partial_rows(s.M, s.h), nb_q = sd_qknorm_rope_bwd_partial_rows(s.M, s.Hq, s.Hkv);
-      const sd_colsum_problem cp[4] = {{(const float*)b.ws_norm2[P], gw.ln2, nb_n, s.h, s.h, acc},
-                                       {(const float*)b.ws_norm1[P], gw.ln1, nb_n, s.h, s.h, acc},
-                                       {(const float*)b.ws_qk[P], gw.q_gain, nb_q, 128, 256, acc},
-                                       {(const float*)b.ws_qk[P] + 128, gw.k_gain, nb_q, 128, 256, acc}};
-      RUN(sd_colsum_reduce_batch(cp, 4, wstream));
-      if (s2 && hipEventRecord(g_ev[10 + P], s2) != hipSuccess) return SD_ERR_WORKSPACE;
-    }
-    if (grouped) {
-      if (pending >= 0 && on_grads_ready) on_grads_ready(pending, cb_user);
-      pending = l;
-    } else if (on_grads_ready && dw) {
-      on_grads_ready(l, cb_user);
-    }
+    const BwdLayer y{c, l};
+    RUN(layer_dx(c, y));
+    RUN(layer_dw(c, y));
+    RUN(layer_dx_out(c, y));
+    RUN(gain_reduce(c, y));
+    hand_over(c, l);
   }
-  if (grouped && pending >= 0) {
-    if (s2 && hipStreamWaitEvent(s1, g_ev[10 + (pending & 1)], 0) != hipSuccess) return SD_ERR_WORKSPACE;
-    if (on_grads_ready) on_grads_ready(pending, cb_user);
-  }
-  JOIN();  // everything the side stream was given (gain reduces, dQ) before the call returns
-  if (!dw) RUN(sd_embedding_bwd_range(ids, b.dxa[1], g->embed, s.M, s.h, s.V, grad_row_lo, 1.0f, stream));
-  else if (!dx0_out) RUN(sd_embedding_bwd(ids, b.dxa[1], g->embed, s.M, s.h, s.V, 1.0f, stream));
-  if (on_grads_ready) on_grads_ready(SD_STAGE_EMBED, cb_user);
-#undef ACC
-#undef NORM_BWD
-#undef SIGNAL
-#undef JOIN
+  RUN(bwd_drain(c));
+  if (!c.dw) RUN(sd_embedding_bwd_range(bt->ids, b.dxa[1], g->embed, s.M, s.h, s.V, o.grad_row_lo, 1.0f, stream));
+  else if (!o.dx0_out) RUN(sd_embedding_bwd(bt->ids, b.dxa[1], g->embed, s.M, s.h, s.V, 1.0f, stream));
+  c.ready(SD_STAGE_EMBED);
   return 0;
 }
 
 // ------------------------------------------------------------------------------------------ KV-cache generation
+// What the four block entries (prefill, extend, and their paged twins) do after their own checks: the head rows behind the
+// prefill's activation set -- for an extend (sink.past) also the gathered cos / sin rows of the block -- then the forward.
+static int block_forward(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* kv_len,
+                         const void* cos_tab, const void* sin_tab, void* acts, void* logits, int B, int T, void* stream,
+                         const KvSink& sink) {
+  const int64_t base = al(sd_qwen3_acts_bytes(d, B, T, SD_SAVE_NONE));
+  int64_t* rows = (int64_t*)((char*)acts + base);
+  RUN(sd_last_rows(sink.past ? sink.new_len : kv_len, rows, B, T, stream));
+  sd_qwen3_batch bt = {ids, kv_len, nullptr, cos_tab, sin_tab, rows, B, B, T, 0};
+  if (sink.past) {  // (an extend has no kv_len)
+    char* cos_rows = (char*)acts + al(sd_qwen3_prefill_acts_bytes(d, B, T));
+    char* sin_rows = cos_rows + al((int64_t)B * T * 128 * 2);
+    RUN(sd_rope_rows_at(cos_tab, sin_tab, sink.past, cos_rows, sin_rows, B, T, sink.cap, stream));
+    bt.cos_tab = cos_rows; bt.sin_tab = sin_rows;
+  }
+  return forward_impl(d, p, &bt, acts, base, logits, SD_SAVE_NONE, stream, &sink);
+}
+
 // (engine/llm_engine.py:37-76: prefill the prompt once, then one token per step over the cache)
 extern "C" int64_t sd_qwen3_prefill_acts_bytes(const sd_qwen3_dims* d, int B, int T) {
   const int64_t base = sd_qwen3_acts_bytes(d, B, T, SD_SAVE_NONE);
@@ -626,12 +718,7 @@ extern "C" int sd_qwen3_prefill(const sd_qwen3_dims* d, const sd_qwen3_params* p
   if (d->head_dim != 128) return SD_ERR_UNSUPPORTED;
   if (B <= 0 || T <= 0 || cap < T || !logits || !cache) return SD_ERR_SHAPE;
   if (acts_bytes < sd_qwen3_prefill_acts_bytes(d, B, T) || cache_bytes < sd_kvcache_bytes(d, B, cap)) return SD_ERR_WORKSPACE;
-  const int64_t base = al(sd_qwen3_acts_bytes(d, B, T, SD_SAVE_NONE));
-  int64_t* rows = (int64_t*)((char*)acts + base);
-  RUN(sd_last_rows(kv_len, rows, B, T, stream));
-  const KvSink sink = {(char*)cache, cap};
-  const sd_qwen3_batch bt = {ids, kv_len, nullptr, cos_tab, sin_tab, rows, B, B, T, 0};
-  return forward_impl(d, p, &bt, acts, base, logits, SD_SAVE_NONE, stream, &sink);
+  return block_forward(d, p, ids, kv_len, cos_tab, sin_tab, acts, logits, B, T, stream, KvSink{(char*)cache, cap});
 }
 
 // Carrying on from a live cache (soulxpodcast.py:342,378-380: one DynamicCache handed to llm.generate turn after turn, each
@@ -651,21 +738,9 @@ extern "C" int sd_qwen3_extend(const sd_qwen3_dims* d, const sd_qwen3_params* p,
   if (d->head_dim != 128) return SD_ERR_UNSUPPORTED;
   if (B <= 0 || T <= 0 || cap < T || !ids || !past || !new_len || !cos_tab || !sin_tab || !acts || !logits || !cache)
     return SD_ERR_SHAPE;
-  if (d->n_kv <= 0 || d->n_q % d->n_kv) return SD_ERR_SHAPE;
-  const int G = d->n_q / d->n_kv;
-  if (G != 1 && G != 2 && G != 4) return SD_ERR_UNSUPPORTED;
+  RUN(gqa_check(d));
   if (acts_bytes < sd_qwen3_extend_acts_bytes(d, B, T) || cache_bytes < sd_kvcache_bytes(d, B, cap)) return SD_ERR_WORKSPACE;
-  const int64_t base = al(sd_qwen3_acts_bytes(d, B, T, SD_SAVE_NONE));
-  int64_t* rows = (int64_t*)((char*)acts + base);
-  char* cos_rows = (char*)acts + al(sd_qwen3_prefill_acts_bytes(d, B, T));
-  char* sin_rows = cos_rows + al((int64_t)B * T * 128 * 2);
-  RUN(sd_last_rows(new_len, rows, B, T, stream));
-  RUN(sd_rope_rows_at(cos_tab, sin_tab, past, cos_rows, sin_rows, B, T, cap, stream));
-  KvSink sink = {(char*)cache, cap};
-  sink.past = past;
-  sink.new_len = new_len;
-  const sd_qwen3_batch bt = {ids, nullptr, nullptr, cos_rows, sin_rows, rows, B, B, T, 0};
-  return forward_impl(d, p, &bt, acts, base, logits, SD_SAVE_NONE, stream, &sink);
+  return block_forward(d, p, ids, nullptr, cos_tab, sin_tab, acts, logits, B, T, stream, KvSink{(char*)cache, cap, past, new_len});
 }
 
 // The two block entries over a page pool (llm_engine.py:91): the twins' launches with the paged sinks.
@@ -682,11 +757,7 @@ extern "C" int sd_qwen3_prefill_paged(const sd_qwen3_dims* d, const sd_qwen3_par
   RUN(paged_sink(d, kv, &sink));
   if (B <= 0 || T <= 0 || sink.cap < T || !logits || !ids || !acts) return SD_ERR_SHAPE;
   if (acts_bytes < sd_qwen3_prefill_acts_bytes(d, B, T)) return SD_ERR_WORKSPACE;
-  const int64_t base = al(sd_qwen3_acts_bytes(d, B, T, SD_SAVE_NONE));
-  int64_t* rows = (int64_t*)((char*)acts + base);
-  RUN(sd_last_rows(kv_len, rows, B, T, stream));
-  const sd_qwen3_batch bt = {ids, kv_len, nullptr, cos_tab, sin_tab, rows, B, B, T, 0};
-  return forward_impl(d, p, &bt, acts, base, logits, SD_SAVE_NONE, stream, &sink);
+  return block_forward(d, p, ids, kv_len, cos_tab, sin_tab, acts, logits, B, T, stream, sink);
 }
 
 extern "C" int64_t sd_qwen3_extend_paged_acts_bytes(const sd_qwen3_dims* d, int B, int T) {
@@ -703,71 +774,17 @@ extern "C" int sd_qwen3_extend_paged(const sd_qwen3_dims* d, const sd_qwen3_para
   RUN(paged_sink(d, kv, &sink));
   if (B <= 0 || T <= 0 || sink.cap < T || !ids || !past || !new_len || !cos_tab || !sin_tab || !acts || !logits)
     return SD_ERR_SHAPE;
-  if (d->n_kv <= 0 || d->n_q % d->n_kv) return SD_ERR_SHAPE;
-  const int G = d->n_q / d->n_kv;
-  if (G != 1 && G != 2 && G != 4) return SD_ERR_UNSUPPORTED;
+  RUN(gqa_check(d));
   if (acts_bytes < sd_qwen3_extend_acts_bytes(d, B, T)) return SD_ERR_WORKSPACE;
-  const int64_t base = al(sd_qwen3_acts_bytes(d, B, T, SD_SAVE_NONE));
-  int64_t* rows = (int64_t*)((char*)acts + base);
-  char* cos_rows = (char*)acts + al(sd_qwen3_prefill_acts_bytes(d, B, T));
-  char* sin_rows = cos_rows + al((int64_t)B * T * 128 * 2);
-  RUN(sd_last_rows(new_len, rows, B, T, stream));
-  RUN(sd_rope_rows_at(cos_tab, sin_tab, past, cos_rows, sin_rows, B, T, sink.cap, stream));
-  sink.past = past;
-  sink.new_len = new_len;
-  const sd_qwen3_batch bt = {ids, nullptr, nullptr, cos_rows, sin_rows, rows, B, B, T, 0};
-  return forward_impl(d, p, &bt, acts, base, logits, SD_SAVE_NONE, stream, &sink);
+  sink.past = past; sink.new_len = new_len;
+  return block_forward(d, p, ids, nullptr, cos_tab, sin_tab, acts, logits, B, T, stream, sink);
 }
-
-namespace {
-struct DecodeActs {
-  char *x, *x_mid, *xn, *qkv, *q, *ao, *gu, *act, *ws;
-  int64_t ws_bytes, total;
-  DecodeActs(const sd_qwen3_dims* d, int B, int cap, char* p) {
-    const Sizes s(d, B, 1);
-    char* p0 = p;
-    x = p; p += s.x;
-    x_mid = p; p += s.x;
-    xn = p; p += s.x;
-    qkv = p; p += s.qkv;
-    q = p; p += s.ao;
-    ao = p; p += s.ao;
-    gu = p; p += s.gu;
-    act = p; p += s.act;
-    ws_bytes = sd_attn_decode_workspace_bytes(B, s.Hq, cap);
-    ws = p; p += al(ws_bytes);
-    total = p - p0;
-  }
-};
-}  // namespace
 
 extern "C" int64_t sd_qwen3_decode_acts_bytes(const sd_qwen3_dims* d, int B, int cap) {
   if (!d || d->head_dim != 128) return SD_ERR_UNSUPPORTED;
   if (B <= 0 || cap <= 0) return SD_ERR_SHAPE;
   return DecodeActs(d, B, cap, nullptr).total;
 }
-
-namespace {
-// true when every GEMV of a skinny step accepts its shape: decided for the whole step before the first launch
-bool skinny_step_ok(const sd_qwen3_params* p, const Sizes& s, const DecodeActs& a, const void* logits, int B) {
-  bool ok = sd_gemv_check(a.x, p->lm_head, logits, nullptr, p->final_norm, B, s.V, s.h, s.h, s.h, s.V, 0) == 0;
-  for (int l = 0; ok && l < s.L; ++l) {
-    const sd_qwen3_layer& w = p->layers_host[l];
-    ok = sd_gemv_check(a.x, w.wqkv, a.qkv, nullptr, w.ln1, B, s.QKV, s.h, s.h, s.h, s.QKV, 0) == 0 &&
-         sd_gemv_check(a.ao, w.wo, a.x_mid, a.x, nullptr, B, s.h, s.QD, s.QD, s.QD, s.h, s.h) == 0 &&
-         sd_gemv_check(a.x_mid, w.wgu, a.act, nullptr, w.ln2, B, s.I, s.h, s.h, s.h, s.I, 0) == 0 &&
-         sd_gemv_check(a.act, w.wdown, a.x, a.x_mid, nullptr, B, s.h, s.I, s.I, s.I, s.h, s.h) == 0;
-  }
-  return ok;
-}
-}  // namespace
-
-namespace {
-// the launches of a decode step over either kind of cache; every argument was checked by the entry
-int decode_step_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* pos, int max_len,
-                     const void* cos_tab, const void* sin_tab, const KvSink& kv, const Sizes& s, const DecodeActs& a,
-                     void* logits, int B, int flags, void* stream);
-}  // namespace
 
 extern "C" int sd_qwen3_decode_step_flags(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
                                           const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab,
@@ -798,9 +815,7 @@ extern "C" int sd_qwen3_decode_step_paged(const sd_qwen3_dims* d, const sd_qwen3
   if (!d || !p) return SD_ERR_SHAPE;
   if (d->head_dim != 128) return SD_ERR_UNSUPPORTED;
   if (B <= 0 || max_len <= 0 || !ids || !pos || !logits || !acts) return SD_ERR_SHAPE;
-  if (d->n_kv <= 0 || d->n_q % d->n_kv) return SD_ERR_SHAPE;
-  const int G = d->n_q / d->n_kv;
-  if (G != 1 && G != 2 && G != 4) return SD_ERR_UNSUPPORTED;
+  RUN(gqa_check(d));
   KvSink kv = {};
   RUN(paged_sink(d, kvp, &kv));
   const Sizes s(d, B, 1);
@@ -808,46 +823,6 @@ extern "C" int sd_qwen3_decode_step_paged(const sd_qwen3_dims* d, const sd_qwen3
   if (acts_bytes < a.total) return SD_ERR_WORKSPACE;
   return decode_step_impl(d, p, ids, pos, max_len, cos_tab, sin_tab, kv, s, a, logits, B, flags, stream);
 }
-
-namespace {
-int decode_step_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* pos, int max_len,
-                     const void* cos_tab, const void* sin_tab, const KvSink& kv, const Sizes& s, const DecodeActs& a,
-                     void* logits, int B, int flags, void* stream) {
-  const bool skinny = (flags & SD_DECODE_SKINNY) && skinny_step_ok(p, s, a, logits, B);
-  RUN(sd_embedding_fwd(ids, p->embed, a.x, B, s.h, s.V, stream));
-  if (skinny) {
-    for (int l = 0; l < s.L; ++l) {
-      const sd_qwen3_layer& w = p->layers_host[l];
-      RUN(sd_gemv_bf16(a.x, w.wqkv, a.qkv, nullptr, w.ln1, d->eps, B, s.QKV, s.h, s.h, s.h, s.QKV, 0, stream));
-      RUN(kv.step(s, l, w, a.qkv, a.q, a.ao, cos_tab, sin_tab, pos, a.ws, a.ws_bytes, B, max_len, d->eps, stream));
-      RUN(sd_gemv_bf16(a.ao, w.wo, a.x_mid, a.x, nullptr, 0.f, B, s.h, s.QD, s.QD, s.QD, s.h, s.h, stream));
-      RUN(sd_gemv_swiglu(a.x_mid, w.wgu, a.act, w.ln2, d->eps, B, s.I, s.h, stream));
-      RUN(sd_gemv_bf16(a.act, w.wdown, a.x, a.x_mid, nullptr, 0.f, B, s.h, s.I, s.I, s.I, s.h, s.h, stream));
-    }
-    RUN(sd_gemv_bf16(a.x, p->lm_head, logits, nullptr, p->final_norm, d->eps, B, s.V, s.h, s.h, s.h, s.V, 0, stream));
-    return 0;
-  }
-  for (int l = 0; l < s.L; ++l) {
-    const sd_qwen3_layer& w = p->layers_host[l];
-    RUN(sd_rmsnorm_fwd(a.x, w.ln1, a.xn, nullptr, B, s.h, d->eps, stream));
-    RUN(sd_gemm_bf16(a.xn, w.wqkv, a.qkv, nullptr, B, s.QKV, s.h, s.h, s.h, s.QKV, 0, 0, 0, stream));
-    RUN(kv.step(s, l, w, a.qkv, a.q, a.ao, cos_tab, sin_tab, pos, a.ws, a.ws_bytes, B, max_len, d->eps, stream));
-    RUN(sd_gemm_bf16(a.ao, w.wo, a.x_mid, a.x, B, s.h, s.QD, s.QD, s.QD, s.h, s.h, 0, 0, stream));
-    RUN(sd_rmsnorm_fwd(a.x_mid, w.ln2, a.xn, nullptr, B, s.h, d->eps, stream));
-    const int rc = sd_gemm_swiglu(a.xn, w.wgu, nullptr, a.act, B, s.I, s.h, stream);
-    if (rc == SD_ERR_UNSUPPORTED) {
-      RUN(sd_gemm_bf16(a.xn, w.wgu, a.gu, nullptr, B, 2 * s.I, s.h, s.h, s.h, 2 * s.I, 0, 0, 0, stream));
-      RUN(sd_swiglu_fwd(a.gu, a.act, B, s.I, stream));
-    } else if (rc) {
-      return rc;
-    }
-    RUN(sd_gemm_bf16(a.act, w.wdown, a.x, a.x_mid, B, s.h, s.I, s.I, s.I, s.h, s.h, 0, 0, stream));
-  }
-  RUN(sd_rmsnorm_fwd(a.x, p->final_norm, a.xn, nullptr, B, s.h, d->eps, stream));
-  RUN(sd_gemm_bf16(a.xn, p->lm_head, logits, nullptr, B, s.V, s.h, s.h, s.h, s.V, 0, 0, 0, stream));
-  return 0;
-}
-}  // namespace
 
 extern "C" int sd_qwen3_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
                                     const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab, void* cache,

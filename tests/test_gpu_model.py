@@ -435,6 +435,53 @@ def test_gradient_checkpointing_recompute_is_bit_identical(sda, layers):
     record("recompute_bit_identical", layers=layers, full_bytes=full_bytes, ckpt_bytes=seen[-1][1])
 
 
+def test_backward_schedules_agree(sda):
+    """Every schedule of sd_qwen3_backward -- one stream; a side stream with "model.overlap_mask" 31 (default: grouped dW,
+    batched gain reduce), 23 (four separate dW GEMMs), 15 (grouped, per-kernel gain reduces), 0 (nothing beside the dX
+    chain but the dW GEMMs) -- orders the same kernels differently across the two streams.  Three layers (both buffer
+    parities and a pending grouped launch joined in the middle), right padding on one row, two accumulating
+    micro-batches.  Per schedule the keep-everything and the recompute-always gradients are equal bit for bit (same
+    kernels, same schedule), and the gradient agrees with the default schedule's within the gradient tolerance stated at
+    the top of this file (norm within 5e-2, cosine >= 0.995): a missing wait shows as a torn gradient."""
+    from speech_distill_amd import _lib
+    model = sda.HipQwen3ForCausalLM(sda.Qwen3Dims(512, 256, 384, 3, 4, 2), device=dev(), seed=3, init_std=0.05)
+    g = torch.Generator().manual_seed(17)
+    B, T, V = 2, 70, 512
+    batches = []
+    for _ in range(2):
+        am = torch.ones(B, T, dtype=torch.long)
+        am[1, T - 19:] = 0
+        batches.append([to_dev(x) for x in (torch.randint(0, V, (B, T), generator=g), am,
+                                            torch.randn(B, T, V, generator=g) * am[..., None])])
+
+    def grad(recompute):
+        model.gradient_checkpointing_enable(gradient_checkpointing_kwargs={"recompute": "always" if recompute else "never"})
+        model.zero_grad()
+        for ids, am, probe in batches:
+            (model(input_ids=ids, attention_mask=am).logits.float() * probe).sum().backward()
+        torch.cuda.synchronize()
+        return model.flat_grad.clone()
+
+    before = _lib.debug_get("model.overlap_mask")
+    try:
+        grads = {}
+        for overlap, mask in ((True, 31), (False, 31), (True, 23), (True, 15), (True, 0)):
+            model.overlap_dw = overlap
+            _lib.debug_set("model.overlap_mask", mask)
+            keep, again = grad(False), grad(True)
+            assert float(keep.float().abs().max()) > 0
+            assert torch.equal(keep, again), (overlap, mask)
+            grads[overlap, mask] = keep
+        ref = grads[True, 31].double()
+        for key, got in grads.items():
+            ratio, c = float(got.double().norm() / ref.norm()), _cos(got, ref)
+            print("backward schedule", key, "norm ratio", ratio, "cosine", c)
+            record("backward_schedule", overlap_dw=key[0], mask=key[1], norm_ratio=ratio, cos=c)
+            assert abs(ratio - 1) <= 5e-2 and c >= 0.995, (key, ratio, c)
+    finally:
+        _lib.debug_set("model.overlap_mask", before)
+
+
 def test_config4_long_context_step(sda):
     """BASELINE config 4 shapes on one GPU: T=2048 (batch 2), student 0.6B + sparse teacher signal.  Size-independent
     checks: CE ~ ln V at random init, finite gradients, bitwise determinism; and the attention path at T=2048 against
