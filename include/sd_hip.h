@@ -658,6 +658,73 @@ int sd_qwen3_decode_step_paged(const sd_qwen3_dims* d, const sd_qwen3_params* p,
                                int max_len, const void* cos_tab, const void* sin_tab, const sd_kv_pages* kv, void* acts,
                                int64_t acts_bytes, void* logits, int B, int flags, void* stream);
 
+/* ---- 8-bit (MXFP8) pages of the paged KV cache.  Opt-in; the contiguous cache, the bf16 paged cache, their entries and
+ * their bits are unchanged.  Every decode step reads every byte of every live row's cache: these pages hold 132 bytes per
+ * (position, kv head) where the bf16 pages hold 256.
+ * Format: exactly that of the "MXFP8 frozen teacher" section above -- e4m3fn elements, one E8M0 scale byte per 32
+ *   consecutive elements along the head dimension (4 scale bytes per position and kv head), e = floor(log2(amax)) - 8
+ *   with the same clamp, RNE, saturation at +-448 -- taken from the bf16 value the bf16 twin would have stored.
+ * Pool: ONE caller-owned byte buffer of sd_kvpool_mx_bytes(d, n_pages) = L * 2 * n_pages * 256 * Hkv * 132 bytes; per
+ *   layer, in this order: a K data plane [n_pages][256][Hkv*128] u8, a K scale plane [n_pages][256][Hkv*4] u8, a V data
+ *   plane and a V scale plane laid out like the K ones.  The kernel entries take the four planes of one layer where the
+ *   bf16 twin takes (k_pool, v_pool); data planes 16-byte, scale planes 4-byte aligned.
+ * SD_KV_PAGE, the page table and every rule of the paged section carry over: entries a row does not reach are never
+ *   read; an out-of-range entry that is read skips the store, or clamps (decode) or zeroes (extend) the load; lengths and
+ *   positions are clamped first.
+ * The value of a cached element is bf16(float(q) * 2^e).  For scale bytes 3..246 that product is a bf16 number for every
+ *   finite e4m3 code, so nothing is rounded on the way back; it fails only for bytes 0-2 and 247-254, i.e. for a block
+ *   whose amax lies below about 2^-116 or above about 2^118.  Such blocks are outside the contract, as NaN / Inf are; an
+ *   all-zero block (byte 0, all codes 0) is inside it.
+ * Stores (sd_kvcache_store_paged_mx, sd_kvcache_store_at_paged_mx, sd_qknorm_rope_append_paged_mx): the twin's arithmetic,
+ *   statement for statement, up to the bf16 head vector it would store; that vector is then quantised (a 16-lane group
+ *   owns its 128 elements, the 4 lanes of a block share one maximum; 8 data bytes per lane, one scale byte per block).
+ *   q_out of the append is the twin's bf16.  The three kernels write identical bytes for identical input rows.
+ * Attention (sd_attn_decode_paged_mx, sd_attn_extend_paged_mx): the twins' kernels with only the K / V read replaced --
+ *   8 bytes per lane and row plus the row's scales, turned back into the bf16 numbers in registers (decode) or on the way
+ *   into the LDS tile (extend: no LDS-DMA; one tile of loads is kept in flight in registers).  Work split, key order,
+ *   masks, online softmax, merge, workspace and the max_len rule are the twins'; keys >= n are never loaded.
+ * Bit contracts (by construction; tests/test_gpu_paged_mx.py):
+ *   - for ANY page layout, o and lse of the two attention entries equal those of sd_attn_decode_paged /
+ *     sd_attn_extend_paged run on a bf16 pool holding the dequantised values;
+ *   - the stored data and scale bytes equal the quantisation above (tests/mx_ref.py mx_quant) of what the bf16 twin stores.
+ * Argument checks: the twins' codes, all before any launch; a NULL plane, a NULL table, max_pages <= 0 or n_pages <= 0 is
+ *   SD_ERR_SHAPE. */
+int64_t sd_kvpool_mx_bytes(const sd_qwen3_dims* d, int n_pages);
+int sd_kvcache_store_paged_mx(const void* qk, const void* qkv, void* k_data, void* k_scale, void* v_data, void* v_scale,
+                              const int32_t* table, int max_pages, int n_pages, const int32_t* kv_len, int B, int T, int Hq,
+                              int Hkv, void* stream);
+int sd_kvcache_store_at_paged_mx(const void* qk, const void* qkv, void* k_data, void* k_scale, void* v_data, void* v_scale,
+                                 const int32_t* table, int max_pages, int n_pages, const int32_t* past,
+                                 const int32_t* new_len, int B, int T, int Hq, int Hkv, void* stream);
+int sd_qknorm_rope_append_paged_mx(const void* qkv, const void* q_gain, const void* k_gain, const void* cos_tab,
+                                   const void* sin_tab, const int32_t* pos, void* q_out, void* k_data, void* k_scale,
+                                   void* v_data, void* v_scale, const int32_t* table, int max_pages, int n_pages, int B,
+                                   int Hq, int Hkv, float eps, void* stream);
+int sd_attn_decode_paged_mx(const void* q, const void* k_data, const void* k_scale, const void* v_data, const void* v_scale,
+                            const int32_t* table, int max_pages, int n_pages, void* o, float* lse, const int32_t* len,
+                            int len_add, void* workspace, int64_t workspace_bytes, int B, int max_len, int Hq, int Hkv,
+                            int head_dim, float scale, void* stream);
+int sd_attn_extend_paged_mx(const void* q, const void* k_data, const void* k_scale, const void* v_data, const void* v_scale,
+                            const int32_t* table, int max_pages, int n_pages, void* o, float* lse, const int32_t* past,
+                            const int32_t* new_len, int64_t ldq, int64_t ldo, int B, int T, int Hq, int Hkv, int head_dim,
+                            float scale, void* stream);
+/* The runner over 8-bit pages: sd_qwen3_prefill_paged / sd_qwen3_extend_paged / sd_qwen3_decode_step_paged with the five
+ * cache kernels swapped for the entries above -- the same launches in the same order through the same code.  kv is the
+ * same descriptor; pool_bytes is held against sd_kvpool_mx_bytes(d, n_pages) (a shortfall is SD_ERR_WORKSPACE); acts of
+ * the paged twins' *_acts_bytes; every other check and code as the paged twin.  The decode step honours SD_DECODE_SKINNY.
+ * sd_qwen3_prefill_paged_mx still attends over the in-flight bf16 K / V of the prompt (sd_attn_fwd): only its sink
+ * quantises, so a prompt's own logits are those of the bf16 prefill, and they differ from what sd_qwen3_extend_paged_mx
+ * with past = 0 computes, which attends over the quantised rows; the bytes the two leave in layer 0 are the same. */
+int sd_qwen3_prefill_paged_mx(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* kv_len,
+                              const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes,
+                              const sd_kv_pages* kv, void* logits, int B, int T, void* stream);
+int sd_qwen3_extend_paged_mx(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* past,
+                             const int32_t* new_len, const void* cos_tab, const void* sin_tab, void* acts,
+                             int64_t acts_bytes, const sd_kv_pages* kv, void* logits, int B, int T, void* stream);
+int sd_qwen3_decode_step_paged_mx(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* pos,
+                                  int max_len, const void* cos_tab, const void* sin_tab, const sd_kv_pages* kv, void* acts,
+                                  int64_t acts_bytes, void* logits, int B, int flags, void* stream);
+
 /* ---- weight-streaming GEMV for decode (M = batch <= 16): the projections of HF:239-262 (q/k/v, o), HF:81-83 (MLP) and the
  * lm_head for one token per sequence, with the RMSNorm of HF:59-64 and the SwiGLU of HF:81-83 fused in.  bf16 operands,
  * fp32 accumulation, nothing transposed: w is [N,K] with K contiguous.

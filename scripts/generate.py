@@ -52,7 +52,14 @@ def parse_args(argv=None):
                    help="0: every batch reserves a contiguous KV cache for its worst case.  N > 0: every batch's session "
                         "draws pages of 256 positions from ONE pool of N pages, turn by turn (the paged cache of the "
                         "reference's engine, llm_engine.py:91); the tokens are the same")
-    return p.parse_args(argv)
+    p.add_argument("--kv_cache_dtype", choices=("bf16", "mxfp8"), default="bf16",
+                   help="mxfp8 (needs --kv_pool_pages): the pool holds 8-bit pages -- e4m3 elements with one power-of-two "
+                        "scale per 32 of them, 0.516 of the bf16 bytes; what is cached is quantised, so the tokens may "
+                        "differ from the bf16 cache's")
+    args = p.parse_args(argv)
+    if args.kv_cache_dtype != "bf16" and args.kv_pool_pages <= 0:
+        p.error("--kv_cache_dtype mxfp8 needs --kv_pool_pages N: only the paged cache has an 8-bit form")
+    return args
 
 
 def read_prompts(path):
@@ -109,7 +116,7 @@ def main(argv=None):
     pad = args.pad_token_id if args.pad_token_id is not None else args.stop_token_id
     dev = model.flat.device
     n_new, elapsed = 0, 0.0
-    pool = model.kv_page_pool(args.kv_pool_pages) if args.kv_pool_pages > 0 else None
+    pool = model.kv_page_pool(args.kv_pool_pages, kv_dtype=args.kv_cache_dtype) if args.kv_pool_pages > 0 else None
     with open(args.output, "w") as out:
         for index, chunk in batches_by_turn_count(dialogues, args.batch_size):
             n_turns = len(chunk[0])

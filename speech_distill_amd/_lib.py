@@ -225,6 +225,22 @@ PROTOTYPES = {
     "sd_qwen3_decode_step_paged_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
     "sd_qwen3_decode_step_paged": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _i, _vp, _vp, C.POINTER(KvPages), _vp,
                                         _i64, _vp, _i, _i, _vp]),
+    # 8-bit (MXFP8) pages: (k_data, k_scale, v_data, v_scale) where the paged twin takes (k_pool, v_pool)
+    "sd_kvpool_mx_bytes": (_i64, [C.POINTER(Dims), _i]),
+    "sd_kvcache_store_paged_mx": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _vp]),
+    "sd_kvcache_store_at_paged_mx": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "sd_qknorm_rope_append_paged_mx": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i,
+                                            _f, _vp]),
+    "sd_attn_decode_paged_mx": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _i, _i,
+                                     _f, _vp]),
+    "sd_attn_extend_paged_mx": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i,
+                                     _i, _f, _vp]),
+    "sd_qwen3_prefill_paged_mx": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _vp, _vp, _vp, _i64,
+                                       C.POINTER(KvPages), _vp, _i, _i, _vp]),
+    "sd_qwen3_extend_paged_mx": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                      C.POINTER(KvPages), _vp, _i, _i, _vp]),
+    "sd_qwen3_decode_step_paged_mx": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _i, _vp, _vp, C.POINTER(KvPages),
+                                           _vp, _i64, _vp, _i, _i, _vp]),
     "sd_gemv_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i64, _i64, _i64, _i64, _vp]),
     "sd_gemv_swiglu": (_i, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp]),
 }

@@ -1241,12 +1241,32 @@ extern "C" int sd_attn_bwd_varlen(const void* q, const void* k, const void* v, c
 // descriptor is rebuilt per page -- base = the page's first row for this kv head, min(256, kv_end - 256 page_index)
 // records, so the slots >= kv_end still arrive as zeros -- from a page number held in scalar registers, which is
 // fetched one page (four tiles) ahead of the DMA that needs it.  Tile order, masks, online softmax and stores are untouched.
+// 8-bit pages (MXFP8, include/sd_hip.h; the pack then also carries the two E8M0 scale planes): only the staging differs.
+// A tile cannot go global -> LDS by DMA, so every lane loads the 8 e4m3 bytes of each 16-byte piece TileDma would have
+// handed it (same row, same swizzled source chunk) and the piece's block scale byte, turns them into the bf16x8 they stand
+// for and writes it to the LDS address the DMA would have written; rows at or past min(256, kv_end - 256 page_index), and
+// every row of an out-of-range page, are written as zeros, as the descriptor delivers them.  The loads of tile i + 1 are
+// issued before tile i is computed and held in registers (2 NP x 8 bytes + 2 NP scale bytes per lane) until the ring
+// slot is free.  The LDS image, and everything that reads it, is the same.
 namespace {
 static_assert(SD_KV_PAGE % 64 == 0, "a 64-key tile must not straddle a page");
 struct ExtPageArgs {
   const int* table;  // int32 [B][max_pages]
   int max_pages, n_pages;
+  const uint8_t *k_scale = nullptr, *v_scale = nullptr;  // 8-bit pages only: E8M0 planes [n_pages][256][Hkv*4]
 };
+// 8 e4m3 bytes and their block's E8M0 byte -> the bf16 values they stand for (exact for scale bytes 3..246)
+SD_DEV bf16x8 mx_to_bf16x8(u32x2 q, uint32_t scale_byte) {
+  const float sc = __builtin_bit_cast(float, scale_byte << 23);
+  bf16x8 r;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)q[h], false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)q[h], true);
+    r[4 * h] = (bf16)(a[0] * sc); r[4 * h + 1] = (bf16)(a[1] * sc);
+    r[4 * h + 2] = (bf16)(b[0] * sc); r[4 * h + 3] = (bf16)(b[1] * sc);
+  }
+  return r;
+}
 template <int G, class... PG>
 __global__ __launch_bounds__(128 * G) void attn_extend_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ Kp,
                                                               const bf16* __restrict__ Vp, bf16* __restrict__ O,
@@ -1254,6 +1274,7 @@ __global__ __launch_bounds__(128 * G) void attn_extend_kernel(const bf16* __rest
                                                               const int* __restrict__ new_p, long ldq, long ldo, int T,
                                                               int cap, int Hq, int Hkv, float scale, PG... pga) {
   constexpr bool PAGED = sizeof...(PG) > 0;
+  constexpr bool MX = sizeof...(PG) == 5;
   constexpr int TPP = SD_KV_PAGE / 64;  // tiles per page
   const ExtPageArgs pg{pga...};
   constexpr int NW = 2 * G;    // waves
@@ -1313,8 +1334,52 @@ __global__ __launch_bounds__(128 * G) void attn_extend_kernel(const bf16* __rest
     kd.rebase(Kp + first, rows);
     vd.rebase(Vp + first, rows);
   };
+  // ---- 8-bit pages: the tile in flight lives in registers between mx_load and mx_put
+  u32x2 kq[MX ? NP : 1], vq[MX ? NP : 1];
+  uint32_t ksc[MX ? NP : 1], vsc[MX ? NP : 1];
+  long mx_first = 0;  // pool row of the open page's row 0
+  int mx_rows = 0;    // rows of the open page that exist: the others are staged as zeros
+  auto mx_set_page = [&](int pi, int page_v) {
+    const int page = __builtin_amdgcn_readfirstlane(page_v);
+    const bool ok = page >= 0 && page < pg.n_pages;
+    mx_first = (long)(ok ? page : 0) * SD_KV_PAGE;
+    mx_rows = ok ? min(SD_KV_PAGE, kv_end - SD_KV_PAGE * pi) : 0;
+  };
+  auto mx_load = [&](int row0) {  // rows row0 .. row0 + 63 of the open page
+    if constexpr (MX) {
+#pragma unroll
+      for (int i = 0; i < NP; ++i) {
+        const int pc = (w * NP + i) * 64 + lane;
+        const int row = pc >> 4, ch = (pc & 15) ^ f_swz(row);
+        kq[i] = vq[i] = u32x2{0u, 0u};
+        ksc[i] = vsc[i] = 0u;
+        if (row0 + row < mx_rows) {
+          const long pr = mx_first + row0 + row;
+          const long od = pr * KD + hkv * D + ch * 8, os = (pr * Hkv + hkv) * 4 + (ch >> 2);
+          kq[i] = *(const u32x2*)((const uint8_t*)Kp + od);
+          vq[i] = *(const u32x2*)((const uint8_t*)Vp + od);
+          ksc[i] = pg.k_scale[os];
+          vsc[i] = pg.v_scale[os];
+        }
+      }
+    }
+  };
+  auto mx_put = [&](char* dst) {  // (K tile, V tile) at dst: the addresses TileDma::issue writes
+    if constexpr (MX) {
+#pragma unroll
+      for (int i = 0; i < NP; ++i) {
+        const int o16 = ((w * NP + i) * 64 + lane) * 16;
+        *(bf16x8*)(dst + o16) = mx_to_bf16x8(kq[i], ksc[i]);
+        *(bf16x8*)(dst + TILE + o16) = mx_to_bf16x8(vq[i], vsc[i]);
+      }
+    }
+  };
   int page_nx = 0;  // the page of the NEXT page boundary the stream crosses
-  if constexpr (PAGED) {
+  if constexpr (MX) {
+    mx_set_page(0, page_no(0));
+    if (nkv > TPP) page_nx = page_no(1);
+    mx_load(0);
+  } else if constexpr (PAGED) {
     kd.init(Kp + hkv * D, KD, 1, w, lane);
     vd.init(Vp + hkv * D, KD, 1, w, lane);
     set_page(0, page_no(0));
@@ -1323,8 +1388,10 @@ __global__ __launch_bounds__(128 * G) void attn_extend_kernel(const bf16* __rest
     kd.init(Kp + (long)b * cap * KD + hkv * D, KD, kv_end, w, lane);
     vd.init(Vp + (long)b * cap * KD + hkv * D, KD, kv_end, w, lane);
   }
-  kd.issue(0, smem, w);
-  vd.issue(0, smem + TILE, w);
+  if constexpr (!MX) {
+    kd.issue(0, smem, w);
+    vd.issue(0, smem + TILE, w);
+  }
   bf16x8 qf[8];
   {
     const bf16* qp = Q + ((long)b * T + tc) * ldq + hq * D + 8 * h;
@@ -1388,6 +1455,22 @@ __global__ __launch_bounds__(128 * G) void attn_extend_kernel(const bf16* __rest
       for (int db = 0; db < 4; ++db) o[db] = mfma32(vt[db], pf, o[db]);
     }
   };
+  if constexpr (MX) {
+    for (int i = 0; i < nkv; ++i) {
+      // tile i: registers -> ring slot i & 1, last read as tile i - 2, which everybody left before the barrier of i - 1
+      mx_put(smem + (i & 1) * 2 * TILE);
+      if (i + 1 < nkv) {  // tile i + 1 travels while tile i is computed
+        const int pi = (i + 1) / TPP;
+        if ((i + 1) % TPP == 0) {  // tile i + 1 opens page pi: its number was fetched when page pi - 1 was opened
+          mx_set_page(pi, page_nx);
+          if ((pi + 1) * TPP < nkv) page_nx = page_no(pi + 1);
+        }
+        mx_load(((i + 1) % TPP) * 64);
+      }
+      __syncthreads();  // everybody's share of tile i is in LDS
+      if (i * 64 < wave_hi) tile(i, i & 1);  // wave-uniform
+    }
+  } else
   for (int i = 0; i < nkv; ++i) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // my share of tile i (and, the first time, my Q rows)
     __builtin_amdgcn_s_barrier();  // everybody's share of tile i has landed; everybody is done reading tile i-1
@@ -1468,6 +1551,39 @@ extern "C" int sd_attn_extend_paged(const void* q, const void* k_pool, const voi
   hipLaunchKernelGGL((attn_extend_kernel<G_, const int*, int, int>), grid, dim3(128 * G_), 0, (hipStream_t)stream,     \
                      (const bf16*)q, (const bf16*)k_pool, (const bf16*)v_pool, (bf16*)o, lse, past, new_len, (long)ldq, \
                      (long)ldo, T, cap, Hq, Hkv, scale, (const int*)table, max_pages, n_pages)
+  if (G == 1) SD_EXT_GO(1); else if (G == 2) SD_EXT_GO(2); else SD_EXT_GO(4);
+#undef SD_EXT_GO
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+// The 8-bit twin: sd_attn_extend_paged's checks and grid; K / V arrive as e4m3 planes with their E8M0 scale planes.
+extern "C" int sd_attn_extend_paged_mx(const void* q, const void* k_data, const void* k_scale, const void* v_data,
+                                       const void* v_scale, const int32_t* table, int max_pages, int n_pages, void* o,
+                                       float* lse, const int32_t* past, const int32_t* new_len, int64_t ldq, int64_t ldo,
+                                       int B, int T, int Hq, int Hkv, int head_dim, float scale, void* stream) {
+  if (!q || !k_data || !k_scale || !v_data || !v_scale || !o || !past || !new_len || !table) return SD_ERR_SHAPE;
+  if (B <= 0 || T <= 0 || max_pages <= 0 || n_pages <= 0 || Hq <= 0 || Hkv <= 0 || (Hq % Hkv) || head_dim <= 0)
+    return SD_ERR_SHAPE;
+  if (head_dim != D) return SD_ERR_UNSUPPORTED;
+  const int G = Hq / Hkv;
+  if (G != 1 && G != 2 && G != 4) return SD_ERR_UNSUPPORTED;
+  if (ldq < (int64_t)Hq * D || ldo < (int64_t)Hq * D) return SD_ERR_SHAPE;
+  if ((ldq | ldo) & 7) return SD_ERR_ALIGN;
+  if (((uintptr_t)q | (uintptr_t)k_data | (uintptr_t)v_data | (uintptr_t)o) & 15) return SD_ERR_ALIGN;
+  if (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3) return SD_ERR_ALIGN;
+  if ((int64_t)SD_KV_PAGE * Hkv * D * 2 >= ((int64_t)1 << 31) || max_pages > (1 << 22) || T > (1 << 30) || B > 65535 ||
+      Hkv > 65535)
+    return SD_ERR_UNSUPPORTED;
+  const int cap = max_pages * SD_KV_PAGE;
+  SdProfScope prof(SD_K_ATTN_FWD, 4.0 * B * Hq * (double)T * cap * D, (hipStream_t)stream);  // upper bound: every key
+  SD_PROF_LABEL("attn_extend_kernel<%d, paged, mx>", G);
+  const dim3 grid((T + 63) / 64, Hkv, B);
+#define SD_EXT_GO(G_)                                                                                                   \
+  hipLaunchKernelGGL((attn_extend_kernel<G_, const int*, int, int, const uint8_t*, const uint8_t*>), grid,              \
+                     dim3(128 * G_), 0, (hipStream_t)stream, (const bf16*)q, (const bf16*)k_data, (const bf16*)v_data,  \
+                     (bf16*)o, lse, past, new_len, (long)ldq, (long)ldo, T, cap, Hq, Hkv, scale, (const int*)table,     \
+                     max_pages, n_pages, (const uint8_t*)k_scale, (const uint8_t*)v_scale)
   if (G == 1) SD_EXT_GO(1); else if (G == 2) SD_EXT_GO(2); else SD_EXT_GO(4);
 #undef SD_EXT_GO
   SD_CHECK_LAUNCH();

@@ -17,6 +17,11 @@
 // [n_pages][256][Hkv*128] and slot s of row b lives at page table[b][s >> 8], row s & 255 (include/sd_hip.h).  The four
 // cache kernels below take the page table as a TRAILING PARAMETER PACK, empty for the contiguous instantiation: its
 // kernel arguments, and with them its code, stay exactly what they were before the paged instantiation existed.
+//
+// 8-bit paged form (MXFP8 pages, include/sd_hip.h): the pool planes hold e4m3 bytes, [n_pages][256][Hkv*128], beside
+// scale planes [n_pages][256][Hkv*4] with one E8M0 byte per 32 elements of a head vector.  The pack then also carries the
+// two scale planes (five arguments): the stores quantise the bf16 value the paged instantiation would have stored, the
+// decode attention turns the bytes back into the bf16 numbers they stand for, in registers.
 #include <math.h>
 #include <stdlib.h>
 #include "sd_common.cuh"
@@ -54,6 +59,7 @@ static_assert(SD_KV_PAGE == kPart, "a page is one decode partition");
 struct PageArgs {
   const int32_t* table;  // int32 [B][max_pages]
   int max_pages, n_pages;
+  uint8_t *k_scale = nullptr, *v_scale = nullptr;  // 8-bit pages only: E8M0 planes [n_pages][256][Hkv*4]
 };
 // Element offset of slot s (0 <= s < max_pages * 256) of row b in a pool plane.  false: the table entry lies outside the
 // pool, and the caller must not store through it.
@@ -61,6 +67,48 @@ SD_DEV bool page_slot(const PageArgs& pg, int b, int s, int KD, long* off) {
   const int page = pg.table[(long)b * pg.max_pages + (s >> 8)];
   *off = ((long)page * SD_KV_PAGE + (s & (SD_KV_PAGE - 1))) * KD;
   return page >= 0 && page < pg.n_pages;
+}
+
+// ---- 8-bit pages: the number format of mx_quant32 (sd_mx.hip) on the 8 elements a lane owns of a 32-element block.
+// The four lanes of a block are a DPP quad (chunks 4i .. 4i + 3 of a head vector sit in four consecutive lanes in every
+// kernel below, and those lanes leave together or not at all), so the block maximum is two quad permutes.
+SD_DEV float quad_max(float v) {
+  v = fmaxf(v, dpp_move<0xB1>(v));  // quad_perm [1,0,3,2]
+  return fmaxf(v, dpp_move<0x4E>(v));  // quad_perm [2,3,0,1]
+}
+// v: the bf16 values the bf16 pool would hold at chunk c (8 elements) of pool row `row`; writes their 8 e4m3 bytes and,
+// from the first lane of the block, the block's E8M0 byte.  e = floor(log2(amax)) - 8 clamped below at -127, RNE,
+// saturation at +-448: every product is exact in fp32.
+SD_DEV void mx_store8(bf16x8 v, uint8_t* data, uint8_t* scale, long row, int Hkv, int c) {
+  float f[8];
+  unpack8(v, f);
+  float amax = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(f[e]));
+  amax = quad_max(amax);
+  const int eb = (int)(__builtin_bit_cast(uint32_t, amax) >> 23);  // biased exponent of amax (sign is 0)
+  const int sb = eb > 8 ? eb - 8 : 0;                              // e + 127
+  const float inv = __builtin_bit_cast(float, (uint32_t)(254 - sb) << 23);  // 2^-e
+  float y[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) y[e] = fminf(fmaxf(f[e] * inv, -448.f), 448.f);
+  int lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], lo, true);
+  int hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], 0, false);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], hi, true);
+  *(u32x2*)(data + (row * Hkv * 16 + c) * 8) = u32x2{(uint32_t)lo, (uint32_t)hi};
+  if ((c & 3) == 0) scale[row * Hkv * 4 + (c >> 2)] = (uint8_t)sb;
+}
+// 8 e4m3 bytes and their block's E8M0 byte -> the values they stand for, float(q) * 2^e.  For scale bytes 3..246 every
+// product is a bf16 number, so the fp32 value IS what a bf16 pool holding the dequantised rows would give unpack8.  An
+// all-zero block (byte 0) comes out as zeros.
+SD_DEV void unpack8_mx(u32x2 q, uint32_t scale_byte, float* f) {
+  const float sc = __builtin_bit_cast(float, scale_byte << 23);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)q[h], false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)q[h], true);
+    f[4 * h] = a[0] * sc; f[4 * h + 1] = a[1] * sc; f[4 * h + 2] = b[0] * sc; f[4 * h + 3] = b[1] * sc;
+  }
 }
 
 // ------------------------------------------------------------------------------------------- cache store (prefill)
@@ -83,7 +131,15 @@ __global__ __launch_bounds__(256) void kvcache_store_kernel(const bf16* __restri
   const int n = kv_len ? clampi(kv_len[b], 0, lim) : lim;
   if (t >= n) return;
   long dst = ((long)b * cap + t) * (Hkv * 128) + c * 8;
-  if constexpr (sizeof...(PG) > 0) {
+  if constexpr (sizeof...(PG) == 5) {  // 8-bit pages: the same source row, quantised
+    const PageArgs pg{pga...};
+    long row;
+    if (!page_slot(pg, b, t, 1, &row)) return;
+    const bf16x8 v = which == 0 ? *(const bf16x8*)(qk + (long)m * (Hq + Hkv) * 128 + Hq * 128 + c * 8)
+                                : *(const bf16x8*)(qkv + (long)m * (Hq + 2 * Hkv) * 128 + (Hq + Hkv) * 128 + c * 8);
+    mx_store8(v, (uint8_t*)(which == 0 ? kp : vp), which == 0 ? pg.k_scale : pg.v_scale, row, Hkv, c);
+    return;
+  } else if constexpr (sizeof...(PG) > 0) {
     if (!page_slot(PageArgs{pga...}, b, t, Hkv * 128, &dst)) return;
     dst += c * 8;
   }
@@ -113,7 +169,15 @@ __global__ __launch_bounds__(256) void kvcache_store_at_kernel(const bf16* __res
   const int n = clampi(new_len[b], 0, T < room ? T : room);
   if (t >= n) return;
   long dst = ((long)b * cap + p0 + t) * (Hkv * 128) + c * 8;
-  if constexpr (sizeof...(PG) > 0) {
+  if constexpr (sizeof...(PG) == 5) {  // 8-bit pages: the same source row, quantised
+    const PageArgs pg{pga...};
+    long row;
+    if (!page_slot(pg, b, p0 + t, 1, &row)) return;
+    const bf16x8 v = which == 0 ? *(const bf16x8*)(qk + (long)m * (Hq + Hkv) * 128 + Hq * 128 + c * 8)
+                                : *(const bf16x8*)(qkv + (long)m * (Hq + 2 * Hkv) * 128 + (Hq + Hkv) * 128 + c * 8);
+    mx_store8(v, (uint8_t*)(which == 0 ? kp : vp), which == 0 ? pg.k_scale : pg.v_scale, row, Hkv, c);
+    return;
+  } else if constexpr (sizeof...(PG) > 0) {
     if (!page_slot(PageArgs{pga...}, b, p0 + t, Hkv * 128, &dst)) return;
     dst += c * 8;
   }
@@ -191,7 +255,18 @@ __global__ __launch_bounds__(256) void qknorm_rope_append_kernel(const bf16* __r
   }
   if (!ok) return;
   long slot = ((long)b * cap + t) * (Hkv * 128);
-  if constexpr (sizeof...(PG) > 0) {
+  if constexpr (sizeof...(PG) == 5) {  // 8-bit pages: q as ever; the bf16 K and V the paged twin stores, quantised
+    const PageArgs pg{pga...};
+    if (hh < Hq) {
+      *(bf16x8*)(q_out + (long)b * Hq * 128 + hh * 128 + j * 8) = pack8(o);
+      return;
+    }
+    long row;
+    if (!inb || !page_slot(pg, b, t, 1, &row)) return;
+    if (hh < Hq + Hkv) mx_store8(pack8(o), (uint8_t*)kp, pg.k_scale, row, Hkv, (hh - Hq) * 16 + j);
+    else mx_store8(raw, (uint8_t*)vp, pg.v_scale, row, Hkv, (hh - Hq - Hkv) * 16 + j);
+    return;
+  } else if constexpr (sizeof...(PG) > 0) {
     if (hh >= Hq && inb) inb = page_slot(PageArgs{pga...}, b, t, Hkv * 128, &slot);
   }
   if (hh < Hq) *(bf16x8*)(q_out + (long)b * Hq * 128 + hh * 128 + j * 8) = pack8(o);
@@ -229,34 +304,58 @@ __global__ __launch_bounds__(256) void attn_decode_part_kernel(const bf16* __res
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[g][e] = 0.f;
   }
+  // 8-bit pages (five pack arguments): a row is 8 bytes per lane plus the dword of the head's four block scales, the
+  // same address for the 16 lanes of the group; lane j's block is j >> 2.  Everything after the unpack is shared.
+  constexpr bool MX = sizeof...(PG) == 5;
   long off = (long)b * cap * KD + hk * 128 + j * 8;
+  const uint8_t *ksb = nullptr, *vsb = nullptr;
   if constexpr (sizeof...(PG) > 0) {
     const PageArgs pg{pga...};
     const int page = clampi(pg.table[(long)b * pg.max_pages + p], 0, pg.n_pages - 1);  // p < max_pages: p * 256 < n <= cap
     off = ((long)page - p) * kPart * KD + hk * 128 + j * 8;  // key = p * 256 + r below lands on row r of the page
+    if constexpr (MX) {
+      const long so = ((long)page - p) * kPart * Hkv * 4 + hk * 4;
+      ksb = pg.k_scale + so;
+      vsb = pg.v_scale + so;
+    }
   }
   const bf16* kb = kp + off;
   const bf16* vb = vp + off;
+  const uint8_t *kb8 = (const uint8_t*)kp + off, *vb8 = (const uint8_t*)vp + off;  // 8-bit pages: one byte per element
   for (int it = 0; it < 16; it += 4) {
     if (p * kPart + it * 16 >= n) break;  // block-uniform
     bf16x8 kv[4], vv[4];
+    u32x2 kq[4], vq[4];
+    uint32_t ksd[4], vsd[4];
     bool okk[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int key = p * kPart + (it + u) * 16 + sg;
       okk[u] = key < n;
-      kv[u] = zero8();
-      vv[u] = zero8();
-      if (okk[u]) {
-        kv[u] = *(const bf16x8*)(kb + (long)key * KD);
-        vv[u] = *(const bf16x8*)(vb + (long)key * KD);
+      if constexpr (MX) {
+        kq[u] = vq[u] = u32x2{0u, 0u};
+        ksd[u] = vsd[u] = 0u;
+        if (okk[u]) {
+          kq[u] = *(const u32x2*)(kb8 + (long)key * KD);
+          vq[u] = *(const u32x2*)(vb8 + (long)key * KD);
+          ksd[u] = *(const uint32_t*)(ksb + (long)key * Hkv * 4);
+          vsd[u] = *(const uint32_t*)(vsb + (long)key * Hkv * 4);
+        }
+      } else {
+        kv[u] = zero8();
+        vv[u] = zero8();
+        if (okk[u]) {
+          kv[u] = *(const bf16x8*)(kb + (long)key * KD);
+          vv[u] = *(const bf16x8*)(vb + (long)key * KD);
+        }
       }
     }
     float s[G][4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       float kf[8];
-      unpack8(kv[u], kf);
+      if constexpr (MX) unpack8_mx(kq[u], (ksd[u] >> (8 * (j >> 2))) & 255u, kf);
+      else unpack8(kv[u], kf);
 #pragma unroll
       for (int g = 0; g < G; ++g) {
         float d = 0.f;
@@ -277,7 +376,8 @@ __global__ __launch_bounds__(256) void attn_decode_part_kernel(const bf16* __res
       for (int u = 0; u < 4; ++u) {
         const float pu = exp2f(s[g][u] - mn);  // masked key: exp2(-inf) = 0
         float vf[8];
-        unpack8(vv[u], vf);
+        if constexpr (MX) unpack8_mx(vq[u], (vsd[u] >> (8 * (j >> 2))) & 255u, vf);
+        else unpack8(vv[u], vf);
         l[g] += pu;
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc[g][e] += pu * vf[e];
@@ -639,6 +739,68 @@ extern "C" int sd_kvcache_store_at_paged(const void* qk, const void* qkv, void* 
   return 0;
 }
 
+// ---- 8-bit pages: the paged twins' checks and grids, the four planes of a layer and the scale planes in the pack
+extern "C" int64_t sd_kvpool_mx_bytes(const sd_qwen3_dims* d, int n_pages) {
+  if (!d || d->head_dim != 128) return SD_ERR_UNSUPPORTED;
+  if (n_pages <= 0) return SD_ERR_SHAPE;
+  return (int64_t)d->layers * 2 * n_pages * SD_KV_PAGE * d->n_kv * (128 + 4);
+}
+
+#define SD_MX_PACK const int32_t*, int, int, uint8_t*, uint8_t*
+
+extern "C" int sd_kvcache_store_paged_mx(const void* qk, const void* qkv, void* k_data, void* k_scale, void* v_data,
+                                         void* v_scale, const int32_t* table, int max_pages, int n_pages,
+                                         const int32_t* kv_len, int B, int T, int Hq, int Hkv, void* stream) {
+  if (!table || max_pages <= 0 || n_pages <= 0 || max_pages > (1 << 22)) return SD_ERR_SHAPE;
+  const int cap = max_pages * SD_KV_PAGE;
+  if (B <= 0 || T <= 0 || T > cap || Hq <= 0 || Hkv <= 0 || !qk || !qkv || !k_data || !k_scale || !v_data || !v_scale)
+    return SD_ERR_SHAPE;
+  const long total = 2l * B * T * Hkv * 16;
+  SdProfScope prof(SD_K_MISC, 1.52 * total * 16, ST);
+  SD_PROF_LABEL("kvcache_store_kernel<paged, mx>");
+  hipLaunchKernelGGL((kvcache_store_kernel<SD_MX_PACK>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ST,
+                     (const bf16*)qk, (const bf16*)qkv, (bf16*)k_data, (bf16*)v_data, kv_len, B, T, cap, Hq, Hkv, table,
+                     max_pages, n_pages, (uint8_t*)k_scale, (uint8_t*)v_scale);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sd_kvcache_store_at_paged_mx(const void* qk, const void* qkv, void* k_data, void* k_scale, void* v_data,
+                                            void* v_scale, const int32_t* table, int max_pages, int n_pages,
+                                            const int32_t* past, const int32_t* new_len, int B, int T, int Hq, int Hkv,
+                                            void* stream) {
+  if (!table || max_pages <= 0 || n_pages <= 0 || max_pages > (1 << 22)) return SD_ERR_SHAPE;
+  if (B <= 0 || T <= 0 || Hq <= 0 || Hkv <= 0 || !qk || !qkv || !k_data || !k_scale || !v_data || !v_scale || !past ||
+      !new_len)
+    return SD_ERR_SHAPE;
+  const long total = 2l * B * T * Hkv * 16;
+  SdProfScope prof(SD_K_MISC, 1.52 * total * 16, ST);
+  SD_PROF_LABEL("kvcache_store_at_kernel<paged, mx>");
+  hipLaunchKernelGGL((kvcache_store_at_kernel<SD_MX_PACK>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ST,
+                     (const bf16*)qk, (const bf16*)qkv, (bf16*)k_data, (bf16*)v_data, past, new_len, B, T,
+                     max_pages * SD_KV_PAGE, Hq, Hkv, table, max_pages, n_pages, (uint8_t*)k_scale, (uint8_t*)v_scale);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sd_qknorm_rope_append_paged_mx(const void* qkv, const void* q_gain, const void* k_gain, const void* cos_tab,
+                                              const void* sin_tab, const int32_t* pos, void* q_out, void* k_data,
+                                              void* k_scale, void* v_data, void* v_scale, const int32_t* table,
+                                              int max_pages, int n_pages, int B, int Hq, int Hkv, float eps, void* stream) {
+  if (!table || max_pages <= 0 || n_pages <= 0 || max_pages > (1 << 22)) return SD_ERR_SHAPE;
+  if (B <= 0 || Hq <= 0 || Hkv <= 0 || !pos || !qkv || !q_out || !k_data || !k_scale || !v_data || !v_scale)
+    return SD_ERR_SHAPE;
+  const long items = (long)B * (Hq + 2 * Hkv);
+  SdProfScope prof(SD_K_MISC, 4.0 * items * 128, ST);
+  SD_PROF_LABEL("qknorm_rope_append_kernel<paged, mx>");
+  hipLaunchKernelGGL((qknorm_rope_append_kernel<SD_MX_PACK>), dim3((unsigned)((items + 15) / 16)), dim3(256), 0, ST,
+                     (const bf16*)qkv, (const bf16*)q_gain, (const bf16*)k_gain, (const bf16*)cos_tab,
+                     (const bf16*)sin_tab, pos, (bf16*)q_out, (bf16*)k_data, (bf16*)v_data, B, max_pages * SD_KV_PAGE, Hq,
+                     Hkv, eps, table, max_pages, n_pages, (uint8_t*)k_scale, (uint8_t*)v_scale);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
 // internal (sd_runner.h): the gathered RoPE tables of sd_qwen3_extend
 int sd_rope_rows_at(const void* cos_tab, const void* sin_tab, const int32_t* past, void* cos_out, void* sin_out, int B,
                     int T, int cap, void* stream) {
@@ -761,6 +923,45 @@ extern "C" int sd_attn_decode_paged(const void* q, const void* k_pool, const voi
   SD_CHECK_LAUNCH();
   return 0;
 }
+
+// The 8-bit twin: sd_attn_decode_paged's checks, grid, workspace and merge; phase 1 reads e4m3 rows and their scales.
+extern "C" int sd_attn_decode_paged_mx(const void* q, const void* k_data, const void* k_scale, const void* v_data,
+                                       const void* v_scale, const int32_t* table, int max_pages, int n_pages, void* o,
+                                       float* lse, const int32_t* len, int len_add, void* workspace,
+                                       int64_t workspace_bytes, int B, int max_len, int Hq, int Hkv, int head_dim,
+                                       float scale, void* stream) {
+  if (head_dim != 128) return SD_ERR_UNSUPPORTED;
+  if (!table || max_pages <= 0 || n_pages <= 0 || max_pages > (1 << 22)) return SD_ERR_SHAPE;
+  if (B <= 0 || max_len <= 0 || Hq <= 0 || Hkv <= 0 || (Hq % Hkv) || !len || !q || !k_data || !k_scale || !v_data ||
+      !v_scale || !o)
+    return SD_ERR_SHAPE;
+  const int G = Hq / Hkv;
+  if (G != 1 && G != 2 && G != 4) return SD_ERR_UNSUPPORTED;
+  if (B > 65535 || Hkv > 65535) return SD_ERR_SHAPE;
+  const int cap = max_pages * SD_KV_PAGE;
+  if (workspace_bytes < sd_attn_decode_workspace_bytes(B, Hq, cap) || !workspace) return SD_ERR_WORKSPACE;
+  if (max_len > cap) max_len = cap;
+  const int pstride = max_pages, np = (max_len + kPart - 1) / kPart;
+  const float sl2 = scale * 1.4426950408889634f;
+  {
+    SdProfScope prof(SD_K_MISC, 2.0 * B * Hkv * 132.0 * max_len, ST);
+    SD_PROF_LABEL("attn_decode_part_kernel<%d, paged, mx>", G);
+#define SD_DEC_GO(G_)                                                                                                  \
+  hipLaunchKernelGGL((attn_decode_part_kernel<G_, SD_MX_PACK>), dim3(np, Hkv, B), dim3(256), 0, ST, (const bf16*)q,    \
+                     (const bf16*)k_data, (const bf16*)v_data, (float*)workspace, len, len_add, cap, max_len, Hq, Hkv, \
+                     pstride, sl2, table, max_pages, n_pages, (uint8_t*)k_scale, (uint8_t*)v_scale)
+    if (G == 1) SD_DEC_GO(1); else if (G == 2) SD_DEC_GO(2); else SD_DEC_GO(4);
+#undef SD_DEC_GO
+    SD_CHECK_LAUNCH();
+  }
+  SdProfScope prof(SD_K_MISC, (double)B * Hq * np * kRec * 4, ST);
+  SD_PROF_LABEL("attn_decode_merge_kernel");
+  hipLaunchKernelGGL(attn_decode_merge_kernel, dim3(Hq, B), dim3(128), 0, ST, (const float*)workspace, (bf16*)o, lse, len,
+                     len_add, cap, max_len, Hq, pstride);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+#undef SD_MX_PACK
 
 extern "C" int64_t sd_sample_workspace_bytes(int B, int V) {
   if (B <= 0 || V <= 0) return SD_ERR_SHAPE;

@@ -88,6 +88,8 @@ LayerActs layer_acts(const Sizes& s, char* base, int l, int save) {
 // -- or, in the paged form (table != nullptr; llm_engine.py:91), the pool [L][2][n_pages][256][Hkv*128] of
 // sd_kvpool_bytes: cache is then the pool's base, cap = max_pages * 256, and plane() gives the layer's pool planes.  The
 // five cache kernels are reached through the members below, which pick the contiguous entry or its paged twin.
+// Third form (mx; 8-bit MXFP8 pages): the pool of sd_kvpool_mx_bytes, per layer K data | K scale | V data | V scale, and
+// the _paged_mx entries.
 struct KvSink {
   char* cache;
   int cap;
@@ -95,17 +97,34 @@ struct KvSink {
   const int32_t *past = nullptr, *new_len = nullptr;
   const int32_t* table = nullptr;
   int n_pages = 0, max_pages = 0;
+  bool mx = false;
+  // 8-bit pages: the data (u8 [n_pages][256][Hkv*128]) or scale (u8 [n_pages][256][Hkv*4]) plane of K (0) or V (1)
+  char* mx_plane(const Sizes& s, int l, int which, bool scale) const {
+    const int64_t data = (int64_t)n_pages * SD_KV_PAGE * s.KD;
+    return cache + ((int64_t)l * 2 + which) * (data + data / 32) + (scale ? data : 0);
+  }
   char* plane(const Sizes& s, int B, int l, int which) const {
     if (table) return cache + ((int64_t)l * 2 + which) * n_pages * SD_KV_PAGE * s.KD * 2;
     return cache + ((int64_t)l * 2 + which) * B * cap * s.KD * 2;
   }
   int store(const Sizes& s, int l, const void* qk, const void* qkv, const int32_t* kv_len, int B, int T, void* stream) const {
+    if (mx)
+      return sd_kvcache_store_paged_mx(qk, qkv, mx_plane(s, l, 0, false), mx_plane(s, l, 0, true), mx_plane(s, l, 1, false),
+                                       mx_plane(s, l, 1, true), table, max_pages, n_pages, kv_len, B, T, s.Hq, s.Hkv, stream);
     char *kp = plane(s, B, l, 0), *vp = plane(s, B, l, 1);
     if (table) return sd_kvcache_store_paged(qk, qkv, kp, vp, table, max_pages, n_pages, kv_len, B, T, s.Hq, s.Hkv, stream);
     return sd_kvcache_store(qk, qkv, kp, vp, kv_len, B, T, cap, s.Hq, s.Hkv, stream);
   }
   // store_at + attention of an extend block
   int extend(const Sizes& s, int l, const void* qk, const void* qkv, void* ao, int B, int T, void* stream) const {
+    if (mx) {
+      char *kd = mx_plane(s, l, 0, false), *ks = mx_plane(s, l, 0, true), *vd = mx_plane(s, l, 1, false),
+           *vs = mx_plane(s, l, 1, true);
+      RUN(sd_kvcache_store_at_paged_mx(qk, qkv, kd, ks, vd, vs, table, max_pages, n_pages, past, new_len, B, T, s.Hq, s.Hkv,
+                                       stream));
+      return sd_attn_extend_paged_mx(qk, kd, ks, vd, vs, table, max_pages, n_pages, ao, nullptr, past, new_len, s.QK, s.QD, B,
+                                     T, s.Hq, s.Hkv, 128, kSdAttnScale, stream);
+    }
     char *kp = plane(s, B, l, 0), *vp = plane(s, B, l, 1);
     if (table) {
       RUN(sd_kvcache_store_at_paged(qk, qkv, kp, vp, table, max_pages, n_pages, past, new_len, B, T, s.Hq, s.Hkv, stream));
@@ -120,6 +139,14 @@ struct KvSink {
   int step(const Sizes& s, int l, const sd_qwen3_layer& w, const void* qkv, void* q, void* ao, const void* cos_tab,
            const void* sin_tab, const int32_t* pos, void* ws, int64_t ws_bytes, int B, int max_len, float eps,
            void* stream) const {
+    if (mx) {
+      char *kd = mx_plane(s, l, 0, false), *ks = mx_plane(s, l, 0, true), *vd = mx_plane(s, l, 1, false),
+           *vs = mx_plane(s, l, 1, true);
+      RUN(sd_qknorm_rope_append_paged_mx(qkv, w.q_gain, w.k_gain, cos_tab, sin_tab, pos, q, kd, ks, vd, vs, table, max_pages,
+                                         n_pages, B, s.Hq, s.Hkv, eps, stream));
+      return sd_attn_decode_paged_mx(q, kd, ks, vd, vs, table, max_pages, n_pages, ao, nullptr, pos, 1, ws, ws_bytes, B,
+                                     max_len, s.Hq, s.Hkv, 128, kSdAttnScale, stream);
+    }
     char *kp = plane(s, B, l, 0), *vp = plane(s, B, l, 1);
     if (table) {
       RUN(sd_qknorm_rope_append_paged(qkv, w.q_gain, w.k_gain, cos_tab, sin_tab, pos, q, kp, vp, table, max_pages, n_pages,
@@ -141,11 +168,14 @@ int gqa_check(const sd_qwen3_dims* d) {
 }
 
 // the checked arguments of the paged runner entries -> a KvSink over the pool (0, or the code to return)
-int paged_sink(const sd_qwen3_dims* d, const sd_kv_pages* kv, KvSink* sink) {
+// mx: the pool holds 8-bit pages (sd_kvpool_mx_bytes)
+int paged_sink(const sd_qwen3_dims* d, const sd_kv_pages* kv, KvSink* sink, bool mx = false) {
   if (!kv || !kv->pool || !kv->table || kv->n_pages <= 0 || kv->max_pages <= 0 || kv->max_pages > (1 << 22))
     return SD_ERR_SHAPE;
-  if (kv->pool_bytes < sd_kvpool_bytes(d, kv->n_pages)) return SD_ERR_WORKSPACE;
-  *sink = KvSink{(char*)kv->pool, kv->max_pages * SD_KV_PAGE, nullptr, nullptr, kv->table, kv->n_pages, kv->max_pages};
+  // sd_kvpool_mx_bytes = sd_kvpool_bytes x 132 / 256: 128 + 4 bytes where bf16 takes 256 per (position, kv head)
+  const int64_t bf16_bytes = sd_kvpool_bytes(d, kv->n_pages);
+  if (kv->pool_bytes < (mx ? bf16_bytes / 256 * 132 : bf16_bytes)) return SD_ERR_WORKSPACE;
+  *sink = KvSink{(char*)kv->pool, kv->max_pages * SD_KV_PAGE, nullptr, nullptr, kv->table, kv->n_pages, kv->max_pages, mx};
   return 0;
 }
 
@@ -748,36 +778,63 @@ extern "C" int64_t sd_qwen3_prefill_paged_acts_bytes(const sd_qwen3_dims* d, int
   return sd_qwen3_prefill_acts_bytes(d, B, T);
 }
 
-extern "C" int sd_qwen3_prefill_paged(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
-                                      const int32_t* kv_len, const void* cos_tab, const void* sin_tab, void* acts,
-                                      int64_t acts_bytes, const sd_kv_pages* kv, void* logits, int B, int T, void* stream) {
+static int prefill_paged(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* kv_len,
+                         const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes, const sd_kv_pages* kv,
+                         void* logits, int B, int T, void* stream, bool mx) {
   if (!d || !p) return SD_ERR_SHAPE;
   if (d->head_dim != 128) return SD_ERR_UNSUPPORTED;
   KvSink sink = {};
-  RUN(paged_sink(d, kv, &sink));
+  RUN(paged_sink(d, kv, &sink, mx));
   if (B <= 0 || T <= 0 || sink.cap < T || !logits || !ids || !acts) return SD_ERR_SHAPE;
   if (acts_bytes < sd_qwen3_prefill_acts_bytes(d, B, T)) return SD_ERR_WORKSPACE;
   return block_forward(d, p, ids, kv_len, cos_tab, sin_tab, acts, logits, B, T, stream, sink);
+}
+
+extern "C" int sd_qwen3_prefill_paged(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
+                                      const int32_t* kv_len, const void* cos_tab, const void* sin_tab, void* acts,
+                                      int64_t acts_bytes, const sd_kv_pages* kv, void* logits, int B, int T, void* stream) {
+  return prefill_paged(d, p, ids, kv_len, cos_tab, sin_tab, acts, acts_bytes, kv, logits, B, T, stream, false);
+}
+
+// 8-bit pages: the prompt still attends over its in-flight bf16 K / V (sd_attn_fwd); only the sink quantises
+extern "C" int sd_qwen3_prefill_paged_mx(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
+                                         const int32_t* kv_len, const void* cos_tab, const void* sin_tab, void* acts,
+                                         int64_t acts_bytes, const sd_kv_pages* kv, void* logits, int B, int T,
+                                         void* stream) {
+  return prefill_paged(d, p, ids, kv_len, cos_tab, sin_tab, acts, acts_bytes, kv, logits, B, T, stream, true);
 }
 
 extern "C" int64_t sd_qwen3_extend_paged_acts_bytes(const sd_qwen3_dims* d, int B, int T) {
   return sd_qwen3_extend_acts_bytes(d, B, T);
 }
 
-extern "C" int sd_qwen3_extend_paged(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
-                                     const int32_t* past, const int32_t* new_len, const void* cos_tab, const void* sin_tab,
-                                     void* acts, int64_t acts_bytes, const sd_kv_pages* kv, void* logits, int B, int T,
-                                     void* stream) {
+static int extend_paged(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* past,
+                        const int32_t* new_len, const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes,
+                        const sd_kv_pages* kv, void* logits, int B, int T, void* stream, bool mx) {
   if (!d || !p) return SD_ERR_SHAPE;
   if (d->head_dim != 128) return SD_ERR_UNSUPPORTED;
   KvSink sink = {};
-  RUN(paged_sink(d, kv, &sink));
+  RUN(paged_sink(d, kv, &sink, mx));
   if (B <= 0 || T <= 0 || sink.cap < T || !ids || !past || !new_len || !cos_tab || !sin_tab || !acts || !logits)
     return SD_ERR_SHAPE;
   RUN(gqa_check(d));
   if (acts_bytes < sd_qwen3_extend_acts_bytes(d, B, T)) return SD_ERR_WORKSPACE;
   sink.past = past; sink.new_len = new_len;
   return block_forward(d, p, ids, nullptr, cos_tab, sin_tab, acts, logits, B, T, stream, sink);
+}
+
+extern "C" int sd_qwen3_extend_paged(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
+                                     const int32_t* past, const int32_t* new_len, const void* cos_tab, const void* sin_tab,
+                                     void* acts, int64_t acts_bytes, const sd_kv_pages* kv, void* logits, int B, int T,
+                                     void* stream) {
+  return extend_paged(d, p, ids, past, new_len, cos_tab, sin_tab, acts, acts_bytes, kv, logits, B, T, stream, false);
+}
+
+extern "C" int sd_qwen3_extend_paged_mx(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
+                                        const int32_t* past, const int32_t* new_len, const void* cos_tab,
+                                        const void* sin_tab, void* acts, int64_t acts_bytes, const sd_kv_pages* kv,
+                                        void* logits, int B, int T, void* stream) {
+  return extend_paged(d, p, ids, past, new_len, cos_tab, sin_tab, acts, acts_bytes, kv, logits, B, T, stream, true);
 }
 
 extern "C" int64_t sd_qwen3_decode_acts_bytes(const sd_qwen3_dims* d, int B, int cap) {
@@ -807,21 +864,35 @@ extern "C" int64_t sd_qwen3_decode_step_paged_acts_bytes(const sd_qwen3_dims* d,
   return sd_qwen3_decode_acts_bytes(d, B, max_pages * SD_KV_PAGE);
 }
 
-extern "C" int sd_qwen3_decode_step_paged(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
-                                          const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab,
-                                          const sd_kv_pages* kvp, void* acts, int64_t acts_bytes, void* logits, int B,
-                                          int flags, void* stream) {
+static int decode_step_paged(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* pos,
+                             int max_len, const void* cos_tab, const void* sin_tab, const sd_kv_pages* kvp, void* acts,
+                             int64_t acts_bytes, void* logits, int B, int flags, void* stream, bool mx) {
   if (flags & ~SD_DECODE_SKINNY) return SD_ERR_SHAPE;
   if (!d || !p) return SD_ERR_SHAPE;
   if (d->head_dim != 128) return SD_ERR_UNSUPPORTED;
   if (B <= 0 || max_len <= 0 || !ids || !pos || !logits || !acts) return SD_ERR_SHAPE;
   RUN(gqa_check(d));
   KvSink kv = {};
-  RUN(paged_sink(d, kvp, &kv));
+  RUN(paged_sink(d, kvp, &kv, mx));
   const Sizes s(d, B, 1);
   const DecodeActs a(d, B, kv.cap, (char*)acts);
   if (acts_bytes < a.total) return SD_ERR_WORKSPACE;
   return decode_step_impl(d, p, ids, pos, max_len, cos_tab, sin_tab, kv, s, a, logits, B, flags, stream);
+}
+
+extern "C" int sd_qwen3_decode_step_paged(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
+                                          const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab,
+                                          const sd_kv_pages* kvp, void* acts, int64_t acts_bytes, void* logits, int B,
+                                          int flags, void* stream) {
+  return decode_step_paged(d, p, ids, pos, max_len, cos_tab, sin_tab, kvp, acts, acts_bytes, logits, B, flags, stream,
+                           false);
+}
+
+extern "C" int sd_qwen3_decode_step_paged_mx(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
+                                             const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab,
+                                             const sd_kv_pages* kvp, void* acts, int64_t acts_bytes, void* logits, int B,
+                                             int flags, void* stream) {
+  return decode_step_paged(d, p, ids, pos, max_len, cos_tab, sin_tab, kvp, acts, acts_bytes, logits, B, flags, stream, true);
 }
 
 extern "C" int sd_qwen3_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,

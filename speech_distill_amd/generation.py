@@ -46,6 +46,13 @@ def _check_decode_kernels(decode_kernels):
         raise ValueError(f"decode_kernels must be one of {DECODE_KERNELS}, got {decode_kernels!r}")
 
 
+def _mx_rows(data, scale):
+    """MXFP8 rows (e4m3 bytes uint8 [n, K], E8M0 bytes uint8 [n, K/32]) -> the bf16 values they stand for, float(q) * 2^e
+    (exact for scale bytes 3..246: include/sd_hip.h)."""
+    f = data.view(torch.float8_e4m3fn).to(torch.float32).view(data.shape[0], -1, 32)
+    return torch.ldexp(f, (scale.to(torch.int32) - 127)[..., None]).view(data.shape).to(torch.bfloat16)
+
+
 class Decoder:
     """The KV cache [L][2][B][cap][Hkv*128] (bf16) of one batch, the activation buffers of the two runner entries, and the
     calls themselves.  ``prefill`` fills the cache from right-padded prompts and returns the logits of each row's last
@@ -57,7 +64,12 @@ class Decoder:
     ``pool`` (a ``PagePool``): the paged form (llm_engine.py:91).  No cache buffer; the decoder owns a device page table
     int32 [B, ceil(cap / 256)] and its host mirror ``pages`` (a ``PageTable``), ``cap`` becomes that many whole pages, and
     the three calls run the paged runner entries, whose logits are bit-identical.  Whoever drives the calls by hand makes
-    the rows own their pages first (``reserve``); ``gather`` stands in for ``planes``."""
+    the rows own their pages first (``reserve``); ``gather`` stands in for ``planes``.
+
+    A pool made with ``kv_dtype="mxfp8"`` selects the ``_paged_mx`` entries (8-bit pages, include/sd_hip.h): the rows are
+    quantised as they are cached and every attention over the cache reads the quantised rows -- except inside
+    ``prefill``, whose prompt attends over its own bf16 K / V in flight.  ``gather`` then returns the dequantised bf16
+    rows and ``gather_raw`` the bytes."""
 
     def __init__(self, model, B, cap, decode_kernels="tile", pool=None):
         _check_decode_kernels(decode_kernels)
@@ -71,6 +83,7 @@ class Decoder:
         _need(model.flat, torch.bfloat16, "model parameters")
         d = model._cdims
         self.pool, self.pages = pool, None
+        self._mx = ""
         if pool is not None:
             if pool.model is not model:
                 raise ValueError("the page pool belongs to another model")
@@ -79,6 +92,7 @@ class Decoder:
             self.max_pages = pages_for(self.cap)
             self.cap = self.max_pages * PAGE
             self.pages = PageTable(pool.alloc, self.B, self.max_pages)
+            self._mx = "_mx" if pool.kv_dtype == "mxfp8" else ""   # the suffix of the runner entries this pool takes
             self.table = torch.full((self.B, self.max_pages), -1, dtype=torch.int32, device=dev)
             self._kvp = _lib.KvPages(pool.buffer.data_ptr(), pool.buffer.numel(), self.table.data_ptr(), pool.n_pages,
                                      self.max_pages)   # include/sd_hip.h sd_kv_pages: fixed for the decoder's life
@@ -110,12 +124,20 @@ class Decoder:
 
     def gather(self, layer, b, n):
         """Copies (K, V) [n, Hkv*128] of row b's first ``n`` cached rows of one layer, through the table."""
+        rows = self.gather_raw(layer, b, n)
+        if not self._mx:
+            return rows
+        kd, ks, vd, vs = rows
+        return _mx_rows(kd, ks), _mx_rows(vd, vs)
+
+    def gather_raw(self, layer, b, n):
+        """Copies of row b's first ``n`` cached rows of one layer as the pool holds them: (K, V) bf16, or of an mxfp8 pool
+        the bytes (K data [n, Hkv*128], K scale [n, Hkv*4], V data, V scale), uint8."""
         pg = self.pages.rows[b][:pages_for(n)]
         if len(pg) < pages_for(n):
             raise ValueError(f"row {b} owns {len(self.pages.rows[b])} pages, fewer than {n} positions need")
         idx = torch.tensor(pg, dtype=torch.int64, device=self.table.device)
-        k, v = self.pool.planes(layer)
-        return k[idx].flatten(0, 1)[:n].clone(), v[idx].flatten(0, 1)[:n].clone()
+        return tuple(p[idx].flatten(0, 1)[:n].clone() for p in self.pool.planes(layer))
 
     def close(self):
         """Give every page back to the pool (host bookkeeping only)."""
@@ -154,10 +176,10 @@ class Decoder:
         nb = lib.sd_qwen3_prefill_acts_bytes(C.byref(m._cdims), B, T)
         acts = torch.empty(nb, dtype=torch.uint8, device=ids.device)
         if self.pool is not None:
-            check(lib.sd_qwen3_prefill_paged(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(),
-                                             0 if kv_len is None else kv_len.data_ptr(), self.cos.data_ptr(),
-                                             self.sin.data_ptr(), acts.data_ptr(), nb, C.byref(self._kvp),
-                                             self.logits.data_ptr(), B, T, _stream()), "sd_qwen3_prefill_paged")
+            name = "sd_qwen3_prefill_paged" + self._mx
+            check(getattr(lib, name)(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(),
+                                     0 if kv_len is None else kv_len.data_ptr(), self.cos.data_ptr(), self.sin.data_ptr(),
+                                     acts.data_ptr(), nb, C.byref(self._kvp), self.logits.data_ptr(), B, T, _stream()), name)
             return self.logits
         check(lib.sd_qwen3_prefill(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(),
                                    0 if kv_len is None else kv_len.data_ptr(), self.cos.data_ptr(), self.sin.data_ptr(),
@@ -179,10 +201,10 @@ class Decoder:
         check(min(nb, 0), "sd_qwen3_extend_acts_bytes")
         acts = torch.empty(nb, dtype=torch.uint8, device=ids.device)
         if self.pool is not None:
-            check(lib.sd_qwen3_extend_paged(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(), past.data_ptr(),
-                                            new_len.data_ptr(), self.cos.data_ptr(), self.sin.data_ptr(), acts.data_ptr(), nb,
-                                            C.byref(self._kvp), self.logits.data_ptr(), B, T, _stream()),
-                  "sd_qwen3_extend_paged")
+            name = "sd_qwen3_extend_paged" + self._mx
+            check(getattr(lib, name)(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(), past.data_ptr(),
+                                     new_len.data_ptr(), self.cos.data_ptr(), self.sin.data_ptr(), acts.data_ptr(), nb,
+                                     C.byref(self._kvp), self.logits.data_ptr(), B, T, _stream()), name)
             return self.logits
         check(lib.sd_qwen3_extend(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(), past.data_ptr(),
                                   new_len.data_ptr(), self.cos.data_ptr(), self.sin.data_ptr(), acts.data_ptr(), nb,
@@ -198,10 +220,11 @@ class Decoder:
         if ids.numel() != self.B or pos.numel() != self.B:
             raise ValueError(f"decode step wants {self.B} tokens and positions")
         if self.pool is not None:
-            check(lib.sd_qwen3_decode_step_paged(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(), pos.data_ptr(),
-                                                 int(max_len), self.cos.data_ptr(), self.sin.data_ptr(), C.byref(self._kvp),
-                                                 self.step_acts.data_ptr(), self.step_acts.numel(), self.logits.data_ptr(),
-                                                 self.B, self.flags, _stream()), "sd_qwen3_decode_step_paged")
+            name = "sd_qwen3_decode_step_paged" + self._mx
+            check(getattr(lib, name)(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(), pos.data_ptr(),
+                                     int(max_len), self.cos.data_ptr(), self.sin.data_ptr(), C.byref(self._kvp),
+                                     self.step_acts.data_ptr(), self.step_acts.numel(), self.logits.data_ptr(), self.B,
+                                     self.flags, _stream()), name)
             return self.logits
         check(lib.sd_qwen3_decode_step_flags(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(), pos.data_ptr(),
                                              int(max_len), self.cos.data_ptr(), self.sin.data_ptr(), self.cache.data_ptr(),
@@ -266,7 +289,9 @@ class GenerationSession:
     Inside the decode loop no table changes and no extra host read happens.  A pool that cannot cover the turn raises
     ValueError before anything is launched on the session's state, and no page has then changed hands.  ``reset`` releases
     the rows' pages, ``trim()`` releases the worst-case leftovers on demand, ``fork(rows)`` continues rows in a new
-    session that shares their full pages, ``close()`` (also run when the session is dropped) releases everything."""
+    session that shares their full pages, ``close()`` (also run when the session is dropped) releases everything.  A pool
+    of 8-bit pages (``kv_page_pool(..., kv_dtype="mxfp8")``) changes none of this: the decoder picks its entries from
+    the pool's dtype."""
 
     def __init__(self, model, batch_size, capacity=None, decode_kernels="tile", pool=None):
         self.model, self.B = model, int(batch_size)

@@ -966,6 +966,85 @@ def attn_decode_paged(q, k_pool, v_pool, table, lens, Hq, Hkv, max_len=None, len
     return (o, lse) if want_lse else o
 
 
+# ---- 8-bit (MXFP8) pages: planes = (k_data, k_scale, v_data, v_scale), data uint8 [n_pages, 256, Hkv*128] (e4m3 bytes),
+# scale uint8 [n_pages, 256, Hkv*4] (E8M0, one per 32 elements); the page table as above
+def _paged_mx_args(planes, table):
+    kd, ks, vd, vs = planes
+    for t, name in ((kd, "k_data"), (ks, "k_scale"), (vd, "v_data"), (vs, "v_scale")):
+        _need(t, torch.uint8, name)
+    _need(table, torch.int32, "table")
+    if (kd.dim() != 3 or kd.shape[1] != 256 or kd.shape[2] % 128 or vd.shape != kd.shape or table.dim() != 2
+            or ks.shape != (kd.shape[0], 256, kd.shape[2] // 32) or vs.shape != ks.shape):
+        raise ValueError("8-bit pool planes must be data [n_pages, 256, Hkv*128] and scale [n_pages, 256, Hkv*4] for K and "
+                         f"V and the table [B, max_pages], got {[tuple(t.shape) for t in planes]}, {tuple(table.shape)}")
+    return (kd.data_ptr(), ks.data_ptr(), vd.data_ptr(), vs.data_ptr()), table.data_ptr(), table.shape[1], kd.shape[0]
+
+
+def kvcache_store_paged_mx(qk, qkv, planes, table, kv_len, B, T, Hq, Hkv):
+    """sd_kvcache_store_paged_mx: ``kvcache_store_paged`` whose rows are stored as MXFP8."""
+    _need(qk, torch.bfloat16, "qk"), _need(qkv, torch.bfloat16, "qkv")
+    pl, tp, max_pages, n_pages = _paged_mx_args(planes, table)
+    check(load_lib().sd_kvcache_store_paged_mx(qk.data_ptr(), qkv.data_ptr(), *pl, tp, max_pages, n_pages, _p(kv_len), B, T,
+                                               Hq, Hkv, _stream()), "sd_kvcache_store_paged_mx")
+
+
+def kvcache_store_at_paged_mx(qk, qkv, planes, table, past, new_len, B, T, Hq, Hkv):
+    """sd_kvcache_store_at_paged_mx: ``kvcache_store_at_paged`` whose rows are stored as MXFP8."""
+    _need(qk, torch.bfloat16, "qk"), _need(qkv, torch.bfloat16, "qkv")
+    _need(past, torch.int32, "past"), _need(new_len, torch.int32, "new_len")
+    pl, tp, max_pages, n_pages = _paged_mx_args(planes, table)
+    check(load_lib().sd_kvcache_store_at_paged_mx(qk.data_ptr(), qkv.data_ptr(), *pl, tp, max_pages, n_pages,
+                                                  past.data_ptr(), new_len.data_ptr(), B, T, Hq, Hkv, _stream()),
+          "sd_kvcache_store_at_paged_mx")
+
+
+def qknorm_rope_append_paged_mx(qkv, q_gain, k_gain, cos, sin, pos, planes, table, Hq, Hkv, eps=1e-6):
+    """sd_qknorm_rope_append_paged_mx: ``qknorm_rope_append_paged`` whose K / V are stored as MXFP8; q is the twin's."""
+    _need(qkv, torch.bfloat16, "qkv"), _need(pos, torch.int32, "pos")
+    pl, tp, max_pages, n_pages = _paged_mx_args(planes, table)
+    B = qkv.shape[0]
+    if cos.shape[0] < max_pages * 256:
+        raise ValueError(f"rope tables hold {cos.shape[0]} positions, the page table {max_pages * 256}")
+    q = torch.empty(B, Hq * 128, dtype=torch.bfloat16, device=qkv.device)
+    check(load_lib().sd_qknorm_rope_append_paged_mx(qkv.data_ptr(), q_gain.data_ptr(), k_gain.data_ptr(), cos.data_ptr(),
+                                                    sin.data_ptr(), pos.data_ptr(), q.data_ptr(), *pl, tp, max_pages,
+                                                    n_pages, B, Hq, Hkv, eps, _stream()), "sd_qknorm_rope_append_paged_mx")
+    return q
+
+
+def attn_decode_paged_mx(q, planes, table, lens, Hq, Hkv, max_len=None, len_add=0, want_lse=False, workspace=None):
+    """sd_attn_decode_paged_mx: ``attn_decode_paged`` over MXFP8 planes; the bits of the twin on the dequantised rows."""
+    _need(q, torch.bfloat16, "q"), _need(lens, torch.int32, "lens")
+    pl, tp, max_pages, n_pages = _paged_mx_args(planes, table)
+    lib = load_lib()
+    B, cap = q.shape[0], max_pages * 256
+    nb = lib.sd_attn_decode_workspace_bytes(B, Hq, cap)
+    if workspace is None:
+        workspace = torch.empty(max(nb, 16), dtype=torch.uint8, device=q.device)
+    o = torch.empty(B, Hq * 128, dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty(B, Hq, dtype=torch.float32, device=q.device) if want_lse else None
+    check(lib.sd_attn_decode_paged_mx(q.data_ptr(), *pl, tp, max_pages, n_pages, o.data_ptr(), _p(lse), lens.data_ptr(),
+                                      int(len_add), workspace.data_ptr(), workspace.numel(), B,
+                                      cap if max_len is None else int(max_len), Hq, Hkv, 128, 128 ** -0.5, _stream()),
+          "sd_attn_decode_paged_mx")
+    return (o, lse) if want_lse else o
+
+
+def attn_extend_paged_mx(q, planes, table, past, new_len, T, Hq, Hkv, want_lse=True):
+    """sd_attn_extend_paged_mx: ``attn_extend_paged`` over MXFP8 planes; the bits of the twin on the dequantised rows."""
+    _need(past, torch.int32, "past"), _need(new_len, torch.int32, "new_len")
+    pl, tp, max_pages, n_pages = _paged_mx_args(planes, table)
+    if not q.is_cuda:
+        raise RuntimeError("speech_distill_amd: q must be a GPU tensor (no CPU fallback)")
+    B = table.shape[0]
+    o = torch.empty(B * T, Hq * 128, dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty(B, Hq, T, dtype=torch.float32, device=q.device) if want_lse else None
+    check(load_lib().sd_attn_extend_paged_mx(q.data_ptr(), *pl, tp, max_pages, n_pages, o.data_ptr(), _p(lse),
+                                             past.data_ptr(), new_len.data_ptr(), q.stride(0), o.stride(0), B, T, Hq, Hkv,
+                                             128, 128 ** -0.5, _stream()), "sd_attn_extend_paged_mx")
+    return (o, lse) if want_lse else o
+
+
 def sample_params(do_sample=True, temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, min_new_tokens=0,
                   eos_token_id=None, pad_token_id=0, use_ras=False, win_size=25, tau_r=0.2):
     """include/sd_hip.h sd_sample_params.  The RAS threshold is handed over as an integer count: count + 1 >= win_size *

@@ -9,13 +9,20 @@ Three layers, the first two pure host code (no device, no library: tests/test_pa
   ``PageAllocator``  free list + reference count per page;
   ``PageTable``      one session's rows -> pages (the host mirror of the device table) with the admission, trim and fork
                      rules; every operation that can fail checks first and changes nothing when it raises;
-  ``PagePool``       the device buffer [L][2][n_pages][256][Hkv*128] of one model plus a ``PageAllocator``.
+  ``PagePool``       the device buffer [L][2][n_pages][256][Hkv*128] of one model plus a ``PageAllocator``; with
+                     ``kv_dtype="mxfp8"`` the 8-bit pool of include/sd_hip.h (e4m3 data planes + E8M0 scale planes).
 """
 from __future__ import annotations
 
 import ctypes as C
 
 PAGE = 256   # include/sd_hip.h SD_KV_PAGE
+KV_DTYPES = ("bf16", "mxfp8")
+
+
+def check_kv_dtype(kv_dtype):
+    if kv_dtype not in KV_DTYPES:
+        raise ValueError(f"kv_dtype must be one of {KV_DTYPES}, got {kv_dtype!r}")
 
 
 def pages_for(n):
@@ -166,14 +173,20 @@ class PageTable:
 
 class PagePool:
     """The device buffer [L][2][n_pages][256][Hkv*128] (bf16) of one model's paged sessions, with the host free list and
-    reference counts (``PageAllocator``).  ``order``: the order in which free pages are handed out."""
+    reference counts (``PageAllocator``).  ``order``: the order in which free pages are handed out.
 
-    def __init__(self, model, n_pages, order=None):
+    ``kv_dtype="mxfp8"``: the 8-bit pool (include/sd_hip.h "8-bit (MXFP8) pages") -- per layer a K data plane uint8
+    [n_pages, 256, Hkv*128] (e4m3 bytes), a K scale plane uint8 [n_pages, 256, Hkv*4] (E8M0, one per 32 elements), then
+    the same two for V: 132 bytes per position and kv head where bf16 takes 256."""
+
+    def __init__(self, model, n_pages, order=None, kv_dtype="bf16"):
         import torch
         from ._lib import check, load_lib
+        check_kv_dtype(kv_dtype)      # before anything is allocated
         self.alloc = PageAllocator(n_pages, order)
-        self.model, self.n_pages = model, int(n_pages)
-        nb = load_lib().sd_kvpool_bytes(C.byref(model._cdims), self.n_pages)
+        self.model, self.n_pages, self.kv_dtype = model, int(n_pages), kv_dtype
+        size = load_lib().sd_kvpool_mx_bytes if kv_dtype == "mxfp8" else load_lib().sd_kvpool_bytes
+        nb = size(C.byref(model._cdims), self.n_pages)
         check(min(nb, 0), "sd_kvpool_bytes")
         self.buffer = torch.empty(nb, dtype=torch.uint8, device=model.flat.device)
         self.bytes_per_page = nb // self.n_pages
@@ -187,9 +200,17 @@ class PagePool:
         return self.alloc.pages_in_use
 
     def planes(self, layer):
-        """(K, V) views [n_pages, 256, Hkv*128] of one layer's pool planes."""
+        """(K, V) views [n_pages, 256, Hkv*128] of one layer's pool planes; of an mxfp8 pool the four uint8 views (K data
+        [n_pages, 256, Hkv*128], K scale [n_pages, 256, Hkv*4], V data, V scale)."""
         import torch
         kd = self.model.dims.kv_dim
+        if self.kv_dtype == "mxfp8":
+            nd, ns = self.n_pages * PAGE * kd, self.n_pages * PAGE * (kd // 32)
+            out, at = [], 2 * layer * (nd + ns)
+            for n, w in ((nd, kd), (ns, kd // 32)) * 2:
+                out.append(self.buffer[at:at + n].view(self.n_pages, PAGE, w))
+                at += n
+            return tuple(out)
         n = self.n_pages * PAGE * kd
         flat = self.buffer.view(torch.bfloat16)
         return (flat[(2 * layer) * n:(2 * layer + 1) * n].view(self.n_pages, PAGE, kd),
@@ -200,8 +221,13 @@ class PagePool:
         import torch
         if not pairs:
             return
-        planes = self.buffer.view(torch.bfloat16).view(-1, self.n_pages, PAGE * self.model.dims.kv_dim)
         dev = self.buffer.device
         src = torch.tensor([s for s, _ in pairs], dtype=torch.int64, device=dev)
         dst = torch.tensor([d for _, d in pairs], dtype=torch.int64, device=dev)
+        if self.kv_dtype == "mxfp8":    # data and scale planes have different page sizes: plane by plane
+            for layer in range(self.model.dims.num_hidden_layers):
+                for plane in self.planes(layer):
+                    plane[dst] = plane[src]
+            return
+        planes = self.buffer.view(torch.bfloat16).view(-1, self.n_pages, PAGE * self.model.dims.kv_dim)
         planes[:, dst] = planes[:, src]

@@ -883,12 +883,15 @@ class HipQwen3ForCausalLM(nn.Module):
         from .generation import GenerationSession
         return GenerationSession(self, batch_size, capacity, decode_kernels, pool=pool)
 
-    def kv_page_pool(self, n_pages, order=None):
+    def kv_page_pool(self, n_pages, order=None, kv_dtype="bf16"):
         """A ``PagePool`` (paged.py) of ``n_pages`` pages of 256 positions for this model's paged sessions
         (``start_session(..., pool=pool)``); ``order``: an optional permutation of the page numbers, the order in which
-        free pages are handed out.  One page costs ``pool.bytes_per_page`` = L * 2 * 256 * Hkv * 128 * 2 bytes."""
+        free pages are handed out.  One page costs ``pool.bytes_per_page`` = L * 2 * 256 * Hkv * 128 * 2 bytes.
+        ``kv_dtype="mxfp8"``: 8-bit pages (e4m3 elements, one E8M0 scale byte per 32 of them; include/sd_hip.h), L * 2 *
+        256 * Hkv * 132 bytes each; the sessions over such a pool quantise what they cache and attend over the quantised
+        rows.  ValueError for any other ``kv_dtype``, before anything is allocated."""
         from .paged import PagePool
-        return PagePool(self, n_pages, order)
+        return PagePool(self, n_pages, order, kv_dtype)
 
     def zero_grad(self, set_to_none: bool = True):
         # keep the flat buffer; the next backward overwrites (accumulate=0) instead of adding
