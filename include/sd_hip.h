@@ -746,6 +746,64 @@ int sd_gemv_bf16(const void* x, const void* w, void* y, const void* r, const voi
 int sd_gemv_swiglu(const void* x, const void* wgu, void* act, const void* norm_gain, float eps, int M, int I, int K,
                    void* stream);
 
+/* ---- the same GEMV over MXFP8 weights (the decode step of a model whose projections are quantised, sd_qwen3_params_mx).
+ * sd_gemv_mxfp8: y[m,n] = bf16(rs[m] * sum_k X^[m,k] * W^[n,k] + r[m,n]).  x bf16 [M,K] (row stride ldx); w_q e4m3fn [N,K]
+ *   and w_scale E8M0 [N,K/32], exactly what sd_mxfp8_quant produces for a weight; X^ is the dequantised sd_mxfp8_quant of
+ *   row m, quantised inside the kernel (the same bytes and scale bytes); rs[m] = that call's rstd, rsqrtf(ss / K + eps),
+ *   when norm != 0, else 1; r (nullable, row stride ldr) may alias y under the rule of sd_gemv_bf16.
+ * sd_gemv_mxfp8_swiglu: wgu = [gate rows | up rows] [2I,K]; g, u = bf16(rs * sum), act bf16 [M,I] = bf16(silu(g) * u) as
+ *   sd_swiglu_fwd computes it -- sd_gemv_mxfp8 with N = 2I followed by sd_swiglu_fwd, bit for bit; sd_mxfp8_quant of act
+ *   gives the bytes sd_gemm_mxfp8_swiglu emits whenever g and u agree.
+ * Every product X^ * W^ is exact in fp32.  The bits of y[m,n] depend on x[m,:], w[n,:] with its scales, r[m,n], eps and K
+ * only: not on M, N, the other rows, the grid or the CU count (one fixed summation order per element, no atomics).  The
+ * weights run as the A operand of v_mfma_scale_f32_16x16x128_f8f6f4 with their E8M0 bytes as its scale operand, read once,
+ * 16 bytes per lane, non-temporal, with no LDS staging.
+ * Supported: 1 <= M <= SD_GEMV_MAX_M, N >= 1, K % 128 == 0, K <= 8192, ldx >= K, ldy >= N, ldr >= N, x rows and w_q 16-byte
+ * aligned, w_scale 4-byte aligned; anything else that is sane is SD_ERR_UNSUPPORTED; M, N or K <= 0 or a NULL x / w_q /
+ * w_scale / y is SD_ERR_SHAPE.  Both are decided before any launch. */
+int sd_gemv_mxfp8(const void* x, int64_t ldx, const void* w_q, const void* w_scale, void* y, int64_t ldy, const void* r,
+                  int64_t ldr, int norm, float eps, int M, int N, int K, void* stream);
+int sd_gemv_mxfp8_swiglu(const void* x, const void* wgu_q, const void* wgu_scale, void* act, int norm, float eps, int M, int I,
+                         int K, void* stream);
+
+/* ---- generation on MXFP8 weights: sd_qwen3_prefill / _extend / _decode_step over sd_qwen3_params_mx.  One descriptor
+ * names the cache of any kind, so there are three entries.  kind 0: the contiguous bf16 cache (cache, cache_bytes >=
+ * sd_kvcache_bytes(d, B, cap), cap); kind 1: bf16 pages and kind 2: MXFP8 pages (pages, held against sd_kvpool_bytes /
+ * sd_kvpool_mx_bytes).  Another kind is SD_ERR_SHAPE.
+ * sd_qwen3_mx_prefill: the launches of sd_qwen3_forward_mx with the cache store behind each layer's q|k|v step and the
+ *   lm_head on each row's last valid token: logits bf16 [B,V], bit-identical to sd_qwen3_forward_mx with those head rows.
+ * sd_qwen3_mx_extend: the same forward on per-token cos / sin rows, the cache's store-at + extend attention standing where
+ *   the attention does (as sd_qwen3_extend).
+ * sd_qwen3_mx_decode_step: flags = 0 runs, per layer, sd_mxfp8_quant(x) + rstd, sd_gemm_mxfp8 (q|k|v), the cache's append
+ *   + decode attention, sd_mxfp8_quant(ao), sd_gemm_mxfp8 + residual (o), sd_mxfp8_quant(x_mid) + rstd,
+ *   sd_gemm_mxfp8_swiglu, sd_gemm_mxfp8 + residual (down); then sd_rmsnorm_fwd and the bf16 lm_head GEMM.
+ *   SD_DECODE_SKINNY (B <= SD_GEMV_MAX_M): sd_gemv_mxfp8(norm) (q|k|v), the cache step, sd_gemv_mxfp8(r = x) (o),
+ *   sd_gemv_mxfp8_swiglu(norm), sd_gemv_mxfp8(r = x_mid) (down); then sd_gemv_bf16(norm_gain = final_norm) for the lm_head.
+ *   When any GEMV of the step would refuse its shape the whole step runs the tile sequence: never a mixture.
+ * Embedding, q/k-norm + RoPE, attention, the final norm and the lm_head are the bf16 entries.  acts of the *_acts_bytes
+ * queries (the step's takes cap = the cache's capacity: cap, or max_pages * 256).  Checks and codes as the bf16 twins
+ * (SD_ERR_SHAPE, SD_ERR_WORKSPACE, SD_ERR_UNSUPPORTED for dims outside sd_qwen3_mx_supported or Hq / Hkv outside
+ * {1, 2, 4}); an unknown flag bit is SD_ERR_SHAPE; all before the first launch. */
+typedef struct {
+  int kind;              /* 0: contiguous bf16, 1: bf16 pages, 2: MXFP8 pages */
+  void* cache;           /* kind 0 */
+  int64_t cache_bytes;   /* kind 0 */
+  int cap;               /* kind 0: positions per row */
+  const sd_kv_pages* pages; /* kinds 1, 2 */
+} sd_kv_ref;
+int64_t sd_qwen3_mx_prefill_acts_bytes(const sd_qwen3_dims* d, int B, int T);
+int sd_qwen3_mx_prefill(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids, const int32_t* kv_len,
+                        const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes, const sd_kv_ref* kv,
+                        void* logits, int B, int T, void* stream);
+int64_t sd_qwen3_mx_extend_acts_bytes(const sd_qwen3_dims* d, int B, int T);
+int sd_qwen3_mx_extend(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids, const int32_t* past,
+                       const int32_t* new_len, const void* cos_tab, const void* sin_tab, void* acts, int64_t acts_bytes,
+                       const sd_kv_ref* kv, void* logits, int B, int T, void* stream);
+int64_t sd_qwen3_mx_decode_step_acts_bytes(const sd_qwen3_dims* d, int B, int cap);
+int sd_qwen3_mx_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids, const int32_t* pos,
+                            int max_len, const void* cos_tab, const void* sin_tab, const sd_kv_ref* kv, void* acts,
+                            int64_t acts_bytes, void* logits, int B, int flags, void* stream);
+
 /* ---- stream placement.  HIP multiplexes streams onto a few hardware queues (4 by default); streams that share a
  * queue never overlap.  Measures, with a `spin_us`-long busy-wait kernel on stream_a and an empty one on stream_b,
  * whether work on b runs while a is busy: *overlap = 1/0.  Synchronises both streams (a calibration call, made once

@@ -56,6 +56,11 @@ def parse_args(argv=None):
                    help="mxfp8 (needs --kv_pool_pages): the pool holds 8-bit pages -- e4m3 elements with one power-of-two "
                         "scale per 32 of them, 0.516 of the bf16 bytes; what is cached is quantised, so the tokens may "
                         "differ from the bf16 cache's")
+    p.add_argument("--weight_dtype", choices=("bf16", "mxfp8"), default="bf16",
+                   help="mxfp8: prefill and every decode step run the q|k|v, o, gate|up and down projections on MXFP8 "
+                        "weights quantised once at start-up (e4m3 with one power-of-two scale per 32 along K; the model "
+                        "is frozen for it); with --decode_kernels skinny they are streamed through the block-scaled "
+                        "GEMV.  Independent of --kv_cache_dtype; the tokens may differ from the bf16 weights'")
     args = p.parse_args(argv)
     if args.kv_cache_dtype != "bf16" and args.kv_pool_pages <= 0:
         p.error("--kv_cache_dtype mxfp8 needs --kv_pool_pages N: only the paged cache has an 8-bit form")
@@ -112,6 +117,8 @@ def main(argv=None):
     import speech_distill_amd as sda
     from speech_distill_amd.generation import cache_capacity
     model = sda.HipQwen3ForCausalLM.from_pretrained(args.checkpoint, device="cuda").eval()
+    if args.weight_dtype == "mxfp8":
+        model.requires_grad_(False)   # the quantised weights are made once: a frozen model
     dialogues = read_prompts(args.prompts)
     pad = args.pad_token_id if args.pad_token_id is not None else args.stop_token_id
     dev = model.flat.device
@@ -123,7 +130,8 @@ def main(argv=None):
             need = max(sum(len(t) for t in d) for d in chunk) + n_turns * args.max_tokens
             if need > cache_capacity(model):
                 raise ValueError(f"a dialogue of {need} positions exceeds the KV-cache capacity {cache_capacity(model)}")
-            sess = model.start_session(len(chunk), (need + 255) // 256 * 256, decode_kernels=args.decode_kernels, pool=pool)
+            sess = model.start_session(len(chunk), (need + 255) // 256 * 256, decode_kernels=args.decode_kernels, pool=pool,
+                                       weight_dtype=args.weight_dtype)
             for turn in range(n_turns):
                 ids, mask = right_pad([d[turn] for d in chunk], pad)
                 torch.cuda.synchronize()

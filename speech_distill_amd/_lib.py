@@ -80,6 +80,11 @@ class KvPages(C.Structure):  # include/sd_hip.h sd_kv_pages (the paged KV cache 
                 ("max_pages", C.c_int32)]
 
 
+class KvRef(C.Structure):  # include/sd_hip.h sd_kv_ref (the cache of any kind, for the runner entries over MXFP8 weights)
+    _fields_ = [("kind", C.c_int32), ("cache", C.c_void_p), ("cache_bytes", C.c_int64), ("cap", C.c_int32),
+                ("pages", C.POINTER(KvPages))]
+
+
 class Params(C.Structure):
     _fields_ = [("embed", C.c_void_p), ("lm_head", C.c_void_p), ("final_norm", C.c_void_p),
                 ("layers_host", C.POINTER(Layer))]
@@ -243,6 +248,18 @@ PROTOTYPES = {
                                            _vp, _i64, _vp, _i, _i, _vp]),
     "sd_gemv_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i64, _i64, _i64, _i64, _vp]),
     "sd_gemv_swiglu": (_i, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp]),
+    # the GEMV over MXFP8 weights and the generation entries over sd_qwen3_params_mx (one cache descriptor, sd_kv_ref)
+    "sd_gemv_mxfp8": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i, _f, _i, _i, _i, _vp]),
+    "sd_gemv_mxfp8_swiglu": (_i, [_vp, _vp, _vp, _vp, _i, _f, _i, _i, _i, _vp]),
+    "sd_qwen3_mx_prefill_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
+    "sd_qwen3_mx_prefill": (_i, [C.POINTER(Dims), C.POINTER(ParamsMx), _vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(KvRef), _vp,
+                                 _i, _i, _vp]),
+    "sd_qwen3_mx_extend_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
+    "sd_qwen3_mx_extend": (_i, [C.POINTER(Dims), C.POINTER(ParamsMx), _vp, _vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(KvRef),
+                                _vp, _i, _i, _vp]),
+    "sd_qwen3_mx_decode_step_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
+    "sd_qwen3_mx_decode_step": (_i, [C.POINTER(Dims), C.POINTER(ParamsMx), _vp, _vp, _i, _vp, _vp, C.POINTER(KvRef), _vp,
+                                     _i64, _vp, _i, _i, _vp]),
 }
 
 

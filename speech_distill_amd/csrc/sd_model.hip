@@ -84,101 +84,6 @@ LayerActs layer_acts(const Sizes& s, char* base, int l, int save) {
   return a;
 }
 
-// Where a prefill leaves the keys and values of its layers: the cache [L][2][B][cap][Hkv*128] of sd_kvcache_bytes
-// -- or, in the paged form (table != nullptr; llm_engine.py:91), the pool [L][2][n_pages][256][Hkv*128] of
-// sd_kvpool_bytes: cache is then the pool's base, cap = max_pages * 256, and plane() gives the layer's pool planes.  The
-// five cache kernels are reached through the members below, which pick the contiguous entry or its paged twin.
-// Third form (mx; 8-bit MXFP8 pages): the pool of sd_kvpool_mx_bytes, per layer K data | K scale | V data | V scale, and
-// the _paged_mx entries.
-struct KvSink {
-  char* cache;
-  int cap;
-  // sd_qwen3_extend: the block's rows go behind past[b] cached ones and attend over the cache (nullptr: a prefill)
-  const int32_t *past = nullptr, *new_len = nullptr;
-  const int32_t* table = nullptr;
-  int n_pages = 0, max_pages = 0;
-  bool mx = false;
-  // 8-bit pages: the data (u8 [n_pages][256][Hkv*128]) or scale (u8 [n_pages][256][Hkv*4]) plane of K (0) or V (1)
-  char* mx_plane(const Sizes& s, int l, int which, bool scale) const {
-    const int64_t data = (int64_t)n_pages * SD_KV_PAGE * s.KD;
-    return cache + ((int64_t)l * 2 + which) * (data + data / 32) + (scale ? data : 0);
-  }
-  char* plane(const Sizes& s, int B, int l, int which) const {
-    if (table) return cache + ((int64_t)l * 2 + which) * n_pages * SD_KV_PAGE * s.KD * 2;
-    return cache + ((int64_t)l * 2 + which) * B * cap * s.KD * 2;
-  }
-  int store(const Sizes& s, int l, const void* qk, const void* qkv, const int32_t* kv_len, int B, int T, void* stream) const {
-    if (mx)
-      return sd_kvcache_store_paged_mx(qk, qkv, mx_plane(s, l, 0, false), mx_plane(s, l, 0, true), mx_plane(s, l, 1, false),
-                                       mx_plane(s, l, 1, true), table, max_pages, n_pages, kv_len, B, T, s.Hq, s.Hkv, stream);
-    char *kp = plane(s, B, l, 0), *vp = plane(s, B, l, 1);
-    if (table) return sd_kvcache_store_paged(qk, qkv, kp, vp, table, max_pages, n_pages, kv_len, B, T, s.Hq, s.Hkv, stream);
-    return sd_kvcache_store(qk, qkv, kp, vp, kv_len, B, T, cap, s.Hq, s.Hkv, stream);
-  }
-  // store_at + attention of an extend block
-  int extend(const Sizes& s, int l, const void* qk, const void* qkv, void* ao, int B, int T, void* stream) const {
-    if (mx) {
-      char *kd = mx_plane(s, l, 0, false), *ks = mx_plane(s, l, 0, true), *vd = mx_plane(s, l, 1, false),
-           *vs = mx_plane(s, l, 1, true);
-      RUN(sd_kvcache_store_at_paged_mx(qk, qkv, kd, ks, vd, vs, table, max_pages, n_pages, past, new_len, B, T, s.Hq, s.Hkv,
-                                       stream));
-      return sd_attn_extend_paged_mx(qk, kd, ks, vd, vs, table, max_pages, n_pages, ao, nullptr, past, new_len, s.QK, s.QD, B,
-                                     T, s.Hq, s.Hkv, 128, kSdAttnScale, stream);
-    }
-    char *kp = plane(s, B, l, 0), *vp = plane(s, B, l, 1);
-    if (table) {
-      RUN(sd_kvcache_store_at_paged(qk, qkv, kp, vp, table, max_pages, n_pages, past, new_len, B, T, s.Hq, s.Hkv, stream));
-      return sd_attn_extend_paged(qk, kp, vp, table, max_pages, n_pages, ao, nullptr, past, new_len, s.QK, s.QD, B, T, s.Hq,
-                                  s.Hkv, 128, kSdAttnScale, stream);
-    }
-    RUN(sd_kvcache_store_at(qk, qkv, kp, vp, past, new_len, B, T, cap, s.Hq, s.Hkv, stream));
-    return sd_attn_extend(qk, kp, vp, ao, nullptr, past, new_len, s.QK, s.QD, B, T, cap, s.Hq, s.Hkv, 128, kSdAttnScale,
-                          stream);
-  }
-  // append + attention of a decode step
-  int step(const Sizes& s, int l, const sd_qwen3_layer& w, const void* qkv, void* q, void* ao, const void* cos_tab,
-           const void* sin_tab, const int32_t* pos, void* ws, int64_t ws_bytes, int B, int max_len, float eps,
-           void* stream) const {
-    if (mx) {
-      char *kd = mx_plane(s, l, 0, false), *ks = mx_plane(s, l, 0, true), *vd = mx_plane(s, l, 1, false),
-           *vs = mx_plane(s, l, 1, true);
-      RUN(sd_qknorm_rope_append_paged_mx(qkv, w.q_gain, w.k_gain, cos_tab, sin_tab, pos, q, kd, ks, vd, vs, table, max_pages,
-                                         n_pages, B, s.Hq, s.Hkv, eps, stream));
-      return sd_attn_decode_paged_mx(q, kd, ks, vd, vs, table, max_pages, n_pages, ao, nullptr, pos, 1, ws, ws_bytes, B,
-                                     max_len, s.Hq, s.Hkv, 128, kSdAttnScale, stream);
-    }
-    char *kp = plane(s, B, l, 0), *vp = plane(s, B, l, 1);
-    if (table) {
-      RUN(sd_qknorm_rope_append_paged(qkv, w.q_gain, w.k_gain, cos_tab, sin_tab, pos, q, kp, vp, table, max_pages, n_pages,
-                                      B, s.Hq, s.Hkv, eps, stream));
-      return sd_attn_decode_paged(q, kp, vp, table, max_pages, n_pages, ao, nullptr, pos, 1, ws, ws_bytes, B, max_len, s.Hq,
-                                  s.Hkv, 128, kSdAttnScale, stream);
-    }
-    RUN(sd_qknorm_rope_append(qkv, w.q_gain, w.k_gain, cos_tab, sin_tab, pos, q, kp, vp, B, cap, s.Hq, s.Hkv, eps, stream));
-    return sd_attn_decode(q, kp, vp, ao, nullptr, pos, 1, ws, ws_bytes, B, cap, max_len, s.Hq, s.Hkv, 128, kSdAttnScale,
-                          stream);
-  }
-};
-
-// the query heads per kv head the cache attention kernels serve (0, or the code to return)
-int gqa_check(const sd_qwen3_dims* d) {
-  if (d->n_kv <= 0 || d->n_q % d->n_kv) return SD_ERR_SHAPE;
-  const int G = d->n_q / d->n_kv;
-  return G != 1 && G != 2 && G != 4 ? SD_ERR_UNSUPPORTED : 0;
-}
-
-// the checked arguments of the paged runner entries -> a KvSink over the pool (0, or the code to return)
-// mx: the pool holds 8-bit pages (sd_kvpool_mx_bytes)
-int paged_sink(const sd_qwen3_dims* d, const sd_kv_pages* kv, KvSink* sink, bool mx = false) {
-  if (!kv || !kv->pool || !kv->table || kv->n_pages <= 0 || kv->max_pages <= 0 || kv->max_pages > (1 << 22))
-    return SD_ERR_SHAPE;
-  // sd_kvpool_mx_bytes = sd_kvpool_bytes x 132 / 256: 128 + 4 bytes where bf16 takes 256 per (position, kv head)
-  const int64_t bf16_bytes = sd_kvpool_bytes(d, kv->n_pages);
-  if (kv->pool_bytes < (mx ? bf16_bytes / 256 * 132 : bf16_bytes)) return SD_ERR_WORKSPACE;
-  *sink = KvSink{(char*)kv->pool, kv->max_pages * SD_KV_PAGE, nullptr, nullptr, kv->table, kv->n_pages, kv->max_pages, mx};
-  return 0;
-}
-
 // "The fused entry, or the two-kernel form when it answers SD_ERR_UNSUPPORTED": rc is what the fused entry returned
 template <class F>
 int fused_or(int rc, F two_kernel_form) { return rc == SD_ERR_UNSUPPORTED ? two_kernel_form() : rc; }
@@ -553,7 +458,8 @@ int decode_step_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int
     for (int l = 0; l < s.L; ++l) {
       const sd_qwen3_layer& w = p->layers_host[l];
       RUN(sd_gemv_bf16(a.x, w.wqkv, a.qkv, nullptr, w.ln1, d->eps, B, s.QKV, s.h, s.h, s.h, s.QKV, 0, stream));
-      RUN(kv.step(s, l, w, a.qkv, a.q, a.ao, cos_tab, sin_tab, pos, a.ws, a.ws_bytes, B, max_len, d->eps, stream));
+      RUN(kv.step(s, l, w.q_gain, w.k_gain, a.qkv, a.q, a.ao, cos_tab, sin_tab, pos, a.ws, a.ws_bytes, B, max_len, d->eps,
+                  stream));
       RUN(sd_gemv_bf16(a.ao, w.wo, a.x_mid, a.x, nullptr, 0.f, B, s.h, s.QD, s.QD, s.QD, s.h, s.h, stream));
       RUN(sd_gemv_swiglu(a.x_mid, w.wgu, a.act, w.ln2, d->eps, B, s.I, s.h, stream));
       RUN(sd_gemv_bf16(a.act, w.wdown, a.x, a.x_mid, nullptr, 0.f, B, s.h, s.I, s.I, s.I, s.h, s.h, stream));
@@ -564,7 +470,8 @@ int decode_step_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int
     const sd_qwen3_layer& w = p->layers_host[l];
     RUN(sd_rmsnorm_fwd(a.x, w.ln1, a.xn, nullptr, B, s.h, d->eps, stream));
     RUN(sd_gemm_bf16(a.xn, w.wqkv, a.qkv, nullptr, B, s.QKV, s.h, s.h, s.h, s.QKV, 0, 0, 0, stream));
-    RUN(kv.step(s, l, w, a.qkv, a.q, a.ao, cos_tab, sin_tab, pos, a.ws, a.ws_bytes, B, max_len, d->eps, stream));
+    RUN(kv.step(s, l, w.q_gain, w.k_gain, a.qkv, a.q, a.ao, cos_tab, sin_tab, pos, a.ws, a.ws_bytes, B, max_len, d->eps,
+                stream));
     RUN(sd_gemm_bf16(a.ao, w.wo, a.x_mid, a.x, B, s.h, s.QD, s.QD, s.QD, s.h, s.h, 0, 0, stream));
     RUN(sd_rmsnorm_fwd(a.x_mid, w.ln2, a.xn, nullptr, B, s.h, d->eps, stream));
     RUN(fused_or(sd_gemm_swiglu(a.xn, w.wgu, nullptr, a.act, B, s.I, s.h, stream), [&] {

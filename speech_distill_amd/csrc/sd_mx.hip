@@ -407,8 +407,12 @@ extern "C" int64_t sd_qwen3_mx_acts_bytes(const sd_qwen3_dims* d, int B, int T) 
   return MxActs(d, B, T, nullptr).total;
 }
 
-extern "C" int sd_qwen3_forward_mx(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const sd_qwen3_batch* bt, void* acts,
-                                   int64_t acts_bytes, void* logits, int flags, void* stream) {
+// The forward of sd_qwen3_forward_mx and of the two block entries over a KV cache below.  sink (sd_qwen3_mx_prefill): each
+// layer's K / V rows below kv_len also go to planes l of the cache, right behind the layer's q|k|v step.  sink->past
+// (sd_qwen3_mx_extend): bt's cos/sin tables hold one row per TOKEN (sd_rope_rows_at) and sink->extend stands where the
+// attention does, as in layer_forward of the bf16 runner.
+static int forward_mx_impl(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const sd_qwen3_batch* bt, void* acts,
+                           int64_t acts_bytes, void* logits, int flags, void* stream, const KvSink* sink) {
   if (!d || !p || !mx_supported(d)) return SD_ERR_UNSUPPORTED;
   RUN(sd_batch_check(bt));
   if (flags & ~SD_FWD_CONCURRENT) return SD_ERR_SHAPE;
@@ -417,6 +421,8 @@ extern "C" int sd_qwen3_forward_mx(const sd_qwen3_dims* d, const sd_qwen3_params
   if (acts_bytes < a.total) return SD_ERR_WORKSPACE;
   SdSharedGpuScope shared((flags & SD_FWD_CONCURRENT) ? 1 : 0);  // read by the bf16 GEMM dispatch (lm_head)
   const int M = a.M, h = a.h;
+  const bool extend = sink && sink->past;
+  const int Trope = extend ? M : T;  // per-token tables: row m of them belongs to token m
   char* x_cur = a.x_a;
   RUN(sd_embedding_fwd(bt->ids, p->embed, x_cur, M, h, a.V, stream));
   for (int l = 0; l < a.L; ++l) {
@@ -426,8 +432,13 @@ extern "C" int sd_qwen3_forward_mx(const sd_qwen3_dims* d, const sd_qwen3_params
     RUN(sd_mxfp8_quant(x_cur, h, a.xq, a.xs, (float*)a.rstd, d->eps, M, h, stream));
     RUN(sd_gemm_mxfp8(a.xq, a.xs, w.wqkv_q, w.wqkv_scale, a.qkv, nullptr, (const float*)a.rstd, M, a.QKV, h, a.QKV, 0,
                       stream));
-    RUN(sd_qknorm_rope_fwd(a.qkv, w.q_gain, w.k_gain, bt->cos_tab, bt->sin_tab, a.qk, M, T, a.Hq, a.Hkv, d->eps, stream));
-    RUN(sd_layer_attn_fwd(a, *bt, a.qk, a.qkv, a.ao, a.lse, stream));
+    RUN(sd_qknorm_rope_fwd(a.qkv, w.q_gain, w.k_gain, bt->cos_tab, bt->sin_tab, a.qk, M, Trope, a.Hq, a.Hkv, d->eps, stream));
+    if (extend) {
+      RUN(sink->extend(a, l, a.qk, a.qkv, a.ao, B, T, stream));
+    } else {
+      if (sink) RUN(sink->store(a, l, a.qk, a.qkv, bt->kv_len, B, T, stream));
+      RUN(sd_layer_attn_fwd(a, *bt, a.qk, a.qkv, a.ao, a.lse, stream));
+    }
     RUN(sd_mxfp8_quant(a.ao, a.QD, a.aoq, a.aos, nullptr, 0.f, M, a.QD, stream));
     RUN(sd_gemm_mxfp8(a.aoq, a.aos, w.wo_q, w.wo_scale, a.x_mid, x_cur, nullptr, M, h, a.QD, h, h, stream));
     // post-attention RMSNorm folded into wgu the same way (HF:59-64, 81-83)
@@ -437,4 +448,167 @@ extern "C" int sd_qwen3_forward_mx(const sd_qwen3_dims* d, const sd_qwen3_params
     x_cur = x_out;
   }
   return sd_head_fwd(d, a, *bt, x_cur, p->final_norm, p->lm_head, a.rstd_f, a.xn_f, a.xn_rows, logits, stream);
+}
+
+extern "C" int sd_qwen3_forward_mx(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const sd_qwen3_batch* bt, void* acts,
+                                   int64_t acts_bytes, void* logits, int flags, void* stream) {
+  return forward_mx_impl(d, p, bt, acts, acts_bytes, logits, flags, stream, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------ generation on MXFP8 weights
+// (llm_engine.py:37-76: prefill the prompt once, then one token per step over the cache) -- the three runner entries of
+// sd_model.hip over sd_qwen3_params_mx; one descriptor (sd_kv_ref) names the cache of any of the three kinds.
+namespace {
+
+// the descriptor -> a KvSink (0, or the code to return); B is positive
+int ref_sink(const sd_qwen3_dims* d, const sd_kv_ref* kv, int B, KvSink* sink) {
+  if (kv->kind == 1 || kv->kind == 2) return paged_sink(d, kv->pages, sink, kv->kind == 2);
+  if (kv->kind != 0 || !kv->cache || kv->cap <= 0) return SD_ERR_SHAPE;
+  if (kv->cache_bytes < sd_kvcache_bytes(d, B, kv->cap)) return SD_ERR_WORKSPACE;
+  *sink = KvSink{(char*)kv->cache, kv->cap};
+  return 0;
+}
+
+// head rows behind the forward's activation set -- for an extend also the gathered cos / sin rows -- then the forward
+int block_forward_mx(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids, const int32_t* kv_len,
+                     const void* cos_tab, const void* sin_tab, void* acts, void* logits, int B, int T, void* stream,
+                     const KvSink& sink) {
+  const int64_t base = al(sd_qwen3_mx_acts_bytes(d, B, T));
+  int64_t* rows = (int64_t*)((char*)acts + base);
+  RUN(sd_last_rows(sink.past ? sink.new_len : kv_len, rows, B, T, stream));
+  sd_qwen3_batch bt = {ids, kv_len, nullptr, cos_tab, sin_tab, rows, B, B, T, 0};
+  if (sink.past) {  // (an extend has no kv_len)
+    char* cos_rows = (char*)acts + al(sd_qwen3_mx_prefill_acts_bytes(d, B, T));
+    char* sin_rows = cos_rows + al((int64_t)B * T * 128 * 2);
+    RUN(sd_rope_rows_at(cos_tab, sin_tab, sink.past, cos_rows, sin_rows, B, T, sink.cap, stream));
+    bt.cos_tab = cos_rows; bt.sin_tab = sin_rows;
+  }
+  return forward_mx_impl(d, p, &bt, acts, base, logits, 0, stream, &sink);
+}
+
+// The buffers of a decode step: the bf16 rows of both kinds of step, the MXFP8 operands of the tile kind, the attention's
+// workspace
+struct MxDecodeActs : SdShape {
+  char *x, *x_mid, *xn, *qkv, *q, *ao, *act, *xq, *xs, *rstd, *aoq, *aos, *actq, *acts, *ws;
+  int64_t ws_bytes, total;
+  MxDecodeActs(const sd_qwen3_dims* d, int B, int cap, char* p) : SdShape(d, B, 1) {
+    int64_t off = 0;  // (p == nullptr: a size query, no address is formed)
+    auto take = [&](int64_t n) { char* q = p ? p + off : nullptr; off += al(n); return q; };
+    const int64_t xb = (int64_t)M * h * 2;
+    x = take(xb); x_mid = take(xb); xn = take(xb);
+    qkv = take((int64_t)M * QKV * 2); q = take((int64_t)M * QD * 2); ao = take((int64_t)M * QD * 2);
+    act = take((int64_t)M * I * 2);
+    xq = take((int64_t)M * h); xs = take((int64_t)M * h / 32); rstd = take((int64_t)M * 4);
+    aoq = take((int64_t)M * QD); aos = take((int64_t)M * QD / 32);
+    actq = take((int64_t)M * I); acts = take((int64_t)M * I / 32);
+    ws_bytes = sd_attn_decode_workspace_bytes(B, Hq, cap);
+    ws = take(ws_bytes);
+    total = off;
+  }
+};
+
+// true when every GEMV of a skinny step accepts its shape: decided for the whole step before the first launch
+bool skinny_mx_ok(const sd_qwen3_params_mx* p, const MxDecodeActs& a, const void* logits, int B) {
+  bool ok = sd_gemv_check(a.x, p->lm_head, logits, nullptr, p->final_norm, B, a.V, a.h, a.h, a.h, a.V, 0) == 0;
+  for (int l = 0; ok && l < a.L; ++l) {
+    const sd_qwen3_layer_mx& w = p->layers_host[l];
+    ok = sd_gemv_mx_check(a.x, a.h, w.wqkv_q, w.wqkv_scale, a.qkv, a.QKV, nullptr, 0, B, a.QKV, a.h) == 0 &&
+         sd_gemv_mx_check(a.ao, a.QD, w.wo_q, w.wo_scale, a.x_mid, a.h, a.x, a.h, B, a.h, a.QD) == 0 &&
+         sd_gemv_mx_check(a.x_mid, a.h, w.wgu_q, w.wgu_scale, a.act, a.I, nullptr, 0, B, a.I, a.h) == 0 &&
+         sd_gemv_mx_check(a.act, a.I, w.wdown_q, w.wdown_scale, a.x, a.h, a.x_mid, a.h, B, a.h, a.I) == 0;
+  }
+  return ok;
+}
+
+}  // namespace
+
+extern "C" int64_t sd_qwen3_mx_prefill_acts_bytes(const sd_qwen3_dims* d, int B, int T) {
+  const int64_t base = sd_qwen3_mx_acts_bytes(d, B, T);
+  return base < 0 ? base : al(base) + al((int64_t)B * 8);  // + the head rows (int64 [B])
+}
+
+extern "C" int sd_qwen3_mx_prefill(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids,
+                                   const int32_t* kv_len, const void* cos_tab, const void* sin_tab, void* acts,
+                                   int64_t acts_bytes, const sd_kv_ref* kv, void* logits, int B, int T, void* stream) {
+  if (!d || !p || !kv) return SD_ERR_SHAPE;
+  if (!mx_supported(d)) return SD_ERR_UNSUPPORTED;
+  if (B <= 0 || T <= 0 || !logits || !ids || !acts) return SD_ERR_SHAPE;
+  KvSink sink = {};
+  RUN(ref_sink(d, kv, B, &sink));
+  if (sink.cap < T) return SD_ERR_SHAPE;
+  if (acts_bytes < sd_qwen3_mx_prefill_acts_bytes(d, B, T)) return SD_ERR_WORKSPACE;
+  return block_forward_mx(d, p, ids, kv_len, cos_tab, sin_tab, acts, logits, B, T, stream, sink);
+}
+
+extern "C" int64_t sd_qwen3_mx_extend_acts_bytes(const sd_qwen3_dims* d, int B, int T) {
+  if (!d) return SD_ERR_SHAPE;
+  const int64_t base = sd_qwen3_mx_prefill_acts_bytes(d, B, T);
+  return base < 0 ? base : al(base) + 2 * al((int64_t)B * T * 128 * 2);
+}
+
+extern "C" int sd_qwen3_mx_extend(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids,
+                                  const int32_t* past, const int32_t* new_len, const void* cos_tab, const void* sin_tab,
+                                  void* acts, int64_t acts_bytes, const sd_kv_ref* kv, void* logits, int B, int T,
+                                  void* stream) {
+  if (!d || !p || !kv) return SD_ERR_SHAPE;
+  if (!mx_supported(d)) return SD_ERR_UNSUPPORTED;
+  if (B <= 0 || T <= 0 || !ids || !past || !new_len || !cos_tab || !sin_tab || !acts || !logits) return SD_ERR_SHAPE;
+  KvSink sink = {};
+  RUN(ref_sink(d, kv, B, &sink));
+  if (sink.cap < T) return SD_ERR_SHAPE;
+  RUN(gqa_check(d));
+  if (acts_bytes < sd_qwen3_mx_extend_acts_bytes(d, B, T)) return SD_ERR_WORKSPACE;
+  sink.past = past; sink.new_len = new_len;
+  return block_forward_mx(d, p, ids, nullptr, cos_tab, sin_tab, acts, logits, B, T, stream, sink);
+}
+
+extern "C" int64_t sd_qwen3_mx_decode_step_acts_bytes(const sd_qwen3_dims* d, int B, int cap) {
+  if (!d || !mx_supported(d)) return SD_ERR_UNSUPPORTED;
+  if (B <= 0 || cap <= 0) return SD_ERR_SHAPE;
+  return MxDecodeActs(d, B, cap, nullptr).total;
+}
+
+extern "C" int sd_qwen3_mx_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids,
+                                       const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab,
+                                       const sd_kv_ref* kvr, void* acts, int64_t acts_bytes, void* logits, int B, int flags,
+                                       void* stream) {
+  if (flags & ~SD_DECODE_SKINNY) return SD_ERR_SHAPE;
+  if (!d || !p || !kvr) return SD_ERR_SHAPE;
+  if (!mx_supported(d)) return SD_ERR_UNSUPPORTED;
+  if (B <= 0 || max_len <= 0 || !ids || !pos || !logits || !acts) return SD_ERR_SHAPE;
+  RUN(gqa_check(d));
+  KvSink kv = {};
+  RUN(ref_sink(d, kvr, B, &kv));
+  const MxDecodeActs a(d, B, kv.cap, (char*)acts);
+  if (acts_bytes < a.total) return SD_ERR_WORKSPACE;
+  const int h = a.h;
+  const float eps = d->eps;
+  const bool skinny = (flags & SD_DECODE_SKINNY) && skinny_mx_ok(p, a, logits, B);
+  RUN(sd_embedding_fwd(ids, p->embed, a.x, B, h, a.V, stream));
+  if (skinny) {
+    for (int l = 0; l < a.L; ++l) {
+      const sd_qwen3_layer_mx& w = p->layers_host[l];
+      RUN(sd_gemv_mxfp8(a.x, h, w.wqkv_q, w.wqkv_scale, a.qkv, a.QKV, nullptr, 0, 1, eps, B, a.QKV, h, stream));
+      RUN(kv.step(a, l, w.q_gain, w.k_gain, a.qkv, a.q, a.ao, cos_tab, sin_tab, pos, a.ws, a.ws_bytes, B, max_len, eps,
+                  stream));
+      RUN(sd_gemv_mxfp8(a.ao, a.QD, w.wo_q, w.wo_scale, a.x_mid, h, a.x, h, 0, 0.f, B, h, a.QD, stream));
+      RUN(sd_gemv_mxfp8_swiglu(a.x_mid, w.wgu_q, w.wgu_scale, a.act, 1, eps, B, a.I, h, stream));
+      RUN(sd_gemv_mxfp8(a.act, a.I, w.wdown_q, w.wdown_scale, a.x, h, a.x_mid, h, 0, 0.f, B, h, a.I, stream));
+    }
+    return sd_gemv_bf16(a.x, p->lm_head, logits, nullptr, p->final_norm, eps, B, a.V, h, h, h, a.V, 0, stream);
+  }
+  for (int l = 0; l < a.L; ++l) {
+    const sd_qwen3_layer_mx& w = p->layers_host[l];
+    RUN(sd_mxfp8_quant(a.x, h, a.xq, a.xs, (float*)a.rstd, eps, B, h, stream));
+    RUN(sd_gemm_mxfp8(a.xq, a.xs, w.wqkv_q, w.wqkv_scale, a.qkv, nullptr, (const float*)a.rstd, B, a.QKV, h, a.QKV, 0,
+                      stream));
+    RUN(kv.step(a, l, w.q_gain, w.k_gain, a.qkv, a.q, a.ao, cos_tab, sin_tab, pos, a.ws, a.ws_bytes, B, max_len, eps, stream));
+    RUN(sd_mxfp8_quant(a.ao, a.QD, a.aoq, a.aos, nullptr, 0.f, B, a.QD, stream));
+    RUN(sd_gemm_mxfp8(a.aoq, a.aos, w.wo_q, w.wo_scale, a.x_mid, a.x, nullptr, B, h, a.QD, h, h, stream));
+    RUN(sd_mxfp8_quant(a.x_mid, h, a.xq, a.xs, (float*)a.rstd, eps, B, h, stream));
+    RUN(sd_gemm_mxfp8_swiglu(a.xq, a.xs, w.wgu_q, w.wgu_scale, (const float*)a.rstd, a.actq, a.acts, B, a.I, h, stream));
+    RUN(sd_gemm_mxfp8(a.actq, a.acts, w.wdown_q, w.wdown_scale, a.x, a.x_mid, nullptr, B, h, a.I, h, h, stream));
+  }
+  RUN(sd_rmsnorm_fwd(a.x, p->final_norm, a.xn, nullptr, B, h, eps, stream));
+  return sd_gemm_bf16(a.xn, p->lm_head, logits, nullptr, B, a.V, h, h, h, a.V, 0, 0, 0, stream);
 }

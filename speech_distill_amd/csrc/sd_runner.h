@@ -38,6 +38,107 @@ struct SdQkv {
   SdQkv(const SdShape& s, char* qk, char* qkv) : q(qk), k(qk + (int64_t)s.QD * 2), v(qkv + (int64_t)(s.QD + s.KD) * 2) {}
 };
 
+// sd_gemv_mx.hip: the checks of sd_gemv_mxfp8 (and, with ldy = N = I and no residual, of sd_gemv_mxfp8_swiglu) without a
+// launch.  The skinny MXFP8 decode step asks them for every projection before its first launch.  Internal.
+__attribute__((visibility("hidden"))) int sd_gemv_mx_check(const void* x, int64_t ldx, const void* w_q, const void* w_scale,
+                                                           const void* y, int64_t ldy, const void* r, int64_t ldr, int M,
+                                                           int N, int K);
+
+// Where a prefill leaves the keys and values of its layers: the cache [L][2][B][cap][Hkv*128] of sd_kvcache_bytes
+// -- or, in the paged form (table != nullptr; llm_engine.py:91), the pool [L][2][n_pages][256][Hkv*128] of
+// sd_kvpool_bytes: cache is then the pool's base, cap = max_pages * 256, and plane() gives the layer's pool planes.  The
+// five cache kernels are reached through the members below, which pick the contiguous entry or its paged twin.
+// Third form (mx; 8-bit MXFP8 pages): the pool of sd_kvpool_mx_bytes, per layer K data | K scale | V data | V scale, and
+// the _paged_mx entries.  Shared by the bf16 runner entries (sd_model.hip) and the MXFP8-weight ones (sd_mx.hip).
+struct KvSink {
+  char* cache;
+  int cap;
+  // sd_qwen3_extend: the block's rows go behind past[b] cached ones and attend over the cache (nullptr: a prefill)
+  const int32_t *past = nullptr, *new_len = nullptr;
+  const int32_t* table = nullptr;
+  int n_pages = 0, max_pages = 0;
+  bool mx = false;
+  // 8-bit pages: the data (u8 [n_pages][256][Hkv*128]) or scale (u8 [n_pages][256][Hkv*4]) plane of K (0) or V (1)
+  char* mx_plane(const SdShape& s, int l, int which, bool scale) const {
+    const int64_t data = (int64_t)n_pages * SD_KV_PAGE * s.KD;
+    return cache + ((int64_t)l * 2 + which) * (data + data / 32) + (scale ? data : 0);
+  }
+  char* plane(const SdShape& s, int B, int l, int which) const {
+    if (table) return cache + ((int64_t)l * 2 + which) * n_pages * SD_KV_PAGE * s.KD * 2;
+    return cache + ((int64_t)l * 2 + which) * B * cap * s.KD * 2;
+  }
+  int store(const SdShape& s, int l, const void* qk, const void* qkv, const int32_t* kv_len, int B, int T, void* stream) const {
+    if (mx)
+      return sd_kvcache_store_paged_mx(qk, qkv, mx_plane(s, l, 0, false), mx_plane(s, l, 0, true), mx_plane(s, l, 1, false),
+                                       mx_plane(s, l, 1, true), table, max_pages, n_pages, kv_len, B, T, s.Hq, s.Hkv, stream);
+    char *kp = plane(s, B, l, 0), *vp = plane(s, B, l, 1);
+    if (table) return sd_kvcache_store_paged(qk, qkv, kp, vp, table, max_pages, n_pages, kv_len, B, T, s.Hq, s.Hkv, stream);
+    return sd_kvcache_store(qk, qkv, kp, vp, kv_len, B, T, cap, s.Hq, s.Hkv, stream);
+  }
+  // store_at + attention of an extend block
+  int extend(const SdShape& s, int l, const void* qk, const void* qkv, void* ao, int B, int T, void* stream) const {
+    if (mx) {
+      char *kd = mx_plane(s, l, 0, false), *ks = mx_plane(s, l, 0, true), *vd = mx_plane(s, l, 1, false),
+           *vs = mx_plane(s, l, 1, true);
+      RUN(sd_kvcache_store_at_paged_mx(qk, qkv, kd, ks, vd, vs, table, max_pages, n_pages, past, new_len, B, T, s.Hq, s.Hkv,
+                                       stream));
+      return sd_attn_extend_paged_mx(qk, kd, ks, vd, vs, table, max_pages, n_pages, ao, nullptr, past, new_len, s.QK, s.QD, B,
+                                     T, s.Hq, s.Hkv, 128, kSdAttnScale, stream);
+    }
+    char *kp = plane(s, B, l, 0), *vp = plane(s, B, l, 1);
+    if (table) {
+      RUN(sd_kvcache_store_at_paged(qk, qkv, kp, vp, table, max_pages, n_pages, past, new_len, B, T, s.Hq, s.Hkv, stream));
+      return sd_attn_extend_paged(qk, kp, vp, table, max_pages, n_pages, ao, nullptr, past, new_len, s.QK, s.QD, B, T, s.Hq,
+                                  s.Hkv, 128, kSdAttnScale, stream);
+    }
+    RUN(sd_kvcache_store_at(qk, qkv, kp, vp, past, new_len, B, T, cap, s.Hq, s.Hkv, stream));
+    return sd_attn_extend(qk, kp, vp, ao, nullptr, past, new_len, s.QK, s.QD, B, T, cap, s.Hq, s.Hkv, 128, kSdAttnScale,
+                          stream);
+  }
+  // append + attention of a decode step (q_gain, k_gain: the layer's q/k-norm gains)
+  int step(const SdShape& s, int l, const void* q_gain, const void* k_gain, const void* qkv, void* q, void* ao,
+           const void* cos_tab, const void* sin_tab, const int32_t* pos, void* ws, int64_t ws_bytes, int B, int max_len,
+           float eps, void* stream) const {
+    if (mx) {
+      char *kd = mx_plane(s, l, 0, false), *ks = mx_plane(s, l, 0, true), *vd = mx_plane(s, l, 1, false),
+           *vs = mx_plane(s, l, 1, true);
+      RUN(sd_qknorm_rope_append_paged_mx(qkv, q_gain, k_gain, cos_tab, sin_tab, pos, q, kd, ks, vd, vs, table, max_pages,
+                                         n_pages, B, s.Hq, s.Hkv, eps, stream));
+      return sd_attn_decode_paged_mx(q, kd, ks, vd, vs, table, max_pages, n_pages, ao, nullptr, pos, 1, ws, ws_bytes, B,
+                                     max_len, s.Hq, s.Hkv, 128, kSdAttnScale, stream);
+    }
+    char *kp = plane(s, B, l, 0), *vp = plane(s, B, l, 1);
+    if (table) {
+      RUN(sd_qknorm_rope_append_paged(qkv, q_gain, k_gain, cos_tab, sin_tab, pos, q, kp, vp, table, max_pages, n_pages, B,
+                                      s.Hq, s.Hkv, eps, stream));
+      return sd_attn_decode_paged(q, kp, vp, table, max_pages, n_pages, ao, nullptr, pos, 1, ws, ws_bytes, B, max_len, s.Hq,
+                                  s.Hkv, 128, kSdAttnScale, stream);
+    }
+    RUN(sd_qknorm_rope_append(qkv, q_gain, k_gain, cos_tab, sin_tab, pos, q, kp, vp, B, cap, s.Hq, s.Hkv, eps, stream));
+    return sd_attn_decode(q, kp, vp, ao, nullptr, pos, 1, ws, ws_bytes, B, cap, max_len, s.Hq, s.Hkv, 128, kSdAttnScale,
+                          stream);
+  }
+};
+
+// the query heads per kv head the cache attention kernels serve (0, or the code to return)
+static inline int gqa_check(const sd_qwen3_dims* d) {
+  if (d->n_kv <= 0 || d->n_q % d->n_kv) return SD_ERR_SHAPE;
+  const int G = d->n_q / d->n_kv;
+  return G != 1 && G != 2 && G != 4 ? SD_ERR_UNSUPPORTED : 0;
+}
+
+// the checked arguments of the paged runner entries -> a KvSink over the pool (0, or the code to return)
+// mx: the pool holds 8-bit pages (sd_kvpool_mx_bytes)
+static inline int paged_sink(const sd_qwen3_dims* d, const sd_kv_pages* kv, KvSink* sink, bool mx = false) {
+  if (!kv || !kv->pool || !kv->table || kv->n_pages <= 0 || kv->max_pages <= 0 || kv->max_pages > (1 << 22))
+    return SD_ERR_SHAPE;
+  // sd_kvpool_mx_bytes = sd_kvpool_bytes x 132 / 256: 128 + 4 bytes where bf16 takes 256 per (position, kv head)
+  const int64_t bf16_bytes = sd_kvpool_bytes(d, kv->n_pages);
+  if (kv->pool_bytes < (mx ? bf16_bytes / 256 * 132 : bf16_bytes)) return SD_ERR_WORKSPACE;
+  *sink = KvSink{(char*)kv->pool, kv->max_pages * SD_KV_PAGE, nullptr, nullptr, kv->table, kv->n_pages, kv->max_pages, mx};
+  return 0;
+}
+
 // every check a batch descriptor must pass before anything is launched
 static inline int sd_batch_check(const sd_qwen3_batch* b) {
   if (!b || b->B <= 0 || b->T <= 0) return SD_ERR_SHAPE;

@@ -31,6 +31,7 @@ from .paged import PAGE, PageTable, pages_for
 REFERENCE_SAMPLING = dict(do_sample=True, temperature=0.6, top_k=100, top_p=0.9, repetition_penalty=1.25, use_ras=True,
                           win_size=25, tau_r=0.2)  # soulxpodcast/config.py:107-118
 DECODE_KERNELS = ("tile", "skinny")
+WEIGHT_DTYPES = ("bf16", "mxfp8")
 DEFAULT_CACHE_CAPACITY = 32768  # positions; Qwen3's max_position_embeddings when the config does not say
 
 
@@ -44,6 +45,21 @@ def cache_capacity(model):
 def _check_decode_kernels(decode_kernels):
     if decode_kernels not in DECODE_KERNELS:
         raise ValueError(f"decode_kernels must be one of {DECODE_KERNELS}, got {decode_kernels!r}")
+
+
+def _check_weight_dtype(model, weight_dtype):
+    """The weights a generation decodes with.  "bf16": the unfolded bf16 weights, for a model whose inference precision is
+    "bf16" (NotImplementedError otherwise, as before the keyword existed).  "mxfp8": the model's quantised, gain-folded
+    projections (``_mx_params``), whatever its inference precision; needs what ``set_inference_precision("mxfp8")`` needs
+    (ValueError).  Raises before anything is allocated or launched."""
+    if weight_dtype not in WEIGHT_DTYPES:
+        raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, got {weight_dtype!r}")
+    if weight_dtype == "mxfp8":
+        model._check_mx()
+    elif model.inference_precision != "bf16":
+        raise NotImplementedError('generate() decodes with the unfolded bf16 weights; this model runs "'
+                                  f'{model.inference_precision}" (set_inference_precision("bf16") first, or pass '
+                                  'weight_dtype="mxfp8" to decode with the quantised weights)')
 
 
 def _mx_rows(data, scale):
@@ -69,14 +85,18 @@ class Decoder:
     A pool made with ``kv_dtype="mxfp8"`` selects the ``_paged_mx`` entries (8-bit pages, include/sd_hip.h): the rows are
     quantised as they are cached and every attention over the cache reads the quantised rows -- except inside
     ``prefill``, whose prompt attends over its own bf16 K / V in flight.  ``gather`` then returns the dequantised bf16
-    rows and ``gather_raw`` the bytes."""
+    rows and ``gather_raw`` the bytes.
 
-    def __init__(self, model, B, cap, decode_kernels="tile", pool=None):
+    ``weight_dtype="mxfp8"`` (independent of the model's inference precision and of the cache kind): the three calls run
+    the sd_qwen3_mx_* entries on ``model._mx_params()`` -- the four projections of every layer in MXFP8, fetched on every
+    call so that ``.to()``, ``load_state_dict`` and the other invalidations are honoured; "skinny" then streams the 8-bit
+    weights through sd_gemv_mxfp8.  Embedding, attention, the norms of q / k, the final norm and the lm_head stay bf16."""
+
+    def __init__(self, model, B, cap, decode_kernels="tile", pool=None, weight_dtype="bf16"):
         _check_decode_kernels(decode_kernels)
+        _check_weight_dtype(model, weight_dtype)
         self.flags = 1 if decode_kernels == "skinny" else 0   # include/sd_hip.h SD_DECODE_SKINNY
-        if model.inference_precision != "bf16":
-            raise NotImplementedError('generate() decodes with the unfolded bf16 weights; this model runs "'
-                                      f'{model.inference_precision}" (set_inference_precision("bf16") first)')
+        self.weight_dtype = weight_dtype
         self.model, self.B, self.cap = model, int(B), int(cap)
         lib = load_lib()
         dev = model.flat.device
@@ -101,8 +121,16 @@ class Decoder:
             nb = lib.sd_kvcache_bytes(C.byref(d), self.B, self.cap)
             check(min(nb, 0), "sd_kvcache_bytes")
             self.cache = torch.empty(nb, dtype=torch.uint8, device=dev)
-        self.step_acts = torch.empty(lib.sd_qwen3_decode_acts_bytes(C.byref(d), self.B, self.cap), dtype=torch.uint8,
-                                     device=dev)
+        if weight_dtype == "mxfp8":   # include/sd_hip.h sd_kv_ref: fixed for the decoder's life
+            if pool is not None:
+                self._kvref = _lib.KvRef(2 if self._mx else 1, None, 0, 0, C.pointer(self._kvp))
+            else:
+                self._kvref = _lib.KvRef(0, self.cache.data_ptr(), self.cache.numel(), self.cap, None)
+            nb = lib.sd_qwen3_mx_decode_step_acts_bytes(C.byref(d), self.B, self.cap)
+            check(min(nb, 0), "sd_qwen3_mx_decode_step_acts_bytes")
+        else:
+            nb = lib.sd_qwen3_decode_acts_bytes(C.byref(d), self.B, self.cap)
+        self.step_acts = torch.empty(nb, dtype=torch.uint8, device=dev)
         self.cos, self.sin = model._tables(self.cap, dev)
         self.logits = torch.empty(self.B, model.dims.vocab_size, dtype=torch.bfloat16, device=dev)
 
@@ -173,6 +201,15 @@ class Decoder:
         B, T = ids.shape
         if B != self.B or T > self.cap:
             raise ValueError(f"prefill of {tuple(ids.shape)} into a cache for {self.B} rows of {self.cap} positions")
+        if self.weight_dtype == "mxfp8":
+            nb = lib.sd_qwen3_mx_prefill_acts_bytes(C.byref(m._cdims), B, T)
+            check(min(nb, 0), "sd_qwen3_mx_prefill_acts_bytes")
+            acts = torch.empty(nb, dtype=torch.uint8, device=ids.device)
+            check(lib.sd_qwen3_mx_prefill(C.byref(m._cdims), C.byref(m._mx_params()), ids.data_ptr(),
+                                          0 if kv_len is None else kv_len.data_ptr(), self.cos.data_ptr(),
+                                          self.sin.data_ptr(), acts.data_ptr(), nb, C.byref(self._kvref),
+                                          self.logits.data_ptr(), B, T, _stream()), "sd_qwen3_mx_prefill")
+            return self.logits
         nb = lib.sd_qwen3_prefill_acts_bytes(C.byref(m._cdims), B, T)
         acts = torch.empty(nb, dtype=torch.uint8, device=ids.device)
         if self.pool is not None:
@@ -197,6 +234,15 @@ class Decoder:
         B, T = ids.shape
         if B != self.B or T < 1 or T > self.cap or past.numel() != B or new_len.numel() != B:
             raise ValueError(f"extend of {tuple(ids.shape)} into a cache for {self.B} rows of {self.cap} positions")
+        if self.weight_dtype == "mxfp8":
+            nb = lib.sd_qwen3_mx_extend_acts_bytes(C.byref(m._cdims), B, T)
+            check(min(nb, 0), "sd_qwen3_mx_extend_acts_bytes")
+            acts = torch.empty(nb, dtype=torch.uint8, device=ids.device)
+            check(lib.sd_qwen3_mx_extend(C.byref(m._cdims), C.byref(m._mx_params()), ids.data_ptr(), past.data_ptr(),
+                                         new_len.data_ptr(), self.cos.data_ptr(), self.sin.data_ptr(), acts.data_ptr(), nb,
+                                         C.byref(self._kvref), self.logits.data_ptr(), B, T, _stream()),
+                  "sd_qwen3_mx_extend")
+            return self.logits
         nb = lib.sd_qwen3_extend_acts_bytes(C.byref(m._cdims), B, T)
         check(min(nb, 0), "sd_qwen3_extend_acts_bytes")
         acts = torch.empty(nb, dtype=torch.uint8, device=ids.device)
@@ -219,6 +265,12 @@ class Decoder:
         _need(ids, torch.int64, "ids"), _need(pos, torch.int32, "pos")
         if ids.numel() != self.B or pos.numel() != self.B:
             raise ValueError(f"decode step wants {self.B} tokens and positions")
+        if self.weight_dtype == "mxfp8":
+            check(lib.sd_qwen3_mx_decode_step(C.byref(m._cdims), C.byref(m._mx_params()), ids.data_ptr(), pos.data_ptr(),
+                                              int(max_len), self.cos.data_ptr(), self.sin.data_ptr(), C.byref(self._kvref),
+                                              self.step_acts.data_ptr(), self.step_acts.numel(), self.logits.data_ptr(),
+                                              self.B, self.flags, _stream()), "sd_qwen3_mx_decode_step")
+            return self.logits
         if self.pool is not None:
             name = "sd_qwen3_decode_step_paged" + self._mx
             check(getattr(lib, name)(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(), pos.data_ptr(),
@@ -235,9 +287,11 @@ class Decoder:
 
 
 def _check_args(model, B, T, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p, repetition_penalty,
-                use_ras, win_size, tau_r, sync_every, decode_kernels="tile", model_capacity=True):
+                use_ras, win_size, tau_r, sync_every, decode_kernels="tile", model_capacity=True, weight_dtype="bf16"):
     """``model_capacity``: also hold T + max_new_tokens against ``cache_capacity(model)`` (a session holds its own
     lengths against its own capacity instead)."""
+    if weight_dtype not in WEIGHT_DTYPES:
+        raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, got {weight_dtype!r}")
     _check_decode_kernels(decode_kernels)
     if max_new_tokens < 1:
         raise ValueError(f"max_new_tokens must be at least 1, got {max_new_tokens}")
@@ -246,9 +300,7 @@ def _check_args(model, B, T, max_new_tokens, min_new_tokens, do_sample, temperat
     cap = cache_capacity(model)
     if model_capacity and T + max_new_tokens > cap:
         raise ValueError(f"prompt length {T} + max_new_tokens {max_new_tokens} exceeds the KV-cache capacity {cap}")
-    if model.inference_precision != "bf16":
-        raise NotImplementedError('generate() decodes with the unfolded bf16 weights; this model runs "'
-                                  f'{model.inference_precision}" (set_inference_precision("bf16") first)')
+    _check_weight_dtype(model, weight_dtype)
     if min_new_tokens < 0 or sync_every < 1:
         raise ValueError("min_new_tokens must be >= 0 and sync_every >= 1")
     if do_sample:
@@ -291,15 +343,18 @@ class GenerationSession:
     the rows' pages, ``trim()`` releases the worst-case leftovers on demand, ``fork(rows)`` continues rows in a new
     session that shares their full pages, ``close()`` (also run when the session is dropped) releases everything.  A pool
     of 8-bit pages (``kv_page_pool(..., kv_dtype="mxfp8")``) changes none of this: the decoder picks its entries from
-    the pool's dtype."""
+    the pool's dtype.
 
-    def __init__(self, model, batch_size, capacity=None, decode_kernels="tile", pool=None):
+    ``weight_dtype="mxfp8"``: every pass of every turn (prefill, extend, decode steps) runs the model's MXFP8 projections
+    (``Decoder``); ``fork`` keeps it.  Everything else above holds unchanged."""
+
+    def __init__(self, model, batch_size, capacity=None, decode_kernels="tile", pool=None, weight_dtype="bf16"):
         self.model, self.B = model, int(batch_size)
         self.capacity = int(capacity) if capacity is not None else cache_capacity(model)
         if self.B < 1 or self.capacity < 1:
             raise ValueError(f"a session needs batch_size >= 1 and capacity >= 1, got {batch_size}, {capacity}")
-        self.pool, self.decode_kernels = pool, decode_kernels
-        self.decoder = Decoder(model, self.B, self.capacity, decode_kernels, pool=pool)
+        self.pool, self.decode_kernels, self.weight_dtype = pool, decode_kernels, weight_dtype
+        self.decoder = Decoder(model, self.B, self.capacity, decode_kernels, pool=pool, weight_dtype=weight_dtype)
         dev = model.flat.device
         self.seq = torch.zeros(self.B, self.capacity, dtype=torch.int64, device=dev)
         self.len = torch.zeros(self.B, dtype=torch.int32, device=dev)
@@ -368,7 +423,9 @@ class GenerationSession:
         new = GenerationSession.__new__(GenerationSession)
         new.model, new.B, new.capacity, new.pool, new.decode_kernels = self.model, len(rows), self.capacity, self.pool, \
             self.decode_kernels
-        new.decoder = Decoder(self.model, new.B, self.capacity, self.decode_kernels, pool=self.pool)
+        new.weight_dtype = self.weight_dtype
+        new.decoder = Decoder(self.model, new.B, self.capacity, self.decode_kernels, pool=self.pool,
+                              weight_dtype=self.weight_dtype)
         cached = self.cached.tolist()   # the one host read
         new.decoder.pages, copies = self.decoder.pages.fork(rows, cached)   # raises before anything changed
         self.pool.copy_pages(copies)
@@ -457,7 +514,7 @@ class GenerationSession:
         model, B = self.model, self.B
         T = input_ids.shape[1] if input_ids.dim() == 2 else 0
         _check_args(model, B, T, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p, repetition_penalty,
-                    use_ras, win_size, tau_r, sync_every, model_capacity=False)
+                    use_ras, win_size, tau_r, sync_every, model_capacity=False, weight_dtype=self.weight_dtype)
         V = model.dims.vocab_size
         pad = pad_token_id if pad_token_id is not None else (eos_token_id if eos_token_id is not None else 0)
         if not 0 <= pad < V or (eos_token_id is not None and not 0 <= eos_token_id < V):
@@ -499,15 +556,15 @@ class GenerationSession:
 @torch.no_grad()
 def generate(model, input_ids, attention_mask=None, max_new_tokens=20, min_new_tokens=0, do_sample=True, temperature=1.0,
              top_k=0, top_p=1.0, repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, use_ras=False, win_size=25,
-             tau_r=0.2, seed=None, sync_every=16, decode_kernels="tile"):
+             tau_r=0.2, seed=None, sync_every=16, decode_kernels="tile", weight_dtype="bf16"):
     """See ``HipQwen3ForCausalLM.generate``: a one-turn ``GenerationSession``."""
     if input_ids.dim() != 2:
         raise ValueError(f"input_ids must be [B,T], got {tuple(input_ids.shape)}")
     B, T = input_ids.shape
     _check_args(model, B, T, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p, repetition_penalty,
-                use_ras, win_size, tau_r, sync_every, decode_kernels)
+                use_ras, win_size, tau_r, sync_every, decode_kernels, weight_dtype=weight_dtype)
     cap = (T + max_new_tokens + 255) // 256 * 256   # whole attention partitions; the output bits do not depend on it
-    sess = GenerationSession(model, B, cap, decode_kernels)
+    sess = GenerationSession(model, B, cap, decode_kernels, weight_dtype=weight_dtype)
     new = sess.generate(input_ids, attention_mask, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p,
                         repetition_penalty, eos_token_id, pad_token_id, use_ras, win_size, tau_r, seed, sync_every)
     return torch.cat([input_ids.to(torch.int64), new], dim=1)

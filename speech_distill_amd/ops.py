@@ -814,6 +814,50 @@ def gemm_mxfp8_swiglu(a_q, a_scale, wgu_q, wgu_scale, rowscale=None):
     return act_q, act_s
 
 
+# ---- weight-streaming GEMV over MXFP8 weights (include/sd_hip.h "the same GEMV over MXFP8 weights"): M = batch <= 16
+def _mx_weight(w_q, w_scale, name):
+    _need(w_q, torch.uint8, name + "_q"), _need(w_scale, torch.uint8, name + "_scale")
+    if w_q.dim() != 2 or tuple(w_scale.shape) != (w_q.shape[0], w_q.shape[1] // 32):
+        raise ValueError(f"{name}: expected e4m3 bytes [N,K] and E8M0 bytes [N,K/32], got {tuple(w_q.shape)} and "
+                         f"{tuple(w_scale.shape)}")
+
+
+def gemv_mxfp8(x, w_q, w_scale, residual=None, norm=False, eps=1e-6, out=None):
+    """y [M,N] = bf16(rs[m] * (X^ . W^T) + residual): x bf16 [M,K] (quantised to MXFP8 inside the kernel, as
+    ``mxfp8_quant`` would), W = (e4m3 bytes [N,K], E8M0 bytes [N,K/32]) as ``mxfp8_quant`` of a weight gives them;
+    rs = that call's rstd when ``norm``, else 1; 1 <= M <= 16.  x, residual and out may have strided rows.  The bits of
+    y[m,n] depend on row m, weight row n and K only."""
+    _rows2d(x, "x"), _mx_weight(w_q, w_scale, "w")
+    M, K = x.shape
+    N, Kw = w_q.shape
+    if Kw != K:
+        raise ValueError(f"gemv_mxfp8: contraction mismatch {K} vs {Kw}")
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
+    _rows2d(out, "out")
+    if out.shape != (M, N) or (residual is not None and _rows2d(residual, "residual").shape != (M, N)):
+        raise ValueError("gemv_mxfp8: out / residual must be [M,N]")
+    check(load_lib().sd_gemv_mxfp8(x.data_ptr(), x.stride(0), w_q.data_ptr(), w_scale.data_ptr(), out.data_ptr(),
+                                   out.stride(0), _p(residual), 0 if residual is None else residual.stride(0),
+                                   1 if norm else 0, float(eps), M, N, K, _stream()), "sd_gemv_mxfp8")
+    return out
+
+
+def gemv_mxfp8_swiglu(x, wgu_q, wgu_scale, norm=False, eps=1e-6):
+    """act bf16 [M,I] = silu(g) * u, g | u = bf16(rs * (X^ . Wgu^T)) with Wgu = [gate rows | up rows] [2I,K] in MXFP8;
+    1 <= M <= 16.  Equals swiglu_fwd(gemv_mxfp8(x, wgu_q, wgu_scale, norm=...)) bit for bit."""
+    _need(x, torch.bfloat16, "x"), _mx_weight(wgu_q, wgu_scale, "wgu")
+    if x.dim() != 2 or wgu_q.shape[0] % 2 or wgu_q.shape[1] != x.shape[1]:
+        raise ValueError(f"gemv_mxfp8_swiglu: x must be [M,K] and wgu_q [2I,K], got {tuple(x.shape)} and "
+                         f"{tuple(wgu_q.shape)}")
+    M, K = x.shape
+    I = wgu_q.shape[0] // 2
+    act = torch.empty(M, I, dtype=torch.bfloat16, device=x.device)
+    check(load_lib().sd_gemv_mxfp8_swiglu(x.data_ptr(), wgu_q.data_ptr(), wgu_scale.data_ptr(), act.data_ptr(),
+                                          1 if norm else 0, float(eps), M, I, K, _stream()), "sd_gemv_mxfp8_swiglu")
+    return act
+
+
 # ------------------------------------------------------------------------------------ KV-cache generation
 def kvcache_store(qk, qkv, k_plane, v_plane, kv_len, B, T, Hq, Hkv):
     """Prefill sink (sd_kvcache_store): K of ``qk`` [B*T,(Hq+Hkv)*128] and V of ``qkv`` [B*T,(Hq+2Hkv)*128] -> slots

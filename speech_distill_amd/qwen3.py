@@ -839,7 +839,8 @@ class HipQwen3ForCausalLM(nn.Module):
 
     def generate(self, input_ids, attention_mask=None, max_new_tokens=20, min_new_tokens=0, do_sample=True,
                  temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, eos_token_id=None, pad_token_id=None,
-                 use_ras=False, win_size=25, tau_r=0.2, seed=None, sync_every=16, decode_kernels="tile"):
+                 use_ras=False, win_size=25, tau_r=0.2, seed=None, sync_every=16, decode_kernels="tile",
+                 weight_dtype="bf16"):
         """Decode ``max_new_tokens`` tokens per row over a KV cache (generation.py; the reference's engine:
         soulxpodcast/engine/llm_engine.py:37-76 with sampler.py:136-189).  Returns int64 [B, T + max_new_tokens]: the given
         ``input_ids`` followed by the new tokens in columns T..., ``pad_token_id`` (default: ``eos_token_id``, else 0) after
@@ -857,13 +858,18 @@ class HipQwen3ForCausalLM(nn.Module):
         Raises before any launch: ValueError for another ``decode_kernels``, when T + max_new_tokens exceeds the cache
         capacity (``kv_cache_capacity`` or the config's ``max_position_embeddings``), when ``top_k > 128`` or when the mask is not right-padded;
         NotImplementedError for a model set to "mxfp8" (the decoder reads the unfolded bf16 weights; a LoRA student's merged
-        weights are those); RuntimeError for CPU tensors."""
+        weights are those); RuntimeError for CPU tensors.
+
+        ``weight_dtype="mxfp8"`` (default "bf16"): prefill and every step run the four projections of each layer on the
+        model's MXFP8 weights (``set_inference_precision``'s format, whatever the precision the model is set to); with
+        "skinny" the 8-bit weights are streamed through the block-scaled GEMV.  Needs a frozen model without LoRA and
+        the dimensions "mxfp8" needs: ValueError otherwise, and for any other value, before any allocation."""
         from .generation import generate
         return generate(self, input_ids, attention_mask, max_new_tokens, min_new_tokens, do_sample, temperature, top_k,
                         top_p, repetition_penalty, eos_token_id, pad_token_id, use_ras, win_size, tau_r, seed, sync_every,
-                        decode_kernels)
+                        decode_kernels, weight_dtype)
 
-    def start_session(self, batch_size, capacity=None, decode_kernels="tile", pool=None):
+    def start_session(self, batch_size, capacity=None, decode_kernels="tile", pool=None, weight_dtype="bf16"):
         """A ``GenerationSession`` (generation.py): multi-turn generation over ONE live KV cache of ``capacity`` positions
         per row (default: ``cache_capacity(self)``), as the reference's dialogue loop keeps one ``DynamicCache`` across
         turns (soulxpodcast/models/soulxpodcast.py:342,378-380).  ``sess.generate(ids, mask, ...)`` takes a turn and returns
@@ -879,9 +885,12 @@ class HipQwen3ForCausalLM(nn.Module):
 
             s = model.start_session(1, pool=pool); s.extend(prompt[:, :-1])
             n = s.fork([0] * 8); out = n.generate(prompt[:, -1:].expand(8, 1), ...)
+
+        ``weight_dtype="mxfp8"``: the session decodes with the model's MXFP8 projections (see ``generate``); it combines
+        with either kind of pool and with contiguous caches.
         """
         from .generation import GenerationSession
-        return GenerationSession(self, batch_size, capacity, decode_kernels, pool=pool)
+        return GenerationSession(self, batch_size, capacity, decode_kernels, pool=pool, weight_dtype=weight_dtype)
 
     def kv_page_pool(self, n_pages, order=None, kv_dtype="bf16"):
         """A ``PagePool`` (paged.py) of ``n_pages`` pages of 256 positions for this model's paged sessions
