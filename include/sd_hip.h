@@ -552,6 +552,34 @@ int64_t sd_sample_workspace_bytes(int B, int V);
 int sd_sample_step(const void* logits, int64_t row_stride, const float* uniforms, int64_t* seq, const int32_t* prompt_len,
                    int32_t* len, uint8_t* finished, int64_t* next_out, int32_t* pos_out, void* workspace,
                    int64_t workspace_bytes, const sd_sample_params* sp, int B, int V, int cap, void* stream);
+/* sd_sample_step with everything per row (llm_engine.py:97-109: one SamplingParams per request of a continuously batched
+ * step).  Row b is sampled exactly as sd_sample_step samples it alone with params[b] and its own uniform pair: the same
+ * kernels, instantiated over where the parameters come from, and bit-identical results.
+ *   params   sd_sample_params [B] in DEVICE memory (4-byte aligned), eos_token_id and pad_token_id included.
+ *   max_new  int32 [B], device: after a commit a row with len[b] - prompt_len[b] >= max_new[b] gets finished[b] = 1, on top
+ *            of the EOS rule and the row-full rule.
+ *   uniforms fp32 [B, u_stride, 2]: row b reads pair g = len[b] - prompt_len[b] (the tokens it has generated), clamped to
+ *            [0, u_stride); the host indexes nothing per step and a row's stream depends on that row only.
+ *   env      HOST, launch decisions only: max_top_k = the largest top_k of any sampling row (0..128, <= V), any_sample =
+ *            some row has do_sample, any_ras = some row may take the RAS fallback, any_full = some row has top_k == 0.
+ * Launches: the scores, ONE sd_logsoftmax_topk with K = max(max_top_k, 1) (candidates come sorted descending, ties to the
+ * lowest index, so a row's own top_k is a prefix of them; a greedy row takes the first), the pick, then the full-vocabulary
+ * pair over the processed rows when any_full and again over the raw logits when any_ras -- each flagged row is served by
+ * its own source.  Without any_sample every row is treated as greedy.
+ * Every field read from device memory is brought into its legal range before it is used or an address is formed: top_k
+ * to [0, K] (0 without any_full: K), use_ras off without any_ras or with top_k == 0, win_size to [0, cap], eos >= V = none,
+ * pad to [0, V), temperature / top_p / repetition_penalty not > 0 (NaN included) = 1, g as above, len and prompt_len as in
+ * sd_sample_step.  Nothing is written outside seq[b, 0 .. cap), and next_out is always a token id in [0, V).
+ * Host checks, all before the first launch, with sd_sample_step's codes: a NULL pointer (env included), B, V, cap,
+ * row_stride, u_stride or env.max_top_k out of range SD_ERR_SHAPE; V or row_stride not a multiple of 8, a misaligned
+ * logits / workspace / params pointer SD_ERR_ALIGN; a short or NULL workspace (sd_sample_workspace_bytes) SD_ERR_WORKSPACE. */
+typedef struct {
+  int32_t max_top_k, any_sample, any_ras, any_full;
+} sd_sample_env;
+int sd_sample_step_rows(const void* logits, int64_t row_stride, const float* uniforms, int u_stride, int64_t* seq,
+                        const int32_t* prompt_len, int32_t* len, uint8_t* finished, int64_t* next_out, int32_t* pos_out,
+                        void* workspace, int64_t workspace_bytes, const sd_sample_params* params, const int32_t* max_new,
+                        const sd_sample_env* env, int B, int V, int cap, void* stream);
 /* The runner over the cache (unfolded bf16 weights only).
  * sd_qwen3_prefill: the SD_SAVE_NONE forward of sd_qwen3_forward with sd_kvcache_store after each layer's q|k|v step
  *   and the lm_head on the last valid row of each sequence (sd_last_rows, on the device): logits bf16 [B,V], bit-identical

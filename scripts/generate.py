@@ -14,6 +14,11 @@ penalty 1.25, min 8 / max 3000 new tokens, stop token 151675, repetition-aware s
 its own text behind the history the cache already holds.  The dialogues of a batch take their turns together, so prompts
 are batched by turn count.  The output holds, per prompt and turn, ``{"index", "turn", "prompt_len", "generated_ids"}``
 with the ids up to and including the stop token.
+
+``--continuous`` (needs ``--kv_pool_pages``): the single-turn prompts are served by the request engine
+(``model.generation_engine``; the reference's engine is vLLM, llm_engine.py:91) -- ``--batch_size`` rows, a row that
+finishes is refilled with the next prompt at once, request i is seeded with ``--seed`` + i, and the results are written
+in input order.  Dialogues (``"turns"``) keep the session path.
 """
 import argparse
 import json
@@ -61,7 +66,12 @@ def parse_args(argv=None):
                         "weights quantised once at start-up (e4m3 with one power-of-two scale per 32 along K; the model "
                         "is frozen for it); with --decode_kernels skinny they are streamed through the block-scaled "
                         "GEMV.  Independent of --kv_cache_dtype; the tokens may differ from the bf16 weights'")
+    p.add_argument("--continuous", action="store_true",
+                   help="continuous batching (needs --kv_pool_pages): --batch_size becomes the engine's max_batch and a "
+                        "finished row is refilled with the next prompt at once; dialogues keep the session path")
     args = p.parse_args(argv)
+    if args.continuous and args.kv_pool_pages <= 0:
+        p.error("--continuous needs --kv_pool_pages N: the engine serves its rows from a page pool")
     if args.kv_cache_dtype != "bf16" and args.kv_pool_pages <= 0:
         p.error("--kv_cache_dtype mxfp8 needs --kv_pool_pages N: only the paged cache has an 8-bit form")
     return args
@@ -112,6 +122,32 @@ def right_pad(rows, pad):
     return ids, mask
 
 
+def serve_continuous(model, pool, args, pad, prompts, out):
+    """Serve ``prompts`` [(index, ids)] through the request engine and write them in input order.  -> (new tokens, s)."""
+    if not prompts:
+        return 0, 0.0
+    dev = model.flat.device
+    eng = model.generation_engine(pool, max_batch=args.batch_size, decode_kernels=args.decode_kernels,
+                                  weight_dtype=args.weight_dtype, sync_every=args.sync_every)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    rids = [eng.submit(torch.tensor(ids, dtype=torch.int64, device=dev), max_new_tokens=args.max_tokens,
+                       seed=None if args.seed is None else args.seed + i, min_new_tokens=args.min_tokens,
+                       do_sample=not args.greedy, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p,
+                       repetition_penalty=args.repetition_penalty, eos_token_id=args.stop_token_id, pad_token_id=pad,
+                       use_ras=not args.no_ras, win_size=args.win_size, tau_r=args.tau_r) for i, ids in prompts]
+    eng.run()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    n_new = 0
+    for (i, ids), rid in zip(prompts, rids):
+        row = eng.result(rid).cpu().tolist()
+        n_new += len(row)
+        out.write(json.dumps({"index": i, "turn": 0, "prompt_len": len(ids), "generated_ids": row}) + "\n")
+    eng.close()
+    return n_new, dt
+
+
 def main(argv=None):
     args = parse_args(argv)
     import speech_distill_amd as sda
@@ -125,7 +161,16 @@ def main(argv=None):
     n_new, elapsed = 0, 0.0
     pool = model.kv_page_pool(args.kv_pool_pages, kv_dtype=args.kv_cache_dtype) if args.kv_pool_pages > 0 else None
     with open(args.output, "w") as out:
-        for index, chunk in batches_by_turn_count(dialogues, args.batch_size):
+        if args.continuous:
+            single = [i for i, d in enumerate(dialogues) if len(d) == 1]
+            n, dt = serve_continuous(model, pool, args, pad, [(i, dialogues[i][0]) for i in single], out)
+            n_new, elapsed = n_new + n, elapsed + dt
+            keep = [i for i, d in enumerate(dialogues) if len(d) > 1]
+            batches = [([keep[j] for j in idx], chunk)
+                       for idx, chunk in batches_by_turn_count([dialogues[i] for i in keep], args.batch_size)]
+        else:
+            batches = batches_by_turn_count(dialogues, args.batch_size)
+        for index, chunk in batches:
             n_turns = len(chunk[0])
             need = max(sum(len(t) for t in d) for d in chunk) + n_turns * args.max_tokens
             if need > cache_capacity(model):

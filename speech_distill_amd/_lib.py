@@ -75,6 +75,10 @@ class SampleParams(C.Structure):  # include/sd_hip.h sd_sample_params
                [(n, C.c_float) for n in ("temperature", "top_p", "repetition_penalty", "pad_")]
 
 
+class SampleEnv(C.Structure):  # include/sd_hip.h sd_sample_env (host: the launch decisions of sd_sample_step_rows)
+    _fields_ = [(n, C.c_int32) for n in ("max_top_k", "any_sample", "any_ras", "any_full")]
+
+
 class KvPages(C.Structure):  # include/sd_hip.h sd_kv_pages (the paged KV cache of the runner entries)
     _fields_ = [("pool", C.c_void_p), ("pool_bytes", C.c_int64), ("table", C.c_void_p), ("n_pages", C.c_int32),
                 ("max_pages", C.c_int32)]
@@ -204,6 +208,8 @@ PROTOTYPES = {
     "sd_sample_workspace_bytes": (_i64, [_i, _i]),
     "sd_sample_step": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, C.POINTER(SampleParams), _i, _i, _i,
                             _vp]),
+    "sd_sample_step_rows": (_i, [_vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                                 C.POINTER(SampleEnv), _i, _i, _i, _vp]),
     "sd_qwen3_prefill_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
     "sd_qwen3_prefill": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i, _vp, _i, _i,
                               _vp]),

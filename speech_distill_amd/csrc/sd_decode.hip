@@ -454,11 +454,66 @@ SD_DEV void row_bounds(const SampleArgs& a, int b, int* n, int* np) {
   *np = clampi(a.prompt_len[b], 0, *n);
 }
 
+// The per-row form (sd_sample_step_rows): every row's parameters, budget and uniform stream live in device memory.  K is
+// the launch's top-k (>= 1), the stride of top_i; `sp` is unused.  flag: 1 = full draw from the processed row, 2 = from
+// the raw logits (one step may need both).
+struct SampleRowsArgs : SampleArgs {
+  const sd_sample_params* spv;  // [B] device
+  const int32_t* max_new;       // [B] device
+  int u_stride, any_full, any_ras;
+};
+
+// Where a row's parameters come from: the kernels below are written once over these accessors (as the paged stores are
+// over their page arguments).  SampleArgs: the one host set in the kernel arguments, exactly the code sd_sample_step had.
+SD_DEV const sd_sample_params& row_params(const SampleArgs& a, int) { return a.sp; }
+SD_DEV const float* row_uniforms(const SampleArgs& a, int b) { return a.u + 2 * b; }
+SD_DEV int row_topk(const SampleArgs& a, const sd_sample_params&) { return a.K; }
+SD_DEV int full_flag(const SampleArgs&, bool) { return 1; }
+template <typename T> SD_DEV bool full_mine(const SampleArgs&, int flag) { return flag != 0; }
+template <typename T> SD_DEV float full_temp(const SampleArgs&, int, float temp) { return temp; }
+SD_DEV bool budget_spent(const SampleArgs&, int, int) { return false; }
+
+// SampleRowsArgs: row b's set is loaded from device memory and every field is brought into its legal range before it is
+// used (include/sd_hip.h): top_k to [0, K] (greedy: 1; 0 without a full-vocabulary launch: K), RAS off without its
+// launch or its candidates, win_size to [0, cap], an EOS id >= V means none, pad to [0, V), a non-positive or NaN
+// temperature / top_p / penalty to 1.
+SD_DEV sd_sample_params row_params(const SampleRowsArgs& a, int b) {
+  sd_sample_params s = a.spv[b];
+  s.do_sample = s.do_sample != 0;
+  s.top_k = s.do_sample ? clampi(s.top_k, 0, a.K) : 1;
+  if (s.top_k == 0 && !a.any_full) s.top_k = a.K;
+  s.use_ras = s.do_sample && s.use_ras != 0 && s.top_k > 0 && a.any_ras;
+  s.win_size = clampi(s.win_size, 0, a.cap);
+  if (s.eos_token_id >= a.V) s.eos_token_id = -1;
+  s.pad_token_id = clampi(s.pad_token_id, 0, a.V - 1);
+  if (!(s.temperature > 0.f)) s.temperature = 1.f;
+  if (!(s.top_p > 0.f)) s.top_p = 1.f;
+  if (!(s.repetition_penalty > 0.f)) s.repetition_penalty = 1.f;
+  return s;
+}
+// pair g = tokens generated so far, clamped to [0, u_stride)
+SD_DEV const float* row_uniforms(const SampleRowsArgs& a, int b) {
+  int n, np;
+  row_bounds(a, b, &n, &np);
+  return a.u + ((long)b * a.u_stride + clampi(n - np, 0, a.u_stride - 1)) * 2;
+}
+SD_DEV int row_topk(const SampleRowsArgs&, const sd_sample_params& sp) { return sp.top_k; }
+SD_DEV int full_flag(const SampleRowsArgs&, bool raw) { return raw ? 2 : 1; }
+template <typename T> SD_DEV bool full_mine(const SampleRowsArgs&, int flag) { return flag == (sizeof(T) == 2 ? 2 : 1); }
+template <typename T> SD_DEV float full_temp(const SampleRowsArgs& a, int b, float temp) {
+  return sizeof(T) == 2 ? temp : row_params(a, b).temperature;
+}
+// after a commit at slot L: the row has spent its budget (np from the length before the commit)
+SD_DEV bool budget_spent(const SampleRowsArgs& a, int b, int L) {
+  return L + 1 - clampi(a.prompt_len[b], 0, L) >= a.max_new[b];
+}
+
 // The token of an unfinished row: appended at seq[b, len], len advanced, EOS sets finished.  A full row finishes.
-SD_DEV void commit(const SampleArgs& a, int b, long tok) {
+template <class A>
+SD_DEV void commit(const A& a, const sd_sample_params& sp, int b, long tok) {
   const int L = clampi(a.len[b], 0, a.cap);
   if (L >= a.cap) {
-    a.next_out[b] = a.sp.pad_token_id;
+    a.next_out[b] = sp.pad_token_id;
     a.pos_out[b] = a.cap - 1;
     a.finished[b] = 1;
     return;
@@ -467,16 +522,19 @@ SD_DEV void commit(const SampleArgs& a, int b, long tok) {
   a.len[b] = L + 1;
   a.next_out[b] = tok;
   a.pos_out[b] = L;
-  if (a.sp.eos_token_id >= 0 && tok == a.sp.eos_token_id) a.finished[b] = 1;
+  if (sp.eos_token_id >= 0 && tok == sp.eos_token_id) a.finished[b] = 1;
+  if (budget_spent(a, b, L)) a.finished[b] = 1;
 }
 
 // Step 1 + 2 of the chain (HF RepetitionPenaltyLogitsProcessor fed the generated ids, MinNewTokensLength): the raw row is
 // copied to fp32, then every GENERATED token's column gets raw < 0 ? raw * p : raw / p.  The penalty reads the raw row
 // and writes the copy, so a token that occurs twice is written twice with the same value: "each distinct token once".
 // grid (slices, B): a workgroup owns a contiguous slice of columns and applies the tokens that fall into it.
-__global__ __launch_bounds__(1024) void sample_scores_kernel(SampleArgs a, int per) {
+template <class A>
+__global__ __launch_bounds__(1024) void sample_scores_kernel(A a, int per) {
   const int b = blockIdx.y;
   if (a.finished[b]) return;
+  const auto& sp = row_params(a, b);
   const int c0 = blockIdx.x * per, c1 = min(a.V, c0 + per);
   const bf16* raw = a.logits + (long)b * a.ld;
   float* out = a.proc + (long)b * a.V;
@@ -489,7 +547,7 @@ __global__ __launch_bounds__(1024) void sample_scores_kernel(SampleArgs a, int p
   __syncthreads();
   int n, np;
   row_bounds(a, b, &n, &np);
-  const float pen = a.sp.repetition_penalty;
+  const float pen = sp.repetition_penalty;
   if (pen != 1.0f)
     for (int i = np + threadIdx.x; i < n; i += 1024) {
       const long tok = a.seq[(long)b * a.cap + i];
@@ -499,42 +557,45 @@ __global__ __launch_bounds__(1024) void sample_scores_kernel(SampleArgs a, int p
       }
     }
   __syncthreads();
-  const int eos = a.sp.eos_token_id;
-  if (threadIdx.x == 0 && eos >= c0 && eos < c1 && n - np < a.sp.min_new_tokens) out[eos] = -INFINITY;
+  const int eos = sp.eos_token_id;
+  if (threadIdx.x == 0 && eos >= c0 && eos < c1 && n - np < sp.min_new_tokens) out[eos] = -INFINITY;
 }
 
 // Steps 3-6 on the top-K candidates, one workgroup per row; thread 0 walks the <= 128 candidates in descending order.
 // Temperature: score / T.  Top-p (HF TopPLogitsWarper on the top-k survivors): walking up from the smallest
 // probability, a candidate is dropped while the cumulative mass is <= 1 - top_p; the largest always stays.
 // Draw: the first candidate whose cumulative mass (descending order, renormalised over the survivors) exceeds u.
-__global__ __launch_bounds__(128) void sample_pick_kernel(SampleArgs a) {
+template <class A>
+__global__ __launch_bounds__(128) void sample_pick_kernel(A a) {
   __shared__ float e_s[128];
   __shared__ int id_s[128];
-  const int b = blockIdx.x, K = a.K;
+  const int b = blockIdx.x;
+  const auto& sp = row_params(a, b);
+  const int K = row_topk(a, sp);   // the row's candidates: a prefix of the launch's a.K
   int n, np;
   row_bounds(a, b, &n, &np);
   if (a.finished[b]) {
     if (threadIdx.x == 0) {
-      a.next_out[b] = a.sp.pad_token_id;
+      a.next_out[b] = sp.pad_token_id;
       a.pos_out[b] = n > 0 ? n - 1 : 0;
       a.flag[b] = 0;
     }
     return;
   }
   if (K == 0) {  // no top-k: the whole processed row is the distribution (sample_full_*)
-    if (threadIdx.x == 0) a.flag[b] = 1;
+    if (threadIdx.x == 0) a.flag[b] = full_flag(a, false);
     return;
   }
   if (threadIdx.x < K) {
-    const int id = clampi(a.top_i[(long)b * K + threadIdx.x], 0, a.V - 1);
+    const int id = clampi(a.top_i[(long)b * a.K + threadIdx.x], 0, a.V - 1);
     id_s[threadIdx.x] = id;
-    e_s[threadIdx.x] = a.proc[(long)b * a.V + id] / a.sp.temperature;
+    e_s[threadIdx.x] = a.proc[(long)b * a.V + id] / sp.temperature;
   }
   __syncthreads();
   if (threadIdx.x != 0) return;
-  if (!a.sp.do_sample) {
+  if (!sp.do_sample) {
     a.flag[b] = 0;
-    commit(a, b, id_s[0]);
+    commit(a, sp, b, id_s[0]);
     return;
   }
   const float mx = e_s[0];
@@ -544,8 +605,8 @@ __global__ __launch_bounds__(128) void sample_pick_kernel(SampleArgs a) {
     Z += e_s[k];
   }
   int keep = K;
-  if (a.sp.top_p < 1.0f) {
-    const float drop = 1.0f - a.sp.top_p;
+  if (sp.top_p < 1.0f) {
+    const float drop = 1.0f - sp.top_p;
     float cum = 0.f;
     while (keep > 1) {
       cum += e_s[keep - 1] / Z;
@@ -564,28 +625,28 @@ __global__ __launch_bounds__(128) void sample_pick_kernel(SampleArgs a) {
     }
     return keep - 1;
   };
-  if (a.sp.use_ras) {
-    const int cand = id_s[draw(a.u[2 * b])];
+  if (sp.use_ras) {
+    const int cand = id_s[draw(row_uniforms(a, b)[0])];
     int cnt = 0;
-    const int w0 = n - a.sp.win_size > 0 ? n - a.sp.win_size : 0;
+    const int w0 = n - sp.win_size > 0 ? n - sp.win_size : 0;
     for (int i = w0; i < n; ++i) cnt += a.seq[(long)b * a.cap + i] == cand;
-    if (cnt + 1 >= a.sp.ras_min_count) {  // the final draw is from softmax(raw logits): sample_full_*
-      a.flag[b] = 1;
+    if (cnt + 1 >= sp.ras_min_count) {  // the final draw is from softmax(raw logits): sample_full_*
+      a.flag[b] = full_flag(a, true);
       return;
     }
   }
   a.flag[b] = 0;
-  commit(a, b, id_s[draw(a.u[2 * b + 1])]);
+  commit(a, sp, b, id_s[draw(row_uniforms(a, b)[1])]);
 }
 
 // Full-vocabulary draw, pass 1: per block of 1024 columns the maximum and the sum of exp(x - block max), fp32, for the
 // rows whose flag is set.  x = value / temp (the raw bf16 row with temp 1, or the processed fp32 row).
-template <typename T>
-__global__ __launch_bounds__(256) void sample_full_partial_kernel(SampleArgs a, const T* __restrict__ src, long ld,
-                                                                  float temp) {
+template <typename T, class A>
+__global__ __launch_bounds__(256) void sample_full_partial_kernel(A a, const T* __restrict__ src, long ld, float temp) {
   __shared__ float red[32];
   const int b = blockIdx.y;
-  if (!a.flag[b]) return;
+  if (!full_mine<T>(a, a.flag[b])) return;
+  temp = full_temp<T>(a, b, temp);
   const int c0 = blockIdx.x * 1024 + threadIdx.x * 4;
   float x[4];
 #pragma unroll
@@ -603,15 +664,15 @@ __global__ __launch_bounds__(256) void sample_full_partial_kernel(SampleArgs a, 
 
 // Pass 2: scan the block sums (thread 0, block order) to the block that holds u * Z, then scan that block's 1024 columns
 // in column order and take the first whose cumulative mass exceeds the target.
-template <typename T>
-__global__ __launch_bounds__(1024) void sample_full_pick_kernel(SampleArgs a, const T* __restrict__ src, long ld,
-                                                                float temp) {
+template <typename T, class A>
+__global__ __launch_bounds__(1024) void sample_full_pick_kernel(A a, const T* __restrict__ src, long ld, float temp) {
   __shared__ float red[32];
   __shared__ float wsum[16];
   __shared__ float sel_base, sel_target, sel_M;
   __shared__ int sel_blk, first_hit;
   const int b = blockIdx.x, t = threadIdx.x;
-  if (!a.flag[b]) return;
+  if (!full_mine<T>(a, a.flag[b])) return;
+  temp = full_temp<T>(a, b, temp);
   const float* bp = a.bpart + (long)b * a.nblk * 2;
   float mx = -INFINITY;
   for (int i = t; i < a.nblk; i += 1024) mx = fmaxf(mx, bp[2 * i]);
@@ -619,7 +680,7 @@ __global__ __launch_bounds__(1024) void sample_full_pick_kernel(SampleArgs a, co
   if (t == 0) {
     float Z = 0.f;
     for (int i = 0; i < a.nblk; ++i) Z += bp[2 * i] == -INFINITY ? 0.f : bp[2 * i + 1] * expf(bp[2 * i] - mx);
-    const float target = a.u[2 * b + 1] * Z;
+    const float target = row_uniforms(a, b)[1] * Z;
     float c = 0.f, base = 0.f;
     int blk = a.nblk - 1;  // rounding may leave the target at or past Z: the last block then
     for (int i = 0; i < a.nblk; ++i) {
@@ -654,7 +715,7 @@ __global__ __launch_bounds__(1024) void sample_full_pick_kernel(SampleArgs a, co
       pick = a.V - 1 - sel_blk * 1024;
       pick = pick > 1023 ? 1023 : pick;
     }
-    commit(a, b, (long)sel_blk * 1024 + pick);
+    commit(a, row_params(a, b), b, (long)sel_blk * 1024 + pick);
   }
 }
 
@@ -994,7 +1055,7 @@ extern "C" int sd_sample_step(const void* logits, int64_t row_stride, const floa
     SdProfScope prof(SD_K_MISC, 6.0 * B * V, ST);
     SD_PROF_LABEL("sample_scores_kernel");
     const int slices = 8, per = ((V + slices - 1) / slices + 7) & ~7;
-    hipLaunchKernelGGL(sample_scores_kernel, dim3(slices, B), dim3(1024), 0, ST, a, per);
+    hipLaunchKernelGGL(sample_scores_kernel<SampleArgs>, dim3(slices, B), dim3(1024), 0, ST, a, per);
     SD_CHECK_LAUNCH();
   }
   if (a.K > 0) {
@@ -1004,23 +1065,84 @@ extern "C" int sd_sample_step(const void* logits, int64_t row_stride, const floa
   {
     SdProfScope prof(SD_K_MISC, 8.0 * B * 128, ST);
     SD_PROF_LABEL("sample_pick_kernel");
-    hipLaunchKernelGGL(sample_pick_kernel, dim3(B), dim3(128), 0, ST, a);
+    hipLaunchKernelGGL(sample_pick_kernel<SampleArgs>, dim3(B), dim3(128), 0, ST, a);
     SD_CHECK_LAUNCH();
   }
   if (!sp->do_sample || (a.K > 0 && !sp->use_ras)) return 0;
   SdProfScope prof(SD_K_MISC, 2.0 * B * V, ST);
   SD_PROF_LABEL("sample_full_kernels");
   if (a.K == 0) {  // the processed row at the caller's temperature
-    hipLaunchKernelGGL((sample_full_partial_kernel<float>), dim3(a.nblk, B), dim3(256), 0, ST, a, (const float*)a.proc,
+    hipLaunchKernelGGL((sample_full_partial_kernel<float, SampleArgs>), dim3(a.nblk, B), dim3(256), 0, ST, a, (const float*)a.proc,
                        (long)V, sp->temperature);
     SD_CHECK_LAUNCH();
-    hipLaunchKernelGGL((sample_full_pick_kernel<float>), dim3(B), dim3(1024), 0, ST, a, (const float*)a.proc, (long)V,
+    hipLaunchKernelGGL((sample_full_pick_kernel<float, SampleArgs>), dim3(B), dim3(1024), 0, ST, a, (const float*)a.proc, (long)V,
                        sp->temperature);
   } else {  // RAS fallback: softmax of the raw logits
-    hipLaunchKernelGGL((sample_full_partial_kernel<bf16>), dim3(a.nblk, B), dim3(256), 0, ST, a, a.logits, a.ld, 1.0f);
+    hipLaunchKernelGGL((sample_full_partial_kernel<bf16, SampleArgs>), dim3(a.nblk, B), dim3(256), 0, ST, a, a.logits, a.ld, 1.0f);
     SD_CHECK_LAUNCH();
-    hipLaunchKernelGGL((sample_full_pick_kernel<bf16>), dim3(B), dim3(1024), 0, ST, a, a.logits, a.ld, 1.0f);
+    hipLaunchKernelGGL((sample_full_pick_kernel<bf16, SampleArgs>), dim3(B), dim3(1024), 0, ST, a, a.logits, a.ld, 1.0f);
   }
   SD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sd_sample_step_rows(const void* logits, int64_t row_stride, const float* uniforms, int u_stride, int64_t* seq,
+                                   const int32_t* prompt_len, int32_t* len, uint8_t* finished, int64_t* next_out,
+                                   int32_t* pos_out, void* workspace, int64_t workspace_bytes,
+                                   const sd_sample_params* params, const int32_t* max_new, const sd_sample_env* env, int B,
+                                   int V, int cap, void* stream) {
+  if (!env || !params || !max_new || !logits || !uniforms || !seq || !prompt_len || !len || !finished || !next_out || !pos_out)
+    return SD_ERR_SHAPE;
+  if (B <= 0 || B > 65535 || V <= 0 || cap <= 0 || row_stride < V || u_stride <= 0) return SD_ERR_SHAPE;
+  if ((V & 7) || (row_stride & 7) || ((uintptr_t)logits & 15) || ((uintptr_t)workspace & 15) || ((uintptr_t)params & 3))
+    return SD_ERR_ALIGN;
+  if (env->max_top_k < 0 || env->max_top_k > 128 || env->max_top_k > V) return SD_ERR_SHAPE;
+  int64_t o_topi, o_topv, o_bpart, o_flag;
+  if (workspace_bytes < sample_ws_layout(B, V, &o_topi, &o_topv, &o_bpart, &o_flag) || !workspace) return SD_ERR_WORKSPACE;
+  char* ws = (char*)workspace;
+  const bool sampling = env->any_sample != 0;
+  SampleRowsArgs a;
+  a.logits = (const bf16*)logits; a.ld = row_stride; a.proc = (float*)ws; a.top_i = (const int32_t*)(ws + o_topi);
+  a.bpart = (float*)(ws + o_bpart); a.flag = (int32_t*)(ws + o_flag); a.u = uniforms; a.seq = seq;
+  a.prompt_len = prompt_len; a.len = len; a.finished = finished; a.next_out = next_out; a.pos_out = pos_out;
+  a.B = B; a.V = V; a.cap = cap; a.nblk = (V + 1023) / 1024; a.sp = sd_sample_params{};
+  // one top-K launch with the envelope's K; a greedy row takes its first candidate, so K >= 1
+  a.K = sampling && env->max_top_k > 1 ? env->max_top_k : 1;
+  a.spv = params; a.max_new = max_new; a.u_stride = u_stride;
+  a.any_full = sampling && env->any_full; a.any_ras = sampling && env->any_ras;
+  {
+    SdProfScope prof(SD_K_MISC, 6.0 * B * V, ST);
+    SD_PROF_LABEL("sample_scores_kernel<rows>");
+    const int slices = 8, per = ((V + slices - 1) / slices + 7) & ~7;
+    hipLaunchKernelGGL(sample_scores_kernel<SampleRowsArgs>, dim3(slices, B), dim3(1024), 0, ST, a, per);
+    SD_CHECK_LAUNCH();
+  }
+  const int rc = sd_logsoftmax_topk(a.proc, ws + o_topv, ws + o_topi, nullptr, B, V, V, a.K, SD_DTYPE_F32, stream);
+  if (rc) return rc;
+  {
+    SdProfScope prof(SD_K_MISC, 8.0 * B * 128, ST);
+    SD_PROF_LABEL("sample_pick_kernel<rows>");
+    hipLaunchKernelGGL(sample_pick_kernel<SampleRowsArgs>, dim3(B), dim3(128), 0, ST, a);
+    SD_CHECK_LAUNCH();
+  }
+  if (!a.any_full && !a.any_ras) return 0;
+  SdProfScope prof(SD_K_MISC, 2.0 * B * V, ST);
+  SD_PROF_LABEL("sample_full_kernels<rows>");
+  if (a.any_full) {  // rows flagged 1: the processed row at the row's temperature
+    hipLaunchKernelGGL((sample_full_partial_kernel<float, SampleRowsArgs>), dim3(a.nblk, B), dim3(256), 0, ST, a,
+                       (const float*)a.proc, (long)V, 1.0f);
+    SD_CHECK_LAUNCH();
+    hipLaunchKernelGGL((sample_full_pick_kernel<float, SampleRowsArgs>), dim3(B), dim3(1024), 0, ST, a,
+                       (const float*)a.proc, (long)V, 1.0f);
+    SD_CHECK_LAUNCH();
+  }
+  if (a.any_ras) {  // rows flagged 2: the RAS fallback, softmax of the raw logits
+    hipLaunchKernelGGL((sample_full_partial_kernel<bf16, SampleRowsArgs>), dim3(a.nblk, B), dim3(256), 0, ST, a, a.logits,
+                       a.ld, 1.0f);
+    SD_CHECK_LAUNCH();
+    hipLaunchKernelGGL((sample_full_pick_kernel<bf16, SampleRowsArgs>), dim3(B), dim3(1024), 0, ST, a, a.logits, a.ld,
+                       1.0f);
+    SD_CHECK_LAUNCH();
+  }
   return 0;
 }

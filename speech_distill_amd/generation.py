@@ -225,6 +225,47 @@ class Decoder:
         return self.logits
 
     @torch.no_grad()
+    def prefill_rows(self, rows, ids, kv_len=None):
+        """The compact admission prefill of a paged decoder (engine.py): ``prefill`` for the chosen ``rows`` only (a host
+        list of k distinct rows, which own their pages and whose table rows are uploaded).  Their rows of the page table
+        are gathered into a scratch table [k, max_pages] and the prefill entry of this decoder's kind runs with B = k on
+        ids int64 [k,T] (kv_len int32 [k], device, or None); every other row's pages and the decoder's own logits buffer
+        stay untouched.  Returns new logits bf16 [k,V], row i for ``rows[i]``: with k = 1 the bits of a one-row decoder's
+        ``prefill``."""
+        lib, m = load_lib(), self.model
+        if self.pool is None:
+            raise ValueError("prefill_rows() is for decoders over a page pool")
+        rows = [int(r) for r in rows]
+        _need(ids, torch.int64, "input_ids")
+        k, T = ids.shape if ids.dim() == 2 else (0, 0)
+        if not rows or k != len(rows) or len(set(rows)) != k or min(rows) < 0 or max(rows) >= self.B or not 1 <= T <= self.cap:
+            raise ValueError(f"prefill_rows of {tuple(ids.shape)} for rows {rows} of a decoder with {self.B} rows of "
+                             f"{self.cap} positions")
+        if kv_len is not None and (_need(kv_len, torch.int32, "kv_len").numel() != k):
+            raise ValueError(f"kv_len must hold {k} lengths")
+        table = self.table[torch.tensor(rows, dtype=torch.int64, device=self.table.device)].contiguous()
+        kvp = _lib.KvPages(self.pool.buffer.data_ptr(), self.pool.buffer.numel(), table.data_ptr(), self.pool.n_pages,
+                           self.max_pages)
+        logits = torch.empty(k, m.dims.vocab_size, dtype=torch.bfloat16, device=ids.device)
+        lens = 0 if kv_len is None else kv_len.data_ptr()
+        if self.weight_dtype == "mxfp8":
+            nb = lib.sd_qwen3_mx_prefill_acts_bytes(C.byref(m._cdims), k, T)
+            check(min(nb, 0), "sd_qwen3_mx_prefill_acts_bytes")
+            acts = torch.empty(nb, dtype=torch.uint8, device=ids.device)
+            kvref = _lib.KvRef(2 if self._mx else 1, None, 0, 0, C.pointer(kvp))
+            check(lib.sd_qwen3_mx_prefill(C.byref(m._cdims), C.byref(m._mx_params()), ids.data_ptr(), lens,
+                                          self.cos.data_ptr(), self.sin.data_ptr(), acts.data_ptr(), nb, C.byref(kvref),
+                                          logits.data_ptr(), k, T, _stream()), "sd_qwen3_mx_prefill")
+            return logits
+        nb = lib.sd_qwen3_prefill_acts_bytes(C.byref(m._cdims), k, T)
+        acts = torch.empty(nb, dtype=torch.uint8, device=ids.device)
+        name = "sd_qwen3_prefill_paged" + self._mx
+        check(getattr(lib, name)(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(), lens, self.cos.data_ptr(),
+                                 self.sin.data_ptr(), acts.data_ptr(), nb, C.byref(kvp), logits.data_ptr(), k, T, _stream()),
+              name)
+        return logits
+
+    @torch.no_grad()
     def extend(self, ids, past, new_len):
         """A block of right-padded NEW tokens ids int64 [B,T] behind ``past[b]`` cached positions (int32 [B], device):
         tokens t < new_len[b] take positions past[b] + t and go into the cache; returns the logits [B,V] of each row's

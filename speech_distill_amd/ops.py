@@ -1122,3 +1122,48 @@ def sample_step(logits, uniforms, seq, prompt_len, lens, finished, params, works
                              workspace.data_ptr(), workspace.numel(), C.byref(params), B, V, seq.shape[1], _stream()),
           "sd_sample_step")
     return next_out, pos_out
+
+
+def sample_env(params):
+    """include/sd_hip.h sd_sample_env of a list of ``SampleParams``: what the launches of one per-row step must cover."""
+    from ._lib import SampleEnv
+    sampling = [p for p in params if p.do_sample]
+    return SampleEnv(max([p.top_k for p in sampling], default=0), int(bool(sampling)),
+                     int(any(p.use_ras for p in sampling)), int(any(p.top_k == 0 for p in sampling)))
+
+
+def sample_params_rows(params, device):
+    """A list of B ``SampleParams`` -> the device array sd_sample_step_rows reads: uint8 [B, 48]."""
+    raw = b"".join(bytes(p) for p in params)
+    return torch.frombuffer(bytearray(raw), dtype=torch.uint8).view(len(params), -1).to(device)
+
+
+def sample_step_rows(logits, uniforms, seq, prompt_len, lens, finished, params, max_new, env, workspace=None,
+                     next_out=None, pos_out=None):
+    """One sampling step with everything per row (sd_sample_step_rows): logits bf16 [B,V]; uniforms fp32 [B,u_stride,2], of
+    which row b reads pair lens[b] - prompt_len[b]; ``params`` uint8 [B,48] on the device (``sample_params_rows``);
+    ``max_new`` int32 [B] on the device; ``env`` the host ``SampleEnv`` (``sample_env``).  Updates seq int64 [B,cap], lens
+    int32 [B] and finished uint8 [B] in place.  -> (next token int64 [B], its position int32 [B])."""
+    _need(logits, torch.bfloat16, "logits"), _need(uniforms, torch.float32, "uniforms"), _need(seq, torch.int64, "seq")
+    _need(prompt_len, torch.int32, "prompt_len"), _need(lens, torch.int32, "lens"), _need(finished, torch.uint8, "finished")
+    _need(params, torch.uint8, "params"), _need(max_new, torch.int32, "max_new")
+    lib = load_lib()
+    B, V = logits.shape
+    from ._lib import SampleParams
+    if uniforms.dim() != 3 or uniforms.shape[0] != B or uniforms.shape[2] != 2 or seq.shape[0] != B:
+        raise ValueError("sample_step_rows: uniforms must be [B,u_stride,2] and seq [B,cap]")
+    if params.numel() != B * C.sizeof(SampleParams) or max_new.numel() != B or prompt_len.numel() != B or \
+            lens.numel() != B or finished.numel() != B:
+        raise ValueError("sample_step_rows: params, max_new, prompt_len, lens and finished hold one entry per row")
+    if workspace is None:
+        workspace = torch.empty(lib.sd_sample_workspace_bytes(B, V), dtype=torch.uint8, device=logits.device)
+    if next_out is None:
+        next_out = torch.empty(B, dtype=torch.int64, device=logits.device)
+    if pos_out is None:
+        pos_out = torch.empty(B, dtype=torch.int32, device=logits.device)
+    check(lib.sd_sample_step_rows(logits.data_ptr(), logits.stride(0), uniforms.data_ptr(), uniforms.shape[1],
+                                  seq.data_ptr(), prompt_len.data_ptr(), lens.data_ptr(), finished.data_ptr(),
+                                  next_out.data_ptr(), pos_out.data_ptr(), workspace.data_ptr(), workspace.numel(),
+                                  params.data_ptr(), max_new.data_ptr(), C.byref(env), B, V, seq.shape[1], _stream()),
+          "sd_sample_step_rows")
+    return next_out, pos_out

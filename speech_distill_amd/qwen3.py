@@ -892,6 +892,17 @@ class HipQwen3ForCausalLM(nn.Module):
         from .generation import GenerationSession
         return GenerationSession(self, batch_size, capacity, decode_kernels, pool=pool, weight_dtype=weight_dtype)
 
+    def generation_engine(self, pool, max_batch=8, decode_kernels="skinny", weight_dtype="bf16", sync_every=16):
+        """A ``GenerationEngine`` (engine.py): continuous batching over a ``PagePool`` -- requests of their own length,
+        budget, seed and sampling parameters are served in ``max_batch`` rows, and a row that finishes is refilled with the
+        next waiting request at once (the reference's engine is vLLM, soulxpodcast/engine/llm_engine.py:91,97-109).
+        ``eng.submit(ids, max_new_tokens=..., seed=..., <generate's sampling keywords>)`` -> id, ``eng.step()``,
+        ``eng.run()``, ``eng.result(id)``, ``eng.stats``, ``eng.close()``.  With ``decode_kernels="skinny"`` a request's
+        tokens are, bit for bit, those of a one-row session given the same prompt, parameters and seed, whatever else is in
+        flight; "tile" is accepted without that claim (its step is not batch-invariant)."""
+        from .engine import GenerationEngine
+        return GenerationEngine(self, pool, max_batch, decode_kernels, weight_dtype, sync_every)
+
     def kv_page_pool(self, n_pages, order=None, kv_dtype="bf16"):
         """A ``PagePool`` (paged.py) of ``n_pages`` pages of 256 positions for this model's paged sessions
         (``start_session(..., pool=pool)``); ``order``: an optional permutation of the page numbers, the order in which
