@@ -832,6 +832,43 @@ int sd_qwen3_mx_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p,
                             int max_len, const void* cos_tab, const void* sin_tab, const sd_kv_ref* kv, void* acts,
                             int64_t acts_bytes, void* logits, int B, int flags, void* stream);
 
+/* ---- wide weight-streaming GEMV for decode (M = batch <= 64): the semantics of sd_gemv_bf16 / sd_gemv_swiglu in the form of
+ * sd_gemv_mxfp8 -- the weights run as the A operand of v_mfma_f32_16x16x32_bf16, the rows of x as up to four 16-column B
+ * tiles against the same A fragment.
+ * sd_gemv_wide_bf16: y[m,n] = bf16(sum_k xn[m,k] w[n,k] + r[m,n]); xn = x, or RMSNorm(x; norm_gain, eps) when norm_gain !=
+ *   NULL -- bit-identical to sd_rmsnorm_fwd into a bf16 buffer followed by sd_gemv_wide_bf16 without a norm.
+ * sd_gemv_wide_swiglu: act[M,I] = silu(xn Wg^T) * (xn Wu^T), wgu = [gate rows | up rows] [2I,K]; gate and up are rounded to
+ *   bf16 -- bit-identical to sd_gemv_wide_bf16 with N = 2I into a bf16 gate|up buffer followed by sd_swiglu_fwd.
+ * Row independence: the bits of y[m,n] depend on x[m,:], w[n,:], r[m,n], norm_gain, eps and K only -- not on M, the other
+ *   rows, the slot of a 16-column B tile that row m occupies, N, the grid or the CU count.
+ * Reduction order of one element, fixed by K alone (no atomics, no split of K across workgroups): inside a K-step of 32 the
+ *   instruction's own order; a wave's K-steps ascending through the accumulator operand; the waves of a workgroup through
+ *   LDS in wave order; one rounding, bf16(sum + float(r)).  The bits are NOT those of sd_gemv_bf16: the order differs.
+ * Loads: the weights are read once per launch, 16 bytes per lane, non-temporal, with no LDS staging; rows >= M of x are
+ *   never read (zero fragments are formed in registers); nothing outside y[0..M, 0..N) is written.  y may be r under the
+ *   rule of sd_gemv_bf16; y must not overlap x or w.
+ * Supported: 1 <= M <= SD_GEMV_WIDE_MAX_M, N >= 1 (any), K % 32 == 0, K <= 8192 (<= 4096 with a norm), ld* >= the row
+ * length, x / w / norm_gain rows 16-byte aligned; anything else that is sane is SD_ERR_UNSUPPORTED, M <= 0 or a NULL x / w /
+ * y is SD_ERR_SHAPE.  Both are decided before any launch, y untouched. */
+#define SD_GEMV_WIDE_MAX_M 64
+int sd_gemv_wide_bf16(const void* x, const void* w, void* y, const void* r, const void* norm_gain, float eps, int M, int N,
+                      int K, int64_t ldx, int64_t ldw, int64_t ldy, int64_t ldr, void* stream);
+int sd_gemv_wide_swiglu(const void* x, const void* wgu, void* act, const void* norm_gain, float eps, int M, int I, int K,
+                        void* stream);
+/* sd_qwen3_decode_step_wide: the decode step of sd_qwen3_decode_step_flags (bf16 weights) on the wide GEMV, over a cache of
+ * any kind (sd_kv_ref).  The embedding; per layer sd_gemv_wide_bf16(norm_gain = ln1) for q|k|v, the cache's append and
+ * decode attention, sd_gemv_wide_bf16(r = x) for o, sd_gemv_wide_swiglu(norm_gain = ln2), sd_gemv_wide_bf16(r = x_mid) for
+ * down; ONE launch for the final norm + lm_head: 7 L + 2 launches.  Row b of the logits then depends on row b's token,
+ * position and cache only.  When any projection would refuse its shape (B > 64, hidden > 4096, ...) the WHOLE step runs
+ * the unflagged tile sequence of sd_qwen3_decode_step: never a mixture.  acts of sd_qwen3_decode_step_wide_acts_bytes(d,
+ * B, cap) with cap = the cache's capacity (cap, or max_pages * 256).  A NULL d / p / kv or a bad kind is SD_ERR_SHAPE, short
+ * acts SD_ERR_WORKSPACE, head_dim != 128 or Hq / Hkv outside {1, 2, 4} SD_ERR_UNSUPPORTED; every other check as
+ * sd_qwen3_mx_decode_step; all before the first launch. */
+int64_t sd_qwen3_decode_step_wide_acts_bytes(const sd_qwen3_dims* d, int B, int cap);
+int sd_qwen3_decode_step_wide(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* pos,
+                              int max_len, const void* cos_tab, const void* sin_tab, const sd_kv_ref* kv, void* acts,
+                              int64_t acts_bytes, void* logits, int B, void* stream);
+
 /* ---- stream placement.  HIP multiplexes streams onto a few hardware queues (4 by default); streams that share a
  * queue never overlap.  Measures, with a `spin_us`-long busy-wait kernel on stream_a and an empty one on stream_b,
  * whether work on b runs while a is busy: *overlap = 1/0.  Synchronises both streams (a calibration call, made once

@@ -51,8 +51,9 @@ def parse_args(argv=None):
     p.add_argument("--greedy", action="store_true", help="arg-max instead of sampling")
     p.add_argument("--seed", type=int, default=None)
     p.add_argument("--sync_every", type=int, default=16)
-    p.add_argument("--decode_kernels", choices=("tile", "skinny"), default="tile",
-                   help="skinny: weight-streaming GEMV kernels for the decode step (batch_size <= 16)")
+    p.add_argument("--decode_kernels", choices=("tile", "skinny", "wide"), default="tile",
+                   help="skinny: weight-streaming GEMV kernels for the decode step (batch_size <= 16); wide: the MFMA "
+                        "weight-streaming kernels (batch_size <= 64, bf16 weights)")
     p.add_argument("--kv_pool_pages", type=int, default=0,
                    help="0: every batch reserves a contiguous KV cache for its worst case.  N > 0: every batch's session "
                         "draws pages of 256 positions from ONE pool of N pages, turn by turn (the paged cache of the "

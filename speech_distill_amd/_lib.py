@@ -266,6 +266,12 @@ PROTOTYPES = {
     "sd_qwen3_mx_decode_step_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
     "sd_qwen3_mx_decode_step": (_i, [C.POINTER(Dims), C.POINTER(ParamsMx), _vp, _vp, _i, _vp, _vp, C.POINTER(KvRef), _vp,
                                      _i64, _vp, _i, _i, _vp]),
+    # the wide GEMV (M <= 64) and the decode step on it, over a cache of any kind
+    "sd_gemv_wide_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i64, _i64, _i64, _i64, _vp]),
+    "sd_gemv_wide_swiglu": (_i, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _vp]),
+    "sd_qwen3_decode_step_wide_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
+    "sd_qwen3_decode_step_wide": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _i, _vp, _vp, C.POINTER(KvRef), _vp,
+                                       _i64, _vp, _i, _vp]),
 }
 
 

@@ -435,36 +435,45 @@ struct DecodeActs {
   }
 };
 
-// true when every GEMV of a skinny step accepts its shape: decided for the whole step before the first launch
-bool skinny_step_ok(const sd_qwen3_params* p, const Sizes& s, const DecodeActs& a, const void* logits, int B) {
-  bool ok = sd_gemv_check(a.x, p->lm_head, logits, nullptr, p->final_norm, B, s.V, s.h, s.h, s.h, s.V, 0) == 0;
+// true when every GEMV of a skinny (sd_gemv_check) or wide (sd_gemv_wide_check) step accepts its shape: decided for the
+// whole step before the first launch
+using GemvCheck = int (*)(const void*, const void*, const void*, const void*, const void*, int, int, int, int64_t, int64_t,
+                          int64_t, int64_t);
+bool gemv_step_ok(GemvCheck chk, const sd_qwen3_params* p, const Sizes& s, const DecodeActs& a, const void* logits, int B) {
+  bool ok = chk(a.x, p->lm_head, logits, nullptr, p->final_norm, B, s.V, s.h, s.h, s.h, s.V, 0) == 0;
   for (int l = 0; ok && l < s.L; ++l) {
     const sd_qwen3_layer& w = p->layers_host[l];
-    ok = sd_gemv_check(a.x, w.wqkv, a.qkv, nullptr, w.ln1, B, s.QKV, s.h, s.h, s.h, s.QKV, 0) == 0 &&
-         sd_gemv_check(a.ao, w.wo, a.x_mid, a.x, nullptr, B, s.h, s.QD, s.QD, s.QD, s.h, s.h) == 0 &&
-         sd_gemv_check(a.x_mid, w.wgu, a.act, nullptr, w.ln2, B, s.I, s.h, s.h, s.h, s.I, 0) == 0 &&
-         sd_gemv_check(a.act, w.wdown, a.x, a.x_mid, nullptr, B, s.h, s.I, s.I, s.I, s.h, s.h) == 0;
+    ok = chk(a.x, w.wqkv, a.qkv, nullptr, w.ln1, B, s.QKV, s.h, s.h, s.h, s.QKV, 0) == 0 &&
+         chk(a.ao, w.wo, a.x_mid, a.x, nullptr, B, s.h, s.QD, s.QD, s.QD, s.h, s.h) == 0 &&
+         chk(a.x_mid, w.wgu, a.act, nullptr, w.ln2, B, s.I, s.h, s.h, s.h, s.I, 0) == 0 &&
+         chk(a.act, w.wdown, a.x, a.x_mid, nullptr, B, s.h, s.I, s.I, s.I, s.h, s.h) == 0;
   }
   return ok;
 }
+
+// internal step kind of decode_step_impl (no entry accepts it as a flag bit): the GEMV sequence on the wide kernels
+constexpr int kStepWide = 0x100;
 
 // the launches of a decode step over either kind of cache; every argument was checked by the entry
 int decode_step_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* pos, int max_len,
                      const void* cos_tab, const void* sin_tab, const KvSink& kv, const Sizes& s, const DecodeActs& a,
                      void* logits, int B, int flags, void* stream) {
-  const bool skinny = (flags & SD_DECODE_SKINNY) && skinny_step_ok(p, s, a, logits, B);
+  const bool wide = (flags & kStepWide) && gemv_step_ok(sd_gemv_wide_check, p, s, a, logits, B);
+  const bool skinny = (flags & SD_DECODE_SKINNY) && gemv_step_ok(sd_gemv_check, p, s, a, logits, B);
   RUN(sd_embedding_fwd(ids, p->embed, a.x, B, s.h, s.V, stream));
-  if (skinny) {
+  if (skinny || wide) {
+    const auto gemv = wide ? sd_gemv_wide_bf16 : sd_gemv_bf16;
+    const auto gemv_swiglu = wide ? sd_gemv_wide_swiglu : sd_gemv_swiglu;
     for (int l = 0; l < s.L; ++l) {
       const sd_qwen3_layer& w = p->layers_host[l];
-      RUN(sd_gemv_bf16(a.x, w.wqkv, a.qkv, nullptr, w.ln1, d->eps, B, s.QKV, s.h, s.h, s.h, s.QKV, 0, stream));
+      RUN(gemv(a.x, w.wqkv, a.qkv, nullptr, w.ln1, d->eps, B, s.QKV, s.h, s.h, s.h, s.QKV, 0, stream));
       RUN(kv.step(s, l, w.q_gain, w.k_gain, a.qkv, a.q, a.ao, cos_tab, sin_tab, pos, a.ws, a.ws_bytes, B, max_len, d->eps,
                   stream));
-      RUN(sd_gemv_bf16(a.ao, w.wo, a.x_mid, a.x, nullptr, 0.f, B, s.h, s.QD, s.QD, s.QD, s.h, s.h, stream));
-      RUN(sd_gemv_swiglu(a.x_mid, w.wgu, a.act, w.ln2, d->eps, B, s.I, s.h, stream));
-      RUN(sd_gemv_bf16(a.act, w.wdown, a.x, a.x_mid, nullptr, 0.f, B, s.h, s.I, s.I, s.I, s.h, s.h, stream));
+      RUN(gemv(a.ao, w.wo, a.x_mid, a.x, nullptr, 0.f, B, s.h, s.QD, s.QD, s.QD, s.h, s.h, stream));
+      RUN(gemv_swiglu(a.x_mid, w.wgu, a.act, w.ln2, d->eps, B, s.I, s.h, stream));
+      RUN(gemv(a.act, w.wdown, a.x, a.x_mid, nullptr, 0.f, B, s.h, s.I, s.I, s.I, s.h, s.h, stream));
     }
-    return sd_gemv_bf16(a.x, p->lm_head, logits, nullptr, p->final_norm, d->eps, B, s.V, s.h, s.h, s.h, s.V, 0, stream);
+    return gemv(a.x, p->lm_head, logits, nullptr, p->final_norm, d->eps, B, s.V, s.h, s.h, s.h, s.V, 0, stream);
   }
   for (int l = 0; l < s.L; ++l) {
     const sd_qwen3_layer& w = p->layers_host[l];
@@ -800,6 +809,27 @@ extern "C" int sd_qwen3_decode_step_paged_mx(const sd_qwen3_dims* d, const sd_qw
                                              const sd_kv_pages* kvp, void* acts, int64_t acts_bytes, void* logits, int B,
                                              int flags, void* stream) {
   return decode_step_paged(d, p, ids, pos, max_len, cos_tab, sin_tab, kvp, acts, acts_bytes, logits, B, flags, stream, true);
+}
+
+// sd_qwen3_decode_step_wide: the GEMV sequence on the wide kernels over a cache of any kind
+extern "C" int64_t sd_qwen3_decode_step_wide_acts_bytes(const sd_qwen3_dims* d, int B, int cap) {
+  return sd_qwen3_decode_acts_bytes(d, B, cap);
+}
+
+extern "C" int sd_qwen3_decode_step_wide(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
+                                         const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab,
+                                         const sd_kv_ref* kvr, void* acts, int64_t acts_bytes, void* logits, int B,
+                                         void* stream) {
+  if (!d || !p || !kvr) return SD_ERR_SHAPE;
+  if (d->head_dim != 128) return SD_ERR_UNSUPPORTED;
+  if (B <= 0 || max_len <= 0 || !ids || !pos || !logits || !acts) return SD_ERR_SHAPE;
+  RUN(gqa_check(d));
+  KvSink kv = {};
+  RUN(ref_sink(d, kvr, B, &kv));
+  const Sizes s(d, B, 1);
+  const DecodeActs a(d, B, kv.cap, (char*)acts);
+  if (acts_bytes < a.total) return SD_ERR_WORKSPACE;
+  return decode_step_impl(d, p, ids, pos, max_len, cos_tab, sin_tab, kv, s, a, logits, B, kStepWide, stream);
 }
 
 extern "C" int sd_qwen3_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,

@@ -460,15 +460,6 @@ extern "C" int sd_qwen3_forward_mx(const sd_qwen3_dims* d, const sd_qwen3_params
 // sd_model.hip over sd_qwen3_params_mx; one descriptor (sd_kv_ref) names the cache of any of the three kinds.
 namespace {
 
-// the descriptor -> a KvSink (0, or the code to return); B is positive
-int ref_sink(const sd_qwen3_dims* d, const sd_kv_ref* kv, int B, KvSink* sink) {
-  if (kv->kind == 1 || kv->kind == 2) return paged_sink(d, kv->pages, sink, kv->kind == 2);
-  if (kv->kind != 0 || !kv->cache || kv->cap <= 0) return SD_ERR_SHAPE;
-  if (kv->cache_bytes < sd_kvcache_bytes(d, B, kv->cap)) return SD_ERR_WORKSPACE;
-  *sink = KvSink{(char*)kv->cache, kv->cap};
-  return 0;
-}
-
 // head rows behind the forward's activation set -- for an extend also the gathered cos / sin rows -- then the forward
 int block_forward_mx(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids, const int32_t* kv_len,
                      const void* cos_tab, const void* sin_tab, void* acts, void* logits, int B, int T, void* stream,

@@ -15,6 +15,19 @@ __attribute__((visibility("hidden"))) int sd_gemv_check(const void* x, const voi
                                                         const void* norm_gain, int M, int N, int K, int64_t ldx,
                                                         int64_t ldw, int64_t ldy, int64_t ldr);
 
+// The checks of sd_gemv_wide_bf16 (and, with N = ldy = I and no residual, of sd_gemv_wide_swiglu) without a launch: 0, or
+// the code the entry returns.  sd_gemv_wide.hip runs them in front of every launch; the wide decode step asks them for
+// every projection before its first launch.  K <= 8192 = 8 waves x 32 K-steps of 32; a norm stops at sd_rmsnorm_fwd's 4096.
+static inline int sd_gemv_wide_check(const void* x, const void* w, const void* y, const void* r, const void* norm_gain, int M,
+                                     int N, int K, int64_t ldx, int64_t ldw, int64_t ldy, int64_t ldr) {
+  if (!x || !w || !y || M <= 0 || N <= 0 || K <= 0) return SD_ERR_SHAPE;
+  if (M > SD_GEMV_WIDE_MAX_M || (K & 31) || K > 8192 || (norm_gain && K > 4096) || N > (1 << 29)) return SD_ERR_UNSUPPORTED;
+  if (ldx < K || ldw < K || ldy < N || (r && ldr < N)) return SD_ERR_UNSUPPORTED;
+  if ((ldx & 7) || (ldw & 7) || ((uintptr_t)x & 15) || ((uintptr_t)w & 15) || ((uintptr_t)norm_gain & 15))
+    return SD_ERR_UNSUPPORTED;
+  return 0;
+}
+
 // sd_decode.hip: cos / sin rows of the positions past[b] + t (clamped to [0, cap - 1]) gathered into [B*T,128] tables, on
 // the device.  sd_qwen3_extend runs its q/k-norm + RoPE step on them with one "sequence" of B*T rows, the way the packed
 // forward feeds per-token positions.  Internal: not exported from the library.
@@ -136,6 +149,15 @@ static inline int paged_sink(const sd_qwen3_dims* d, const sd_kv_pages* kv, KvSi
   const int64_t bf16_bytes = sd_kvpool_bytes(d, kv->n_pages);
   if (kv->pool_bytes < (mx ? bf16_bytes / 256 * 132 : bf16_bytes)) return SD_ERR_WORKSPACE;
   *sink = KvSink{(char*)kv->pool, kv->max_pages * SD_KV_PAGE, nullptr, nullptr, kv->table, kv->n_pages, kv->max_pages, mx};
+  return 0;
+}
+
+// the cache descriptor of any kind -> a KvSink (0, or the code to return); B is positive
+static inline int ref_sink(const sd_qwen3_dims* d, const sd_kv_ref* kv, int B, KvSink* sink) {
+  if (kv->kind == 1 || kv->kind == 2) return paged_sink(d, kv->pages, sink, kv->kind == 2);
+  if (kv->kind != 0 || !kv->cache || kv->cap <= 0) return SD_ERR_SHAPE;
+  if (kv->cache_bytes < sd_kvcache_bytes(d, B, kv->cap)) return SD_ERR_WORKSPACE;
+  *sink = KvSink{(char*)kv->cache, kv->cap};
   return 0;
 }
 

@@ -6,7 +6,9 @@ fixed batch until its last row stops; here a row that finishes is refilled at on
 only.  With ``decode_kernels="skinny"`` the contract is exact: a request served by the engine yields, bit for bit, the
 tokens a one-row session yields for it alone -- its prefill is the B = 1 prefill of exactly its prompt, the skinny decode
 step makes a row's logits independent of the batch around it, and the sampler (sd_sample_step_rows) works row by row
-with the row's own parameters, budget and uniform stream.
+with the row's own parameters, budget and uniform stream.  "skinny" is exact up to ``max_batch = 16`` (above it its step
+falls back to the tile GEMMs); ``decode_kernels="wide"`` (bf16 weights) carries the same contract up to ``max_batch = 64``,
+against a one-row "wide" session.
 
 Two layers, in the style of paged.py; the first is pure host code (no device, no library: tests/test_engine_cpu.py runs it
 as it is):
@@ -226,8 +228,9 @@ class GenerationEngine(EngineLoop):
     def __init__(self, model, pool, max_batch=8, decode_kernels="skinny", weight_dtype="bf16", sync_every=16, capacity=None):
         import torch
         from ._lib import load_lib
-        from .generation import Decoder, cache_capacity
+        from .generation import Decoder, _check_decode_kernels, cache_capacity
         from .ops import sample_params, sample_params_rows
+        _check_decode_kernels(decode_kernels, weight_dtype)
         if pool is None:
             raise ValueError("the engine serves its rows from a page pool: model.kv_page_pool(n_pages)")
         if int(max_batch) < 1 or int(sync_every) < 1:

@@ -30,7 +30,7 @@ from .paged import PAGE, PageTable, pages_for
 
 REFERENCE_SAMPLING = dict(do_sample=True, temperature=0.6, top_k=100, top_p=0.9, repetition_penalty=1.25, use_ras=True,
                           win_size=25, tau_r=0.2)  # soulxpodcast/config.py:107-118
-DECODE_KERNELS = ("tile", "skinny")
+DECODE_KERNELS = ("tile", "skinny", "wide")
 WEIGHT_DTYPES = ("bf16", "mxfp8")
 DEFAULT_CACHE_CAPACITY = 32768  # positions; Qwen3's max_position_embeddings when the config does not say
 
@@ -42,9 +42,12 @@ def cache_capacity(model):
     return int(cap or DEFAULT_CACHE_CAPACITY)
 
 
-def _check_decode_kernels(decode_kernels):
+def _check_decode_kernels(decode_kernels, weight_dtype="bf16"):
     if decode_kernels not in DECODE_KERNELS:
         raise ValueError(f"decode_kernels must be one of {DECODE_KERNELS}, got {decode_kernels!r}")
+    if decode_kernels == "wide" and weight_dtype == "mxfp8":
+        raise ValueError('decode_kernels="wide" streams bf16 weights only: there is no 64-row MXFP8 GEMV (use "skinny" '
+                         'or "tile" with weight_dtype="mxfp8")')
 
 
 def _check_weight_dtype(model, weight_dtype):
@@ -76,6 +79,10 @@ class Decoder:
     logits [B,V].  ``decode_kernels``: "tile" runs the step's projections on the training tile GEMMs; "skinny" (B <= 16)
     streams the weights through the GEMV kernels with the norms and the SwiGLU fused in (SD_DECODE_SKINNY) -- a row's
     logits then do not depend on the batch around it.  A step whose shapes the GEMV kernels refuse runs the tile sequence.
+    "wide" (B <= 64, bf16 weights only): the same seven launches per layer on the MFMA weight-streaming kernels
+    (sd_qwen3_decode_step_wide, one entry for the three cache kinds) -- batch-invariant like "skinny", with other bits than
+    "skinny" (another summation order); B > 64 runs the tile sequence.  ``prefill`` and ``extend`` do not depend on the
+    mode.  ``flags`` is SD_DECODE_SKINNY for "skinny" and 0 otherwise; ``wide`` says whether the wide entry is called.
 
     ``pool`` (a ``PagePool``): the paged form (llm_engine.py:91).  No cache buffer; the decoder owns a device page table
     int32 [B, ceil(cap / 256)] and its host mirror ``pages`` (a ``PageTable``), ``cap`` becomes that many whole pages, and
@@ -93,9 +100,10 @@ class Decoder:
     weights through sd_gemv_mxfp8.  Embedding, attention, the norms of q / k, the final norm and the lm_head stay bf16."""
 
     def __init__(self, model, B, cap, decode_kernels="tile", pool=None, weight_dtype="bf16"):
-        _check_decode_kernels(decode_kernels)
+        _check_decode_kernels(decode_kernels, weight_dtype)
         _check_weight_dtype(model, weight_dtype)
         self.flags = 1 if decode_kernels == "skinny" else 0   # include/sd_hip.h SD_DECODE_SKINNY
+        self.wide = decode_kernels == "wide"
         self.weight_dtype = weight_dtype
         self.model, self.B, self.cap = model, int(B), int(cap)
         lib = load_lib()
@@ -121,13 +129,14 @@ class Decoder:
             nb = lib.sd_kvcache_bytes(C.byref(d), self.B, self.cap)
             check(min(nb, 0), "sd_kvcache_bytes")
             self.cache = torch.empty(nb, dtype=torch.uint8, device=dev)
-        if weight_dtype == "mxfp8":   # include/sd_hip.h sd_kv_ref: fixed for the decoder's life
+        if weight_dtype == "mxfp8" or self.wide:   # include/sd_hip.h sd_kv_ref: fixed for the decoder's life
             if pool is not None:
                 self._kvref = _lib.KvRef(2 if self._mx else 1, None, 0, 0, C.pointer(self._kvp))
             else:
                 self._kvref = _lib.KvRef(0, self.cache.data_ptr(), self.cache.numel(), self.cap, None)
-            nb = lib.sd_qwen3_mx_decode_step_acts_bytes(C.byref(d), self.B, self.cap)
-            check(min(nb, 0), "sd_qwen3_mx_decode_step_acts_bytes")
+            name = "sd_qwen3_decode_step_wide_acts_bytes" if self.wide else "sd_qwen3_mx_decode_step_acts_bytes"
+            nb = getattr(lib, name)(C.byref(d), self.B, self.cap)
+            check(min(nb, 0), name)
         else:
             nb = lib.sd_qwen3_decode_acts_bytes(C.byref(d), self.B, self.cap)
         self.step_acts = torch.empty(nb, dtype=torch.uint8, device=dev)
@@ -312,6 +321,12 @@ class Decoder:
                                               self.step_acts.data_ptr(), self.step_acts.numel(), self.logits.data_ptr(),
                                               self.B, self.flags, _stream()), "sd_qwen3_mx_decode_step")
             return self.logits
+        if self.wide:
+            check(lib.sd_qwen3_decode_step_wide(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(), pos.data_ptr(),
+                                                int(max_len), self.cos.data_ptr(), self.sin.data_ptr(), C.byref(self._kvref),
+                                                self.step_acts.data_ptr(), self.step_acts.numel(), self.logits.data_ptr(),
+                                                self.B, _stream()), "sd_qwen3_decode_step_wide")
+            return self.logits
         if self.pool is not None:
             name = "sd_qwen3_decode_step_paged" + self._mx
             check(getattr(lib, name)(C.byref(m._cdims), C.byref(self._params()), ids.data_ptr(), pos.data_ptr(),
@@ -333,7 +348,7 @@ def _check_args(model, B, T, max_new_tokens, min_new_tokens, do_sample, temperat
     lengths against its own capacity instead)."""
     if weight_dtype not in WEIGHT_DTYPES:
         raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, got {weight_dtype!r}")
-    _check_decode_kernels(decode_kernels)
+    _check_decode_kernels(decode_kernels, weight_dtype)
     if max_new_tokens < 1:
         raise ValueError(f"max_new_tokens must be at least 1, got {max_new_tokens}")
     if top_k < 0 or top_k > 128:
@@ -373,6 +388,7 @@ class GenerationSession:
     The host keeps an upper bound of the lengths (old bound + T_in + max_new_tokens) and reads the true lengths only when
     that bound would pass ``capacity``.  ``decode_kernels="skinny"``: the decode STEPS are batch-invariant; the extend pass
     runs the tile GEMMs at M = B * T, so a row equals the row generated alone within a turn's decode steps only.
+    ``decode_kernels="wide"`` (bf16 weights): the same for up to 64 rows, on the MFMA weight-streaming kernels.
 
     ``pool`` (a ``PagePool``; llm_engine.py:91): the paged session.  It holds no cache buffer but a page table, and several
     sessions may share one pool.  Allocation rule: a paged session ALWAYS takes its one host read at the start of a turn,

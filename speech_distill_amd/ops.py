@@ -673,9 +673,11 @@ def _rows2d(t, name):
     return t
 
 
-def gemv_bf16(x, w, residual=None, norm_gain=None, eps=1e-6, out=None):
+def gemv_bf16(x, w, residual=None, norm_gain=None, eps=1e-6, out=None, wide=False):
     """y [M,N] = xn [M,K] @ w[N,K]^T (+ residual), xn = x or RMSNorm(x; norm_gain, eps); 1 <= M <= 16.  x, w, residual and
-    out may have strided rows.  The bits of y[m,n] depend on row m, weight row n and K only."""
+    out may have strided rows.  The bits of y[m,n] depend on row m, weight row n and K only.  ``wide``: sd_gemv_wide_bf16
+    (the MFMA form, 1 <= M <= 64, K % 32 == 0; another summation order, so other bits than the 16-row kernel)."""
+    entry = "sd_gemv_wide_bf16" if wide else "sd_gemv_bf16"
     _rows2d(x, "x"), _rows2d(w, "w")
     M, K = x.shape
     N, Kw = w.shape
@@ -688,15 +690,17 @@ def gemv_bf16(x, w, residual=None, norm_gain=None, eps=1e-6, out=None):
         raise ValueError("gemv_bf16: out / residual must be [M,N]")
     if norm_gain is not None and _need(norm_gain, torch.bfloat16, "norm_gain").numel() != K:
         raise ValueError(f"norm_gain must hold K = {K} elements, got {norm_gain.numel()}")
-    check(load_lib().sd_gemv_bf16(x.data_ptr(), w.data_ptr(), out.data_ptr(), _p(residual), _p(norm_gain), float(eps), M, N,
-                                  K, x.stride(0), w.stride(0), out.stride(0),
-                                  0 if residual is None else residual.stride(0), _stream()), "sd_gemv_bf16")
+    check(getattr(load_lib(), entry)(x.data_ptr(), w.data_ptr(), out.data_ptr(), _p(residual), _p(norm_gain), float(eps), M, N,
+                                     K, x.stride(0), w.stride(0), out.stride(0),
+                                     0 if residual is None else residual.stride(0), _stream()), entry)
     return out
 
 
-def gemv_swiglu(x, wgu, norm_gain=None, eps=1e-6):
+def gemv_swiglu(x, wgu, norm_gain=None, eps=1e-6, wide=False):
     """act [M,I] = silu(xn Wg^T) * (xn Wu^T) with wgu = [gate rows | up rows] [2I,K]; 1 <= M <= 16.  Equals
-    swiglu_fwd(gemv_bf16(x, wgu, norm_gain=...)) bit for bit."""
+    swiglu_fwd(gemv_bf16(x, wgu, norm_gain=...)) bit for bit.  ``wide``: sd_gemv_wide_swiglu (1 <= M <= 64), which equals
+    swiglu_fwd(gemv_bf16(x, wgu, norm_gain=..., wide=True))."""
+    entry = "sd_gemv_wide_swiglu" if wide else "sd_gemv_swiglu"
     _need(x, torch.bfloat16, "x"), _need(wgu, torch.bfloat16, "wgu")
     if x.dim() != 2 or wgu.dim() != 2:
         raise ValueError(f"gemv_swiglu: x must be [M,K] and wgu [2I,K], got {tuple(x.shape)} and {tuple(wgu.shape)}")
@@ -707,8 +711,8 @@ def gemv_swiglu(x, wgu, norm_gain=None, eps=1e-6):
     if norm_gain is not None and _need(norm_gain, torch.bfloat16, "norm_gain").numel() != K:
         raise ValueError(f"norm_gain must hold K = {K} elements, got {norm_gain.numel()}")
     act = torch.empty(M, I, dtype=torch.bfloat16, device=x.device)
-    check(load_lib().sd_gemv_swiglu(x.data_ptr(), wgu.data_ptr(), act.data_ptr(), _p(norm_gain), float(eps), M, I, K,
-                                    _stream()), "sd_gemv_swiglu")
+    check(getattr(load_lib(), entry)(x.data_ptr(), wgu.data_ptr(), act.data_ptr(), _p(norm_gain), float(eps), M, I, K,
+                                     _stream()), entry)
     return act
 
 

@@ -853,7 +853,8 @@ class HipQwen3ForCausalLM(nn.Module):
         under no_grad on the current stream; the host reads the finished flags once every ``sync_every`` steps, and the
         tokens do not depend on that number.  ``decode_kernels``: "tile" (default) runs the step's projections on the tile
         GEMMs; "skinny" streams the weights through the GEMV kernels for batches of up to 16 rows, with the norms and the
-        SwiGLU fused in: a row's tokens then equal those of the row generated alone.
+        SwiGLU fused in: a row's tokens then equal those of the row generated alone.  "wide" does the same for up to 64
+        rows on the MFMA weight-streaming kernels (bf16 weights only; its bits are not those of "skinny").
 
         Raises before any launch: ValueError for another ``decode_kernels``, when T + max_new_tokens exceeds the cache
         capacity (``kv_cache_capacity`` or the config's ``max_position_embeddings``), when ``top_k > 128`` or when the mask is not right-padded;
@@ -863,7 +864,8 @@ class HipQwen3ForCausalLM(nn.Module):
         ``weight_dtype="mxfp8"`` (default "bf16"): prefill and every step run the four projections of each layer on the
         model's MXFP8 weights (``set_inference_precision``'s format, whatever the precision the model is set to); with
         "skinny" the 8-bit weights are streamed through the block-scaled GEMV.  Needs a frozen model without LoRA and
-        the dimensions "mxfp8" needs: ValueError otherwise, and for any other value, before any allocation."""
+        the dimensions "mxfp8" needs: ValueError otherwise, and for any other value, before any allocation.  ValueError
+        too for ``decode_kernels="wide"`` with "mxfp8": there is no 64-row MXFP8 GEMV."""
         from .generation import generate
         return generate(self, input_ids, attention_mask, max_new_tokens, min_new_tokens, do_sample, temperature, top_k,
                         top_p, repetition_penalty, eos_token_id, pad_token_id, use_ras, win_size, tau_r, seed, sync_every,
@@ -875,7 +877,8 @@ class HipQwen3ForCausalLM(nn.Module):
         turns (soulxpodcast/models/soulxpodcast.py:342,378-380).  ``sess.generate(ids, mask, ...)`` takes a turn and returns
         its new tokens, ``sess.extend(ids, mask)`` appends without sampling (chunked prefill), ``sess.reset(rows)`` forgets
         rows.  With ``decode_kernels="skinny"`` only the decode steps of a turn are batch-invariant: the extend pass runs the
-        tile GEMMs.  NotImplementedError for a model set to "mxfp8".
+        tile GEMMs; "wide" is the same for up to 64 rows (bf16 weights only).  NotImplementedError for a model set to
+        "mxfp8".
 
         ``pool`` (a ``PagePool`` of ``kv_page_pool``): the session keeps no cache buffer of its own; it owns a page table
         and takes pages of 256 positions from the pool turn by turn (paged.py; the reference's engine runs vLLM's paged
@@ -899,7 +902,8 @@ class HipQwen3ForCausalLM(nn.Module):
         ``eng.submit(ids, max_new_tokens=..., seed=..., <generate's sampling keywords>)`` -> id, ``eng.step()``,
         ``eng.run()``, ``eng.result(id)``, ``eng.stats``, ``eng.close()``.  With ``decode_kernels="skinny"`` a request's
         tokens are, bit for bit, those of a one-row session given the same prompt, parameters and seed, whatever else is in
-        flight; "tile" is accepted without that claim (its step is not batch-invariant)."""
+        flight, for ``max_batch <= 16``; ``decode_kernels="wide"`` (bf16 weights) holds the same against a one-row "wide"
+        session for ``max_batch <= 64``; "tile" is accepted without that claim (its step is not batch-invariant)."""
         from .engine import GenerationEngine
         return GenerationEngine(self, pool, max_batch, decode_kernels, weight_dtype, sync_every)
 
