@@ -181,8 +181,8 @@ int sd_rows_scatter(const void* src, const int64_t* rows, void* dst, int n, int 
 int sd_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse, const int32_t* kv_len, int64_t ldq,
                 int64_t ldk, int64_t ldv, int64_t ldo, int B, int T, int Hq, int Hkv, int head_dim, float scale,
                 void* stream);
-/* delta: fp32 [B,Hq,T] scratch (rowsum(dO*O)).  sd_attn_bwd2: same, with the dQ kernel launched on `side_stream`
- * (nullable) beside the dK/dV kernel -- they only share read-only inputs; `stream` has joined when it returns. */
+/* delta: fp32 [B,Hq,T] scratch (rowsum(dO*O)).  sd_attn_bwd2: the same call; dQ, dK and dV come from ONE launch on
+ * `stream`, and `side_stream` (nullable) is not used (it carried the dQ kernel while that was a launch of its own). */
 int sd_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
                 float* delta, void* dq, void* dk, void* dv, const int32_t* kv_len, int64_t ldq, int64_t ldk, int64_t ldv,
                 int64_t ldo, int64_t lddq, int64_t lddk, int64_t lddv, int B, int T, int Hq, int Hkv, int head_dim,

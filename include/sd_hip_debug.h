@@ -37,11 +37,14 @@
  *                                       decoder layers of a SD_FWD_CONCURRENT forward that run with the shared-GPU tiles, the
  *                                       rest run as if alone (-1 = all): for an INFERENCE forward (the teacher) / for a forward
  *                                       that saves activations (the student)
- *   model.overlap_mask         31       sd_qwen3_backward: bit0 lm_head dW, bit1 gain reduces, bit2 attention dQ on the side
- *                                       stream, bit3 grouped per-layer dW, bit4 one batched gain reduce per layer
+ *   model.overlap_mask         31       sd_qwen3_backward: bit0 lm_head dW, bit1 gain reduces, bit2 the side stream is handed to
+ *                                       sd_attn_bwd2 (which uses it only under attn.bwd_split), bit3 grouped per-layer dW, bit4
+ *                                       one batched gain reduce per layer
  *   topk.nt                    0        threads per row of topk_kernel (256|512|1024; 0 = 512)
  *   qk_bwd.blocks              512      workgroups of qknorm_rope_bwd_kernel
  *   attn.variant               0        bit0: forward without the in-wave software pipeline at any T; bit1: with it at any T
+ *   attn.bwd_split             0        sd_attn_bwd2: 1 = dQ and dK/dV as two launches (dQ on side_stream when given, joined
+ *                                       by events) instead of one launch on `stream`; same results bit for bit
  *   reset                      -        restore every default
  */
 #pragma once

@@ -760,20 +760,20 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const bf16* __restrict_
 // a group rb = w&1 is the 32-row block and half = (w>>1)&1 splits the K/V tiles (t = 2i + half) through its own double
 // buffer; the two partial dQ^T of a row block are added through LDS at the end in a fixed order.
 // dQ^T[d][q] = scale * sum_key K^T[d][key] dS^T[key][q].
+// The body of workgroup `wg_id` of `n_wg` (the numbering attn_wg decodes), written once for the kernel of its own and
+// for attn_bwd_kernel; smem: the caller's ONE __shared__ object, 8 tiles = 2 halves x 2 stages x (K,V).
 template <bool VARLEN, class... VA>  // as attn_fwd_kernel
-__global__ __launch_bounds__(512) void attn_bwd_dq_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ Kp,
-                                                          const bf16* __restrict__ Vp, const bf16* __restrict__ dO,
-                                                          const float* __restrict__ LSE, const float* __restrict__ delta,
-                                                          bf16* __restrict__ dQ, const int* __restrict__ kv_len, long ldq,
-                                                          long ldk, long ldv, long ldo, long lddq, int T, int Hq, int Hkv,
-                                                          float scale, VA... vla) {
-  __shared__ __attribute__((aligned(16))) char smem[8 * TILE];  // 2 halves x 2 stages x (K,V)
+SD_DEV void attn_bwd_dq_body(char* smem, int wg_id, int n_wg, const bf16* __restrict__ Q, const bf16* __restrict__ Kp,
+                             const bf16* __restrict__ Vp, const bf16* __restrict__ dO, const float* __restrict__ LSE,
+                             const float* __restrict__ delta, bf16* __restrict__ dQ, const int* __restrict__ kv_len,
+                             long ldq, long ldk, long ldv, long ldo, long lddq, int T, int Hq, int Hkv, float scale,
+                             VA... vla) {
   const int lane = lane_id(), w8 = wave_id_uniform();
   const VarlenArgs vl{vla...};
   AttnWg vwg = {};
   long vtok0 = 0;
   if constexpr (VARLEN) {
-    vwg = attn_wg((int)blockIdx.x, (int)gridDim.x / Hq, Hq / Hkv, Hkv, 1);
+    vwg = attn_wg(wg_id, n_wg / Hq, Hq / Hkv, Hkv, 1);
     const VarlenDoc dc = varlen_doc(vl, vwg.pair, lane);
     if (dc.len == 0) return;
     T = dc.len;
@@ -783,7 +783,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(const bf16* __restrict
   const int grp = w8 >> 2, rb = w8 & 1, half = (w8 >> 1) & 1;
   const int w = grp * 2 + rb;  // 0..3 inside my half: staging share and merge slot
   const int n64 = (T + 63) / 64;
-  const AttnWg wg = VARLEN ? vwg : attn_wg((int)blockIdx.x, (n64 + 1) / 2, Hq / Hkv, Hkv, (int)gridDim.x / (((n64 + 1) / 2) * Hq));
+  const AttnWg wg = VARLEN ? vwg : attn_wg(wg_id, (n64 + 1) / 2, Hq / Hkv, Hkv, n_wg / (((n64 + 1) / 2) * Hq));
   const int tA = n64 - 1 - wg.pair, tB = wg.pair;
   const bool active = grp == 0 || tB != tA;
   const int hkv = wg.hkv, b = wg.b;
@@ -897,23 +897,20 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(const bf16* __restrict
 // tile strictly one after the other; two independent waves per SIMD overlap those phases.  To fit two waves into the
 // SIMD's 512 registers the two blocks' K and V (128 keys) live in LDS instead of registers (64 KiB), beside a 2-stage
 // (Q, dO) ring (64 KiB): waves 0-3 stage K and the Q tiles, waves 4-7 stage V and the dO tiles.
-template <bool VARLEN, class... VA>  // as attn_fwd_kernel, grid (ceil(M/128) + n) * Hkv
-__global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ Kp,
-                                                           const bf16* __restrict__ Vp, const bf16* __restrict__ dO,
-                                                           const float* __restrict__ LSE, const float* __restrict__ delta,
-                                                           bf16* __restrict__ dK, bf16* __restrict__ dV,
-                                                           const int* __restrict__ kv_len, long ldq, long ldk, long ldv,
-                                                           long ldo, long lddk, long lddv, int T, int Hq, int Hkv,
-                                                           float scale, VA... vla) {
-  // [K: heavy block 64 rows | light block 64 rows][V: same][stage 0: Q, dO | stage 1: Q, dO | stat[2 stages][lse2|delta][64 q rows]]
-  // (ONE __shared__ object: a second one beside an LDS-DMA target makes hipcc drain vmcnt before LDS reads)
-  __shared__ __attribute__((aligned(16))) char smem[8 * TILE + 1024];
+// The body of workgroup `wg_id` of `n_wg`, as attn_bwd_dq_body.  smem, 8 tiles + 1 KiB:
+// [K: heavy block 64 rows | light block 64 rows][V: same][stage 0: Q, dO | stage 1: Q, dO | stat[2 stages][lse2|delta][64 q rows]]
+template <bool VARLEN, class... VA>  // as attn_fwd_kernel, (ceil(M/128) + n) * Hkv workgroups
+SD_DEV void attn_bwd_dkv_body(char* smem, int wg_id, int n_wg, const bf16* __restrict__ Q, const bf16* __restrict__ Kp,
+                              const bf16* __restrict__ Vp, const bf16* __restrict__ dO, const float* __restrict__ LSE,
+                              const float* __restrict__ delta, bf16* __restrict__ dK, bf16* __restrict__ dV,
+                              const int* __restrict__ kv_len, long ldq, long ldk, long ldv, long ldo, long lddk,
+                              long lddv, int T, int Hq, int Hkv, float scale, VA... vla) {
   const int lane = lane_id(), w8 = wave_id_uniform();
   const VarlenArgs vl{vla...};
   AttnWg vwg = {};
   long vtok0 = 0;
   if constexpr (VARLEN) {
-    vwg = attn_wg((int)blockIdx.x, (int)gridDim.x / Hkv, 1, Hkv, 1);
+    vwg = attn_wg(wg_id, n_wg / Hkv, 1, Hkv, 1);
     const VarlenDoc dc = varlen_doc(vl, vwg.pair, lane);
     if (dc.len == 0) return;
     T = dc.len;
@@ -924,7 +921,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const bf16* __restric
   const int sw = w8 & 3;                                       // staging share inside my group of four
   const int G = Hq / Hkv;
   const int n64 = (T + 63) / 64;
-  const AttnWg wg = VARLEN ? vwg : attn_wg((int)blockIdx.x, (n64 + 1) / 2, 1, Hkv, (int)gridDim.x / (((n64 + 1) / 2) * Hkv));
+  const AttnWg wg = VARLEN ? vwg : attn_wg(wg_id, (n64 + 1) / 2, 1, Hkv, n_wg / (((n64 + 1) / 2) * Hkv));
   const int hkv = wg.hkv, b = wg.b;
   const int kbA = wg.pair, kbB = n64 - 1 - wg.pair;  // heavy / light key block
   const bool active = grp == 0 || kbB != kbA;                       // odd block count: the middle block has no partner
@@ -1054,6 +1051,57 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const bf16* __restric
   }
 }
 
+// The whole backward as ONE launch: the role of a workgroup follows from blockIdx.x.  Ids [0, n_dkv) run the dK/dV body,
+// ids n_dkv8 + [0, n_dq) the dQ body, n_dkv8 = n_dkv rounded up to a multiple of 8 (the ids between return at once): a dQ
+// workgroup's own id then has the low three bits of blockIdx.x, which attn_wg takes for the XCD.  The two bodies share
+// read-only inputs only, and a workgroup is one or the other, so every barrier stays workgroup-uniform.  Workgroups are
+// dispatched in id order: the long dK/dV workgroups go out first and the dQ workgroups fill what is left (longest first).
+// Against two launches on two streams joined by events: 43 us instead of 38 + 23 us per layer on one stream, -0.44 /
+// -0.50 ms per config-2 step (tests/bench_knob_ab.py attn.bwd_split 0 1).
+// (ONE __shared__ object for both roles: a second one beside an LDS-DMA target makes hipcc drain vmcnt before LDS reads)
+template <bool VARLEN, class... VA>
+__global__ __launch_bounds__(512) void attn_bwd_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ Kp,
+                                                       const bf16* __restrict__ Vp, const bf16* __restrict__ dO,
+                                                       const float* __restrict__ LSE, const float* __restrict__ delta,
+                                                       bf16* __restrict__ dQ, bf16* __restrict__ dK, bf16* __restrict__ dV,
+                                                       const int* __restrict__ kv_len, long ldq, long ldk, long ldv,
+                                                       long ldo, long lddq, long lddk, long lddv, int T, int Hq, int Hkv,
+                                                       float scale, int n_dkv, int n_dq, VA... vla) {
+  __shared__ __attribute__((aligned(16))) char smem[8 * TILE + 1024];
+  const int id = (int)blockIdx.x, n_dkv8 = (n_dkv + 7) & ~7;
+  if (id < n_dkv)
+    attn_bwd_dkv_body<VARLEN>(smem, id, n_dkv, Q, Kp, Vp, dO, LSE, delta, dK, dV, kv_len, ldq, ldk, ldv, ldo, lddk, lddv, T,
+                              Hq, Hkv, scale, vla...);
+  else if (id >= n_dkv8)
+    attn_bwd_dq_body<VARLEN>(smem, id - n_dkv8, n_dq, Q, Kp, Vp, dO, LSE, delta, dQ, kv_len, ldq, ldk, ldv, ldo, lddq, T, Hq,
+                             Hkv, scale, vla...);
+}
+
+// The two bodies as kernels of their own (attn.bwd_split: the two-launch schedule, for A/B measurements and parity tests)
+template <bool VARLEN, class... VA>
+__global__ __launch_bounds__(512) void attn_bwd_dq_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ Kp,
+                                                          const bf16* __restrict__ Vp, const bf16* __restrict__ dO,
+                                                          const float* __restrict__ LSE, const float* __restrict__ delta,
+                                                          bf16* __restrict__ dQ, const int* __restrict__ kv_len, long ldq,
+                                                          long ldk, long ldv, long ldo, long lddq, int T, int Hq, int Hkv,
+                                                          float scale, VA... vla) {
+  __shared__ __attribute__((aligned(16))) char smem[8 * TILE];
+  attn_bwd_dq_body<VARLEN>(smem, (int)blockIdx.x, (int)gridDim.x, Q, Kp, Vp, dO, LSE, delta, dQ, kv_len, ldq, ldk, ldv, ldo,
+                           lddq, T, Hq, Hkv, scale, vla...);
+}
+template <bool VARLEN, class... VA>
+__global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const bf16* __restrict__ Q, const bf16* __restrict__ Kp,
+                                                           const bf16* __restrict__ Vp, const bf16* __restrict__ dO,
+                                                           const float* __restrict__ LSE, const float* __restrict__ delta,
+                                                           bf16* __restrict__ dK, bf16* __restrict__ dV,
+                                                           const int* __restrict__ kv_len, long ldq, long ldk, long ldv,
+                                                           long ldo, long lddk, long lddv, int T, int Hq, int Hkv,
+                                                           float scale, VA... vla) {
+  __shared__ __attribute__((aligned(16))) char smem[8 * TILE + 1024];
+  attn_bwd_dkv_body<VARLEN>(smem, (int)blockIdx.x, (int)gridDim.x, Q, Kp, Vp, dO, LSE, delta, dK, dV, kv_len, ldq, ldk, ldv,
+                            ldo, lddk, lddv, T, Hq, Hkv, scale, vla...);
+}
+
 int check_common(int B, int T, int Hq, int Hkv, long ldq, long ldk, long ldv, long ldo) {
   if (B <= 0 || T <= 0 || Hq <= 0 || Hkv <= 0 || (Hq % Hkv)) return SD_ERR_SHAPE;
   if ((ldq | ldk | ldv | ldo) & 7) return SD_ERR_ALIGN;
@@ -1099,6 +1147,52 @@ extern "C" int sd_attn_fwd(const void* q, const void* k, const void* v, void* o,
   return 0;
 }
 
+namespace {
+
+struct BwdTensors {
+  const bf16 *q, *k, *v, *d_o; const float *lse, *delta; bf16 *dq, *dk, *dv; const int* kv_len;
+  long ldq, ldk, ldv, ldo, lddq, lddk, lddv; int T, Hq, Hkv; float scale;
+};
+
+// dQ, dK and dV of one call once delta is final on `stream`.  groups: tile pairs times batch rows, i.e. workgroups per
+// head; work: FLOPs of ONE of the seven half-masked products.  One launch on `stream` (attn_bwd_kernel); `side_stream`
+// is not used.  attn.bwd_split (sd_hip_debug.h): the dQ kernel on the side stream (when given) beside the dK/dV kernel,
+// ordered by this call's events.
+template <bool VARLEN, class... VA>
+int launch_bwd(const BwdTensors& t, long groups, double work, void* side_stream, void* stream, VA... va) {
+  const long n_dq = groups * t.Hq, n_dkv = groups * t.Hkv, n_dkv8 = (n_dkv + 7) & ~7L;
+  if (n_dkv8 + n_dq > 0x7fffffffL) return SD_ERR_SHAPE;
+  if (!g_sd_debug.attn_bwd_split) {
+    hipStream_t st = (hipStream_t)stream;
+    SdProfScope prof(SD_K_ATTN_BWD_DKV, 7.0 * work, st);  // S, dP, dV, dK + S, dP (recomputed), dQ
+    hipLaunchKernelGGL((attn_bwd_kernel<VARLEN, VA...>), dim3((unsigned)(n_dkv8 + n_dq)), dim3(512), 0, st, t.q, t.k, t.v,
+                       t.d_o, t.lse, t.delta, t.dq, t.dk, t.dv, t.kv_len, t.ldq, t.ldk, t.ldv, t.ldo, t.lddq, t.lddk, t.lddv,
+                       t.T, t.Hq, t.Hkv, t.scale, (int)n_dkv, (int)n_dq, va...);
+    SD_CHECK_LAUNCH();
+    return 0;
+  }
+  SdStreamOrder ord;  // this call's events (per call, per device)
+  if (int e = ord.init(stream, side_stream)) return e;
+  hipStream_t st = ord.main, sq = ord.side ? ord.side : ord.main;  // sq: stream of the dQ kernel
+  if (int e = ord.side_waits_for_main(kEvAttnInputs)) return e;
+  {
+    SdProfScope prof2(SD_K_ATTN_BWD_DQ, 3.0 * work, sq);  // S, dP (recomputed), dQ
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<VARLEN, VA...>), dim3((unsigned)n_dq), dim3(512), 0, sq, t.q, t.k, t.v, t.d_o,
+                       t.lse, t.delta, t.dq, t.kv_len, t.ldq, t.ldk, t.ldv, t.ldo, t.lddq, t.T, t.Hq, t.Hkv, t.scale, va...);
+  }
+  SD_CHECK_LAUNCH();
+  {
+    SdProfScope prof(SD_K_ATTN_BWD_DKV, 4.0 * work, st);  // S, dP, dV, dK
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<VARLEN, VA...>), dim3((unsigned)n_dkv), dim3(512), 0, st, t.q, t.k, t.v, t.d_o,
+                       t.lse, t.delta, t.dk, t.dv, t.kv_len, t.ldq, t.ldk, t.ldv, t.ldo, t.lddk, t.lddv, t.T, t.Hq, t.Hkv,
+                       t.scale, va...);
+  }
+  SD_CHECK_LAUNCH();
+  return ord.main_waits_for_side(kEvAttnDq);
+}
+
+}  // namespace
+
 extern "C" int sd_attn_bwd2(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
                             float* delta, void* dq, void* dk, void* dv, const int32_t* kv_len, int64_t ldq, int64_t ldk,
                             int64_t ldv, int64_t ldo, int64_t lddq, int64_t lddk, int64_t lddv, int B, int T, int Hq,
@@ -1106,32 +1200,15 @@ extern "C" int sd_attn_bwd2(const void* q, const void* k, const void* v, const v
   if (head_dim != D) return SD_ERR_UNSUPPORTED;
   if (int e = check_common(B, T, Hq, Hkv, ldq, ldk, ldv, ldo)) return e;
   if ((lddq | lddk | lddv) & 7) return SD_ERR_ALIGN;
-  SdStreamOrder ord;  // this call's events (per call, per device)
-  if (int e = ord.init(stream, side_stream)) return e;
-  hipStream_t st = ord.main, s2 = ord.side;
   const long total = (long)B * T * Hq;
   if (o) {  // o == NULL: `delta` already holds rowsum(dO * O) (sd_gemm_odx_delta)
-    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, st, (const bf16*)d_o,
-                       (const bf16*)o, delta, ldo, T, Hq, total);
+    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16*)d_o, (const bf16*)o, delta, ldo, T, Hq, total);
     SD_CHECK_LAUNCH();
   }
-  hipStream_t sq = s2 ? s2 : st;  // stream of the dQ kernel
-  if (int e = ord.side_waits_for_main(kEvAttnInputs)) return e;
-  {
-    SdProfScope prof2(SD_K_ATTN_BWD_DQ, 3.0 * B * Hq * (double)T * T * D, sq);  // S, dP (recomputed), dQ
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, dim3((((T + 63) / 64 + 1) / 2) * Hq * B), dim3(512), 0, sq, (const bf16*)q, (const bf16*)k,
-                       (const bf16*)v, (const bf16*)d_o, lse, (const float*)delta, (bf16*)dq, kv_len, ldq, ldk, ldv, ldo,
-                       lddq, T, Hq, Hkv, scale);
-  }
-  SD_CHECK_LAUNCH();
-  {
-    SdProfScope prof(SD_K_ATTN_BWD_DKV, 4.0 * B * Hq * (double)T * T * D, st);  // S, dP, dV, dK
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, dim3((((T + 63) / 64 + 1) / 2) * Hkv * B), dim3(512), 0, st, (const bf16*)q,
-                       (const bf16*)k, (const bf16*)v, (const bf16*)d_o, lse, (const float*)delta, (bf16*)dk, (bf16*)dv,
-                       kv_len, ldq, ldk, ldv, ldo, lddk, lddv, T, Hq, Hkv, scale);
-  }
-  SD_CHECK_LAUNCH();
-  return ord.main_waits_for_side(kEvAttnDq);
+  const BwdTensors t{(const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)d_o, lse, delta, (bf16*)dq, (bf16*)dk,
+                     (bf16*)dv, kv_len, ldq, ldk, ldv, ldo, lddq, lddk, lddv, T, Hq, Hkv, scale};
+  return launch_bwd<false>(t, (long)(((T + 63) / 64 + 1) / 2) * B, (double)B * Hq * (double)T * T * D, side_stream, stream);
 }
 
 extern "C" int sd_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
@@ -1191,33 +1268,16 @@ extern "C" int sd_attn_bwd_varlen(const void* q, const void* k, const void* v, c
   unsigned pairs;
   if (int e = varlen_check(vl, M, Hq, Hkv, ldq, ldk, ldv, ldo, &va, &pairs)) return e;
   if ((lddq | lddk | lddv) & 7) return SD_ERR_ALIGN;
-  SdStreamOrder ord;  // this call's events (per call, per device)
-  if (int e = ord.init(stream, side_stream)) return e;
-  hipStream_t st = ord.main, s2 = ord.side;
   const long total = (long)M * Hq;
   if (o) {  // per token: one row of M tokens is exactly the [Hq, M] layout of the packed LSE / delta
-    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, st, (const bf16*)d_o,
-                       (const bf16*)o, delta, ldo, M, Hq, total);
+    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((total + 15) / 16)), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16*)d_o, (const bf16*)o, delta, ldo, M, Hq, total);
     SD_CHECK_LAUNCH();
   }
-  hipStream_t sq = s2 ? s2 : st;
-  if (int e = ord.side_waits_for_main(kEvAttnInputs)) return e;
   const double ml = vl->max_seqlen > 0 ? (double)(vl->max_seqlen < M ? vl->max_seqlen : M) : (double)M;
-  {
-    SdProfScope prof2(SD_K_ATTN_BWD_DQ, 3.0 * Hq * (double)M * ml * D, sq);
-    attn_bwd_dq_kernel<true, VarlenArgs><<<dim3(pairs * Hq), dim3(512), 0, sq>>>(
-        (const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)d_o, lse, (const float*)delta, (bf16*)dq, nullptr,
-        ldq, ldk, ldv, ldo, lddq, M, Hq, Hkv, scale, va);
-  }
-  SD_CHECK_LAUNCH();
-  {
-    SdProfScope prof(SD_K_ATTN_BWD_DKV, 4.0 * Hq * (double)M * ml * D, st);
-    attn_bwd_dkv_kernel<true, VarlenArgs><<<dim3(pairs * Hkv), dim3(512), 0, st>>>(
-        (const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)d_o, lse, (const float*)delta, (bf16*)dk, (bf16*)dv,
-        nullptr, ldq, ldk, ldv, ldo, lddk, lddv, M, Hq, Hkv, scale, va);
-  }
-  SD_CHECK_LAUNCH();
-  return ord.main_waits_for_side(kEvAttnDq);
+  const BwdTensors t{(const bf16*)q, (const bf16*)k, (const bf16*)v, (const bf16*)d_o, lse, delta, (bf16*)dq, (bf16*)dk,
+                     (bf16*)dv, nullptr, ldq, ldk, ldv, ldo, lddq, lddk, lddv, M, Hq, Hkv, scale};
+  return launch_bwd<true>(t, (long)pairs, Hq * (double)M * ml * D, side_stream, stream, va);
 }
 
 // ------------------------------------------------------------------------------------------ extend

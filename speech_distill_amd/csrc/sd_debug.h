@@ -30,6 +30,7 @@ struct SdDebug {
   int topk_nt = 0;
   int qk_bwd_blocks = 512;
   int attn_variant = 0;  // bit0: forward without the in-wave pipeline at any T; bit1: with it at any T
+  int attn_bwd_split = 0;  // sd_attn_bwd2: dQ and dK/dV as two launches on two streams (the earlier schedule)
 };
 extern SdDebug g_sd_debug;
 

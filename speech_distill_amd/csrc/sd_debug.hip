@@ -35,6 +35,7 @@ const Key kKeys[] = {
     {"topk.nt", &SdDebug::topk_nt},
     {"qk_bwd.blocks", &SdDebug::qk_bwd_blocks},
     {"attn.variant", &SdDebug::attn_variant},
+    {"attn.bwd_split", &SdDebug::attn_bwd_split},
 };
 }  // namespace
 

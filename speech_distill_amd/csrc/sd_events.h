@@ -31,7 +31,7 @@ enum SdBwdEvent {
   kEvLayerDone = 10,    // + the layer's parity (10, 11): side records behind the layer's grouped dW (and batched gain
                         // reduce); main waits in the next layer, before it overwrites their inputs and before the callback
 };
-// sd_attn_bwd2 / sd_attn_bwd_varlen (a set of their own)
+// sd_attn_bwd2 / sd_attn_bwd_varlen under attn.bwd_split (a set of their own; the default single launch needs none)
 enum SdAttnEvent {
   kEvAttnInputs = 0,  // main records when delta is final; side waits before the dQ kernel
   kEvAttnDq = 1,      // side records behind the dQ kernel; main waits before the entry returns
