@@ -869,6 +869,60 @@ int sd_qwen3_decode_step_wide(const sd_qwen3_dims* d, const sd_qwen3_params* p, 
                               int max_len, const void* cos_tab, const void* sin_tab, const sd_kv_ref* kv, void* acts,
                               int64_t acts_bytes, void* logits, int B, void* stream);
 
+/* ---- the cache step of a decode layer as ONE launch (llm_engine.py:37-76, the decode loop over a KV cache, :91 for the
+ * paged form; per layer HF:252-257 q/k-norm + RoPE, the cache update, HF:185-207 with one query row).
+ * sd_cache_step does what sd_qknorm_rope_append{,_paged,_paged_mx} followed by sd_attn_decode{,_paged,_paged_mx} with len =
+ * pos and len_add = 1 do, BIT FOR BIT: o [B,Hq*128] bf16, lse fp32 [B,Hq] (nullable) and every byte of the planes are what
+ * that pair leaves, for every pos (values outside [0, cap) store nothing), every max_len (a bound below pos + 1 still
+ * stores the row) and every page layout.  q is formed in registers and never written.
+ * sd_kv_planes: ONE layer's planes of any kind.  kind 0: k, v = the contiguous planes [B][cap][Hkv*128] bf16; kind 1: the
+ *   pool planes [n_pages][256][Hkv*128] bf16 and the table int32 [B][max_pages] (device); kind 2: the e4m3 data planes and
+ *   the E8M0 scale planes of MXFP8 pages.  Fields another kind uses are ignored.
+ * Grid (ceil(min(cap, max_len) / 256), Hkv, B): a workgroup owns a partition of 256 keys of one kv head of one sequence.
+ *   The workgroup whose partition holds slot pos[b] appends the row and is the only one that reads it, after its own
+ *   stores have landed.  The partitions that hold a visible key publish their records and draw a ticket; the workgroup
+ *   that draws the last one merges them in increasing partition order (one partition: no ticket, no fence).  No workgroup
+ *   ever waits for another.  One rule the pair does not need: a slot that one row appends in a step must not be a visible
+ *   key of ANOTHER row in the same step (rows that share a page share only positions below both their pos).
+ * workspace: sd_cache_step_workspace_bytes(B, Hq, Hkv, cap) bytes (cap, or max_pages * 256), the partition records; it may
+ *   hold anything.  tickets: int32 [B][Hkv], which MUST be zero at the launch (the caller zeroes them on the stream, once
+ *   for all the layers of a step, each layer taking its own [B][Hkv] slice) and are zero again when it ends.
+ * Checks, all before the launch: head_dim != 128 or Hq / Hkv outside {1, 2, 4} SD_ERR_UNSUPPORTED; a NULL pointer (lse
+ *   apart), an unknown kind, B / cap / max_len / a page count <= 0, Hq % Hkv != 0 SD_ERR_SHAPE; a short or NULL workspace
+ *   SD_ERR_WORKSPACE; qkv / gains / cos / sin / planes not 16-byte aligned (8-bit data planes 8, scale planes 4), workspace
+ *   or tickets not 4-byte aligned SD_ERR_ALIGN. */
+typedef struct {
+  int kind;               /* 0: contiguous bf16, 1: bf16 pages, 2: MXFP8 pages */
+  void *k, *v;            /* the layer's K and V planes (kind 2: the data planes) */
+  void *k_scale, *v_scale; /* kind 2: the scale planes */
+  int cap;                /* kind 0: positions per row */
+  const int32_t* table;   /* kinds 1, 2 */
+  int max_pages, n_pages; /* kinds 1, 2 */
+} sd_kv_planes;
+int64_t sd_cache_step_workspace_bytes(int B, int Hq, int Hkv, int cap);
+int sd_cache_step(const void* qkv, const void* q_gain, const void* k_gain, const void* cos_tab, const void* sin_tab,
+                  const int32_t* pos, const sd_kv_planes* kv, void* o, float* lse, void* workspace, int64_t workspace_bytes,
+                  int32_t* tickets, int B, int max_len, int Hq, int Hkv, int head_dim, float eps, float scale,
+                  void* stream);
+/* The decode steps on the one-launch cache step, over a cache of any kind (sd_kv_ref).  The launches of
+ * sd_qwen3_decode_step_flags (kernels = 0: the tile sequence, 1: SD_DECODE_SKINNY) or sd_qwen3_decode_step_wide (kernels =
+ * 2), and of sd_qwen3_mx_decode_step (flags = 0 or SD_DECODE_SKINNY), with sd_cache_step standing where the append and the
+ * decode attention do: two launches fewer per layer (5 L + 2 kernels on the GEMV sequences, 7 L + 2 on the bf16 tile
+ * sequence, 9 L + 2 on the MXFP8 tile one), plus ONE memset of the step's tickets ahead of layer 0.  Logits and cache are
+ * bit-identical to those entries.  A step whose GEMVs would refuse their shape runs the tile sequence, still on
+ * sd_cache_step.  acts of the *_fused_acts_bytes queries (the twins' set + the tickets int32 [L][B][Hkv]).  Another
+ * `kernels` / flag value is SD_ERR_SHAPE; every other check and code as sd_qwen3_decode_step_wide / sd_qwen3_mx_decode_step;
+ * all before the first launch. */
+int64_t sd_qwen3_decode_step_fused_acts_bytes(const sd_qwen3_dims* d, int B, int cap);
+int sd_qwen3_decode_step_fused(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* pos,
+                               int max_len, const void* cos_tab, const void* sin_tab, const sd_kv_ref* kv, void* acts,
+                               int64_t acts_bytes, void* logits, int B, int kernels, void* stream);
+int64_t sd_qwen3_mx_decode_step_fused_acts_bytes(const sd_qwen3_dims* d, int B, int cap);
+int sd_qwen3_mx_decode_step_fused(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids,
+                                  const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab,
+                                  const sd_kv_ref* kv, void* acts, int64_t acts_bytes, void* logits, int B, int flags,
+                                  void* stream);
+
 /* ---- stream placement.  HIP multiplexes streams onto a few hardware queues (4 by default); streams that share a
  * queue never overlap.  Measures, with a `spin_us`-long busy-wait kernel on stream_a and an empty one on stream_b,
  * whether work on b runs while a is busy: *overlap = 1/0.  Synchronises both streams (a calibration call, made once

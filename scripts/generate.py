@@ -54,6 +54,9 @@ def parse_args(argv=None):
     p.add_argument("--decode_kernels", choices=("tile", "skinny", "wide"), default="tile",
                    help="skinny: weight-streaming GEMV kernels for the decode step (batch_size <= 16); wide: the MFMA "
                         "weight-streaming kernels (batch_size <= 64, bf16 weights)")
+    p.add_argument("--decode_attention", choices=("split", "fused"), default="split",
+                   help="fused: every decode step runs each layer's q/k-norm + RoPE, cache append, split-KV attention and "
+                        "merge as one launch instead of three; the tokens are the same")
     p.add_argument("--kv_pool_pages", type=int, default=0,
                    help="0: every batch reserves a contiguous KV cache for its worst case.  N > 0: every batch's session "
                         "draws pages of 256 positions from ONE pool of N pages, turn by turn (the paged cache of the "
@@ -129,7 +132,8 @@ def serve_continuous(model, pool, args, pad, prompts, out):
         return 0, 0.0
     dev = model.flat.device
     eng = model.generation_engine(pool, max_batch=args.batch_size, decode_kernels=args.decode_kernels,
-                                  weight_dtype=args.weight_dtype, sync_every=args.sync_every)
+                                  weight_dtype=args.weight_dtype, sync_every=args.sync_every,
+                                  decode_attention=args.decode_attention)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     rids = [eng.submit(torch.tensor(ids, dtype=torch.int64, device=dev), max_new_tokens=args.max_tokens,
@@ -177,7 +181,7 @@ def main(argv=None):
             if need > cache_capacity(model):
                 raise ValueError(f"a dialogue of {need} positions exceeds the KV-cache capacity {cache_capacity(model)}")
             sess = model.start_session(len(chunk), (need + 255) // 256 * 256, decode_kernels=args.decode_kernels, pool=pool,
-                                       weight_dtype=args.weight_dtype)
+                                       weight_dtype=args.weight_dtype, decode_attention=args.decode_attention)
             for turn in range(n_turns):
                 ids, mask = right_pad([d[turn] for d in chunk], pad)
                 torch.cuda.synchronize()

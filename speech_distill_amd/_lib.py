@@ -89,6 +89,11 @@ class KvRef(C.Structure):  # include/sd_hip.h sd_kv_ref (the cache of any kind, 
                 ("pages", C.POINTER(KvPages))]
 
 
+class KvPlanes(C.Structure):  # include/sd_hip.h sd_kv_planes (one layer's planes of any kind, for sd_cache_step)
+    _fields_ = [("kind", C.c_int32), ("k", C.c_void_p), ("v", C.c_void_p), ("k_scale", C.c_void_p), ("v_scale", C.c_void_p),
+                ("cap", C.c_int32), ("table", C.c_void_p), ("max_pages", C.c_int32), ("n_pages", C.c_int32)]
+
+
 class Params(C.Structure):
     _fields_ = [("embed", C.c_void_p), ("lm_head", C.c_void_p), ("final_norm", C.c_void_p),
                 ("layers_host", C.POINTER(Layer))]
@@ -272,6 +277,16 @@ PROTOTYPES = {
     "sd_qwen3_decode_step_wide_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
     "sd_qwen3_decode_step_wide": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _i, _vp, _vp, C.POINTER(KvRef), _vp,
                                        _i64, _vp, _i, _vp]),
+    # the one-launch cache step (append + decode attention + merge) and the decode steps on it
+    "sd_cache_step_workspace_bytes": (_i64, [_i, _i, _i, _i]),
+    "sd_cache_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(KvPlanes), _vp, _vp, _vp, _i64, _vp, _i, _i, _i, _i, _i,
+                           _f, _f, _vp]),
+    "sd_qwen3_decode_step_fused_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
+    "sd_qwen3_decode_step_fused": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _i, _vp, _vp, C.POINTER(KvRef), _vp,
+                                        _i64, _vp, _i, _i, _vp]),
+    "sd_qwen3_mx_decode_step_fused_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
+    "sd_qwen3_mx_decode_step_fused": (_i, [C.POINTER(Dims), C.POINTER(ParamsMx), _vp, _vp, _i, _vp, _vp, C.POINTER(KvRef),
+                                           _vp, _i64, _vp, _i, _i, _vp]),
 }
 
 

@@ -422,8 +422,9 @@ int bwd_drain(Bwd& c) {
 
 struct DecodeActs {
   char *x, *x_mid, *xn, *qkv, *q, *ao, *gu, *act, *ws;
+  int32_t* tickets = nullptr;  // fused: the tickets of the one-launch cache step, int32 [L][B][Hkv], at the tail
   int64_t ws_bytes, total;
-  DecodeActs(const sd_qwen3_dims* d, int B, int cap, char* p) {
+  DecodeActs(const sd_qwen3_dims* d, int B, int cap, char* p, bool fused = false) {
     const Sizes s(d, B, 1);
     int64_t off = 0;  // (p == nullptr: a size query, no address is formed)
     auto take = [&](int64_t n) { char* q = p ? p + off : nullptr; off += n; return q; };
@@ -431,6 +432,7 @@ struct DecodeActs {
     gu = take(s.gu); act = take(s.act);
     ws_bytes = sd_attn_decode_workspace_bytes(B, s.Hq, cap);
     ws = take(al(ws_bytes));
+    if (fused) tickets = (int32_t*)take(KvSink::ticket_bytes(s, B));
     total = off;
   }
 };
@@ -460,6 +462,7 @@ int decode_step_impl(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int
                      void* logits, int B, int flags, void* stream) {
   const bool wide = (flags & kStepWide) && gemv_step_ok(sd_gemv_wide_check, p, s, a, logits, B);
   const bool skinny = (flags & SD_DECODE_SKINNY) && gemv_step_ok(sd_gemv_check, p, s, a, logits, B);
+  RUN(kv.begin_step(s, B, stream));
   RUN(sd_embedding_fwd(ids, p->embed, a.x, B, s.h, s.V, stream));
   if (skinny || wide) {
     const auto gemv = wide ? sd_gemv_wide_bf16 : sd_gemv_bf16;
@@ -830,6 +833,33 @@ extern "C" int sd_qwen3_decode_step_wide(const sd_qwen3_dims* d, const sd_qwen3_
   const DecodeActs a(d, B, kv.cap, (char*)acts);
   if (acts_bytes < a.total) return SD_ERR_WORKSPACE;
   return decode_step_impl(d, p, ids, pos, max_len, cos_tab, sin_tab, kv, s, a, logits, B, kStepWide, stream);
+}
+
+// sd_qwen3_decode_step_fused: any of the three sequences over a cache of any kind, on the one-launch cache step
+extern "C" int64_t sd_qwen3_decode_step_fused_acts_bytes(const sd_qwen3_dims* d, int B, int cap) {
+  if (!d || d->head_dim != 128) return SD_ERR_UNSUPPORTED;
+  if (B <= 0 || cap <= 0) return SD_ERR_SHAPE;
+  return DecodeActs(d, B, cap, nullptr, true).total;
+}
+
+extern "C" int sd_qwen3_decode_step_fused(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
+                                          const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab,
+                                          const sd_kv_ref* kvr, void* acts, int64_t acts_bytes, void* logits, int B,
+                                          int kernels, void* stream) {
+  if (kernels < 0 || kernels > 2) return SD_ERR_SHAPE;
+  if (!d || !p || !kvr) return SD_ERR_SHAPE;
+  if (d->head_dim != 128) return SD_ERR_UNSUPPORTED;
+  if (B <= 0 || max_len <= 0 || !ids || !pos || !logits || !acts || !cos_tab || !sin_tab) return SD_ERR_SHAPE;
+  RUN(gqa_check(d));
+  KvSink kv = {};
+  RUN(ref_sink(d, kvr, B, &kv));
+  const Sizes s(d, B, 1);
+  const DecodeActs a(d, B, kv.cap, (char*)acts, true);
+  if (acts_bytes < a.total) return SD_ERR_WORKSPACE;
+  RUN(fused_align_check(acts, kv));
+  kv.tickets = a.tickets;
+  const int flags = kernels == 2 ? kStepWide : kernels == 1 ? SD_DECODE_SKINNY : 0;
+  return decode_step_impl(d, p, ids, pos, max_len, cos_tab, sin_tab, kv, s, a, logits, B, flags, stream);
 }
 
 extern "C" int sd_qwen3_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,

@@ -481,8 +481,9 @@ int block_forward_mx(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const 
 // workspace
 struct MxDecodeActs : SdShape {
   char *x, *x_mid, *xn, *qkv, *q, *ao, *act, *xq, *xs, *rstd, *aoq, *aos, *actq, *acts, *ws;
+  int32_t* tickets = nullptr;  // fused: the tickets of the one-launch cache step, int32 [L][B][Hkv], at the tail
   int64_t ws_bytes, total;
-  MxDecodeActs(const sd_qwen3_dims* d, int B, int cap, char* p) : SdShape(d, B, 1) {
+  MxDecodeActs(const sd_qwen3_dims* d, int B, int cap, char* p, bool fused = false) : SdShape(d, B, 1) {
     int64_t off = 0;  // (p == nullptr: a size query, no address is formed)
     auto take = [&](int64_t n) { char* q = p ? p + off : nullptr; off += al(n); return q; };
     const int64_t xb = (int64_t)M * h * 2;
@@ -494,6 +495,7 @@ struct MxDecodeActs : SdShape {
     actq = take((int64_t)M * I); acts = take((int64_t)M * I / 32);
     ws_bytes = sd_attn_decode_workspace_bytes(B, Hq, cap);
     ws = take(ws_bytes);
+    if (fused) tickets = (int32_t*)take(KvSink::ticket_bytes(*this, B));
     total = off;
   }
 };
@@ -559,22 +561,26 @@ extern "C" int64_t sd_qwen3_mx_decode_step_acts_bytes(const sd_qwen3_dims* d, in
   return MxDecodeActs(d, B, cap, nullptr).total;
 }
 
-extern "C" int sd_qwen3_mx_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids,
-                                       const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab,
-                                       const sd_kv_ref* kvr, void* acts, int64_t acts_bytes, void* logits, int B, int flags,
-                                       void* stream) {
+// the checks and launches of sd_qwen3_mx_decode_step; fused: on the one-launch cache step (sd_qwen3_mx_decode_step_fused)
+static int mx_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids, const int32_t* pos,
+                          int max_len, const void* cos_tab, const void* sin_tab, const sd_kv_ref* kvr, void* acts,
+                          int64_t acts_bytes, void* logits, int B, int flags, void* stream, bool fused) {
   if (flags & ~SD_DECODE_SKINNY) return SD_ERR_SHAPE;
   if (!d || !p || !kvr) return SD_ERR_SHAPE;
   if (!mx_supported(d)) return SD_ERR_UNSUPPORTED;
   if (B <= 0 || max_len <= 0 || !ids || !pos || !logits || !acts) return SD_ERR_SHAPE;
+  if (fused && (!cos_tab || !sin_tab)) return SD_ERR_SHAPE;
   RUN(gqa_check(d));
   KvSink kv = {};
   RUN(ref_sink(d, kvr, B, &kv));
-  const MxDecodeActs a(d, B, kv.cap, (char*)acts);
+  const MxDecodeActs a(d, B, kv.cap, (char*)acts, fused);
   if (acts_bytes < a.total) return SD_ERR_WORKSPACE;
+  if (fused) RUN(fused_align_check(acts, kv));
+  kv.tickets = a.tickets;
   const int h = a.h;
   const float eps = d->eps;
   const bool skinny = (flags & SD_DECODE_SKINNY) && skinny_mx_ok(p, a, logits, B);
+  RUN(kv.begin_step(a, B, stream));
   RUN(sd_embedding_fwd(ids, p->embed, a.x, B, h, a.V, stream));
   if (skinny) {
     for (int l = 0; l < a.L; ++l) {
@@ -602,4 +608,24 @@ extern "C" int sd_qwen3_mx_decode_step(const sd_qwen3_dims* d, const sd_qwen3_pa
   }
   RUN(sd_rmsnorm_fwd(a.x, p->final_norm, a.xn, nullptr, B, h, eps, stream));
   return sd_gemm_bf16(a.xn, p->lm_head, logits, nullptr, B, a.V, h, h, h, a.V, 0, 0, 0, stream);
+}
+
+extern "C" int sd_qwen3_mx_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids,
+                                       const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab,
+                                       const sd_kv_ref* kvr, void* acts, int64_t acts_bytes, void* logits, int B, int flags,
+                                       void* stream) {
+  return mx_decode_step(d, p, ids, pos, max_len, cos_tab, sin_tab, kvr, acts, acts_bytes, logits, B, flags, stream, false);
+}
+
+extern "C" int64_t sd_qwen3_mx_decode_step_fused_acts_bytes(const sd_qwen3_dims* d, int B, int cap) {
+  if (!d || !mx_supported(d)) return SD_ERR_UNSUPPORTED;
+  if (B <= 0 || cap <= 0) return SD_ERR_SHAPE;
+  return MxDecodeActs(d, B, cap, nullptr, true).total;
+}
+
+extern "C" int sd_qwen3_mx_decode_step_fused(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids,
+                                             const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab,
+                                             const sd_kv_ref* kvr, void* acts, int64_t acts_bytes, void* logits, int B,
+                                             int flags, void* stream) {
+  return mx_decode_step(d, p, ids, pos, max_len, cos_tab, sin_tab, kvr, acts, acts_bytes, logits, B, flags, stream, true);
 }

@@ -1,6 +1,7 @@
 // What the decoder runners of sd_model.hip (bf16) and sd_mx.hip (MXFP8 teacher) share.  Internal: not installed, not ABI.
 #pragma once
 #include <stdint.h>
+#include <hip/hip_runtime.h>
 #include "../../include/sd_hip.h"
 
 #define RUN(call) do { int e__ = (call); if (e__) return e__; } while (0)
@@ -71,6 +72,9 @@ struct KvSink {
   const int32_t* table = nullptr;
   int n_pages = 0, max_pages = 0;
   bool mx = false;
+  // The decode step on the one-launch cache step (sd_cache_step): int32 [L][B][Hkv] at the tail of the step's acts,
+  // zeroed by begin_step ahead of layer 0; layer l draws from its own [B][Hkv] slice.  nullptr: the two-entry step.
+  int32_t* tickets = nullptr;
   // 8-bit pages: the data (u8 [n_pages][256][Hkv*128]) or scale (u8 [n_pages][256][Hkv*4]) plane of K (0) or V (1)
   char* mx_plane(const SdShape& s, int l, int which, bool scale) const {
     const int64_t data = (int64_t)n_pages * SD_KV_PAGE * s.KD;
@@ -112,6 +116,16 @@ struct KvSink {
   int step(const SdShape& s, int l, const void* q_gain, const void* k_gain, const void* qkv, void* q, void* ao,
            const void* cos_tab, const void* sin_tab, const int32_t* pos, void* ws, int64_t ws_bytes, int B, int max_len,
            float eps, void* stream) const {
+    if (tickets) {
+      sd_kv_planes pl = {};
+      pl.kind = mx ? 2 : table ? 1 : 0;
+      pl.k = mx ? mx_plane(s, l, 0, false) : plane(s, B, l, 0);
+      pl.v = mx ? mx_plane(s, l, 1, false) : plane(s, B, l, 1);
+      if (mx) { pl.k_scale = mx_plane(s, l, 0, true); pl.v_scale = mx_plane(s, l, 1, true); }
+      pl.cap = cap; pl.table = table; pl.max_pages = max_pages; pl.n_pages = n_pages;
+      return sd_cache_step(qkv, q_gain, k_gain, cos_tab, sin_tab, pos, &pl, ao, nullptr, ws, ws_bytes,
+                           tickets + (int64_t)l * B * s.Hkv, B, max_len, s.Hq, s.Hkv, 128, eps, kSdAttnScale, stream);
+    }
     if (mx) {
       char *kd = mx_plane(s, l, 0, false), *ks = mx_plane(s, l, 0, true), *vd = mx_plane(s, l, 1, false),
            *vs = mx_plane(s, l, 1, true);
@@ -130,6 +144,16 @@ struct KvSink {
     RUN(sd_qknorm_rope_append(qkv, q_gain, k_gain, cos_tab, sin_tab, pos, q, kp, vp, B, cap, s.Hq, s.Hkv, eps, stream));
     return sd_attn_decode(q, kp, vp, ao, nullptr, pos, 1, ws, ws_bytes, B, cap, max_len, s.Hq, s.Hkv, 128, kSdAttnScale,
                           stream);
+  }
+  // bytes of the tickets of a decode step on sd_cache_step
+  static int64_t ticket_bytes(const SdShape& s, int B) { return al((int64_t)s.L * B * s.Hkv * 4); }
+  // ahead of layer 0 of a decode step: the ONE memset of the step's tickets, on the launch stream.  A launch that found
+  // them poisoned (an aborted step, fresh memory) must not survive into this step, so the reducers' own reset is not
+  // relied on.  Nothing without tickets.
+  int begin_step(const SdShape& s, int B, void* stream) const {
+    if (!tickets) return 0;
+    if (hipMemsetAsync(tickets, 0, (size_t)s.L * B * s.Hkv * 4, (hipStream_t)stream) != hipSuccess) return SD_ERR_WORKSPACE;
+    return 0;
   }
 };
 
@@ -159,6 +183,12 @@ static inline int ref_sink(const sd_qwen3_dims* d, const sd_kv_ref* kv, int B, K
   if (kv->cache_bytes < sd_kvcache_bytes(d, B, kv->cap)) return SD_ERR_WORKSPACE;
   *sink = KvSink{(char*)kv->cache, kv->cap};
   return 0;
+}
+
+// sd_cache_step's alignment rule held against a step's buffers before the first launch: every buffer of the acts lies a
+// multiple of 256 bytes behind `acts`, every plane of a layer a multiple of 16 bytes (8-bit pages: 4) behind the cache
+static inline int fused_align_check(const void* acts, const KvSink& kv) {
+  return (((uintptr_t)acts | (uintptr_t)kv.cache) & 15) ? SD_ERR_ALIGN : 0;
 }
 
 // every check a batch descriptor must pass before anything is launched

@@ -225,11 +225,13 @@ class GenerationEngine(EngineLoop):
     position 0 that map the parking page, so every table entry a kernel reads lies in the pool.  ``result(id)`` (a host
     read of one length) returns the new tokens up to and including the first EOS."""
 
-    def __init__(self, model, pool, max_batch=8, decode_kernels="skinny", weight_dtype="bf16", sync_every=16, capacity=None):
+    def __init__(self, model, pool, max_batch=8, decode_kernels="skinny", weight_dtype="bf16", sync_every=16, capacity=None,
+                 decode_attention="split"):
         import torch
         from ._lib import load_lib
-        from .generation import Decoder, _check_decode_kernels, cache_capacity
+        from .generation import Decoder, _check_decode_attention, _check_decode_kernels, cache_capacity
         from .ops import sample_params, sample_params_rows
+        _check_decode_attention(decode_attention)
         _check_decode_kernels(decode_kernels, weight_dtype)
         if pool is None:
             raise ValueError("the engine serves its rows from a page pool: model.kv_page_pool(n_pages)")
@@ -240,7 +242,9 @@ class GenerationEngine(EngineLoop):
             raise ValueError("the engine needs a pool of at least two pages (one is its parking page)")
         self.model, self.pool, self.B = model, pool, int(max_batch)
         self.decode_kernels, self.weight_dtype, self.sync_every = decode_kernels, weight_dtype, int(sync_every)
-        self.decoder = dec = Decoder(model, self.B, cap, decode_kernels, pool=pool, weight_dtype=weight_dtype)
+        self.decode_attention = decode_attention   # "fused": each layer's cache step is one launch, same tokens (Decoder)
+        self.decoder = dec = Decoder(model, self.B, cap, decode_kernels, pool=pool, weight_dtype=weight_dtype,
+                                     decode_attention=decode_attention)
         super().__init__(Scheduler(dec.pages, min(dec.cap, cache_capacity(model)), sync_every))
         dev, B, V = model.flat.device, self.B, model.dims.vocab_size
         self.seq = torch.zeros(B, dec.cap, dtype=torch.int64, device=dev)

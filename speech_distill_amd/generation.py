@@ -32,6 +32,7 @@ REFERENCE_SAMPLING = dict(do_sample=True, temperature=0.6, top_k=100, top_p=0.9,
                           win_size=25, tau_r=0.2)  # soulxpodcast/config.py:107-118
 DECODE_KERNELS = ("tile", "skinny", "wide")
 WEIGHT_DTYPES = ("bf16", "mxfp8")
+DECODE_ATTENTION = ("split", "fused")
 DEFAULT_CACHE_CAPACITY = 32768  # positions; Qwen3's max_position_embeddings when the config does not say
 
 
@@ -48,6 +49,11 @@ def _check_decode_kernels(decode_kernels, weight_dtype="bf16"):
     if decode_kernels == "wide" and weight_dtype == "mxfp8":
         raise ValueError('decode_kernels="wide" streams bf16 weights only: there is no 64-row MXFP8 GEMV (use "skinny" '
                          'or "tile" with weight_dtype="mxfp8")')
+
+
+def _check_decode_attention(decode_attention):
+    if decode_attention not in DECODE_ATTENTION:
+        raise ValueError(f"decode_attention must be one of {DECODE_ATTENTION}, got {decode_attention!r}")
 
 
 def _check_weight_dtype(model, weight_dtype):
@@ -97,13 +103,21 @@ class Decoder:
     ``weight_dtype="mxfp8"`` (independent of the model's inference precision and of the cache kind): the three calls run
     the sd_qwen3_mx_* entries on ``model._mx_params()`` -- the four projections of every layer in MXFP8, fetched on every
     call so that ``.to()``, ``load_state_dict`` and the other invalidations are honoured; "skinny" then streams the 8-bit
-    weights through sd_gemv_mxfp8.  Embedding, attention, the norms of q / k, the final norm and the lm_head stay bf16."""
+    weights through sd_gemv_mxfp8.  Embedding, attention, the norms of q / k, the final norm and the lm_head stay bf16.
 
-    def __init__(self, model, B, cap, decode_kernels="tile", pool=None, weight_dtype="bf16"):
+    ``decode_attention``: "split" (default) runs each layer's cache step as the append launch and the two decode-attention
+    launches; "fused" runs it as ONE launch (sd_cache_step, through sd_qwen3_decode_step_fused /
+    sd_qwen3_mx_decode_step_fused: two launches fewer per layer, one memset per step).  Logits, tokens and every byte of the
+    cache are those of "split", for every cache kind, ``decode_kernels`` and ``weight_dtype``; ``prefill`` and ``extend`` do
+    not depend on it.  Another value is a ValueError before anything is allocated."""
+
+    def __init__(self, model, B, cap, decode_kernels="tile", pool=None, weight_dtype="bf16", decode_attention="split"):
+        _check_decode_attention(decode_attention)
         _check_decode_kernels(decode_kernels, weight_dtype)
         _check_weight_dtype(model, weight_dtype)
         self.flags = 1 if decode_kernels == "skinny" else 0   # include/sd_hip.h SD_DECODE_SKINNY
         self.wide = decode_kernels == "wide"
+        self.fused = decode_attention == "fused"
         self.weight_dtype = weight_dtype
         self.model, self.B, self.cap = model, int(B), int(cap)
         lib = load_lib()
@@ -129,12 +143,16 @@ class Decoder:
             nb = lib.sd_kvcache_bytes(C.byref(d), self.B, self.cap)
             check(min(nb, 0), "sd_kvcache_bytes")
             self.cache = torch.empty(nb, dtype=torch.uint8, device=dev)
-        if weight_dtype == "mxfp8" or self.wide:   # include/sd_hip.h sd_kv_ref: fixed for the decoder's life
+        if weight_dtype == "mxfp8" or self.wide or self.fused:   # include/sd_hip.h sd_kv_ref: fixed for the decoder's life
             if pool is not None:
                 self._kvref = _lib.KvRef(2 if self._mx else 1, None, 0, 0, C.pointer(self._kvp))
             else:
                 self._kvref = _lib.KvRef(0, self.cache.data_ptr(), self.cache.numel(), self.cap, None)
-            name = "sd_qwen3_decode_step_wide_acts_bytes" if self.wide else "sd_qwen3_mx_decode_step_acts_bytes"
+            if self.fused:
+                name = "sd_qwen3_mx_decode_step_fused_acts_bytes" if weight_dtype == "mxfp8" else \
+                    "sd_qwen3_decode_step_fused_acts_bytes"
+            else:
+                name = "sd_qwen3_decode_step_wide_acts_bytes" if self.wide else "sd_qwen3_mx_decode_step_acts_bytes"
             nb = getattr(lib, name)(C.byref(d), self.B, self.cap)
             check(min(nb, 0), name)
         else:
@@ -315,6 +333,16 @@ class Decoder:
         _need(ids, torch.int64, "ids"), _need(pos, torch.int32, "pos")
         if ids.numel() != self.B or pos.numel() != self.B:
             raise ValueError(f"decode step wants {self.B} tokens and positions")
+        if self.fused:   # one entry per weight dtype, over the cache of any kind
+            if self.weight_dtype == "mxfp8":
+                name, params, kind = "sd_qwen3_mx_decode_step_fused", m._mx_params(), self.flags
+            else:   # kernels: 0 tile, 1 skinny, 2 wide
+                name, params, kind = "sd_qwen3_decode_step_fused", self._params(), 2 if self.wide else self.flags
+            check(getattr(lib, name)(C.byref(m._cdims), C.byref(params), ids.data_ptr(), pos.data_ptr(), int(max_len),
+                                     self.cos.data_ptr(), self.sin.data_ptr(), C.byref(self._kvref),
+                                     self.step_acts.data_ptr(), self.step_acts.numel(), self.logits.data_ptr(), self.B,
+                                     kind, _stream()), name)
+            return self.logits
         if self.weight_dtype == "mxfp8":
             check(lib.sd_qwen3_mx_decode_step(C.byref(m._cdims), C.byref(m._mx_params()), ids.data_ptr(), pos.data_ptr(),
                                               int(max_len), self.cos.data_ptr(), self.sin.data_ptr(), C.byref(self._kvref),
@@ -343,11 +371,13 @@ class Decoder:
 
 
 def _check_args(model, B, T, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p, repetition_penalty,
-                use_ras, win_size, tau_r, sync_every, decode_kernels="tile", model_capacity=True, weight_dtype="bf16"):
+                use_ras, win_size, tau_r, sync_every, decode_kernels="tile", model_capacity=True, weight_dtype="bf16",
+                decode_attention="split"):
     """``model_capacity``: also hold T + max_new_tokens against ``cache_capacity(model)`` (a session holds its own
     lengths against its own capacity instead)."""
     if weight_dtype not in WEIGHT_DTYPES:
         raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, got {weight_dtype!r}")
+    _check_decode_attention(decode_attention)
     _check_decode_kernels(decode_kernels, weight_dtype)
     if max_new_tokens < 1:
         raise ValueError(f"max_new_tokens must be at least 1, got {max_new_tokens}")
@@ -403,15 +433,22 @@ class GenerationSession:
     the pool's dtype.
 
     ``weight_dtype="mxfp8"``: every pass of every turn (prefill, extend, decode steps) runs the model's MXFP8 projections
-    (``Decoder``); ``fork`` keeps it.  Everything else above holds unchanged."""
+    (``Decoder``); ``fork`` keeps it.  Everything else above holds unchanged.
 
-    def __init__(self, model, batch_size, capacity=None, decode_kernels="tile", pool=None, weight_dtype="bf16"):
+    ``decode_attention="fused"``: the decode steps of every turn run each layer's cache step as one launch (``Decoder``),
+    with the tokens and the cache bytes of "split"; ``fork`` keeps it."""
+
+    def __init__(self, model, batch_size, capacity=None, decode_kernels="tile", pool=None, weight_dtype="bf16",
+                 decode_attention="split"):
+        _check_decode_attention(decode_attention)
         self.model, self.B = model, int(batch_size)
         self.capacity = int(capacity) if capacity is not None else cache_capacity(model)
         if self.B < 1 or self.capacity < 1:
             raise ValueError(f"a session needs batch_size >= 1 and capacity >= 1, got {batch_size}, {capacity}")
         self.pool, self.decode_kernels, self.weight_dtype = pool, decode_kernels, weight_dtype
-        self.decoder = Decoder(model, self.B, self.capacity, decode_kernels, pool=pool, weight_dtype=weight_dtype)
+        self.decode_attention = decode_attention
+        self.decoder = Decoder(model, self.B, self.capacity, decode_kernels, pool=pool, weight_dtype=weight_dtype,
+                               decode_attention=decode_attention)
         dev = model.flat.device
         self.seq = torch.zeros(self.B, self.capacity, dtype=torch.int64, device=dev)
         self.len = torch.zeros(self.B, dtype=torch.int32, device=dev)
@@ -480,9 +517,9 @@ class GenerationSession:
         new = GenerationSession.__new__(GenerationSession)
         new.model, new.B, new.capacity, new.pool, new.decode_kernels = self.model, len(rows), self.capacity, self.pool, \
             self.decode_kernels
-        new.weight_dtype = self.weight_dtype
+        new.weight_dtype, new.decode_attention = self.weight_dtype, self.decode_attention
         new.decoder = Decoder(self.model, new.B, self.capacity, self.decode_kernels, pool=self.pool,
-                              weight_dtype=self.weight_dtype)
+                              weight_dtype=self.weight_dtype, decode_attention=self.decode_attention)
         cached = self.cached.tolist()   # the one host read
         new.decoder.pages, copies = self.decoder.pages.fork(rows, cached)   # raises before anything changed
         self.pool.copy_pages(copies)
@@ -613,15 +650,16 @@ class GenerationSession:
 @torch.no_grad()
 def generate(model, input_ids, attention_mask=None, max_new_tokens=20, min_new_tokens=0, do_sample=True, temperature=1.0,
              top_k=0, top_p=1.0, repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, use_ras=False, win_size=25,
-             tau_r=0.2, seed=None, sync_every=16, decode_kernels="tile", weight_dtype="bf16"):
+             tau_r=0.2, seed=None, sync_every=16, decode_kernels="tile", weight_dtype="bf16", decode_attention="split"):
     """See ``HipQwen3ForCausalLM.generate``: a one-turn ``GenerationSession``."""
     if input_ids.dim() != 2:
         raise ValueError(f"input_ids must be [B,T], got {tuple(input_ids.shape)}")
     B, T = input_ids.shape
     _check_args(model, B, T, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p, repetition_penalty,
-                use_ras, win_size, tau_r, sync_every, decode_kernels, weight_dtype=weight_dtype)
+                use_ras, win_size, tau_r, sync_every, decode_kernels, weight_dtype=weight_dtype,
+                decode_attention=decode_attention)
     cap = (T + max_new_tokens + 255) // 256 * 256   # whole attention partitions; the output bits do not depend on it
-    sess = GenerationSession(model, B, cap, decode_kernels, weight_dtype=weight_dtype)
+    sess = GenerationSession(model, B, cap, decode_kernels, weight_dtype=weight_dtype, decode_attention=decode_attention)
     new = sess.generate(input_ids, attention_mask, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p,
                         repetition_penalty, eos_token_id, pad_token_id, use_ras, win_size, tau_r, seed, sync_every)
     return torch.cat([input_ids.to(torch.int64), new], dim=1)

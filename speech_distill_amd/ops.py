@@ -11,6 +11,7 @@ import os
 
 import torch
 
+from . import _lib
 from ._lib import check, load_lib
 
 BF16, F32 = 0, 1
@@ -1090,6 +1091,52 @@ def attn_extend_paged_mx(q, planes, table, past, new_len, T, Hq, Hkv, want_lse=T
     check(load_lib().sd_attn_extend_paged_mx(q.data_ptr(), *pl, tp, max_pages, n_pages, o.data_ptr(), _p(lse),
                                              past.data_ptr(), new_len.data_ptr(), q.stride(0), o.stride(0), B, T, Hq, Hkv,
                                              128, 128 ** -0.5, _stream()), "sd_attn_extend_paged_mx")
+    return (o, lse) if want_lse else o
+
+
+def cache_step(qkv, q_gain, k_gain, cos, sin, pos, planes, Hq, Hkv, table=None, max_len=None, eps=1e-6, want_lse=False,
+               workspace=None, tickets=None):
+    """sd_cache_step: ``qknorm_rope_append*`` followed by ``attn_decode*(len_add=1)`` as ONE launch, with their bits.
+    ``planes``: (k_plane, v_plane) [B, cap, Hkv*128] bf16 of a contiguous cache (no ``table``), (k_pool, v_pool) of bf16
+    pages or (k_data, k_scale, v_data, v_scale) of MXFP8 pages with the page ``table`` int32 [B, max_pages].  pos int32 [B]
+    (device); max_len: host upper bound of every pos + 1 (default cap).  ``tickets``: int32 [B, Hkv], zero at the call and
+    zero again after it (default: fresh zeros).  -> o [B,Hq*128] (, lse [B,Hq]).
+    One rule the pair does not have, and nothing here checks it: a slot that one row appends in this call must not be a
+    visible key of ANOTHER row in the same call (rows that share a page may share only positions below both their pos) --
+    the pair orders that store and that read by a kernel boundary, this launch does not."""
+    _need(qkv, torch.bfloat16, "qkv"), _need(pos, torch.int32, "pos")
+    lib = load_lib()
+    B = qkv.shape[0]
+    if table is None:
+        k, v = planes
+        _need(k, torch.bfloat16, "k_plane"), _need(v, torch.bfloat16, "v_plane")
+        cap = k.shape[1]
+        kv = _lib.KvPlanes(0, k.data_ptr(), v.data_ptr(), None, None, cap, None, 0, 0)
+    elif len(planes) == 2:
+        kp, vp, tp, max_pages, n_pages = _paged_args(planes[0], planes[1], table)
+        cap = max_pages * 256
+        kv = _lib.KvPlanes(1, kp, vp, None, None, 0, tp, max_pages, n_pages)
+    else:
+        (kd, ks, vd, vs), tp, max_pages, n_pages = _paged_mx_args(planes, table)
+        cap = max_pages * 256
+        kv = _lib.KvPlanes(2, kd, vd, ks, vs, 0, tp, max_pages, n_pages)
+    if cos.shape[0] < cap:
+        raise ValueError(f"rope tables hold {cos.shape[0]} positions, the cache {cap}")
+    nb = lib.sd_cache_step_workspace_bytes(B, Hq, Hkv, cap)
+    check(min(nb, 0), "sd_cache_step_workspace_bytes")
+    if workspace is None:
+        workspace = torch.empty(max(nb, 16), dtype=torch.uint8, device=qkv.device)
+    if tickets is None:
+        tickets = torch.zeros(B, Hkv, dtype=torch.int32, device=qkv.device)
+    _need(tickets, torch.int32, "tickets")
+    if tickets.numel() < B * Hkv:
+        raise ValueError(f"tickets must hold {B} x {Hkv} counters")
+    o = torch.empty(B, Hq * 128, dtype=torch.bfloat16, device=qkv.device)
+    lse = torch.empty(B, Hq, dtype=torch.float32, device=qkv.device) if want_lse else None
+    check(lib.sd_cache_step(qkv.data_ptr(), q_gain.data_ptr(), k_gain.data_ptr(), cos.data_ptr(), sin.data_ptr(),
+                            pos.data_ptr(), C.byref(kv), o.data_ptr(), _p(lse), workspace.data_ptr(), workspace.numel(),
+                            tickets.data_ptr(), B, cap if max_len is None else int(max_len), Hq, Hkv, 128, eps, 128 ** -0.5,
+                            _stream()), "sd_cache_step")
     return (o, lse) if want_lse else o
 
 

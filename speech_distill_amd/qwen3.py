@@ -840,7 +840,7 @@ class HipQwen3ForCausalLM(nn.Module):
     def generate(self, input_ids, attention_mask=None, max_new_tokens=20, min_new_tokens=0, do_sample=True,
                  temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, eos_token_id=None, pad_token_id=None,
                  use_ras=False, win_size=25, tau_r=0.2, seed=None, sync_every=16, decode_kernels="tile",
-                 weight_dtype="bf16"):
+                 weight_dtype="bf16", decode_attention="split"):
         """Decode ``max_new_tokens`` tokens per row over a KV cache (generation.py; the reference's engine:
         soulxpodcast/engine/llm_engine.py:37-76 with sampler.py:136-189).  Returns int64 [B, T + max_new_tokens]: the given
         ``input_ids`` followed by the new tokens in columns T..., ``pad_token_id`` (default: ``eos_token_id``, else 0) after
@@ -865,13 +865,19 @@ class HipQwen3ForCausalLM(nn.Module):
         model's MXFP8 weights (``set_inference_precision``'s format, whatever the precision the model is set to); with
         "skinny" the 8-bit weights are streamed through the block-scaled GEMV.  Needs a frozen model without LoRA and
         the dimensions "mxfp8" needs: ValueError otherwise, and for any other value, before any allocation.  ValueError
-        too for ``decode_kernels="wide"`` with "mxfp8": there is no 64-row MXFP8 GEMV."""
+        too for ``decode_kernels="wide"`` with "mxfp8": there is no 64-row MXFP8 GEMV.
+
+        ``decode_attention="fused"`` (default "split"): every decode step runs each layer's cache step -- q/k-norm + RoPE,
+        the append, the split-KV attention and its merge -- as one launch instead of three (sd_cache_step).  The tokens
+        are those of "split", bit for bit, with every ``decode_kernels``, ``weight_dtype`` and cache kind.  ValueError for
+        any other value, before any allocation."""
         from .generation import generate
         return generate(self, input_ids, attention_mask, max_new_tokens, min_new_tokens, do_sample, temperature, top_k,
                         top_p, repetition_penalty, eos_token_id, pad_token_id, use_ras, win_size, tau_r, seed, sync_every,
-                        decode_kernels, weight_dtype)
+                        decode_kernels, weight_dtype, decode_attention)
 
-    def start_session(self, batch_size, capacity=None, decode_kernels="tile", pool=None, weight_dtype="bf16"):
+    def start_session(self, batch_size, capacity=None, decode_kernels="tile", pool=None, weight_dtype="bf16",
+                      decode_attention="split"):
         """A ``GenerationSession`` (generation.py): multi-turn generation over ONE live KV cache of ``capacity`` positions
         per row (default: ``cache_capacity(self)``), as the reference's dialogue loop keeps one ``DynamicCache`` across
         turns (soulxpodcast/models/soulxpodcast.py:342,378-380).  ``sess.generate(ids, mask, ...)`` takes a turn and returns
@@ -890,12 +896,15 @@ class HipQwen3ForCausalLM(nn.Module):
             n = s.fork([0] * 8); out = n.generate(prompt[:, -1:].expand(8, 1), ...)
 
         ``weight_dtype="mxfp8"``: the session decodes with the model's MXFP8 projections (see ``generate``); it combines
-        with either kind of pool and with contiguous caches.
+        with either kind of pool and with contiguous caches.  ``decode_attention="fused"``: the one-launch cache step in
+        every decode step (see ``generate``); ``fork`` keeps it.
         """
         from .generation import GenerationSession
-        return GenerationSession(self, batch_size, capacity, decode_kernels, pool=pool, weight_dtype=weight_dtype)
+        return GenerationSession(self, batch_size, capacity, decode_kernels, pool=pool, weight_dtype=weight_dtype,
+                                 decode_attention=decode_attention)
 
-    def generation_engine(self, pool, max_batch=8, decode_kernels="skinny", weight_dtype="bf16", sync_every=16):
+    def generation_engine(self, pool, max_batch=8, decode_kernels="skinny", weight_dtype="bf16", sync_every=16,
+                          decode_attention="split"):
         """A ``GenerationEngine`` (engine.py): continuous batching over a ``PagePool`` -- requests of their own length,
         budget, seed and sampling parameters are served in ``max_batch`` rows, and a row that finishes is refilled with the
         next waiting request at once (the reference's engine is vLLM, soulxpodcast/engine/llm_engine.py:91,97-109).
@@ -903,9 +912,11 @@ class HipQwen3ForCausalLM(nn.Module):
         ``eng.run()``, ``eng.result(id)``, ``eng.stats``, ``eng.close()``.  With ``decode_kernels="skinny"`` a request's
         tokens are, bit for bit, those of a one-row session given the same prompt, parameters and seed, whatever else is in
         flight, for ``max_batch <= 16``; ``decode_kernels="wide"`` (bf16 weights) holds the same against a one-row "wide"
-        session for ``max_batch <= 64``; "tile" is accepted without that claim (its step is not batch-invariant)."""
+        session for ``max_batch <= 64``; "tile" is accepted without that claim (its step is not batch-invariant).
+        ``decode_attention="fused"``: the one-launch cache step in every decode step, same tokens (see ``generate``)."""
         from .engine import GenerationEngine
-        return GenerationEngine(self, pool, max_batch, decode_kernels, weight_dtype, sync_every)
+        return GenerationEngine(self, pool, max_batch, decode_kernels, weight_dtype, sync_every,
+                                decode_attention=decode_attention)
 
     def kv_page_pool(self, n_pages, order=None, kv_dtype="bf16"):
         """A ``PagePool`` (paged.py) of ``n_pages`` pages of 256 positions for this model's paged sessions
