@@ -155,6 +155,19 @@ int sd_qknorm_rope_bwd(const void* dqk, const void* qkv, const void* q_gain, con
 int sd_swiglu_fwd(const void* gate_up, void* act, int M, int I, void* stream);
 int sd_swiglu_bwd(const void* dact, const void* gate_up, void* dgate_up, int M, int I, void* stream);
 
+/* ---- Contracts of the row kernels on ids and on untouched columns (pinned by tests/test_gpu_row_kernels.py):
+ *   sd_embedding_fwd, sd_embedding_fwd_ssq   an id outside [0, V) is CLAMPED: id < 0 reads row 0, id >= V reads row V - 1
+ *                                            (no error is raised; E is never read outside its V rows);
+ *   sd_embedding_bwd                         a token whose id is outside [0, V) is SKIPPED: it adds to no row of dE, and
+ *                                            the rows of the other ids get exactly the sums they get without it;
+ *   sd_embedding_bwd_range                   likewise for ids outside [row_lo, V): rows of dE below row_lo are never read
+ *                                            or written (row_lo == V: dE is left as it was);
+ *   sd_rows_scatter                          a row index outside [0, M) is SKIPPED: dst is the zero-filled scatter of
+ *                                            the remaining rows (n == 0: dst is all zero);
+ *   sd_qknorm_rope_bwd, sd_qknorm_rope_bwd2  write the q and k columns [0, (Hq+Hkv)*128) of every row of dqkv and leave
+ *                                            the v columns [(Hq+Hkv)*128, (Hq+2Hkv)*128) UNTOUCHED (in the decoder runner
+ *                                            the attention backward has already stored dV there). */
+
 /* ---- embedding (HF:381) and its deterministic scatter-add backward (dE += scale * rows of dx) */
 int sd_embedding_fwd(const int64_t* ids, const void* E, void* x, int M, int H, int V, void* stream);
 int sd_embedding_bwd(const int64_t* ids, const void* dx, void* dE, int M, int H, int V, float scale, void* stream);

@@ -569,6 +569,22 @@ def test_rmsnorm_fwd_bwd(ops, O, M, H):
     dx, dw = ops.rmsnorm_bwd(to_dev(dy), to_dev(x), to_dev(w), rstd, dres=to_dev(dres))
     check_close(f"rmsnorm_bwd_dx_{M}x{H}", dx, xr.grad + dres.double(), 1.2e-2, 3e-3)
     check_close(f"rmsnorm_bwd_dw_{M}x{H}", dw, wr.grad, 1.2e-2, 4e-3)
+    # the bounds above are relative to the maximum of the whole tensor; per element (tests/rowk_ref.py, DESIGN.md section
+    # 5): y inside the interval bound of its two roundings, rstd to fp32 accuracy, and -- the backward fed the fp64 rstd,
+    # so that it is judged on its own -- dx within half a bf16 ulp plus the fp32 floor of its row, dw within the
+    # bound of an fp32 sum of M terms
+    import rowk_ref as R
+    from parity_ref import rowwise_close
+    r64 = R.rstd64(x)
+    v = R.elem_close(y, yr.detach(), R.rmsnorm_fwd_bound(x, w))
+    assert v.ok, v
+    assert float(((rstd.cpu().double() - r64).abs() / r64).max()) <= R.RSTD_RTOL
+    assert R.differing_share(y, R.rmsnorm_fwd_f32(x, w, rstd32=r64.float())[0]) <= R.ROUNDING_SHARE
+    ref = R.rmsnorm_ref(x, w, dy, dres)
+    dx, dw = ops.rmsnorm_bwd(to_dev(dy), to_dev(x), to_dev(w), to_dev(r64.float()), dres=to_dev(dres))
+    vx = rowwise_close(dx, ref["dx"], torch.bfloat16, R.RMS_BWD_FLOOR)
+    vw = R.elem_close(dw[None], ref["dw"][None], R.gain_bound(ref["dw"], ref["dw_n"], ref["dw_abs"])[None])
+    assert vx.ok and vw.ok, (vx, vw)
 
 
 def test_rmsnorm_bwd_consumes_splitk_slabs(ops):
@@ -613,6 +629,22 @@ def test_qknorm_rope_fwd_bwd(ops, O, B, T, Hq, Hkv):
     check_close(f"qknorm_rope_bwd_dx_T{T}", dqkv[:, :(Hq + Hkv) * 128], x.grad[:, :(Hq + Hkv) * 128], 1.5e-2, 4e-3)
     check_close(f"qknorm_rope_bwd_dqg_T{T}", dqg, qgr.grad, 1.5e-2, 5e-3)
     check_close(f"qknorm_rope_bwd_dkg_T{T}", dkg, kgr.grad, 1.5e-2, 5e-3)
+    # per element (tests/rowk_ref.py): the forward inside the interval bound of its three roundings and rounding where HF
+    # rounds; dqkv per head vector within half a bf16 ulp plus the fp32 floor; the gains within the bound of an fp32 sum;
+    # the v columns of dqkv as the wrapper zero-filled them
+    import rowk_ref as R
+    from parity_ref import rowwise_close
+    inp = dict(qkv=qkv, qg=qg, kg=kg, cos=cos.cpu(), sin=sin.cpu(), dout=dout)
+    r = R.qk_ref(inp, T, Hq, Hkv, backward=True)
+    v = R.elem_close(out, r["out"], R.qk_fwd_bound(inp, T, Hq, Hkv))
+    assert v.ok, v
+    assert R.differing_share(out, R.qk_fwd_f32(inp, T, Hq, Hkv, rstd32=R.qk_rstd64(inp, Hq, Hkv).float())) <= R.ROUNDING_SHARE
+    nqk = (Hq + Hkv) * 128
+    vx = rowwise_close(dqkv[:, :nqk].reshape(-1, 128), r["dqk"].reshape(-1, 128), torch.bfloat16, R.QK_BWD_FLOOR)
+    vq = R.elem_close(dqg[None], r["dqg"][None], R.gain_bound(r["dqg"], r["dqg_n"], r["dqg_abs"])[None])
+    vk = R.elem_close(dkg[None], r["dkg"][None], R.gain_bound(r["dkg"], r["dkg_n"], r["dkg_abs"])[None])
+    assert vx.ok and vq.ok and vk.ok, (vx, vq, vk)
+    assert float(dqkv[:, nqk:].abs().max()) == 0.0
 
 
 def test_colsum_reduce_batch(ops):
@@ -657,7 +689,17 @@ def test_swiglu_fwd_bwd(ops):
     ref = torch.nn.functional.silu(x[:, :256]) * x[:, 256:]
     check_close("swiglu_fwd", ops.swiglu_fwd(to_dev(gu)), ref, 8e-3, 3e-3)
     (ref * dact.double()).sum().backward()
-    check_close("swiglu_bwd", ops.swiglu_bwd(to_dev(dact), to_dev(gu)), x.grad, 8e-3, 3e-3)
+    dgu = ops.swiglu_bwd(to_dev(dact), to_dev(gu))
+    check_close("swiglu_bwd", dgu, x.grad, 8e-3, 3e-3)
+    # per element (tests/rowk_ref.py): half a bf16 ulp plus 2^-16 of the magnitude (|gate| <= 16 here)
+    import rowk_ref as R
+    r = R.swiglu_ref(gu, dact)
+    none = torch.zeros(256, dtype=torch.bool)
+    assert float(gu[:, :256].float().abs().max()) <= R.SWIGLU_GATE_MAX
+    va = R.elem_close(ops.swiglu_fwd(to_dev(gu)), r["act"], R.swiglu_bound(r["act"], r["act_mag"], none))
+    vg = R.elem_close(dgu[:, :256], r["dg"], R.swiglu_bound(r["dg"], r["dg_mag"], none))
+    vu = R.elem_close(dgu[:, 256:], r["du"], R.swiglu_bound(r["du"], r["du_mag"], none))
+    assert va.ok and vg.ok and vu.ok, (va, vg, vu)
 
 
 def test_embedding_fwd_bwd(ops):
