@@ -936,6 +936,52 @@ int sd_qwen3_mx_decode_step_fused(const sd_qwen3_dims* d, const sd_qwen3_params_
                                   const sd_kv_ref* kv, void* acts, int64_t acts_bytes, void* logits, int B, int flags,
                                   void* stream);
 
+/* ---- decode attention for rows that SHARE pages (llm_engine.py:91: prefix caching; a forked session maps the history's
+ * full pages into every row's table).  sd_attn_decode_paged{,_mx} runs one workgroup per (page, kv head, row) and so reads
+ * a page once per row that maps it.  The shared entries take exactly the twins' arguments and leave o and lse BIT-IDENTICAL
+ * to them, for any table, lengths, len_add, max_len and page layout, through the same workspace
+ * (sd_attn_decode_workspace_bytes), the same records and the same merge launch; checks and codes are the twins', in the
+ * twins' order, all before the first launch.
+ * Rows are taken in GROUPS of R consecutive rows, R = sd_attn_shared_group_rows(Hq, Hkv); the last group may be short.  Grid
+ *   (R * ceil(min(cap, max_len) / 256), Hkv, ceil(B / R)): one workgroup per (logical page p, row w of the group, kv head).
+ *   The rows of the group that are live for p (p * 256 < n_b) are partitioned by table[b][p]; the workgroup of the FIRST row
+ *   of a set walks the set's physical page once, loading and unpacking each key / value row once for all the rows mapped to
+ *   it, and the workgroups of the set's other rows leave at once.  So every DISTINCT physical page of a group is walked
+ *   once; a group that shares nothing does the twin's work in the twin's number of workgroups.  Sharing is found on the device from the table, per logical index p (one
+ *   physical page at different logical indices of two rows is two walks); the host passes nothing.  The entry of a row that
+ *   is not live for p is never read; an entry outside [0, n_pages) is clamped as in the twin (no access leaves the pool,
+ *   that row alone is unspecified).
+ * One rule the twin does not need: where rows of DIFFERENT lengths share a page, the shorter row meets the value rows up
+ *   to the longest length as 0 * value, so those slots must hold finite numbers (8-bit pages: no NaN code, no scale byte
+ *   255).  A fork shares only full pages, and a pool that was zero-filled or written satisfies it.
+ * R = 4 for Hq == Hkv and 2 for Hq / Hkv in {2, 4}: 4 query heads per workgroup (8 for Hq / Hkv = 4).  Registers would
+ *   admit 16 heads (R = 8, 8, 4: 256 VGPRs, no scratch), but a workgroup's time grows with its heads -- one wave per SIMD
+ *   scoring 16 heads took twice the time of 4 -- so the measured rule is the small one.
+ * sd_attn_shared_group_rows: R, or SD_ERR_SHAPE (Hq, Hkv <= 0, Hq % Hkv != 0) / SD_ERR_UNSUPPORTED (Hq / Hkv not 1, 2, 4). */
+int sd_attn_shared_group_rows(int Hq, int Hkv);
+int sd_attn_decode_shared_paged(const void* q, const void* k_pool, const void* v_pool, const int32_t* table, int max_pages,
+                                int n_pages, void* o, float* lse, const int32_t* len, int len_add, void* workspace,
+                                int64_t workspace_bytes, int B, int max_len, int Hq, int Hkv, int head_dim, float scale,
+                                void* stream);
+int sd_attn_decode_shared_paged_mx(const void* q, const void* k_data, const void* k_scale, const void* v_data,
+                                   const void* v_scale, const int32_t* table, int max_pages, int n_pages, void* o, float* lse,
+                                   const int32_t* len, int len_add, void* workspace, int64_t workspace_bytes, int B,
+                                   int max_len, int Hq, int Hkv, int head_dim, float scale, void* stream);
+/* The decode steps with the shared attention standing where sd_attn_decode_paged{,_mx} does, over a PAGED cache
+ * (sd_kv_ref kind 1 or 2; kind 0 is SD_ERR_SHAPE).  kernels: 0 the tile sequence, 1 SD_DECODE_SKINNY, 2 wide (bf16 weights);
+ * flags: 0 or SD_DECODE_SKINNY (MXFP8 weights).  The launches, the acts (the *_shared_acts_bytes queries: the twins' sizes)
+ * and every other check and code are those of sd_qwen3_decode_step_paged{,_mx} / _wide / sd_qwen3_mx_decode_step; logits and
+ * every byte of the pool are bit-identical to them.  All checks before the first launch. */
+int64_t sd_qwen3_decode_step_shared_acts_bytes(const sd_qwen3_dims* d, int B, int cap);
+int sd_qwen3_decode_step_shared(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids, const int32_t* pos,
+                                int max_len, const void* cos_tab, const void* sin_tab, const sd_kv_ref* kv, void* acts,
+                                int64_t acts_bytes, void* logits, int B, int kernels, void* stream);
+int64_t sd_qwen3_mx_decode_step_shared_acts_bytes(const sd_qwen3_dims* d, int B, int cap);
+int sd_qwen3_mx_decode_step_shared(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids,
+                                   const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab,
+                                   const sd_kv_ref* kv, void* acts, int64_t acts_bytes, void* logits, int B, int flags,
+                                   void* stream);
+
 /* ---- stream placement.  HIP multiplexes streams onto a few hardware queues (4 by default); streams that share a
  * queue never overlap.  Measures, with a `spin_us`-long busy-wait kernel on stream_a and an empty one on stream_b,
  * whether work on b runs while a is busy: *overlap = 1/0.  Synchronises both streams (a calibration call, made once

@@ -287,6 +287,18 @@ PROTOTYPES = {
     "sd_qwen3_mx_decode_step_fused_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
     "sd_qwen3_mx_decode_step_fused": (_i, [C.POINTER(Dims), C.POINTER(ParamsMx), _vp, _vp, _i, _vp, _vp, C.POINTER(KvRef),
                                            _vp, _i64, _vp, _i, _i, _vp]),
+    # decode attention for rows that share pages (the twins' arguments) and the decode steps on it, over a paged cache
+    "sd_attn_shared_group_rows": (_i, [_i, _i]),
+    "sd_attn_decode_shared_paged": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _i, _i, _i, _f,
+                                         _vp]),
+    "sd_attn_decode_shared_paged_mx": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _i,
+                                            _i, _i, _f, _vp]),
+    "sd_qwen3_decode_step_shared_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
+    "sd_qwen3_decode_step_shared": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _i, _vp, _vp, C.POINTER(KvRef), _vp,
+                                         _i64, _vp, _i, _i, _vp]),
+    "sd_qwen3_mx_decode_step_shared_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
+    "sd_qwen3_mx_decode_step_shared": (_i, [C.POINTER(Dims), C.POINTER(ParamsMx), _vp, _vp, _i, _vp, _vp, C.POINTER(KvRef),
+                                            _vp, _i64, _vp, _i, _i, _vp]),
 }
 
 

@@ -877,6 +877,18 @@ extern "C" int sd_attn_decode(const void* q, const void* k_plane, const void* v_
   return 0;
 }
 
+// internal (sd_runner.h): phase 2 alone, the second launch of the three entries around it, for sd_attn_shared.hip --
+// the grouped phase 1 there is finished by this very kernel
+int sd_attn_decode_merge_launch(const void* workspace, void* o, float* lse, const int32_t* len, int len_add, int cap,
+                                int max_len, int B, int Hq, int pstride, int np, void* stream) {
+  SdProfScope prof(SD_K_MISC, (double)B * Hq * np * kRec * 4, ST);
+  SD_PROF_LABEL("attn_decode_merge_kernel");
+  hipLaunchKernelGGL(attn_decode_merge_kernel, dim3(Hq, B), dim3(128), 0, ST, (const float*)workspace, (bf16*)o, lse, len,
+                     len_add, cap, max_len, Hq, pstride);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
 // The paged twin (llm_engine.py:91): phase 1 reads its page from the table, phase 2 and the workspace are the twin's.
 extern "C" int sd_attn_decode_paged(const void* q, const void* k_pool, const void* v_pool, const int32_t* table,
                                     int max_pages, int n_pages, void* o, float* lse, const int32_t* len, int len_add,

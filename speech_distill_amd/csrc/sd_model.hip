@@ -862,6 +862,31 @@ extern "C" int sd_qwen3_decode_step_fused(const sd_qwen3_dims* d, const sd_qwen3
   return decode_step_impl(d, p, ids, pos, max_len, cos_tab, sin_tab, kv, s, a, logits, B, flags, stream);
 }
 
+// sd_qwen3_decode_step_shared: any of the three sequences over a PAGED cache, on the shared-page decode attention
+extern "C" int64_t sd_qwen3_decode_step_shared_acts_bytes(const sd_qwen3_dims* d, int B, int cap) {
+  return sd_qwen3_decode_acts_bytes(d, B, cap);
+}
+
+extern "C" int sd_qwen3_decode_step_shared(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
+                                           const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab,
+                                           const sd_kv_ref* kvr, void* acts, int64_t acts_bytes, void* logits, int B,
+                                           int kernels, void* stream) {
+  if (kernels < 0 || kernels > 2) return SD_ERR_SHAPE;
+  if (!d || !p || !kvr) return SD_ERR_SHAPE;
+  if (d->head_dim != 128) return SD_ERR_UNSUPPORTED;
+  if (B <= 0 || max_len <= 0 || !ids || !pos || !logits || !acts || !cos_tab || !sin_tab) return SD_ERR_SHAPE;
+  if (kvr->kind == 0) return SD_ERR_SHAPE;  // rows of a contiguous cache share nothing
+  RUN(gqa_check(d));
+  KvSink kv = {};
+  RUN(ref_sink(d, kvr, B, &kv));
+  const Sizes s(d, B, 1);
+  const DecodeActs a(d, B, kv.cap, (char*)acts);
+  if (acts_bytes < a.total) return SD_ERR_WORKSPACE;
+  kv.shared = true;
+  const int flags = kernels == 2 ? kStepWide : kernels == 1 ? SD_DECODE_SKINNY : 0;
+  return decode_step_impl(d, p, ids, pos, max_len, cos_tab, sin_tab, kv, s, a, logits, B, flags, stream);
+}
+
 extern "C" int sd_qwen3_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params* p, const int64_t* ids,
                                     const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab, void* cache,
                                     int64_t cache_bytes, int cap, void* acts, int64_t acts_bytes, void* logits, int B,

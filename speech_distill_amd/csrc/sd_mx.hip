@@ -561,15 +561,18 @@ extern "C" int64_t sd_qwen3_mx_decode_step_acts_bytes(const sd_qwen3_dims* d, in
   return MxDecodeActs(d, B, cap, nullptr).total;
 }
 
-// the checks and launches of sd_qwen3_mx_decode_step; fused: on the one-launch cache step (sd_qwen3_mx_decode_step_fused)
+// the checks and launches of sd_qwen3_mx_decode_step; fused: on the one-launch cache step (sd_qwen3_mx_decode_step_fused);
+// shared: on the shared-page decode attention over a paged cache (sd_qwen3_mx_decode_step_shared)
 static int mx_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids, const int32_t* pos,
                           int max_len, const void* cos_tab, const void* sin_tab, const sd_kv_ref* kvr, void* acts,
-                          int64_t acts_bytes, void* logits, int B, int flags, void* stream, bool fused) {
+                          int64_t acts_bytes, void* logits, int B, int flags, void* stream, bool fused,
+                          bool shared = false) {
   if (flags & ~SD_DECODE_SKINNY) return SD_ERR_SHAPE;
   if (!d || !p || !kvr) return SD_ERR_SHAPE;
   if (!mx_supported(d)) return SD_ERR_UNSUPPORTED;
   if (B <= 0 || max_len <= 0 || !ids || !pos || !logits || !acts) return SD_ERR_SHAPE;
-  if (fused && (!cos_tab || !sin_tab)) return SD_ERR_SHAPE;
+  if ((fused || shared) && (!cos_tab || !sin_tab)) return SD_ERR_SHAPE;
+  if (shared && kvr->kind == 0) return SD_ERR_SHAPE;  // rows of a contiguous cache share nothing
   RUN(gqa_check(d));
   KvSink kv = {};
   RUN(ref_sink(d, kvr, B, &kv));
@@ -577,6 +580,7 @@ static int mx_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, c
   if (acts_bytes < a.total) return SD_ERR_WORKSPACE;
   if (fused) RUN(fused_align_check(acts, kv));
   kv.tickets = a.tickets;
+  kv.shared = shared;
   const int h = a.h;
   const float eps = d->eps;
   const bool skinny = (flags & SD_DECODE_SKINNY) && skinny_mx_ok(p, a, logits, B);
@@ -628,4 +632,16 @@ extern "C" int sd_qwen3_mx_decode_step_fused(const sd_qwen3_dims* d, const sd_qw
                                              const sd_kv_ref* kvr, void* acts, int64_t acts_bytes, void* logits, int B,
                                              int flags, void* stream) {
   return mx_decode_step(d, p, ids, pos, max_len, cos_tab, sin_tab, kvr, acts, acts_bytes, logits, B, flags, stream, true);
+}
+
+extern "C" int64_t sd_qwen3_mx_decode_step_shared_acts_bytes(const sd_qwen3_dims* d, int B, int cap) {
+  return sd_qwen3_mx_decode_step_acts_bytes(d, B, cap);
+}
+
+extern "C" int sd_qwen3_mx_decode_step_shared(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids,
+                                              const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab,
+                                              const sd_kv_ref* kvr, void* acts, int64_t acts_bytes, void* logits, int B,
+                                              int flags, void* stream) {
+  return mx_decode_step(d, p, ids, pos, max_len, cos_tab, sin_tab, kvr, acts, acts_bytes, logits, B, flags, stream, false,
+                        true);
 }

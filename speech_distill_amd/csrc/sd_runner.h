@@ -36,6 +36,13 @@ __attribute__((visibility("hidden"))) int sd_rope_rows_at(const void* cos_tab, c
                                                           void* cos_out, void* sin_out, int B, int T, int cap,
                                                           void* stream);
 
+// sd_decode.hip: attn_decode_merge_kernel on the records of a phase 1 (B, Hq checked by the caller; np: partitions of the
+// launch, for the profiler's byte count).  sd_attn_shared.hip ends its entries with it.  Internal: not exported.
+__attribute__((visibility("hidden"))) int sd_attn_decode_merge_launch(const void* workspace, void* o, float* lse,
+                                                                      const int32_t* len, int len_add, int cap,
+                                                                      int max_len, int B, int Hq, int pstride, int np,
+                                                                      void* stream);
+
 // the shape ints every runner derives from the dims and the batch
 struct SdShape {
   int M, h, I, QD, KD, QKV, QK, V, L, Hq, Hkv;
@@ -75,6 +82,9 @@ struct KvSink {
   // The decode step on the one-launch cache step (sd_cache_step): int32 [L][B][Hkv] at the tail of the step's acts,
   // zeroed by begin_step ahead of layer 0; layer l draws from its own [B][Hkv] slice.  nullptr: the two-entry step.
   int32_t* tickets = nullptr;
+  // Paged kinds only (sd_qwen3_decode_step_shared): the decode attention of step() is sd_attn_decode_shared_paged{,_mx},
+  // which reads a physical page once for all the rows of a group that map it.  Same bits; the append is unchanged.
+  bool shared = false;
   // 8-bit pages: the data (u8 [n_pages][256][Hkv*128]) or scale (u8 [n_pages][256][Hkv*4]) plane of K (0) or V (1)
   char* mx_plane(const SdShape& s, int l, int which, bool scale) const {
     const int64_t data = (int64_t)n_pages * SD_KV_PAGE * s.KD;
@@ -131,15 +141,17 @@ struct KvSink {
            *vs = mx_plane(s, l, 1, true);
       RUN(sd_qknorm_rope_append_paged_mx(qkv, q_gain, k_gain, cos_tab, sin_tab, pos, q, kd, ks, vd, vs, table, max_pages,
                                          n_pages, B, s.Hq, s.Hkv, eps, stream));
-      return sd_attn_decode_paged_mx(q, kd, ks, vd, vs, table, max_pages, n_pages, ao, nullptr, pos, 1, ws, ws_bytes, B,
-                                     max_len, s.Hq, s.Hkv, 128, kSdAttnScale, stream);
+      return (shared ? sd_attn_decode_shared_paged_mx : sd_attn_decode_paged_mx)(
+          q, kd, ks, vd, vs, table, max_pages, n_pages, ao, nullptr, pos, 1, ws, ws_bytes, B, max_len, s.Hq, s.Hkv, 128,
+          kSdAttnScale, stream);
     }
     char *kp = plane(s, B, l, 0), *vp = plane(s, B, l, 1);
     if (table) {
       RUN(sd_qknorm_rope_append_paged(qkv, q_gain, k_gain, cos_tab, sin_tab, pos, q, kp, vp, table, max_pages, n_pages, B,
                                       s.Hq, s.Hkv, eps, stream));
-      return sd_attn_decode_paged(q, kp, vp, table, max_pages, n_pages, ao, nullptr, pos, 1, ws, ws_bytes, B, max_len, s.Hq,
-                                  s.Hkv, 128, kSdAttnScale, stream);
+      return (shared ? sd_attn_decode_shared_paged : sd_attn_decode_paged)(
+          q, kp, vp, table, max_pages, n_pages, ao, nullptr, pos, 1, ws, ws_bytes, B, max_len, s.Hq, s.Hkv, 128,
+          kSdAttnScale, stream);
     }
     RUN(sd_qknorm_rope_append(qkv, q_gain, k_gain, cos_tab, sin_tab, pos, q, kp, vp, B, cap, s.Hq, s.Hkv, eps, stream));
     return sd_attn_decode(q, kp, vp, ao, nullptr, pos, 1, ws, ws_bytes, B, cap, max_len, s.Hq, s.Hkv, 128, kSdAttnScale,

@@ -56,6 +56,19 @@ def _check_decode_attention(decode_attention):
         raise ValueError(f"decode_attention must be one of {DECODE_ATTENTION}, got {decode_attention!r}")
 
 
+def _check_shared_kv_reads(shared_kv_reads, pool, decode_attention):
+    """``shared_kv_reads=True`` needs pages that rows can share (a ``pool``) and the split cache step (the one-launch step
+    reads a page per row).  Raises before anything is allocated."""
+    if not shared_kv_reads:
+        return
+    if pool is None:
+        raise ValueError("shared_kv_reads=True is for sessions over a page pool: rows of a contiguous cache share nothing "
+                         "(start_session(..., pool=pool))")
+    if decode_attention == "fused":
+        raise ValueError('shared_kv_reads=True runs the split cache step: the one-launch step (decode_attention="fused") '
+                         "reads a page once per row")
+
+
 def _check_weight_dtype(model, weight_dtype):
     """The weights a generation decodes with.  "bf16": the unfolded bf16 weights, for a model whose inference precision is
     "bf16" (NotImplementedError otherwise, as before the keyword existed).  "mxfp8": the model's quantised, gain-folded
@@ -109,10 +122,19 @@ class Decoder:
     launches; "fused" runs it as ONE launch (sd_cache_step, through sd_qwen3_decode_step_fused /
     sd_qwen3_mx_decode_step_fused: two launches fewer per layer, one memset per step).  Logits, tokens and every byte of the
     cache are those of "split", for every cache kind, ``decode_kernels`` and ``weight_dtype``; ``prefill`` and ``extend`` do
-    not depend on it.  Another value is a ValueError before anything is allocated."""
+    not depend on it.  Another value is a ValueError before anything is allocated.
 
-    def __init__(self, model, B, cap, decode_kernels="tile", pool=None, weight_dtype="bf16", decode_attention="split"):
+    ``shared_kv_reads=True`` (paged decoders on the split cache step; a ValueError otherwise, before anything is
+    allocated): the decode attention of every step reads a physical page ONCE for all the rows of a group of consecutive
+    rows that map it (sd_qwen3_decode_step_shared / sd_qwen3_mx_decode_step_shared) -- the rows of a forked session share
+    their history's pages.  Logits, tokens and every byte of the pool are those of the default, for every
+    ``decode_kernels``, ``weight_dtype`` and page dtype; rows that share nothing cost more time, never other bits."""
+
+    def __init__(self, model, B, cap, decode_kernels="tile", pool=None, weight_dtype="bf16", decode_attention="split",
+                 shared_kv_reads=False):
         _check_decode_attention(decode_attention)
+        _check_shared_kv_reads(shared_kv_reads, pool, decode_attention)
+        self.shared = bool(shared_kv_reads)
         _check_decode_kernels(decode_kernels, weight_dtype)
         _check_weight_dtype(model, weight_dtype)
         self.flags = 1 if decode_kernels == "skinny" else 0   # include/sd_hip.h SD_DECODE_SKINNY
@@ -143,14 +165,14 @@ class Decoder:
             nb = lib.sd_kvcache_bytes(C.byref(d), self.B, self.cap)
             check(min(nb, 0), "sd_kvcache_bytes")
             self.cache = torch.empty(nb, dtype=torch.uint8, device=dev)
-        if weight_dtype == "mxfp8" or self.wide or self.fused:   # include/sd_hip.h sd_kv_ref: fixed for the decoder's life
+        if weight_dtype == "mxfp8" or self.wide or self.fused or self.shared:   # include/sd_hip.h sd_kv_ref: fixed for the decoder's life
             if pool is not None:
                 self._kvref = _lib.KvRef(2 if self._mx else 1, None, 0, 0, C.pointer(self._kvp))
             else:
                 self._kvref = _lib.KvRef(0, self.cache.data_ptr(), self.cache.numel(), self.cap, None)
-            if self.fused:
-                name = "sd_qwen3_mx_decode_step_fused_acts_bytes" if weight_dtype == "mxfp8" else \
-                    "sd_qwen3_decode_step_fused_acts_bytes"
+            if self.fused or self.shared:
+                name = "sd_qwen3%s_decode_step_%s_acts_bytes" % ("_mx" if weight_dtype == "mxfp8" else "",
+                                                                 "fused" if self.fused else "shared")
             else:
                 name = "sd_qwen3_decode_step_wide_acts_bytes" if self.wide else "sd_qwen3_mx_decode_step_acts_bytes"
             nb = getattr(lib, name)(C.byref(d), self.B, self.cap)
@@ -333,11 +355,12 @@ class Decoder:
         _need(ids, torch.int64, "ids"), _need(pos, torch.int32, "pos")
         if ids.numel() != self.B or pos.numel() != self.B:
             raise ValueError(f"decode step wants {self.B} tokens and positions")
-        if self.fused:   # one entry per weight dtype, over the cache of any kind
+        if self.fused or self.shared:   # one entry per weight dtype, over the cache of any kind (shared: any paged kind)
+            how = "fused" if self.fused else "shared"
             if self.weight_dtype == "mxfp8":
-                name, params, kind = "sd_qwen3_mx_decode_step_fused", m._mx_params(), self.flags
+                name, params, kind = "sd_qwen3_mx_decode_step_" + how, m._mx_params(), self.flags
             else:   # kernels: 0 tile, 1 skinny, 2 wide
-                name, params, kind = "sd_qwen3_decode_step_fused", self._params(), 2 if self.wide else self.flags
+                name, params, kind = "sd_qwen3_decode_step_" + how, self._params(), 2 if self.wide else self.flags
             check(getattr(lib, name)(C.byref(m._cdims), C.byref(params), ids.data_ptr(), pos.data_ptr(), int(max_len),
                                      self.cos.data_ptr(), self.sin.data_ptr(), C.byref(self._kvref),
                                      self.step_acts.data_ptr(), self.step_acts.numel(), self.logits.data_ptr(), self.B,
@@ -436,19 +459,25 @@ class GenerationSession:
     (``Decoder``); ``fork`` keeps it.  Everything else above holds unchanged.
 
     ``decode_attention="fused"``: the decode steps of every turn run each layer's cache step as one launch (``Decoder``),
-    with the tokens and the cache bytes of "split"; ``fork`` keeps it."""
+    with the tokens and the cache bytes of "split"; ``fork`` keeps it.
+
+    ``shared_kv_reads=True`` (paged sessions on the split cache step): the decode steps read a page that several rows of
+    a group map once for all of them (``Decoder``), with the tokens and the pool bytes of the default.  It pays where rows
+    share pages -- ``fork([0] * 8, shared_kv_reads=True)`` turns the keyword on for the continuations alone; ``fork``
+    inherits it otherwise."""
 
     def __init__(self, model, batch_size, capacity=None, decode_kernels="tile", pool=None, weight_dtype="bf16",
-                 decode_attention="split"):
+                 decode_attention="split", shared_kv_reads=False):
         _check_decode_attention(decode_attention)
+        _check_shared_kv_reads(shared_kv_reads, pool, decode_attention)
         self.model, self.B = model, int(batch_size)
         self.capacity = int(capacity) if capacity is not None else cache_capacity(model)
         if self.B < 1 or self.capacity < 1:
             raise ValueError(f"a session needs batch_size >= 1 and capacity >= 1, got {batch_size}, {capacity}")
         self.pool, self.decode_kernels, self.weight_dtype = pool, decode_kernels, weight_dtype
-        self.decode_attention = decode_attention
+        self.decode_attention, self.shared_kv_reads = decode_attention, bool(shared_kv_reads)
         self.decoder = Decoder(model, self.B, self.capacity, decode_kernels, pool=pool, weight_dtype=weight_dtype,
-                               decode_attention=decode_attention)
+                               decode_attention=decode_attention, shared_kv_reads=shared_kv_reads)
         dev = model.flat.device
         self.seq = torch.zeros(self.B, self.capacity, dtype=torch.int64, device=dev)
         self.len = torch.zeros(self.B, dtype=torch.int32, device=dev)
@@ -502,24 +531,28 @@ class GenerationSession:
         except Exception:
             pass
 
-    def fork(self, rows):
+    def fork(self, rows, shared_kv_reads=None):
         """A new session on the same pool whose row i continues this session's row ``rows[i]`` (repeats allowed: ``fork([0]
         * 8)`` gives 8 continuations of row 0), with one host read of the source lengths.  Pages wholly below ``cached[src]``
         are shared -- a row only writes at positions >= cached[b], so nobody writes there again; the page that holds
         position ``cached[src]`` is copied across all layers when that position does not start a page.  ``seq``, ``len``,
-        ``cached`` and the session flags are copied.  ValueError on a contiguous session, or when the pool lacks the pages
-        for the copies (nothing has changed then)."""
+        ``cached`` and the session flags are copied.  ``shared_kv_reads``: the new session's switch (None: this session's).
+        ValueError on a contiguous session, for ``shared_kv_reads=True`` on a session with ``decode_attention="fused"``, or
+        when the pool lacks the pages for the copies (nothing has changed then)."""
         if self.pool is None:
             raise ValueError("fork() is for sessions over a page pool (start_session(..., pool=pool))")
+        shared = self.shared_kv_reads if shared_kv_reads is None else bool(shared_kv_reads)
+        _check_shared_kv_reads(shared, self.pool, self.decode_attention)
         rows = [int(r) for r in rows]
         if not rows or min(rows) < 0 or max(rows) >= self.B:
             raise ValueError(f"fork rows must lie in [0, {self.B}), got {rows}")
         new = GenerationSession.__new__(GenerationSession)
         new.model, new.B, new.capacity, new.pool, new.decode_kernels = self.model, len(rows), self.capacity, self.pool, \
             self.decode_kernels
-        new.weight_dtype, new.decode_attention = self.weight_dtype, self.decode_attention
+        new.weight_dtype, new.decode_attention, new.shared_kv_reads = self.weight_dtype, self.decode_attention, shared
         new.decoder = Decoder(self.model, new.B, self.capacity, self.decode_kernels, pool=self.pool,
-                              weight_dtype=self.weight_dtype, decode_attention=self.decode_attention)
+                              weight_dtype=self.weight_dtype, decode_attention=self.decode_attention,
+                              shared_kv_reads=shared)
         cached = self.cached.tolist()   # the one host read
         new.decoder.pages, copies = self.decoder.pages.fork(rows, cached)   # raises before anything changed
         self.pool.copy_pages(copies)

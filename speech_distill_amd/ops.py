@@ -1079,6 +1079,52 @@ def attn_decode_paged_mx(q, planes, table, lens, Hq, Hkv, max_len=None, len_add=
     return (o, lse) if want_lse else o
 
 
+# ---- decode attention for rows that share pages (a forked session): the twins' arguments and bits, a page read once
+# for every group of ``attn_shared_group_rows(Hq, Hkv)`` consecutive rows that map it
+def attn_shared_group_rows(Hq, Hkv):
+    """sd_attn_shared_group_rows: rows per group of the shared decode attention (no GPU needed)."""
+    r = load_lib().sd_attn_shared_group_rows(int(Hq), int(Hkv))
+    check(min(r, 0), "sd_attn_shared_group_rows")
+    return r
+
+
+def attn_decode_shared_paged(q, k_pool, v_pool, table, lens, Hq, Hkv, max_len=None, len_add=0, want_lse=False,
+                             workspace=None):
+    """sd_attn_decode_shared_paged: ``attn_decode_paged`` with every physical page read once per group of rows."""
+    _need(q, torch.bfloat16, "q"), _need(lens, torch.int32, "lens")
+    kp, vp, tp, max_pages, n_pages = _paged_args(k_pool, v_pool, table)
+    lib = load_lib()
+    B, cap = q.shape[0], max_pages * 256
+    nb = lib.sd_attn_decode_workspace_bytes(B, Hq, cap)
+    if workspace is None:
+        workspace = torch.empty(max(nb, 16), dtype=torch.uint8, device=q.device)
+    o = torch.empty(B, Hq * 128, dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty(B, Hq, dtype=torch.float32, device=q.device) if want_lse else None
+    check(lib.sd_attn_decode_shared_paged(q.data_ptr(), kp, vp, tp, max_pages, n_pages, o.data_ptr(), _p(lse),
+                                          lens.data_ptr(), int(len_add), workspace.data_ptr(), workspace.numel(), B,
+                                          cap if max_len is None else int(max_len), Hq, Hkv, 128, 128 ** -0.5, _stream()),
+          "sd_attn_decode_shared_paged")
+    return (o, lse) if want_lse else o
+
+
+def attn_decode_shared_paged_mx(q, planes, table, lens, Hq, Hkv, max_len=None, len_add=0, want_lse=False, workspace=None):
+    """sd_attn_decode_shared_paged_mx: ``attn_decode_paged_mx`` with every physical page read once per group of rows."""
+    _need(q, torch.bfloat16, "q"), _need(lens, torch.int32, "lens")
+    pl, tp, max_pages, n_pages = _paged_mx_args(planes, table)
+    lib = load_lib()
+    B, cap = q.shape[0], max_pages * 256
+    nb = lib.sd_attn_decode_workspace_bytes(B, Hq, cap)
+    if workspace is None:
+        workspace = torch.empty(max(nb, 16), dtype=torch.uint8, device=q.device)
+    o = torch.empty(B, Hq * 128, dtype=torch.bfloat16, device=q.device)
+    lse = torch.empty(B, Hq, dtype=torch.float32, device=q.device) if want_lse else None
+    check(lib.sd_attn_decode_shared_paged_mx(q.data_ptr(), *pl, tp, max_pages, n_pages, o.data_ptr(), _p(lse),
+                                             lens.data_ptr(), int(len_add), workspace.data_ptr(), workspace.numel(), B,
+                                             cap if max_len is None else int(max_len), Hq, Hkv, 128, 128 ** -0.5,
+                                             _stream()), "sd_attn_decode_shared_paged_mx")
+    return (o, lse) if want_lse else o
+
+
 def attn_extend_paged_mx(q, planes, table, past, new_len, T, Hq, Hkv, want_lse=True):
     """sd_attn_extend_paged_mx: ``attn_extend_paged`` over MXFP8 planes; the bits of the twin on the dequantised rows."""
     _need(past, torch.int32, "past"), _need(new_len, torch.int32, "new_len")

@@ -877,7 +877,7 @@ class HipQwen3ForCausalLM(nn.Module):
                         decode_kernels, weight_dtype, decode_attention)
 
     def start_session(self, batch_size, capacity=None, decode_kernels="tile", pool=None, weight_dtype="bf16",
-                      decode_attention="split"):
+                      decode_attention="split", shared_kv_reads=False):
         """A ``GenerationSession`` (generation.py): multi-turn generation over ONE live KV cache of ``capacity`` positions
         per row (default: ``cache_capacity(self)``), as the reference's dialogue loop keeps one ``DynamicCache`` across
         turns (soulxpodcast/models/soulxpodcast.py:342,378-380).  ``sess.generate(ids, mask, ...)`` takes a turn and returns
@@ -898,10 +898,14 @@ class HipQwen3ForCausalLM(nn.Module):
         ``weight_dtype="mxfp8"``: the session decodes with the model's MXFP8 projections (see ``generate``); it combines
         with either kind of pool and with contiguous caches.  ``decode_attention="fused"``: the one-launch cache step in
         every decode step (see ``generate``); ``fork`` keeps it.
+
+        ``shared_kv_reads=True`` (needs ``pool`` and the split cache step; ValueError otherwise): the decode steps read a
+        page that several rows map once for a group of rows, with the same tokens and pool bytes.  It is meant for the
+        continuations of a fork, which share the history's pages: ``s.fork([0] * 8, shared_kv_reads=True)``.
         """
         from .generation import GenerationSession
         return GenerationSession(self, batch_size, capacity, decode_kernels, pool=pool, weight_dtype=weight_dtype,
-                                 decode_attention=decode_attention)
+                                 decode_attention=decode_attention, shared_kv_reads=shared_kv_reads)
 
     def generation_engine(self, pool, max_batch=8, decode_kernels="skinny", weight_dtype="bf16", sync_every=16,
                           decode_attention="split"):
