@@ -882,6 +882,38 @@ int sd_qwen3_decode_step_wide(const sd_qwen3_dims* d, const sd_qwen3_params* p, 
                               int max_len, const void* cos_tab, const void* sin_tab, const sd_kv_ref* kv, void* acts,
                               int64_t acts_bytes, void* logits, int B, void* stream);
 
+/* ---- wide weight-streaming GEMV over MXFP8 weights (M = batch <= 64): sd_gemv_mxfp8 / sd_gemv_mxfp8_swiglu, argument for
+ * argument and statement for statement, with up to four 16-column B tiles of quantised rows against the same weight
+ * fragment (the tiling of sd_gemv_wide_bf16).
+ * Order contract: one element's summation order is sd_gemv_mxfp8's -- K-steps of 128 per wave from K alone (nk <= 8: 1,
+ *   <= 16: 2, <= 32: 4, else 8), a wave's K-steps ascending through the accumulator from 0, the waves through LDS in wave
+ *   order, one rounding bf16(sum * rs + float(r)).  So for any 16-row slice s of x, sd_gemv_mxfp8_wide(x)[s] ==
+ *   sd_gemv_mxfp8(x[s]) bit for bit, both forms, any M, N, K; a row's bits do not know the batch around it or the slot
+ *   of the tile it occupies.
+ * Loads and stores: the weights are read 16 bytes per lane, non-temporal, with no LDS staging -- once per launch for K <=
+ *   4096, once per group of two B tiles (M > 32: twice) above it; rows >= M of x are never read; weight rows past N
+ *   re-read row N - 1; nothing outside y[0..M, 0..N) is written.  y may be r under the rule of sd_gemv_bf16.
+ * Supported: 1 <= M <= SD_GEMV_MX_WIDE_MAX_M; every other limit and the SD_ERR_SHAPE / SD_ERR_UNSUPPORTED split are those
+ * of sd_gemv_mxfp8.  Decided before any launch, y untouched. */
+#define SD_GEMV_MX_WIDE_MAX_M 64
+int sd_gemv_mxfp8_wide(const void* x, int64_t ldx, const void* w_q, const void* w_scale, void* y, int64_t ldy, const void* r,
+                       int64_t ldr, int norm, float eps, int M, int N, int K, void* stream);
+int sd_gemv_mxfp8_wide_swiglu(const void* x, const void* wgu_q, const void* wgu_scale, void* act, int norm, float eps, int M,
+                              int I, int K, void* stream);
+/* sd_qwen3_mx_decode_step_wide: the SD_DECODE_SKINNY sequence of sd_qwen3_mx_decode_step on the wide kernels, over a cache
+ * of any kind.  The embedding; per layer sd_gemv_mxfp8_wide(norm) for q|k|v, the cache's append and decode attention,
+ * sd_gemv_mxfp8_wide(r = x) for o, sd_gemv_mxfp8_wide_swiglu(norm), sd_gemv_mxfp8_wide(r = x_mid) for down; then
+ * sd_gemv_wide_bf16(norm_gain = final_norm) for the lm_head at every B: 7 L + 2 launches.  Row b of the logits depends on
+ * row b's token, position and cache only; the hidden state entering the head has the bits of the skinny step's at B <= 16
+ * (the logits do not: another head kernel).  When any projection or the head would refuse its shape (B > 64, ...) the
+ * WHOLE step runs the tile sequence of sd_qwen3_mx_decode_step(flags = 0): never a mixture.  acts of
+ * sd_qwen3_mx_decode_step_wide_acts_bytes (= sd_qwen3_mx_decode_step_acts_bytes).  Checks and codes as
+ * sd_qwen3_mx_decode_step; all before the first launch. */
+int64_t sd_qwen3_mx_decode_step_wide_acts_bytes(const sd_qwen3_dims* d, int B, int cap);
+int sd_qwen3_mx_decode_step_wide(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids, const int32_t* pos,
+                                 int max_len, const void* cos_tab, const void* sin_tab, const sd_kv_ref* kv, void* acts,
+                                 int64_t acts_bytes, void* logits, int B, void* stream);
+
 /* ---- the cache step of a decode layer as ONE launch (llm_engine.py:37-76, the decode loop over a KV cache, :91 for the
  * paged form; per layer HF:252-257 q/k-norm + RoPE, the cache update, HF:185-207 with one query row).
  * sd_cache_step does what sd_qknorm_rope_append{,_paged,_paged_mx} followed by sd_attn_decode{,_paged,_paged_mx} with len =

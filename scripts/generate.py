@@ -54,6 +54,9 @@ def parse_args(argv=None):
     p.add_argument("--decode_kernels", choices=("tile", "skinny", "wide"), default="tile",
                    help="skinny: weight-streaming GEMV kernels for the decode step (batch_size <= 16); wide: the MFMA "
                         "weight-streaming kernels (batch_size <= 64, bf16 weights)")
+    p.add_argument("--gemv_rows", type=int, choices=(16, 64), default=16,
+                   help="64 (with --decode_kernels skinny --weight_dtype mxfp8): the 64-row block-scaled GEMV kernels, "
+                        "batch-invariant steps for batch_size <= 64")
     p.add_argument("--decode_attention", choices=("split", "fused"), default="split",
                    help="fused: every decode step runs each layer's q/k-norm + RoPE, cache append, split-KV attention and "
                         "merge as one launch instead of three; the tokens are the same")
@@ -133,7 +136,7 @@ def serve_continuous(model, pool, args, pad, prompts, out):
     dev = model.flat.device
     eng = model.generation_engine(pool, max_batch=args.batch_size, decode_kernels=args.decode_kernels,
                                   weight_dtype=args.weight_dtype, sync_every=args.sync_every,
-                                  decode_attention=args.decode_attention)
+                                  decode_attention=args.decode_attention, gemv_rows=args.gemv_rows)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     rids = [eng.submit(torch.tensor(ids, dtype=torch.int64, device=dev), max_new_tokens=args.max_tokens,
@@ -181,7 +184,8 @@ def main(argv=None):
             if need > cache_capacity(model):
                 raise ValueError(f"a dialogue of {need} positions exceeds the KV-cache capacity {cache_capacity(model)}")
             sess = model.start_session(len(chunk), (need + 255) // 256 * 256, decode_kernels=args.decode_kernels, pool=pool,
-                                       weight_dtype=args.weight_dtype, decode_attention=args.decode_attention)
+                                       weight_dtype=args.weight_dtype, decode_attention=args.decode_attention,
+                                       gemv_rows=args.gemv_rows)
             for turn in range(n_turns):
                 ids, mask = right_pad([d[turn] for d in chunk], pad)
                 torch.cuda.synchronize()

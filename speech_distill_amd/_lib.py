@@ -277,6 +277,12 @@ PROTOTYPES = {
     "sd_qwen3_decode_step_wide_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
     "sd_qwen3_decode_step_wide": (_i, [C.POINTER(Dims), C.POINTER(Params), _vp, _vp, _i, _vp, _vp, C.POINTER(KvRef), _vp,
                                        _i64, _vp, _i, _vp]),
+    # the 64-row GEMV over MXFP8 weights and the MXFP8 decode step on it
+    "sd_gemv_mxfp8_wide": (_i, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i, _f, _i, _i, _i, _vp]),
+    "sd_gemv_mxfp8_wide_swiglu": (_i, [_vp, _vp, _vp, _vp, _i, _f, _i, _i, _i, _vp]),
+    "sd_qwen3_mx_decode_step_wide_acts_bytes": (_i64, [C.POINTER(Dims), _i, _i]),
+    "sd_qwen3_mx_decode_step_wide": (_i, [C.POINTER(Dims), C.POINTER(ParamsMx), _vp, _vp, _i, _vp, _vp, C.POINTER(KvRef),
+                                          _vp, _i64, _vp, _i, _vp]),
     # the one-launch cache step (append + decode attention + merge) and the decode steps on it
     "sd_cache_step_workspace_bytes": (_i64, [_i, _i, _i, _i]),
     "sd_cache_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(KvPlanes), _vp, _vp, _vp, _i64, _vp, _i, _i, _i, _i, _i,

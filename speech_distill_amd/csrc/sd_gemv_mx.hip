@@ -1,7 +1,9 @@
 // Weight-streaming GEMV over MXFP8 weights for the decode step on gfx950: y[M,N] = rs[m] * (X^[M,K] . W^[N,K]^T) (+ r) for
 // 1 <= M <= 16, W = e4m3fn bytes [N,K] + E8M0 scale bytes [N,K/32] exactly as sd_mxfp8_quant leaves a weight, X^ = the
 // MXFP8 quantisation of the bf16 rows of x, made inside the kernel (the bytes and scale bytes of mx_quant32, sd_mx.hip),
-// rs[m] = 1 or the row's RMSNorm statistic (sd_mxfp8_quant's rstd).  An optional fused SwiGLU epilogue.
+// rs[m] = 1 or the row's RMSNorm statistic (sd_mxfp8_quant's rstd).  An optional fused SwiGLU epilogue.  The quantiser of
+// a K-step, the row statistic, the checks and the KPW / grid rules are in sd_gemv_mx.cuh, shared with the 64-row kernel of
+// sd_gemv_mx_wide.hip.
 //
 // What they replace in the decode step of an MXFP8 model (one token per sequence, M = batch): per projection the
 // sd_mxfp8_quant launch and the 128-row sd_gemm_mxfp8 tile that a batch of <= 16 rows fills to an eighth (HF
@@ -35,50 +37,11 @@
 #include "sd_common.cuh"
 #include "sd_prof.h"
 #include "sd_runner.h"
+#include "sd_gemv_mx.cuh"
 
 #define ST ((hipStream_t)stream)
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) int i32x8;
-
-constexpr int kMaxWaves = 8;   // K slices of a workgroup at most
-constexpr int kMaxK = 8192;    // = kMaxWaves * 8 K-steps of 128
-
-struct GemvMxArgs {
-  const bf16* x;
-  const uint8_t *wq, *ws;
-  const bf16* r;
-  bf16* y;
-  float eps;
-  int norm;
-  int M, N, K;  // N: weight rows of the plain form; columns of act (= I) of the SwiGLU form
-  long ldx, ldy, ldr;
-  int KS;       // waves of the workgroup = K slices
-  int upw;      // 16-row units per workgroup (a multiple of the units per step): tiles, or gate/up tile pairs
-};
-
-// One 16-element run of a 32-block whose amax is known: mx_quant32's arithmetic on half a block
-SD_DEV u32x4 quant16(const float (&x)[16], float inv) {
-  uint32_t w[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    float y[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) y[j] = fminf(fmaxf(x[4 * i + j] * inv, -448.f), 448.f);
-    int p = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], 0, false);
-    p = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], p, true);
-    w[i] = (uint32_t)p;
-  }
-  return u32x4{w[0], w[1], w[2], w[3]};
-}
-// scale byte (e + 127) and 2^-e of a block with this amax: the statements of mx_quant32
-SD_DEV int scale_of(float amax, float& inv) {
-  const int eb = (int)(__builtin_bit_cast(uint32_t, amax) >> 23);
-  const int sb = eb > 8 ? eb - 8 : 0;
-  inv = __builtin_bit_cast(float, (uint32_t)(254 - sb) << 23);
-  return sb;
-}
 
 // TR: 16-row weight tiles a wave takes per step (SwiGLU: TR / 2 gate tiles, each followed by its up tile)
 template <int KPW, int TR, bool SWIGLU>
@@ -144,56 +107,19 @@ __global__ __launch_bounds__(512) void gemv_mx_kernel(const GemvMxArgs a) {
   for (int i = 0; i < KPW; ++i) {
     load_x(raw_next, i + 1);
     float lo[16], hi[16];
-    const bool live = fr < M && k0 + i < nk;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      lo[e] = live ? (float)raw[0][e] : 0.f; lo[8 + e] = live ? (float)raw[1][e] : 0.f;
-      hi[e] = live ? (float)raw[2][e] : 0.f; hi[8 + e] = live ? (float)raw[3][e] : 0.f;
-    }
+    kstep_floats(raw, fr < M && k0 + i < nk, lo, hi);
 #pragma unroll
     for (int e = 0; e < 4; ++e) raw[e] = raw_next[e];
-    float alo = 0.f, ahi = 0.f;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { alo = fmaxf(alo, fabsf(lo[e])); ahi = fmaxf(ahi, fabsf(hi[e])); }
-    // the other half of each 32-block is in the lane with fg ^ 1
-    alo = fmaxf(alo, __shfl_xor(alo, 16, 64));
-    ahi = fmaxf(ahi, __shfl_xor(ahi, 16, 64));
-    float ilo, ihi;
-    const int slo = scale_of(alo, ilo), shi = scale_of(ahi, ihi);
-    const u32x4 qlo = quant16(lo, ilo), qhi = quant16(hi, ihi);
-    const i32x8 q = {(int)qlo[0], (int)qlo[1], (int)qlo[2], (int)qlo[3], (int)qhi[0], (int)qhi[1], (int)qhi[2], (int)qhi[3]};
-    // this lane carries the scale of block fg: blocks 0, 1 are the low runs of the lanes fg = 0, 2; blocks 2, 3 the high
-    // runs of the lanes fg = 0, 3
-    const int src_g = fg == 1 ? 2 : fg == 2 ? 0 : fg;
-    const int both = __shfl(slo | (shi << 8), fr + 16 * src_g, 64);
-    const int sc = (fg < 2 ? both : both >> 8) & 0xff;
+    i32x8 q;
+    int sc;
+    quant_kstep(lo, hi, fr, fg, q, sc);
 #pragma unroll
     for (int j = 0; j < KPW; ++j)
       if (j == i) { xq[j] = q; xs[j] = sc; }
   }
 
-  // ---- the rows' RMSNorm statistic: mxfp8_quant_kernel's statements (one wave per row, one 32-block per lane and pass)
-  if (a.norm) {
-    for (int row = wv; row < M; row += nw) {
-      const bf16* xr = a.x + (long)row * a.ldx;
-      float ss = 0.f;
-      for (int b = lane; b < nblk; b += 64) {
-        float f[32];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const bf16x8 v = *(const bf16x8*)(xr + b * 32 + i * 8);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) f[i * 8 + e] = (float)v[e];
-        }
-#pragma unroll
-        for (int i = 0; i < 32; ++i) ss += f[i] * f[i];
-      }
-      ss = wave_sum(ss);
-      if (lane == 0) rstd_s[row] = rsqrtf(ss / (float)K + a.eps);
-    }
-  } else if (threadIdx.x < 16) {
-    rstd_s[threadIdx.x] = 1.f;
-  }
+  // ---- the rows' RMSNorm statistic (published by the barrier in front of the first combine)
+  row_rstd<SD_GEMV_MAX_M>(a.x, a.ldx, M, K, a.norm, a.eps, rstd_s, lane, wv, nw);
 
   const int tid = threadIdx.x, nthr = nw * 64;
   for (int t = 0; t < nsteps; ++t) {
@@ -254,39 +180,16 @@ __global__ __launch_bounds__(512) void gemv_mx_kernel(const GemvMxArgs a) {
   }
 }
 
-// CUs of the current device (kept per device; it only sizes the grid, no output bit depends on it)
-int cu_count() {
-  static int cached[64];
-  int dev = 0, n = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;
-  if (dev >= 0 && dev < 64 && cached[dev] > 0) return cached[dev];
-  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-  if (dev >= 0 && dev < 64) cached[dev] = n;
-  return n;
-}
-
-int validate(const void* x, const void* wq, const void* ws, const void* y, const void* r, int M, int N, int K, int64_t ldx,
-             int64_t ldy, int64_t ldr) {
-  if (!x || !wq || !ws || !y || M <= 0 || N <= 0 || K <= 0) return SD_ERR_SHAPE;
-  if (M > SD_GEMV_MAX_M || (K & 127) || K > kMaxK || N > (1 << 29)) return SD_ERR_UNSUPPORTED;
-  if (ldx < K || ldy < N || (r && ldr < N)) return SD_ERR_UNSUPPORTED;
-  if ((ldx & 7) || ((uintptr_t)x & 15) || ((uintptr_t)wq & 15) || ((uintptr_t)ws & 3)) return SD_ERR_UNSUPPORTED;
-  return 0;
-}
-
 template <bool SWIGLU>
 int launch(GemvMxArgs a, void* stream) {
   const int nk = a.K >> 7;
-  const int kpw = nk <= 8 ? 1 : nk <= 16 ? 2 : nk <= 32 ? 4 : 8;  // from K alone: it fixes the summation order
+  const int kpw = kpw_of(nk);
   a.KS = (nk + kpw - 1) / kpw;
-  // grid: from N and the CU count only -- about two workgroups per CU while a workgroup keeps one 16-row unit; the
-  // units a wave takes per step (1, 2 or 4 tiles; 1 or 2 gate/up pairs) follow from what a workgroup got
   const int cus = cu_count();
   if (cus <= 0) return SD_ERR_WORKSPACE;
   const int units = (a.N + 15) >> 4;
-  int upw = (units + 2 * cus - 1) / (2 * cus);
-  const int ups = SWIGLU ? (upw >= 2 ? 2 : 1) : (upw >= 4 ? 4 : upw >= 2 ? 2 : 1);
-  upw = (upw + ups - 1) / ups * ups;
+  int upw, ups;
+  grid_of(units, cus, SWIGLU, upw, ups);
   a.upw = upw;
   const int tr = SWIGLU ? 2 * ups : ups;
   const unsigned grid = (unsigned)((units + upw - 1) / upw), block = (unsigned)(a.KS * 64);
@@ -317,12 +220,12 @@ int launch(GemvMxArgs a, void* stream) {
 // ldy = N and no residual stand for the SwiGLU form with N = I
 int sd_gemv_mx_check(const void* x, int64_t ldx, const void* w_q, const void* w_scale, const void* y, int64_t ldy,
                      const void* r, int64_t ldr, int M, int N, int K) {
-  return validate(x, w_q, w_scale, y, r, M, N, K, ldx, ldy, ldr);
+  return validate(x, w_q, w_scale, y, r, M, N, K, ldx, ldy, ldr, SD_GEMV_MAX_M);
 }
 
 extern "C" int sd_gemv_mxfp8(const void* x, int64_t ldx, const void* w_q, const void* w_scale, void* y, int64_t ldy,
                              const void* r, int64_t ldr, int norm, float eps, int M, int N, int K, void* stream) {
-  const int rc = validate(x, w_q, w_scale, y, r, M, N, K, ldx, ldy, ldr);
+  const int rc = validate(x, w_q, w_scale, y, r, M, N, K, ldx, ldy, ldr, SD_GEMV_MAX_M);
   if (rc) return rc;
   GemvMxArgs a = {};
   a.x = (const bf16*)x; a.wq = (const uint8_t*)w_q; a.ws = (const uint8_t*)w_scale; a.r = (const bf16*)r; a.y = (bf16*)y;
@@ -333,7 +236,7 @@ extern "C" int sd_gemv_mxfp8(const void* x, int64_t ldx, const void* w_q, const 
 
 extern "C" int sd_gemv_mxfp8_swiglu(const void* x, const void* wgu_q, const void* wgu_scale, void* act, int norm, float eps,
                                     int M, int I, int K, void* stream) {
-  const int rc = validate(x, wgu_q, wgu_scale, act, nullptr, M, I, K, K, I, 0);
+  const int rc = validate(x, wgu_q, wgu_scale, act, nullptr, M, I, K, K, I, 0, SD_GEMV_MAX_M);
   if (rc) return rc;
   GemvMxArgs a = {};
   a.x = (const bf16*)x; a.wq = (const uint8_t*)wgu_q; a.ws = (const uint8_t*)wgu_scale; a.y = (bf16*)act;

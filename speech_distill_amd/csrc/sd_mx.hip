@@ -500,15 +500,18 @@ struct MxDecodeActs : SdShape {
   }
 };
 
-// true when every GEMV of a skinny step accepts its shape: decided for the whole step before the first launch
-bool skinny_mx_ok(const sd_qwen3_params_mx* p, const MxDecodeActs& a, const void* logits, int B) {
-  bool ok = sd_gemv_check(a.x, p->lm_head, logits, nullptr, p->final_norm, B, a.V, a.h, a.h, a.h, a.V, 0) == 0;
+// true when every GEMV of a skinny step accepts its shape: decided for the whole step before the first launch.  wide: the
+// step of sd_qwen3_mx_decode_step_wide (the 64-row kernels, the head on sd_gemv_wide_bf16)
+bool skinny_mx_ok(const sd_qwen3_params_mx* p, const MxDecodeActs& a, const void* logits, int B, bool wide) {
+  const auto check = wide ? sd_gemv_mx_wide_check : sd_gemv_mx_check;
+  bool ok = (wide ? sd_gemv_wide_check(a.x, p->lm_head, logits, nullptr, p->final_norm, B, a.V, a.h, a.h, a.h, a.V, 0)
+                  : sd_gemv_check(a.x, p->lm_head, logits, nullptr, p->final_norm, B, a.V, a.h, a.h, a.h, a.V, 0)) == 0;
   for (int l = 0; ok && l < a.L; ++l) {
     const sd_qwen3_layer_mx& w = p->layers_host[l];
-    ok = sd_gemv_mx_check(a.x, a.h, w.wqkv_q, w.wqkv_scale, a.qkv, a.QKV, nullptr, 0, B, a.QKV, a.h) == 0 &&
-         sd_gemv_mx_check(a.ao, a.QD, w.wo_q, w.wo_scale, a.x_mid, a.h, a.x, a.h, B, a.h, a.QD) == 0 &&
-         sd_gemv_mx_check(a.x_mid, a.h, w.wgu_q, w.wgu_scale, a.act, a.I, nullptr, 0, B, a.I, a.h) == 0 &&
-         sd_gemv_mx_check(a.act, a.I, w.wdown_q, w.wdown_scale, a.x, a.h, a.x_mid, a.h, B, a.h, a.I) == 0;
+    ok = check(a.x, a.h, w.wqkv_q, w.wqkv_scale, a.qkv, a.QKV, nullptr, 0, B, a.QKV, a.h) == 0 &&
+         check(a.ao, a.QD, w.wo_q, w.wo_scale, a.x_mid, a.h, a.x, a.h, B, a.h, a.QD) == 0 &&
+         check(a.x_mid, a.h, w.wgu_q, w.wgu_scale, a.act, a.I, nullptr, 0, B, a.I, a.h) == 0 &&
+         check(a.act, a.I, w.wdown_q, w.wdown_scale, a.x, a.h, a.x_mid, a.h, B, a.h, a.I) == 0;
   }
   return ok;
 }
@@ -562,11 +565,12 @@ extern "C" int64_t sd_qwen3_mx_decode_step_acts_bytes(const sd_qwen3_dims* d, in
 }
 
 // the checks and launches of sd_qwen3_mx_decode_step; fused: on the one-launch cache step (sd_qwen3_mx_decode_step_fused);
-// shared: on the shared-page decode attention over a paged cache (sd_qwen3_mx_decode_step_shared)
+// shared: on the shared-page decode attention over a paged cache (sd_qwen3_mx_decode_step_shared); wide: the skinny
+// sequence on the 64-row kernels (sd_qwen3_mx_decode_step_wide)
 static int mx_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids, const int32_t* pos,
                           int max_len, const void* cos_tab, const void* sin_tab, const sd_kv_ref* kvr, void* acts,
                           int64_t acts_bytes, void* logits, int B, int flags, void* stream, bool fused,
-                          bool shared = false) {
+                          bool shared = false, bool wide = false) {
   if (flags & ~SD_DECODE_SKINNY) return SD_ERR_SHAPE;
   if (!d || !p || !kvr) return SD_ERR_SHAPE;
   if (!mx_supported(d)) return SD_ERR_UNSUPPORTED;
@@ -583,20 +587,23 @@ static int mx_decode_step(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, c
   kv.shared = shared;
   const int h = a.h;
   const float eps = d->eps;
-  const bool skinny = (flags & SD_DECODE_SKINNY) && skinny_mx_ok(p, a, logits, B);
+  const bool skinny = (flags & SD_DECODE_SKINNY) && skinny_mx_ok(p, a, logits, B, wide);
   RUN(kv.begin_step(a, B, stream));
   RUN(sd_embedding_fwd(ids, p->embed, a.x, B, h, a.V, stream));
   if (skinny) {
+    const auto gemv = wide ? sd_gemv_mxfp8_wide : sd_gemv_mxfp8;
+    const auto gemv_swiglu = wide ? sd_gemv_mxfp8_wide_swiglu : sd_gemv_mxfp8_swiglu;
     for (int l = 0; l < a.L; ++l) {
       const sd_qwen3_layer_mx& w = p->layers_host[l];
-      RUN(sd_gemv_mxfp8(a.x, h, w.wqkv_q, w.wqkv_scale, a.qkv, a.QKV, nullptr, 0, 1, eps, B, a.QKV, h, stream));
+      RUN(gemv(a.x, h, w.wqkv_q, w.wqkv_scale, a.qkv, a.QKV, nullptr, 0, 1, eps, B, a.QKV, h, stream));
       RUN(kv.step(a, l, w.q_gain, w.k_gain, a.qkv, a.q, a.ao, cos_tab, sin_tab, pos, a.ws, a.ws_bytes, B, max_len, eps,
                   stream));
-      RUN(sd_gemv_mxfp8(a.ao, a.QD, w.wo_q, w.wo_scale, a.x_mid, h, a.x, h, 0, 0.f, B, h, a.QD, stream));
-      RUN(sd_gemv_mxfp8_swiglu(a.x_mid, w.wgu_q, w.wgu_scale, a.act, 1, eps, B, a.I, h, stream));
-      RUN(sd_gemv_mxfp8(a.act, a.I, w.wdown_q, w.wdown_scale, a.x, h, a.x_mid, h, 0, 0.f, B, h, a.I, stream));
+      RUN(gemv(a.ao, a.QD, w.wo_q, w.wo_scale, a.x_mid, h, a.x, h, 0, 0.f, B, h, a.QD, stream));
+      RUN(gemv_swiglu(a.x_mid, w.wgu_q, w.wgu_scale, a.act, 1, eps, B, a.I, h, stream));
+      RUN(gemv(a.act, a.I, w.wdown_q, w.wdown_scale, a.x, h, a.x_mid, h, 0, 0.f, B, h, a.I, stream));
     }
-    return sd_gemv_bf16(a.x, p->lm_head, logits, nullptr, p->final_norm, eps, B, a.V, h, h, h, a.V, 0, stream);
+    return (wide ? sd_gemv_wide_bf16 : sd_gemv_bf16)(a.x, p->lm_head, logits, nullptr, p->final_norm, eps, B, a.V, h, h, h,
+                                                     a.V, 0, stream);
   }
   for (int l = 0; l < a.L; ++l) {
     const sd_qwen3_layer_mx& w = p->layers_host[l];
@@ -644,4 +651,17 @@ extern "C" int sd_qwen3_mx_decode_step_shared(const sd_qwen3_dims* d, const sd_q
                                               int flags, void* stream) {
   return mx_decode_step(d, p, ids, pos, max_len, cos_tab, sin_tab, kvr, acts, acts_bytes, logits, B, flags, stream, false,
                         true);
+}
+
+// sd_qwen3_mx_decode_step_wide: the skinny sequence on the 64-row kernels over a cache of any kind
+extern "C" int64_t sd_qwen3_mx_decode_step_wide_acts_bytes(const sd_qwen3_dims* d, int B, int cap) {
+  return sd_qwen3_mx_decode_step_acts_bytes(d, B, cap);
+}
+
+extern "C" int sd_qwen3_mx_decode_step_wide(const sd_qwen3_dims* d, const sd_qwen3_params_mx* p, const int64_t* ids,
+                                            const int32_t* pos, int max_len, const void* cos_tab, const void* sin_tab,
+                                            const sd_kv_ref* kvr, void* acts, int64_t acts_bytes, void* logits, int B,
+                                            void* stream) {
+  return mx_decode_step(d, p, ids, pos, max_len, cos_tab, sin_tab, kvr, acts, acts_bytes, logits, B, SD_DECODE_SKINNY,
+                        stream, false, false, true);
 }

@@ -226,13 +226,14 @@ class GenerationEngine(EngineLoop):
     read of one length) returns the new tokens up to and including the first EOS."""
 
     def __init__(self, model, pool, max_batch=8, decode_kernels="skinny", weight_dtype="bf16", sync_every=16, capacity=None,
-                 decode_attention="split"):
+                 decode_attention="split", gemv_rows=16):
         import torch
         from ._lib import load_lib
-        from .generation import Decoder, _check_decode_attention, _check_decode_kernels, cache_capacity
+        from .generation import Decoder, _check_decode_attention, _check_decode_kernels, _check_gemv_rows, cache_capacity
         from .ops import sample_params, sample_params_rows
         _check_decode_attention(decode_attention)
         _check_decode_kernels(decode_kernels, weight_dtype)
+        _check_gemv_rows(gemv_rows, decode_kernels, weight_dtype, decode_attention)
         if pool is None:
             raise ValueError("the engine serves its rows from a page pool: model.kv_page_pool(n_pages)")
         if int(max_batch) < 1 or int(sync_every) < 1:
@@ -243,8 +244,9 @@ class GenerationEngine(EngineLoop):
         self.model, self.pool, self.B = model, pool, int(max_batch)
         self.decode_kernels, self.weight_dtype, self.sync_every = decode_kernels, weight_dtype, int(sync_every)
         self.decode_attention = decode_attention   # "fused": each layer's cache step is one launch, same tokens (Decoder)
+        self.gemv_rows = gemv_rows   # 64: the MXFP8 "skinny" step on the 64-row kernels (Decoder)
         self.decoder = dec = Decoder(model, self.B, cap, decode_kernels, pool=pool, weight_dtype=weight_dtype,
-                                     decode_attention=decode_attention)
+                                     decode_attention=decode_attention, gemv_rows=gemv_rows)
         super().__init__(Scheduler(dec.pages, min(dec.cap, cache_capacity(model)), sync_every))
         dev, B, V = model.flat.device, self.B, model.dims.vocab_size
         self.seq = torch.zeros(B, dec.cap, dtype=torch.int64, device=dev)

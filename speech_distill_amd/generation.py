@@ -33,6 +33,7 @@ REFERENCE_SAMPLING = dict(do_sample=True, temperature=0.6, top_k=100, top_p=0.9,
 DECODE_KERNELS = ("tile", "skinny", "wide")
 WEIGHT_DTYPES = ("bf16", "mxfp8")
 DECODE_ATTENTION = ("split", "fused")
+GEMV_ROWS = (16, 64)   # rows the "skinny" step's GEMV kernels take; 64: the wide MXFP8 kernels (sd_gemv_mxfp8_wide)
 DEFAULT_CACHE_CAPACITY = 32768  # positions; Qwen3's max_position_embeddings when the config does not say
 
 
@@ -47,8 +48,28 @@ def _check_decode_kernels(decode_kernels, weight_dtype="bf16"):
     if decode_kernels not in DECODE_KERNELS:
         raise ValueError(f"decode_kernels must be one of {DECODE_KERNELS}, got {decode_kernels!r}")
     if decode_kernels == "wide" and weight_dtype == "mxfp8":
-        raise ValueError('decode_kernels="wide" streams bf16 weights only: there is no 64-row MXFP8 GEMV (use "skinny" '
-                         'or "tile" with weight_dtype="mxfp8")')
+        raise ValueError('decode_kernels="wide" streams bf16 weights only: the 64-row MXFP8 step is decode_kernels="skinny" '
+                         'with gemv_rows=64 (or use "skinny" / "tile" with weight_dtype="mxfp8")')
+
+
+def _check_gemv_rows(gemv_rows, decode_kernels="skinny", weight_dtype="mxfp8", decode_attention="split",
+                     shared_kv_reads=False):
+    """``gemv_rows``: the rows the "skinny" step's GEMV kernels take.  16 (default) changes nothing anywhere; 64 selects
+    the wide MXFP8 kernels (sd_qwen3_mx_decode_step_wide) and exists for ``decode_kernels="skinny"`` with
+    ``weight_dtype="mxfp8"`` on the split cache step only.  Raises before anything is allocated or launched."""
+    if not isinstance(gemv_rows, int) or isinstance(gemv_rows, bool) or gemv_rows not in GEMV_ROWS:
+        raise ValueError(f"gemv_rows must be one of {GEMV_ROWS}, got {gemv_rows!r}")
+    if gemv_rows == 16:
+        return
+    if decode_kernels != "skinny":
+        raise ValueError(f'gemv_rows=64 belongs to decode_kernels="skinny", got {decode_kernels!r}')
+    if weight_dtype != "mxfp8":
+        raise ValueError('gemv_rows=64 streams MXFP8 weights (weight_dtype="mxfp8"): the 64-row step on bf16 weights is '
+                         'decode_kernels="wide"')
+    if decode_attention == "fused":
+        raise ValueError('gemv_rows=64 with decode_attention="fused" is not built')
+    if shared_kv_reads:
+        raise ValueError("gemv_rows=64 with shared_kv_reads=True is not built")
 
 
 def _check_decode_attention(decode_attention):
@@ -118,6 +139,11 @@ class Decoder:
     call so that ``.to()``, ``load_state_dict`` and the other invalidations are honoured; "skinny" then streams the 8-bit
     weights through sd_gemv_mxfp8.  Embedding, attention, the norms of q / k, the final norm and the lm_head stay bf16.
 
+    ``gemv_rows`` (16, or 64 with "skinny" on MXFP8 weights and the split cache step; a ValueError otherwise, before
+    anything is allocated): 64 runs the step as sd_qwen3_mx_decode_step_wide -- the skinny sequence on sd_gemv_mxfp8_wide
+    for B <= 64 with the lm_head on sd_gemv_wide_bf16, batch-invariant; B > 64 runs the MXFP8 tile sequence.  The hidden
+    state entering the head has the skinny step's bits at B <= 16; the logits differ as "wide" differs from "skinny".
+
     ``decode_attention``: "split" (default) runs each layer's cache step as the append launch and the two decode-attention
     launches; "fused" runs it as ONE launch (sd_cache_step, through sd_qwen3_decode_step_fused /
     sd_qwen3_mx_decode_step_fused: two launches fewer per layer, one memset per step).  Logits, tokens and every byte of the
@@ -131,12 +157,14 @@ class Decoder:
     ``decode_kernels``, ``weight_dtype`` and page dtype; rows that share nothing cost more time, never other bits."""
 
     def __init__(self, model, B, cap, decode_kernels="tile", pool=None, weight_dtype="bf16", decode_attention="split",
-                 shared_kv_reads=False):
+                 shared_kv_reads=False, gemv_rows=16):
         _check_decode_attention(decode_attention)
         _check_shared_kv_reads(shared_kv_reads, pool, decode_attention)
         self.shared = bool(shared_kv_reads)
         _check_decode_kernels(decode_kernels, weight_dtype)
+        _check_gemv_rows(gemv_rows, decode_kernels, weight_dtype, decode_attention, shared_kv_reads)
         _check_weight_dtype(model, weight_dtype)
+        self.mx_wide = gemv_rows == 64   # the step is sd_qwen3_mx_decode_step_wide
         self.flags = 1 if decode_kernels == "skinny" else 0   # include/sd_hip.h SD_DECODE_SKINNY
         self.wide = decode_kernels == "wide"
         self.fused = decode_attention == "fused"
@@ -174,7 +202,8 @@ class Decoder:
                 name = "sd_qwen3%s_decode_step_%s_acts_bytes" % ("_mx" if weight_dtype == "mxfp8" else "",
                                                                  "fused" if self.fused else "shared")
             else:
-                name = "sd_qwen3_decode_step_wide_acts_bytes" if self.wide else "sd_qwen3_mx_decode_step_acts_bytes"
+                name = "sd_qwen3_decode_step_wide_acts_bytes" if self.wide else \
+                    "sd_qwen3_mx_decode_step_wide_acts_bytes" if self.mx_wide else "sd_qwen3_mx_decode_step_acts_bytes"
             nb = getattr(lib, name)(C.byref(d), self.B, self.cap)
             check(min(nb, 0), name)
         else:
@@ -366,6 +395,13 @@ class Decoder:
                                      self.step_acts.data_ptr(), self.step_acts.numel(), self.logits.data_ptr(), self.B,
                                      kind, _stream()), name)
             return self.logits
+        if self.mx_wide:
+            check(lib.sd_qwen3_mx_decode_step_wide(C.byref(m._cdims), C.byref(m._mx_params()), ids.data_ptr(),
+                                                   pos.data_ptr(), int(max_len), self.cos.data_ptr(), self.sin.data_ptr(),
+                                                   C.byref(self._kvref), self.step_acts.data_ptr(), self.step_acts.numel(),
+                                                   self.logits.data_ptr(), self.B, _stream()),
+                  "sd_qwen3_mx_decode_step_wide")
+            return self.logits
         if self.weight_dtype == "mxfp8":
             check(lib.sd_qwen3_mx_decode_step(C.byref(m._cdims), C.byref(m._mx_params()), ids.data_ptr(), pos.data_ptr(),
                                               int(max_len), self.cos.data_ptr(), self.sin.data_ptr(), C.byref(self._kvref),
@@ -395,13 +431,14 @@ class Decoder:
 
 def _check_args(model, B, T, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p, repetition_penalty,
                 use_ras, win_size, tau_r, sync_every, decode_kernels="tile", model_capacity=True, weight_dtype="bf16",
-                decode_attention="split"):
+                decode_attention="split", gemv_rows=16):
     """``model_capacity``: also hold T + max_new_tokens against ``cache_capacity(model)`` (a session holds its own
     lengths against its own capacity instead)."""
     if weight_dtype not in WEIGHT_DTYPES:
         raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, got {weight_dtype!r}")
     _check_decode_attention(decode_attention)
     _check_decode_kernels(decode_kernels, weight_dtype)
+    _check_gemv_rows(gemv_rows, decode_kernels, weight_dtype, decode_attention)
     if max_new_tokens < 1:
         raise ValueError(f"max_new_tokens must be at least 1, got {max_new_tokens}")
     if top_k < 0 or top_k > 128:
@@ -464,10 +501,14 @@ class GenerationSession:
     ``shared_kv_reads=True`` (paged sessions on the split cache step): the decode steps read a page that several rows of
     a group map once for all of them (``Decoder``), with the tokens and the pool bytes of the default.  It pays where rows
     share pages -- ``fork([0] * 8, shared_kv_reads=True)`` turns the keyword on for the continuations alone; ``fork``
-    inherits it otherwise."""
+    inherits it otherwise.
+
+    ``gemv_rows=64`` (with ``decode_kernels="skinny"``, ``weight_dtype="mxfp8"``): the decode steps stream the 8-bit
+    weights through the 64-row kernels (``Decoder``), batch-invariant for up to 64 rows; ``fork`` inherits it.  A fork
+    that asks for ``shared_kv_reads=True`` on such a session is a ValueError."""
 
     def __init__(self, model, batch_size, capacity=None, decode_kernels="tile", pool=None, weight_dtype="bf16",
-                 decode_attention="split", shared_kv_reads=False):
+                 decode_attention="split", shared_kv_reads=False, gemv_rows=16):
         _check_decode_attention(decode_attention)
         _check_shared_kv_reads(shared_kv_reads, pool, decode_attention)
         self.model, self.B = model, int(batch_size)
@@ -476,8 +517,9 @@ class GenerationSession:
             raise ValueError(f"a session needs batch_size >= 1 and capacity >= 1, got {batch_size}, {capacity}")
         self.pool, self.decode_kernels, self.weight_dtype = pool, decode_kernels, weight_dtype
         self.decode_attention, self.shared_kv_reads = decode_attention, bool(shared_kv_reads)
+        self.gemv_rows = gemv_rows
         self.decoder = Decoder(model, self.B, self.capacity, decode_kernels, pool=pool, weight_dtype=weight_dtype,
-                               decode_attention=decode_attention, shared_kv_reads=shared_kv_reads)
+                               decode_attention=decode_attention, shared_kv_reads=shared_kv_reads, gemv_rows=gemv_rows)
         dev = model.flat.device
         self.seq = torch.zeros(self.B, self.capacity, dtype=torch.int64, device=dev)
         self.len = torch.zeros(self.B, dtype=torch.int32, device=dev)
@@ -543,6 +585,7 @@ class GenerationSession:
             raise ValueError("fork() is for sessions over a page pool (start_session(..., pool=pool))")
         shared = self.shared_kv_reads if shared_kv_reads is None else bool(shared_kv_reads)
         _check_shared_kv_reads(shared, self.pool, self.decode_attention)
+        _check_gemv_rows(self.gemv_rows, self.decode_kernels, self.weight_dtype, self.decode_attention, shared)
         rows = [int(r) for r in rows]
         if not rows or min(rows) < 0 or max(rows) >= self.B:
             raise ValueError(f"fork rows must lie in [0, {self.B}), got {rows}")
@@ -550,9 +593,10 @@ class GenerationSession:
         new.model, new.B, new.capacity, new.pool, new.decode_kernels = self.model, len(rows), self.capacity, self.pool, \
             self.decode_kernels
         new.weight_dtype, new.decode_attention, new.shared_kv_reads = self.weight_dtype, self.decode_attention, shared
+        new.gemv_rows = self.gemv_rows
         new.decoder = Decoder(self.model, new.B, self.capacity, self.decode_kernels, pool=self.pool,
                               weight_dtype=self.weight_dtype, decode_attention=self.decode_attention,
-                              shared_kv_reads=shared)
+                              shared_kv_reads=shared, gemv_rows=self.gemv_rows)
         cached = self.cached.tolist()   # the one host read
         new.decoder.pages, copies = self.decoder.pages.fork(rows, cached)   # raises before anything changed
         self.pool.copy_pages(copies)
@@ -683,16 +727,18 @@ class GenerationSession:
 @torch.no_grad()
 def generate(model, input_ids, attention_mask=None, max_new_tokens=20, min_new_tokens=0, do_sample=True, temperature=1.0,
              top_k=0, top_p=1.0, repetition_penalty=1.0, eos_token_id=None, pad_token_id=None, use_ras=False, win_size=25,
-             tau_r=0.2, seed=None, sync_every=16, decode_kernels="tile", weight_dtype="bf16", decode_attention="split"):
+             tau_r=0.2, seed=None, sync_every=16, decode_kernels="tile", weight_dtype="bf16", decode_attention="split",
+             gemv_rows=16):
     """See ``HipQwen3ForCausalLM.generate``: a one-turn ``GenerationSession``."""
     if input_ids.dim() != 2:
         raise ValueError(f"input_ids must be [B,T], got {tuple(input_ids.shape)}")
     B, T = input_ids.shape
     _check_args(model, B, T, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p, repetition_penalty,
                 use_ras, win_size, tau_r, sync_every, decode_kernels, weight_dtype=weight_dtype,
-                decode_attention=decode_attention)
+                decode_attention=decode_attention, gemv_rows=gemv_rows)
     cap = (T + max_new_tokens + 255) // 256 * 256   # whole attention partitions; the output bits do not depend on it
-    sess = GenerationSession(model, B, cap, decode_kernels, weight_dtype=weight_dtype, decode_attention=decode_attention)
+    sess = GenerationSession(model, B, cap, decode_kernels, weight_dtype=weight_dtype, decode_attention=decode_attention,
+                             gemv_rows=gemv_rows)
     new = sess.generate(input_ids, attention_mask, max_new_tokens, min_new_tokens, do_sample, temperature, top_k, top_p,
                         repetition_penalty, eos_token_id, pad_token_id, use_ras, win_size, tau_r, seed, sync_every)
     return torch.cat([input_ids.to(torch.int64), new], dim=1)

@@ -820,6 +820,7 @@ def gemm_mxfp8_swiglu(a_q, a_scale, wgu_q, wgu_scale, rowscale=None):
 
 
 # ---- weight-streaming GEMV over MXFP8 weights (include/sd_hip.h "the same GEMV over MXFP8 weights"): M = batch <= 16
+# (wide=True: <= 64)
 def _mx_weight(w_q, w_scale, name):
     _need(w_q, torch.uint8, name + "_q"), _need(w_scale, torch.uint8, name + "_scale")
     if w_q.dim() != 2 or tuple(w_scale.shape) != (w_q.shape[0], w_q.shape[1] // 32):
@@ -827,11 +828,13 @@ def _mx_weight(w_q, w_scale, name):
                          f"{tuple(w_scale.shape)}")
 
 
-def gemv_mxfp8(x, w_q, w_scale, residual=None, norm=False, eps=1e-6, out=None):
+def gemv_mxfp8(x, w_q, w_scale, residual=None, norm=False, eps=1e-6, out=None, wide=False):
     """y [M,N] = bf16(rs[m] * (X^ . W^T) + residual): x bf16 [M,K] (quantised to MXFP8 inside the kernel, as
     ``mxfp8_quant`` would), W = (e4m3 bytes [N,K], E8M0 bytes [N,K/32]) as ``mxfp8_quant`` of a weight gives them;
     rs = that call's rstd when ``norm``, else 1; 1 <= M <= 16.  x, residual and out may have strided rows.  The bits of
-    y[m,n] depend on row m, weight row n and K only."""
+    y[m,n] depend on row m, weight row n and K only.  ``wide``: sd_gemv_mxfp8_wide (1 <= M <= 64), whose rows have the
+    same bits."""
+    entry = "sd_gemv_mxfp8_wide" if wide else "sd_gemv_mxfp8"
     _rows2d(x, "x"), _mx_weight(w_q, w_scale, "w")
     M, K = x.shape
     N, Kw = w_q.shape
@@ -842,15 +845,17 @@ def gemv_mxfp8(x, w_q, w_scale, residual=None, norm=False, eps=1e-6, out=None):
     _rows2d(out, "out")
     if out.shape != (M, N) or (residual is not None and _rows2d(residual, "residual").shape != (M, N)):
         raise ValueError("gemv_mxfp8: out / residual must be [M,N]")
-    check(load_lib().sd_gemv_mxfp8(x.data_ptr(), x.stride(0), w_q.data_ptr(), w_scale.data_ptr(), out.data_ptr(),
-                                   out.stride(0), _p(residual), 0 if residual is None else residual.stride(0),
-                                   1 if norm else 0, float(eps), M, N, K, _stream()), "sd_gemv_mxfp8")
+    check(getattr(load_lib(), entry)(x.data_ptr(), x.stride(0), w_q.data_ptr(), w_scale.data_ptr(), out.data_ptr(),
+                                     out.stride(0), _p(residual), 0 if residual is None else residual.stride(0),
+                                     1 if norm else 0, float(eps), M, N, K, _stream()), entry)
     return out
 
 
-def gemv_mxfp8_swiglu(x, wgu_q, wgu_scale, norm=False, eps=1e-6):
+def gemv_mxfp8_swiglu(x, wgu_q, wgu_scale, norm=False, eps=1e-6, wide=False):
     """act bf16 [M,I] = silu(g) * u, g | u = bf16(rs * (X^ . Wgu^T)) with Wgu = [gate rows | up rows] [2I,K] in MXFP8;
-    1 <= M <= 16.  Equals swiglu_fwd(gemv_mxfp8(x, wgu_q, wgu_scale, norm=...)) bit for bit."""
+    1 <= M <= 16.  Equals swiglu_fwd(gemv_mxfp8(x, wgu_q, wgu_scale, norm=...)) bit for bit.  ``wide``:
+    sd_gemv_mxfp8_wide_swiglu (1 <= M <= 64), same bits."""
+    entry = "sd_gemv_mxfp8_wide_swiglu" if wide else "sd_gemv_mxfp8_swiglu"
     _need(x, torch.bfloat16, "x"), _mx_weight(wgu_q, wgu_scale, "wgu")
     if x.dim() != 2 or wgu_q.shape[0] % 2 or wgu_q.shape[1] != x.shape[1]:
         raise ValueError(f"gemv_mxfp8_swiglu: x must be [M,K] and wgu_q [2I,K], got {tuple(x.shape)} and "
@@ -858,8 +863,8 @@ def gemv_mxfp8_swiglu(x, wgu_q, wgu_scale, norm=False, eps=1e-6):
     M, K = x.shape
     I = wgu_q.shape[0] // 2
     act = torch.empty(M, I, dtype=torch.bfloat16, device=x.device)
-    check(load_lib().sd_gemv_mxfp8_swiglu(x.data_ptr(), wgu_q.data_ptr(), wgu_scale.data_ptr(), act.data_ptr(),
-                                          1 if norm else 0, float(eps), M, I, K, _stream()), "sd_gemv_mxfp8_swiglu")
+    check(getattr(load_lib(), entry)(x.data_ptr(), wgu_q.data_ptr(), wgu_scale.data_ptr(), act.data_ptr(),
+                                     1 if norm else 0, float(eps), M, I, K, _stream()), entry)
     return act
 
 

@@ -840,7 +840,7 @@ class HipQwen3ForCausalLM(nn.Module):
     def generate(self, input_ids, attention_mask=None, max_new_tokens=20, min_new_tokens=0, do_sample=True,
                  temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, eos_token_id=None, pad_token_id=None,
                  use_ras=False, win_size=25, tau_r=0.2, seed=None, sync_every=16, decode_kernels="tile",
-                 weight_dtype="bf16", decode_attention="split"):
+                 weight_dtype="bf16", decode_attention="split", gemv_rows=16):
         """Decode ``max_new_tokens`` tokens per row over a KV cache (generation.py; the reference's engine:
         soulxpodcast/engine/llm_engine.py:37-76 with sampler.py:136-189).  Returns int64 [B, T + max_new_tokens]: the given
         ``input_ids`` followed by the new tokens in columns T..., ``pad_token_id`` (default: ``eos_token_id``, else 0) after
@@ -865,7 +865,13 @@ class HipQwen3ForCausalLM(nn.Module):
         model's MXFP8 weights (``set_inference_precision``'s format, whatever the precision the model is set to); with
         "skinny" the 8-bit weights are streamed through the block-scaled GEMV.  Needs a frozen model without LoRA and
         the dimensions "mxfp8" needs: ValueError otherwise, and for any other value, before any allocation.  ValueError
-        too for ``decode_kernels="wide"`` with "mxfp8": there is no 64-row MXFP8 GEMV.
+        too for ``decode_kernels="wide"`` with "mxfp8": the 64-row MXFP8 step is spelled ``gemv_rows=64``.
+
+        ``gemv_rows=64`` (default 16; only with ``decode_kernels="skinny"`` and ``weight_dtype="mxfp8"``): the steps
+        stream the 8-bit weights through the 64-row block-scaled GEMV (sd_gemv_mxfp8_wide), so a row's tokens equal those
+        of the row generated alone with the same keywords for batches of up to 64 rows.  ValueError, before any
+        allocation, for another value, with bf16 weights (that step is ``decode_kernels="wide"``), with "tile" / "wide",
+        or with ``decode_attention="fused"`` (not built).
 
         ``decode_attention="fused"`` (default "split"): every decode step runs each layer's cache step -- q/k-norm + RoPE,
         the append, the split-KV attention and its merge -- as one launch instead of three (sd_cache_step).  The tokens
@@ -874,10 +880,10 @@ class HipQwen3ForCausalLM(nn.Module):
         from .generation import generate
         return generate(self, input_ids, attention_mask, max_new_tokens, min_new_tokens, do_sample, temperature, top_k,
                         top_p, repetition_penalty, eos_token_id, pad_token_id, use_ras, win_size, tau_r, seed, sync_every,
-                        decode_kernels, weight_dtype, decode_attention)
+                        decode_kernels, weight_dtype, decode_attention, gemv_rows)
 
     def start_session(self, batch_size, capacity=None, decode_kernels="tile", pool=None, weight_dtype="bf16",
-                      decode_attention="split", shared_kv_reads=False):
+                      decode_attention="split", shared_kv_reads=False, gemv_rows=16):
         """A ``GenerationSession`` (generation.py): multi-turn generation over ONE live KV cache of ``capacity`` positions
         per row (default: ``cache_capacity(self)``), as the reference's dialogue loop keeps one ``DynamicCache`` across
         turns (soulxpodcast/models/soulxpodcast.py:342,378-380).  ``sess.generate(ids, mask, ...)`` takes a turn and returns
@@ -902,13 +908,17 @@ class HipQwen3ForCausalLM(nn.Module):
         ``shared_kv_reads=True`` (needs ``pool`` and the split cache step; ValueError otherwise): the decode steps read a
         page that several rows map once for a group of rows, with the same tokens and pool bytes.  It is meant for the
         continuations of a fork, which share the history's pages: ``s.fork([0] * 8, shared_kv_reads=True)``.
+
+        ``gemv_rows=64`` (with "skinny" and "mxfp8"; see ``generate``): batch-invariant decode steps on the 8-bit weights
+        for up to 64 rows; ``fork`` keeps it.  Not built with ``decode_attention="fused"`` or ``shared_kv_reads=True``
+        (ValueError).
         """
         from .generation import GenerationSession
         return GenerationSession(self, batch_size, capacity, decode_kernels, pool=pool, weight_dtype=weight_dtype,
-                                 decode_attention=decode_attention, shared_kv_reads=shared_kv_reads)
+                                 decode_attention=decode_attention, shared_kv_reads=shared_kv_reads, gemv_rows=gemv_rows)
 
     def generation_engine(self, pool, max_batch=8, decode_kernels="skinny", weight_dtype="bf16", sync_every=16,
-                          decode_attention="split"):
+                          decode_attention="split", gemv_rows=16):
         """A ``GenerationEngine`` (engine.py): continuous batching over a ``PagePool`` -- requests of their own length,
         budget, seed and sampling parameters are served in ``max_batch`` rows, and a row that finishes is refilled with the
         next waiting request at once (the reference's engine is vLLM, soulxpodcast/engine/llm_engine.py:91,97-109).
@@ -917,10 +927,12 @@ class HipQwen3ForCausalLM(nn.Module):
         tokens are, bit for bit, those of a one-row session given the same prompt, parameters and seed, whatever else is in
         flight, for ``max_batch <= 16``; ``decode_kernels="wide"`` (bf16 weights) holds the same against a one-row "wide"
         session for ``max_batch <= 64``; "tile" is accepted without that claim (its step is not batch-invariant).
-        ``decode_attention="fused"``: the one-launch cache step in every decode step, same tokens (see ``generate``)."""
+        ``decode_attention="fused"``: the one-launch cache step in every decode step, same tokens (see ``generate``).
+        ``gemv_rows=64`` with ("skinny", "mxfp8"): the contract holds against a one-row session with the same three
+        keywords for ``max_batch <= 64``."""
         from .engine import GenerationEngine
         return GenerationEngine(self, pool, max_batch, decode_kernels, weight_dtype, sync_every,
-                                decode_attention=decode_attention)
+                                decode_attention=decode_attention, gemv_rows=gemv_rows)
 
     def kv_page_pool(self, n_pages, order=None, kv_dtype="bf16"):
         """A ``PagePool`` (paged.py) of ``n_pages`` pages of 256 positions for this model's paged sessions
