@@ -37,7 +37,11 @@ int sd_abi_version(void);
 
 /* ---- GEMM: every nn.Linear of the decoder and its backward (HF:81-83, 252-254, 279, 441).
  * C[M,N] = op(A) op(B) (+ R).  trans_a=0: A is [M][K]; 1: A is stored [K][M].  trans_b=0: B is [N][K]
- * (torch weight layout); 1: B is stored [K][N].  R (nullable, may alias C) is added in fp32. */
+ * (torch weight layout); 1: B is stored [K][N].  R (nullable, may alias C) is added in fp32.
+ * Operands may be strided views (ld* >= the row length, ld* % 8 == 0, 16-byte aligned pointers).  C[m][n] depends only
+ * on the K elements of op(A)'s row m and of op(B)'s column n (and R[m][n]): the bytes between the rows of a view are never
+ * interpreted (a NaN or Inf there, or in another row, does not reach it), and nothing outside the M x N elements of C is
+ * written. */
 int sd_gemm_bf16(const void* A, const void* B, void* C, const void* R, int M, int N, int K, int64_t lda,
                  int64_t ldb, int64_t ldc, int64_t ldr, int trans_a, int trans_b, void* stream);
 

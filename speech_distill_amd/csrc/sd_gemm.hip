@@ -15,7 +15,7 @@
 // run half a K-step apart (one loads while the other computes) -- the dominant kernel of the step.
 // Common to both: operand tiles go HBM -> LDS by 16-byte LDS-DMA through buffer descriptors
 // (buffer_load_dwordx4 ... lds: loop-invariant per-lane offsets, scalar K advance, hardware range check = zero
-// fill; a pointer-based path with a zero page remains for K % 64 != 0 with two K-contiguous operands); the LDS image
+// fill; a pointer-based path with a zero page remains for K % 64 != 0 with a K-contiguous operand); the LDS image
 // is lane-linear, so the bank-conflict swizzle is applied to the per-lane SOURCE address and undone on the fragment
 // read.  K-contiguous operands are read with ds_read_b128, operands whose contraction index is the slow one with
 // ds_read_b64_tr_b16 (hardware transpose, issued as asm so hipcc does not drain the DMA in front of it).  The
@@ -1448,9 +1448,13 @@ GemmPlan gemm_plan(const GemmQuery& q, const SdDebug& d) {
     if (bm == 64 && (bump & 4)) { bm = 128; nst = 3; }
     else if (bm == 128 && (bump & 8)) { bm = 256; nst = 9; }
   }
-  // 5. Descriptor-based staging needs every k >= K to read as zero in at least one operand (transposed operands get that
-  // from the hardware range check; two K-contiguous ones need K % 64 == 0) and 31-bit offsets.  Two forms of that test:
-  const bool desc_k_ok = !d.gemm_checked_staging && (ta || tb || (K % BK) == 0);
+  // 5. Descriptor-based staging needs every k >= K of the last K tile to read as zero in BOTH operands: 0 * x is NaN for
+  // a non-finite x.  A transposed operand gets that from the hardware range check (its rows k >= K lie behind the
+  // descriptor's end).  A K-contiguous one does not: the descriptor covers (rows - 1) * ld + K elements, so row r at
+  // k >= K reads the bytes behind its own K -- the gap of a strided view, or the head of row r + 1 -- and only
+  // K % 64 == 0 keeps the staging inside the row.  (sd_hip.h: a result row depends on its own operand rows only.)
+  // Plus 31-bit offsets.  Two forms of that test:
+  const bool desc_k_ok = !d.gemm_checked_staging && ((ta && tb) || (K % BK) == 0);
   // stag_ok guards gemm_stag_kernel and gemm_pstag_kernel, which only have the descriptor path: without it 256x9 -> 256x3
   const bool stag_ok = desc_k_ok && ((long)K * (ta ? q.lda : 1) + (long)M * (ta ? 1 : q.lda)) * 2 < 0x70000000L &&
                        ((long)K * (tb ? q.ldb : 1) + (long)N * (tb ? 1 : q.ldb)) * 2 < 0x70000000L;
@@ -1614,9 +1618,9 @@ int dispatch(const void* A, const void* B, void* C, const void* R, float* slabs,
   const GemmQuery q{M, N, K, lda, ldb, ta != 0, tb != 0, epi_kind, R != nullptr, slabs != nullptr, splits, ea.I,
                     ea.ssq_in != nullptr, t_sd_shared_gpu != 0, device_cus()};
   const GemmPlan p = gemm_plan(q, g_sd_debug);
+  if (p.rc) return p.rc;  // refused before anything is launched or recorded
   SdProfScope prof(ta ? SD_K_GEMM_TN : (tb ? SD_K_GEMM_NN : (p.nst == 9 ? SD_K_GEMM_NT_STAG : SD_K_GEMM_NT)),
                    2.0 * M * N * K, st);
-  if (p.rc) return p.rc;
 #ifdef SD_STAMPS
   if (p.kernel == K_PSTAG) ea.cos_t = (const bf16*)g_stamp_buffer;  // diagnostic build: its epilogues do not read cos_t
 #endif

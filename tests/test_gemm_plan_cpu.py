@@ -106,10 +106,15 @@ def test_shared_gpu_bump_of_the_student_o_projection():
 def test_forced_staggered_tile_without_descriptor_staging_takes_the_three_stage_ring():
     _lib.debug_set("gemm.force_bm", 256)
     _lib.debug_set("gemm.force_nst", 9)
-    p = _lib.gemm_plan(520, 264, 200)  # two K-contiguous operands, K % 64 != 0: pointer staging
+    p = _lib.gemm_plan(520, 264, 200)  # a K-contiguous operand, K % 64 != 0: pointer staging
     assert (p["symbol"], p["grid_x"], p["block"], p["gm"]) == ("gemm_bf16_kernel<256, 3, false, false, 0, false>", 9, 512, 3)
     assert _lib.gemm_plan(520, 264, 192)["symbol"] == "gemm_stag_kernel<false, false, 0>"
-    assert _lib.gemm_plan(520, 264, 200, False, True)["symbol"] == "gemm_stag_kernel<false, true, 0>"
+    # one K-contiguous operand is enough: its rows are not zero-filled behind K (descriptor staging would multiply the gap
+    # of a strided view, or the next row, by the other operand's zeros: NaN for a non-finite neighbour)
+    assert _lib.gemm_plan(520, 264, 200, False, True)["symbol"] == "gemm_bf16_kernel<256, 3, false, true, 0, false>"
+    assert _lib.gemm_plan(520, 264, 200, True, False)["symbol"] == "gemm_bf16_kernel<256, 3, true, false, 0, false>"
+    assert _lib.gemm_plan(520, 264, 192, False, True)["symbol"] == "gemm_stag_kernel<false, true, 0>"
+    assert _lib.gemm_plan(520, 264, 200, True, True)["symbol"] == "gemm_stag_kernel<true, true, 0>"  # both transposed
 
 
 def test_checked_staging():

@@ -490,19 +490,25 @@ def test_gemm_split_k(ops):
 
 # name, (M, N, K), ta, tb, residual, split_k, switches, the kernel gemm_plan() picks for it on 256 CUs.
 # Two cases come from a case list that named the wrong kernel for them (forced 256 x 9 NT at K = 200 as the staggered
-# kernel, K = 96 on the 256 x 256 shape as its unpaired form): with two K-contiguous operands and K % 64 != 0 there is no
+# kernel, K = 96 on the 256 x 256 shape as its unpaired form): with a K-contiguous operand and K % 64 != 0 there is no
 # descriptor staging, so both take gemm_bf16_kernel<256, 3, ..., false>.  They stay, with that expectation, and
-# stag_nn_residual / p256_unpaired reach the two kernels that were meant.
+# stag_nn_residual (K = 192) / p256_unpaired reach the two kernels that were meant.
 _FORCE_STAG = {"gemm.force_bm": 256, "gemm.force_nst": 9}
 _P256_SHAPE = (3584, 3328, 64)  # 14 x 26 = 364 tiles of 256 x 128 (> 256 CUs); 14 x 13 = 182 of 256 x 256 (>= 70 % of a round)
 GEMM_PLAN_CASES = [
     ("bf16_64_nt", (200, 136, 72), False, False, False, False, {}, "gemm_bf16_kernel<64, 4, false, false, 0, false>"),
-    ("bf16_64_nn", (200, 136, 72), False, True, False, False, {}, "gemm_bf16_kernel<64, 3, false, true, 0, true>"),
+    # one K-contiguous operand and K % 64 != 0: pointer staging (descriptor staging does not zero-fill such an operand's rows
+    # behind K); at K = 64 the same calls take the descriptor form
+    ("bf16_64_nn", (200, 136, 72), False, True, False, False, {}, "gemm_bf16_kernel<64, 3, false, true, 0, false>"),
     ("bf16_64_tn", (200, 136, 72), True, True, False, False, {}, "gemm_bf16_kernel<64, 3, true, true, 0, true>"),
-    ("bf16_64_ta", (200, 136, 72), True, False, False, False, {}, "gemm_bf16_kernel<64, 3, true, false, 0, true>"),
-    # forced (256, 9) with two K-contiguous operands and K % 64 != 0 has no descriptor staging: the 3-stage ring, pointer form
+    ("bf16_64_ta", (200, 136, 72), True, False, False, False, {}, "gemm_bf16_kernel<64, 3, true, false, 0, false>"),
+    ("bf16_64_nn_k64", (200, 136, 64), False, True, False, False, {}, "gemm_bf16_kernel<64, 3, false, true, 0, true>"),
+    ("bf16_64_ta_k64", (200, 136, 64), True, False, False, False, {}, "gemm_bf16_kernel<64, 3, true, false, 0, true>"),
+    # forced (256, 9) with a K-contiguous operand and K % 64 != 0 has no descriptor staging: the 3-stage ring, pointer form
     ("forced_stag_nt_residual", (520, 264, 200), False, False, True, False, _FORCE_STAG, "gemm_bf16_kernel<256, 3, false, false, 1, false>"),
-    ("stag_nn_residual", (520, 264, 200), False, True, True, False, _FORCE_STAG, "gemm_stag_kernel<false, true, 1>"),
+    ("forced_stag_nn_residual", (520, 264, 200), False, True, True, False, _FORCE_STAG, "gemm_bf16_kernel<256, 3, false, true, 1, false>"),
+    ("stag_nn_residual", (520, 264, 192), False, True, True, False, _FORCE_STAG, "gemm_stag_kernel<false, true, 1>"),
+    ("stag_tn_residual", (520, 264, 200), True, True, True, False, _FORCE_STAG, "gemm_stag_kernel<true, true, 1>"),
     ("pstag", _P256_SHAPE, False, False, False, False, {"gemm.no_p256": 1}, "gemm_pstag_kernel<4, false, false, 0>"),
     ("p256_paired", _P256_SHAPE, False, False, False, False, {"gemm.p256_min_tiles": 150}, "gemm_p256_kernel<0, true>"),
     ("p256_unpaired", _P256_SHAPE, False, False, False, False, {"gemm.p256_min_tiles": 150, "gemm.p256_unpaired": 1},
