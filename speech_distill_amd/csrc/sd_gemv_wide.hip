@@ -1,6 +1,7 @@
 // Wide weight-streaming GEMV for the decode step on gfx950: y[M,N] = xn[M,K] . w[N,K]^T (+ r) for 1 <= M <= 64, bf16
 // operands, with an optional fused RMSNorm of x and an optional fused SwiGLU epilogue.  The semantics of sd_gemv.hip; the
-// form of sd_gemv_mx.hip.
+// form of sd_gemv_mx.hip, with which it shares the walk over a workgroup's units, the combine with its epilogue and the
+// grid rule (sd_gemv_mfma.cuh).
 //
 // What they replace in the decode step (one token per sequence, M = batch): the projections of HF modeling_qwen3.py:239-262
 // (q/k/v, o), :81-83 (the MLP) and the lm_head, with the RMSNorm of :59-64 fused in, reached through the reference's decode
@@ -39,13 +40,11 @@
 #include "sd_common.cuh"
 #include "sd_prof.h"
 #include "sd_runner.h"
+#include "sd_gemv_mfma.cuh"
 
 #define ST ((hipStream_t)stream)
 
 namespace {
-
-constexpr int kMaxWaves = 8;     // K slices of a workgroup at most
-constexpr int kRound = 4;        // accumulator tiles that pass through LDS together
 
 struct WideArgs {
   const bf16 *x, *w, *r, *gain;
@@ -70,27 +69,14 @@ SD_DEV bf16x8 zero8() {
 template <int MT, int TR, bool SWIGLU>
 __global__ __launch_bounds__(512) void wide_gemv_kernel(const WideArgs a) {
   constexpr int G = SWIGLU ? 2 : 1;          // weight tiles per unit
-  constexpr int UPS = TR / G;                // units per step
-  constexpr int NA = TR * MT;                // accumulator tiles of a step, in the order (unit, m-tile, gate / up)
-  constexpr int RP = NA < kRound ? NA : kRound;
-  constexpr int NR = (NA + RP - 1) / RP;
-  static_assert(TR % G == 0 && RP % G == 0, "a gate / up pair stays in one round");
-  __shared__ f32x4 red_s[kMaxWaves][RP][64];
   __shared__ float rstd_s[SD_GEMV_WIDE_MAX_M];
   const int lane = lane_id(), wv = wave_id_uniform(), nw = a.KS;
   const int fr = lane & 15, fg = lane >> 4;
   const int K = a.K, M = a.M, nk = K >> 5, kpw = a.kpw;
-  const int units = (a.N + 15) >> 4;
-  const int u0 = blockIdx.x * a.upw, u1 = min(units, u0 + a.upw);
-  const int nsteps = (u1 - u0 + UPS - 1) / UPS;
-  if (nsteps <= 0) return;  // block-uniform (the grid leaves no workgroup without rows)
+  const UnitWalk<TR / G, G> wk(a.N, a.upw);
+  const int nsteps = wk.nsteps;
+  if (nsteps <= 0) return;
 
-  // weight row behind (step t, tile j, fragment row fr); rows past the edge re-read the last row, never stored
-  auto w_row = [&](int t, int j) {
-    const int u = min(u0 + t * UPS + j / G, u1 - 1);
-    const int c = min(u * 16 + fr, a.N - 1);
-    return (SWIGLU && (j & 1)) ? a.N + c : c;
-  };
   // Unit (step t, K-step i of this wave): TR weight fragments, the raw rows of x and -- with a norm -- the gains of the
   // K-step.  K-steps past the end re-read the last one (an address inside the row) and are not multiplied; columns m >= M
   // are not loaded at all.
@@ -100,7 +86,7 @@ __global__ __launch_bounds__(512) void wide_gemv_kernel(const WideArgs a) {
     const int kc = min(k0 + i, nk - 1) * 32 + fg * 8;
 #pragma unroll
     for (int j = 0; j < TR; ++j)
-      wa[j] = __builtin_nontemporal_load((const bf16x8*)(a.w + (long)w_row(t, j) * a.ldw + kc));
+      wa[j] = __builtin_nontemporal_load((const bf16x8*)(a.w + (long)wk.w_row(t, j, fr) * a.ldw + kc));
 #pragma unroll
     for (int q = 0; q < MT; ++q) {
       const int m = q * 16 + fr;
@@ -138,7 +124,7 @@ __global__ __launch_bounds__(512) void wide_gemv_kernel(const WideArgs a) {
     for (int q = 0; q < MT; ++q) rs[q] = q * 16 + fr < M ? rstd_s[q * 16 + fr] : 0.f;  // columns >= M stay zero
   }
 
-  f32x4 acc[TR][MT];
+  AccTiles<TR, MT> acc;
   auto compute = [&](const bf16x8(&wa)[TR], const bf16x8(&xb)[MT], const bf16x8& gv, int i) {
     if (k0 + i >= nk) return;  // wave-uniform
     bf16x8 b[MT];
@@ -154,15 +140,14 @@ __global__ __launch_bounds__(512) void wide_gemv_kernel(const WideArgs a) {
 #pragma unroll
     for (int j = 0; j < TR; ++j)
 #pragma unroll
-      for (int q = 0; q < MT; ++q) acc[j][q] = mfma16(wa[j], b[q], acc[j][q]);
+      for (int q = 0; q < MT; ++q) acc.t[j][q] = mfma16(wa[j], b[q], acc.t[j][q]);
   };
 
-  const int tid = threadIdx.x, nthr = nw * 64;
   for (int t = 0; t < nsteps; ++t) {
 #pragma unroll
     for (int j = 0; j < TR; ++j)
 #pragma unroll
-      for (int q = 0; q < MT; ++q) acc[j][q] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int q = 0; q < MT; ++q) acc.t[j][q] = f32x4{0.f, 0.f, 0.f, 0.f};
     // K-steps in pairs (kpw is even): each unit's loads go out before the unit ahead of it is multiplied.  Past the last
     // step the first unit of the last step is loaded again, so that every load stays unconditional.
     for (int i = 0; i < kpw; i += 2) {
@@ -172,85 +157,27 @@ __global__ __launch_bounds__(512) void wide_gemv_kernel(const WideArgs a) {
       load(wa0, xb0, g0, more ? t : min(t + 1, nsteps - 1), more ? i + 2 : 0);
       compute(wa1, xb1, g1, i + 1);
     }
-    // ---- combine, RP accumulator tiles per round: entry (tile c of the round, lane slot l) = column m = 16 q + (l & 15),
-    // rows 4 (l >> 4) + 0..3 of the weight tile
-#pragma unroll
-    for (int rd = 0; rd < NR; ++rd) {
-#pragma unroll
-      for (int c = 0; c < RP; ++c) {
-        const int idx = rd * RP + c;
-        if (idx < NA) red_s[wv][c][lane] = acc[(idx / (G * MT)) * G + idx % G][(idx / G) % MT];
-      }
-      __syncthreads();
-      for (int e = tid; e < (RP / G) * 64; e += nthr) {
-        const int c = (e >> 6) * G, l = e & 63;
-        const int idx = rd * RP + c;
-        if (idx >= NA) continue;
-        const int q = (idx / G) % MT, u = u0 + t * UPS + idx / (G * MT);
-        const int m = q * 16 + (l & 15);
-        if (m >= M || u >= u1) continue;
-        const int n0 = u * 16 + 4 * (l >> 4);
-        if constexpr (!SWIGLU) {
-          f32x4 sum = red_s[0][c][l];
-          for (int s = 1; s < nw; ++s) sum += red_s[s][c][l];  // slice order: fixed
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const int n = n0 + k;
-            if (n < a.N) {
-              const float v = a.r ? sum[k] + (float)a.r[(long)m * a.ldr + n] : sum[k];
-              a.y[(long)m * a.ldy + n] = (bf16)v;
-            }
-          }
-        } else {
-          f32x4 sg = red_s[0][c][l], su = red_s[0][c + 1][l];
-          for (int s = 1; s < nw; ++s) { sg += red_s[s][c][l]; su += red_s[s][c + 1][l]; }
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const int n = n0 + k;
-            if (n < a.N) {
-              // gate and up as the bf16 projection stores them, then swiglu_fwd_kernel's expression
-              const float g = (float)(bf16)sg[k], up = (float)(bf16)su[k];
-              a.y[(long)m * a.ldy + n] = (bf16)(g / (1.f + __expf(-g)) * up);
-            }
-          }
-        }
-      }
-      if (rd + 1 < NR || t + 1 < nsteps) __syncthreads();  // red_s is free again before the next sums land
-    }
+    combine_store<TR, MT, SWIGLU, false>(acc, nullptr, a, wk, t, 0, false, wv, lane, nw);
   }
 }
 
-// CUs of the current device (kept per device; it only sizes the grid, no output bit depends on it)
-int cu_count() {
-  static int cached[64];
-  int dev = 0, n = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;
-  if (dev >= 0 && dev < 64 && cached[dev] > 0) return cached[dev];
-  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-  if (dev >= 0 && dev < 64) cached[dev] = n;
-  return n;
-}
-
+// One entry: the checks, the arguments, the launch (N = ldy = I, ldx = ldw = K and no residual: the SwiGLU form)
 template <bool SWIGLU>
-int launch(WideArgs a, void* stream) {
-  const int nk = a.K >> 5;
+int run(const void* x, const void* w, void* y, const void* r, const void* norm_gain, float eps, int M, int N, int K,
+        int64_t ldx, int64_t ldw, int64_t ldy, int64_t ldr, void* stream) {
+  const int rc = sd_gemv_wide_check(x, w, y, r, norm_gain, M, N, K, ldx, ldw, ldy, ldr);
+  if (rc) return rc;
+  const int nk = K >> 5;
   int kpw = (nk + kMaxWaves - 1) / kMaxWaves;  // from K alone: it fixes the summation order
   kpw = (kpw + 1) & ~1;
   if (kpw < 4) kpw = 4;
-  a.kpw = kpw;
-  a.KS = (nk + kpw - 1) / kpw;
-  // grid: from N and the CU count only -- about two workgroups per CU while a workgroup keeps one 16-row unit; the
-  // units a wave takes per step (1, 2 or 4 tiles; 1 or 2 gate/up pairs) follow from what a workgroup got
-  const int cus = cu_count();
-  if (cus <= 0) return SD_ERR_WORKSPACE;
-  const int units = (a.N + 15) >> 4;
-  int upw = (units + 2 * cus - 1) / (2 * cus);
-  const int ups = SWIGLU ? (upw >= 2 ? 2 : 1) : (upw >= 4 ? 4 : upw >= 2 ? 2 : 1);
-  upw = (upw + ups - 1) / ups * ups;
-  a.upw = upw;
-  const int tr = SWIGLU ? 2 * ups : ups, mt = (a.M + 15) >> 4;
-  const unsigned grid = (unsigned)((units + upw - 1) / upw), block = (unsigned)(a.KS * 64);
-  SdProfScope prof(SD_K_GEMM_NT, 2.0 * a.M * (SWIGLU ? 2.0 : 1.0) * a.N * a.K, ST);
+  GemvGrid g;
+  if (!grid_for(N, SWIGLU, g)) return SD_ERR_WORKSPACE;  // from N and the CU count only
+  const WideArgs a = {(const bf16*)x, (const bf16*)w, (const bf16*)r, (const bf16*)norm_gain, (bf16*)y, eps, M, N, K,
+                      ldx, ldw, ldy, ldr, (nk + kpw - 1) / kpw, kpw, g.upw};
+  const int tr = g.tr, mt = (M + 15) >> 4;
+  const unsigned grid = g.grid, block = (unsigned)(a.KS * 64);
+  SdProfScope prof(SD_K_GEMM_NT, 2.0 * M * (SWIGLU ? 2.0 : 1.0) * N * K, ST);
   SD_PROF_LABEL("wide_gemv_kernel<%d, %d, %s>", mt, tr, SWIGLU ? "true" : "false");
 #define SD_GO(MT_, TR_) hipLaunchKernelGGL((wide_gemv_kernel<MT_, TR_, SWIGLU>), dim3(grid), dim3(block), 0, ST, a)
 #define SD_TR(MT_)                                          \
@@ -275,22 +202,10 @@ int launch(WideArgs a, void* stream) {
 
 extern "C" int sd_gemv_wide_bf16(const void* x, const void* w, void* y, const void* r, const void* norm_gain, float eps,
                                  int M, int N, int K, int64_t ldx, int64_t ldw, int64_t ldy, int64_t ldr, void* stream) {
-  const int rc = sd_gemv_wide_check(x, w, y, r, norm_gain, M, N, K, ldx, ldw, ldy, ldr);
-  if (rc) return rc;
-  WideArgs a = {};
-  a.x = (const bf16*)x; a.w = (const bf16*)w; a.r = (const bf16*)r; a.gain = (const bf16*)norm_gain; a.y = (bf16*)y;
-  a.eps = eps; a.M = M; a.N = N; a.K = K;
-  a.ldx = ldx; a.ldw = ldw; a.ldy = ldy; a.ldr = ldr;
-  return launch<false>(a, stream);
+  return run<false>(x, w, y, r, norm_gain, eps, M, N, K, ldx, ldw, ldy, ldr, stream);
 }
 
 extern "C" int sd_gemv_wide_swiglu(const void* x, const void* wgu, void* act, const void* norm_gain, float eps, int M, int I,
                                    int K, void* stream) {
-  const int rc = sd_gemv_wide_check(x, wgu, act, nullptr, norm_gain, M, I, K, K, K, I, 0);
-  if (rc) return rc;
-  WideArgs a = {};
-  a.x = (const bf16*)x; a.w = (const bf16*)wgu; a.gain = (const bf16*)norm_gain; a.y = (bf16*)act;
-  a.eps = eps; a.M = M; a.N = I; a.K = K;
-  a.ldx = K; a.ldw = K; a.ldy = I; a.ldr = 0;
-  return launch<true>(a, stream);
+  return run<true>(x, wgu, act, nullptr, norm_gain, eps, M, I, K, K, K, I, 0, stream);
 }

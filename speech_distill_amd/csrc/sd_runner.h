@@ -64,7 +64,7 @@ struct SdQkv {
 __attribute__((visibility("hidden"))) int sd_gemv_mx_check(const void* x, int64_t ldx, const void* w_q, const void* w_scale,
                                                            const void* y, int64_t ldy, const void* r, int64_t ldr, int M,
                                                            int N, int K);
-// sd_gemv_mx_wide.hip: the same for sd_gemv_mxfp8_wide / _wide_swiglu (M <= SD_GEMV_MX_WIDE_MAX_M).  The entries run them in
+// sd_gemv_mx.hip: the same for sd_gemv_mxfp8_wide / _wide_swiglu (M <= SD_GEMV_MX_WIDE_MAX_M).  The entries run them in
 // front of every launch; the wide MXFP8 decode step asks them for every projection before its first launch.  Internal.
 __attribute__((visibility("hidden"))) int sd_gemv_mx_wide_check(const void* x, int64_t ldx, const void* w_q,
                                                                 const void* w_scale, const void* y, int64_t ldy,

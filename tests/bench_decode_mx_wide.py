@@ -1,5 +1,5 @@
 """GPU measurement (not a pytest): the MXFP8 decode step with gemv_rows=64 (sd_qwen3_mx_decode_step_wide on the 64-row
-block-scaled GEMV of sd_gemv_mx_wide.hip) against the steps the project already has.  Writes
+block-scaled GEMV of sd_gemv_mx.hip) against the steps the project already has.  Writes
 profiles/decode_mx_wide_bench.json.
 
   (a) per token: Decoder.step on the 0.6B student and the 1.7B teacher shape (random weights), B in {16, 32, 64}, context 512,

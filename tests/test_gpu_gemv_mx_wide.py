@@ -1,5 +1,5 @@
 """-m gpu tests of the wide weight-streaming GEMV over MXFP8 weights (include/sd_hip.h "wide weight-streaming GEMV over MXFP8
-weights"; csrc/sd_gemv_mx_wide.hip): sd_gemv_mxfp8_wide and sd_gemv_mxfp8_wide_swiglu for 1 <= M <= 64.
+weights"; gemv_mx_wide_kernel in csrc/sd_gemv_mx.hip): sd_gemv_mxfp8_wide and sd_gemv_mxfp8_wide_swiglu for 1 <= M <= 64.
 
 The order contract is the first oracle: any 16-row slice of a wide call must EQUAL the existing 16-row kernel (sd_gemv_mxfp8)
 on that slice -- the oracle is the old kernel, not the code under test.  Independent of it: exact integers against an fp64

@@ -1,5 +1,5 @@
 """-m gpu: generation on MXFP8 weights with ``gemv_rows=64`` -- the decode step on the 64-row block-scaled GEMV
-(sd_qwen3_mx_decode_step_wide; csrc/sd_gemv_mx_wide.hip, sd_mx.hip, generation.py).
+(sd_qwen3_mx_decode_step_wide; csrc/sd_gemv_mx.hip, sd_mx.hip, generation.py).
 
 Yardsticks: the step's launches composed by hand from the ``ops`` bindings over a cache of the hand's own (logits and
 every cache byte, each cache kind), the same step on one row for the batch invariance, sd_qwen3_mx_decode_step(flags = 0)
