@@ -320,7 +320,9 @@ typedef struct {
   int32_t out_features, in_features;
 } SdLoraTarget;
 int64_t sd_lora_plan_bytes(int n_targets);
-/* Fills `plan_host` (host memory, sd_lora_plan_bytes(n) bytes); the caller copies it to the device once. */
+/* Fills `plan_host` (host memory, sd_lora_plan_bytes(n) bytes); the caller copies it to the device once.  Every target is
+ * judged before the first byte is written: a refused build (a null member or n <= 0: SD_ERR_SHAPE; a member off 16 bytes:
+ * SD_ERR_ALIGN) leaves `plan_host` as it was. */
 int sd_lora_plan_build(const SdLoraTarget* targets, int n_targets, int r_pad, void* plan_host, int64_t plan_bytes);
 int sd_lora_merge(const void* plan_dev, const void* plan_host, void* stream);
 int sd_lora_project(const void* plan_dev, const void* plan_host, void* stream);

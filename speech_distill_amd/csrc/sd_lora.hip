@@ -294,8 +294,7 @@ extern "C" int sd_lora_plan_build(const SdLoraTarget* t, int n, int r_pad, void*
   if (!t || n <= 0 || !plan_host) return SD_ERR_SHAPE;
   if (plan_bytes < sd_lora_plan_bytes(n)) return SD_ERR_WORKSPACE;
   if (r_pad != 32 && r_pad != 64 && r_pad != 128) return SD_ERR_UNSUPPORTED;
-  PlanHeader* h = (PlanHeader*)plan_host;
-  PlanEntry* e = (PlanEntry*)(h + 1);
+  // every target is judged before the first byte of the plan is written: a refused build leaves plan_host as it was
   long merge = 0, db = 0, da = 0;
   for (int i = 0; i < n; ++i) {
     const SdLoraTarget& s = t[i];
@@ -304,6 +303,15 @@ extern "C" int sd_lora_plan_build(const SdLoraTarget* t, int n, int r_pad, void*
     if (((uintptr_t)s.w_res | (uintptr_t)s.w_out | (uintptr_t)s.w_grad | (uintptr_t)s.a_shadow | (uintptr_t)s.a_scaled |
          (uintptr_t)s.b_scaled | (uintptr_t)s.d_a | (uintptr_t)s.d_b) & 15) return SD_ERR_ALIGN;
     if (!s.w_res || !s.w_out || !s.w_grad || !s.a_shadow || !s.a_scaled || !s.b_scaled || !s.d_a || !s.d_b) return SD_ERR_SHAPE;
+    merge += (long)(s.in_features / kColBlock) * ((s.out_features + kMergeRows - 1) / kMergeRows);
+    db += (s.out_features + kDbRows - 1) / kDbRows;
+    if (merge > 0x3fffffffL || db > 0x3fffffffL) return SD_ERR_UNSUPPORTED;
+  }
+  PlanHeader* h = (PlanHeader*)plan_host;
+  PlanEntry* e = (PlanEntry*)(h + 1);
+  merge = db = 0;
+  for (int i = 0; i < n; ++i) {
+    const SdLoraTarget& s = t[i];
     PlanEntry& p = e[i];
     p.w_res = (const bf16*)s.w_res; p.w_out = (bf16*)s.w_out; p.w_grad = (const bf16*)s.w_grad;
     p.a_sh = (const bf16*)s.a_shadow; p.a_scaled = (const bf16*)s.a_scaled; p.b_scaled = (const bf16*)s.b_scaled;
@@ -315,7 +323,6 @@ extern "C" int sd_lora_plan_build(const SdLoraTarget* t, int n, int r_pad, void*
     merge += (long)p.col_blocks * ((s.out_features + kMergeRows - 1) / kMergeRows);
     db += (s.out_features + kDbRows - 1) / kDbRows;
     da += p.col_blocks;
-    if (merge > 0x3fffffffL || db > 0x3fffffffL) return SD_ERR_UNSUPPORTED;
   }
   h->n = n; h->r_pad = r_pad; h->merge_items = (int)merge; h->db_items = (int)db; h->da_items = (int)da;
   h->pad[0] = h->pad[1] = h->pad[2] = 0;
