@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void attn_shared_part_kernel(const bf16* __res
       const int nn = clampi(len[b0 + r] + len_add, 0, lim);
       if (p * kPart < nn) {  // p < max_pages: p * 256 < n <= cap; a row that is not live forms no table address
         n[r] = nn;
-        page[r] = clampi(pg.table[(long)(b0 + r) * pg.max_pages + p], 0, pg.n_pages - 1);
+        page[r] = kv_page(pg, b0 + r, p);
       }
     }
   }
@@ -88,7 +88,6 @@ __global__ __launch_bounds__(256) void attn_shared_part_kernel(const bf16* __res
   if (!first) return;  // block-uniform: an earlier row's workgroup walks this page for row w
   const int lane = lane_id(), j = lane & 15;
   const int sg = (threadIdx.x >> 6) * 4 + (lane >> 4);
-  const int KD = Hkv * 128;
   // the group's queries -> LDS as fp32 (exact), one 16-byte chunk per thread and pass
   for (int c = threadIdx.x; c < H * 16; c += 256) {
     const int h = c >> 4, r = h / G, g = h - r * G;
@@ -112,56 +111,15 @@ __global__ __launch_bounds__(256) void attn_shared_part_kernel(const bf16* __res
   __syncthreads();
   // the one walk of the page
   {
-    const long off = ((long)pw - p) * kPart * KD + hk * 128 + j * 8;  // key = p * 256 + r lands on row r of the page
-    const bf16 *kb = kp + off, *vb = vp + off;
-    const uint8_t *kb8 = (const uint8_t*)kp + off, *vb8 = (const uint8_t*)vp + off;
-    const uint8_t *ksb = nullptr, *vsb = nullptr;
-    if constexpr (MX) {
-      const long so = ((long)pw - p) * kPart * Hkv * 4 + hk * 4;
-      ksb = pg.k_scale + so;
-      vsb = pg.v_scale + so;
-    }
+    const KvPart pt = kv_part<MX>(pg, ((long)pw - p) * kPart, Hkv, hk, j);  // key = p * 256 + r lands on row r of the page
     for (int it = 0; it < 16; it += 4) {
       const int base = p * kPart + it * 16;
       if (base >= nmax) break;  // block-uniform
-      // the trip's 4 key and value rows, loaded and unpacked ONCE for every member row and head
-      float kf[4][8], vf[4][8];
-      {
-        bf16x8 kv[4], vv[4];
-        u32x2 kq[4], vq[4];
-        uint32_t ksd[4], vsd[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int key = base + u * 16 + sg;
-          if constexpr (MX) {
-            kq[u] = vq[u] = u32x2{0u, 0u};
-            ksd[u] = vsd[u] = 0u;
-            if (key < nmax) {
-              kq[u] = *(const u32x2*)(kb8 + (long)key * KD);
-              vq[u] = *(const u32x2*)(vb8 + (long)key * KD);
-              ksd[u] = *(const uint32_t*)(ksb + (long)key * Hkv * 4);
-              vsd[u] = *(const uint32_t*)(vsb + (long)key * Hkv * 4);
-            }
-          } else {
-            kv[u] = zero8();
-            vv[u] = zero8();
-            if (key < nmax) {
-              kv[u] = *(const bf16x8*)(kb + (long)key * KD);
-              vv[u] = *(const bf16x8*)(vb + (long)key * KD);
-            }
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          if constexpr (MX) {
-            unpack8_mx(kq[u], (ksd[u] >> (8 * (j >> 2))) & 255u, kf[u]);
-            unpack8_mx(vq[u], (vsd[u] >> (8 * (j >> 2))) & 255u, vf[u]);
-          } else {
-            unpack8(kv[u], kf[u]);
-            unpack8(vv[u], vf[u]);
-          }
-        }
-      }
+      // the trip's 4 key and value rows, loaded (up to the longest member's length) and unpacked ONCE for every member
+      KvTrip<MX> tr;
+      kv_load_trip(kp, vp, pt, Hkv, base + sg, nmax, tr);
+      KvTripF tf;
+      tf.unpack(tr, j);
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         if (base >= ne[r]) continue;  // block-uniform: the twin's `break` (and every trip of a row outside the set)
@@ -169,44 +127,7 @@ __global__ __launch_bounds__(256) void attn_shared_part_kernel(const bf16* __res
         for (int g = 0; g < G; ++g) {
           const f32x4 q0 = *(const f32x4*)&qs[r * G + g][j * 8], q1 = *(const f32x4*)&qs[r * G + g][j * 8 + 4];
           const float qf[8] = {q0[0], q0[1], q0[2], q0[3], q1[0], q1[1], q1[2], q1[3]};
-          // The head's arithmetic, stated operation by operation with contraction OFF: which multiply-adds of the twin's
-          // loop are fused is the compiler's choice there, and these are the choices it made for the G-head twin
-          // (tests/test_gpu_attn_shared.py holds the two together; DESIGN.md section 11h lists them).
-          {
-#pragma clang fp contract(off)
-            float s[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              float d = __builtin_fmaf(qf[0], kf[u][0], 0.f);  // elements 0..3: one fused chain
-#pragma unroll
-              for (int e = 1; e < 4; ++e) d = __builtin_fmaf(qf[e], kf[u][e], d);
-#pragma unroll
-              for (int e = 4; e < 8; ++e) d = d + qf[e] * kf[u][e];  // elements 4..7: rounded products, added in order
-              d = row16_sum(d);
-              s[u] = base + u * 16 + sg < ne[r] ? d * scale_log2 : -INFINITY;
-            }
-            const float mn = fmaxf(fmaxf(m[r][g], fmaxf(s[0], s[1])), fmaxf(s[2], s[3]));
-            const float c = exp2f(m[r][g] - mn);
-            float pu[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) pu[u] = exp2f(s[u] - mn);  // masked key: exp2(-inf) = 0
-            l[r][g] = ((__builtin_fmaf(l[r][g], c, pu[0]) + pu[1]) + pu[2]) + pu[3];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              float a = acc[r][g][e];
-              if constexpr (G == 1) {
-                a = __builtin_fmaf(c, a, pu[0] * vf[0][e]);
-#pragma unroll
-                for (int u = 1; u < 4; ++u) a = e < 6 ? __builtin_fmaf(pu[u], vf[u][e], a) : a + pu[u] * vf[u][e];
-              } else {
-                a = a * c;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) a = __builtin_fmaf(pu[u], vf[u][e], a);
-              }
-              acc[r][g][e] = a;
-            }
-            m[r][g] = mn;
-          }
+          kv_head_trip<G>(qf, tf, j, base + sg, ne[r], scale_log2, m[r][g], l[r][g], acc[r][g]);  // masks by the row's OWN length
         }
       }
     }
@@ -218,26 +139,12 @@ __global__ __launch_bounds__(256) void attn_shared_part_kernel(const bf16* __res
 #pragma unroll
     for (int rr = 0; rr < CH; ++rr)
 #pragma unroll
-      for (int g = 0; g < G; ++g) {
-        if (j == 0) { sh[sg][rr * G + g][0] = m[r0 + rr][g]; sh[sg][rr * G + g][1] = l[r0 + rr][g]; }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sh[sg][rr * G + g][4 + j * 8 + e] = acc[r0 + rr][g][e];
-      }
+      for (int g = 0; g < G; ++g) kv_group_put(sh, sg, rr * G + g, j, m[r0 + rr][g], l[r0 + rr][g], acc[r0 + rr][g]);
     __syncthreads();
     for (int i = threadIdx.x; i < CH * G * 128; i += 256) {
       const int hh = i >> 7, c = i & 127, rr = hh / G, g = hh - rr * G;
       if (!((members >> (r0 + rr)) & 1u)) continue;
-      float M = sh[0][hh][0];
-      for (int x = 1; x < 16; ++x) M = fmaxf(M, sh[x][hh][0]);
-      float L = 0.f, A = 0.f;
-      for (int x = 0; x < 16; ++x) {  // group order: fixed
-        const float wx = exp2f(sh[x][hh][0] - M);
-        L += sh[x][hh][1] * wx;
-        A += sh[x][hh][4 + c] * wx;
-      }
-      float* rec = ws + (((long)(b0 + r0 + rr) * Hq + hk * G + g) * pstride + p) * kRec;
-      rec[4 + c] = A;
-      if (c == 0) { rec[0] = M; rec[1] = L; }
+      kv_group_merge(sh, hh, c, ws + (((long)(b0 + r0 + rr) * Hq + hk * G + g) * pstride + p) * kRec);
     }
     __syncthreads();
   }

@@ -7,10 +7,9 @@
 //
 // What it replaces here: sd_qknorm_rope_append{,_paged,_paged_mx} followed by sd_attn_decode{,_paged,_paged_mx} with len =
 // pos and len_add = 1 (sd_decode.hip) -- three launches between which q and the partition records make two dependent
-// round trips through memory.  The contract is bit equality with that pair: o, lse and every byte of the cache.  The
-// kernel below therefore holds the three kernels' statements unchanged and in place (they stay as they are: moving their
-// loops into shared functions changed their code, and with it which products become FMAs); the number formats, the page
-// lookup and the constants are the shared ones of sd_kv_dev.cuh.
+// round trips through memory.  The contract is bit equality with that pair: o, lse and every byte of the cache.  It
+// holds because the arithmetic is stated once, with contraction off, in the device functions of sd_kv_dev.cuh that the
+// three kernels and this one call; the number formats, the page lookup and the constants are that file's too.
 //
 // One workgroup = (partition of 256 keys, kv head, sequence), as in attn_decode_part_kernel; written once over the cache
 // kind with that file's trailing pack (empty: contiguous, three arguments: bf16 pages, five: MXFP8 pages).
@@ -38,9 +37,8 @@
 
 namespace {
 
-// The body below holds the statements of qknorm_rope_append_kernel, attn_decode_part_kernel and attn_decode_merge_kernel
-// (sd_decode.hip) UNCHANGED and in their order, written out in place the way those kernels write them: which products the
-// compiler contracts into FMAs depends on the shape of the code around them, and the contract is bit equality.
+// The work of qknorm_rope_append_kernel, attn_decode_part_kernel and attn_decode_merge_kernel (sd_decode.hip) in their
+// order; this kernel holds the control flow, the stores and the ordering, the arithmetic is sd_kv_dev.cuh's.
 // ws: records [B][Hq][pstride][kRec] as attn_decode_part_kernel lays them out; ticket: int32 [B][Hkv], zero on entry,
 // zero again on exit.  kp / vp are read and written by this launch: no __restrict__ on them.
 template <int G, class... PG>
@@ -72,24 +70,8 @@ __global__ __launch_bounds__(256) void cache_step_kernel(const bf16* __restrict_
   if (appender) {  // block-uniform: K (normed, rotated) and the raw V of head hk -> slot pos[b]
     const bf16x8 vraw = *(const bf16x8*)(qkv + (long)b * nh * 128 + (Hq + Hkv + hk) * 128 + j * 8);
     const bf16x8 raw = *(const bf16x8*)(qkv + (long)b * nh * 128 + (Hq + hk) * 128 + j * 8);
-    float f[8], g[8], cs[8], sn[8];
-    unpack8(raw, f);
-    float ss = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) ss += f[e] * f[e];
-    ss = row16_sum(ss);
-    const float rs = rsqrtf(ss * (1.f / 128.f) + eps);
-    unpack8(*(const bf16x8*)(kw + j * 8), g);
-    unpack8(*(const bf16x8*)(cosb + (long)t * 128 + j * 8), cs);
-    unpack8(*(const bf16x8*)(sinb + (long)t * 128 + j * 8), sn);
     float ko[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float n = (float)(bf16)(g[e] * (float)(bf16)(f[e] * rs));  // normed value as HF holds it (bf16)
-      const float pr = row16_xor8(n);
-      const float rot = (j < 8) ? -pr : pr;
-      ko[e] = n * cs[e] + rot * sn[e];
-    }
+    kv_qknorm_rope8(raw, kw, cosb, sinb, t, j, eps, ko);
     bool st = inb && sg == 0;  // one 16-lane group stores the row
     if constexpr (MX) {
       const PageArgs pg{pga...};
@@ -124,135 +106,38 @@ __global__ __launch_bounds__(256) void cache_step_kernel(const bf16* __restrict_
     return;
   }
 
-  // ---- q of the G heads: qknorm_rope_append_kernel's statements, rounded to the bf16 it hands sd_attn_decode
+  // ---- q of the G heads, rounded to the bf16 that qknorm_rope_append_kernel hands sd_attn_decode
   float qf[G][8], m[G], l[G], acc[G][8];
 #pragma unroll
-  for (int gq = 0; gq < G; ++gq) {
-    const bf16x8 raw = *(const bf16x8*)(qkv + (long)b * nh * 128 + (hk * G + gq) * 128 + j * 8);
-    float f[8], g[8], cs[8], sn[8];
-    unpack8(raw, f);
-    float ss = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) ss += f[e] * f[e];
-    ss = row16_sum(ss);
-    const float rs = rsqrtf(ss * (1.f / 128.f) + eps);
-    unpack8(*(const bf16x8*)(qw + j * 8), g);
-    unpack8(*(const bf16x8*)(cosb + (long)t * 128 + j * 8), cs);
-    unpack8(*(const bf16x8*)(sinb + (long)t * 128 + j * 8), sn);
+  for (int g = 0; g < G; ++g) {
     float qo[8];
+    kv_qknorm_rope8(*(const bf16x8*)(qkv + (long)b * nh * 128 + (hk * G + g) * 128 + j * 8), qw, cosb, sinb, t, j, eps, qo);
+    unpack8(pack8(qo), qf[g]);
+    m[g] = kNegBig;
+    l[g] = 0.f;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float n = (float)(bf16)(g[e] * (float)(bf16)(f[e] * rs));  // normed value as HF holds it (bf16)
-      const float pr = row16_xor8(n);
-      const float rot = (j < 8) ? -pr : pr;
-      qo[e] = n * cs[e] + rot * sn[e];
-    }
-    unpack8(pack8(qo), qf[gq]);
-    m[gq] = kNegBig;
-    l[gq] = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) acc[gq][e] = 0.f;
+    for (int e = 0; e < 8; ++e) acc[g][e] = 0.f;
   }
 
-  // ---- attn_decode_part_kernel from here to its record stores
-  long off = (long)b * cap * KD + hk * 128 + j * 8;
-  const uint8_t *ksb = nullptr, *vsb = nullptr;
-  if constexpr (sizeof...(PG) > 0) {
-    const PageArgs pg{pga...};
-    const int page = clampi(pg.table[(long)b * pg.max_pages + p], 0, pg.n_pages - 1);  // p < max_pages: p * 256 < n <= cap
-    off = ((long)page - p) * kPart * KD + hk * 128 + j * 8;  // key = p * 256 + r below lands on row r of the page
-    if constexpr (MX) {
-      const long so = ((long)page - p) * kPart * Hkv * 4 + hk * 4;
-      ksb = pg.k_scale + so;
-      vsb = pg.v_scale + so;
-    }
-  }
-  const bf16* kb = kp + off;
-  const bf16* vb = vp + off;
-  const uint8_t *kb8 = (const uint8_t*)kp + off, *vb8 = (const uint8_t*)vp + off;  // 8-bit pages: one byte per element
+  // ---- the walk of attn_decode_part_kernel, to its record stores
+  const PageArgs pg{pga...};
+  long row0 = (long)b * cap;
+  if constexpr (sizeof...(PG) > 0) row0 = ((long)kv_page(pg, b, p) - p) * kPart;  // p < max_pages: p * 256 < n <= cap
+  const KvPart pt = kv_part<MX>(pg, row0, Hkv, hk, j);
   for (int it = 0; it < 16; it += 4) {
-    if (p * kPart + it * 16 >= n) break;  // block-uniform
-    bf16x8 kv[4], vv[4];
-    u32x2 kq[4], vq[4];
-    uint32_t ksd[4], vsd[4];
-    bool okk[4];
+    const int base = p * kPart + it * 16;
+    if (base >= n) break;  // block-uniform
+    KvTrip<MX> tr;
+    kv_load_trip(kp, vp, pt, Hkv, base + sg, n, tr);
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int key = p * kPart + (it + u) * 16 + sg;
-      okk[u] = key < n;
-      if constexpr (MX) {
-        kq[u] = vq[u] = u32x2{0u, 0u};
-        ksd[u] = vsd[u] = 0u;
-        if (okk[u]) {
-          kq[u] = *(const u32x2*)(kb8 + (long)key * KD);
-          vq[u] = *(const u32x2*)(vb8 + (long)key * KD);
-          ksd[u] = *(const uint32_t*)(ksb + (long)key * Hkv * 4);
-          vsd[u] = *(const uint32_t*)(vsb + (long)key * Hkv * 4);
-        }
-      } else {
-        kv[u] = zero8();
-        vv[u] = zero8();
-        if (okk[u]) {
-          kv[u] = *(const bf16x8*)(kb + (long)key * KD);
-          vv[u] = *(const bf16x8*)(vb + (long)key * KD);
-        }
-      }
-    }
-    float s[G][4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      float kf[8];
-      if constexpr (MX) unpack8_mx(kq[u], (ksd[u] >> (8 * (j >> 2))) & 255u, kf);
-      else unpack8(kv[u], kf);
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        float d = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) d += qf[g][e] * kf[e];
-        d = row16_sum(d);
-        s[g][u] = okk[u] ? d * scale_log2 : -INFINITY;
-      }
-    }
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      const float mn = fmaxf(fmaxf(m[g], fmaxf(s[g][0], s[g][1])), fmaxf(s[g][2], s[g][3]));
-      const float c = exp2f(m[g] - mn);
-      l[g] *= c;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) acc[g][e] *= c;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const float pu = exp2f(s[g][u] - mn);  // masked key: exp2(-inf) = 0
-        float vf[8];
-        if constexpr (MX) unpack8_mx(vq[u], (vsd[u] >> (8 * (j >> 2))) & 255u, vf);
-        else unpack8(vv[u], vf);
-        l[g] += pu;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[g][e] += pu * vf[e];
-      }
-      m[g] = mn;
-    }
+    for (int g = 0; g < G; ++g) kv_head_trip<G>(qf[g], tr, j, base + sg, n, scale_log2, m[g], l[g], acc[g]);
   }
 #pragma unroll
-  for (int g = 0; g < G; ++g) {
-    if (j == 0) { sh[sg][g][0] = m[g]; sh[sg][g][1] = l[g]; }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) sh[sg][g][4 + j * 8 + e] = acc[g][e];
-  }
+  for (int g = 0; g < G; ++g) kv_group_put(sh, sg, g, j, m[g], l[g], acc[g]);
   __syncthreads();
   for (int i = threadIdx.x; i < G * 128; i += 256) {
     const int g = i >> 7, c = i & 127;
-    float M = sh[0][g][0];
-    for (int x = 1; x < 16; ++x) M = fmaxf(M, sh[x][g][0]);
-    float L = 0.f, A = 0.f;
-    for (int x = 0; x < 16; ++x) {  // group order: fixed
-      const float w = exp2f(sh[x][g][0] - M);
-      L += sh[x][g][1] * w;
-      A += sh[x][g][4 + c] * w;
-    }
-    float* rec = ws + (((long)b * Hq + hk * G + g) * pstride + p) * kRec;
-    rec[4 + c] = A;
-    if (c == 0) { rec[0] = M; rec[1] = L; }
+    kv_group_merge(sh, g, c, ws + (((long)b * Hq + hk * G + g) * pstride + p) * kRec);
   }
   // every wave: its record stores have left; then every thread is done with sh, and a record of this workgroup that
   // another of its threads wrote is visible to it (np == 1 reads its own record back below)
@@ -275,21 +160,11 @@ __global__ __launch_bounds__(256) void cache_step_kernel(const bf16* __restrict_
     if (sh[0][0][0] == 0.f) return;  // block-uniform: a later arrival merges
   }
 
-  // ---- attn_decode_merge_kernel's statements, for the G heads of the group (np == 1: over this workgroup's own record)
+  // ---- the partition merge of attn_decode_merge_kernel, for the G heads (np == 1: over this workgroup's own record)
   for (int i = threadIdx.x; i < G * 128; i += 256) {
     const int h = hk * G + (i >> 7), c = i & 127;
-    float M = kNegBig, L = 0.f, A = 0.f;
-    const float* rec = ws + ((long)b * Hq + h) * pstride * kRec;
-    for (int pp = 0; pp < np; ++pp, rec += kRec) {
-      const float mp = rec[0], lp = rec[1], ap = rec[4 + c];
-      const float mn = fmaxf(M, mp);
-      const float c0 = exp2f(M - mn), c1 = exp2f(mp - mn);
-      L = L * c0 + lp * c1;
-      A = A * c0 + ap * c1;
-      M = mn;
-    }
-    o[((long)b * Hq + h) * 128 + c] = (bf16)(np > 0 ? A / L : 0.f);
-    if (lse && c == 0) lse[(long)b * Hq + h] = np > 0 ? (M + log2f(L)) * 0.6931471805599453f : -INFINITY;
+    kv_part_merge(ws + ((long)b * Hq + h) * pstride * kRec, np, c, o + ((long)b * Hq + h) * 128,
+                  lse ? lse + (long)b * Hq + h : nullptr);
   }
   // every ticket of this (b, hk) has been drawn: back to zero for the next launch on these tickets
   if (np > 1 && threadIdx.x == 0)

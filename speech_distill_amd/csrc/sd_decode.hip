@@ -26,7 +26,7 @@
 #include <stdlib.h>
 #include "sd_common.cuh"
 #include "../../include/sd_hip.h"
-#include "sd_kv_dev.cuh"  // the partition constants, the page and 8-bit helpers: shared with sd_cache_step.hip
+#include "sd_kv_dev.cuh"  // the partition constants, the page and 8-bit helpers, the cache step's arithmetic
 #include "sd_prof.h"
 #include "sd_runner.h"
 
@@ -135,12 +135,10 @@ __global__ void last_rows_kernel(const int32_t* __restrict__ kv_len, int64_t* __
 }
 
 // ------------------------------------------------------------------------------- q/k norm + RoPE + append (decode)
-// The arithmetic of qknorm_rope_fwd_kernel (sd_elementwise.hip), statement for statement, for ONE token per sequence
-// whose position is pos[b]: q goes to q_out, k and the raw v into cache slot pos[b].  A head vector of 128 bf16 is owned
-// by 16 lanes; every lane runs the norm / rotation (the DPP row operations want whole rows active), the head kind only
-// picks the store.
-// (cache_step_kernel in sd_cache_step.hip holds these statements a second time and is held bit for bit against this
-// kernel: mirror any edit there.)
+// The arithmetic of qknorm_rope_fwd_kernel (sd_elementwise.hip) for ONE token per sequence whose position is pos[b]
+// (kv_qknorm_rope8 in sd_kv_dev.cuh, shared with cache_step_kernel): q goes to q_out, k and the raw v into cache slot
+// pos[b].  A head vector of 128 bf16 is owned by 16 lanes; every lane runs the norm / rotation (the DPP row operations
+// want whole rows active), the head kind only picks the store.
 template <class... PG>
 __global__ __launch_bounds__(256) void qknorm_rope_append_kernel(const bf16* __restrict__ qkv, const bf16* __restrict__ qw,
                                                                  const bf16* __restrict__ kw, const bf16* __restrict__ cosb,
@@ -160,24 +158,8 @@ __global__ __launch_bounds__(256) void qknorm_rope_append_kernel(const bf16* __r
   bool inb = p >= 0 && p < cap;
   const int t = clampi(p, 0, cap - 1);
   const bf16x8 raw = *(const bf16x8*)(qkv + (long)b * nh * 128 + hh * 128 + j * 8);
-  float f[8], g[8], cs[8], sn[8];
-  unpack8(raw, f);
-  float ss = 0.f;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) ss += f[e] * f[e];
-  ss = row16_sum(ss);
-  const float rs = rsqrtf(ss * (1.f / 128.f) + eps);
-  unpack8(*(const bf16x8*)((hh < Hq ? qw : kw) + j * 8), g);
-  unpack8(*(const bf16x8*)(cosb + (long)t * 128 + j * 8), cs);
-  unpack8(*(const bf16x8*)(sinb + (long)t * 128 + j * 8), sn);
   float o[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float n = (float)(bf16)(g[e] * (float)(bf16)(f[e] * rs));  // normed value as HF holds it (bf16)
-    const float pr = row16_xor8(n);
-    const float rot = (j < 8) ? -pr : pr;
-    o[e] = n * cs[e] + rot * sn[e];
-  }
+  kv_qknorm_rope8(raw, hh < Hq ? qw : kw, cosb, sinb, t, j, eps, o);
   if (!ok) return;
   long slot = ((long)b * cap + t) * (Hkv * 128);
   if constexpr (sizeof...(PG) == 5) {  // 8-bit pages: q as ever; the bf16 K and V the paged twin stores, quantised
@@ -207,7 +189,8 @@ __global__ __launch_bounds__(256) void qknorm_rope_append_kernel(const bf16* __r
 // columns a lane owns stay in registers per group, and the 16 group states are merged in group order through LDS.
 // Keys >= n are never loaded and get probability exactly 0.
 // Paged: the partition IS a page; the workgroup reads table[b][p] once (uniform: a scalar load), after the early exit.
-// (cache_step_kernel in sd_cache_step.hip holds this body a second time, bit for bit: mirror any edit there.)
+// The loads, the per-head arithmetic and the group merge are the device functions of sd_kv_dev.cuh, shared with
+// cache_step_kernel and attn_shared_part_kernel.
 template <int G, class... PG>
 __global__ __launch_bounds__(256) void attn_decode_part_kernel(const bf16* __restrict__ q, const bf16* __restrict__ kp,
                                                                const bf16* __restrict__ vp, float* __restrict__ ws,
@@ -220,7 +203,6 @@ __global__ __launch_bounds__(256) void attn_decode_part_kernel(const bf16* __res
   if (p * kPart >= n) return;  // block-uniform: this partition holds no visible key
   const int lane = lane_id(), j = lane & 15;
   const int sg = (threadIdx.x >> 6) * 4 + (lane >> 4);
-  const int KD = Hkv * 128;
   float qf[G][8], m[G], l[G], acc[G][8];
 #pragma unroll
   for (int g = 0; g < G; ++g) {
@@ -230,131 +212,38 @@ __global__ __launch_bounds__(256) void attn_decode_part_kernel(const bf16* __res
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[g][e] = 0.f;
   }
-  // 8-bit pages (five pack arguments): a row is 8 bytes per lane plus the dword of the head's four block scales, the
-  // same address for the 16 lanes of the group; lane j's block is j >> 2.  Everything after the unpack is shared.
-  constexpr bool MX = sizeof...(PG) == 5;
-  long off = (long)b * cap * KD + hk * 128 + j * 8;
-  const uint8_t *ksb = nullptr, *vsb = nullptr;
-  if constexpr (sizeof...(PG) > 0) {
-    const PageArgs pg{pga...};
-    const int page = clampi(pg.table[(long)b * pg.max_pages + p], 0, pg.n_pages - 1);  // p < max_pages: p * 256 < n <= cap
-    off = ((long)page - p) * kPart * KD + hk * 128 + j * 8;  // key = p * 256 + r below lands on row r of the page
-    if constexpr (MX) {
-      const long so = ((long)page - p) * kPart * Hkv * 4 + hk * 4;
-      ksb = pg.k_scale + so;
-      vsb = pg.v_scale + so;
-    }
-  }
-  const bf16* kb = kp + off;
-  const bf16* vb = vp + off;
-  const uint8_t *kb8 = (const uint8_t*)kp + off, *vb8 = (const uint8_t*)vp + off;  // 8-bit pages: one byte per element
+  constexpr bool MX = sizeof...(PG) == 5;  // 8-bit pages: five pack arguments
+  const PageArgs pg{pga...};
+  long row0 = (long)b * cap;
+  if constexpr (sizeof...(PG) > 0) row0 = ((long)kv_page(pg, b, p) - p) * kPart;  // p < max_pages: p * 256 < n <= cap
+  const KvPart pt = kv_part<MX>(pg, row0, Hkv, hk, j);
   for (int it = 0; it < 16; it += 4) {
-    if (p * kPart + it * 16 >= n) break;  // block-uniform
-    bf16x8 kv[4], vv[4];
-    u32x2 kq[4], vq[4];
-    uint32_t ksd[4], vsd[4];
-    bool okk[4];
+    const int base = p * kPart + it * 16;
+    if (base >= n) break;  // block-uniform
+    KvTrip<MX> tr;
+    kv_load_trip(kp, vp, pt, Hkv, base + sg, n, tr);
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int key = p * kPart + (it + u) * 16 + sg;
-      okk[u] = key < n;
-      if constexpr (MX) {
-        kq[u] = vq[u] = u32x2{0u, 0u};
-        ksd[u] = vsd[u] = 0u;
-        if (okk[u]) {
-          kq[u] = *(const u32x2*)(kb8 + (long)key * KD);
-          vq[u] = *(const u32x2*)(vb8 + (long)key * KD);
-          ksd[u] = *(const uint32_t*)(ksb + (long)key * Hkv * 4);
-          vsd[u] = *(const uint32_t*)(vsb + (long)key * Hkv * 4);
-        }
-      } else {
-        kv[u] = zero8();
-        vv[u] = zero8();
-        if (okk[u]) {
-          kv[u] = *(const bf16x8*)(kb + (long)key * KD);
-          vv[u] = *(const bf16x8*)(vb + (long)key * KD);
-        }
-      }
-    }
-    float s[G][4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      float kf[8];
-      if constexpr (MX) unpack8_mx(kq[u], (ksd[u] >> (8 * (j >> 2))) & 255u, kf);
-      else unpack8(kv[u], kf);
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        float d = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) d += qf[g][e] * kf[e];
-        d = row16_sum(d);
-        s[g][u] = okk[u] ? d * scale_log2 : -INFINITY;
-      }
-    }
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      const float mn = fmaxf(fmaxf(m[g], fmaxf(s[g][0], s[g][1])), fmaxf(s[g][2], s[g][3]));
-      const float c = exp2f(m[g] - mn);
-      l[g] *= c;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) acc[g][e] *= c;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const float pu = exp2f(s[g][u] - mn);  // masked key: exp2(-inf) = 0
-        float vf[8];
-        if constexpr (MX) unpack8_mx(vq[u], (vsd[u] >> (8 * (j >> 2))) & 255u, vf);
-        else unpack8(vv[u], vf);
-        l[g] += pu;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc[g][e] += pu * vf[e];
-      }
-      m[g] = mn;
-    }
+    for (int g = 0; g < G; ++g) kv_head_trip<G>(qf[g], tr, j, base + sg, n, scale_log2, m[g], l[g], acc[g]);
   }
 #pragma unroll
-  for (int g = 0; g < G; ++g) {
-    if (j == 0) { sh[sg][g][0] = m[g]; sh[sg][g][1] = l[g]; }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) sh[sg][g][4 + j * 8 + e] = acc[g][e];
-  }
+  for (int g = 0; g < G; ++g) kv_group_put(sh, sg, g, j, m[g], l[g], acc[g]);
   __syncthreads();
   for (int i = threadIdx.x; i < G * 128; i += 256) {
     const int g = i >> 7, c = i & 127;
-    float M = sh[0][g][0];
-    for (int x = 1; x < 16; ++x) M = fmaxf(M, sh[x][g][0]);
-    float L = 0.f, A = 0.f;
-    for (int x = 0; x < 16; ++x) {  // group order: fixed
-      const float w = exp2f(sh[x][g][0] - M);
-      L += sh[x][g][1] * w;
-      A += sh[x][g][4 + c] * w;
-    }
-    float* rec = ws + (((long)b * Hq + hk * G + g) * pstride + p) * kRec;
-    rec[4 + c] = A;
-    if (c == 0) { rec[0] = M; rec[1] = L; }
+    kv_group_merge(sh, g, c, ws + (((long)b * Hq + hk * G + g) * pstride + p) * kRec);
   }
 }
 
 // Phase 2.  One workgroup per (query head, sequence), one thread per output column: the partitions [0, ceil(n/256)) are
-// merged in increasing index order.  n == 0: a zero row, LSE = -inf.
-// (cache_step_kernel in sd_cache_step.hip holds these statements a second time, bit for bit: mirror any edit there.)
+// merged in increasing index order (kv_part_merge, shared with cache_step_kernel).  n == 0: a zero row, LSE = -inf.
 __global__ __launch_bounds__(128) void attn_decode_merge_kernel(const float* __restrict__ ws, bf16* __restrict__ o,
                                                                 float* __restrict__ lse, const int32_t* __restrict__ len,
                                                                 int len_add, int cap, int max_len, int Hq, int pstride) {
   const int h = blockIdx.x, b = blockIdx.y, c = threadIdx.x;
   const int n = clampi(len[b] + len_add, 0, cap < max_len ? cap : max_len);
   const int np = (n + kPart - 1) / kPart;
-  float M = kNegBig, L = 0.f, A = 0.f;
-  const float* rec = ws + ((long)b * Hq + h) * pstride * kRec;
-  for (int p = 0; p < np; ++p, rec += kRec) {
-    const float mp = rec[0], lp = rec[1], ap = rec[4 + c];
-    const float mn = fmaxf(M, mp);
-    const float c0 = exp2f(M - mn), c1 = exp2f(mp - mn);
-    L = L * c0 + lp * c1;
-    A = A * c0 + ap * c1;
-    M = mn;
-  }
-  o[((long)b * Hq + h) * 128 + c] = (bf16)(np > 0 ? A / L : 0.f);
-  if (lse && c == 0) lse[(long)b * Hq + h] = np > 0 ? (M + log2f(L)) * 0.6931471805599453f : -INFINITY;
+  kv_part_merge(ws + ((long)b * Hq + h) * pstride * kRec, np, c, o + ((long)b * Hq + h) * 128,
+                lse ? lse + (long)b * Hq + h : nullptr);
 }
 
 // --------------------------------------------------------------------------------------------------------- sampler
