@@ -93,16 +93,23 @@ def test_in_kernel_quantiser_equals_the_reference_rule(ops, M, K):
     assert torch.equal(got.float().cpu(), want), f"{int((got.float().cpu() != want).sum())} elements differ"
 
 
+@pytest.mark.parametrize("M,wide", [(5, False), (16, False), (33, True)])
+def test_in_kernel_quantiser_on_the_ratio_sweep(ops, M, wide):
+    """The same identity-weight probe on the deterministic edge rows of mx_ref (fixed blocks, then the ratio sweep: every
+    bf16 mantissa at every exponent below block maxima from the smallest bf16 subnormal to the top exponent -- every tie,
+    the saturating band, e4m3 subnormals, scale byte 0), M rows per call, on the 16-row kernel and (M = 33) the wide one."""
+    x = mx_ref.edge_matrix(4, mx_ref.sweep_blocks())
+    K = x.shape[1]
+    wq = to_dev(torch.eye(K).to(torch.float8_e4m3fn).view(torch.uint8))
+    ws = to_dev(torch.full((K, K // 32), 127, dtype=torch.uint8))
+    want = mx_ref.mx_deq(*mx_ref.mx_quant(x.float()))
+    assert torch.equal(want.bfloat16().float(), want)
+    got = torch.cat([ops.gemv_mxfp8(to_dev(x[r:r + M]), wq, ws, wide=wide) for r in range(0, x.shape[0], M)]).float().cpu()
+    bad = ~(got == want)
+    assert not bool(bad.any()), f"{int(bad.sum())} elements differ, first at {bad.nonzero()[0].tolist()}"
+
+
 # ------------------------------------------------------------------------------------------------ 3: norm and residual
-def _bf16_neighbours(ref):
-    """The correctly rounded bf16 of an fp64 tensor and its two bf16 neighbours, as fp64."""
-    c = ref.float().bfloat16()
-    bits = c.view(torch.int16).to(torch.int32)
-    up = (bits + 1).to(torch.int16).view(torch.bfloat16)
-    down = (bits - 1).to(torch.int16).view(torch.bfloat16)
-    return c.double(), up.double(), down.double()
-
-
 @pytest.mark.parametrize("M,N,K", [(3, 37, 384), (9, 160, 2048), (16, 17, 6144)])
 def test_norm_and_residual_within_one_bf16_ulp(ops, M, N, K):
     """Exact-integer weights, so acc is exact; x is integers too, rstd comes from the existing ops.mxfp8_quant.  Reference
@@ -119,7 +126,7 @@ def test_norm_and_residual_within_one_bf16_ulp(ops, M, N, K):
         ref = rstd.cpu().double()[:, None] * acc + (0 if res is None else res.double())
         got = ops.gemv_mxfp8(to_dev(x), to_dev(wq), to_dev(ws), residual=None if res is None else to_dev(res), norm=True,
                              eps=1e-6).cpu().double()
-        c, up, down = _bf16_neighbours(ref)
+        c, up, down = mx_ref.bf16_neighbours(ref)
         ok = (got == c) | (got == up) | (got == down)
         assert bool(ok.all()), f"{int((~ok).sum())} of {ok.numel()} elements are further than one bf16 ulp away"
 

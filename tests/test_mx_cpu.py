@@ -177,3 +177,89 @@ def test_isa_of_the_mx_kernels():
         at = txt.index(".name:           " + name)
         vg = re.search(r"\.vgpr_count:\s+(\d+)", txt[at:at + 600])
         assert int(vg.group(1)) <= 256, (name, vg.group(1))
+
+
+# ------------------------------------------------------------------------------------------------ edge data of the kernel tests
+def test_mx_ref_equals_the_fp64_restatement_on_every_bf16_pattern():
+    """mx_ref.mx_quant (torch's e4m3 cast, fp32 frexp / ldexp) against mx_ref.mx_quant_fp64 (explicit step 2^(max(floor(log2
+    |y|), -6) - 3), half to even) on all 65,280 finite bf16 patterns and on the ratio sweep: scale bytes equal, every
+    dequantised value equal; the patterns' scale bytes span 0..246."""
+    for x in (mx_ref.all_bf16_blocks(), mx_ref.sweep_blocks()):  # [blocks, 32]: one block per row
+        q, s = mx_ref.mx_quant(x.float())
+        s64, v64, _ = mx_ref.mx_quant_fp64(x)
+        assert torch.equal(s, s64)
+        d = mx_ref.mx_deq(q, s)
+        assert bool((d.double() == v64).all()), int((d.double() != v64).sum())
+        assert torch.equal(d.bfloat16().float(), d)  # every MX value is a bf16 number, subnormal ones included
+    assert mx_ref.all_bf16_blocks().shape == (2040, 32)
+    s = mx_ref.mx_quant(mx_ref.all_bf16_blocks().float())[1]
+    assert int(s.min()) == 0 and int(s.max()) == 246
+    bits = mx_ref.all_bf16_blocks().view(torch.int16).to(torch.int32).flatten() & 0xFFFF
+    assert torch.equal(bits, torch.cat([torch.arange(0, 0x7F80), torch.arange(0x8000, 0xFF80)]).to(torch.int32))
+
+
+def test_ratio_sweep_reaches_every_code_every_tie_and_every_edge():
+    """The sweep holds an element that quantises to each of the 254 finite e4m3 codes, exact ties that round up and ties that
+    round down, scaled values in the saturating band (448, 512), e4m3-subnormal results, flushes to zero, blocks of the
+    bf16-subnormal range (scale byte 0), of the top exponent (246) and with amax an exact power of two; edge_matrix lays
+    it out with the fixed blocks in front."""
+    sw = mx_ref.sweep_blocks()
+    assert bool(sw.float().isfinite().all()) and torch.equal(sw[:, 0].double().unique(), mx_ref.sweep_maxima().unique())
+    assert bool((sw.float().abs() <= sw[:, :1].float()).all())  # element 0 is the block's maximum
+    q, s = mx_ref.mx_quant(sw.float())
+    codes = set(q.view(torch.uint8).flatten().tolist())
+    assert codes == set(range(256)) - {0x7F, 0xFF}
+    _, _, tie = mx_ref.mx_quant_fp64(sw)
+    assert int((tie > 0).sum()) > 0 and int((tie < 0).sum()) > 0
+    y = torch.ldexp(sw.double(), -(s.to(torch.int32) - 127)).abs()
+    assert bool(((y > 448) & (y < 512)).any())
+    d = q.to(torch.float32).abs()
+    assert bool(((d > 0) & (d < 2.0 ** -6)).any()) and bool(((d == 0) & (sw.float() != 0)).any())
+    assert int(s.min()) == 0 and int(s.max()) == 246 and bool((s == 0).sum() > 3)
+    assert {127 - 8, 127 + 100 - 8} <= set(s.flatten().tolist())
+    x = mx_ref.edge_matrix(4)
+    assert x.dtype == torch.bfloat16 and x.shape[1] == 512 and bool(x.float().isfinite().all())
+    assert not x[0].any() and not x[3].any() and not x[1, 32:64].any() and bool(x[1, :32].any())
+    assert torch.equal(x[2, 0:2].float(), torch.tensor([448.0 * 2.0 ** -15, -448.0 * 2.0 ** -15]))
+    body = torch.cat([sw, mx_ref.all_bf16_blocks()])
+    assert torch.equal(x[4:].reshape(-1, 32)[:body.shape[0]].view(torch.int16), body.view(torch.int16))
+
+
+def test_gemm_probes_are_single_exact_products():
+    """The one-hot probes of tests/test_gpu_mx_kernels.py: every output is at most one non-zero product, the stated results
+    equal the fp64 matmul of the dequantised operands, and over the runs the probed A scale bytes cover 0..254 while the
+    exponent sums reach both ends of [-100, 100]."""
+    sas, ts = set(), set()
+    probes = [mx_ref.code_table_probe(r) for r in range(mx_ref.CODE_TABLE_RUNS)]
+    for p in probes:
+        sas |= set(p[5].tolist())
+        ts |= set(p[6].tolist())
+        assert set(p[0][p[0] != 0].tolist()) == set(range(256)) - {0, 0x7F, 0xFF}  # -0 (0x80) is placed; byte 0 is the fill
+        at = p[0] == 0x80
+        assert int(at.sum()) == 1 and not p[1][at.any(1)].any() and not p[4][at.any(1)].any()  # its row: scale bytes 0, C == 0
+    assert sas == set(range(255)) and min(ts) == -100 and max(ts) == 100
+    for aq, as_, bq, bs, want in [p[:5] for p in probes] + [mx_ref.position_probe(K) for K in (128, 384)]:
+        terms = (aq & 0x7F != 0).double() @ (bq & 0x7F != 0).double().T
+        assert float(terms.max()) == 1
+        ref = mx_ref.mx_deq(aq, as_, torch.float64) @ mx_ref.mx_deq(bq, bs, torch.float64).T
+        assert bool((ref == want.double()).all())
+        nz = want.float()[want != 0].abs()
+        assert float(nz.min()) >= 2.0 ** -126  # normal bf16 numbers
+    for aq, as_, bq, bs, want in (mx_ref.position_probe(K) for K in (128, 384)):
+        for row in as_.tolist():
+            assert len(set(row)) == len(row)  # a scale taken from another block of the row is another scale
+
+
+def test_swiglu_probe_is_exact_and_has_its_zero_blocks():
+    """act of mx_ref.swiglu_probe: both kinds of gate in every block, one all-negative-gate (zero) block in every row,
+    negative up values, and an MXFP8 image with a zero scale byte and several others."""
+    for M, I, K, scaled in ((1, 128, 128, False), (130, 384, 384, True)):
+        aq, as_, wq, ws, rs, act = mx_ref.swiglu_probe(M, I, K, scaled)
+        blk = act.view(M, I // 32, 32)
+        zero = (blk == 0).all(-1)
+        assert bool(zero.any(-1).all()) and bool((~zero).any(-1).all())
+        assert bool((blk[~zero] != 0).any(-1).all()) and bool((blk == 0).any(-1).all())
+        assert bool((act < 0).any()) and bool((act > 0).any())
+        q, s = mx_ref.mx_quant(act.float())
+        assert torch.equal(s == 0, zero) and s.unique().numel() >= 3
+        assert (rs is None) == (not scaled)
