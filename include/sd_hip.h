@@ -274,6 +274,30 @@ int sd_kdloss_bwd_rows(const void* student_logits, const void* teacher_logits, c
                        const int64_t* row_labels, const void* row_stats, const float* loss_out, const float* grad_total,
                        void* grad_logits, int R, int V, int K, float temperature, float alpha, int dtype, void* stream);
 
+/* ---- on-policy (generalised) distillation: reverse KL and the beta-skewed Jensen-Shannon divergence on selected rows.
+ * With q = softmax(s/T), p = softmax(t/T) per row, the row's divergence D is
+ *   SD_DIV_REVERSE_KL: KL(q || p);      SD_DIV_JSD: beta KL(p || m) + (1 - beta) KL(q || m),  m = (1 - beta) q + beta p
+ * (TRL's generalized_jsd_loss for 0 < beta < 1; its beta = 0 / 1 are the forward KL of sd_kdloss_* / SD_DIV_REVERSE_KL).
+ * student_logits, teacher_logits [R,V] (bf16 or fp32 per `dtype`, the teacher dense) whose rows the caller already
+ * shifted and selected; row_labels int64 [R], -100 or a value outside [0, V) masks a row (stats zero, gradient exactly
+ * zero).  loss_out fp32[8] = {total, task, distill, teacher, N, N, 0, 0}: distill = T^2 mean D, task = mean CE of the
+ * student, total = alpha task + (1 - alpha) distill, teacher = mean CE of the teacher; all zero when no row is valid.
+ * row_stats: scratch of sd_gjsd_stats_bytes(R) kept from fwd to bwd; a row's stats do not depend on the other rows.
+ * grad_total fp32 [1] nullable (= 1); grad_logits may alias student_logits; beta is ignored by SD_DIV_REVERSE_KL.
+ * fp32 arithmetic, fixed reduction order.  Before any launch: R or V <= 0 or a NULL student / labels / stats / loss_out /
+ * grad_logits, temperature not in (0, inf), SD_DIV_JSD with beta outside (0, 1) (NaN included) SD_ERR_SHAPE; a NULL
+ * teacher SD_ERR_NO_TEACHER; V % 8 != 0 or a logits / gradient pointer off 16 bytes SD_ERR_ALIGN; an unknown mode or
+ * dtype SD_ERR_UNSUPPORTED. */
+#define SD_DIV_REVERSE_KL 1
+#define SD_DIV_JSD 2
+int64_t sd_gjsd_stats_bytes(int R);
+int sd_gjsd_fwd_rows(const void* student_logits, const void* teacher_logits, const int64_t* row_labels, void* row_stats,
+                     float* loss_out, int R, int V, float temperature, float alpha, float beta, int mode, int dtype,
+                     void* stream);
+int sd_gjsd_bwd_rows(const void* student_logits, const void* teacher_logits, const int64_t* row_labels,
+                     const void* row_stats, const float* loss_out, const float* grad_total, void* grad_logits, int R, int V,
+                     float temperature, float alpha, float beta, int mode, int dtype, void* stream);
+
 /* ---- causal-LM cross-entropy on selected rows: the Stage-1 loss (stage1.py: TRL SFTTrainer over HF
  * Qwen3ForCausalLM(labels=...), i.e. HF ForCausalLMLoss -- shift by one, ignore_index -100, reduction "sum" divided by
  * num_items_in_batch when the Trainer passes it, else the mean over valid rows).  Teacher-free counterpart of

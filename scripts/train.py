@@ -17,7 +17,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def parse_args():
+def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--teacher_model", default=None)           # train.py:432-437
     p.add_argument("--student_model", default=None)           # train.py:438-443
@@ -86,9 +86,38 @@ def parse_args():
     p.add_argument("--recompute", default="auto", choices=["auto", "always", "never"],
                    help="(+) what gradient checkpointing (on, as in train.py:512-517) does: layer recompute always, never, "
                         "or only when the activations would take more than a quarter of HBM")
+    # (+) on-policy (generalised) distillation; the defaults are the reference's loop
+    p.add_argument("--divergence", choices=("forward_kl", "reverse_kl", "jsd"), default="forward_kl",
+                   help="(+) the distillation term: forward KL (the reference), reverse KL, or the beta-skewed Jensen-Shannon "
+                        "divergence; the last two need the dense teacher (--top_k 0)")
+    p.add_argument("--beta", type=float, default=0.5, help="(+) skew of --divergence jsd, in (0, 1)")
+    p.add_argument("--lmbda", type=float, default=0.0,
+                   help="(+) probability that a training micro-batch is made on-policy (the student's own sampled completion)")
+    p.add_argument("--on_policy_max_new_tokens", type=int, default=256)
+    p.add_argument("--on_policy_temperature", type=float, default=1.0)
+    p.add_argument("--on_policy_top_k", type=int, default=0)
+    p.add_argument("--on_policy_decode_kernels", choices=("tile", "skinny", "wide"), default="tile")
     p.add_argument("--log_json", default=None, help="(+) write trainer.state.log_history there (rank 0; every rank if the "
                    "path contains {rank})")
-    return p.parse_args()
+    return p.parse_args(argv)
+
+
+def distill_kwargs(cfg, pad=None):
+    """The DistillationTrainer keywords of the (+) on-policy flags: only what differs from the trainer's defaults, so the
+    default command line constructs the trainer exactly as before.  Exits when the flags cannot work together."""
+    if cfg.divergence != "forward_kl" and cfg.top_k > 0 and not (cfg.load_teacher_in_4bit or cfg.load_teacher_in_8bit):
+        raise SystemExit(f"--divergence {cfg.divergence} needs the dense teacher distribution: pass --top_k 0 "
+                         f"(got --top_k {cfg.top_k}; a top-K teacher defines it on K entries only)")
+    kw = {}
+    if cfg.divergence != "forward_kl":
+        kw.update(divergence=cfg.divergence, beta=cfg.beta)
+    if cfg.lmbda > 0:
+        gen = dict(max_new_tokens=cfg.on_policy_max_new_tokens, temperature=cfg.on_policy_temperature,
+                   top_k=cfg.on_policy_top_k, decode_kernels=cfg.on_policy_decode_kernels)
+        if pad is not None:   # the dataset's rows end with the pad token (= <|semantic_token_end|>): it ends a rollout too
+            gen.update(eos_token_id=pad, pad_token_id=pad)
+        kw.update(lmbda=cfg.lmbda, on_policy_generate=gen)
+    return kw
 
 
 class _BosTok:
@@ -116,6 +145,7 @@ def build_models(cfg, dev):
 
 def main():
     cfg = parse_args()
+    distill_kwargs(cfg)                                # (+) refuse flags that cannot work together before anything is built
     from transformers import TrainingArguments
     import speech_distill_amd as sda
     from speech_distill_amd.collator import ProcessedDataCollator
@@ -190,7 +220,8 @@ def main():
     trainer = DistillationTrainer(model=student, args=args, train_dataset=dataset, eval_dataset=eval_dataset,
                                   data_collator=ProcessedDataCollator(tokenizer, speech_bos=cfg.speech_bos, pad_token_id=pad),
                                   teacher_model=teacher, temperature=cfg.temperature, alpha=cfg.alpha, top_k=cfg.top_k,
-                                  is_quantized_teacher=cfg.load_teacher_in_4bit or cfg.load_teacher_in_8bit)
+                                  is_quantized_teacher=cfg.load_teacher_in_4bit or cfg.load_teacher_in_8bit,
+                                  **distill_kwargs(cfg, pad))
     t0 = time.time()
     if os.environ.get("SD_PROFILE_HOST"):              # (+) where the host spends its time: cProfile, top of cumulative
         import cProfile

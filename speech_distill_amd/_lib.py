@@ -175,6 +175,9 @@ PROTOTYPES = {
     "sd_gemm_odx_delta": (_i, [_vp, _vp, _vp, _vp, _i64, _vp, _i, _i, _i, _i, _vp]),
     "sd_kdloss_fwd_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp]),
     "sd_kdloss_bwd_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp]),
+    "sd_gjsd_stats_bytes": (_i64, [_i]),
+    "sd_gjsd_fwd_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _i, _i, _vp]),
+    "sd_gjsd_bwd_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _i, _i, _vp]),
     "sd_rows_scatter": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "sd_loss_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "sd_rmsnorm_bwd_partial_rows": (_i, [_i, _i]),

@@ -656,3 +656,302 @@ extern "C" int sd_loss_rows(const int64_t* labels, const int64_t* speech_mask, c
   SD_CHECK_LAUNCH();
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------- reverse KL / skewed JSD
+// On-policy (generalised) distillation: divergences that do not force the student to cover every teacher mode.  With
+// q = softmax(s/T), p = softmax(t/T) per selected row:
+//   SD_DIV_REVERSE_KL  D = KL(q || p) = sum q (log q - log p)
+//   SD_DIV_JSD         m = (1-b) q + b p,  D = b KL(p || m) + (1-b) KL(q || m),  0 < b < 1
+//   d total / d s_j = [ a (softmax(s)_j - e_y) + (1-a) T q_j (g_j - c) ] / N,   c = sum_v q_v g_v
+//     reverse KL: g_j = log q_j - log p_j (c = D);   JSD: g_j = (1-b)(log q_j - log m_j) (c = (1-b) KL(q || m))
+// Unlike the forward KL of kd_fwd_kernel, no term can be formed before BOTH normalisers are known (log q and log p sit
+// inside the sum), so the forward is one kernel that sweeps the row pair twice: sweep 1 is kd_fwd_kernel's dense sweep
+// (online max / sum-exp of s at 1 and T, of t at 1 and T), sweep 2 forms the divergence terms.  One workgroup owns the pair,
+// so the 2 x V x sizeof(T) bytes of sweep 2 (638 KB at V = 159 488 bf16) were read by this same workgroup microseconds
+// before, where a second launch would re-read 0.98 GB behind a full grid.  With 512 row pairs in flight (327 MB, more than
+// the Infinity Cache) only part of sweep 2 is served on-die: measured, it costs 0.7 x of an HBM sweep.
+// Same streaming as kd_fwd_kernel (512 threads, PF chunks in flight per thread, unconditional loads with the clamped
+// re-read of the last chunk, exp2, the T == 2 squaring).  Transcendentals per logit pair:
+// sweep 1: 2 at T == 2, else 4; sweep 2: reverse KL 1 (exp), JSD 3 (exp, exp, log); backward: one more exp for
+// softmax(s) unless T == 2, where softmax(s)_j = q_j^2 exp(2 lseT - lse1).
+// 0 log 0 = 0: an element whose q (or p) underflows contributes 0 -- guarded by a select, not by a log-domain logaddexp;
+// m is clamped at FLT_MIN before its log (v_log_f32 takes no denormal), which moves a term of weight < 1e-37 by < 1e-36.
+namespace {
+
+// Every log-normaliser is kept as (row maximum, log of the max-subtracted sum) and applied as (x - max) / T - log sum:
+// the difference is exact where it matters (0 at the maximum itself) and the log is small, where x / T - lse rounds at
+// the magnitude of lse -- on a peaked row (one logit 60 above the rest) that alone is 2e-6 on every log q.
+// The logs and c stay in the log2 units they were computed in, so that the backward forms bit for bit the forward's terms.
+struct GjsdStats {  // 12 floats per row; m .. c are what the backward reads: lse(s) = m + ln 2 ls1, lse(s/T) = m / T + ln 2 lsT,
+  float m, ls1, lsT, mt, ltT, c, valid, task, distill, teacher, pad0, pad1;  // lse(t/T) = mt / T + ln 2 ltT; c: see the forward
+};
+
+constexpr int GJ_NF = 512;  // threads per row, as kd_fwd_kernel's dense variant (here 2 to 4 workgroups per CU by VGPRs)
+constexpr int GJ_PF = 4;    // chunks in flight per thread and row
+constexpr float GJ_LN2 = 0.6931471805599453f, GJ_LOG2E = 1.4426950408889634f, GJ_FLT_MIN = 1.17549435e-38f;
+
+// Streams the row pair through `body(c, f, g)` (c: first element of the 8-element chunk, f / g its student / teacher
+// values), every thread seeing its chunks in increasing order.  The loads are the ones of kd_fwd_kernel: GJ_PF chunks
+// per thread in flight, each slot refilled before the arithmetic on it, all unconditional.  `body` may store to chunk c
+// of a buffer that aliases `s`: a thread only ever reads ahead in its OWN chunks (which it has not written yet), and the
+// clamped re-read of the last chunk is never used.
+template <typename T, typename F>
+SD_DEV void gj_sweep(const T* s, const T* tl, int V, F&& body) {
+  typedef typename Ld8<T>::Raw Raw;
+  constexpr int stride = GJ_NF * 8;
+  Raw sbuf[GJ_PF], tbuf[GJ_PF];
+  const int clast = ((V - 1) >> 3) << 3;
+#pragma unroll
+  for (int j = 0; j < GJ_PF; ++j) {
+    const int cj = min((int)threadIdx.x * 8 + j * stride, clast);
+    sbuf[j] = Ld8<T>::raw(s + cj);
+    tbuf[j] = Ld8<T>::raw(tl + cj);
+  }
+  for (int c0 = threadIdx.x * 8; c0 < V; c0 += GJ_PF * stride) {
+#pragma unroll
+    for (int j = 0; j < GJ_PF; ++j) {
+      const int c = c0 + j * stride;
+      float f[8], g[8];
+      Ld8<T>::cvt(sbuf[j], f);
+      Ld8<T>::cvt(tbuf[j], g);
+      const int cn = min(c + GJ_PF * stride, clast);
+      sbuf[j] = Ld8<T>::raw(s + cn);
+      tbuf[j] = Ld8<T>::raw(tl + cn);
+      if (c >= V) continue;
+      body(c, f, g);
+    }
+  }
+}
+
+// one element of sweep 2 / of the backward: q and (in log2 units) log q - log p, or log q - log m.
+// m, mt: the row maxima; A0, B0: -log2 of the max-subtracted sums at T
+template <bool JSD>
+SD_DEV void gj_term(float f, float g, float m, float mt, float kT, float A0, float B0, float beta, float& q, float& dq,
+                    float& p, float& dp) {
+  const float a2 = __builtin_fmaf(f - m, kT, A0), b2 = __builtin_fmaf(g - mt, kT, B0);  // log2 q, log2 p
+  q = __builtin_amdgcn_exp2f(a2);
+  if constexpr (JSD) {
+    p = __builtin_amdgcn_exp2f(b2);
+    const float lm = __builtin_amdgcn_logf(fmaxf(__builtin_fmaf(1.f - beta, q, beta * p), GJ_FLT_MIN));  // v_log_f32 = log2
+    dq = a2 - lm;
+    dp = b2 - lm;
+  } else {
+    p = 0.f;
+    dq = a2 - b2;
+    dp = 0.f;
+  }
+}
+
+template <typename T, bool T2, bool JSD>
+__global__ __launch_bounds__(GJ_NF) void gjsd_fwd_kernel(const T* __restrict__ S, const T* __restrict__ Tl,
+                                                         const int64_t* __restrict__ labels, GjsdStats* __restrict__ stats,
+                                                         int V, float temperature, float beta) {
+  __shared__ float sc[32];
+  const int row = blockIdx.x;
+  const long y = labels[row];
+  if (y < 0 || y >= V) {  // -100 (and anything outside the vocabulary) masks the row
+    if (threadIdx.x == 0) stats[row] = GjsdStats{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    return;
+  }
+  const float invT = 1.f / temperature;
+  const float k1 = GJ_LOG2E, kT = invT * k1;
+  const T* s = S + (long)row * V;
+  const T* tl = Tl + (long)row * V;
+  // ---- sweep 1: the four normalisers (kd_fwd_kernel's dense sweep without its cross term)
+  float m = -INFINITY, s1 = 0.f, sT = 0.f, mt = -INFINITY, t1 = 0.f, tT = 0.f;
+  gj_sweep<T>(s, tl, V, [&](int, const float* f, const float* g) {
+    float cm = f[0], tm = g[0];
+#pragma unroll
+    for (int e = 1; e < 8; ++e) { cm = fmaxf(cm, f[e]); tm = fmaxf(tm, g[e]); }
+    if (cm > m) {
+      const float rT = __expf((m - cm) * invT), r1 = T2 ? rT * rT : __expf(m - cm);
+      s1 *= r1; sT *= rT; m = cm;
+    }
+    if (tm > mt) {
+      const float rT = __expf((mt - tm) * invT), r1 = T2 ? rT * rT : __expf(mt - tm);
+      t1 *= r1; tT *= rT; mt = tm;
+    }
+    // exp2((f - m) kT), NOT kd_fwd_kernel's folded exp2(f kT - m kT): the fold leaves the rounding error of m kT in every
+    // exponent (the maximum itself gives 1 + 1e-6 instead of 1).  A forward KL forgives that, it shifts lse(s) and the
+    // cross term alike; here log q and log p each take their own shift, which on a peaked row near its teacher is
+    // ten thousand times D.  One subtraction more per logit, next to exponentials at a quarter of the vector rate.
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float df = f[e] - m, dg = g[e] - mt;
+      const float q = __builtin_amdgcn_exp2f(df * kT);
+      const float w = __builtin_amdgcn_exp2f(dg * kT);
+      sT += q;
+      tT += w;
+      s1 += T2 ? q * q : __builtin_amdgcn_exp2f(df * k1);
+      t1 += T2 ? w * w : __builtin_amdgcn_exp2f(dg * k1);
+    }
+  });
+  block_merge<GJ_NF>(m, s1, sT, invT, sc);
+  block_merge<GJ_NF>(mt, t1, tT, invT, sc);
+  const float ls1 = __builtin_amdgcn_logf(s1), lt1 = __builtin_amdgcn_logf(t1);  // v_log_f32: log2
+  const float lsT = __builtin_amdgcn_logf(sT), ltT = __builtin_amdgcn_logf(tT);
+  // ---- sweep 2: the divergence terms, in log2 units (one multiplication by ln 2 per row)
+  const float A0 = -lsT, B0 = -ltT;
+  float accq = 0.f, accp = 0.f;
+  gj_sweep<T>(s, tl, V, [&](int, const float* f, const float* g) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float q, dq, p, dp;
+      gj_term<JSD>(f[e], g[e], m, mt, kT, A0, B0, beta, q, dq, p, dp);
+      accq += q > 0.f ? q * dq : 0.f;
+      if constexpr (JSD) accp += p > 0.f ? p * dp : 0.f;
+    }
+  });
+  // c is kept as it was summed (log2 units, without the 1 - beta of g): the backward forms (log q_j - log . _j) - c in
+  // those units first, so that on a one-hot q, where c IS the peak's own term, the difference is exactly 0
+  const float c = block_sum<GJ_NF>(accq, sc);  // KL(q || p) / ln 2, or KL(q || m) / ln 2
+  float D = c * GJ_LN2;
+  if constexpr (JSD) D = beta * (block_sum<GJ_NF>(accp, sc) * GJ_LN2) + (1.f - beta) * D;
+  if (threadIdx.x == 0)
+    stats[row] = GjsdStats{m, ls1, lsT, mt, ltT, c, 1.f, (m - (float)s[y]) + ls1 * GJ_LN2, D,
+                           (mt - (float)tl[y]) + lt1 * GJ_LN2, 0.f, 0.f};
+}
+
+// out[0..7] = total, task, distill, teacher, N, N, 0, 0      (single block, fixed order)
+__global__ __launch_bounds__(NT) void gjsd_finalize_kernel(const GjsdStats* __restrict__ stats, float* __restrict__ out,
+                                                           int rows, float temperature, float alpha) {
+  __shared__ float sc[32];
+  float n = 0, task = 0, dist = 0, teach = 0;
+  for (int r = threadIdx.x; r < rows; r += NT) {
+    const GjsdStats st = stats[r];
+    n += st.valid; task += st.task; dist += st.distill; teach += st.teacher;
+  }
+  n = block_sum<NT>(n, sc); task = block_sum<NT>(task, sc); dist = block_sum<NT>(dist, sc); teach = block_sum<NT>(teach, sc);
+  if (threadIdx.x == 0) {
+    float tk = 0.f, ds = 0.f, tc = 0.f;
+    if (n != 0.f) {
+      tk = task / n;
+      ds = dist / n * temperature * temperature;
+      tc = teach / n;
+    }
+    out[0] = n != 0.f ? alpha * tk + (1.f - alpha) * ds : 0.f;
+    out[1] = tk; out[2] = ds; out[3] = tc; out[4] = n; out[5] = n; out[6] = 0.f; out[7] = 0.f;
+  }
+}
+
+// One read of both rows, one write of the gradient; G may alias S (see gj_sweep).
+template <typename T, bool T2, bool JSD>
+__global__ __launch_bounds__(GJ_NF) void gjsd_bwd_kernel(const T* S, const T* __restrict__ Tl,
+                                                         const int64_t* __restrict__ labels,
+                                                         const GjsdStats* __restrict__ stats,
+                                                         const float* __restrict__ loss_out,
+                                                         const float* __restrict__ grad_out, T* G, int V, float temperature,
+                                                         float alpha, float beta) {
+  const int row = blockIdx.x;
+  const GjsdStats st = stats[row];
+  T* gr = G + (long)row * V;
+  if (st.valid == 0.f) {
+    float z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int c = threadIdx.x * 8; c < V; c += GJ_NF * 8) Ld8<T>::store(gr + c, z);
+    return;
+  }
+  const float invT = 1.f / temperature;
+  const float k1 = GJ_LOG2E, kT = invT * k1;
+  const float N = loss_out[4];
+  const float go = grad_out ? grad_out[0] : 1.f;
+  const float a1 = go * alpha / N;                        // * (softmax(s) - e_y)
+  const float gs = JSD ? (1.f - beta) * GJ_LN2 : GJ_LN2;        // log2 units -> g
+  const float aT = go * (1.f - alpha) * temperature / N * gs;  // * q (g - c), g - c still in log2 units
+  const long y = labels[row];
+  const float A0 = -st.lsT, B0 = -st.ltT, L1 = -st.ls1;
+  const float r1 = T2 ? __builtin_amdgcn_exp2f(2.f * st.lsT - st.ls1) : 0.f;  // softmax(s) = q^2 r1 at T == 2
+  gj_sweep<T>(S + (long)row * V, Tl + (long)row * V, V, [&](int c, const float* f, const float* g) {
+    float o[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float q, dq, p, dp;
+      gj_term<JSD>(f[e], g[e], st.m, st.mt, kT, A0, B0, beta, q, dq, p, dp);
+      const float sm = T2 ? q * q * r1 : __builtin_amdgcn_exp2f(__builtin_fmaf(f[e] - st.m, k1, L1));
+      const float w = q > 0.f ? q * (dq - st.c) : 0.f;
+      o[e] = __builtin_fmaf(a1, sm, aT * w);
+    }
+    if (y >= c && y < c + 8) o[y - c] -= a1;
+    Ld8<T>::store(gr + c, o);
+  });
+}
+
+int gjsd_check(const void* S, const void* Tl, const int64_t* labels, const void* stats, const float* out, int R, int V,
+               float temperature, float beta, int mode, int dtype) {
+  if (R <= 0 || V <= 0 || !S || !labels || !stats || !out) return SD_ERR_SHAPE;
+  if (!Tl) return SD_ERR_NO_TEACHER;
+  if (V & 7) return SD_ERR_ALIGN;
+  if (((uintptr_t)S & 15) || ((uintptr_t)Tl & 15)) return SD_ERR_ALIGN;
+  if (dtype != SD_DTYPE_BF16 && dtype != SD_DTYPE_F32) return SD_ERR_UNSUPPORTED;
+  if (mode != SD_DIV_REVERSE_KL && mode != SD_DIV_JSD) return SD_ERR_UNSUPPORTED;
+  if (!(temperature > 0.f) || !(temperature < INFINITY)) return SD_ERR_SHAPE;       // NaN fails both comparisons
+  if (mode == SD_DIV_JSD && !(beta > 0.f && beta < 1.f)) return SD_ERR_SHAPE;    // likewise
+  return 0;
+}
+
+template <typename T>
+int gjsd_run_fwd(const void* S, const void* Tl, const int64_t* labels, void* stats, float* out, int R, int V,
+                 float temperature, float alpha, float beta, int mode, hipStream_t st) {
+  {
+    SdProfScope prof(SD_K_LOSS_FWD, (double)R * V * sizeof(T) * 2, st);
+    SD_PROF_LABEL("gjsd_fwd_kernel<%s, %s, %s>", sizeof(T) == 2 ? "__bf16" : "float", temperature == 2.0f ? "true" : "false",
+                  mode == SD_DIV_JSD ? "true" : "false");
+#define SD_GJ_FWD(T2_, JSD_)                                                                                              \
+  hipLaunchKernelGGL((gjsd_fwd_kernel<T, T2_, JSD_>), dim3(R), dim3(GJ_NF), 0, st, (const T*)S, (const T*)Tl, labels,        \
+                     (GjsdStats*)stats, V, temperature, beta)
+    const bool t2 = temperature == 2.0f, jsd = mode == SD_DIV_JSD;
+    if (t2) { if (jsd) SD_GJ_FWD(true, true); else SD_GJ_FWD(true, false); }
+    else { if (jsd) SD_GJ_FWD(false, true); else SD_GJ_FWD(false, false); }
+#undef SD_GJ_FWD
+    SD_CHECK_LAUNCH();
+  }
+  hipLaunchKernelGGL(gjsd_finalize_kernel, dim3(1), dim3(NT), 0, st, (const GjsdStats*)stats, out, R, temperature, alpha);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+template <typename T>
+int gjsd_run_bwd(const void* S, const void* Tl, const int64_t* labels, const void* stats, const float* out, const float* go,
+                 void* G, int R, int V, float temperature, float alpha, float beta, int mode, hipStream_t st) {
+  SdProfScope prof(SD_K_LOSS_BWD, (double)R * V * sizeof(T) * 3, st);
+  SD_PROF_LABEL("gjsd_bwd_kernel<%s, %s, %s>", sizeof(T) == 2 ? "__bf16" : "float", temperature == 2.0f ? "true" : "false",
+                mode == SD_DIV_JSD ? "true" : "false");
+#define SD_GJ_BWD(T2_, JSD_)                                                                                              \
+  hipLaunchKernelGGL((gjsd_bwd_kernel<T, T2_, JSD_>), dim3(R), dim3(GJ_NF), 0, st, (const T*)S, (const T*)Tl, labels,        \
+                     (const GjsdStats*)stats, out, go, (T*)G, V, temperature, alpha, beta)
+  const bool t2 = temperature == 2.0f, jsd = mode == SD_DIV_JSD;
+  if (t2) { if (jsd) SD_GJ_BWD(true, true); else SD_GJ_BWD(true, false); }
+  else { if (jsd) SD_GJ_BWD(false, true); else SD_GJ_BWD(false, false); }
+#undef SD_GJ_BWD
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int64_t sd_gjsd_stats_bytes(int R) { return (int64_t)R * sizeof(GjsdStats); }
+
+extern "C" int sd_gjsd_fwd_rows(const void* student_logits, const void* teacher_logits, const int64_t* row_labels,
+                                void* row_stats, float* loss_out, int R, int V, float temperature, float alpha, float beta,
+                                int mode, int dtype, void* stream) {
+  if (int e = gjsd_check(student_logits, teacher_logits, row_labels, row_stats, loss_out, R, V, temperature, beta, mode, dtype))
+    return e;
+  if (dtype == SD_DTYPE_BF16)
+    return gjsd_run_fwd<bf16>(student_logits, teacher_logits, row_labels, row_stats, loss_out, R, V, temperature, alpha, beta,
+                              mode, (hipStream_t)stream);
+  return gjsd_run_fwd<float>(student_logits, teacher_logits, row_labels, row_stats, loss_out, R, V, temperature, alpha, beta,
+                             mode, (hipStream_t)stream);
+}
+
+extern "C" int sd_gjsd_bwd_rows(const void* student_logits, const void* teacher_logits, const int64_t* row_labels,
+                                const void* row_stats, const float* loss_out, const float* grad_total, void* grad_logits,
+                                int R, int V, float temperature, float alpha, float beta, int mode, int dtype, void* stream) {
+  if (int e = gjsd_check(student_logits, teacher_logits, row_labels, row_stats, loss_out, R, V, temperature, beta, mode, dtype))
+    return e;
+  if (!grad_logits) return SD_ERR_SHAPE;
+  if ((uintptr_t)grad_logits & 15) return SD_ERR_ALIGN;
+  if (dtype == SD_DTYPE_BF16)
+    return gjsd_run_bwd<bf16>(student_logits, teacher_logits, row_labels, row_stats, loss_out, grad_total, grad_logits, R, V,
+                              temperature, alpha, beta, mode, (hipStream_t)stream);
+  return gjsd_run_bwd<float>(student_logits, teacher_logits, row_labels, row_stats, loss_out, grad_total, grad_logits, R, V,
+                             temperature, alpha, beta, mode, (hipStream_t)stream);
+}

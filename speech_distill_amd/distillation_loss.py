@@ -8,16 +8,26 @@ same ``ValueError`` when neither teacher form is given.  Differences, all docume
     in the logits' dtype), outputs are fp32 0-d tensors;
   * N == 0 returns zeros that ARE connected to autograd (reference: constants, distillation_loss.py:47-53);
   * sub-losses are returned detached (the reference only ever ``.item()``s them, train.py:108-114).
+
+Beyond the reference: ``divergence`` chooses the distillation term.  "forward_kl" (the default) is the reference's
+KL(teacher || student) and the code path above, untouched.  "reverse_kl" is KL(student || teacher) and "jsd" the
+beta-skewed Jensen-Shannon divergence beta KL(p || m) + (1 - beta) KL(q || m), m = (1 - beta) q + beta p (TRL's
+``generalized_jsd_loss`` for 0 < beta < 1; its beta = 0 / 1 are "forward_kl" / "reverse_kl"), both with the same T^2 and
+alpha conventions, on a DENSE teacher only (a top-K teacher defines p on K entries): DESIGN.md section 12.
 """
 import torch
 import torch.nn as nn
 
-from .ops import KDLossFn, KDLossRowsFn
+from . import ops
+from .ops import GJSDLossRowsFn, KDLossFn, KDLossRowsFn
 
 
 class DistillationLoss(nn.Module):
-    def __init__(self, temperature=2.0, alpha=0.5, inplace_grad=False):
+    def __init__(self, temperature=2.0, alpha=0.5, inplace_grad=False, divergence="forward_kl", beta=0.5):
         super().__init__()
+        ops.check_divergence(divergence, beta)
+        self.divergence = divergence
+        self.beta = beta
         self.temperature = temperature
         self.alpha = alpha
         # write d loss / d logits over the logits buffer itself (saves V*B*T*2 bytes); only safe
@@ -28,6 +38,13 @@ class DistillationLoss(nn.Module):
                 speech_token_mask=None):
         if teacher_logits is None and (teacher_top_k_v is None or teacher_top_k_i is None):
             raise ValueError("Either teacher_logits or top_k must be provided")
+        if self.divergence != "forward_kl":
+            # eval / return_outputs path: select the rows as the trainer does and gather them (one copy of R rows)
+            self._need_dense(teacher_logits)
+            rows, row_labels = ops.loss_rows(labels, speech_token_mask)
+            V = student_logits.shape[-1]
+            return self.forward_rows(student_logits.reshape(-1, V)[rows], row_labels,
+                                     teacher_logits=teacher_logits.detach().reshape(-1, V)[rows])
         if not student_logits.is_contiguous():
             student_logits = student_logits.contiguous()
         if teacher_logits is not None:
@@ -44,7 +61,18 @@ class DistillationLoss(nn.Module):
             raise ValueError("Either teacher_logits or top_k must be provided")
         if teacher_logits is not None:
             teacher_logits = teacher_logits.detach()
+        if self.divergence != "forward_kl":
+            self._need_dense(teacher_logits)
+            total, out = GJSDLossRowsFn.apply(student_logits.contiguous(), row_labels, teacher_logits, self.temperature,
+                                              self.alpha, self.beta, self.divergence,
+                                              self.inplace_grad and student_logits.requires_grad)
+            return total, out[1], out[2], out[3]
         total, out = KDLossRowsFn.apply(student_logits.contiguous(), row_labels, teacher_logits, teacher_top_k_v,
                                         teacher_top_k_i, self.temperature, self.alpha,
                                         self.inplace_grad and student_logits.requires_grad)
         return total, out[1], out[2], out[3]
+
+    def _need_dense(self, teacher_logits):
+        if teacher_logits is None:
+            raise ValueError(f"divergence={self.divergence!r} needs dense teacher_logits: a top-K teacher defines the "
+                             "teacher distribution on K entries only")

@@ -456,6 +456,70 @@ class KDLossRowsFn(torch.autograd.Function):
         return grad, None, None, None, None, None, None, None
 
 
+DIVERGENCES = {"reverse_kl": 1, "jsd": 2}  # include/sd_hip.h SD_DIV_*; "forward_kl" is KDLossRowsFn
+
+
+def check_divergence(divergence, beta):
+    """ValueError for a divergence the loss does not know, or a ``jsd`` whose beta is outside (0, 1) (NaN included):
+    the jsd formula tends to 0 at both ends, TRL's beta = 0 / 1 are ``forward_kl`` / ``reverse_kl``."""
+    if divergence != "forward_kl" and divergence not in DIVERGENCES:
+        raise ValueError(f"unknown divergence {divergence!r}: one of 'forward_kl', 'reverse_kl', 'jsd'")
+    if divergence == "jsd" and not 0.0 < float(beta) < 1.0:
+        raise ValueError(f"divergence='jsd' needs 0 < beta < 1, got {beta!r} (beta = 0 is 'forward_kl', beta = 1 is "
+                         "'reverse_kl')")
+
+
+class GJSDLossRowsFn(torch.autograd.Function):
+    """Reverse KL / beta-skewed Jensen-Shannon distillation loss (sd_gjsd_*_rows) on rows the caller has already shifted
+    and selected: student_logits [R,V], row_labels [R], dense teacher_logits [R,V]; ``divergence`` "reverse_kl" or "jsd".
+    Returns (total, out fp32[8] = total, task, distill, teacher, N, N, 0, 0).  R == 0 (a batch without a loss row) launches
+    nothing and returns zeros that are connected to autograd, as a batch whose rows are all masked does."""
+
+    @staticmethod
+    def forward(ctx, student_logits, row_labels, teacher_logits, temperature, alpha, beta, divergence, inplace_grad):
+        check_divergence(divergence, beta)
+        if divergence not in DIVERGENCES:
+            raise ValueError("GJSDLossRowsFn computes 'reverse_kl' and 'jsd'; 'forward_kl' is KDLossRowsFn")
+        if teacher_logits is None:
+            raise ValueError(f"divergence={divergence!r} needs dense teacher_logits")
+        s = _need(student_logits, None, "student_logits")
+        R, V = s.shape
+        dt = _dt(s)
+        lib = load_lib()
+        row_labels = _need(row_labels.to(torch.int64), torch.int64, "row_labels")
+        teacher_logits = _need(teacher_logits.to(s.dtype), None, "teacher_logits")
+        if teacher_logits.shape != s.shape:
+            raise ValueError(f"teacher_logits {tuple(teacher_logits.shape)} != student_logits {tuple(s.shape)}")
+        mode = DIVERGENCES[divergence]
+        ctx.cfg = (R, V, float(temperature), float(alpha), float(beta), mode, dt, bool(inplace_grad))
+        if R == 0:   # the C entry refuses R <= 0; the loss of no row is 0 and so is its (empty) gradient
+            out = torch.zeros(8, dtype=torch.float32, device=s.device)
+            ctx.save_for_backward(s, row_labels, teacher_logits, out, out)
+            ctx.mark_non_differentiable(out)
+            return out[0].clone(), out
+        stats = torch.empty(lib.sd_gjsd_stats_bytes(R), dtype=torch.uint8, device=s.device)
+        out = torch.empty(8, dtype=torch.float32, device=s.device)
+        check(lib.sd_gjsd_fwd_rows(s.data_ptr(), teacher_logits.data_ptr(), row_labels.data_ptr(), stats.data_ptr(),
+                                   out.data_ptr(), R, V, float(temperature), float(alpha), float(beta), mode, dt, _stream()),
+              "sd_gjsd_fwd_rows")
+        ctx.save_for_backward(s, row_labels, teacher_logits, stats, out)
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, g_total, _g_out):
+        s, row_labels, teacher_logits, stats, out = ctx.saved_tensors
+        R, V, temperature, alpha, beta, mode, dt, inplace = ctx.cfg
+        grad = s if inplace else torch.empty_like(s)
+        if R == 0:
+            return grad, None, None, None, None, None, None, None
+        go = g_total.to(torch.float32).reshape(1).contiguous()
+        check(load_lib().sd_gjsd_bwd_rows(s.data_ptr(), teacher_logits.data_ptr(), row_labels.data_ptr(), stats.data_ptr(),
+                                          out.data_ptr(), go.data_ptr(), grad.data_ptr(), R, V, temperature, alpha, beta,
+                                          mode, dt, _stream()), "sd_gjsd_bwd_rows")
+        return grad, None, None, None, None, None, None, None
+
+
 class CELossRowsFn(torch.autograd.Function):
     """Causal-LM cross-entropy on rows the caller already shifted and selected (Stage-1 loss: HF ForCausalLMLoss as the
     reference's SFTTrainer computes it): logits [R,V] bf16/fp32, row_labels [R] (-100 masks a row), divisor: fp32 [1] device

@@ -6,6 +6,10 @@ inputs, as in the reference)  ->  pop labels  ->  teacher no-grad forward unless
 present  ->  on-the-fly log-softmax + top-K unless the teacher is quantized or top_k <= 0  ->
 DistillationLoss  ->  log {student_loss, teacher_loss, distill_loss} when
 ``state.global_step % args.logging_steps == 0``  ->  ``loss`` or ``(loss, outputs)``.
+
+Beyond the reference: ``divergence`` / ``beta`` choose the distillation term (``DistillationLoss``),
+and ``lmbda`` makes a share of the training micro-batches on-policy (``on_policy.py``): the student's own sampled
+continuation replaces the completion before the step.  The defaults (``"forward_kl"``, ``lmbda=0``) are the reference's loop.
 """
 import os
 import time
@@ -13,7 +17,7 @@ import time
 import torch
 from transformers import Trainer
 
-from . import ddp, ops
+from . import ddp, on_policy, ops
 from .distillation_loss import DistillationLoss
 from .qwen3 import HipQwen3ForCausalLM
 
@@ -93,15 +97,50 @@ class FlatStudentTrainer(Trainer):
 
 
 class DistillationTrainer(FlatStudentTrainer):
+    """``divergence`` ("forward_kl", "reverse_kl", "jsd") and ``beta``: see ``DistillationLoss``; anything but
+    "forward_kl" needs the dense teacher (``top_k <= 0`` or ``is_quantized_teacher``) and refuses batches that carry
+    pre-extracted ``teacher_top_k_v``.
+
+    ``lmbda`` in [0, 1]: the probability that a training micro-batch is made on-policy -- one draw per micro-batch from a
+    CPU generator seeded from ``args.seed`` and the process index; below ``lmbda`` the student generates from the batch's
+    prompts with the ``generate`` keywords of ``on_policy_generate`` (``on_policy.GENERATE_KEYS``, at least
+    ``max_new_tokens``) and ``on_policy.rollout`` rebuilds the batch around its tokens.  Needs a ``HipQwen3ForCausalLM``
+    student on the GPU without LoRA and a teacher model.  With ``lmbda > 0`` the three lookaheads (loss rows ahead, teacher
+    ahead, window ahead) are switched off: they would select rows of, and run the teacher on, a batch that is about to be
+    replaced.  ``on_policy_fraction`` (the share of on-policy micro-batches since the previous log) is logged next to the
+    three sub-losses."""
+
     def __init__(self, *args, teacher_model=None, temperature=2.0, alpha=0.5, top_k=100, is_quantized_teacher=False,
-                 **kwargs):
+                 divergence="forward_kl", beta=0.5, lmbda=0.0, on_policy_generate=None, **kwargs):
+        # everything that can be refused without a model is refused before HF's constructor touches one
+        ops.check_divergence(divergence, beta)
+        if divergence != "forward_kl" and not (top_k <= 0 or is_quantized_teacher):
+            raise ValueError(f"divergence={divergence!r} needs the dense teacher distribution: pass top_k=0 (a top-K "
+                             f"teacher defines it on K entries only), got top_k={top_k}")
+        if not 0.0 <= float(lmbda) <= 1.0:
+            raise ValueError(f"lmbda must lie in [0, 1], got {lmbda!r}")
+        if lmbda > 0:
+            on_policy.check_generate_kwargs(on_policy_generate)
+            if teacher_model is None:
+                raise ValueError("lmbda > 0 needs a teacher model: on-policy tokens have no pre-extracted teacher logits")
         super().__init__(*args, **kwargs)
         self.teacher_model = teacher_model
         if self.teacher_model is not None:
             self.teacher_model.eval()
         self.top_k = top_k
-        self.distill_loss_fn = DistillationLoss(temperature=temperature, alpha=alpha)
+        self.distill_loss_fn = DistillationLoss(temperature=temperature, alpha=alpha, divergence=divergence, beta=beta)
         self.is_quantized_teacher = is_quantized_teacher
+        self.divergence = divergence
+        self.lmbda = float(lmbda)
+        self.on_policy_generate = dict(on_policy_generate) if on_policy_generate is not None else None
+        self._on_policy_rng = None      # CPU generator of the per-micro-batch draw and the rollout seeds
+        self._on_policy_seen = [0, 0]   # [on-policy, all] training micro-batches since the previous log
+        if self.lmbda > 0:
+            core = ddp.unwrap(self.model)
+            if not (isinstance(core, HipQwen3ForCausalLM) and core.flat.is_cuda and core._lora is None):
+                raise ValueError("lmbda > 0 is built for a HipQwen3ForCausalLM student on the GPU without LoRA (the rollout "
+                                 "decodes from the live flat weights)")
+            self._on_policy_rng = torch.Generator().manual_seed(int(self.args.seed) + int(self.args.process_index))
         # compute back-ends; the product ones are the HIP kernels (tests may inject a checker here)
         self._extract_topk = ops.logsoftmax_topk
         # throughput of the loop: positions (B*T of every training micro-batch, padding included -- what the kernels
@@ -169,7 +208,7 @@ class DistillationTrainer(FlatStudentTrainer):
         Same selection, validation and arguments as ``compute_loss`` would use on its own."""
         core = ddp.unwrap(self.model)
         ahead = (self.compact_head and os.environ.get("SD_ROWS_AHEAD", "1") != "0" and isinstance(core, HipQwen3ForCausalLM)
-                 and core.flat.is_cuda and isinstance(self.distill_loss_fn, DistillationLoss))
+                 and core.flat.is_cuda and isinstance(self.distill_loss_fn, DistillationLoss) and self.lmbda == 0)
         if not ahead:
             self._rows_ahead.clear()
             self._window, self._window_next, self._ahead_results, self._prefetched = [], [], {}, None
@@ -235,12 +274,26 @@ class DistillationTrainer(FlatStudentTrainer):
     _TEACHER_SIDE_KEYS = ("teacher_input_ids", "teacher_attention_mask", "speech_token_mask", "teacher_top_k_v", "teacher_top_k_i")
 
     def training_step(self, model, inputs, *args, **kwargs):
+        if self.lmbda > 0:
+            inputs = self._maybe_on_policy(model, inputs)
         lab = inputs.get("labels") if isinstance(inputs, dict) else None
         loss = super().training_step(model, inputs, *args, **kwargs)
         mode = os.environ.get("SD_TEACHER_AHEAD", "auto")
-        if lab is not None and self._window and (mode == "1" or (mode == "auto" and self.args.logging_nan_inf_filter)):
+        if (lab is not None and self._window and self.lmbda == 0
+                and (mode == "1" or (mode == "auto" and self.args.logging_nan_inf_filter))):
             self._launch_teacher_ahead(id(lab))
         return loss
+
+    def _maybe_on_policy(self, model, inputs):
+        """One draw per training micro-batch; below ``lmbda`` the batch is rebuilt around the student's own continuation
+        (``on_policy.rollout``: no_grad, the decoder reads the live flat weights; ``flat``, ``flat_grad``, the saved
+        activations and the train/eval flag are not touched).  The rollout's seed comes from the same generator."""
+        self._on_policy_seen[1] += 1
+        if float(torch.rand(1, generator=self._on_policy_rng)) >= self.lmbda:
+            return inputs
+        seed = int(torch.randint(0, 2 ** 31 - 1, (1,), generator=self._on_policy_rng))
+        self._on_policy_seen[0] += 1
+        return on_policy.rollout(ddp.unwrap(model).generate, self._prepare_inputs(inputs), self.on_policy_generate, seed)
 
     def _launch_teacher_ahead(self, cur_id):
         """Enqueue the frozen teacher's pass for the micro-batch that follows ``cur_id`` in this accumulation window."""
@@ -309,6 +362,9 @@ class DistillationTrainer(FlatStudentTrainer):
         teacher_top_k_v = inputs.pop("teacher_top_k_v", None)
         teacher_top_k_i = inputs.pop("teacher_top_k_i", None)
 
+        if self.divergence != "forward_kl" and teacher_top_k_v is not None:
+            raise ValueError(f"divergence={self.divergence!r} needs the dense teacher distribution; this batch carries "
+                             "pre-extracted teacher_top_k_v (K entries per position)")
         need_teacher = teacher_top_k_v is None and self.teacher_model is not None
         ids0 = inputs.get("input_ids")
         if (need_teacher and teacher_input_ids is not None and ids0 is not None
@@ -416,7 +472,12 @@ class DistillationTrainer(FlatStudentTrainer):
             # one device->host sync for the three scalars instead of three .item() calls
             vals = torch.stack([task_loss.detach().float(), teacher_loss.detach().float(),
                                 distill_loss.detach().float()]).tolist()
-            self.log({"student_loss": vals[0], "teacher_loss": vals[1], "distill_loss": vals[2]})
+            logs = {"student_loss": vals[0], "teacher_loss": vals[1], "distill_loss": vals[2]}
+            if self.lmbda > 0 and model.training:   # evaluation neither reports nor resets the training counters
+                on, seen = self._on_policy_seen
+                logs["on_policy_fraction"] = on / max(seen, 1)
+                self._on_policy_seen = [0, 0]
+            self.log(logs)
         return (loss, outputs) if return_outputs else loss
 
 
