@@ -14,7 +14,8 @@
 // Forward keeps per-row normalisers (lse at T=1, lse at T, teacher lse at T) so that backward is one
 // read of the logits and one write of the gradient.  All reductions are deterministic (per-row
 // partials + a fixed-order final reduce); no float atomics.
-#include "sd_common.cuh"
+#include <type_traits>
+#include "sd_rows.cuh"
 #include "../../include/sd_hip.h"
 #include "sd_prof.h"
 
@@ -23,41 +24,19 @@ namespace {
 constexpr int NT = 1024;
 constexpr int KMAX = 1024;
 
-template <typename T> struct Ld8;
-template <> struct Ld8<bf16> {
-  typedef bf16x8 Raw;  // 8 elements as loaded (prefetched chunks wait in registers in this form)
-  static SD_DEV Raw raw(const bf16* p) { return *(const bf16x8*)p; }
-  static SD_DEV void cvt(const Raw& v, float* f) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] = (float)v[e];
-  }
-  static SD_DEV void load(const bf16* p, float* f) {
-    bf16x8 v = *(const bf16x8*)p;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] = (float)v[e];
-  }
-  static SD_DEV void store(bf16* p, const float* f) {
-    bf16x8 v;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = (bf16)f[e];
-    *(bf16x8*)p = v;
-  }
-};
-template <> struct Ld8<float> {
-  struct Raw { f32x4 a, b; };
-  static SD_DEV Raw raw(const float* p) { return Raw{*(const f32x4*)p, *(const f32x4*)(p + 4)}; }
-  static SD_DEV void cvt(const Raw& v, float* f) {
-    f[0] = v.a[0]; f[1] = v.a[1]; f[2] = v.a[2]; f[3] = v.a[3]; f[4] = v.b[0]; f[5] = v.b[1]; f[6] = v.b[2]; f[7] = v.b[3];
-  }
-  static SD_DEV void load(const float* p, float* f) {
-    f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
-    f[0] = a[0]; f[1] = a[1]; f[2] = a[2]; f[3] = a[3]; f[4] = b[0]; f[5] = b[1]; f[6] = b[2]; f[7] = b[3];
-  }
-  static SD_DEV void store(float* p, const float* f) {
-    *(f32x4*)p = f32x4{f[0], f[1], f[2], f[3]};
-    *(f32x4*)(p + 4) = f32x4{f[4], f[5], f[6], f[7]};
-  }
-};
+// Host dispatch of a run-time value to a template argument: fn gets a tag whose ::type is the element type / an
+// integral_constant whose ::value is the flag.  Every entry's check has refused all dtypes but bf16 and fp32 before.
+template <typename T> struct TypeTag { typedef T type; };
+template <typename F> int by_dtype(int dtype, F&& fn) {
+  return dtype == SD_DTYPE_BF16 ? fn(TypeTag<bf16>{}) : fn(TypeTag<float>{});
+}
+template <typename F> void by_flag(bool b, F&& fn) {
+  if (b) fn(std::true_type{}); else fn(std::false_type{});
+}
+#define SD_TAG_TYPE(tag) typename decltype(tag)::type
+#define SD_FLAG(tag) decltype(tag)::value
+inline const char* type_name(size_t size) { return size == 2 ? "__bf16" : "float"; }
+inline const char* flag_name(bool b) { return b ? "true" : "false"; }
 
 // row -> (b, t); label / mask are taken at t+1 (the causal shift).  T == 0: the caller already selected and
 // shifted the rows (sd_kdloss_fwd_rows): label / mask are taken at `row` itself.
@@ -79,24 +58,15 @@ struct RowStats {  // 8 floats per row
   float lse1, lseT, t_lseT, valid, task, distill, teacher, hits;
 };
 
-// merge (m, s) online-softmax partials across the block; returns the block totals to all threads
-template <int NF>
-SD_DEV void block_merge(float& m, float& s1, float& sT, float invT, float* sc) {
-  const float M = block_max<NF>(m, sc);
-  const float f1 = (m == -INFINITY) ? 0.f : __expf(m - M);
-  const float fT = (m == -INFINITY) ? 0.f : __expf((m - M) * invT);
-  s1 = block_sum<NF>(s1 * f1, sc);
-  sT = block_sum<NF>(sT * fT, sc);
-  m = M;
-}
-
 // T2: temperature == 2 (the reference's default, train.py:488-491).  Then exp(z) = exp(z / 2)^2, so the sum-exp at T = 1
 // comes from the T = 2 exponential by one multiplication: half the transcendentals of a kernel that is bound by them
 // (129 us = 3.8 TB/s before, with two v_exp_f32 per logit at a quarter of the vector rate).
 // NF threads per row: 512 (four workgroups per CU, 128 chunks of a CU in flight) whenever the K teacher entries fit one
 // thread each, else 1024.  DENSE: teacher logits instead of top-K (its prefetch registers only exist in that variant).
+// The bf16 1024-thread variant is held to 8 waves per SIMD (64 VGPRs, two workgroups per CU): left alone the compiler
+// lands on 64 or 66 registers with the shape of the surrounding code, and 66 leaves one workgroup per CU.
 template <typename T, bool T2, int NF, bool DENSE>
-__global__ __launch_bounds__(NF) void kd_fwd_kernel(const T* __restrict__ S, const T* __restrict__ Tl,
+__global__ __launch_bounds__(NF, (NF == 1024 && sizeof(T) == 2) ? 8 : 1) void kd_fwd_kernel(const T* __restrict__ S, const T* __restrict__ Tl,
                                                     const _Float16* __restrict__ topv, const int32_t* __restrict__ topi,
                                                     const int64_t* __restrict__ labels, const uint8_t* __restrict__ mask,
                                                     RowStats* __restrict__ stats, int rows, int Tlen, int V, int K,
@@ -117,67 +87,29 @@ __global__ __launch_bounds__(NF) void kd_fwd_kernel(const T* __restrict__ S, con
   // ---- dense teacher: max, sum-exp at 1 and T, cross = sum exp((t-mt)/T) (t - s)
   float mt = -INFINITY, t1 = 0.f, tT = 0.f, cross = 0.f;
   const T* tl = DENSE ? Tl + (long)row * V : nullptr;
-  // The row is streamed with PF chunks per thread in flight: with one (load, wait, compute) per trip the 32 waves of a CU
-  // keep 32 KB outstanding, which at ~2 us of loaded HBM latency is 4 TB/s whatever the kernel does (measured 3.9-4.1).
-  // Each thread still sees its chunks in the same order: the sums are bit for bit the ones of the plain loop.
-  constexpr int PF = 4;
-  typedef typename Ld8<T>::Raw Raw;
-  const int stride = NF * 8;
-  Raw sbuf[PF], tbuf[DENSE ? PF : 1];
-  // every load is UNCONDITIONAL (a chunk past the end re-reads the row's last one and is never used): with loads behind
-  // branches hipcc's wait insertion falls back to vmcnt(0) at every use and drains the chunks in flight
-  const int clast = ((V - 1) >> 3) << 3;  // start of the row's last chunk
+  row_sweep<T, NF, DENSE>(s, tl, V, [&](int, const float* f, const float* g) {
+    online_raise<T2>(chunk_max8(f), invT, m, s1, sT);
+    // exp((f - m) / T) = exp2(f * kT - m * kT): one fused multiply-add per exponential argument.  The fold leaves the
+    // rounding error of m * kT in every exponent, which a forward KL forgives (gjsd_fwd_kernel says why it cannot)
+    const float mkT = -m * kT, mk1 = -m * k1;
 #pragma unroll
-  for (int j = 0; j < PF; ++j) {
-    const int cj = min((int)threadIdx.x * 8 + j * stride, clast);
-    sbuf[j] = Ld8<T>::raw(s + cj);
-    if constexpr (DENSE) tbuf[j] = Ld8<T>::raw(tl + cj);
-  }
-  for (int c0 = threadIdx.x * 8; c0 < V; c0 += PF * stride) {
-#pragma unroll
-    for (int j = 0; j < PF; ++j) {
-      const int c = c0 + j * stride;
-      float f[8], g[8];
-      Ld8<T>::cvt(sbuf[j], f);
-      if constexpr (DENSE) Ld8<T>::cvt(tbuf[j], g);
-      const int cn = min(c + PF * stride, clast);  // refill the slot before the arithmetic
-      sbuf[j] = Ld8<T>::raw(s + cn);
-      if constexpr (DENSE) tbuf[j] = Ld8<T>::raw(tl + cn);
-      if (c >= V) continue;
-      float cm = f[0];
-#pragma unroll
-      for (int e = 1; e < 8; ++e) cm = fmaxf(cm, f[e]);
-      if (cm > m) {
-        const float rT = __expf((m - cm) * invT), r1 = T2 ? rT * rT : __expf(m - cm);
-        s1 *= r1; sT *= rT; m = cm;
-      }
-      // exp((f - m) / T) = exp2(f * kT - m * kT): one fused multiply-add per exponential argument
-      const float mkT = -m * kT, mk1 = -m * k1;
+    for (int e = 0; e < 8; ++e) {
+      const float q = __builtin_amdgcn_exp2f(__builtin_fmaf(f[e], kT, mkT));
+      sT += q;
+      s1 += T2 ? q * q : __builtin_amdgcn_exp2f(__builtin_fmaf(f[e], k1, mk1));
+    }
+    if constexpr (DENSE) {
+      online_raise<T2>(chunk_max8(g), invT, mt, t1, tT, cross);
+      const float tkT = -mt * kT, tk1 = -mt * k1;
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        const float q = __builtin_amdgcn_exp2f(__builtin_fmaf(f[e], kT, mkT));
-        sT += q;
-        s1 += T2 ? q * q : __builtin_amdgcn_exp2f(__builtin_fmaf(f[e], k1, mk1));
-      }
-      if constexpr (DENSE) {
-        float tm = g[0];
-#pragma unroll
-        for (int e = 1; e < 8; ++e) tm = fmaxf(tm, g[e]);
-        if (tm > mt) {
-          const float rT = __expf((mt - tm) * invT), r1 = T2 ? rT * rT : __expf(mt - tm);
-          t1 *= r1; tT *= rT; cross *= rT; mt = tm;
-        }
-        const float tkT = -mt * kT, tk1 = -mt * k1;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float w = __builtin_amdgcn_exp2f(__builtin_fmaf(g[e], kT, tkT));
-          t1 += T2 ? w * w : __builtin_amdgcn_exp2f(__builtin_fmaf(g[e], k1, tk1));
-          tT += w;
-          cross += w * (g[e] - f[e]);
-        }
+        const float w = __builtin_amdgcn_exp2f(__builtin_fmaf(g[e], kT, tkT));
+        t1 += T2 ? w * w : __builtin_amdgcn_exp2f(__builtin_fmaf(g[e], k1, tk1));
+        tT += w;
+        cross += w * (g[e] - f[e]);
       }
     }
-  }
+  });
   block_merge<NF>(m, s1, sT, invT, sc);
   const float lse1 = m + __logf(s1);
   const float lseT = m * invT + __logf(sT);
@@ -185,16 +117,11 @@ __global__ __launch_bounds__(NF) void kd_fwd_kernel(const T* __restrict__ S, con
   const float task = lse1 - sy;
   float distill = 0.f, teacher = 0.f, hits = 0.f, t_lseT = 0.f;
   if constexpr (DENSE) {
-    const float MT = block_max<NF>(mt, sc);
-    const float f1 = (mt == -INFINITY) ? 0.f : __expf(mt - MT);
-    const float fT = (mt == -INFINITY) ? 0.f : __expf((mt - MT) * invT);
-    t1 = block_sum<NF>(t1 * f1, sc);
-    tT = block_sum<NF>(tT * fT, sc);
-    cross = block_sum<NF>(cross * fT, sc);
-    t_lseT = MT * invT + __logf(tT);
+    block_merge<NF>(mt, t1, tT, invT, sc, cross);
+    t_lseT = mt * invT + __logf(tT);
     // sum_v q (log q - log p) = (1/T) sum_v q (t - s) - t_lseT + lseT      (sum_v q = 1)
     distill = cross / tT * invT - t_lseT + lseT;
-    teacher = MT + __logf(t1) - (float)tl[y];
+    teacher = mt + __logf(t1) - (float)tl[y];
     hits = 1.f;
   } else {
     // sparse: q = softmax(v/T) over the K stored teacher log-probs (renormalised over top-K)
@@ -220,18 +147,24 @@ __global__ __launch_bounds__(NF) void kd_fwd_kernel(const T* __restrict__ S, con
   if (threadIdx.x == 0) stats[row] = RowStats{lse1, lseT, t_lseT, 1.f, task, distill, teacher, hits};
 }
 
-// out[0..5] = total, task, distill, teacher, N, n_hits      (single block, fixed order)
-__global__ __launch_bounds__(NT) void kd_finalize_kernel(const RowStats* __restrict__ stats, float* __restrict__ out,
-                                                         int rows, float temperature, float alpha, int dense) {
+// The batch scalars from the per-row stats of kd_fwd_kernel (RowStats, HITS) or gjsd_fwd_kernel (GjsdStats): single
+// block, fixed order.
+//   RowStats:  out[0..5] = total, task, distill, teacher, N, n_hits
+//   GjsdStats: out[0..7] = total, task, distill, teacher, N, N, 0, 0
+template <typename Stats, bool HITS>
+__global__ __launch_bounds__(NT) void kd_finalize_kernel(const Stats* __restrict__ stats, float* __restrict__ out, int rows,
+                                                         float temperature, float alpha, int dense) {
   __shared__ float sc[32];
   float n = 0, task = 0, dist = 0, teach = 0, hits = 0;
   for (int r = threadIdx.x; r < rows; r += NT) {
-    const RowStats st = stats[r];
-    n += st.valid; task += st.task; dist += st.distill; teach += st.teacher; hits += st.hits;
+    const Stats st = stats[r];
+    n += st.valid; task += st.task; dist += st.distill; teach += st.teacher;
+    if constexpr (HITS) hits += st.hits;
   }
-  n = block_sum<NT>(n, sc); task = block_sum<NT>(task, sc); dist = block_sum<NT>(dist, sc);
-  teach = block_sum<NT>(teach, sc); hits = block_sum<NT>(hits, sc);
-  if (threadIdx.x == 0) {
+  n = block_sum<NT>(n, sc); task = block_sum<NT>(task, sc); dist = block_sum<NT>(dist, sc); teach = block_sum<NT>(teach, sc);
+  if constexpr (HITS) hits = block_sum<NT>(hits, sc);
+  if (threadIdx.x != 0) return;
+  if constexpr (HITS) {
     if (n == 0.f) {
       out[0] = out[1] = out[2] = out[3] = 0.f; out[4] = 0.f; out[5] = 0.f;
     } else {
@@ -240,6 +173,15 @@ __global__ __launch_bounds__(NT) void kd_finalize_kernel(const RowStats* __restr
       const float tc = dense ? teach / n : (hits > 0.f ? -teach / hits : 0.f);
       out[0] = alpha * tk + (1.f - alpha) * ds; out[1] = tk; out[2] = ds; out[3] = tc; out[4] = n; out[5] = hits;
     }
+  } else {
+    float tk = 0.f, ds = 0.f, tc = 0.f;
+    if (n != 0.f) {
+      tk = task / n;
+      ds = dist / n * temperature * temperature;
+      tc = teach / n;
+    }
+    out[0] = n != 0.f ? alpha * tk + (1.f - alpha) * ds : 0.f;
+    out[1] = tk; out[2] = ds; out[3] = tc; out[4] = n; out[5] = n; out[6] = 0.f; out[7] = 0.f;
   }
 }
 
@@ -257,11 +199,7 @@ __global__ __launch_bounds__(NT) void kd_bwd_kernel(const T* S, const T* __restr
   const int row = blockIdx.x;
   const RowStats st = stats[row];
   T* g = G + (long)row * V;
-  if (st.valid == 0.f) {
-    float z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int c = threadIdx.x * 8; c < V; c += NT * 8) Ld8<T>::store(g + c, z);
-    return;
-  }
+  if (st.valid == 0.f) return zero_row<T, NT>(g, V);
   const float invT = 1.f / temperature;
   const float N = loss_out[4];
   const float go = grad_out ? grad_out[0] : 1.f;
@@ -323,44 +261,6 @@ __global__ __launch_bounds__(NT) void kd_bwd_kernel(const T* S, const T* __restr
   }
 }
 
-template <typename T>
-int run_fwd(const void* S, const void* Tl, const void* topv, const void* topi, const int64_t* labels, const uint8_t* mask,
-            void* stats, float* out, int B, int Tlen, int V, int K, float temperature, float alpha, hipStream_t st) {
-  const int rows = Tlen ? B * Tlen : B;  // Tlen == 0: B pre-selected rows
-  SdProfScope prof(SD_K_LOSS_FWD, (double)rows * V * sizeof(T) * (Tl ? 2 : 1), st);
-  // the symbol as rocprofv3 --kernel-trace prints it: kd_fwd_kernel<T, T2, NF, DENSE> (same dispatch as below)
-  SD_PROF_LABEL("kd_fwd_kernel<%s, %s, %d, %s>", sizeof(T) == 2 ? "__bf16" : "float", temperature == 2.0f ? "true" : "false",
-                (Tl || K <= 512) ? 512 : 1024, Tl ? "true" : "false");
-#define SD_KD_FWD(T2_, NF_, DENSE_)                                                                                      \
-  hipLaunchKernelGGL((kd_fwd_kernel<T, T2_, NF_, DENSE_>), dim3(rows), dim3(NF_), 0, st, (const T*)S, (const T*)Tl,        \
-                     (const _Float16*)topv, (const int32_t*)topi, labels, mask, (RowStats*)stats, rows, Tlen, V, K,          \
-                     temperature)
-  const bool t2 = temperature == 2.0f;
-  if (Tl) { if (t2) SD_KD_FWD(true, 512, true); else SD_KD_FWD(false, 512, true); }
-  else if (K <= 512) { if (t2) SD_KD_FWD(true, 512, false); else SD_KD_FWD(false, 512, false); }
-  else { if (t2) SD_KD_FWD(true, 1024, false); else SD_KD_FWD(false, 1024, false); }
-#undef SD_KD_FWD
-  SD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(kd_finalize_kernel, dim3(1), dim3(NT), 0, st, (const RowStats*)stats, out, rows, temperature, alpha,
-                     Tl ? 1 : 0);
-  SD_CHECK_LAUNCH();
-  return 0;
-}
-
-template <typename T>
-int run_bwd(const void* S, const void* Tl, const void* topv, const void* topi, const int64_t* labels, const void* stats,
-            const float* out, const float* go, void* G, int B, int Tlen, int V, int K, float temperature, float alpha,
-            hipStream_t st) {
-  const int rows = Tlen ? B * Tlen : B;
-  SdProfScope prof(SD_K_LOSS_BWD, (double)rows * V * sizeof(T) * (Tl ? 3 : 2), st);
-  SD_PROF_LABEL("kd_bwd_kernel<%s>", sizeof(T) == 2 ? "__bf16" : "float");
-  hipLaunchKernelGGL((kd_bwd_kernel<T>), dim3(rows), dim3(NT), 0, st, (const T*)S, (const T*)Tl, (const _Float16*)topv,
-                     (const int32_t*)topi, labels, (const RowStats*)stats, out, go, (T*)G, rows, Tlen, V, K, temperature,
-                     alpha);
-  SD_CHECK_LAUNCH();
-  return 0;
-}
-
 int check(const void* S, const void* Tl, const void* topv, const void* topi, int B, int Tlen, int V, int K, int dtype) {
   if (B <= 0 || Tlen < 0 || V <= 0) return SD_ERR_SHAPE;
   if (V & 7) return SD_ERR_ALIGN;
@@ -371,6 +271,56 @@ int check(const void* S, const void* Tl, const void* topv, const void* topi, int
   return 0;
 }
 
+// Both forward entries: B sequences of Tlen positions, shifted and masked by the kernel (sd_kdloss_fwd), or Tlen == 0 and
+// no mask: B rows the caller already shifted and selected (sd_kdloss_fwd_rows).
+int kd_fwd(const void* S, const void* Tl, const void* topv, const void* topi, const int64_t* labels, const uint8_t* mask,
+           void* stats, float* out, int B, int Tlen, int V, int K, float temperature, float alpha, int dtype, void* stream) {
+  if (int e = check(S, Tl, topv, topi, B, Tlen, V, K, dtype)) return e;
+  hipStream_t st = (hipStream_t)stream;
+  const int rows = Tlen ? B * Tlen : B;
+  return by_dtype(dtype, [&](auto tt) -> int {
+    typedef SD_TAG_TYPE(tt) T;
+    SdProfScope prof(SD_K_LOSS_FWD, (double)rows * V * sizeof(T) * (Tl ? 2 : 1), st);
+    auto launch = [&](auto t2, auto wide, auto dense) {
+      constexpr int NF = SD_FLAG(wide) ? 1024 : 512;
+      // the symbol as rocprofv3 --kernel-trace prints it
+      SD_PROF_LABEL("kd_fwd_kernel<%s, %s, %d, %s>", type_name(sizeof(T)), flag_name(SD_FLAG(t2)), NF, flag_name(SD_FLAG(dense)));
+      hipLaunchKernelGGL((kd_fwd_kernel<T, SD_FLAG(t2), NF, SD_FLAG(dense)>), dim3(rows), dim3(NF), 0, st, (const T*)S,
+                         (const T*)Tl, (const _Float16*)topv, (const int32_t*)topi, labels, mask, (RowStats*)stats, rows, Tlen,
+                         V, K, temperature);
+    };
+    // 1024 threads only where the K teacher entries do not fit one thread each at 512
+    by_flag(temperature == 2.0f, [&](auto t2) {
+      if (Tl) launch(t2, std::false_type{}, std::true_type{});
+      else by_flag(K > 512, [&](auto wide) { launch(t2, wide, std::false_type{}); });
+    });
+    SD_CHECK_LAUNCH();
+    hipLaunchKernelGGL((kd_finalize_kernel<RowStats, true>), dim3(1), dim3(NT), 0, st, (const RowStats*)stats, out, rows,
+                       temperature, alpha, Tl ? 1 : 0);
+    SD_CHECK_LAUNCH();
+    return 0;
+  });
+}
+
+int kd_bwd(const void* S, const void* Tl, const void* topv, const void* topi, const int64_t* labels, const void* stats,
+           const float* out, const float* go, void* G, int B, int Tlen, int V, int K, float temperature, float alpha,
+           int dtype, void* stream) {
+  if (int e = check(S, Tl, topv, topi, B, Tlen, V, K, dtype)) return e;
+  if ((uintptr_t)G & 15) return SD_ERR_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  const int rows = Tlen ? B * Tlen : B;
+  return by_dtype(dtype, [&](auto tt) -> int {
+    typedef SD_TAG_TYPE(tt) T;
+    SdProfScope prof(SD_K_LOSS_BWD, (double)rows * V * sizeof(T) * (Tl ? 3 : 2), st);
+    SD_PROF_LABEL("kd_bwd_kernel<%s>", type_name(sizeof(T)));
+    hipLaunchKernelGGL((kd_bwd_kernel<T>), dim3(rows), dim3(NT), 0, st, (const T*)S, (const T*)Tl, (const _Float16*)topv,
+                       (const int32_t*)topi, labels, (const RowStats*)stats, out, go, (T*)G, rows, Tlen, V, K, temperature,
+                       alpha);
+    SD_CHECK_LAUNCH();
+    return 0;
+  });
+}
+
 }  // namespace
 
 extern "C" int64_t sd_kdloss_stats_bytes(int B, int T) { return (int64_t)B * T * sizeof(RowStats); }
@@ -378,58 +328,39 @@ extern "C" int64_t sd_kdloss_stats_bytes(int B, int T) { return (int64_t)B * T *
 extern "C" int sd_kdloss_fwd_rows(const void* student_logits, const void* teacher_logits, const void* top_k_v,
                                   const void* top_k_i, const int64_t* row_labels, void* row_stats, float* loss_out, int R,
                                   int V, int K, float temperature, float alpha, int dtype, void* stream) {
-  if (int e = check(student_logits, teacher_logits, top_k_v, top_k_i, R, 0, V, K, dtype)) return e;
-  if (dtype == SD_DTYPE_BF16)
-    return run_fwd<bf16>(student_logits, teacher_logits, top_k_v, top_k_i, row_labels, nullptr, row_stats, loss_out, R, 0,
-                         V, K, temperature, alpha, (hipStream_t)stream);
-  return run_fwd<float>(student_logits, teacher_logits, top_k_v, top_k_i, row_labels, nullptr, row_stats, loss_out, R, 0,
-                        V, K, temperature, alpha, (hipStream_t)stream);
+  return kd_fwd(student_logits, teacher_logits, top_k_v, top_k_i, row_labels, nullptr, row_stats, loss_out, R, 0, V, K,
+                temperature, alpha, dtype, stream);
 }
 
 extern "C" int sd_kdloss_bwd_rows(const void* student_logits, const void* teacher_logits, const void* top_k_v,
                                   const void* top_k_i, const int64_t* row_labels, const void* row_stats,
                                   const float* loss_out, const float* grad_total, void* grad_logits, int R, int V, int K,
                                   float temperature, float alpha, int dtype, void* stream) {
-  if (int e = check(student_logits, teacher_logits, top_k_v, top_k_i, R, 0, V, K, dtype)) return e;
-  if ((uintptr_t)grad_logits & 15) return SD_ERR_ALIGN;
-  if (dtype == SD_DTYPE_BF16)
-    return run_bwd<bf16>(student_logits, teacher_logits, top_k_v, top_k_i, row_labels, row_stats, loss_out, grad_total,
-                         grad_logits, R, 0, V, K, temperature, alpha, (hipStream_t)stream);
-  return run_bwd<float>(student_logits, teacher_logits, top_k_v, top_k_i, row_labels, row_stats, loss_out, grad_total,
-                        grad_logits, R, 0, V, K, temperature, alpha, (hipStream_t)stream);
+  return kd_bwd(student_logits, teacher_logits, top_k_v, top_k_i, row_labels, row_stats, loss_out, grad_total, grad_logits,
+                R, 0, V, K, temperature, alpha, dtype, stream);
 }
 
 extern "C" int sd_kdloss_fwd(const void* student_logits, const void* teacher_logits, const void* top_k_v,
                              const void* top_k_i, const int64_t* labels, const uint8_t* speech_mask, void* row_stats,
                              float* loss_out, int B, int T, int V, int K, float temperature, float alpha, int dtype,
                              void* stream) {
-  if (int e = check(student_logits, teacher_logits, top_k_v, top_k_i, B, T, V, K, dtype)) return e;
-  if (dtype == SD_DTYPE_BF16)
-    return run_fwd<bf16>(student_logits, teacher_logits, top_k_v, top_k_i, labels, speech_mask, row_stats, loss_out, B, T,
-                         V, K, temperature, alpha, (hipStream_t)stream);
-  return run_fwd<float>(student_logits, teacher_logits, top_k_v, top_k_i, labels, speech_mask, row_stats, loss_out, B, T,
-                        V, K, temperature, alpha, (hipStream_t)stream);
+  return kd_fwd(student_logits, teacher_logits, top_k_v, top_k_i, labels, speech_mask, row_stats, loss_out, B, T, V, K,
+                temperature, alpha, dtype, stream);
 }
 
 extern "C" int sd_kdloss_bwd(const void* student_logits, const void* teacher_logits, const void* top_k_v,
                              const void* top_k_i, const int64_t* labels, const void* row_stats, const float* loss_out,
                              const float* grad_total, void* grad_logits, int B, int T, int V, int K, float temperature,
                              float alpha, int dtype, void* stream) {
-  if (int e = check(student_logits, teacher_logits, top_k_v, top_k_i, B, T, V, K, dtype)) return e;
-  if ((uintptr_t)grad_logits & 15) return SD_ERR_ALIGN;
-  if (dtype == SD_DTYPE_BF16)
-    return run_bwd<bf16>(student_logits, teacher_logits, top_k_v, top_k_i, labels, row_stats, loss_out, grad_total,
-                         grad_logits, B, T, V, K, temperature, alpha, (hipStream_t)stream);
-  return run_bwd<float>(student_logits, teacher_logits, top_k_v, top_k_i, labels, row_stats, loss_out, grad_total,
-                        grad_logits, B, T, V, K, temperature, alpha, (hipStream_t)stream);
+  return kd_bwd(student_logits, teacher_logits, top_k_v, top_k_i, labels, row_stats, loss_out, grad_total, grad_logits, B, T,
+                V, K, temperature, alpha, dtype, stream);
 }
 
 // ---------------------------------------------------------------------------------------- causal-LM cross-entropy
 // Stage-1 alignment loss (stage1.py: TRL SFTTrainer over HF Qwen3ForCausalLM(labels=...), i.e. HF's ForCausalLMLoss:
 // logits.float(), shift by one, cross_entropy(ignore_index=-100, reduction = "sum" / num_items_in_batch when the Trainer
 // passes num_items_in_batch, else "mean")) on rows the caller already shifted and selected -- the teacher-free
-// counterpart of sd_kdloss_*_rows.  Same row streaming as kd_fwd_kernel (PF chunks in flight per thread, unconditional
-// loads), one exponential per logit; per-row stats + a fixed-order single-block finalize: deterministic, no atomics.
+// counterpart of sd_kdloss_*_rows.  Same row streaming as kd_fwd_kernel (row_sweep), one exponential per logit; per-row stats + a fixed-order single-block finalize: deterministic, no atomics.
 namespace {
 
 struct CeStats {  // 4 floats per row
@@ -449,33 +380,16 @@ __global__ __launch_bounds__(NF) void ce_fwd_kernel(const T* __restrict__ S, con
   const float k1 = 1.4426950408889634f;  // log2(e)
   const T* s = S + (long)row * V;
   float m = -INFINITY, s1 = 0.f;
-  constexpr int PF = 4;
-  typedef typename Ld8<T>::Raw Raw;
-  const int stride = NF * 8;
-  Raw sbuf[PF];
-  const int clast = ((V - 1) >> 3) << 3;
-#pragma unroll
-  for (int j = 0; j < PF; ++j) sbuf[j] = Ld8<T>::raw(s + min((int)threadIdx.x * 8 + j * stride, clast));
-  for (int c0 = threadIdx.x * 8; c0 < V; c0 += PF * stride) {
-#pragma unroll
-    for (int j = 0; j < PF; ++j) {
-      const int c = c0 + j * stride;
-      float f[8];
-      Ld8<T>::cvt(sbuf[j], f);
-      sbuf[j] = Ld8<T>::raw(s + min(c + PF * stride, clast));
-      if (c >= V) continue;
-      float cm = f[0];
-#pragma unroll
-      for (int e = 1; e < 8; ++e) cm = fmaxf(cm, f[e]);
-      if (cm > m) {
-        s1 *= __builtin_amdgcn_exp2f((m - cm) * k1);
-        m = cm;
-      }
-      const float mk1 = -m * k1;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s1 += __builtin_amdgcn_exp2f(__builtin_fmaf(f[e], k1, mk1));
+  row_sweep<T, NF, false>(s, (const T*)nullptr, V, [&](int, const float* f, const float*) {
+    const float cm = chunk_max8(f);
+    if (cm > m) {  // one sum, rescaled with exp2 (online_raise, for kd_fwd_kernel's two sums, rescales with __expf)
+      s1 *= __builtin_amdgcn_exp2f((m - cm) * k1);
+      m = cm;
     }
-  }
+    const float mk1 = -m * k1;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s1 += __builtin_amdgcn_exp2f(__builtin_fmaf(f[e], k1, mk1));
+  });
   const float M = block_max<NF>(m, sc);
   s1 = block_sum<NF>(m == -INFINITY ? 0.f : s1 * __expf(m - M), sc);
   const float lse = M + __logf(s1);
@@ -512,11 +426,7 @@ __global__ __launch_bounds__(NT) void ce_bwd_kernel(const T* S, const int64_t* _
   const CeStats st = stats[row];
   T* g = G + (long)row * V;
   const float d = loss_out[3];
-  if (st.valid == 0.f || d == 0.f) {
-    float z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int c = threadIdx.x * 8; c < V; c += NT * 8) Ld8<T>::store(g + c, z);
-    return;
-  }
+  if (st.valid == 0.f || d == 0.f) return zero_row<T, NT>(g, V);
   const float a = (grad_out ? grad_out[0] : 1.f) / d;
   const long y = labels[row];
   const T* s = S + (long)row * V;
@@ -546,17 +456,16 @@ extern "C" int sd_celoss_fwd_rows(const void* logits, const int64_t* row_labels,
                                   float* loss_out, int R, int V, int dtype, void* stream) {
   if (int e = ce_check(logits, row_labels, R, V, dtype)) return e;
   hipStream_t st = (hipStream_t)stream;
-  {
-    SdProfScope prof(SD_K_LOSS_FWD, (double)R * V * (dtype == SD_DTYPE_BF16 ? 2 : 4), st);
-    SD_PROF_LABEL("ce_fwd_kernel<%s, 512>", dtype == SD_DTYPE_BF16 ? "__bf16" : "float");
-    if (dtype == SD_DTYPE_BF16)
-      hipLaunchKernelGGL((ce_fwd_kernel<bf16, 512>), dim3(R), dim3(512), 0, st, (const bf16*)logits, row_labels,
-                         (CeStats*)row_stats, V);
-    else
-      hipLaunchKernelGGL((ce_fwd_kernel<float, 512>), dim3(R), dim3(512), 0, st, (const float*)logits, row_labels,
-                         (CeStats*)row_stats, V);
-    SD_CHECK_LAUNCH();
-  }
+  if (int e = by_dtype(dtype, [&](auto tt) -> int {
+        typedef SD_TAG_TYPE(tt) T;
+        SdProfScope prof(SD_K_LOSS_FWD, (double)R * V * sizeof(T), st);
+        SD_PROF_LABEL("ce_fwd_kernel<%s, 512>", type_name(sizeof(T)));
+        hipLaunchKernelGGL((ce_fwd_kernel<T, 512>), dim3(R), dim3(512), 0, st, (const T*)logits, row_labels,
+                           (CeStats*)row_stats, V);
+        SD_CHECK_LAUNCH();
+        return 0;
+      }))
+    return e;
   hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(NT), 0, st, (const CeStats*)row_stats, divisor, loss_out, R);
   SD_CHECK_LAUNCH();
   return 0;
@@ -568,16 +477,15 @@ extern "C" int sd_celoss_bwd_rows(const void* logits, const int64_t* row_labels,
   if (int e = ce_check(logits, row_labels, R, V, dtype)) return e;
   if ((uintptr_t)grad_logits & 15) return SD_ERR_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-  SdProfScope prof(SD_K_LOSS_BWD, (double)R * V * (dtype == SD_DTYPE_BF16 ? 2 : 4) * 2, st);
-  SD_PROF_LABEL("ce_bwd_kernel<%s>", dtype == SD_DTYPE_BF16 ? "__bf16" : "float");
-  if (dtype == SD_DTYPE_BF16)
-    hipLaunchKernelGGL((ce_bwd_kernel<bf16>), dim3(R), dim3(NT), 0, st, (const bf16*)logits, row_labels,
-                       (const CeStats*)row_stats, loss_out, grad_total, (bf16*)grad_logits, V);
-  else
-    hipLaunchKernelGGL((ce_bwd_kernel<float>), dim3(R), dim3(NT), 0, st, (const float*)logits, row_labels,
-                       (const CeStats*)row_stats, loss_out, grad_total, (float*)grad_logits, V);
-  SD_CHECK_LAUNCH();
-  return 0;
+  return by_dtype(dtype, [&](auto tt) -> int {
+    typedef SD_TAG_TYPE(tt) T;
+    SdProfScope prof(SD_K_LOSS_BWD, (double)R * V * sizeof(T) * 2, st);
+    SD_PROF_LABEL("ce_bwd_kernel<%s>", type_name(sizeof(T)));
+    hipLaunchKernelGGL((ce_bwd_kernel<T>), dim3(R), dim3(NT), 0, st, (const T*)logits, row_labels, (const CeStats*)row_stats,
+                       loss_out, grad_total, (T*)grad_logits, V);
+    SD_CHECK_LAUNCH();
+    return 0;
+  });
 }
 
 // ---------------------------------------------------------------------------------------- loss rows
@@ -670,8 +578,7 @@ extern "C" int sd_loss_rows(const int64_t* labels, const int64_t* speech_mask, c
 // so the 2 x V x sizeof(T) bytes of sweep 2 (638 KB at V = 159 488 bf16) were read by this same workgroup microseconds
 // before, where a second launch would re-read 0.98 GB behind a full grid.  With 512 row pairs in flight (327 MB, more than
 // the Infinity Cache) only part of sweep 2 is served on-die: measured, it costs 0.7 x of an HBM sweep.
-// Same streaming as kd_fwd_kernel (512 threads, PF chunks in flight per thread, unconditional loads with the clamped
-// re-read of the last chunk, exp2, the T == 2 squaring).  Transcendentals per logit pair:
+// Same streaming as kd_fwd_kernel (512 threads, row_sweep, exp2, the T == 2 squaring).  Transcendentals per logit pair:
 // sweep 1: 2 at T == 2, else 4; sweep 2: reverse KL 1 (exp), JSD 3 (exp, exp, log); backward: one more exp for
 // softmax(s) unless T == 2, where softmax(s)_j = q_j^2 exp(2 lseT - lse1).
 // 0 log 0 = 0: an element whose q (or p) underflows contributes 0 -- guarded by a select, not by a log-domain logaddexp;
@@ -687,41 +594,7 @@ struct GjsdStats {  // 12 floats per row; m .. c are what the backward reads: ls
 };
 
 constexpr int GJ_NF = 512;  // threads per row, as kd_fwd_kernel's dense variant (here 2 to 4 workgroups per CU by VGPRs)
-constexpr int GJ_PF = 4;    // chunks in flight per thread and row
 constexpr float GJ_LN2 = 0.6931471805599453f, GJ_LOG2E = 1.4426950408889634f, GJ_FLT_MIN = 1.17549435e-38f;
-
-// Streams the row pair through `body(c, f, g)` (c: first element of the 8-element chunk, f / g its student / teacher
-// values), every thread seeing its chunks in increasing order.  The loads are the ones of kd_fwd_kernel: GJ_PF chunks
-// per thread in flight, each slot refilled before the arithmetic on it, all unconditional.  `body` may store to chunk c
-// of a buffer that aliases `s`: a thread only ever reads ahead in its OWN chunks (which it has not written yet), and the
-// clamped re-read of the last chunk is never used.
-template <typename T, typename F>
-SD_DEV void gj_sweep(const T* s, const T* tl, int V, F&& body) {
-  typedef typename Ld8<T>::Raw Raw;
-  constexpr int stride = GJ_NF * 8;
-  Raw sbuf[GJ_PF], tbuf[GJ_PF];
-  const int clast = ((V - 1) >> 3) << 3;
-#pragma unroll
-  for (int j = 0; j < GJ_PF; ++j) {
-    const int cj = min((int)threadIdx.x * 8 + j * stride, clast);
-    sbuf[j] = Ld8<T>::raw(s + cj);
-    tbuf[j] = Ld8<T>::raw(tl + cj);
-  }
-  for (int c0 = threadIdx.x * 8; c0 < V; c0 += GJ_PF * stride) {
-#pragma unroll
-    for (int j = 0; j < GJ_PF; ++j) {
-      const int c = c0 + j * stride;
-      float f[8], g[8];
-      Ld8<T>::cvt(sbuf[j], f);
-      Ld8<T>::cvt(tbuf[j], g);
-      const int cn = min(c + GJ_PF * stride, clast);
-      sbuf[j] = Ld8<T>::raw(s + cn);
-      tbuf[j] = Ld8<T>::raw(tl + cn);
-      if (c >= V) continue;
-      body(c, f, g);
-    }
-  }
-}
 
 // one element of sweep 2 / of the backward: q and (in log2 units) log q - log p, or log q - log m.
 // m, mt: the row maxima; A0, B0: -log2 of the max-subtracted sums at T
@@ -759,18 +632,9 @@ __global__ __launch_bounds__(GJ_NF) void gjsd_fwd_kernel(const T* __restrict__ S
   const T* tl = Tl + (long)row * V;
   // ---- sweep 1: the four normalisers (kd_fwd_kernel's dense sweep without its cross term)
   float m = -INFINITY, s1 = 0.f, sT = 0.f, mt = -INFINITY, t1 = 0.f, tT = 0.f;
-  gj_sweep<T>(s, tl, V, [&](int, const float* f, const float* g) {
-    float cm = f[0], tm = g[0];
-#pragma unroll
-    for (int e = 1; e < 8; ++e) { cm = fmaxf(cm, f[e]); tm = fmaxf(tm, g[e]); }
-    if (cm > m) {
-      const float rT = __expf((m - cm) * invT), r1 = T2 ? rT * rT : __expf(m - cm);
-      s1 *= r1; sT *= rT; m = cm;
-    }
-    if (tm > mt) {
-      const float rT = __expf((mt - tm) * invT), r1 = T2 ? rT * rT : __expf(mt - tm);
-      t1 *= r1; tT *= rT; mt = tm;
-    }
+  row_sweep<T, GJ_NF, true>(s, tl, V, [&](int, const float* f, const float* g) {
+    online_raise<T2>(chunk_max8(f), invT, m, s1, sT);
+    online_raise<T2>(chunk_max8(g), invT, mt, t1, tT);
     // exp2((f - m) kT), NOT kd_fwd_kernel's folded exp2(f kT - m kT): the fold leaves the rounding error of m kT in every
     // exponent (the maximum itself gives 1 + 1e-6 instead of 1).  A forward KL forgives that, it shifts lse(s) and the
     // cross term alike; here log q and log p each take their own shift, which on a peaked row near its teacher is
@@ -793,7 +657,7 @@ __global__ __launch_bounds__(GJ_NF) void gjsd_fwd_kernel(const T* __restrict__ S
   // ---- sweep 2: the divergence terms, in log2 units (one multiplication by ln 2 per row)
   const float A0 = -lsT, B0 = -ltT;
   float accq = 0.f, accp = 0.f;
-  gj_sweep<T>(s, tl, V, [&](int, const float* f, const float* g) {
+  row_sweep<T, GJ_NF, true>(s, tl, V, [&](int, const float* f, const float* g) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       float q, dq, p, dp;
@@ -812,29 +676,7 @@ __global__ __launch_bounds__(GJ_NF) void gjsd_fwd_kernel(const T* __restrict__ S
                            (mt - (float)tl[y]) + lt1 * GJ_LN2, 0.f, 0.f};
 }
 
-// out[0..7] = total, task, distill, teacher, N, N, 0, 0      (single block, fixed order)
-__global__ __launch_bounds__(NT) void gjsd_finalize_kernel(const GjsdStats* __restrict__ stats, float* __restrict__ out,
-                                                           int rows, float temperature, float alpha) {
-  __shared__ float sc[32];
-  float n = 0, task = 0, dist = 0, teach = 0;
-  for (int r = threadIdx.x; r < rows; r += NT) {
-    const GjsdStats st = stats[r];
-    n += st.valid; task += st.task; dist += st.distill; teach += st.teacher;
-  }
-  n = block_sum<NT>(n, sc); task = block_sum<NT>(task, sc); dist = block_sum<NT>(dist, sc); teach = block_sum<NT>(teach, sc);
-  if (threadIdx.x == 0) {
-    float tk = 0.f, ds = 0.f, tc = 0.f;
-    if (n != 0.f) {
-      tk = task / n;
-      ds = dist / n * temperature * temperature;
-      tc = teach / n;
-    }
-    out[0] = n != 0.f ? alpha * tk + (1.f - alpha) * ds : 0.f;
-    out[1] = tk; out[2] = ds; out[3] = tc; out[4] = n; out[5] = n; out[6] = 0.f; out[7] = 0.f;
-  }
-}
-
-// One read of both rows, one write of the gradient; G may alias S (see gj_sweep).
+// One read of both rows, one write of the gradient; G may alias S (see row_sweep).
 template <typename T, bool T2, bool JSD>
 __global__ __launch_bounds__(GJ_NF) void gjsd_bwd_kernel(const T* S, const T* __restrict__ Tl,
                                                          const int64_t* __restrict__ labels,
@@ -845,11 +687,7 @@ __global__ __launch_bounds__(GJ_NF) void gjsd_bwd_kernel(const T* S, const T* __
   const int row = blockIdx.x;
   const GjsdStats st = stats[row];
   T* gr = G + (long)row * V;
-  if (st.valid == 0.f) {
-    float z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int c = threadIdx.x * 8; c < V; c += GJ_NF * 8) Ld8<T>::store(gr + c, z);
-    return;
-  }
+  if (st.valid == 0.f) return zero_row<T, GJ_NF>(gr, V);
   const float invT = 1.f / temperature;
   const float k1 = GJ_LOG2E, kT = invT * k1;
   const float N = loss_out[4];
@@ -860,7 +698,7 @@ __global__ __launch_bounds__(GJ_NF) void gjsd_bwd_kernel(const T* S, const T* __
   const long y = labels[row];
   const float A0 = -st.lsT, B0 = -st.ltT, L1 = -st.ls1;
   const float r1 = T2 ? __builtin_amdgcn_exp2f(2.f * st.lsT - st.ls1) : 0.f;  // softmax(s) = q^2 r1 at T == 2
-  gj_sweep<T>(S + (long)row * V, Tl + (long)row * V, V, [&](int c, const float* f, const float* g) {
+  row_sweep<T, GJ_NF, true>(S + (long)row * V, Tl + (long)row * V, V, [&](int c, const float* f, const float* g) {
     float o[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -888,42 +726,9 @@ int gjsd_check(const void* S, const void* Tl, const int64_t* labels, const void*
   return 0;
 }
 
-template <typename T>
-int gjsd_run_fwd(const void* S, const void* Tl, const int64_t* labels, void* stats, float* out, int R, int V,
-                 float temperature, float alpha, float beta, int mode, hipStream_t st) {
-  {
-    SdProfScope prof(SD_K_LOSS_FWD, (double)R * V * sizeof(T) * 2, st);
-    SD_PROF_LABEL("gjsd_fwd_kernel<%s, %s, %s>", sizeof(T) == 2 ? "__bf16" : "float", temperature == 2.0f ? "true" : "false",
-                  mode == SD_DIV_JSD ? "true" : "false");
-#define SD_GJ_FWD(T2_, JSD_)                                                                                              \
-  hipLaunchKernelGGL((gjsd_fwd_kernel<T, T2_, JSD_>), dim3(R), dim3(GJ_NF), 0, st, (const T*)S, (const T*)Tl, labels,        \
-                     (GjsdStats*)stats, V, temperature, beta)
-    const bool t2 = temperature == 2.0f, jsd = mode == SD_DIV_JSD;
-    if (t2) { if (jsd) SD_GJ_FWD(true, true); else SD_GJ_FWD(true, false); }
-    else { if (jsd) SD_GJ_FWD(false, true); else SD_GJ_FWD(false, false); }
-#undef SD_GJ_FWD
-    SD_CHECK_LAUNCH();
-  }
-  hipLaunchKernelGGL(gjsd_finalize_kernel, dim3(1), dim3(NT), 0, st, (const GjsdStats*)stats, out, R, temperature, alpha);
-  SD_CHECK_LAUNCH();
-  return 0;
-}
-
-template <typename T>
-int gjsd_run_bwd(const void* S, const void* Tl, const int64_t* labels, const void* stats, const float* out, const float* go,
-                 void* G, int R, int V, float temperature, float alpha, float beta, int mode, hipStream_t st) {
-  SdProfScope prof(SD_K_LOSS_BWD, (double)R * V * sizeof(T) * 3, st);
-  SD_PROF_LABEL("gjsd_bwd_kernel<%s, %s, %s>", sizeof(T) == 2 ? "__bf16" : "float", temperature == 2.0f ? "true" : "false",
-                mode == SD_DIV_JSD ? "true" : "false");
-#define SD_GJ_BWD(T2_, JSD_)                                                                                              \
-  hipLaunchKernelGGL((gjsd_bwd_kernel<T, T2_, JSD_>), dim3(R), dim3(GJ_NF), 0, st, (const T*)S, (const T*)Tl, labels,        \
-                     (const GjsdStats*)stats, out, go, (T*)G, V, temperature, alpha, beta)
-  const bool t2 = temperature == 2.0f, jsd = mode == SD_DIV_JSD;
-  if (t2) { if (jsd) SD_GJ_BWD(true, true); else SD_GJ_BWD(true, false); }
-  else { if (jsd) SD_GJ_BWD(false, true); else SD_GJ_BWD(false, false); }
-#undef SD_GJ_BWD
-  SD_CHECK_LAUNCH();
-  return 0;
+// fn(T2, JSD): the two flags every gjsd kernel is instantiated over
+template <typename F> void gjsd_flags(float temperature, int mode, F&& fn) {
+  by_flag(temperature == 2.0f, [&](auto t2) { by_flag(mode == SD_DIV_JSD, [&](auto jsd) { fn(t2, jsd); }); });
 }
 
 }  // namespace
@@ -935,11 +740,24 @@ extern "C" int sd_gjsd_fwd_rows(const void* student_logits, const void* teacher_
                                 int mode, int dtype, void* stream) {
   if (int e = gjsd_check(student_logits, teacher_logits, row_labels, row_stats, loss_out, R, V, temperature, beta, mode, dtype))
     return e;
-  if (dtype == SD_DTYPE_BF16)
-    return gjsd_run_fwd<bf16>(student_logits, teacher_logits, row_labels, row_stats, loss_out, R, V, temperature, alpha, beta,
-                              mode, (hipStream_t)stream);
-  return gjsd_run_fwd<float>(student_logits, teacher_logits, row_labels, row_stats, loss_out, R, V, temperature, alpha, beta,
-                             mode, (hipStream_t)stream);
+  hipStream_t st = (hipStream_t)stream;
+  if (int e = by_dtype(dtype, [&](auto tt) -> int {
+        typedef SD_TAG_TYPE(tt) T;
+        SdProfScope prof(SD_K_LOSS_FWD, (double)R * V * sizeof(T) * 2, st);
+        gjsd_flags(temperature, mode, [&](auto t2, auto jsd) {
+          SD_PROF_LABEL("gjsd_fwd_kernel<%s, %s, %s>", type_name(sizeof(T)), flag_name(SD_FLAG(t2)), flag_name(SD_FLAG(jsd)));
+          hipLaunchKernelGGL((gjsd_fwd_kernel<T, SD_FLAG(t2), SD_FLAG(jsd)>), dim3(R), dim3(GJ_NF), 0, st,
+                             (const T*)student_logits, (const T*)teacher_logits, row_labels, (GjsdStats*)row_stats, V,
+                             temperature, beta);
+        });
+        SD_CHECK_LAUNCH();
+        return 0;
+      }))
+    return e;
+  hipLaunchKernelGGL((kd_finalize_kernel<GjsdStats, false>), dim3(1), dim3(NT), 0, st, (const GjsdStats*)row_stats, loss_out,
+                     R, temperature, alpha, 1);
+  SD_CHECK_LAUNCH();
+  return 0;
 }
 
 extern "C" int sd_gjsd_bwd_rows(const void* student_logits, const void* teacher_logits, const int64_t* row_labels,
@@ -949,9 +767,17 @@ extern "C" int sd_gjsd_bwd_rows(const void* student_logits, const void* teacher_
     return e;
   if (!grad_logits) return SD_ERR_SHAPE;
   if ((uintptr_t)grad_logits & 15) return SD_ERR_ALIGN;
-  if (dtype == SD_DTYPE_BF16)
-    return gjsd_run_bwd<bf16>(student_logits, teacher_logits, row_labels, row_stats, loss_out, grad_total, grad_logits, R, V,
-                              temperature, alpha, beta, mode, (hipStream_t)stream);
-  return gjsd_run_bwd<float>(student_logits, teacher_logits, row_labels, row_stats, loss_out, grad_total, grad_logits, R, V,
-                             temperature, alpha, beta, mode, (hipStream_t)stream);
+  hipStream_t st = (hipStream_t)stream;
+  return by_dtype(dtype, [&](auto tt) -> int {
+    typedef SD_TAG_TYPE(tt) T;
+    SdProfScope prof(SD_K_LOSS_BWD, (double)R * V * sizeof(T) * 3, st);
+    gjsd_flags(temperature, mode, [&](auto t2, auto jsd) {
+      SD_PROF_LABEL("gjsd_bwd_kernel<%s, %s, %s>", type_name(sizeof(T)), flag_name(SD_FLAG(t2)), flag_name(SD_FLAG(jsd)));
+      hipLaunchKernelGGL((gjsd_bwd_kernel<T, SD_FLAG(t2), SD_FLAG(jsd)>), dim3(R), dim3(GJ_NF), 0, st,
+                         (const T*)student_logits, (const T*)teacher_logits, row_labels, (const GjsdStats*)row_stats, loss_out,
+                         grad_total, (T*)grad_logits, V, temperature, alpha, beta);
+    });
+    SD_CHECK_LAUNCH();
+    return 0;
+  });
 }

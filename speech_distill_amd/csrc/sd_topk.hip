@@ -8,7 +8,7 @@
 // value go to the LOWEST indices.  One 512-thread workgroup per row, two resident per CU; the row is re-read from
 // L2/Infinity Cache by the later radix passes, so HBM sees it about once.
 #include <stdlib.h>
-#include "sd_common.cuh"
+#include "sd_rows.cuh"
 #include "../../include/sd_hip.h"
 #include "sd_prof.h"
 #include "sd_debug.h"
@@ -24,29 +24,6 @@ SD_DEV uint32_t f2key(float f) {
 SD_DEV float key2f(uint32_t k) {
   const uint32_t u = (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
   return __uint_as_float(u);
-}
-
-template <typename T> struct Raw8;
-template <> struct Raw8<bf16> { typedef bf16x8 R; };
-template <> struct Raw8<float> { struct R { f32x4 a, b; }; };
-SD_DEV bf16x8 raw8(const bf16* p) { return *(const bf16x8*)p; }
-SD_DEV Raw8<float>::R raw8(const float* p) { return Raw8<float>::R{*(const f32x4*)p, *(const f32x4*)(p + 4)}; }
-SD_DEV void cvt8(const bf16x8& v, float* f) {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) f[e] = (float)v[e];
-}
-SD_DEV void cvt8(const Raw8<float>::R& v, float* f) {
-  f[0] = v.a[0]; f[1] = v.a[1]; f[2] = v.a[2]; f[3] = v.a[3]; f[4] = v.b[0]; f[5] = v.b[1]; f[6] = v.b[2]; f[7] = v.b[3];
-}
-template <typename T> SD_DEV void load8(const T* p, float* f);
-template <> SD_DEV void load8<bf16>(const bf16* p, float* f) {
-  bf16x8 v = *(const bf16x8*)p;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) f[e] = (float)v[e];
-}
-template <> SD_DEV void load8<float>(const float* p, float* f) {
-  f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
-  f[0] = a[0]; f[1] = a[1]; f[2] = a[2]; f[3] = a[3]; f[4] = b[0]; f[5] = b[1]; f[6] = b[2]; f[7] = b[3];
 }
 
 // wave-aggregated histogram increment: lanes with the same bin share one LDS atomic
@@ -137,43 +114,37 @@ __global__ __launch_bounds__(NT) void topk_kernel(const T* __restrict__ X, _Floa
   constexpr int MAXCH = (NT == 512) ? 40 : (NT == 1024 ? 20 : 0);
   const bool keep_max = MAXCH > 0 && V <= MAXCH * NT * 8;
   float cmx[MAXCH > 0 ? MAXCH : 1];
+  // one chunk of the online log-sum-exp (a single sum, at T = 1); -> the chunk's maximum
+  auto lse_chunk = [&](const float* f) {
+    const float cm = chunk_max8(f);
+    if (cm > m) { s *= __expf(m - cm); m = cm; }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s += __expf(f[e] - m);
+    return cm;
+  };
   if (keep_max) {
-    // PF chunks per thread in flight (one load per trip leaves a CU's 32 waves with 32 KB outstanding: ~4 TB/s at the
-    // loaded HBM latency, whatever the arithmetic); the chunks are consumed in the same order
-    constexpr int PF = 4;
-    typename Raw8<T>::R buf[PF];
-    // every load is UNCONDITIONAL (a chunk past the end re-reads the row's last one and is not used): with loads behind
-    // branches hipcc's wait insertion falls back to vmcnt(0) at every use and drains the chunks in flight
+    // The streamed read of row_sweep (sd_rows.cuh: ROW_PF chunks per thread in flight, every load unconditional with the
+    // clamped re-read of the last chunk, the same chunk order), unrolled at compile time because cmx[] is indexed by
+    // the trip
+    constexpr int PF = ROW_PF;
+    typename Ld8<T>::Raw buf[PF];
     const int clast = ((V - 1) >> 3) << 3;  // start of the row's last chunk
 #pragma unroll
-    for (int j = 0; j < PF; ++j) buf[j] = raw8(x + min((j * NT + (int)threadIdx.x) * 8, clast));
+    for (int j = 0; j < PF; ++j) buf[j] = Ld8<T>::raw(x + min((j * NT + (int)threadIdx.x) * 8, clast));
 #pragma unroll
     for (int i = 0; i < MAXCH; ++i) {
       const int c = (i * NT + (int)threadIdx.x) * 8;
       cmx[i] = -INFINITY;
       float f[8];
-      cvt8(buf[i % PF], f);
-      if (i + PF < MAXCH) buf[i % PF] = raw8(x + min(((i + PF) * NT + (int)threadIdx.x) * 8, clast));
-      if (c < V) {
-        float cm = f[0];
-#pragma unroll
-        for (int e = 1; e < 8; ++e) cm = fmaxf(cm, f[e]);
-        if (cm > m) { s *= __expf(m - cm); m = cm; }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += __expf(f[e] - m);
-        cmx[i] = cm;
-      }
+      Ld8<T>::cvt(buf[i % PF], f);
+      if (i + PF < MAXCH) buf[i % PF] = Ld8<T>::raw(x + min(((i + PF) * NT + (int)threadIdx.x) * 8, clast));
+      if (c < V) cmx[i] = lse_chunk(f);
     }
   } else {
     for (int c = threadIdx.x * 8; c < V; c += NT * 8) {
       float f[8];
-      load8<T>(x + c, f);
-      float cm = f[0];
-#pragma unroll
-      for (int e = 1; e < 8; ++e) cm = fmaxf(cm, f[e]);
-      if (cm > m) { s *= __expf(m - cm); m = cm; }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s += __expf(f[e] - m);
+      Ld8<T>::load(x + c, f);
+      lse_chunk(f);
     }
   }
   tkeys[threadIdx.x] = (m == -INFINITY) ? 0u : f2key(m);
@@ -207,7 +178,7 @@ __global__ __launch_bounds__(NT) void topk_kernel(const T* __restrict__ X, _Floa
     // (from L2 / Infinity Cache); rows too long for the register-resident maxima are re-read whole
     auto gather = [&](int c) {
       float f[8];
-      load8<T>(x + c, f);
+      Ld8<T>::load(x + c, f);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const uint32_t k = f2key(f[e]);
@@ -252,7 +223,7 @@ __global__ __launch_bounds__(NT) void topk_kernel(const T* __restrict__ X, _Floa
         const int c = c0 + threadIdx.x * 8;
         const bool in = c < V;
         float f[8];
-        if (in) load8<T>(x + c, f);
+        if (in) Ld8<T>::load(x + c, f);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           const uint32_t k = in ? f2key(f[e]) : 0u;
@@ -275,7 +246,7 @@ __global__ __launch_bounds__(NT) void topk_kernel(const T* __restrict__ X, _Floa
       float f[8];
       uint32_t kk[8];
       int nt_mine = 0;
-      if (in) load8<T>(x + c, f);
+      if (in) Ld8<T>::load(x + c, f);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         kk[e] = in ? f2key(f[e]) : 0u;

@@ -33,8 +33,8 @@ MODES = ("reverse_kl", "jsd")
 # (divergence, beta, temperature) of every loss case; beta is ignored by reverse_kl
 GJSD_MODES = [("reverse_kl", 0.5, 2.0), ("reverse_kl", 0.5, 3.0), ("jsd", 0.5, 2.0), ("jsd", 0.1, 3.0), ("jsd", 0.9, 1.0)]
 UNDERFLOW_MODES = [("reverse_kl", 0.5, 1.0), ("jsd", 0.5, 1.0), ("jsd", 0.9, 1.0)]
-# vocabulary edges of gjsd_*_kernel's streaming loop (512 threads per row, 4 chunks of 8 in flight per thread, the loop of
-# kd_fwd_kernel's dense variant): one chunk in all, one chunk per thread, exactly one prefetch trip, one chunk more
+# vocabulary edges of gjsd_*_kernel's streaming loop (512 threads per row, 4 chunks of 8 in flight per thread: row_sweep of
+# csrc/sd_rows.cuh, as kd_fwd_kernel's dense variant): one chunk in all, one chunk per thread, exactly one prefetch trip, one chunk more
 GJSD_EDGE_V = (8, 4096, 16384, 16392)
 GJSD_V = P.LOSS_V
 GJSD_ALPHA = P.LOSS_ALPHA

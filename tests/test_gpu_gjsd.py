@@ -3,7 +3,7 @@ reference of tests/gjsd_ref.py, per row and per element; tests/test_gjsd_ref_cpu
 teeth and where its tolerances come from.
 
 Shapes.  gjsd_fwd_kernel / gjsd_bwd_kernel stream a row with 512 threads and four 8-element chunks in flight per thread,
-the loop of kd_fwd_kernel's dense variant, so the vocabulary edges are the same four: V = 8 (one chunk in all), 4096 (one
+the row_sweep of csrc/sd_rows.cuh that kd_fwd_kernel's dense variant calls too, so the vocabulary edges are the same four: V = 8 (one chunk in all), 4096 (one
 chunk per thread), 16 384 (exactly one prefetch trip), 16 392 (one chunk more); the case table runs at V = 40 008 (9.8
 chunks per thread: several trips, a ragged last one).  Every case covers both sweeps of the forward and the backward.
 """
@@ -95,7 +95,7 @@ def _check_case(ops, family, V, dtype, mode):
         assert got[4] == 1.0 and got[5] == 1.0
         rows.append(got)
     rows = np.array(rows, dtype=np.float64)
-    # gjsd_finalize_kernel adds at most 8 row terms in fp32 and divides: a dozen roundings of numbers no larger than the
+    # kd_finalize_kernel<GjsdStats, false> adds at most 8 row terms in fp32 and divides: a dozen roundings of numbers no larger than the
     # sum of the rows' magnitudes (the bound of tests/test_gpu_loss_topk_optim.py)
     for j, what in enumerate(("total", "task", "distill", "teacher")):
         mean, tol = rows[:, j].mean(), 16 * ULP32 * np.abs(rows[:, j]).sum() / n
