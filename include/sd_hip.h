@@ -250,6 +250,20 @@ int sd_logsoftmax_topk(const void* logits, void* top_v, void* top_i, float* lse_
 int sd_loss_rows(const int64_t* labels, const int64_t* speech_mask, const int64_t* mask_a, const int64_t* mask_b,
                  int64_t* rows, int64_t* row_labels, int32_t* meta, int B, int T, void* stream);
 
+/* ---- the same selection over packed documents (sd_varlen's layout: labels int64 [M], document s = the flat tokens
+ * [cu_seqlens[s], cu_seqlens[s+1]), int32 [n_seqs + 1] in device memory).  Flat token m is a loss row iff m + 1 < M, m + 1
+ * lies in the same document as m (the last token of a document predicts nothing, whatever the label of the next document's
+ * first token), labels[m+1] != -100 and (with a mask) speech_mask[m+1] != 0.  rows / row_labels: int64 [M] out, as above.
+ * meta int32 [4] in device memory, ONE 16-byte host read for everything a packed step needs on the host:
+ *   meta[0] row count;
+ *   meta[1] error bits: bit 0 when cu_seqlens[0] != 0, cu_seqlens[n_seqs] != M or the array decreases anywhere; bit 1 when
+ *           position_ids is given and holds a negative value;
+ *   meta[2] the longest document;  meta[3] the largest position (0 without position_ids; int64 [M], nullable).
+ * Empty documents are allowed.  With a malformed cu_seqlens the kernel still reads and writes only inside [0, M) (the
+ * contract of sd_varlen).  SD_ERR_SHAPE: a NULL required pointer, M <= 0, n_seqs <= 0 or M > 2^30. */
+int sd_packed_rows(const int64_t* labels, const int64_t* speech_mask, const int32_t* cu_seqlens, int n_seqs,
+                   const int64_t* position_ids, int64_t* rows, int64_t* row_labels, int32_t* meta, int M, void* stream);
+
 /* ---- DistillationLoss.forward / backward (distillation_loss.py:14-128).
  * student_logits [B,T,V] (bf16 or fp32 per `dtype`); exactly one of teacher_logits [B,T,V] (dense) or
  * (top_k_v fp16, top_k_i int32) [B,T,K] (sparse); labels int64 [B,T]; speech_mask uint8 [B,T] nullable.

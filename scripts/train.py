@@ -99,7 +99,17 @@ def parse_args(argv=None):
     p.add_argument("--on_policy_decode_kernels", choices=("tile", "skinny", "wide"), default="tile")
     p.add_argument("--log_json", default=None, help="(+) write trainer.state.log_history there (rank 0; every rank if the "
                    "path contains {rank})")
-    return p.parse_args(argv)
+    # (+) padding-free packed batches; the defaults are the reference's right-padded [B, T] batches
+    p.add_argument("--padding_free", action="store_true",
+                   help="(+) collate each batch's samples into one row without padding (varlen attention per document)")
+    p.add_argument("--pack_tokens", type=int, default=0,
+                   help="(+) implies --padding_free: bin the samples best-fit-decreasing under this many tokens per packed "
+                        "row; --per_device_train_batch_size then counts bins")
+    cfg = p.parse_args(argv)
+    if cfg.pack_tokens < 0:
+        p.error("--pack_tokens must be positive")
+    cfg.padding_free = cfg.padding_free or cfg.pack_tokens > 0
+    return cfg
 
 
 def distill_kwargs(cfg, pad=None):
@@ -108,6 +118,9 @@ def distill_kwargs(cfg, pad=None):
     if cfg.divergence != "forward_kl" and cfg.top_k > 0 and not (cfg.load_teacher_in_4bit or cfg.load_teacher_in_8bit):
         raise SystemExit(f"--divergence {cfg.divergence} needs the dense teacher distribution: pass --top_k 0 "
                          f"(got --top_k {cfg.top_k}; a top-K teacher defines it on K entries only)")
+    if cfg.lmbda > 0 and cfg.padding_free:
+        raise SystemExit(f"--lmbda {cfg.lmbda} cannot go with --padding_free / --pack_tokens: on-policy rollouts rebuild "
+                         "right-padded rows and are not built for packed batches")
     kw = {}
     if cfg.divergence != "forward_kl":
         kw.update(divergence=cfg.divergence, beta=cfg.beta)
@@ -202,6 +215,14 @@ def main():
             split = dataset.train_test_split(test_size=min(cfg.eval_samples, max(1, len(dataset) // 5)), seed=42)
             dataset, eval_dataset = split["train"], split["test"]
     evaluate = eval_dataset is not None
+    if cfg.pack_tokens:                                # (+) token-budget bins: a dataset item is a bin of samples
+        from speech_distill_amd.packing import PackedView, pack_bfd_indices
+
+        def binned(ds):
+            lengths = [len(ids) for ids in (ds["student_input_ids"] if hasattr(ds, "column_names") else
+                                            (r["student_input_ids"] for r in ds))]
+            return PackedView(ds, pack_bfd_indices(lengths, cfg.pack_tokens))
+        dataset, eval_dataset = binned(dataset), (binned(eval_dataset) if evaluate else None)
     args = TrainingArguments(
         output_dir=cfg.output_dir, per_device_train_batch_size=cfg.per_device_train_batch_size,
         gradient_accumulation_steps=cfg.gradient_accumulation_steps, num_train_epochs=cfg.epochs,
@@ -218,7 +239,8 @@ def main():
     # Under torchrun the trainer wraps the student in ddp.HipDataParallel itself (DistillationTrainer._wrap_model):
     # bucketed RCCL all-reduce of the flat gradient under the backward, no_sync on accumulation micro-batches.
     trainer = DistillationTrainer(model=student, args=args, train_dataset=dataset, eval_dataset=eval_dataset,
-                                  data_collator=ProcessedDataCollator(tokenizer, speech_bos=cfg.speech_bos, pad_token_id=pad),
+                                  data_collator=ProcessedDataCollator(tokenizer, speech_bos=cfg.speech_bos, pad_token_id=pad,
+                                                                      **({"padding_free": True} if cfg.padding_free else {})),
                                   teacher_model=teacher, temperature=cfg.temperature, alpha=cfg.alpha, top_k=cfg.top_k,
                                   is_quantized_teacher=cfg.load_teacher_in_4bit or cfg.load_teacher_in_8bit,
                                   **distill_kwargs(cfg, pad))

@@ -565,6 +565,102 @@ extern "C" int sd_loss_rows(const int64_t* labels, const int64_t* speech_mask, c
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------- loss rows of packed documents
+// The same selection over ONE flat row of n_seqs documents laid end to end (padding-free packing): token m is a loss row
+// iff m+1 < M, m+1 is not the first token of a document (the last token of a document predicts nothing, whatever label
+// the next document starts with), labels[m+1] != -100 and (with a mask) speech_mask[m+1] != 0.  The launch also checks
+// the segment array and reduces what the host needs to build the varlen descriptor and the RoPE gather without reading
+// anything else: the longest document and the largest position.  A chunk of 1024 tokens marks its document starts in LDS
+// from cu_seqlens (every offset is range-checked against the chunk before it indexes anything, so a malformed array gives
+// wrong rows and meta[1] bit 0, never an access outside [0, M)); the compaction is loss_rows_kernel's.
+namespace {
+
+__global__ __launch_bounds__(1024) void packed_rows_kernel(const long long* __restrict__ labels,
+                                                           const long long* __restrict__ speech_mask,
+                                                           const int* __restrict__ cu, int n_seqs,
+                                                           const long long* __restrict__ pos, long long* __restrict__ rows,
+                                                           long long* __restrict__ row_labels, int* __restrict__ meta,
+                                                           int M) {
+  __shared__ int wave_tot[16];
+  __shared__ int base_s, bad_s, longest_s, maxpos_s;
+  __shared__ unsigned char next_starts[1024];  // next_starts[i]: token c0 + i + 1 opens a document
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (tid == 0) { base_s = 0; bad_s = 0; longest_s = 0; maxpos_s = 0; }
+  __syncthreads();
+  int bad = 0, longest = 0, maxpos = 0;
+  for (int s = tid; s < n_seqs; s += 1024) {
+    const int a = cu[s], b = cu[s + 1];
+    if (b < a || (s == 0 && a != 0) || (s == n_seqs - 1 && b != M)) bad |= 1;
+    longest = max(longest, b - a);
+  }
+  for (int c0 = 0; c0 < M; c0 += 1024) {
+    next_starts[tid] = 0;
+    __syncthreads();
+    for (int s = tid; s <= n_seqs; s += 1024) {
+      const long d = (long)cu[s] - c0 - 1;
+      if (d >= 0 && d < 1024) next_starts[d] = 1;
+    }
+    __syncthreads();
+    const int e = c0 + tid;
+    bool valid = false;
+    long long lab = -100;
+    if (e < M) {
+      if (e + 1 < M && !next_starts[tid]) {
+        lab = labels[e + 1];
+        valid = lab != -100 && (!speech_mask || speech_mask[e + 1] != 0);
+      }
+      if (pos) {
+        const long long p = pos[e];
+        if (p < 0) bad |= 2;
+        maxpos = max(maxpos, (int)min(p, 0x7fffffffll));
+      }
+    }
+    const unsigned long long bal = __ballot(valid);
+    const int before = __popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_tot[wv] = __popcll(bal);
+    __syncthreads();
+    int off = base_s;
+    for (int w = 0; w < wv; ++w) off += wave_tot[w];
+    if (valid) {
+      rows[off + before] = e;
+      row_labels[off + before] = lab;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int tot = 0;
+      for (int w = 0; w < 16; ++w) tot += wave_tot[w];
+      base_s += tot;
+    }
+    __syncthreads();
+  }
+  if (bad) atomicOr(&bad_s, bad);
+  atomicMax(&longest_s, longest);
+  atomicMax(&maxpos_s, maxpos);
+  __syncthreads();
+  if (tid == 0) {
+    meta[0] = base_s;
+    meta[1] = bad_s;
+    meta[2] = longest_s;
+    meta[3] = maxpos_s;
+  }
+}
+
+}  // namespace
+
+extern "C" int sd_packed_rows(const int64_t* labels, const int64_t* speech_mask, const int32_t* cu_seqlens, int n_seqs,
+                              const int64_t* position_ids, int64_t* rows, int64_t* row_labels, int32_t* meta, int M,
+                              void* stream) {
+  if (M <= 0 || n_seqs <= 0 || M > (1 << 30)) return SD_ERR_SHAPE;
+  if (!labels || !cu_seqlens || !rows || !row_labels || !meta) return SD_ERR_SHAPE;
+  SD_PROF_LABEL("packed_rows M=%d n=%d", M, n_seqs);
+  SdProfScope prof(SD_K_MISC, 8.0 * M, (hipStream_t)stream);
+  hipLaunchKernelGGL(packed_rows_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const long long*)labels,
+                     (const long long*)speech_mask, cu_seqlens, n_seqs, (const long long*)position_ids, (long long*)rows,
+                     (long long*)row_labels, meta, M);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------------- reverse KL / skewed JSD
 // On-policy (generalised) distillation: divergences that do not force the student to cover every teacher mode.  With
 // q = softmax(s/T), p = softmax(t/T) per selected row:

@@ -618,6 +618,67 @@ def loss_rows(labels, speech_mask=None, right_padded=()):
     return rows, nxt.reshape(-1)[rows]
 
 
+def packed_rows(labels, cu_seqlens, speech_mask=None, position_ids=None):
+    """``loss_rows`` for packed documents (padding-free packing: ``labels`` holds M tokens, document s = the flat tokens
+    ``[cu_seqlens[s], cu_seqlens[s+1])``): flat token m is a loss row iff m + 1 < M, m + 1 lies in the same document
+    (the last token of a document predicts nothing, whatever the next document's first label), ``labels[m+1] != -100``
+    and (with a mask) ``speech_mask[m+1] != 0``.  -> (rows, row_labels, longest document, largest position): the two
+    numbers are what a ``qwen3.PackedBatch`` needs from the host, so a packed step has ONE host read (the 16 bytes of
+    sd_packed_rows' meta).  ValueError for a ``cu_seqlens`` that does not rise from 0 to M, or a negative position."""
+    M = labels.numel()
+    cu = cu_seqlens
+    if cu.dim() != 1 or cu.numel() < 2 or cu.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"packed_rows: cu_seqlens must be a 1-D integer tensor of n_seqs + 1 offsets, got {cu.dtype} "
+                         f"{tuple(cu.shape)}")
+    for what, t in (("speech_token_mask", speech_mask), ("position_ids", position_ids)):
+        if t is not None and t.numel() != M:
+            raise ValueError(f"packed_rows: {what} {tuple(t.shape)} does not hold the labels' {M} tokens")
+    if M == 0:
+        raise ValueError("packed_rows: empty batch")
+    if labels.is_cuda:  # one launch (sd_packed_rows) + one 16-byte read
+        dev = labels.device
+        lab = labels.to(torch.int64).reshape(-1).contiguous()
+        sm = None
+        if speech_mask is not None:
+            sm = speech_mask.to(dev).reshape(-1)
+            sm = (sm if sm.dtype == torch.int64 else (sm != 0).to(torch.int64)).contiguous()
+        pos = None if position_ids is None else position_ids.to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+        cu32 = cu.to(device=dev, dtype=torch.int32).contiguous()
+        rows = torch.empty(M, dtype=torch.int64, device=dev)
+        row_labels = torch.empty(M, dtype=torch.int64, device=dev)
+        meta = torch.empty(4, dtype=torch.int32, device=dev)
+        check(load_lib().sd_packed_rows(lab.data_ptr(), _p(sm), cu32.data_ptr(), cu32.numel() - 1, _p(pos), rows.data_ptr(),
+                                        row_labels.data_ptr(), meta.data_ptr(), M, _stream()), "sd_packed_rows")
+        n_rows, bad, longest, max_pos = meta.tolist()
+        rows, row_labels = rows[:n_rows], row_labels[:n_rows]
+    else:  # the rule, in torch
+        lab = labels.to(torch.int64).reshape(-1)
+        c = cu.to(torch.int64)
+        bad = int(c[0] != 0 or c[-1] != M or bool((c[1:] < c[:-1]).any()))
+        if position_ids is not None and bool((position_ids < 0).any()):
+            bad |= 2
+        longest = max_pos = 0
+        rows = row_labels = lab[:0]
+        if not bad:
+            nxt = torch.full_like(lab, -100)
+            nxt[:-1] = lab[1:]
+            if speech_mask is not None:
+                keep = torch.zeros(M, dtype=torch.bool)
+                keep[:-1] = speech_mask.reshape(-1)[1:] != 0
+                nxt[~keep] = -100
+            last = c[1:][c[1:] > c[:-1]] - 1   # the last token of every non-empty document: its successor is another document's
+            nxt[last] = -100
+            rows = torch.nonzero(nxt != -100).reshape(-1)
+            row_labels = nxt[rows]
+            longest = int((c[1:] - c[:-1]).max())
+            max_pos = 0 if position_ids is None else int(position_ids.max())
+    if bad & 1:
+        raise ValueError(f"cu_seqlens must rise from 0 to the token count {M} without decreasing")
+    if bad & 2:
+        raise ValueError("position_ids must be non-negative")
+    return rows, row_labels, longest, max_pos
+
+
 def colsum_reduce_batch(problems):
     """[(partials [nb, stride] fp32, out [H] bf16, H, accumulate), ...] (at most 8): out[c] (+)= sum_r partials[r, c] for
     every problem in ONE launch (sd_colsum_reduce_batch: a layer's four gain gradients)."""

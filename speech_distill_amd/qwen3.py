@@ -31,15 +31,34 @@ class PackedBatch:
     ``cu_seqlens`` on the device, the C descriptor (include/sd_hip.h sd_varlen) and the per-token RoPE tables (row m =
     the angles of token m's position).  Kept by the autograd function for the backward."""
 
-    def __init__(self, cu_host, cos, sin, device):
+    def __init__(self, cu_host, cos, sin, device, rope_theta=None):
+        self._set(cu_host.to(torch.int32).to(device), int(cu_host[-1]), cu_host.numel() - 1,
+                  int((cu_host[1:] - cu_host[:-1]).max()), cos, sin, rope_theta)
+
+    @classmethod
+    def from_device(cls, cu_seqlens, M, n, max_seqlen, cos, sin, rope_theta=None):
+        """From an int32 ``cu_seqlens`` [n+1] already on the device and already checked (``ops.packed_rows``: it rises from
+        0 to M, its longest document is ``max_seqlen``): no host read.  ``rope_theta``: the base of the tables, so that a
+        second model can tell whether this descriptor's RoPE rows are its own."""
+        if cu_seqlens.dtype != torch.int32 or cu_seqlens.dim() != 1 or cu_seqlens.numel() != n + 1:
+            raise ValueError(f"PackedBatch: cu_seqlens must be int32 [{n + 1}], got {cu_seqlens.dtype} {tuple(cu_seqlens.shape)}")
+        if cos.shape != sin.shape or cos.dim() != 2 or cos.size(0) != M:
+            raise ValueError(f"PackedBatch: RoPE tables must be [{M}, head_dim], got {tuple(cos.shape)} / {tuple(sin.shape)}")
+        pb = cls.__new__(cls)
+        pb._set(cu_seqlens.contiguous(), int(M), int(n), int(max_seqlen), cos, sin, rope_theta)
+        return pb
+
+    def _set(self, cu, M, n, max_seqlen, cos, sin, rope_theta):
         from . import ops
-        self.M, self.n = int(cu_host[-1]), cu_host.numel() - 1
-        self.max_seqlen = int((cu_host[1:] - cu_host[:-1]).max())
-        self.cu = cu_host.to(torch.int32).to(device)
+        self.M, self.n, self.max_seqlen, self.cu = M, n, max_seqlen, cu
         nb = load_lib().sd_varlen_work_bytes(self.M)
-        self.work = torch.empty(nb, dtype=torch.uint8, device=device) if nb > 0 else None
+        self.work = torch.empty(nb, dtype=torch.uint8, device=cu.device) if nb > 0 else None
         self.desc = ops.varlen_desc(self.cu, self.max_seqlen, self.work)
-        self.cos, self.sin = cos, sin
+        self.cos, self.sin, self.rope_theta = cos, sin, rope_theta
+
+    def tensors(self):
+        """The device tensors a stream must keep alive while it uses this descriptor."""
+        return [t for t in (self.cu, self.work, self.cos, self.sin) if t is not None]
 
 
 @dataclass
@@ -510,7 +529,26 @@ class HipQwen3ForCausalLM(nn.Module):
             n *= 2
         cos, sin = self._tables(n, ids.device)
         flat = pos.reshape(-1).to(torch.int64)
-        return PackedBatch(cu_host, cos[flat].contiguous(), sin[flat].contiguous(), ids.device)
+        return PackedBatch(cu_host, cos[flat].contiguous(), sin[flat].contiguous(), ids.device, self.dims.rope_theta)
+
+    def packed_batch(self, cu_seqlens, position_ids, max_seqlen, max_pos):
+        """The PackedBatch ``_packed`` would build, from numbers the caller has already read and checked
+        (``ops.packed_rows``: ``cu_seqlens`` rises from 0 to ``position_ids.numel()``, its longest document is
+        ``max_seqlen``, the positions lie in [0, ``max_pos``]): no host read, same tables, same bits.  Pass it to
+        ``forward(..., packed_batch=)``; a model of the same ``head_dim`` and ``rope_theta`` can share it."""
+        dev = self.flat.device
+        n = 64
+        while n <= max_pos:
+            n *= 2
+        cos, sin = self._tables(n, dev)
+        flat = position_ids.to(device=dev, dtype=torch.int64).reshape(-1)
+        cu = cu_seqlens.to(device=dev, dtype=torch.int32)
+        return PackedBatch.from_device(cu, flat.numel(), cu.numel() - 1, max_seqlen, cos[flat].contiguous(),
+                                       sin[flat].contiguous(), self.dims.rope_theta)
+
+    def shares_packed_batch(self, other):
+        """Whether a PackedBatch built by ``other`` carries this model's RoPE rows too."""
+        return self.dims.head_dim == other.dims.head_dim and self.dims.rope_theta == other.dims.rope_theta
 
     def _fold_layer(self, l):
         """bf16(W diag(g)) of layer l's q|k|v and gate|up projections, g = the RMSNorm gain in front of each."""
@@ -780,7 +818,9 @@ class HipQwen3ForCausalLM(nn.Module):
         consecutive ``position_ids`` (a new document wherever ``pos[t] != pos[t-1] + 1`` and at every row start); rows of
         ``B > 1`` are flattened.  No token attends across a document boundary (varlen attention kernels) and RoPE uses the
         given positions.  With an ``attention_mask``, ``position_ids`` are ignored (positions 0..T-1 per right-padded
-        row), as before."""
+        row), as before.  ``packed_batch`` (keyword, a ``PackedBatch`` from ``packed_batch()``): the documents of this
+        call, already read and checked by the caller; used in place of the host read above (the trainer builds one per
+        micro-batch for student and teacher)."""
         ids = _need(input_ids.to(torch.int64), torch.int64, "input_ids")
         rows = None
         if logit_rows is not None:
@@ -798,8 +838,16 @@ class HipQwen3ForCausalLM(nn.Module):
                 raise ValueError("attention_mask is not right-padded (a 1 follows a 0): the HIP attention kernels take a "
                                  "valid-prefix length per sequence, as ProcessedDataCollator produces (data.py:280-327)")
             kv_len = am.sum(-1).to(torch.int32).contiguous()
-        packed = None
-        if attention_mask is None and position_ids is not None:
+        packed = kwargs.get("packed_batch")
+        if packed is not None:   # the caller has read and checked the segments already (ops.packed_rows): host-side checks only
+            if attention_mask is not None:
+                raise ValueError("packed_batch with an attention_mask: packed documents have no padding to mask")
+            if (packed.M != ids.numel() or packed.cos.size(-1) != self.dims.head_dim
+                    or packed.rope_theta not in (None, self.dims.rope_theta)):
+                raise ValueError(f"packed_batch was built for {packed.M} tokens, RoPE width {packed.cos.size(-1)}, theta "
+                                 f"{packed.rope_theta}; this call has {ids.numel()} tokens, head_dim {self.dims.head_dim}, "
+                                 f"theta {self.dims.rope_theta}")
+        elif attention_mask is None and position_ids is not None:
             packed = self._packed(ids, position_ids, kwargs.get("cu_seq_lens_q"), kwargs.get("cu_seq_lens_k"))
         elif attention_mask is None and kwargs.get("cu_seq_lens_q") is not None:
             raise ValueError("cu_seq_lens_q without position_ids: packed documents need their positions (HF packs only "

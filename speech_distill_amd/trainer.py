@@ -108,7 +108,13 @@ class DistillationTrainer(FlatStudentTrainer):
     student on the GPU without LoRA and a teacher model.  With ``lmbda > 0`` the three lookaheads (loss rows ahead, teacher
     ahead, window ahead) are switched off: they would select rows of, and run the teacher on, a batch that is about to be
     replaced.  ``on_policy_fraction`` (the share of on-policy micro-batches since the previous log) is logged next to the
-    three sub-losses."""
+    three sub-losses.
+
+    Packed batches (``ProcessedDataCollator(padding_free=True)``; a batch is packed by its keys: ``position_ids`` present
+    and ``attention_mask`` absent): ``ops.packed_rows`` selects the loss rows inside each document and checks the segments
+    in the step's one host read, one ``PackedBatch`` descriptor serves student and teacher, and the teacher is called with
+    the packed keys.  The three lookaheads work as on padded batches.  Refused: ``lmbda > 0``, teacher ids of another
+    shape, and a packed batch that also carries an attention mask."""
 
     def __init__(self, *args, teacher_model=None, temperature=2.0, alpha=0.5, top_k=100, is_quantized_teacher=False,
                  divergence="forward_kl", beta=0.5, lmbda=0.0, on_policy_generate=None, **kwargs):
@@ -189,9 +195,75 @@ class DistillationTrainer(FlatStudentTrainer):
         return super().create_optimizer(model) if model is not None else super().create_optimizer()
 
     @staticmethod
-    def _rows_key(lab, speech_mask, am, tam):
+    def _rows_key(lab, speech_mask, am, tam, cu=None):
         return (id(lab), lab.data_ptr(), tuple(lab.shape), None if speech_mask is None else speech_mask.data_ptr(),
-                None if am is None else am.data_ptr(), None if tam is None else tam.data_ptr())
+                None if am is None else am.data_ptr(), None if tam is None else tam.data_ptr(),
+                None if cu is None else cu.data_ptr())
+
+    # ------------------------------------------------------------------------------ packed (padding-free) batches
+    PACKED_KEYS = ("position_ids", "cu_seq_lens_q", "cu_seq_lens_k", "max_length_q", "max_length_k")
+
+    @staticmethod
+    def _is_packed(batch):
+        """A batch is packed by its keys, exactly when HF Qwen3 and HipQwen3ForCausalLM pack: ``position_ids`` present and
+        ``attention_mask`` absent (``ProcessedDataCollator(padding_free=True)``)."""
+        return batch.get("position_ids") is not None and batch.get("attention_mask") is None
+
+    def _check_packed(self, batch, teacher_input_ids, teacher_attention_mask):
+        """What a packed step refuses, before any launch."""
+        ids = batch.get("input_ids")
+        if batch.get("cu_seq_lens_q") is not None and (batch.get("attention_mask") is not None
+                                                       or teacher_attention_mask is not None):
+            raise ValueError("a packed batch (cu_seq_lens_q) also carries an attention_mask: packed documents have no "
+                             "padding to mask, and a model given both would not pack")
+        if not self._is_packed(batch):
+            return False
+        if self.lmbda > 0:
+            raise ValueError("lmbda > 0 with a packed batch: on-policy rollouts rebuild right-padded [B, T] rows and are "
+                             "not built for packed documents (use the padded collator, or lmbda=0)")
+        if teacher_input_ids is not None and ids is not None and tuple(teacher_input_ids.shape) != tuple(ids.shape):
+            raise ValueError(f"teacher_input_ids {tuple(teacher_input_ids.shape)} and input_ids {tuple(ids.shape)} must be "
+                             "position-aligned (data.py:20-60 align_prefixes): packed documents share one set of boundaries")
+        return True
+
+    def _select_packed(self, core, batch, lab, speech_mask):
+        """Loss rows and descriptors of one packed micro-batch: ``ops.packed_rows`` (the step's ONE host read: row count,
+        segment check, longest document, largest position), then one ``PackedBatch`` for the student, shared with the
+        teacher when its RoPE rows are the same (else a second one from the same checked numbers, still without a read).
+        -> (rows, row_labels, (student descriptor, teacher descriptor)); a descriptor is None for a model that is not a
+        HipQwen3ForCausalLM (it takes the packed keys themselves)."""
+        cu, pos = batch["cu_seq_lens_q"], batch["position_ids"]
+        cu_k = batch.get("cu_seq_lens_k")   # (compared by shape only: comparing the values would be a second host read)
+        if cu_k is not None and cu_k is not cu and tuple(cu_k.shape) != tuple(cu.shape):
+            raise ValueError("cu_seq_lens_k differs from cu_seq_lens_q: packed causal attention takes one set of segments")
+        rows, row_labels, longest, max_pos = ops.packed_rows(lab, cu, speech_mask, pos)
+        pbs = [None, None]
+        for i, m in enumerate((core, self.teacher_model)):
+            if isinstance(m, HipQwen3ForCausalLM) and m.flat.is_cuda and lab.is_cuda:
+                if i == 1 and pbs[0] is not None and m.shares_packed_batch(core):
+                    pbs[1] = pbs[0]
+                else:
+                    pbs[i] = m.packed_batch(cu, pos, longest, max_pos)
+        return rows, row_labels, tuple(pbs)
+
+    @staticmethod
+    def _packed_tensors(pbs):
+        return [t for pb in {id(pb): pb for pb in pbs or () if pb is not None}.values() for t in pb.tensors()]
+
+    def _document_start_labels(self, labels, batch):
+        """``labels`` with -100 at every document start of a packed batch (one scatter, no read): after the causal shift
+        the last token of a document then predicts nothing on the full [1, M, V] path, whatever the collator wrote."""
+        M = labels.numel()
+        cu = batch.get("cu_seq_lens_q")
+        if cu is not None:
+            start = torch.zeros(M + 1, dtype=torch.bool, device=labels.device)   # (an empty last document starts at M)
+            start[cu.to(device=labels.device, dtype=torch.int64)] = True
+            start = start[:M].reshape(labels.shape)
+        else:   # position_ids alone: HF's rule (ops.packed_segments)
+            pos = batch["position_ids"].to(labels.device)
+            start = torch.ones_like(pos, dtype=torch.bool)
+            start[:, 1:] = pos[:, 1:] != pos[:, :-1] + 1
+        return torch.where(start, torch.full_like(labels, -100), labels)
 
     def get_batch_samples(self, epoch_iterator, num_batches, device):
         """HF fetches the micro-batches of one optimizer step here, together, right after it has enqueued the previous
@@ -240,7 +312,7 @@ class DistillationTrainer(FlatStudentTrainer):
 
     def _fetch_window(self, core, epoch_iterator, num_batches, device):
         """HF's fetch of one accumulation window + the loss-row selection of its micro-batches, on the copy stream.
-        Returns (batch_samples, num_items_in_batch, [(key, (rows, row_labels))], event)."""
+        Returns (batch_samples, num_items_in_batch, [(key, (rows, row_labels, packed descriptors or None))], event)."""
         main = torch.cuda.current_stream(core.flat.device)
         if self._copy_stream is None:
             self._copy_stream = ops.concurrent_stream(core.flat.device, "h2d")
@@ -254,18 +326,26 @@ class DistillationTrainer(FlatStudentTrainer):
                 if lab is None or not torch.is_tensor(lab) or not lab.is_cuda:
                     continue
                 need_teacher = b.get("teacher_top_k_v") is None and self.teacher_model is not None
+                sm = b.get("speech_token_mask")
+                if self._is_packed(b) and b.get("cu_seq_lens_q") is None:
+                    continue   # segments by position_ids alone: selected in compute_loss, after the document starts are masked
+                if self._is_packed(b):
+                    self._check_packed(b, b.get("teacher_input_ids"), b.get("teacher_attention_mask"))
+                    selected.append((self._rows_key(lab, sm, None, None, b["cu_seq_lens_q"]),
+                                     self._select_packed(core, b, lab, sm)))
+                    continue
                 am = b.get("attention_mask")
                 tam = b.get("teacher_attention_mask") if hip_teacher and need_teacher else None
                 am = am if am is not None and tuple(am.shape) == tuple(lab.shape) else None
                 tam = tam if tam is not None and tuple(tam.shape) == tuple(lab.shape) else None
-                sm = b.get("speech_token_mask")
-                selected.append((self._rows_key(lab, sm, am, tam), ops.loss_rows(lab, sm, right_padded=(am, tam))))
+                selected.append((self._rows_key(lab, sm, am, tam), ops.loss_rows(lab, sm, right_padded=(am, tam)) + (None,)))
             ready = torch.cuda.Event()
             ready.record(cs)
         # the tensors were allocated on the copy stream and are used on the main and the teacher's stream
         users = [main] + ([self._teacher_stream] if self._teacher_stream is not None else [])
         held = [t for b in batch_samples if isinstance(b, dict) for t in b.values() if torch.is_tensor(t) and t.is_cuda]
-        held += [t for _, rr in selected for t in rr] + ([num_items] if torch.is_tensor(num_items) and num_items.is_cuda else [])
+        held += [t for _, rr in selected for t in list(rr[:2]) + self._packed_tensors(rr[2])]
+        held += [num_items] if torch.is_tensor(num_items) and num_items.is_cuda else []
         for t in held:
             for st in users:
                 t.record_stream(st)
@@ -275,6 +355,8 @@ class DistillationTrainer(FlatStudentTrainer):
 
     def training_step(self, model, inputs, *args, **kwargs):
         if self.lmbda > 0:
+            if isinstance(inputs, dict):   # (a packed batch is refused before the rollout, not after it)
+                self._check_packed(inputs, inputs.get("teacher_input_ids"), inputs.get("teacher_attention_mask"))
             inputs = self._maybe_on_policy(model, inputs)
         lab = inputs.get("labels") if isinstance(inputs, dict) else None
         loss = super().training_step(model, inputs, *args, **kwargs)
@@ -310,15 +392,17 @@ class DistillationTrainer(FlatStudentTrainer):
                 or not isinstance(self.teacher_model, HipQwen3ForCausalLM) or not isinstance(core, HipQwen3ForCausalLM)
                 or ids is None or (tids is not None and tuple(tids.shape) != tuple(ids.shape))):
             return
-        _, (rows, _), fetched = entry
+        _, (rows, _, pbs), fetched = entry
         tam = nxt.get("teacher_attention_mask")
         aligned = tam is not None and tuple(tam.shape) == tuple(lab.shape)
         kw = dict({"padding_checked": True} if aligned or tam is None else {}, concurrent=True)
+        if pbs is not None:
+            kw = dict(concurrent=True, packed_batch=pbs[1])
         if self._teacher_stream is None:
             self._teacher_stream = ops.concurrent_stream(ids.device, "teacher")
         side = self._teacher_stream
         side.wait_event(fetched)
-        for t in (ids, tids, tam, nxt.get("attention_mask"), rows):
+        for t in [ids, tids, tam, nxt.get("attention_mask"), rows, nxt.get("position_ids")] + self._packed_tensors(pbs):
             if torch.is_tensor(t) and t.is_cuda:
                 t.record_stream(side)
         base = {k: v for k, v in nxt.items() if k not in self._TEACHER_SIDE_KEYS}
@@ -337,11 +421,16 @@ class DistillationTrainer(FlatStudentTrainer):
     def _teacher_pass(self, inputs, teacher_input_ids, teacher_attention_mask, vocab_size, rows=None, model_kw=None):
         """train.py:60-94: teacher no-grad forward, then on-the-fly top-K unless quantized / top_k <= 0.
         ``rows``: only those flat rows of the logits are produced (our own teacher) or kept (any other module);
-        ``model_kw``: extra keyword arguments for a HipQwen3ForCausalLM teacher (``padding_checked``)."""
+        ``model_kw``: extra keyword arguments for a HipQwen3ForCausalLM teacher (``padding_checked``, ``packed_batch``).
+        A packed batch (``_is_packed(inputs)``): the teacher's own ids go with the batch's packed keys and no mask -- one
+        set of document boundaries serves both models."""
         model_kw = model_kw or {}
         with torch.no_grad():
             extra = {"logit_rows": rows} if rows is not None and isinstance(self.teacher_model, HipQwen3ForCausalLM) else {}
-            if teacher_input_ids is not None:
+            if teacher_input_ids is not None and teacher_attention_mask is None and self._is_packed(inputs):
+                teacher_outputs = self.teacher_model(input_ids=teacher_input_ids, **extra, **model_kw,
+                                                     **{k: inputs[k] for k in self.PACKED_KEYS if inputs.get(k) is not None})
+            elif teacher_input_ids is not None:
                 teacher_outputs = self.teacher_model(input_ids=teacher_input_ids, attention_mask=teacher_attention_mask,
                                                      **extra, **model_kw)
             else:
@@ -367,6 +456,7 @@ class DistillationTrainer(FlatStudentTrainer):
                              "pre-extracted teacher_top_k_v (K entries per position)")
         need_teacher = teacher_top_k_v is None and self.teacher_model is not None
         ids0 = inputs.get("input_ids")
+        packed = self._check_packed(inputs, teacher_input_ids, teacher_attention_mask)
         if (need_teacher and teacher_input_ids is not None and ids0 is not None
                 and tuple(teacher_input_ids.shape) != tuple(ids0.shape)):
             # The collator pads teacher and student separately (data.py:219-278) and the loss indexes both with ONE
@@ -389,7 +479,26 @@ class DistillationTrainer(FlatStudentTrainer):
         rows = row_labels = None
         lab = inputs.get("labels")
         checked = {}
-        if (self.compact_head and not return_outputs and hip_student and lab is not None
+        pbs = None
+        full_labels = None   # packed: the labels with -100 at every document start, where this step needs them
+        if packed and lab is not None and inputs.get("cu_seq_lens_q") is None:
+            full_labels = self._document_start_labels(lab, inputs)
+        if packed and lab is not None and inputs.get("cu_seq_lens_q") is not None:
+            # the one host read of a packed step: row count, segment check, longest document, largest position
+            key = self._rows_key(lab, speech_mask, None, None, inputs["cu_seq_lens_q"])
+            hit = self._rows_ahead.pop(key[0], None)
+            if hit is not None and hit[0] == key:
+                (rows, row_labels, pbs), fetched = hit[1], hit[2]
+            else:
+                rows, row_labels, pbs = self._select_packed(core, inputs, lab, speech_mask)
+            if pbs[0] is not None:
+                checked = {"packed_batch": pbs[0]}
+            teacher_checked = {"packed_batch": pbs[1]} if pbs[1] is not None else {}
+            if (rows.numel() == 0 or not self.compact_head or return_outputs or not hip_student or not lab.is_cuda
+                    or not isinstance(self.distill_loss_fn, DistillationLoss)):
+                rows = row_labels = None     # the full path; the descriptors still serve both models
+                fetched = None
+        elif (self.compact_head and not return_outputs and hip_student and lab is not None
                 and lab.is_cuda and isinstance(self.distill_loss_fn, DistillationLoss)):
             # the one host read of the step: the row count, and (same read) that the masks are right-padded
             # only masks laid out on the labels' [B, T] grid go into the fused check; any other keeps its own validation
@@ -400,10 +509,11 @@ class DistillationTrainer(FlatStudentTrainer):
             key = self._rows_key(lab, speech_mask, am, tam)
             hit = self._rows_ahead.pop(key[0], None)
             if hit is not None and hit[0] == key:   # selected with the accumulation window's other batches (get_batch_samples)
-                rows, row_labels = hit[1]
+                rows, row_labels = hit[1][:2]
                 fetched = hit[2]                    # event: this batch (and its rows) are on the device
-            else:
-                rows, row_labels = ops.loss_rows(lab, speech_mask, right_padded=(am, tam))
+            else:   # (position_ids without cu_seq_lens: the models read the segments themselves, and the rows come from
+                # the labels with every document start masked, so that none crosses a document boundary)
+                rows, row_labels = ops.loss_rows(full_labels if packed else lab, speech_mask, right_padded=(am, tam))
             checked = {"padding_checked": True} if am is not None or inputs.get("attention_mask") is None else {}
             teacher_checked = {"padding_checked": True} if tam is not None or teacher_attention_mask is None else {}
             if rows.numel() == 0:  # N == 0: the full path returns the reference's zeros (distillation_loss.py:47-53)
@@ -424,7 +534,8 @@ class DistillationTrainer(FlatStudentTrainer):
             side = self._teacher_stream
             if fetched is not None:   # the teacher needs the batch, not whatever else the main stream still has queued
                 side.wait_event(fetched)
-                for t in (ids, teacher_input_ids, teacher_attention_mask, inputs.get("attention_mask"), rows):
+                for t in [ids, teacher_input_ids, teacher_attention_mask, inputs.get("attention_mask"), rows,
+                          inputs.get("position_ids")] + self._packed_tensors(pbs):
                     if torch.is_tensor(t) and t.is_cuda:
                         t.record_stream(side)
             else:
@@ -444,6 +555,8 @@ class DistillationTrainer(FlatStudentTrainer):
         outputs = model(**inputs, **checked) if rows is None else model(**inputs, logit_rows=rows, **checked)  # train.py:54
         student_logits = outputs.logits
         labels = inputs.pop("labels", None)
+        if packed and rows is None and labels is not None:   # the full [1, M, V] path shifts across the flat row itself
+            labels = full_labels if full_labels is not None else self._document_start_labels(labels, inputs)
 
         teacher_logits_local = None
         if side is not None:
