@@ -312,6 +312,32 @@ int sd_gjsd_bwd_rows(const void* student_logits, const void* teacher_logits, con
                      const void* row_stats, const float* loss_out, const float* grad_total, void* grad_logits, int R, int V,
                      float temperature, float alpha, float beta, int mode, int dtype, void* stream);
 
+/* ---- the same skewed Jensen-Shannon divergence against a TOP-K teacher (the reference's sparse teacher,
+ * distillation_loss.py:73-118: top_k_v fp16 [R,K] stored log-probs, top_k_i int32 [R,K] their indices).  Per row:
+ *   p_k = softmax(v / T)_k over the K entries,  P_j = sum_{k: i_k = j} p_k (duplicated indices sum their mass),
+ *   S = {j : P_j > 0},  q = softmax(s / T) over the vocabulary,  m = (1 - beta) q + beta P,
+ *   D = beta sum_S P_j (log P_j - log m_j) + (1 - beta) sum_S q_j (log q_j - log m_j) + (1 - Q_S) g0,
+ *   Q_S = sum_S q_j,  g0 = -(1 - beta) log(1 - beta)
+ * i.e. SD_DIV_JSD against the dense distribution P; D reaches 0 only when the student puts all its mass on S.  An entry
+ * whose index is outside [0, V) or whose value is not finite carries no mass and behaves as absent (never read or
+ * written through); a row whose entries are all absent is a masked row, as is a row whose label is -100 or outside
+ * [0, V): stats zero, gradient exactly zero, not counted in N.
+ * loss_out fp32[8] = {total, task, distill, teacher, N, n_hits, 0, 0}; teacher / n_hits as sd_kdloss_*'s sparse form
+ * (minus the mean of v_k over the entries with i_k = the label; 0 without a hit).  row_stats: scratch of
+ * sd_gjsd_topk_stats_bytes(R) kept from fwd to bwd; a row's stats do not depend on the other rows.  grad_total fp32 [1]
+ * nullable (= 1); grad_logits may alias student_logits.  fp32 arithmetic, fixed reduction order, no float atomics.
+ * Before any launch: R or V <= 0, K <= 0 or K > 1024, a NULL student / labels / stats / loss_out / grad_logits,
+ * temperature not in (0, inf), beta outside (0, 1) (NaN included) SD_ERR_SHAPE; a NULL top_k_v / top_k_i
+ * SD_ERR_NO_TEACHER; V % 8 != 0 or a logits / gradient pointer off 16 bytes SD_ERR_ALIGN; an unknown dtype
+ * SD_ERR_UNSUPPORTED.  (Reverse KL has no such form: KL(q || P) is infinite wherever P_j = 0 < q_j.) */
+int64_t sd_gjsd_topk_stats_bytes(int R);
+int sd_gjsd_topk_fwd_rows(const void* student_logits, const void* top_k_v, const void* top_k_i, const int64_t* row_labels,
+                          void* row_stats, float* loss_out, int R, int V, int K, float temperature, float alpha, float beta,
+                          int dtype, void* stream);
+int sd_gjsd_topk_bwd_rows(const void* student_logits, const void* top_k_v, const void* top_k_i, const int64_t* row_labels,
+                          const void* row_stats, const float* loss_out, const float* grad_total, void* grad_logits, int R,
+                          int V, int K, float temperature, float alpha, float beta, int dtype, void* stream);
+
 /* ---- causal-LM cross-entropy on selected rows: the Stage-1 loss (stage1.py: TRL SFTTrainer over HF
  * Qwen3ForCausalLM(labels=...), i.e. HF ForCausalLMLoss -- shift by one, ignore_index -100, reduction "sum" divided by
  * num_items_in_batch when the Trainer passes it, else the mean over valid rows).  Teacher-free counterpart of

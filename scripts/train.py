@@ -87,10 +87,11 @@ def parse_args(argv=None):
                    help="(+) what gradient checkpointing (on, as in train.py:512-517) does: layer recompute always, never, "
                         "or only when the activations would take more than a quarter of HBM")
     # (+) on-policy (generalised) distillation; the defaults are the reference's loop
-    p.add_argument("--divergence", choices=("forward_kl", "reverse_kl", "jsd"), default="forward_kl",
+    p.add_argument("--divergence", choices=("forward_kl", "reverse_kl", "jsd", "jsd_topk"), default="forward_kl",
                    help="(+) the distillation term: forward KL (the reference), reverse KL, or the beta-skewed Jensen-Shannon "
-                        "divergence; the last two need the dense teacher (--top_k 0)")
-    p.add_argument("--beta", type=float, default=0.5, help="(+) skew of --divergence jsd, in (0, 1)")
+                        "divergence; reverse_kl and jsd need the dense teacher (--top_k 0), jsd_topk is jsd against the "
+                        "renormalised top-K teacher (--top_k > 0, or a pre-extracted dataset)")
+    p.add_argument("--beta", type=float, default=0.5, help="(+) skew of --divergence jsd / jsd_topk, in (0, 1)")
     p.add_argument("--lmbda", type=float, default=0.0,
                    help="(+) probability that a training micro-batch is made on-policy (the student's own sampled completion)")
     p.add_argument("--on_policy_max_new_tokens", type=int, default=256)
@@ -115,7 +116,11 @@ def parse_args(argv=None):
 def distill_kwargs(cfg, pad=None):
     """The DistillationTrainer keywords of the (+) on-policy flags: only what differs from the trainer's defaults, so the
     default command line constructs the trainer exactly as before.  Exits when the flags cannot work together."""
-    if cfg.divergence != "forward_kl" and cfg.top_k > 0 and not (cfg.load_teacher_in_4bit or cfg.load_teacher_in_8bit):
+    if cfg.divergence == "jsd_topk":
+        if cfg.top_k <= 0 or cfg.load_teacher_in_4bit or cfg.load_teacher_in_8bit:
+            raise SystemExit("--divergence jsd_topk needs a top-K teacher (--top_k > 0, no 4/8-bit teacher); on the dense "
+                             "teacher distribution the same divergence is --divergence jsd")
+    elif cfg.divergence != "forward_kl" and cfg.top_k > 0 and not (cfg.load_teacher_in_4bit or cfg.load_teacher_in_8bit):
         raise SystemExit(f"--divergence {cfg.divergence} needs the dense teacher distribution: pass --top_k 0 "
                          f"(got --top_k {cfg.top_k}; a top-K teacher defines it on K entries only)")
     if cfg.lmbda > 0 and cfg.padding_free:

@@ -178,6 +178,9 @@ PROTOTYPES = {
     "sd_gjsd_stats_bytes": (_i64, [_i]),
     "sd_gjsd_fwd_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _i, _i, _vp]),
     "sd_gjsd_bwd_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _i, _i, _vp]),
+    "sd_gjsd_topk_stats_bytes": (_i64, [_i]),
+    "sd_gjsd_topk_fwd_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _i, _vp]),
+    "sd_gjsd_topk_bwd_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _i, _vp]),
     "sd_rows_scatter": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "sd_loss_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "sd_packed_rows": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),

@@ -147,10 +147,11 @@ __global__ __launch_bounds__(NF, (NF == 1024 && sizeof(T) == 2) ? 8 : 1) void kd
   if (threadIdx.x == 0) stats[row] = RowStats{lse1, lseT, t_lseT, 1.f, task, distill, teacher, hits};
 }
 
-// The batch scalars from the per-row stats of kd_fwd_kernel (RowStats, HITS) or gjsd_fwd_kernel (GjsdStats): single
-// block, fixed order.
-//   RowStats:  out[0..5] = total, task, distill, teacher, N, n_hits
-//   GjsdStats: out[0..7] = total, task, distill, teacher, N, N, 0, 0
+// The batch scalars from the per-row stats of kd_fwd_kernel (RowStats, HITS), gjsd_fwd_kernel (GjsdStats) or
+// gjsd_topk_fwd_kernel (GjsdTopkStats, HITS): single block, fixed order.
+//   RowStats:      out[0..5] = total, task, distill, teacher, N, n_hits
+//   GjsdStats:     out[0..7] = total, task, distill, teacher, N, N, 0, 0
+//   GjsdTopkStats: out[0..7] = total, task, distill, teacher, N, n_hits, 0, 0
 template <typename Stats, bool HITS>
 __global__ __launch_bounds__(NT) void kd_finalize_kernel(const Stats* __restrict__ stats, float* __restrict__ out, int rows,
                                                          float temperature, float alpha, int dense) {
@@ -165,6 +166,7 @@ __global__ __launch_bounds__(NT) void kd_finalize_kernel(const Stats* __restrict
   if constexpr (HITS) hits = block_sum<NT>(hits, sc);
   if (threadIdx.x != 0) return;
   if constexpr (HITS) {
+    if constexpr (!std::is_same<Stats, RowStats>::value) out[6] = out[7] = 0.f;  // GjsdTopkStats: fp32[8], as GjsdStats
     if (n == 0.f) {
       out[0] = out[1] = out[2] = out[3] = 0.f; out[4] = 0.f; out[5] = 0.f;
     } else {
@@ -872,6 +874,303 @@ extern "C" int sd_gjsd_bwd_rows(const void* student_logits, const void* teacher_
       hipLaunchKernelGGL((gjsd_bwd_kernel<T, SD_FLAG(t2), SD_FLAG(jsd)>), dim3(R), dim3(GJ_NF), 0, st,
                          (const T*)student_logits, (const T*)teacher_logits, row_labels, (const GjsdStats*)row_stats, loss_out,
                          grad_total, (T*)grad_logits, V, temperature, alpha, beta);
+    });
+    SD_CHECK_LAUNCH();
+    return 0;
+  });
+}
+
+// ---------------------------------------------------------------------------------------- skewed JSD, top-K teacher
+// SD_DIV_JSD against the reference's sparse teacher (distillation_loss.py:73-118: K stored log-probs v_k and indices i_k
+// per row).  p_k = softmax(v / T)_k over the K entries, P_j = sum_{k: i_k = j} p_k, S = {j : P_j > 0}; then exactly
+// gjsd_fwd_kernel's JSD with P as the teacher distribution.  Off S the mixture is m_j = (1-b) q_j, so every off-support
+// element has the same g_j = g0 = -(1-b) log(1-b) and the V - |S| terms collapse into (1 - Q_S) g0, Q_S = sum_S q_j:
+//   D = b sum_S P_j (log P_j - log m_j) + (1-b) sum_S q_j (log q_j - log m_j) + (1 - Q_S) g0
+//   c = sum_v q_v g_v = (1-b) sum_S q_j (log q_j - log m_j) + (1 - Q_S) g0
+// Nothing but the student's normalisers needs the whole row: ONE sweep (kd_fwd_kernel's sparse sweep with gjsd_fwd_kernel's
+// unfolded exponent) and an epilogue over the K entries.  The backward is one read and one write of the row with one
+// exponential per element at T == 2 (every off-support element is a1 softmax(s)_j + aT q_j (g0 - c)), then a fix-up of
+// the at most K on-support elements after a barrier, as kd_bwd_kernel has it.
+// An entry whose index is outside [0, V) or whose value is not finite carries no mass: it is dropped before the
+// renormalisation and its index is never used as an address.  A merged mass below FLT_MIN counts as 0 (v_log_f32 takes no
+// denormal): such an element is treated as off-support, which moves D by less than 1e-36.
+namespace {
+
+struct GjsdTopkStats {  // 12 floats per row; m .. c are what the backward reads (GjsdStats' conventions: log2 units)
+  float m, ls1, lsT, c, valid, task, distill, teacher, hits, mv, sv, pad0;  // mv, sv: the teacher's renormalisation, so that
+};                                                                            // the backward forms the forward's p_k bit for bit
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+// The row's K entries -> LDS: k_i[k] the index (-1: dropped), k_p[k] = softmax(v / T)_k over the kept entries; both
+// padded to a multiple of 4 with (-1, 0).  Thread t takes the entries t + u NF, u < E.  hv / hc: this thread's sum of v_k
+// and count over its kept entries with i_k == y (the sparse forward KL's teacher monitor).  false: no entry is kept.
+// mv, sv: the maximum of the kept v_k and the sum of exp((v_k - mv) / T).  GIVEN (the backward): they are the forward's,
+// read from the row's stats -- no reduction here, and p_k does not depend on how many threads the caller runs.
+template <int NF, int E, bool GIVEN>
+SD_DEV bool tk_renorm(const _Float16* __restrict__ topv, const int32_t* __restrict__ topi, long kb, int K, int V, float kT,
+                      long y, float* sc, int* k_i, float* k_p, float& hv, float& hc, float& mv, float& sv) {
+  float v[E], mx = -INFINITY;
+  int idx[E];
+  hv = hc = 0.f;
+#pragma unroll
+  for (int u = 0; u < E; ++u) {
+    const int k = threadIdx.x + u * NF;
+    idx[u] = k < K ? topi[kb + k] : -1;
+    v[u] = k < K ? (float)topv[kb + k] : -INFINITY;
+    if (idx[u] < 0 || idx[u] >= V || !(fabsf(v[u]) < INFINITY)) {  // NaN fails the comparison
+      idx[u] = -1;
+      v[u] = -INFINITY;
+    } else if ((long)idx[u] == y) {
+      hv += v[u];
+      hc += 1.f;
+    }
+    mx = fmaxf(mx, v[u]);
+  }
+  if constexpr (!GIVEN) {
+    mv = block_max<NF>(mx, sc);
+    if (mv == -INFINITY) return false;
+  }
+  float ev[E], se = 0.f;
+#pragma unroll
+  for (int u = 0; u < E; ++u) {
+    ev[u] = idx[u] >= 0 ? __builtin_amdgcn_exp2f((v[u] - mv) * kT) : 0.f;
+    se += ev[u];
+  }
+  if constexpr (!GIVEN) sv = block_sum<NF>(se, sc);
+  const int K4 = (K + 3) & ~3;
+#pragma unroll
+  for (int u = 0; u < E; ++u) {
+    const int k = threadIdx.x + u * NF;
+    if (k < K4) {
+      k_i[k] = idx[u];
+      k_p[k] = ev[u] / sv;
+    }
+  }
+  __syncthreads();
+  return true;
+}
+
+// P of index idx over the K entries, summed in entry order whoever asks (so the forward and the backward get the same
+// bits), and whether entry k is the first one that holds it.  Four entries per LDS read, every lane the same address.
+// A thread without a kept entry (idx < 0) does not walk: a wave that holds none skips the loop altogether.
+SD_DEV float tk_mass(const int* k_i, const float* k_p, int K, int k, int idx, bool& first) {
+  first = idx >= 0;
+  float P = 0.f;
+  if (idx < 0) return P;
+  for (int k2 = 0; k2 < K; k2 += 4) {
+    const i32x4 ii = *(const i32x4*)(k_i + k2);
+    const f32x4 pp = *(const f32x4*)(k_p + k2);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (ii[e] == idx) {
+        P += pp[e];
+        if (k2 + e < k) first = false;
+      }
+    }
+  }
+  return P;
+}
+
+// one on-support element: q_j, a2 = log2 q_j and lm = log2 m_j.  m: the row maximum, A0 = -log2 of the max-subtracted sum at T
+SD_DEV void tk_term(float sj, float P, float m, float kT, float A0, float beta, float& q, float& a2, float& lm) {
+  a2 = __builtin_fmaf(sj - m, kT, A0);
+  q = __builtin_amdgcn_exp2f(a2);
+  lm = __builtin_amdgcn_logf(fmaxf(__builtin_fmaf(1.f - beta, q, beta * P), GJ_FLT_MIN));  // v_log_f32 = log2
+}
+
+// No register cap (kd_fwd_kernel's 8 waves per SIMD): held to 64 VGPRs every bf16 instantiation spills (20 / 108 bytes of
+// scratch per lane); left alone they take 68 (NF = 512: three workgroups per CU) and 93-95 (NF = 1024: one).
+template <typename T, bool T2, int NF>
+__global__ __launch_bounds__(NF) void gjsd_topk_fwd_kernel(const T* __restrict__ S, const _Float16* __restrict__ topv,
+                                                           const int32_t* __restrict__ topi,
+                                                           const int64_t* __restrict__ labels,
+                                                           GjsdTopkStats* __restrict__ stats, int V, int K,
+                                                           float temperature, float beta) {
+  __shared__ float sc[32];
+  __shared__ __attribute__((aligned(16))) float k_p[NF];
+  __shared__ __attribute__((aligned(16))) int k_i[NF];
+  const int row = blockIdx.x;
+  const long y = labels[row];
+  const float invT = 1.f / temperature;
+  const float k1 = GJ_LOG2E, kT = invT * k1;
+  float hv = 0.f, hc = 0.f, mv = 0.f, sv = 0.f;
+  // -100 (and anything outside the vocabulary) masks the row, and so does a teacher without a single kept entry
+  if (y < 0 || y >= V || !tk_renorm<NF, 1, false>(topv, topi, (long)row * K, K, V, kT, y, sc, k_i, k_p, hv, hc, mv, sv)) {
+    if (threadIdx.x == 0) stats[row] = GjsdTopkStats{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    return;
+  }
+  const T* s = S + (long)row * V;
+  // ---- the one sweep: the student's normalisers at 1 and at T, exponent unfolded (see gjsd_fwd_kernel)
+  float m = -INFINITY, s1 = 0.f, sT = 0.f;
+  row_sweep<T, NF, false>(s, (const T*)nullptr, V, [&](int, const float* f, const float*) {
+    online_raise<T2>(chunk_max8(f), invT, m, s1, sT);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float df = f[e] - m;
+      const float q = __builtin_amdgcn_exp2f(df * kT);
+      sT += q;
+      s1 += T2 ? q * q : __builtin_amdgcn_exp2f(df * k1);
+    }
+  });
+  block_merge<NF>(m, s1, sT, invT, sc);
+  const float ls1 = __builtin_amdgcn_logf(s1), lsT = __builtin_amdgcn_logf(sT);  // v_log_f32: log2
+  // ---- epilogue: one thread per entry; the first entry of an index owns its element of S
+  const int k = threadIdx.x;
+  bool first = false;
+  const int idx = k < K ? k_i[k] : -1;
+  const float P = tk_mass(k_i, k_p, K, k, idx, first);
+  float tp = 0.f, tq = 0.f, qs = 0.f;
+  if (first && P >= GJ_FLT_MIN) {
+    float q, a2, lm;
+    tk_term((float)s[idx], P, m, kT, -lsT, beta, q, a2, lm);
+    tp = P * (__builtin_amdgcn_logf(P) - lm);
+    tq = q > 0.f ? q * (a2 - lm) : 0.f;
+    qs = q;
+  }
+  const float Sp = block_sum<NF>(tp, sc), Sq = block_sum<NF>(tq, sc), Qs = block_sum<NF>(qs, sc);
+  hv = block_sum<NF>(hv, sc);
+  hc = block_sum<NF>(hc, sc);
+  // c in log2 units and without the 1 - beta of g, as gjsd_fwd_kernel keeps it: sum_S q_j d_j + (1 - Q_S) d0
+  const float c = __builtin_fmaf(fmaxf(1.f - Qs, 0.f), -__builtin_amdgcn_logf(1.f - beta), Sq);
+  const float D = (beta * Sp + (1.f - beta) * c) * GJ_LN2;
+  if (threadIdx.x == 0)
+    stats[row] = GjsdTopkStats{m, ls1, lsT, c, 1.f, (m - (float)s[y]) + ls1 * GJ_LN2, D, hv, hc, mv, sv, 0.f};
+}
+
+// One read of the student row, one write of the gradient; G may alias S: the on-support values are formed from s
+// BEFORE the dense pass, with a workgroup barrier between the two, and stored after it.
+template <typename T, bool T2>
+__global__ __launch_bounds__(GJ_NF) void gjsd_topk_bwd_kernel(const T* S, const _Float16* __restrict__ topv,
+                                                              const int32_t* __restrict__ topi,
+                                                              const int64_t* __restrict__ labels,
+                                                              const GjsdTopkStats* __restrict__ stats,
+                                                              const float* __restrict__ loss_out,
+                                                              const float* __restrict__ grad_out, T* G, int V, int K,
+                                                              float temperature, float alpha, float beta) {
+  constexpr int E = KMAX / GJ_NF;  // entries per thread
+  __shared__ float sc[32];
+  __shared__ __attribute__((aligned(16))) float k_p[KMAX];
+  __shared__ __attribute__((aligned(16))) int k_i[KMAX];
+  const int row = blockIdx.x;
+  const GjsdTopkStats st = stats[row];
+  T* gr = G + (long)row * V;
+  if (st.valid == 0.f) return zero_row<T, GJ_NF>(gr, V);
+  const float invT = 1.f / temperature;
+  const float k1 = GJ_LOG2E, kT = invT * k1;
+  const float N = loss_out[4];
+  const float go = grad_out ? grad_out[0] : 1.f;
+  const float a1 = go * alpha / N;                                                      // * (softmax(s) - e_y)
+  const float aT = go * (1.f - alpha) * temperature / N * ((1.f - beta) * GJ_LN2);  // * q (d - c), d - c in log2 units
+  const long y = labels[row];
+  const T* s = S + (long)row * V;
+  const float A0 = -st.lsT, L1 = -st.ls1;
+  const float r1 = T2 ? __builtin_amdgcn_exp2f(2.f * st.lsT - st.ls1) : 0.f;  // softmax(s) = q^2 r1 at T == 2
+  auto soft1 = [&](float f, float q) { return T2 ? q * q * r1 : __builtin_amdgcn_exp2f(__builtin_fmaf(f - st.m, k1, L1)); };
+  float hv, hc, mv = st.mv, sv = st.sv;  // the forward's renormalisation (a valid row keeps an entry)
+  tk_renorm<GJ_NF, E, true>(topv, topi, (long)row * K, K, V, kT, y, sc, k_i, k_p, hv, hc, mv, sv);
+  int fi[E];
+  float fo[E];
+#pragma unroll
+  for (int u = 0; u < E; ++u) {
+    const int k = threadIdx.x + u * GJ_NF;
+    bool first = false;
+    const int idx = k < K ? k_i[k] : -1;
+    const float P = tk_mass(k_i, k_p, K, k, idx, first);
+    fi[u] = -1;
+    fo[u] = 0.f;
+    if (first && P >= GJ_FLT_MIN) {
+      const float sj = (float)s[idx];
+      float q, a2, lm;
+      tk_term(sj, P, st.m, kT, A0, beta, q, a2, lm);
+      const float w = q > 0.f ? q * ((a2 - lm) - st.c) : 0.f;
+      fi[u] = idx;
+      fo[u] = __builtin_fmaf(a1, soft1(sj, q), aT * w) - ((long)idx == y ? a1 : 0.f);
+    }
+  }
+  // Every gather of s above has returned (fo[] is computed from it) in EVERY wave before any wave stores: with G == S the
+  // dense pass below overwrites logits that another wave's entries point at (kd_bwd_kernel's barrier, same place).
+  __syncthreads();
+  const float w0 = aT * (-__builtin_amdgcn_logf(1.f - beta) - st.c);  // off S: d_j = d0 = -log2(1 - beta)
+  row_sweep<T, GJ_NF, false>(s, (const T*)nullptr, V, [&](int c, const float* f, const float*) {
+    float o[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float q = __builtin_amdgcn_exp2f(__builtin_fmaf(f[e] - st.m, kT, A0));
+      o[e] = __builtin_fmaf(a1, soft1(f[e], q), w0 * q);
+    }
+    if (y >= c && y < c + 8) o[y - c] -= a1;
+    Ld8<T>::store(gr + c, o);
+  });
+  __syncthreads();  // every dense store of this row is complete (vmcnt(0) + barrier) before the fix-up
+#pragma unroll
+  for (int u = 0; u < E; ++u)
+    if (fi[u] >= 0) gr[fi[u]] = (T)fo[u];
+}
+
+int gjsd_topk_check(const void* S, const void* topv, const void* topi, const int64_t* labels, const void* stats,
+                    const float* out, int R, int V, int K, float temperature, float beta, int dtype) {
+  if (R <= 0 || V <= 0 || !S || !labels || !stats || !out) return SD_ERR_SHAPE;
+  if (!topv || !topi) return SD_ERR_NO_TEACHER;
+  if (K <= 0 || K > KMAX) return SD_ERR_SHAPE;
+  if (V & 7) return SD_ERR_ALIGN;
+  if ((uintptr_t)S & 15) return SD_ERR_ALIGN;
+  if (dtype != SD_DTYPE_BF16 && dtype != SD_DTYPE_F32) return SD_ERR_UNSUPPORTED;
+  if (!(temperature > 0.f) || !(temperature < INFINITY)) return SD_ERR_SHAPE;  // NaN fails both comparisons
+  if (!(beta > 0.f && beta < 1.f)) return SD_ERR_SHAPE;                          // likewise
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int64_t sd_gjsd_topk_stats_bytes(int R) { return (int64_t)R * sizeof(GjsdTopkStats); }
+
+extern "C" int sd_gjsd_topk_fwd_rows(const void* student_logits, const void* top_k_v, const void* top_k_i,
+                                     const int64_t* row_labels, void* row_stats, float* loss_out, int R, int V, int K,
+                                     float temperature, float alpha, float beta, int dtype, void* stream) {
+  if (int e = gjsd_topk_check(student_logits, top_k_v, top_k_i, row_labels, row_stats, loss_out, R, V, K, temperature, beta, dtype))
+    return e;
+  hipStream_t st = (hipStream_t)stream;
+  if (int e = by_dtype(dtype, [&](auto tt) -> int {
+        typedef SD_TAG_TYPE(tt) T;
+        SdProfScope prof(SD_K_LOSS_FWD, (double)R * V * sizeof(T), st);
+        // 1024 threads only where the K teacher entries do not fit one thread each at 512 (kd_fwd_kernel's rule)
+        by_flag(temperature == 2.0f, [&](auto t2) {
+          by_flag(K > 512, [&](auto wide) {
+            constexpr int NF = SD_FLAG(wide) ? 1024 : 512;
+            SD_PROF_LABEL("gjsd_topk_fwd_kernel<%s, %s, %d>", type_name(sizeof(T)), flag_name(SD_FLAG(t2)), NF);
+            hipLaunchKernelGGL((gjsd_topk_fwd_kernel<T, SD_FLAG(t2), NF>), dim3(R), dim3(NF), 0, st, (const T*)student_logits,
+                               (const _Float16*)top_k_v, (const int32_t*)top_k_i, row_labels, (GjsdTopkStats*)row_stats, V, K,
+                               temperature, beta);
+          });
+        });
+        SD_CHECK_LAUNCH();
+        return 0;
+      }))
+    return e;
+  hipLaunchKernelGGL((kd_finalize_kernel<GjsdTopkStats, true>), dim3(1), dim3(NT), 0, st, (const GjsdTopkStats*)row_stats,
+                     loss_out, R, temperature, alpha, 0);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sd_gjsd_topk_bwd_rows(const void* student_logits, const void* top_k_v, const void* top_k_i,
+                                     const int64_t* row_labels, const void* row_stats, const float* loss_out,
+                                     const float* grad_total, void* grad_logits, int R, int V, int K, float temperature,
+                                     float alpha, float beta, int dtype, void* stream) {
+  if (int e = gjsd_topk_check(student_logits, top_k_v, top_k_i, row_labels, row_stats, loss_out, R, V, K, temperature, beta, dtype))
+    return e;
+  if (!grad_logits) return SD_ERR_SHAPE;
+  if ((uintptr_t)grad_logits & 15) return SD_ERR_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  return by_dtype(dtype, [&](auto tt) -> int {
+    typedef SD_TAG_TYPE(tt) T;
+    SdProfScope prof(SD_K_LOSS_BWD, (double)R * V * sizeof(T) * 2, st);
+    by_flag(temperature == 2.0f, [&](auto t2) {
+      SD_PROF_LABEL("gjsd_topk_bwd_kernel<%s, %s>", type_name(sizeof(T)), flag_name(SD_FLAG(t2)));
+      hipLaunchKernelGGL((gjsd_topk_bwd_kernel<T, SD_FLAG(t2)>), dim3(R), dim3(GJ_NF), 0, st, (const T*)student_logits,
+                         (const _Float16*)top_k_v, (const int32_t*)top_k_i, row_labels, (const GjsdTopkStats*)row_stats,
+                         loss_out, grad_total, (T*)grad_logits, V, K, temperature, alpha, beta);
     });
     SD_CHECK_LAUNCH();
     return 0;

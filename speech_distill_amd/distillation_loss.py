@@ -14,12 +14,17 @@ KL(teacher || student) and the code path above, untouched.  "reverse_kl" is KL(s
 beta-skewed Jensen-Shannon divergence beta KL(p || m) + (1 - beta) KL(q || m), m = (1 - beta) q + beta p (TRL's
 ``generalized_jsd_loss`` for 0 < beta < 1; its beta = 0 / 1 are "forward_kl" / "reverse_kl"), both with the same T^2 and
 alpha conventions, on a DENSE teacher only (a top-K teacher defines p on K entries): DESIGN.md section 12.
+"jsd_topk" is that same "jsd" against a TOP-K teacher: the K stored log-probs are renormalised at T and scattered to a
+distribution P over the vocabulary (duplicated indices sum), and the divergence is "jsd" with p = P.  It reaches 0 only
+when the student puts all its mass on the K indices, which is what a renormalised top-K teacher asks for.  It takes
+``teacher_top_k_v`` / ``teacher_top_k_i`` only (dense ``teacher_logits`` are "jsd"'s).  There is no "reverse_kl" on a
+top-K teacher: KL(q || P) is infinite as soon as P is 0 where the student has any mass.  DESIGN.md section 12b.
 """
 import torch
 import torch.nn as nn
 
 from . import ops
-from .ops import GJSDLossRowsFn, KDLossFn, KDLossRowsFn
+from .ops import GJSDLossRowsFn, GJSDTopKLossRowsFn, KDLossFn, KDLossRowsFn
 
 
 class DistillationLoss(nn.Module):
@@ -38,6 +43,14 @@ class DistillationLoss(nn.Module):
                 speech_token_mask=None):
         if teacher_logits is None and (teacher_top_k_v is None or teacher_top_k_i is None):
             raise ValueError("Either teacher_logits or top_k must be provided")
+        if self.divergence == ops.TOPK_DIVERGENCE:
+            # as below, with the top-K rows selected the way the trainer selects them for the forward KL
+            self._need_topk(teacher_logits, teacher_top_k_v, teacher_top_k_i)
+            rows, row_labels = ops.loss_rows(labels, speech_token_mask)
+            V = student_logits.shape[-1]
+            pick = (lambda x: x.to(rows.device).reshape(-1, x.size(-1))[rows])
+            return self.forward_rows(student_logits.reshape(-1, V)[rows], row_labels,
+                                     teacher_top_k_v=pick(teacher_top_k_v), teacher_top_k_i=pick(teacher_top_k_i))
         if self.divergence != "forward_kl":
             # eval / return_outputs path: select the rows as the trainer does and gather them (one copy of R rows)
             self._need_dense(teacher_logits)
@@ -61,6 +74,12 @@ class DistillationLoss(nn.Module):
             raise ValueError("Either teacher_logits or top_k must be provided")
         if teacher_logits is not None:
             teacher_logits = teacher_logits.detach()
+        if self.divergence == ops.TOPK_DIVERGENCE:
+            self._need_topk(teacher_logits, teacher_top_k_v, teacher_top_k_i)
+            total, out = GJSDTopKLossRowsFn.apply(student_logits.contiguous(), row_labels, teacher_top_k_v, teacher_top_k_i,
+                                                  self.temperature, self.alpha, self.beta,
+                                                  self.inplace_grad and student_logits.requires_grad)
+            return total, out[1], out[2], out[3]
         if self.divergence != "forward_kl":
             self._need_dense(teacher_logits)
             total, out = GJSDLossRowsFn.apply(student_logits.contiguous(), row_labels, teacher_logits, self.temperature,
@@ -76,3 +95,8 @@ class DistillationLoss(nn.Module):
         if teacher_logits is None:
             raise ValueError(f"divergence={self.divergence!r} needs dense teacher_logits: a top-K teacher defines the "
                              "teacher distribution on K entries only")
+
+    def _need_topk(self, teacher_logits, teacher_top_k_v, teacher_top_k_i):
+        if teacher_logits is not None or teacher_top_k_v is None or teacher_top_k_i is None:
+            raise ValueError(f"divergence={self.divergence!r} takes a top-K teacher (teacher_top_k_v, teacher_top_k_i); "
+                             "for dense teacher_logits use divergence='jsd'")

@@ -457,15 +457,16 @@ class KDLossRowsFn(torch.autograd.Function):
 
 
 DIVERGENCES = {"reverse_kl": 1, "jsd": 2}  # include/sd_hip.h SD_DIV_*; "forward_kl" is KDLossRowsFn
+TOPK_DIVERGENCE = "jsd_topk"               # the jsd against a top-K teacher: GJSDTopKLossRowsFn (sd_gjsd_topk_*_rows)
 
 
 def check_divergence(divergence, beta):
     """ValueError for a divergence the loss does not know, or a ``jsd`` whose beta is outside (0, 1) (NaN included):
     the jsd formula tends to 0 at both ends, TRL's beta = 0 / 1 are ``forward_kl`` / ``reverse_kl``."""
-    if divergence != "forward_kl" and divergence not in DIVERGENCES:
-        raise ValueError(f"unknown divergence {divergence!r}: one of 'forward_kl', 'reverse_kl', 'jsd'")
-    if divergence == "jsd" and not 0.0 < float(beta) < 1.0:
-        raise ValueError(f"divergence='jsd' needs 0 < beta < 1, got {beta!r} (beta = 0 is 'forward_kl', beta = 1 is "
+    if divergence != "forward_kl" and divergence not in DIVERGENCES and divergence != TOPK_DIVERGENCE:
+        raise ValueError(f"unknown divergence {divergence!r}: one of 'forward_kl', 'reverse_kl', 'jsd', 'jsd_topk'")
+    if divergence in ("jsd", TOPK_DIVERGENCE) and not 0.0 < float(beta) < 1.0:
+        raise ValueError(f"divergence={divergence!r} needs 0 < beta < 1, got {beta!r} (beta = 0 is 'forward_kl', beta = 1 is "
                          "'reverse_kl')")
 
 
@@ -517,6 +518,59 @@ class GJSDLossRowsFn(torch.autograd.Function):
         check(load_lib().sd_gjsd_bwd_rows(s.data_ptr(), teacher_logits.data_ptr(), row_labels.data_ptr(), stats.data_ptr(),
                                           out.data_ptr(), go.data_ptr(), grad.data_ptr(), R, V, temperature, alpha, beta,
                                           mode, dt, _stream()), "sd_gjsd_bwd_rows")
+        return grad, None, None, None, None, None, None, None
+
+
+class GJSDTopKLossRowsFn(torch.autograd.Function):
+    """The beta-skewed Jensen-Shannon loss against a top-K teacher (sd_gjsd_topk_*_rows) on rows the caller has already
+    shifted and selected: student_logits [R,V], row_labels [R], (top_v fp16, top_i int32) [R,K] as ``logsoftmax_topk`` or
+    the offline extraction writes them.  The teacher's K entries are renormalised at T and scattered to a distribution P
+    over the vocabulary (duplicates sum); the divergence is "jsd" against P.  An entry with an index outside [0, V) or a
+    value that is not finite is ignored; a row without a usable entry is a masked row.
+    Returns (total, out fp32[8] = total, task, distill, teacher, N, n_hits, 0, 0).  R == 0 launches nothing and returns
+    zeros that are connected to autograd."""
+
+    @staticmethod
+    def forward(ctx, student_logits, row_labels, top_v, top_i, temperature, alpha, beta, inplace_grad):
+        check_divergence(TOPK_DIVERGENCE, beta)
+        if top_v is None or top_i is None:
+            raise ValueError(f"divergence={TOPK_DIVERGENCE!r} needs a top-K teacher (teacher_top_k_v, teacher_top_k_i)")
+        s = _need(student_logits, None, "student_logits")
+        R, V = s.shape
+        dt = _dt(s)
+        lib = load_lib()
+        row_labels = _need(row_labels.to(torch.int64), torch.int64, "row_labels")
+        K = int(top_v.shape[-1])
+        if tuple(top_v.shape) != (R, K) or tuple(top_i.shape) != (R, K):
+            raise ValueError(f"top-K teacher {tuple(top_v.shape)} / {tuple(top_i.shape)} for {R} rows: expected [R, K] twice")
+        top_v = top_v.to(device=s.device, dtype=torch.float16).contiguous()
+        top_i = top_i.to(device=s.device, dtype=torch.int32).contiguous()
+        ctx.cfg = (R, V, K, float(temperature), float(alpha), float(beta), dt, bool(inplace_grad))
+        if R == 0:   # the C entry refuses R <= 0; the loss of no row is 0 and so is its (empty) gradient
+            out = torch.zeros(8, dtype=torch.float32, device=s.device)
+            ctx.save_for_backward(s, row_labels, top_v, top_i, out, out)
+            ctx.mark_non_differentiable(out)
+            return out[0].clone(), out
+        stats = torch.empty(lib.sd_gjsd_topk_stats_bytes(R), dtype=torch.uint8, device=s.device)
+        out = torch.empty(8, dtype=torch.float32, device=s.device)
+        check(lib.sd_gjsd_topk_fwd_rows(s.data_ptr(), top_v.data_ptr(), top_i.data_ptr(), row_labels.data_ptr(),
+                                        stats.data_ptr(), out.data_ptr(), R, V, K, float(temperature), float(alpha),
+                                        float(beta), dt, _stream()), "sd_gjsd_topk_fwd_rows")
+        ctx.save_for_backward(s, row_labels, top_v, top_i, stats, out)
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, g_total, _g_out):
+        s, row_labels, top_v, top_i, stats, out = ctx.saved_tensors
+        R, V, K, temperature, alpha, beta, dt, inplace = ctx.cfg
+        grad = s if inplace else torch.empty_like(s)
+        if R == 0:
+            return grad, None, None, None, None, None, None, None
+        go = g_total.to(torch.float32).reshape(1).contiguous()
+        check(load_lib().sd_gjsd_topk_bwd_rows(s.data_ptr(), top_v.data_ptr(), top_i.data_ptr(), row_labels.data_ptr(),
+                                               stats.data_ptr(), out.data_ptr(), go.data_ptr(), grad.data_ptr(), R, V, K,
+                                               temperature, alpha, beta, dt, _stream()), "sd_gjsd_topk_bwd_rows")
         return grad, None, None, None, None, None, None, None
 
 

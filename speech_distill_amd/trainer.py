@@ -99,7 +99,9 @@ class FlatStudentTrainer(Trainer):
 class DistillationTrainer(FlatStudentTrainer):
     """``divergence`` ("forward_kl", "reverse_kl", "jsd") and ``beta``: see ``DistillationLoss``; anything but
     "forward_kl" needs the dense teacher (``top_k <= 0`` or ``is_quantized_teacher``) and refuses batches that carry
-    pre-extracted ``teacher_top_k_v``.
+    pre-extracted ``teacher_top_k_v``.  ``"jsd_topk"`` is the "jsd" against a top-K teacher and runs wherever the forward KL
+    does: a live teacher with ``top_k > 0`` (refused at construction otherwise, or with a quantised teacher), or batches
+    that carry pre-extracted ``teacher_top_k_v`` / ``teacher_top_k_i``, with or without a teacher model.
 
     ``lmbda`` in [0, 1]: the probability that a training micro-batch is made on-policy -- one draw per micro-batch from a
     CPU generator seeded from ``args.seed`` and the process index; below ``lmbda`` the student generates from the batch's
@@ -120,7 +122,12 @@ class DistillationTrainer(FlatStudentTrainer):
                  divergence="forward_kl", beta=0.5, lmbda=0.0, on_policy_generate=None, **kwargs):
         # everything that can be refused without a model is refused before HF's constructor touches one
         ops.check_divergence(divergence, beta)
-        if divergence != "forward_kl" and not (top_k <= 0 or is_quantized_teacher):
+        if divergence == ops.TOPK_DIVERGENCE:
+            if top_k <= 0 or is_quantized_teacher:
+                raise ValueError(f"divergence={divergence!r} needs a top-K teacher (top_k > 0, not a quantised teacher), got "
+                                 f"top_k={top_k}, is_quantized_teacher={is_quantized_teacher}: the dense teacher "
+                                 "distribution goes with divergence='jsd'")
+        elif divergence != "forward_kl" and not (top_k <= 0 or is_quantized_teacher):
             raise ValueError(f"divergence={divergence!r} needs the dense teacher distribution: pass top_k=0 (a top-K "
                              f"teacher defines it on K entries only), got top_k={top_k}")
         if not 0.0 <= float(lmbda) <= 1.0:
@@ -451,7 +458,7 @@ class DistillationTrainer(FlatStudentTrainer):
         teacher_top_k_v = inputs.pop("teacher_top_k_v", None)
         teacher_top_k_i = inputs.pop("teacher_top_k_i", None)
 
-        if self.divergence != "forward_kl" and teacher_top_k_v is not None:
+        if self.divergence not in ("forward_kl", ops.TOPK_DIVERGENCE) and teacher_top_k_v is not None:
             raise ValueError(f"divergence={self.divergence!r} needs the dense teacher distribution; this batch carries "
                              "pre-extracted teacher_top_k_v (K entries per position)")
         need_teacher = teacher_top_k_v is None and self.teacher_model is not None
