@@ -241,6 +241,16 @@ int sd_attn_bwd_varlen(const void* q, const void* k, const void* v, const void* 
  * descending, ties to the lowest index; lse_out fp32 [rows] nullable. */
 int sd_logsoftmax_topk(const void* logits, void* top_v, void* top_i, float* lse_out, int rows, int64_t row_stride,
                        int V, int K, int dtype, void* stream);
+/* the teacher's TAIL mass at a temperature, from the same logits and the top-K indices of above (top_i int32 [rows,K]):
+ *   tail_out[r] = sum_{j not in {top_i[r,k]}} exp(x_j / T) / sum_{j < V} exp(x_j / T)       fp32 [rows]
+ * summed directly over the non-members (not 1 - the members' share: that loses a tail below ~1e-6), membership by index
+ * (ties cross the K-th value).  An index outside [0, V) is ignored and never used as an address, a duplicate counts
+ * once; columns V..row_stride are never read.  One sweep of the row; fixed reduction order.
+ * rows, V or K <= 0, K > 1024, K > V, row_stride < V, a NULL pointer, temperature not in (0, inf) SD_ERR_SHAPE; V or
+ * row_stride % 8 != 0 or logits off 16 bytes SD_ERR_ALIGN; V > 524 288 (the row's bitmap is 64 KB of LDS) or an unknown
+ * dtype SD_ERR_UNSUPPORTED. */
+int sd_topk_tail(const void* logits, const void* top_i, float* tail_out, int rows, int64_t row_stride, int V, int K,
+                 float temperature, int dtype, void* stream);
 
 /* ---- which rows the loss reads (distillation_loss.py:31-45: shift by one, labels != -100, optional speech mask).
  * labels int64 [B,T]; speech_mask int64 [B,T] nullable; mask_a / mask_b: attention masks int64 [B,T] (nullable) to
@@ -337,6 +347,32 @@ int sd_gjsd_topk_fwd_rows(const void* student_logits, const void* top_k_v, const
 int sd_gjsd_topk_bwd_rows(const void* student_logits, const void* top_k_v, const void* top_k_i, const int64_t* row_labels,
                           const void* row_stats, const float* loss_out, const float* grad_total, void* grad_logits, int R,
                           int V, int K, float temperature, float alpha, float beta, int dtype, void* stream);
+
+/* ---- a top-K teacher WITH A TAIL BUCKET: forward KL, reverse KL and the skewed JSD over K + 1 outcomes.  top_k_tail fp32
+ * [R] is the teacher's mass outside its top-K at the loss temperature (sd_topk_tail).  Per row, with p, the kept
+ * entries and the duplicate merge as sd_gjsd_topk_*:
+ *   P_j = (1 - tau) sum_{k: i_k = j} p_k on S = {j : P_j > 0},  P_0 = tau;   q = softmax(s / T),  q_j on S,
+ *   q_0 = sum_{j not in S} q_j                       (b ranges over S and bucket 0, 0 log 0 = 0)
+ *   SD_DIV_FORWARD_KL  D = sum_b P_b (log P_b - log q_b)
+ *   SD_DIV_REVERSE_KL  D = sum_b q_b (log q_b - log P_b)
+ *   SD_DIV_JSD         D = beta sum_b P_b (log P_b - log m_b) + (1 - beta) sum_b q_b (log q_b - log m_b),  m = (1 - beta) q + beta P
+ * Every D is finite, exact on the top-K part, and a lower bound of the divergence against the dense teacher (merging
+ * outcomes cannot increase it).  log q_0 is formed in log space from the off-support elements' own maximum.
+ * A row is masked (stats zero, gradient exactly zero, not in N) when its label is -100 or outside [0, V), when no entry
+ * is kept, or when its tau is NaN, < 0 or >= 1; a tau in [0, 2^-100) counts as 2^-100.
+ * loss_out, row_stats (sd_gjsd_tail_stats_bytes(R)), grad_total, aliasing, arithmetic and order: as sd_gjsd_topk_*.
+ * Before any launch: what sd_gjsd_topk_* refuses, with beta checked for SD_DIV_JSD only; K >= V SD_ERR_SHAPE (an
+ * off-support element always exists); a NULL top_k_tail SD_ERR_NO_TEACHER; an unknown mode, or V > 458 752 (the
+ * forward keeps a V-bit bitmap in LDS), SD_ERR_UNSUPPORTED. */
+#define SD_DIV_FORWARD_KL 0
+int64_t sd_gjsd_tail_stats_bytes(int R);
+int sd_gjsd_tail_fwd_rows(const void* student_logits, const void* top_k_v, const void* top_k_i, const float* top_k_tail,
+                          const int64_t* row_labels, void* row_stats, float* loss_out, int R, int V, int K,
+                          float temperature, float alpha, float beta, int mode, int dtype, void* stream);
+int sd_gjsd_tail_bwd_rows(const void* student_logits, const void* top_k_v, const void* top_k_i, const float* top_k_tail,
+                          const int64_t* row_labels, const void* row_stats, const float* loss_out,
+                          const float* grad_total, void* grad_logits, int R, int V, int K, float temperature, float alpha,
+                          float beta, int mode, int dtype, void* stream);
 
 /* ---- causal-LM cross-entropy on selected rows: the Stage-1 loss (stage1.py: TRL SFTTrainer over HF
  * Qwen3ForCausalLM(labels=...), i.e. HF ForCausalLMLoss -- shift by one, ignore_index -100, reduction "sum" divided by

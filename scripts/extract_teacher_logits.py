@@ -2,7 +2,10 @@
 """Offline teacher top-K extraction on the MI355X path: counterpart of the reference's
 ``extract_teacher_logits.py`` (:17-146).  Teacher-only forward (BASELINE config 5: batch 64, seq_len 512)
 -> log-softmax -> top-K -> per-sample UNPADDED fp16 / int32 arrays ``teacher_top_k_v`` / ``teacher_top_k_i``
-(extract_teacher_logits.py:120-141), written next to the input columns with ``save_to_disk``."""
+(extract_teacher_logits.py:120-141), written next to the input columns with ``save_to_disk``.
+(+) ``--tail_temperature T`` also writes ``teacher_top_k_tail`` (per position, fp32: the teacher's mass outside its top-K at
+temperature T, ``ops.topk_tail``) and ``teacher_top_k_tail_T`` (per sample: that T) for the ``_tail`` divergences of
+scripts/train.py, which compares the stored T with its ``--temperature``."""
 import argparse
 import os
 import sys
@@ -12,22 +15,26 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def extract(teacher, batches, top_k, device):
-    """batches: iterable of dicts with (teacher_)input_ids / attention_mask (right padded). Yields per-sample arrays."""
+def extract(teacher, batches, top_k, device, tail_temperature=None):
+    """batches: iterable of dicts with (teacher_)input_ids / attention_mask (right padded). Yields per-sample arrays:
+    (values, indices), and with a ``tail_temperature`` also the per-position tails at it."""
     from speech_distill_amd import ops
-    all_v, all_i = [], []
+    all_v, all_i, all_t = [], [], []
     with torch.no_grad():
         for b in batches:
             ids = b.get("teacher_input_ids", b["input_ids"]).to(device)                       # :105
             am = b.get("teacher_attention_mask", b["attention_mask"]).to(device)
             logits = teacher(input_ids=ids, attention_mask=am).logits                         # :110
             v, i = ops.logsoftmax_topk(logits, top_k)                                         # :114-117
+            tail = ops.topk_tail(logits, i, tail_temperature).cpu() if tail_temperature is not None else None
             lens = am.sum(1).cpu().tolist()
             v, i = v.cpu(), i.cpu()
             for r, n in enumerate(lens):                                                      # :120-129
                 all_v.append(v[r, : int(n)].numpy())
                 all_i.append(i[r, : int(n)].numpy())
-    return all_v, all_i
+                if tail is not None:
+                    all_t.append(tail[r, : int(n)].numpy())
+    return (all_v, all_i) if tail_temperature is None else (all_v, all_i, all_t)
 
 
 def nested_column(arrays, arrow_type, max_chunk_elems=1 << 30):
@@ -58,6 +65,16 @@ def nested_column(arrays, arrow_type, max_chunk_elems=1 << 30):
     return pa.chunked_array(chunks)
 
 
+def tail_columns(tails, tail_temperature):
+    """(+) the two arrow columns of ``--tail_temperature``: per-sample [len_i] fp32 tails and the temperature they were
+    taken at, once per sample; nothing when the flag is off."""
+    if tail_temperature is None:
+        return {}
+    import pyarrow as pa
+    return {"teacher_top_k_tail": pa.array([t.tolist() for t in tails], type=pa.list_(pa.float32())),
+            "teacher_top_k_tail_T": pa.array([float(tail_temperature)] * len(tails), type=pa.float32())}
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--teacher_model_path", required=True)   # extract_teacher_logits.py:154
@@ -78,7 +95,13 @@ def parse_args(argv=None):
     ap.add_argument("--pad_token_id", type=int, default=153478, help="(+) when the model directory holds no tokenizer")
     ap.add_argument("--teacher_precision", choices=("bf16", "mxfp8"), default="bf16",
                     help="(+) mxfp8: the frozen teacher's decoder projections run as MXFP8 GEMMs (lm_head stays bf16)")
-    return ap.parse_args(argv)
+    ap.add_argument("--tail_temperature", type=float, default=None,
+                    help="(+) also store the teacher's mass outside its top-K at this temperature (teacher_top_k_tail, "
+                         "teacher_top_k_tail_T): what train.py --divergence *_tail reads; default: off")
+    cfg = ap.parse_args(argv)
+    if cfg.tail_temperature is not None and not 0.0 < cfg.tail_temperature < float("inf"):
+        ap.error(f"--tail_temperature must be a positive number, got {cfg.tail_temperature}")
+    return cfg
 
 
 def main():
@@ -113,11 +136,13 @@ def main():
     pad_id = tok.pad_token_id
     loader = torch.utils.data.DataLoader(ds, batch_size=cfg.batch_size, shuffle=False,
                                          collate_fn=ProcessedDataCollator(tok, speech_bos=cfg.speech_bos, pad_token_id=pad_id))
-    v, i = extract(teacher, loader, cfg.top_k, dev)
+    v, i, *tails = extract(teacher, loader, cfg.top_k, dev, cfg.tail_temperature)
     assert len(v) == len(ds)                                                                   # :133-137
     import pyarrow as pa
     ds = ds.add_column("teacher_top_k_v", nested_column(v, pa.float16()))                      # :140-141
     ds = ds.add_column("teacher_top_k_i", nested_column(i, pa.int32()))
+    for name, col in tail_columns(tails[0] if tails else None, cfg.tail_temperature).items():   # (+)
+        ds = ds.add_column(name, col)
     ds.save_to_disk(cfg.output_path)                                                           # :145
 
 

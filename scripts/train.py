@@ -87,11 +87,15 @@ def parse_args(argv=None):
                    help="(+) what gradient checkpointing (on, as in train.py:512-517) does: layer recompute always, never, "
                         "or only when the activations would take more than a quarter of HBM")
     # (+) on-policy (generalised) distillation; the defaults are the reference's loop
-    p.add_argument("--divergence", choices=("forward_kl", "reverse_kl", "jsd", "jsd_topk"), default="forward_kl",
+    p.add_argument("--divergence", default="forward_kl",
+                   choices=("forward_kl", "reverse_kl", "jsd", "jsd_topk", "forward_kl_tail", "reverse_kl_tail", "jsd_tail"),
                    help="(+) the distillation term: forward KL (the reference), reverse KL, or the beta-skewed Jensen-Shannon "
                         "divergence; reverse_kl and jsd need the dense teacher (--top_k 0), jsd_topk is jsd against the "
-                        "renormalised top-K teacher (--top_k > 0, or a pre-extracted dataset)")
-    p.add_argument("--beta", type=float, default=0.5, help="(+) skew of --divergence jsd / jsd_topk, in (0, 1)")
+                        "renormalised top-K teacher (--top_k > 0, or a pre-extracted dataset); forward_kl_tail, "
+                        "reverse_kl_tail and jsd_tail compare over the K indices plus one bucket for the teacher's mass "
+                        "outside them (--top_k > 0, or a dataset extracted with --tail_temperature): finite on a top-K "
+                        "teacher, so they go with --lmbda > 0 at the default --top_k")
+    p.add_argument("--beta", type=float, default=0.5, help="(+) skew of --divergence jsd / jsd_topk / jsd_tail, in (0, 1)")
     p.add_argument("--lmbda", type=float, default=0.0,
                    help="(+) probability that a training micro-batch is made on-policy (the student's own sampled completion)")
     p.add_argument("--on_policy_max_new_tokens", type=int, default=256)
@@ -113,6 +117,19 @@ def parse_args(argv=None):
     return cfg
 
 
+def check_tail_temperature(dataset, cfg):
+    """A dataset extracted with ``--tail_temperature`` stores the temperature of its ``teacher_top_k_tail`` per sample
+    (``teacher_top_k_tail_T``): a ``_tail`` divergence at another ``--temperature`` would read tails that are not its
+    teacher's.  Compares the first sample's; exits on a mismatch."""
+    if not cfg.divergence.endswith("_tail") or "teacher_top_k_tail_T" not in (getattr(dataset, "column_names", None) or ()):
+        return
+    stored = float(dataset[0]["teacher_top_k_tail_T"])
+    if abs(stored - float(cfg.temperature)) > 1e-6 * max(1.0, abs(stored)):
+        raise SystemExit(f"--divergence {cfg.divergence} at --temperature {cfg.temperature}: the dataset's teacher_top_k_tail "
+                         f"was extracted at temperature {stored} (extract_teacher_logits.py --tail_temperature); extract it "
+                         "again at the training temperature")
+
+
 def distill_kwargs(cfg, pad=None):
     """The DistillationTrainer keywords of the (+) on-policy flags: only what differs from the trainer's defaults, so the
     default command line constructs the trainer exactly as before.  Exits when the flags cannot work together."""
@@ -120,6 +137,10 @@ def distill_kwargs(cfg, pad=None):
         if cfg.top_k <= 0 or cfg.load_teacher_in_4bit or cfg.load_teacher_in_8bit:
             raise SystemExit("--divergence jsd_topk needs a top-K teacher (--top_k > 0, no 4/8-bit teacher); on the dense "
                              "teacher distribution the same divergence is --divergence jsd")
+    elif cfg.divergence.endswith("_tail"):
+        if cfg.top_k <= 0 or cfg.load_teacher_in_4bit or cfg.load_teacher_in_8bit:
+            raise SystemExit(f"--divergence {cfg.divergence} needs a top-K teacher (--top_k > 0, no 4/8-bit teacher); on the "
+                             f"dense teacher distribution the same divergence is --divergence {cfg.divergence[:-len('_tail')]}")
     elif cfg.divergence != "forward_kl" and cfg.top_k > 0 and not (cfg.load_teacher_in_4bit or cfg.load_teacher_in_8bit):
         raise SystemExit(f"--divergence {cfg.divergence} needs the dense teacher distribution: pass --top_k 0 "
                          f"(got --top_k {cfg.top_k}; a top-K teacher defines it on K entries only)")
@@ -215,6 +236,7 @@ def main():
         if not {"student_input_ids", "teacher_input_ids"} <= set(dataset.column_names):   # train.py:253-256
             raise SystemExit("this path takes PRE-PROCESSED rows (student_input_ids / teacher_input_ids [+ teacher_top_k_v/i]); "
                              "the on-the-fly DistillDataProcessor of train.py:279-328 is outside the hot path")
+        check_tail_temperature(dataset, cfg)           # (+)
         eval_dataset = None
         if cfg.save_strategy != "no":                  # train.py:262-269
             split = dataset.train_test_split(test_size=min(cfg.eval_samples, max(1, len(dataset) // 5)), seed=42)

@@ -164,6 +164,7 @@ PROTOTYPES = {
     "sd_attn_fwd_varlen": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(Varlen), _i64, _i64, _i64, _i64, _i, _i, _i, _i, _f, _vp]),
     "sd_attn_bwd_varlen": (_i, [_vp] * 10 + [C.POINTER(Varlen)] + [_i64] * 7 + [_i, _i, _i, _i, _f, _vp, _vp]),
     "sd_logsoftmax_topk": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp]),
+    "sd_topk_tail": (_i, [_vp, _vp, _vp, _i, _i64, _i, _i, _f, _i, _vp]),
     "sd_kdloss_stats_bytes": (_i64, [_i, _i]),
     "sd_celoss_stats_bytes": (_i64, [_i]),
     "sd_celoss_fwd_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
@@ -181,6 +182,9 @@ PROTOTYPES = {
     "sd_gjsd_topk_stats_bytes": (_i64, [_i]),
     "sd_gjsd_topk_fwd_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _i, _vp]),
     "sd_gjsd_topk_bwd_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _i, _vp]),
+    "sd_gjsd_tail_stats_bytes": (_i64, [_i]),
+    "sd_gjsd_tail_fwd_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _i, _i, _vp]),
+    "sd_gjsd_tail_bwd_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _i, _i, _vp]),
     "sd_rows_scatter": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "sd_loss_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "sd_packed_rows": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),

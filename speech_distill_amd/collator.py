@@ -9,7 +9,11 @@ fixture G3, ``tests/test_collator_golden.py``) --
   without one has no targets, data.py:273-276, 350-387);
 * ``teacher_input_ids`` / ``teacher_attention_mask`` when the features carry teacher sequences;
 * ``teacher_top_k_v`` (pad 0.0) / ``teacher_top_k_i`` (pad 0) ``[B, T, K]`` cut or padded to the STUDENT width when the
-  features carry pre-extracted top-K (data.py:330-348).
+  features carry pre-extracted top-K (data.py:330-348);
+* beyond the reference, ``teacher_top_k_tail`` fp32 ``[B, T]`` (the teacher's mass outside its top-K per position, written
+  by ``extract_teacher_logits.py --tail_temperature``) when the features carry it next to the top-K: cut or padded like
+  its siblings, pad value 1.0 -- a tail of 1 masks the position for the ``_tail`` divergences, as its label does.
+  Batches without the column are unchanged.
 
 ``padding_free=True`` (beyond the reference): the batch's samples flattened in order into ONE row without padding, in the
 format of ``stage1.Stage1Collator`` / HF ``DataCollatorWithFlattening(return_flash_attn_kwargs=True, separator_id=-100)``:
@@ -17,7 +21,7 @@ format of ``stage1.Stage1Collator`` / HF ``DataCollatorWithFlattening(return_fla
 int32 ``[n+1]``, ``max_length_q`` / ``_k`` ints, no attention masks.  A document's labels are the padded collator's labels
 of that sample (both rules above, the ``speech_bos`` one evaluated per document) with -100 in its first cell;
 ``teacher_input_ids`` ``[1, M]`` (per sample as long as the student's, else ValueError) and the top-K blocks, each cut or
-padded to its sample's student length, ``[1, M, K]``.  A feature may be ``{"samples": [sample, ...]}`` (a bin of
+padded to its sample's student length, ``[1, M, K]`` (``teacher_top_k_tail`` likewise, ``[1, M]``).  A feature may be ``{"samples": [sample, ...]}`` (a bin of
 ``packing.PackedView``): its samples are taken in order.
 
 Built differently from the reference: every ragged field becomes ONE scatter of its concatenated values into a
@@ -87,6 +91,12 @@ class ProcessedDataCollator:
             out[b, :n] = it[:n]
         return out
 
+    @staticmethod
+    def _tail_grid(items, width: int) -> torch.Tensor:
+        """Per-sample ``[len_i]`` tails -> fp32 ``[B, width]``, cut or padded with 1.0 (the top-K blocks' rule)."""
+        return _ragged_to_grid([torch.as_tensor(it, dtype=torch.float32).reshape(-1)[:width] for it in items], width, 1.0,
+                               torch.float32)
+
     # -------------------------------------------------------------------------------------------------- call
     def __call__(self, features: List[Dict[str, Any]]) -> Dict[str, torch.Tensor]:
         if self.padding_free:
@@ -106,6 +116,8 @@ class ProcessedDataCollator:
         if features[0].get("teacher_top_k_v") is not None:
             batch["teacher_top_k_v"] = self._topk_grid([f["teacher_top_k_v"] for f in features], ids.size(1), 0.0)
             batch["teacher_top_k_i"] = self._topk_grid([f["teacher_top_k_i"] for f in features], ids.size(1), 0)
+            if features[0].get("teacher_top_k_tail") is not None:
+                batch["teacher_top_k_tail"] = self._tail_grid([f["teacher_top_k_tail"] for f in features], ids.size(1))
         return batch
 
     # ------------------------------------------------------------------------------------------ padding-free
@@ -156,4 +168,7 @@ class ProcessedDataCollator:
             for key, fill in (("teacher_top_k_v", 0.0), ("teacher_top_k_i", 0)):
                 # one [1, len_i, K] grid per sample (the padded rule, with the sample's own length as the width)
                 batch[key] = torch.cat([self._topk_grid([s[key]], int(n), fill) for s, n in zip(samples, lens)], dim=1)
+            if samples[0].get("teacher_top_k_tail") is not None:
+                batch["teacher_top_k_tail"] = torch.cat([self._tail_grid([s["teacher_top_k_tail"]], int(n))
+                                                         for s, n in zip(samples, lens)], dim=1)
         return batch

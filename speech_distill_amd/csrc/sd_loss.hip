@@ -1176,3 +1176,306 @@ extern "C" int sd_gjsd_topk_bwd_rows(const void* student_logits, const void* top
     return 0;
   });
 }
+
+// ---------------------------------------------------------------------- top-K teacher with a tail bucket: KL, reverse KL, JSD
+// The top-K teacher of above plus ONE number per row: tau, the teacher's mass outside its top-K at T (sd_topk_tail).
+// Teacher and student are compared as distributions over K + 1 outcomes -- the indices of S and bucket 0, "anything else":
+//   P_j = (1 - tau) sum_{k: i_k = j} p_k on S,  P_0 = tau;   q_j = softmax(s / T)_j on S,  q_0 = sum_{j not in S} q_j
+//   SD_DIV_FORWARD_KL  D = sum_b P_b (log P_b - log q_b)         d D / d s_j = (q_j - P_j) / T on S, q_j (1 - tau / q_0) / T off
+//   SD_DIV_REVERSE_KL  D = sum_b q_b (log q_b - log P_b)         g_b = log q_b - log P_b  (+ 1)
+//   SD_DIV_JSD         D = b sum_b P_b (log P_b - log m_b) + (1-b) sum_b q_b (log q_b - log m_b),  g_b = (1-b)(log q_b - log m_b)
+//   d D / d s_j = q_j (g_b(j) - c) / T,  c = sum_b q_b g_b;  every off-support element shares g_0.
+// p, the kept entries and the duplicate merge are tk_renorm / tk_mass; S = {j : P_j >= FLT_MIN}.
+// Forward: the members of S are marked in an LDS bitmap (sd_rows.cuh) BEFORE the sweep, and the sweep takes the online
+// (max, sum-exp at 1, sum-exp at T) over the OFF-support elements only, with their own maximum m0: log q_0 =
+// (m0 - m) / T + log sum0 - log sumT never passes through q_0 (a student spike of 200 on a support index leaves q_0 =
+// 1e-80, and 1 - Q_S = 0).  The at most K on-support logits are gathered in the epilogue and added to the normalisers.
+// Backward: gjsd_topk_bwd_kernel's shape; no bitmap (the fix-up overwrites the on-support elements).  The forward KL's
+// off-support element is q_j - tau q_j / q_0 = q_j - exp2(log2 q_j + log2 tau - log2 q_0): the second exponential is the
+// price of never forming tau / q_0, which overflows where q_0 underflows.
+namespace {
+
+struct GjsdTailStats {  // 12 floats per row, GjsdTopkStats' layout with log2 q_0 in its last slot
+  float m, ls1, lsT, c, valid, task, distill, teacher, hits, mv, sv, lq0;
+};
+
+constexpr float GJ_TAIL_MIN = 0x1p-100f;  // a tail in [0, 2^-100) counts as 2^-100
+
+// tau of a row that is not masked by it: in [0, 1), NaN fails
+SD_DEV bool tail_ok(float tau) { return tau >= 0.f && tau < 1.f; }
+
+// log2 m_0 of the JSD's bucket 0, m_0 = (1 - beta) q_0 + beta tau, from log2 q_0 and log2 tau: in log space
+SD_DEV float tail_lm0(float lq0, float lt, float beta) {
+  const float a = __builtin_amdgcn_logf(1.f - beta) + lq0, b = __builtin_amdgcn_logf(beta) + lt;
+  const float hi = fmaxf(a, b), lo = fminf(a, b);
+  return hi + __builtin_amdgcn_logf(1.f + __builtin_amdgcn_exp2f(lo - hi));
+}
+
+// No register cap, as gjsd_topk_fwd_kernel (see the note in front of it).
+template <typename T, bool T2, int NF>
+__global__ __launch_bounds__(NF) void gjsd_tail_fwd_kernel(const T* __restrict__ S, const _Float16* __restrict__ topv,
+                                                           const int32_t* __restrict__ topi,
+                                                           const float* __restrict__ tail,
+                                                           const int64_t* __restrict__ labels,
+                                                           GjsdTailStats* __restrict__ stats, int V, int K,
+                                                           float temperature, float beta, int mode) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t row_bits[];
+  __shared__ float sc[32];
+  __shared__ __attribute__((aligned(16))) float k_p[NF];
+  __shared__ __attribute__((aligned(16))) int k_i[NF];
+  const int row = blockIdx.x;
+  const long y = labels[row];
+  const float invT = 1.f / temperature;
+  const float k1 = GJ_LOG2E, kT = invT * k1;
+  const float tau_in = tail[row];
+  float hv = 0.f, hc = 0.f, mv = 0.f, sv = 0.f;
+  if (y < 0 || y >= V || !tail_ok(tau_in) ||
+      !tk_renorm<NF, 1, false>(topv, topi, (long)row * K, K, V, kT, y, sc, k_i, k_p, hv, hc, mv, sv)) {
+    if (threadIdx.x == 0) stats[row] = GjsdTailStats{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    return;
+  }
+  const float tau = fmaxf(tau_in, GJ_TAIL_MIN);
+  const T* s = S + (long)row * V;
+  // ---- the support: one thread per entry; the first entry of an index owns its element of S and marks it
+  row_bits_clear<NF>(row_bits, V);
+  const int k = threadIdx.x;
+  bool first = false;
+  const int idx = k < K ? k_i[k] : -1;
+  const float P = (1.f - tau) * tk_mass(k_i, k_p, K, k, idx, first);
+  const bool on = first && P >= GJ_FLT_MIN;
+  __syncthreads();
+  if (on) row_bits_set(row_bits, idx);
+  __syncthreads();
+  // ---- the one sweep: the OFF-support normalisers at 1 and at T with their own maximum, exponent unfolded
+  float m0 = -INFINITY, s1 = 0.f, sT = 0.f;
+  row_sweep<T, NF, false>(s, (const T*)nullptr, V, [&](int c, const float* f, const float*) {
+    const unsigned b = row_bits_chunk(row_bits, c);
+    float g[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) g[e] = ((b >> e) & 1u) ? -INFINITY : f[e];
+    const float cm = chunk_max8(g);
+    if (cm == -INFINITY) return;  // a chunk of members only
+    online_raise<T2>(cm, invT, m0, s1, sT);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float df = g[e] - m0;
+      const float q = __builtin_amdgcn_exp2f(df * kT);
+      sT += q;
+      s1 += T2 ? q * q : __builtin_amdgcn_exp2f(df * k1);
+    }
+  });
+  block_merge<NF>(m0, s1, sT, invT, sc);
+  const float ls0 = __builtin_amdgcn_logf(sT);  // v_log_f32: log2
+  // ---- epilogue: the on-support logits join the normalisers, then the K + 1 terms
+  const float sj = on ? (float)s[idx] : -INFINITY;
+  const float m = block_max<NF>(fmaxf(m0, sj), sc);
+  const float eT = on ? __builtin_amdgcn_exp2f((sj - m) * kT) : 0.f;
+  const float e1 = on ? (T2 ? eT * eT : __builtin_amdgcn_exp2f((sj - m) * k1)) : 0.f;
+  const float d0 = m0 - m;
+  sT = __builtin_fmaf(sT, __builtin_amdgcn_exp2f(d0 * kT), block_sum<NF>(eT, sc));
+  s1 = __builtin_fmaf(s1, __builtin_amdgcn_exp2f(d0 * k1), block_sum<NF>(e1, sc));
+  const float ls1 = __builtin_amdgcn_logf(s1), lsT = __builtin_amdgcn_logf(sT);
+  const float lq0 = __builtin_fmaf(d0, kT, ls0) - lsT;
+  float tp = 0.f, tq = 0.f;
+  if (on) {
+    float q, a2, lm;
+    tk_term(sj, P, m, kT, -lsT, beta, q, a2, lm);
+    const float lP = __builtin_amdgcn_logf(P);
+    if (mode == SD_DIV_FORWARD_KL) {
+      tp = P * (lP - a2);
+    } else {
+      const float ref = mode == SD_DIV_JSD ? lm : lP;
+      tq = q > 0.f ? q * (a2 - ref) : 0.f;
+      if (mode == SD_DIV_JSD) tp = P * (lP - lm);
+    }
+  }
+  float Sp = block_sum<NF>(tp, sc), Sq = block_sum<NF>(tq, sc);
+  hv = block_sum<NF>(hv, sc);
+  hc = block_sum<NF>(hc, sc);
+  // bucket 0, and c in log2 units without the 1 - beta of the JSD's g (gjsd_fwd_kernel's convention)
+  const float lt = __builtin_amdgcn_logf(tau), q0 = __builtin_amdgcn_exp2f(lq0);
+  float D;
+  if (mode == SD_DIV_FORWARD_KL) {
+    Sp = __builtin_fmaf(tau, lt - lq0, Sp);
+    D = Sp * GJ_LN2;
+  } else if (mode == SD_DIV_REVERSE_KL) {
+    Sq = __builtin_fmaf(q0, lq0 - lt, Sq);
+    D = Sq * GJ_LN2;
+  } else {
+    const float lm0 = tail_lm0(lq0, lt, beta);
+    Sp = __builtin_fmaf(tau, lt - lm0, Sp);
+    Sq = __builtin_fmaf(q0, lq0 - lm0, Sq);
+    D = (beta * Sp + (1.f - beta) * Sq) * GJ_LN2;
+  }
+  if (threadIdx.x == 0)
+    stats[row] = GjsdTailStats{m, ls1, lsT, Sq, 1.f, (m - (float)s[y]) + ls1 * GJ_LN2, D, hv, hc, mv, sv, lq0};
+}
+
+// One read of the student row, one write of the gradient; G may alias S (gjsd_topk_bwd_kernel's two barriers).
+template <typename T, bool T2, int MODE>
+__global__ __launch_bounds__(GJ_NF) void gjsd_tail_bwd_kernel(const T* S, const _Float16* __restrict__ topv,
+                                                              const int32_t* __restrict__ topi,
+                                                              const float* __restrict__ tail,
+                                                              const int64_t* __restrict__ labels,
+                                                              const GjsdTailStats* __restrict__ stats,
+                                                              const float* __restrict__ loss_out,
+                                                              const float* __restrict__ grad_out, T* G, int V, int K,
+                                                              float temperature, float alpha, float beta) {
+  constexpr int E = KMAX / GJ_NF;  // entries per thread
+  constexpr bool FKL = MODE == SD_DIV_FORWARD_KL, JSD = MODE == SD_DIV_JSD;
+  __shared__ float sc[32];
+  __shared__ __attribute__((aligned(16))) float k_p[KMAX];
+  __shared__ __attribute__((aligned(16))) int k_i[KMAX];
+  const int row = blockIdx.x;
+  const GjsdTailStats st = stats[row];
+  T* gr = G + (long)row * V;
+  if (st.valid == 0.f) return zero_row<T, GJ_NF>(gr, V);
+  const float invT = 1.f / temperature;
+  const float k1 = GJ_LOG2E, kT = invT * k1;
+  const float N = loss_out[4];
+  const float go = grad_out ? grad_out[0] : 1.f;
+  const float a1 = go * alpha / N;  // * (softmax(s) - e_y)
+  // * q (d - c), d - c in log2 units (the forward KL: * (q - P))
+  const float aT = go * (1.f - alpha) * temperature / N * (FKL ? 1.f : (JSD ? (1.f - beta) * GJ_LN2 : GJ_LN2));
+  const long y = labels[row];
+  const T* s = S + (long)row * V;
+  const float A0 = -st.lsT, L1 = -st.ls1;
+  const float r1 = T2 ? __builtin_amdgcn_exp2f(2.f * st.lsT - st.ls1) : 0.f;  // softmax(s) = q^2 r1 at T == 2
+  auto soft1 = [&](float f, float q) { return T2 ? q * q * r1 : __builtin_amdgcn_exp2f(__builtin_fmaf(f - st.m, k1, L1)); };
+  const float tau = fmaxf(tail[row], GJ_TAIL_MIN);  // (a valid row's tau passed tail_ok in the forward)
+  const float lt = __builtin_amdgcn_logf(tau);
+  float hv, hc, mv = st.mv, sv = st.sv;  // the forward's renormalisation (a valid row keeps an entry)
+  tk_renorm<GJ_NF, E, true>(topv, topi, (long)row * K, K, V, kT, y, sc, k_i, k_p, hv, hc, mv, sv);
+  int fi[E];
+  float fo[E];
+#pragma unroll
+  for (int u = 0; u < E; ++u) {
+    const int k = threadIdx.x + u * GJ_NF;
+    bool first = false;
+    const int idx = k < K ? k_i[k] : -1;
+    const float P = (1.f - tau) * tk_mass(k_i, k_p, K, k, idx, first);
+    fi[u] = -1;
+    fo[u] = 0.f;
+    if (first && P >= GJ_FLT_MIN) {
+      const float sj = (float)s[idx];
+      float q, a2, lm;
+      tk_term(sj, P, st.m, kT, A0, beta, q, a2, lm);
+      float w;
+      if constexpr (FKL) {
+        w = q - P;
+      } else {
+        const float ref = JSD ? lm : __builtin_amdgcn_logf(P);
+        w = q > 0.f ? q * ((a2 - ref) - st.c) : 0.f;
+      }
+      fi[u] = idx;
+      fo[u] = __builtin_fmaf(a1, soft1(sj, q), aT * w) - ((long)idx == y ? a1 : 0.f);
+    }
+  }
+  // Every gather of s above has returned in EVERY wave before any wave stores (gjsd_topk_bwd_kernel's barrier, same place)
+  __syncthreads();
+  // off S: the forward KL subtracts tau q_j / q_0 = exp2(log2 q_j + dl); the others scale q_j by the row's d_0 - c
+  const float dl = lt - st.lq0;
+  const float w0 = FKL ? 0.f : aT * ((st.lq0 - (JSD ? tail_lm0(st.lq0, lt, beta) : lt)) - st.c);
+  row_sweep<T, GJ_NF, false>(s, (const T*)nullptr, V, [&](int c, const float* f, const float*) {
+    float o[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float a2 = __builtin_fmaf(f[e] - st.m, kT, A0);
+      const float q = __builtin_amdgcn_exp2f(a2);
+      if constexpr (FKL)
+        o[e] = __builtin_fmaf(a1, soft1(f[e], q), aT * (q - __builtin_amdgcn_exp2f(a2 + dl)));
+      else
+        o[e] = __builtin_fmaf(a1, soft1(f[e], q), w0 * q);
+    }
+    if (y >= c && y < c + 8) o[y - c] -= a1;
+    Ld8<T>::store(gr + c, o);
+  });
+  __syncthreads();  // every dense store of this row is complete (vmcnt(0) + barrier) before the fix-up
+#pragma unroll
+  for (int u = 0; u < E; ++u)
+    if (fi[u] >= 0) gr[fi[u]] = (T)fo[u];
+}
+
+constexpr int GJ_TAIL_VMAX = 458752;  // the forward's V-bit bitmap beside its other LDS: 56 KB of the 64 KB
+
+int gjsd_tail_check(const void* S, const void* topv, const void* topi, const float* tail, const int64_t* labels,
+                    const void* stats, const float* out, int R, int V, int K, float temperature, float beta, int mode,
+                    int dtype) {
+  if (R <= 0 || V <= 0 || !S || !labels || !stats || !out) return SD_ERR_SHAPE;
+  if (!topv || !topi || !tail) return SD_ERR_NO_TEACHER;
+  if (K <= 0 || K > KMAX || K >= V) return SD_ERR_SHAPE;  // K < V: an off-support element always exists
+  if (V & 7) return SD_ERR_ALIGN;
+  if ((uintptr_t)S & 15) return SD_ERR_ALIGN;
+  if (dtype != SD_DTYPE_BF16 && dtype != SD_DTYPE_F32) return SD_ERR_UNSUPPORTED;
+  if (mode != SD_DIV_FORWARD_KL && mode != SD_DIV_REVERSE_KL && mode != SD_DIV_JSD) return SD_ERR_UNSUPPORTED;
+  if (V > GJ_TAIL_VMAX) return SD_ERR_UNSUPPORTED;
+  if (!(temperature > 0.f) || !(temperature < INFINITY)) return SD_ERR_SHAPE;   // NaN fails both comparisons
+  if (mode == SD_DIV_JSD && !(beta > 0.f && beta < 1.f)) return SD_ERR_SHAPE;    // likewise
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int64_t sd_gjsd_tail_stats_bytes(int R) { return (int64_t)R * sizeof(GjsdTailStats); }
+
+extern "C" int sd_gjsd_tail_fwd_rows(const void* student_logits, const void* top_k_v, const void* top_k_i,
+                                     const float* top_k_tail, const int64_t* row_labels, void* row_stats, float* loss_out,
+                                     int R, int V, int K, float temperature, float alpha, float beta, int mode, int dtype,
+                                     void* stream) {
+  if (int e = gjsd_tail_check(student_logits, top_k_v, top_k_i, top_k_tail, row_labels, row_stats, loss_out, R, V, K,
+                              temperature, beta, mode, dtype))
+    return e;
+  hipStream_t st = (hipStream_t)stream;
+  if (int e = by_dtype(dtype, [&](auto tt) -> int {
+        typedef SD_TAG_TYPE(tt) T;
+        SdProfScope prof(SD_K_LOSS_FWD, (double)R * V * sizeof(T), st);
+        // 1024 threads only where the K teacher entries do not fit one thread each at 512 (kd_fwd_kernel's rule)
+        by_flag(temperature == 2.0f, [&](auto t2) {
+          by_flag(K > 512, [&](auto wide) {
+            constexpr int NF = SD_FLAG(wide) ? 1024 : 512;
+            SD_PROF_LABEL("gjsd_tail_fwd_kernel<%s, %s, %d>", type_name(sizeof(T)), flag_name(SD_FLAG(t2)), NF);
+            hipLaunchKernelGGL((gjsd_tail_fwd_kernel<T, SD_FLAG(t2), NF>), dim3(R), dim3(NF), row_bits_bytes(V), st,
+                               (const T*)student_logits, (const _Float16*)top_k_v, (const int32_t*)top_k_i, top_k_tail,
+                               row_labels, (GjsdTailStats*)row_stats, V, K, temperature, beta, mode);
+          });
+        });
+        SD_CHECK_LAUNCH();
+        return 0;
+      }))
+    return e;
+  hipLaunchKernelGGL((kd_finalize_kernel<GjsdTailStats, true>), dim3(1), dim3(NT), 0, st, (const GjsdTailStats*)row_stats,
+                     loss_out, R, temperature, alpha, 0);
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int sd_gjsd_tail_bwd_rows(const void* student_logits, const void* top_k_v, const void* top_k_i,
+                                     const float* top_k_tail, const int64_t* row_labels, const void* row_stats,
+                                     const float* loss_out, const float* grad_total, void* grad_logits, int R, int V, int K,
+                                     float temperature, float alpha, float beta, int mode, int dtype, void* stream) {
+  if (int e = gjsd_tail_check(student_logits, top_k_v, top_k_i, top_k_tail, row_labels, row_stats, loss_out, R, V, K,
+                              temperature, beta, mode, dtype))
+    return e;
+  if (!grad_logits) return SD_ERR_SHAPE;
+  if ((uintptr_t)grad_logits & 15) return SD_ERR_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  return by_dtype(dtype, [&](auto tt) -> int {
+    typedef SD_TAG_TYPE(tt) T;
+    SdProfScope prof(SD_K_LOSS_BWD, (double)R * V * sizeof(T) * 2, st);
+    by_flag(temperature == 2.0f, [&](auto t2) {
+      auto go = [&](auto md) {
+        constexpr int MODE = decltype(md)::value;
+        SD_PROF_LABEL("gjsd_tail_bwd_kernel<%s, %s, %d>", type_name(sizeof(T)), flag_name(SD_FLAG(t2)), MODE);
+        hipLaunchKernelGGL((gjsd_tail_bwd_kernel<T, SD_FLAG(t2), MODE>), dim3(R), dim3(GJ_NF), 0, st,
+                           (const T*)student_logits, (const _Float16*)top_k_v, (const int32_t*)top_k_i, top_k_tail,
+                           row_labels, (const GjsdTailStats*)row_stats, loss_out, grad_total, (T*)grad_logits, V, K,
+                           temperature, alpha, beta);
+      };
+      if (mode == SD_DIV_FORWARD_KL) go(std::integral_constant<int, SD_DIV_FORWARD_KL>{});
+      else if (mode == SD_DIV_REVERSE_KL) go(std::integral_constant<int, SD_DIV_REVERSE_KL>{});
+      else go(std::integral_constant<int, SD_DIV_JSD>{});
+    });
+    SD_CHECK_LAUNCH();
+    return 0;
+  });
+}

@@ -108,6 +108,19 @@ SD_DEV void block_merge(float& m, float& s1, float& sT, float invT, float* sc, A
   m = M;
 }
 
+// A row's membership bitmap in LDS (the top-K tail kernels): bit j of `bits` says that vocabulary index j is one of the
+// row's top-K indices.  V bits, rounded up to whole 16-byte stores: row_bits_bytes(V) of (dynamic) LDS, 19 936 bytes at
+// V = 159 488.  Cleared per row by the whole block, set with LDS atomicOr (indices share words), read one BYTE per
+// 8-element chunk: V % 8 == 0 and chunks start at multiples of 8, so bit e of that byte is element c + e.
+inline __host__ __device__ int row_bits_bytes(int V) { return ((V + 127) >> 7) << 4; }
+template <int NF>
+SD_DEV void row_bits_clear(uint32_t* bits, int V) {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  for (int i = threadIdx.x; i < row_bits_bytes(V) >> 4; i += NF) ((u32x4*)bits)[i] = u32x4{0u, 0u, 0u, 0u};
+}
+SD_DEV void row_bits_set(uint32_t* bits, int j) { atomicOr(&bits[j >> 5], 1u << (j & 31)); }
+SD_DEV unsigned row_bits_chunk(const uint32_t* bits, int c) { return ((const uint8_t*)bits)[c >> 3]; }
+
 // the gradient of a masked row: V zeros, NF threads
 template <typename T, int NF>
 SD_DEV void zero_row(T* g, int V) {

@@ -296,6 +296,64 @@ __global__ __launch_bounds__(NT) void topk_kernel(const T* __restrict__ X, _Floa
   }
 }
 
+// The teacher's mass OUTSIDE its top-K at temperature T: tail[r] = sum_{j not in {i_k}} exp(x_j / T) / sum_j exp(x_j / T).
+// One sweep of the row with two online (max, sum-exp) pairs, the members' and the non-members', each with its own
+// maximum: the non-members are summed DIRECTLY (1 - sum over the K entries loses a tail below ~1e-6 to cancellation, and
+// that is where a reverse KL multiplies by log tail).  Membership is by INDEX (ties cross the K-th value): a V-bit bitmap
+// in LDS (sd_rows.cuh), one byte read per chunk.  An index outside [0, V) sets nothing; a duplicate sets its bit once.
+template <typename T, int NT>
+__global__ __launch_bounds__(NT) void topk_tail_kernel(const T* __restrict__ X, const int32_t* __restrict__ topi,
+                                                       float* __restrict__ tail, long row_stride, int V, int K,
+                                                       float invT) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t row_bits[];  // max(row_bits_bytes(V), 128) bytes
+  const int row = blockIdx.x;
+  const T* x = X + (long)row * row_stride;
+  row_bits_clear<NT>(row_bits, V);
+  __syncthreads();
+  for (int k = threadIdx.x; k < K; k += NT) {
+    const int idx = topi[(long)row * K + k];
+    if (idx >= 0 && idx < V) row_bits_set(row_bits, idx);
+  }
+  __syncthreads();
+  const float kT = invT * 1.4426950408889634f;
+  float mo = -INFINITY, so = 0.f, mi = -INFINITY, si = 0.f, unused = 0.f;  // (online_raise's sum at T = 1 is not kept here)
+  row_sweep<T, NT, false>(x, (const T*)nullptr, V, [&](int c, const float* f, const float*) {
+    const unsigned b = row_bits_chunk(row_bits, c);
+    float g[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) g[e] = ((b >> e) & 1u) ? -INFINITY : f[e];
+    float cm = chunk_max8(g);
+    if (cm > -INFINITY) {  // (a chunk of members only has nothing to add, and -inf - -inf is to be avoided)
+      online_raise<true>(cm, invT, mo, unused, so);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) so += __builtin_amdgcn_exp2f((g[e] - mo) * kT);
+    }
+    if (b) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) g[e] = ((b >> e) & 1u) ? f[e] : -INFINITY;
+      cm = chunk_max8(g);
+      if (cm > -INFINITY) {
+        online_raise<true>(cm, invT, mi, unused, si);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) si += __builtin_amdgcn_exp2f((g[e] - mi) * kT);
+      }
+    }
+  });
+  // the reductions' scratch takes the bitmap's place once every wave has left the sweep: at V = 524 288 the bitmap is
+  // the whole 64 KB
+  __syncthreads();
+  float* sc = (float*)row_bits;
+  const float Mo = block_max<NT>(mo, sc), Mi = block_max<NT>(mi, sc);
+  so = block_sum<NT>(mo == -INFINITY ? 0.f : so * __builtin_amdgcn_exp2f((mo - Mo) * kT), sc);
+  si = block_sum<NT>(mi == -INFINITY ? 0.f : si * __builtin_amdgcn_exp2f((mi - Mi) * kT), sc);
+  if (threadIdx.x == 0) {
+    const float M = fmaxf(Mo, Mi);
+    const float out = Mo == -INFINITY ? 0.f : so * __builtin_amdgcn_exp2f((Mo - M) * kT);
+    const float in = Mi == -INFINITY ? 0.f : si * __builtin_amdgcn_exp2f((Mi - M) * kT);
+    tail[row] = out / (out + in);
+  }
+}
+
 }  // namespace
 
 extern "C" int sd_logsoftmax_topk(const void* logits, void* top_v, void* top_i, float* lse_out, int rows,
@@ -320,6 +378,32 @@ extern "C" int sd_logsoftmax_topk(const void* logits, void* top_v, void* top_i, 
     return SD_ERR_UNSUPPORTED;
   }
 #undef SD_TOPK_GO
+  SD_CHECK_LAUNCH();
+  return 0;
+}
+
+constexpr int TAIL_VMAX = 524288;  // a V-bit bitmap of 64 KB of LDS
+
+extern "C" int sd_topk_tail(const void* logits, const void* top_i, float* tail_out, int rows, int64_t row_stride, int V,
+                            int K, float temperature, int dtype, void* stream) {
+  if (rows <= 0 || V <= 0 || K <= 0 || K > KMAX || K > V || row_stride < V || !logits || !top_i || !tail_out)
+    return SD_ERR_SHAPE;
+  if (!(temperature > 0.f) || !(temperature < INFINITY)) return SD_ERR_SHAPE;  // NaN fails both comparisons
+  if ((V & 7) || (row_stride & 7) || ((uintptr_t)logits & 15)) return SD_ERR_ALIGN;
+  if (V > TAIL_VMAX || (dtype != SD_DTYPE_BF16 && dtype != SD_DTYPE_F32)) return SD_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  SdProfScope prof(SD_K_TOPK, (double)rows * V * (dtype == SD_DTYPE_BF16 ? 2 : 4), st);
+  constexpr int NT = 512;
+  const int lds = row_bits_bytes(V) > 128 ? row_bits_bytes(V) : 128;
+  if (dtype == SD_DTYPE_BF16) {
+    SD_PROF_LABEL("topk_tail_kernel<%s, %d>", "__bf16", NT);
+    hipLaunchKernelGGL((topk_tail_kernel<bf16, NT>), dim3(rows), dim3(NT), lds, st, (const bf16*)logits,
+                       (const int32_t*)top_i, tail_out, (long)row_stride, V, K, 1.f / temperature);
+  } else {
+    SD_PROF_LABEL("topk_tail_kernel<%s, %d>", "float", NT);
+    hipLaunchKernelGGL((topk_tail_kernel<float, NT>), dim3(rows), dim3(NT), lds, st, (const float*)logits,
+                       (const int32_t*)top_i, tail_out, (long)row_stride, V, K, 1.f / temperature);
+  }
   SD_CHECK_LAUNCH();
   return 0;
 }

@@ -19,12 +19,17 @@ distribution P over the vocabulary (duplicated indices sum), and the divergence 
 when the student puts all its mass on the K indices, which is what a renormalised top-K teacher asks for.  It takes
 ``teacher_top_k_v`` / ``teacher_top_k_i`` only (dense ``teacher_logits`` are "jsd"'s).  There is no "reverse_kl" on a
 top-K teacher: KL(q || P) is infinite as soon as P is 0 where the student has any mass.  DESIGN.md section 12b.
+"forward_kl_tail", "reverse_kl_tail" and "jsd_tail" keep one more number per row, ``teacher_top_k_tail``: the teacher's
+mass outside its top-K at T (``ops.topk_tail``).  Teacher and student are compared over K + 1 outcomes -- the K indices
+and "anything else" -- so all three are finite, exact on the top-K part and a lower bound of the dense divergence.  They
+take a top-K teacher only; without the tail, T = 1 derives it from the stored log-probs (``ops.tail_from_logprobs``) and
+any other temperature is an error.  DESIGN.md section 12c.
 """
 import torch
 import torch.nn as nn
 
 from . import ops
-from .ops import GJSDLossRowsFn, GJSDTopKLossRowsFn, KDLossFn, KDLossRowsFn
+from .ops import GJSDLossRowsFn, GJSDTailLossRowsFn, GJSDTopKLossRowsFn, KDLossFn, KDLossRowsFn
 
 
 class DistillationLoss(nn.Module):
@@ -40,17 +45,20 @@ class DistillationLoss(nn.Module):
         self.inplace_grad = inplace_grad
 
     def forward(self, student_logits, labels, teacher_logits=None, teacher_top_k_v=None, teacher_top_k_i=None,
-                speech_token_mask=None):
+                speech_token_mask=None, teacher_top_k_tail=None):
         if teacher_logits is None and (teacher_top_k_v is None or teacher_top_k_i is None):
             raise ValueError("Either teacher_logits or top_k must be provided")
-        if self.divergence == ops.TOPK_DIVERGENCE:
+        if self.divergence == ops.TOPK_DIVERGENCE or self.divergence in ops.TAIL_DIVERGENCES:
             # as below, with the top-K rows selected the way the trainer selects them for the forward KL
             self._need_topk(teacher_logits, teacher_top_k_v, teacher_top_k_i)
             rows, row_labels = ops.loss_rows(labels, speech_token_mask)
             V = student_logits.shape[-1]
             pick = (lambda x: x.to(rows.device).reshape(-1, x.size(-1))[rows])
+            tail = {}
+            if self.divergence in ops.TAIL_DIVERGENCES:
+                tail = {"teacher_top_k_tail": self._tail(teacher_top_k_v, teacher_top_k_tail).to(rows.device).reshape(-1)[rows]}
             return self.forward_rows(student_logits.reshape(-1, V)[rows], row_labels,
-                                     teacher_top_k_v=pick(teacher_top_k_v), teacher_top_k_i=pick(teacher_top_k_i))
+                                     teacher_top_k_v=pick(teacher_top_k_v), teacher_top_k_i=pick(teacher_top_k_i), **tail)
         if self.divergence != "forward_kl":
             # eval / return_outputs path: select the rows as the trainer does and gather them (one copy of R rows)
             self._need_dense(teacher_logits)
@@ -67,9 +75,11 @@ class DistillationLoss(nn.Module):
                                     self.inplace_grad and student_logits.requires_grad)
         return total, out[1], out[2], out[3]
 
-    def forward_rows(self, student_logits, row_labels, teacher_logits=None, teacher_top_k_v=None, teacher_top_k_i=None):
+    def forward_rows(self, student_logits, row_labels, teacher_logits=None, teacher_top_k_v=None, teacher_top_k_i=None,
+                     teacher_top_k_tail=None):
         """Same 4-tuple for rows already shifted and selected by ``ops.loss_rows`` (what distillation_loss.py:31-45
-        does with copies): ``student_logits`` [R,V], ``row_labels`` [R], teacher form [R,V] or ([R,K], [R,K])."""
+        does with copies): ``student_logits`` [R,V], ``row_labels`` [R], teacher form [R,V] or ([R,K], [R,K]), for the
+        ``_tail`` divergences with ``teacher_top_k_tail`` [R]."""
         if teacher_logits is None and (teacher_top_k_v is None or teacher_top_k_i is None):
             raise ValueError("Either teacher_logits or top_k must be provided")
         if teacher_logits is not None:
@@ -78,6 +88,13 @@ class DistillationLoss(nn.Module):
             self._need_topk(teacher_logits, teacher_top_k_v, teacher_top_k_i)
             total, out = GJSDTopKLossRowsFn.apply(student_logits.contiguous(), row_labels, teacher_top_k_v, teacher_top_k_i,
                                                   self.temperature, self.alpha, self.beta,
+                                                  self.inplace_grad and student_logits.requires_grad)
+            return total, out[1], out[2], out[3]
+        if self.divergence in ops.TAIL_DIVERGENCES:
+            self._need_topk(teacher_logits, teacher_top_k_v, teacher_top_k_i)
+            total, out = GJSDTailLossRowsFn.apply(student_logits.contiguous(), row_labels, teacher_top_k_v, teacher_top_k_i,
+                                                  self._tail(teacher_top_k_v, teacher_top_k_tail), self.temperature,
+                                                  self.alpha, self.beta, self.divergence,
                                                   self.inplace_grad and student_logits.requires_grad)
             return total, out[1], out[2], out[3]
         if self.divergence != "forward_kl":
@@ -98,5 +115,17 @@ class DistillationLoss(nn.Module):
 
     def _need_topk(self, teacher_logits, teacher_top_k_v, teacher_top_k_i):
         if teacher_logits is not None or teacher_top_k_v is None or teacher_top_k_i is None:
+            dense = self.divergence[:-len("_tail")] if self.divergence in ops.TAIL_DIVERGENCES else "jsd"
             raise ValueError(f"divergence={self.divergence!r} takes a top-K teacher (teacher_top_k_v, teacher_top_k_i); "
-                             "for dense teacher_logits use divergence='jsd'")
+                             f"for dense teacher_logits use divergence={dense!r}")
+
+    def _tail(self, teacher_top_k_v, teacher_top_k_tail):
+        """The tail of a ``_tail`` divergence: the caller's, or at T = 1 the one the stored log-probs imply."""
+        if teacher_top_k_tail is not None:
+            return teacher_top_k_tail
+        if float(self.temperature) != 1.0:
+            raise ValueError(f"divergence={self.divergence!r} at temperature {self.temperature} needs teacher_top_k_tail (the "
+                             "teacher's mass outside its top-K at that temperature: ops.topk_tail, or "
+                             "extract_teacher_logits.py --tail_temperature); only at temperature 1 do the stored "
+                             "log-probs imply it")
+        return ops.tail_from_logprobs(teacher_top_k_v)

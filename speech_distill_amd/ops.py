@@ -318,6 +318,36 @@ def logsoftmax_topk(logits, k, vocab_size=None):
     return tv, ti
 
 
+def topk_tail(logits, top_i, temperature, vocab_size=None):
+    """The teacher's mass outside its top-K at ``temperature`` (sd_topk_tail): logits [..., Vt] (the first ``vocab_size``
+    columns count), top_i int32 [..., K] as ``logsoftmax_topk`` returned them for the same logits -> fp32 [...].  Summed
+    directly over the non-members, so a tail of 1e-12 keeps its digits."""
+    _need(logits, None, "logits")
+    lead = logits.shape[:-1]
+    Vt = logits.shape[-1]
+    V = Vt if vocab_size is None else min(int(vocab_size), Vt)
+    if (Vt % 8) or (logits.data_ptr() % 16):   # as logsoftmax_topk: rows must start 16-byte aligned
+        logits = logits[..., :V].contiguous()
+        Vt = V
+    K = int(top_i.shape[-1])
+    if tuple(top_i.shape[:-1]) != tuple(lead):
+        raise ValueError(f"top_i {tuple(top_i.shape)} for logits {tuple(logits.shape)}: expected {tuple(lead) + (K,)}")
+    top_i = _need(top_i.to(device=logits.device, dtype=torch.int32), torch.int32, "top_i")
+    rows = logits.numel() // Vt
+    tail = torch.empty(*lead, dtype=torch.float32, device=logits.device)
+    if rows:
+        check(load_lib().sd_topk_tail(logits.data_ptr(), top_i.data_ptr(), tail.data_ptr(), rows, Vt, V, K,
+                                      float(temperature), _dt(logits), _stream()), "sd_topk_tail")
+    return tail
+
+
+def tail_from_logprobs(top_v):
+    """The T = 1 fallback for a top-K teacher stored without its tail: clamp(1 - sum_k exp(v_k), 0, 1) in fp32, [..., K] ->
+    [...].  The stored log-probs are fp16, so this is good to about 2e-4 absolute (0.21732 against a true 0.21715); at any
+    other temperature the tail cannot be had from the K values and has to come from ``topk_tail`` / the extraction."""
+    return (1.0 - top_v.to(torch.float32).exp().sum(-1)).clamp_(0.0, 1.0)
+
+
 class KDLossFn(torch.autograd.Function):
     """DistillationLoss.forward + its backward on the HIP kernels (distillation_loss.py:14-128)."""
 
@@ -460,12 +490,17 @@ DIVERGENCES = {"reverse_kl": 1, "jsd": 2}  # include/sd_hip.h SD_DIV_*; "forward
 TOPK_DIVERGENCE = "jsd_topk"               # the jsd against a top-K teacher: GJSDTopKLossRowsFn (sd_gjsd_topk_*_rows)
 
 
+TAIL_DIVERGENCES = {"forward_kl_tail": 0, "reverse_kl_tail": 1, "jsd_tail": 2}  # a top-K teacher with a tail bucket:
+#                                                       GJSDTailLossRowsFn (sd_gjsd_tail_*_rows), SD_DIV_* of the same kind
+ALL_DIVERGENCES = ("forward_kl", *DIVERGENCES, TOPK_DIVERGENCE, *TAIL_DIVERGENCES)
+
+
 def check_divergence(divergence, beta):
-    """ValueError for a divergence the loss does not know, or a ``jsd`` whose beta is outside (0, 1) (NaN included):
-    the jsd formula tends to 0 at both ends, TRL's beta = 0 / 1 are ``forward_kl`` / ``reverse_kl``."""
-    if divergence != "forward_kl" and divergence not in DIVERGENCES and divergence != TOPK_DIVERGENCE:
-        raise ValueError(f"unknown divergence {divergence!r}: one of 'forward_kl', 'reverse_kl', 'jsd', 'jsd_topk'")
-    if divergence in ("jsd", TOPK_DIVERGENCE) and not 0.0 < float(beta) < 1.0:
+    """ValueError for a divergence the loss does not know, or a ``jsd`` / ``jsd_topk`` / ``jsd_tail`` whose beta is outside
+    (0, 1) (NaN included): the jsd formula tends to 0 at both ends, TRL's beta = 0 / 1 are ``forward_kl`` / ``reverse_kl``."""
+    if divergence not in ALL_DIVERGENCES:
+        raise ValueError(f"unknown divergence {divergence!r}: one of " + ", ".join(repr(d) for d in ALL_DIVERGENCES))
+    if divergence in ("jsd", TOPK_DIVERGENCE, "jsd_tail") and not 0.0 < float(beta) < 1.0:
         raise ValueError(f"divergence={divergence!r} needs 0 < beta < 1, got {beta!r} (beta = 0 is 'forward_kl', beta = 1 is "
                          "'reverse_kl')")
 
@@ -572,6 +607,68 @@ class GJSDTopKLossRowsFn(torch.autograd.Function):
                                                stats.data_ptr(), out.data_ptr(), go.data_ptr(), grad.data_ptr(), R, V, K,
                                                temperature, alpha, beta, dt, _stream()), "sd_gjsd_topk_bwd_rows")
         return grad, None, None, None, None, None, None, None
+
+
+class GJSDTailLossRowsFn(torch.autograd.Function):
+    """Forward KL, reverse KL or the beta-skewed Jensen-Shannon loss against a top-K teacher WITH A TAIL BUCKET
+    (sd_gjsd_tail_*_rows; ``divergence`` one of ``TAIL_DIVERGENCES``) on rows the caller has already shifted and selected:
+    student_logits [R,V], row_labels [R], (top_v fp16, top_i int32) [R,K], top_tail fp32 [R] the teacher's mass outside
+    its top-K at ``temperature`` (``topk_tail``).  Teacher and student are compared over K + 1 outcomes, the K indices
+    and "anything else", so every divergence is finite.  A row whose tail is NaN, negative or >= 1 is a masked row, as
+    is a row without a usable entry.  Needs K < V.
+    Returns (total, out fp32[8] = total, task, distill, teacher, N, n_hits, 0, 0).  R == 0 launches nothing and returns
+    zeros that are connected to autograd."""
+
+    @staticmethod
+    def forward(ctx, student_logits, row_labels, top_v, top_i, top_tail, temperature, alpha, beta, divergence, inplace_grad):
+        if divergence not in TAIL_DIVERGENCES:
+            raise ValueError(f"GJSDTailLossRowsFn: divergence {divergence!r} is not one of {sorted(TAIL_DIVERGENCES)}")
+        check_divergence(divergence, beta)
+        if top_v is None or top_i is None or top_tail is None:
+            raise ValueError(f"divergence={divergence!r} needs a top-K teacher with its tail (teacher_top_k_v, "
+                             "teacher_top_k_i, teacher_top_k_tail)")
+        s = _need(student_logits, None, "student_logits")
+        R, V = s.shape
+        dt = _dt(s)
+        lib = load_lib()
+        row_labels = _need(row_labels.to(torch.int64), torch.int64, "row_labels")
+        K = int(top_v.shape[-1])
+        if tuple(top_v.shape) != (R, K) or tuple(top_i.shape) != (R, K) or tuple(top_tail.shape) != (R,):
+            raise ValueError(f"top-K teacher {tuple(top_v.shape)} / {tuple(top_i.shape)} / tail {tuple(top_tail.shape)} for "
+                             f"{R} rows: expected [R, K] twice and [R]")
+        top_v = top_v.to(device=s.device, dtype=torch.float16).contiguous()
+        top_i = top_i.to(device=s.device, dtype=torch.int32).contiguous()
+        top_tail = top_tail.to(device=s.device, dtype=torch.float32).contiguous()
+        ctx.cfg = (R, V, K, float(temperature), float(alpha), float(beta), TAIL_DIVERGENCES[divergence], dt, bool(inplace_grad))
+        if R == 0:   # the C entry refuses R <= 0; the loss of no row is 0 and so is its (empty) gradient
+            out = torch.zeros(8, dtype=torch.float32, device=s.device)
+            ctx.save_for_backward(s, row_labels, top_v, top_i, top_tail, out, out)
+            ctx.mark_non_differentiable(out)
+            return out[0].clone(), out
+        stats = torch.empty(lib.sd_gjsd_tail_stats_bytes(R), dtype=torch.uint8, device=s.device)
+        out = torch.empty(8, dtype=torch.float32, device=s.device)
+        check(lib.sd_gjsd_tail_fwd_rows(s.data_ptr(), top_v.data_ptr(), top_i.data_ptr(), top_tail.data_ptr(),
+                                        row_labels.data_ptr(), stats.data_ptr(), out.data_ptr(), R, V, K, float(temperature),
+                                        float(alpha), float(beta), TAIL_DIVERGENCES[divergence], dt, _stream()),
+              "sd_gjsd_tail_fwd_rows")
+        ctx.save_for_backward(s, row_labels, top_v, top_i, top_tail, stats, out)
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, g_total, _g_out):
+        s, row_labels, top_v, top_i, top_tail, stats, out = ctx.saved_tensors
+        R, V, K, temperature, alpha, beta, mode, dt, inplace = ctx.cfg
+        grad = s if inplace else torch.empty_like(s)
+        none = (None,) * 9
+        if R == 0:
+            return (grad,) + none
+        go = g_total.to(torch.float32).reshape(1).contiguous()
+        check(load_lib().sd_gjsd_tail_bwd_rows(s.data_ptr(), top_v.data_ptr(), top_i.data_ptr(), top_tail.data_ptr(),
+                                               row_labels.data_ptr(), stats.data_ptr(), out.data_ptr(), go.data_ptr(),
+                                               grad.data_ptr(), R, V, K, temperature, alpha, beta, mode, dt, _stream()),
+              "sd_gjsd_tail_bwd_rows")
+        return (grad,) + none
 
 
 class CELossRowsFn(torch.autograd.Function):

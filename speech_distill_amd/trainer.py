@@ -102,6 +102,11 @@ class DistillationTrainer(FlatStudentTrainer):
     pre-extracted ``teacher_top_k_v``.  ``"jsd_topk"`` is the "jsd" against a top-K teacher and runs wherever the forward KL
     does: a live teacher with ``top_k > 0`` (refused at construction otherwise, or with a quantised teacher), or batches
     that carry pre-extracted ``teacher_top_k_v`` / ``teacher_top_k_i``, with or without a teacher model.
+    ``"forward_kl_tail"``, ``"reverse_kl_tail"`` and ``"jsd_tail"`` (a top-K teacher with a tail bucket) run in the same
+    places: the live teacher's pass also returns its tail mass at the loss temperature (``ops.topk_tail`` on the logits it
+    already holds), which travels with the top-K through every lookahead; a batch with pre-extracted keys brings
+    ``teacher_top_k_tail`` (or, at temperature 1, the stored log-probs imply it).  They are finite on a top-K teacher, so
+    ``lmbda > 0`` runs with the default ``top_k``.
 
     ``lmbda`` in [0, 1]: the probability that a training micro-batch is made on-policy -- one draw per micro-batch from a
     CPU generator seeded from ``args.seed`` and the process index; below ``lmbda`` the student generates from the batch's
@@ -122,11 +127,11 @@ class DistillationTrainer(FlatStudentTrainer):
                  divergence="forward_kl", beta=0.5, lmbda=0.0, on_policy_generate=None, **kwargs):
         # everything that can be refused without a model is refused before HF's constructor touches one
         ops.check_divergence(divergence, beta)
-        if divergence == ops.TOPK_DIVERGENCE:
+        if divergence == ops.TOPK_DIVERGENCE or divergence in ops.TAIL_DIVERGENCES:
             if top_k <= 0 or is_quantized_teacher:
                 raise ValueError(f"divergence={divergence!r} needs a top-K teacher (top_k > 0, not a quantised teacher), got "
                                  f"top_k={top_k}, is_quantized_teacher={is_quantized_teacher}: the dense teacher "
-                                 "distribution goes with divergence='jsd'")
+                                 f"distribution goes with divergence={self._dense_name(divergence)!r}")
         elif divergence != "forward_kl" and not (top_k <= 0 or is_quantized_teacher):
             raise ValueError(f"divergence={divergence!r} needs the dense teacher distribution: pass top_k=0 (a top-K "
                              f"teacher defines it on K entries only), got top_k={top_k}")
@@ -156,6 +161,7 @@ class DistillationTrainer(FlatStudentTrainer):
             self._on_policy_rng = torch.Generator().manual_seed(int(self.args.seed) + int(self.args.process_index))
         # compute back-ends; the product ones are the HIP kernels (tests may inject a checker here)
         self._extract_topk = ops.logsoftmax_topk
+        self._extract_tail = ops.topk_tail
         # throughput of the loop: positions (B*T of every training micro-batch, padding included -- what the kernels
         # process and what bench.py counts) seen by THIS rank; `log` turns it into whole-job tokens/sec
         self.tokens_seen = 0
@@ -181,6 +187,11 @@ class DistillationTrainer(FlatStudentTrainer):
         # The optimizer HF would build by default (AdamW over ~310 HF-named tensors, HF trainer.py:1778-1796) is replaced
         # by the one-launch FlatAdamW over the flat buffers when the student offers them; set False to keep HF's.
         self.fused_optimizer = True
+
+    @staticmethod
+    def _dense_name(divergence):
+        """The divergence that takes the dense teacher distribution where ``divergence`` takes a top-K teacher."""
+        return divergence[:-len("_tail")] if divergence in ops.TAIL_DIVERGENCES else "jsd"
 
     def create_optimizer(self, model=None):
         """HF trainer.py `create_optimizer(self, model=None)`: TrainingArguments' default is torch AdamW (the reference passes no
@@ -358,7 +369,8 @@ class DistillationTrainer(FlatStudentTrainer):
                 t.record_stream(st)
         return batch_samples, num_items, selected, ready
 
-    _TEACHER_SIDE_KEYS = ("teacher_input_ids", "teacher_attention_mask", "speech_token_mask", "teacher_top_k_v", "teacher_top_k_i")
+    _TEACHER_SIDE_KEYS = ("teacher_input_ids", "teacher_attention_mask", "speech_token_mask", "teacher_top_k_v", "teacher_top_k_i",
+                          "teacher_top_k_tail")
 
     def training_step(self, model, inputs, *args, **kwargs):
         if self.lmbda > 0:
@@ -427,6 +439,7 @@ class DistillationTrainer(FlatStudentTrainer):
 
     def _teacher_pass(self, inputs, teacher_input_ids, teacher_attention_mask, vocab_size, rows=None, model_kw=None):
         """train.py:60-94: teacher no-grad forward, then on-the-fly top-K unless quantized / top_k <= 0.
+        -> (logits, None, None, None) or (None, top_v, top_i, tail); ``tail`` is None but for the ``_tail`` divergences.
         ``rows``: only those flat rows of the logits are produced (our own teacher) or kept (any other module);
         ``model_kw``: extra keyword arguments for a HipQwen3ForCausalLM teacher (``padding_checked``, ``packed_batch``).
         A packed batch (``_is_packed(inputs)``): the teacher's own ids go with the batch's packed keys and no mask -- one
@@ -448,8 +461,11 @@ class DistillationTrainer(FlatStudentTrainer):
                 teacher_logits = teacher_logits.reshape(-1, teacher_logits.size(-1))[rows]
             if not self.is_quantized_teacher and self.top_k > 0:
                 v, i = self._extract_topk(teacher_logits, self.top_k, vocab_size)
-                return None, v, i
-        return teacher_logits, None, None
+                tail = None
+                if self.divergence in ops.TAIL_DIVERGENCES:   # the logits are still here: their mass outside the top-K at T
+                    tail = self._extract_tail(teacher_logits, i, self.distill_loss_fn.temperature, vocab_size)
+                return None, v, i, tail
+        return teacher_logits, None, None, None
 
     def compute_loss(self, model, inputs, return_outputs=False, **kwargs):
         teacher_input_ids = inputs.pop("teacher_input_ids", None)
@@ -457,8 +473,10 @@ class DistillationTrainer(FlatStudentTrainer):
         speech_mask = inputs.pop("speech_token_mask", None)
         teacher_top_k_v = inputs.pop("teacher_top_k_v", None)
         teacher_top_k_i = inputs.pop("teacher_top_k_i", None)
+        teacher_top_k_tail = inputs.pop("teacher_top_k_tail", None)   # (read by the _tail divergences only)
 
-        if self.divergence not in ("forward_kl", ops.TOPK_DIVERGENCE) and teacher_top_k_v is not None:
+        if (self.divergence not in ("forward_kl", ops.TOPK_DIVERGENCE) and self.divergence not in ops.TAIL_DIVERGENCES
+                and teacher_top_k_v is not None):
             raise ValueError(f"divergence={self.divergence!r} needs the dense teacher distribution; this batch carries "
                              "pre-extracted teacher_top_k_v (K entries per position)")
         need_teacher = teacher_top_k_v is None and self.teacher_model is not None
@@ -531,7 +549,7 @@ class DistillationTrainer(FlatStudentTrainer):
         ahead = self._ahead_results.pop(id(lab), None) if fetched is not None and rows is not None else None
         if ahead is not None:   # SD_TEACHER_AHEAD: this batch's teacher pass was enqueued at the end of the previous micro-step
             side = self._teacher_stream
-            teacher_logits, teacher_top_k_v, teacher_top_k_i = ahead
+            teacher_logits, teacher_top_k_v, teacher_top_k_i, teacher_top_k_tail = ahead
             if hip_student:
                 checked = dict(checked, concurrent=True)
         elif (need_teacher and self.overlap_teacher and vocab is not None and ids is not None and ids.is_cuda
@@ -552,12 +570,14 @@ class DistillationTrainer(FlatStudentTrainer):
             if hip_student:
                 checked = dict(checked, concurrent=True)
             with torch.cuda.stream(side):
-                teacher_logits, teacher_top_k_v, teacher_top_k_i = self._teacher_pass(
+                teacher_logits, teacher_top_k_v, teacher_top_k_i, teacher_top_k_tail = self._teacher_pass(
                     inputs, teacher_input_ids, teacher_attention_mask, vocab, rows, teacher_kw)
         elif rows is not None and teacher_top_k_v is not None:  # pre-extracted top-K: keep the same rows
             dev = lab.device
             teacher_top_k_v = teacher_top_k_v.to(dev).reshape(-1, teacher_top_k_v.size(-1))[rows]
             teacher_top_k_i = teacher_top_k_i.to(dev).reshape(-1, teacher_top_k_i.size(-1))[rows]
+            if teacher_top_k_tail is not None:
+                teacher_top_k_tail = teacher_top_k_tail.to(dev).reshape(-1)[rows]
 
         outputs = model(**inputs, **checked) if rows is None else model(**inputs, logit_rows=rows, **checked)  # train.py:54
         student_logits = outputs.logits
@@ -568,25 +588,28 @@ class DistillationTrainer(FlatStudentTrainer):
         teacher_logits_local = None
         if side is not None:
             torch.cuda.current_stream().wait_stream(side)
-            for t in (teacher_logits, teacher_top_k_v, teacher_top_k_i):   # allocated on the teacher's stream, read on this one
+            # allocated on the teacher's stream, read on this one
+            for t in (teacher_logits, teacher_top_k_v, teacher_top_k_i, teacher_top_k_tail):
                 if torch.is_tensor(t) and t.is_cuda:
                     t.record_stream(torch.cuda.current_stream())
             teacher_logits_local = teacher_logits
         elif need_teacher:  # reference order: student first, then teacher (train.py:60-94)
-            teacher_logits_local, teacher_top_k_v, teacher_top_k_i = self._teacher_pass(
+            teacher_logits_local, teacher_top_k_v, teacher_top_k_i, teacher_top_k_tail = self._teacher_pass(
                 inputs, teacher_input_ids, teacher_attention_mask, student_logits.size(-1), rows, teacher_kw)
         teacher_logits = teacher_logits_local
 
         if isinstance(self.distill_loss_fn, DistillationLoss):
             self.distill_loss_fn.inplace_grad = (not return_outputs) and hip_student
+        # (the tail goes to the _tail divergences only: any other loss, a caller's own included, keeps its signature)
+        tail_kw = {"teacher_top_k_tail": teacher_top_k_tail} if self.divergence in ops.TAIL_DIVERGENCES else {}
         if rows is not None:
             loss, task_loss, distill_loss, teacher_loss = self.distill_loss_fn.forward_rows(
                 student_logits, row_labels, teacher_logits=teacher_logits, teacher_top_k_v=teacher_top_k_v,
-                teacher_top_k_i=teacher_top_k_i)
+                teacher_top_k_i=teacher_top_k_i, **tail_kw)
         else:
             loss, task_loss, distill_loss, teacher_loss = self.distill_loss_fn(
                 student_logits=student_logits, labels=labels, teacher_logits=teacher_logits,
-                teacher_top_k_v=teacher_top_k_v, teacher_top_k_i=teacher_top_k_i, speech_token_mask=speech_mask)
+                teacher_top_k_v=teacher_top_k_v, teacher_top_k_i=teacher_top_k_i, speech_token_mask=speech_mask, **tail_kw)
 
         if self.state.global_step % self.args.logging_steps == 0:  # train.py:107-114
             # one device->host sync for the three scalars instead of three .item() calls
