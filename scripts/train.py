@@ -102,6 +102,15 @@ def parse_args(argv=None):
     p.add_argument("--on_policy_temperature", type=float, default=1.0)
     p.add_argument("--on_policy_top_k", type=int, default=0)
     p.add_argument("--on_policy_decode_kernels", choices=("tile", "skinny", "wide"), default="tile")
+    p.add_argument("--on_policy_rollout", choices=("micro_batch", "window"), default="micro_batch",
+                   help="(+) window: roll out every drawn micro-batch of an accumulation window in one run of a continuous-"
+                        "batching engine (DESIGN.md section 12d); inert at --lmbda 0")
+    p.add_argument("--on_policy_max_batch", type=int, default=None,
+                   help="(+) rows of the window engine (default: batch size x accumulation steps, at most 64; more than 16 "
+                        "needs --on_policy_decode_kernels wide or tile)")
+    p.add_argument("--on_policy_admission", choices=("single", "batch"), default="single",
+                   help="(+) batch: the window engine prefills the requests it admits together in one pass (not bit-exact "
+                        "against a one-row generation)")
     p.add_argument("--log_json", default=None, help="(+) write trainer.state.log_history there (rank 0; every rank if the "
                    "path contains {rank})")
     # (+) padding-free packed batches; the defaults are the reference's right-padded [B, T] batches
@@ -113,6 +122,8 @@ def parse_args(argv=None):
     cfg = p.parse_args(argv)
     if cfg.pack_tokens < 0:
         p.error("--pack_tokens must be positive")
+    if cfg.on_policy_max_batch is not None and cfg.on_policy_max_batch < 1:
+        p.error("--on_policy_max_batch must be positive")
     cfg.padding_free = cfg.padding_free or cfg.pack_tokens > 0
     return cfg
 
@@ -156,6 +167,13 @@ def distill_kwargs(cfg, pad=None):
         if pad is not None:   # the dataset's rows end with the pad token (= <|semantic_token_end|>): it ends a rollout too
             gen.update(eos_token_id=pad, pad_token_id=pad)
         kw.update(lmbda=cfg.lmbda, on_policy_generate=gen)
+        if cfg.on_policy_rollout != "micro_batch":   # (at --lmbda 0 the three window flags are inert: nothing is passed)
+            eng = {}
+            if cfg.on_policy_max_batch is not None:
+                eng["max_batch"] = cfg.on_policy_max_batch
+            if cfg.on_policy_admission != "single":
+                eng["admission"] = cfg.on_policy_admission
+            kw.update(on_policy_rollout=cfg.on_policy_rollout, **({"on_policy_engine": eng} if eng else {}))
     return kw
 
 

@@ -18,14 +18,20 @@ as it is):
                         with lengths given in advance (what ``stats`` must come to for realised lengths).
   ``GenerationEngine``  the loop on the device: one ``Decoder`` over the pool plus the state of sd_sample_step_rows.
 
-Not built: pre-emption and swapping, batched admission prefill (one request per prefill pass is what keeps the bit
-contract), prefix matching between requests, per-request parameters inside sessions, captured graphs.
+One request per prefill pass is what keeps the bit contract; ``admission="batch"`` (opt-in) prefills an iteration's
+admissions in one pass and gives the contract up (``GenerationEngine``).  An engine is reusable: ``forget`` drops finished
+requests, ``reset_stats`` restarts the counters, and its decoder reads the model's live weights at every call.
+
+Not built: pre-emption and swapping, prefix matching between requests, per-request parameters inside sessions, captured
+graphs.
 """
 from __future__ import annotations
 
 from collections import deque
 
 from .paged import PAGE, PageAllocator, PageTable, pages_for
+
+ADMISSION = ("single", "batch")
 
 
 class Request:
@@ -135,15 +141,38 @@ class EngineLoop:
 
     def __init__(self, sched):
         self.sched = sched
-        self.stats = {"decode_steps": 0, "prefills": 0, "peak_pages": sched.alloc.pages_in_use, "iterations": 0}
         self.requests = {}
+        self.reset_stats()
+
+    def reset_stats(self):
+        """Start ``stats`` again, as a new loop over this scheduler would."""
+        self.stats = {"decode_steps": 0, "prefills": 0, "peak_pages": self.sched.alloc.pages_in_use, "iterations": 0}
+
+    def forget(self, rids=None):
+        """Drop finished requests (``rids``; None: every finished one) and their results, so that a loop that serves
+        window after window does not grow.  ValueError, with nothing dropped, for an unknown id or a request that is
+        still waiting or running."""
+        rids = [r for r, q in self.requests.items() if q.done] if rids is None else list(rids)
+        for r in rids:
+            if r not in self.requests:
+                raise ValueError(f"no request {r}")
+            if not self.requests[r].done:
+                raise ValueError(f"request {r} has not finished")
+        for r in rids:
+            self.requests.pop(r, None)
+
+    def _admit_all(self, reqs):
+        """The admissions of one iteration, in FIFO order: one ``_admit`` each (a loop may override it to batch them)."""
+        for req in reqs:
+            self._admit(req)
 
     def step(self):
         """Admissions, one sampler step, the frees it brings, one decode step.  -> the ids that finished."""
         s = self.sched
-        for req in s.admit():
-            self._admit(req)
-            self.stats["prefills"] += 1
+        reqs = s.admit()
+        if reqs:
+            self._admit_all(reqs)
+            self.stats["prefills"] += len(reqs)
         self.stats["peak_pages"] = max(self.stats["peak_pages"], s.alloc.pages_in_use)
         if not s.live:
             if s.waiting:    # only when somebody else holds the pool's pages: waiting would never end
@@ -222,12 +251,29 @@ class GenerationEngine(EngineLoop):
     row's state, and ``U[row]`` filled with the values a one-row session draws for the seed -- then runs ONE
     sd_sample_step_rows and ONE decode step over all rows.  The host reads ``finished`` once every ``sync_every``
     iterations and at no other time; a row whose budget is spent is freed without a read.  Free rows are finished rows at
-    position 0 that map the parking page, so every table entry a kernel reads lies in the pool.  ``result(id)`` (a host
-    read of one length) returns the new tokens up to and including the first EOS."""
+    position 0 that map the parking page, so every table entry a kernel reads lies in the pool.  ``result(id)`` returns the
+    new tokens up to and including the first EOS (one host read for the lengths of all finished requests not read yet).
+
+    ``admission``: "single" (default) is the above.  "batch" admits the requests the scheduler admits in one iteration --
+    same FIFO order, same page reservations -- through ONE ``Decoder.prefill_rows`` call over their right-padded prompts.
+    It gives up the one-row bit contract: the prefill's tile GEMMs then run at another M, whose summation order is not
+    the B = 1 prefill's, so a request's first logits (and what follows from them) may differ in the last bf16 bit from a
+    one-row session's.  An iteration that admits one request is the "single" admission.
+
+    The engine serves any number of ``run()``s: after each every page but the parking page is back in the pool,
+    ``forget`` drops finished requests and ``reset_stats`` starts the counters again.  Every prefill and decode step reads
+    the model's LIVE bf16 weights (``Decoder._params()`` is fetched per call and points into ``model.flat``), so weights
+    that an optimizer changes in place between two runs are the ones the second run decodes with.  What a ``Decoder``
+    keeps from its construction -- RoPE tables, the pool and table pointers, the step's scratch -- does not depend on
+    the weights; the one weight-derived cache is the MXFP8 copy (``model._mx_params()``), which is built once and which
+    ``_check_weight_dtype`` refuses for a model with trainable parameters."""
 
     def __init__(self, model, pool, max_batch=8, decode_kernels="skinny", weight_dtype="bf16", sync_every=16, capacity=None,
-                 decode_attention="split", gemv_rows=16):
+                 decode_attention="split", gemv_rows=16, admission="single"):
         import torch
+        if admission not in ADMISSION:
+            raise ValueError(f"admission must be one of {ADMISSION}, got {admission!r}")
+        self.admission = admission
         from ._lib import load_lib
         from .generation import Decoder, _check_decode_attention, _check_decode_kernels, _check_gemv_rows, cache_capacity
         from .ops import sample_params, sample_params_rows
@@ -294,10 +340,15 @@ class GenerationEngine(EngineLoop):
 
     def result(self, rid):
         """int64 [n] (device): the request's new tokens up to and including its first EOS, or all ``max_new_tokens``."""
+        import torch
         req = self.requests[rid]
         if not req.done:
             raise ValueError(f"request {rid} has not finished")
-        return req.tokens[:max(int(req.n_dev) - req.T, 0)]
+        if getattr(req, "n_host", None) is None:   # one read for every finished request whose length the host lacks
+            unread = [q for q in self.requests.values() if q.done and getattr(q, "n_host", None) is None]
+            for q, n in zip(unread, torch.cat([q.n_dev for q in unread]).tolist()):
+                q.n_host = n
+        return req.tokens[:max(req.n_host - req.T, 0)]
 
     def close(self):
         """Drop every request and give every page, the parking page included, back to the pool."""
@@ -330,12 +381,31 @@ class GenerationEngine(EngineLoop):
 
     # ---- the loop's hooks
     def _admit(self, req):
+        self._upload()
+        self._seat(req, self.decoder.prefill_rows([req.row], req.ids)[0])
+
+    def _admit_all(self, reqs):
+        """``admission="batch"``: one prefill pass for everything this iteration admits (right-padded to the longest
+        prompt; the pad slots are never cached), then each row's state as ``_admit`` sets it."""
+        import torch
+        if self.admission != "batch" or len(reqs) < 2:
+            return super()._admit_all(reqs)
+        dev, width = self.seq.device, max(r.T for r in reqs)
+        ids = torch.zeros(len(reqs), width, dtype=torch.int64, device=dev)
+        for i, req in enumerate(reqs):
+            ids[i, :req.T] = req.ids[0]
+        self._upload()
+        logits = self.decoder.prefill_rows([r.row for r in reqs], ids,
+                                           torch.tensor([r.T for r in reqs], dtype=torch.int32).to(dev))
+        for i, req in enumerate(reqs):
+            self._seat(req, logits[i])
+
+    def _seat(self, req, logits):
+        """The state of an admitted request's row behind its prefill (``logits`` bf16 [V]: its last prompt token's)."""
         import torch
         from .ops import sample_params_rows
         dev, r, T, n = self.seq.device, req.row, req.T, req.max_new
-        self._upload()
-        logits = self.decoder.prefill_rows([r], req.ids)
-        self.decoder.logits[r] = logits[0]
+        self.decoder.logits[r] = logits
         self.seq[r, :T] = req.ids[0]
         self._ints[:, r] = torch.tensor([T, T, n], dtype=torch.int32).to(dev)
         self.finished[r] = 0

@@ -966,7 +966,7 @@ class HipQwen3ForCausalLM(nn.Module):
                                  decode_attention=decode_attention, shared_kv_reads=shared_kv_reads, gemv_rows=gemv_rows)
 
     def generation_engine(self, pool, max_batch=8, decode_kernels="skinny", weight_dtype="bf16", sync_every=16,
-                          decode_attention="split", gemv_rows=16):
+                          decode_attention="split", gemv_rows=16, admission="single"):
         """A ``GenerationEngine`` (engine.py): continuous batching over a ``PagePool`` -- requests of their own length,
         budget, seed and sampling parameters are served in ``max_batch`` rows, and a row that finishes is refilled with the
         next waiting request at once (the reference's engine is vLLM, soulxpodcast/engine/llm_engine.py:91,97-109).
@@ -977,10 +977,13 @@ class HipQwen3ForCausalLM(nn.Module):
         session for ``max_batch <= 64``; "tile" is accepted without that claim (its step is not batch-invariant).
         ``decode_attention="fused"``: the one-launch cache step in every decode step, same tokens (see ``generate``).
         ``gemv_rows=64`` with ("skinny", "mxfp8"): the contract holds against a one-row session with the same three
-        keywords for ``max_batch <= 64``."""
+        keywords for ``max_batch <= 64``.  ``admission="batch"`` (default "single"): the requests admitted in one iteration
+        share ONE prefill pass over their right-padded prompts; faster admission, without the bit contract (the tile GEMMs
+        run at another M).  ``eng.forget(ids)`` and ``eng.reset_stats()`` make one engine serve run after run; every call
+        reads the model's live bf16 weights."""
         from .engine import GenerationEngine
         return GenerationEngine(self, pool, max_batch, decode_kernels, weight_dtype, sync_every,
-                                decode_attention=decode_attention, gemv_rows=gemv_rows)
+                                decode_attention=decode_attention, gemv_rows=gemv_rows, admission=admission)
 
     def kv_page_pool(self, n_pages, order=None, kv_dtype="bf16"):
         """A ``PagePool`` (paged.py) of ``n_pages`` pages of 256 positions for this model's paged sessions

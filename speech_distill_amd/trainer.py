@@ -21,6 +21,10 @@ from . import ddp, on_policy, ops
 from .distillation_loss import DistillationLoss
 from .qwen3 import HipQwen3ForCausalLM
 
+ON_POLICY_ROLLOUTS = ("micro_batch", "window")
+ENGINE_KEYS = ("max_batch", "n_pages", "sync_every", "admission")   # of DistillationTrainer(on_policy_engine={...})
+WINDOW_MAX_ROWS = 64   # the rows of the widest batch-invariant decode step (decode_kernels="wide")
+
 
 class FlatStudentTrainer(Trainer):
     """HF Trainer plumbing shared by the trainers of a flat-buffer student (``HipQwen3ForCausalLM``): the data-parallel
@@ -117,6 +121,20 @@ class DistillationTrainer(FlatStudentTrainer):
     replaced.  ``on_policy_fraction`` (the share of on-policy micro-batches since the previous log) is logged next to the
     three sub-losses.
 
+    ``on_policy_rollout``: "micro_batch" (default) is the above, one ``generate`` per drawn micro-batch inside
+    ``training_step``.  "window"  draws for every micro-batch of an accumulation window when HF
+    fetches the window (``get_batch_samples``; same generator, same stream of draws) and rolls all the drawn ones out in
+    ONE run of a ``GenerationEngine`` that lives as long as the trainer: one request per row with the row's own width as
+    its budget and ``on_policy.request_seed`` as its seed, rows refilled as requests stop.  The weights do not change
+    inside a window, so this is exactly as on-policy as the micro-batch loop.  ``on_policy_engine``: a dict of
+    ``max_batch`` (default: ``per_device_train_batch_size * gradient_accumulation_steps``, at most 64), ``n_pages``
+    (default: ``max_batch`` rows' worst case at the window's width plus the parking page), ``sync_every`` (16) and
+    ``admission`` ("single" / "batch", see ``GenerationEngine``).  ``decode_kernels`` comes from ``on_policy_generate``.
+    Refused at construction (ValueError): a LoRA student, a ``padding_free`` collator (packed batches are refused again
+    when they arrive), a missing teacher, "skinny" with ``max_batch > 16`` (use "wide"), ``WORLD_SIZE > 1``.  With
+    ``lmbda = 0`` the keyword is inert.  The rollouts happen inside HF's loop: a ``training_step`` called by hand in
+    window mode trains on the batch it is given.
+
     Packed batches (``ProcessedDataCollator(padding_free=True)``; a batch is packed by its keys: ``position_ids`` present
     and ``attention_mask`` absent): ``ops.packed_rows`` selects the loss rows inside each document and checks the segments
     in the step's one host read, one ``PackedBatch`` descriptor serves student and teacher, and the teacher is called with
@@ -124,7 +142,8 @@ class DistillationTrainer(FlatStudentTrainer):
     shape, and a packed batch that also carries an attention mask."""
 
     def __init__(self, *args, teacher_model=None, temperature=2.0, alpha=0.5, top_k=100, is_quantized_teacher=False,
-                 divergence="forward_kl", beta=0.5, lmbda=0.0, on_policy_generate=None, **kwargs):
+                 divergence="forward_kl", beta=0.5, lmbda=0.0, on_policy_generate=None, on_policy_rollout="micro_batch",
+                 on_policy_engine=None, **kwargs):
         # everything that can be refused without a model is refused before HF's constructor touches one
         ops.check_divergence(divergence, beta)
         if divergence == ops.TOPK_DIVERGENCE or divergence in ops.TAIL_DIVERGENCES:
@@ -141,7 +160,20 @@ class DistillationTrainer(FlatStudentTrainer):
             on_policy.check_generate_kwargs(on_policy_generate)
             if teacher_model is None:
                 raise ValueError("lmbda > 0 needs a teacher model: on-policy tokens have no pre-extracted teacher logits")
+        if on_policy_rollout not in ON_POLICY_ROLLOUTS:
+            raise ValueError(f"on_policy_rollout must be one of {ON_POLICY_ROLLOUTS}, got {on_policy_rollout!r}")
+        engine_cfg = self._check_engine_config(on_policy_engine)
+        if on_policy_rollout == "window" and lmbda > 0:   # (with lmbda = 0 the mode is inert: nothing is checked or built)
+            engine_cfg = self._window_plan(kwargs.get("model", args[0] if args else None),
+                                           kwargs.get("args", args[1] if len(args) > 1 else None),
+                                           kwargs.get("data_collator", args[2] if len(args) > 2 else None),
+                                           on_policy_generate, engine_cfg)
         super().__init__(*args, **kwargs)
+        self.on_policy_rollout = on_policy_rollout
+        self.on_policy_engine = engine_cfg     # "window" with lmbda > 0: max_batch, sync_every and admission resolved
+        self._engine, self._engine_pool, self._engine_pages = None, None, 0   # built at the first window (_window_engine)
+        self.engines_built = 0
+        self._window_draws = []   # "window": the draws of the fetched window's micro-batches that training_step has not taken yet
         self.teacher_model = teacher_model
         if self.teacher_model is not None:
             self.teacher_model.eval()
@@ -192,6 +224,108 @@ class DistillationTrainer(FlatStudentTrainer):
     def _dense_name(divergence):
         """The divergence that takes the dense teacher distribution where ``divergence`` takes a top-K teacher."""
         return divergence[:-len("_tail")] if divergence in ops.TAIL_DIVERGENCES else "jsd"
+
+    # ------------------------------------------------------------------------------ on-policy window rollouts
+    @staticmethod
+    def _check_engine_config(cfg):
+        """``on_policy_engine``: None or a dict of ``ENGINE_KEYS``.  -> a copy; ValueError for anything else."""
+        if cfg is None:
+            return {}
+        if not isinstance(cfg, dict) or set(cfg) - set(ENGINE_KEYS):
+            raise ValueError(f"on_policy_engine must be a dict of {ENGINE_KEYS}, got {cfg!r}")
+        from .engine import ADMISSION
+        if cfg.get("admission", "single") not in ADMISSION:
+            raise ValueError(f"on_policy_engine['admission'] must be one of {ADMISSION}, got {cfg['admission']!r}")
+        for k in ("max_batch", "n_pages", "sync_every"):
+            if cfg.get(k) is not None and (not isinstance(cfg[k], int) or isinstance(cfg[k], bool) or cfg[k] < 1):
+                raise ValueError(f"on_policy_engine[{k!r}] must be a positive integer, got {cfg[k]!r}")
+        return dict(cfg)
+
+    @staticmethod
+    def _window_plan(model, targs, collator, generate_kwargs, cfg):
+        """What ``on_policy_rollout="window"`` refuses, before HF's constructor and long before anything is allocated,
+        and the engine's shape: -> ``cfg`` with ``max_batch`` (default: the rows of one accumulation window, at most
+        ``WINDOW_MAX_ROWS``), ``sync_every`` and ``admission`` filled in (``n_pages``: None = sized at the first window)."""
+        core = ddp.unwrap(model) if model is not None else None
+        if getattr(core, "_lora", None) is not None:
+            raise ValueError('on_policy_rollout="window" is not built for a LoRA student: the engine decodes from the '
+                             "live flat weights, an adapter's merged copy would have to be refreshed every window")
+        if getattr(collator, "padding_free", False):
+            raise ValueError('on_policy_rollout="window" with packed batches (padding_free): on-policy rollouts rebuild '
+                             "right-padded [B, T] rows")
+        world = max(int(os.environ.get("WORLD_SIZE", "1") or 1), int(getattr(targs, "world_size", 1) or 1))
+        if world > 1:
+            raise ValueError(f'on_policy_rollout="window" is built and tested on one rank only, got WORLD_SIZE {world}')
+        rows = 1
+        if targs is not None:
+            rows = int(targs.per_device_train_batch_size) * int(targs.gradient_accumulation_steps)
+        out = dict(cfg)
+        out["max_batch"] = int(cfg.get("max_batch") or min(rows, WINDOW_MAX_ROWS))
+        out["sync_every"] = int(cfg.get("sync_every") or 16)
+        out["admission"] = cfg.get("admission", "single")
+        out.setdefault("n_pages", None)
+        kernels = generate_kwargs.get("decode_kernels", "tile")
+        if kernels == "skinny" and out["max_batch"] > 16:
+            raise ValueError(f'decode_kernels="skinny" keeps a row\'s tokens independent of the batch for up to 16 rows, the '
+                             f'window engine would hold {out["max_batch"]}: use decode_kernels="wide" (up to 64 rows), or '
+                             "on_policy_engine={'max_batch': 16}")
+        if kernels == "wide" and out["max_batch"] > WINDOW_MAX_ROWS:
+            raise ValueError(f'decode_kernels="wide" takes up to {WINDOW_MAX_ROWS} rows, got max_batch {out["max_batch"]}')
+        return out
+
+    def _window_engine(self, core, width):
+        """The trainer's one ``GenerationEngine`` over a pool of its own, built at the first window.  ``n_pages`` defaults
+        to ``max_batch`` rows' worst case at the window's width (a request holds at most ``width`` positions: its prompt
+        and a budget cut at the row's width) plus the parking page; a later window that needs more pages per row than
+        every window before it replaces engine and pool (a given ``n_pages`` is kept, and ``submit`` refuses what it
+        cannot hold)."""
+        from .paged import PAGE, pages_for
+        cfg = self.on_policy_engine
+        per_row = pages_for(width)
+        if self._engine is not None and (cfg["n_pages"] is not None or per_row <= self._engine_pages):
+            return self._engine
+        self.close_engine()
+        n_pages = cfg["n_pages"] if cfg["n_pages"] is not None else cfg["max_batch"] * per_row + 1
+        self._engine_pool = core.kv_page_pool(n_pages)
+        from .engine import GenerationEngine
+        self._engine = GenerationEngine(core, self._engine_pool, cfg["max_batch"],
+                                        self.on_policy_generate.get("decode_kernels", "tile"), "bf16", cfg["sync_every"],
+                                        capacity=None if cfg["n_pages"] is not None else per_row * PAGE,
+                                        admission=cfg["admission"])
+        self._engine_pages = per_row
+        self.engines_built += 1
+        return self._engine
+
+    def close_engine(self):
+        """Close the window engine (its pages go back to its pool) and drop both."""
+        if self._engine is not None:
+            self._engine.close()
+        self._engine, self._engine_pool, self._engine_pages = None, None, 0
+
+    def __del__(self):
+        try:
+            self.close_engine()
+        except Exception:
+            pass
+
+    def _roll_out_window(self, batch_samples):
+        """``on_policy_rollout="window"``: one draw per micro-batch of the window, in order (``on_policy.draw``: the stream
+        of the micro-batch mode), then ONE engine run for every drawn micro-batch (``on_policy.rollout_window``, under
+        no_grad; the engine reads the live flat weights, which do not change inside a window).  Undrawn micro-batches pass
+        through as the same objects.  ``model.training``, ``flat_grad`` and saved activations are not touched."""
+        core = ddp.unwrap(self.model)
+        for b in batch_samples:
+            if isinstance(b, dict):   # (a packed batch is refused before anything is drawn or allocated)
+                self._check_packed(b, b.get("teacher_input_ids"), b.get("teacher_attention_mask"))
+        draws = [on_policy.draw(self._on_policy_rng, self.lmbda) for _ in batch_samples]
+        self._window_draws = [on for on, _ in draws]   # counted one by one as training_step takes the micro-batches
+        if not any(on for on, _ in draws):
+            return batch_samples
+        batches = [self._prepare_inputs(b) if on else b for b, (on, _) in zip(batch_samples, draws)]
+        width = max(b["input_ids"].shape[1] for b, (on, _) in zip(batches, draws) if on)
+        with torch.no_grad():
+            return on_policy.rollout_window(self._window_engine(core, width), batches, self.on_policy_generate,
+                                            [seed for _, seed in draws])
 
     def create_optimizer(self, model=None):
         """HF trainer.py `create_optimizer(self, model=None)`: TrainingArguments' default is torch AdamW (the reference passes no
@@ -302,7 +436,10 @@ class DistillationTrainer(FlatStudentTrainer):
         if not ahead:
             self._rows_ahead.clear()
             self._window, self._window_next, self._ahead_results, self._prefetched = [], [], {}, None
-            return super().get_batch_samples(epoch_iterator, num_batches, device)
+            batch_samples, num_items = super().get_batch_samples(epoch_iterator, num_batches, device)
+            if self.lmbda > 0 and self.on_policy_rollout == "window":   # the whole window's rollouts, before its first step
+                batch_samples = self._roll_out_window(batch_samples)
+            return batch_samples, num_items
         # window k comes from the previous call's lookahead when there is one (same iterator object = same epoch)
         pre, self._prefetched = self._prefetched, None
         if pre is not None and pre[0] is epoch_iterator:
@@ -376,7 +513,11 @@ class DistillationTrainer(FlatStudentTrainer):
         if self.lmbda > 0:
             if isinstance(inputs, dict):   # (a packed batch is refused before the rollout, not after it)
                 self._check_packed(inputs, inputs.get("teacher_input_ids"), inputs.get("teacher_attention_mask"))
-            inputs = self._maybe_on_policy(model, inputs)
+            if self.on_policy_rollout == "micro_batch":
+                inputs = self._maybe_on_policy(model, inputs)
+            else:   # "window": drawn and rolled out in get_batch_samples; counted here, where the micro-batch mode counts
+                self._on_policy_seen[1] += 1
+                self._on_policy_seen[0] += int(self._window_draws.pop(0)) if self._window_draws else 0
         lab = inputs.get("labels") if isinstance(inputs, dict) else None
         loss = super().training_step(model, inputs, *args, **kwargs)
         mode = os.environ.get("SD_TEACHER_AHEAD", "auto")
@@ -390,9 +531,9 @@ class DistillationTrainer(FlatStudentTrainer):
         (``on_policy.rollout``: no_grad, the decoder reads the live flat weights; ``flat``, ``flat_grad``, the saved
         activations and the train/eval flag are not touched).  The rollout's seed comes from the same generator."""
         self._on_policy_seen[1] += 1
-        if float(torch.rand(1, generator=self._on_policy_rng)) >= self.lmbda:
+        on, seed = on_policy.draw(self._on_policy_rng, self.lmbda)
+        if not on:
             return inputs
-        seed = int(torch.randint(0, 2 ** 31 - 1, (1,), generator=self._on_policy_rng))
         self._on_policy_seen[0] += 1
         return on_policy.rollout(ddp.unwrap(model).generate, self._prepare_inputs(inputs), self.on_policy_generate, seed)
 
