@@ -37,6 +37,45 @@ template <typename F> void by_flag(bool b, F&& fn) {
 #define SD_FLAG(tag) decltype(tag)::value
 inline const char* type_name(size_t size) { return size == 2 ? "__bf16" : "float"; }
 inline const char* flag_name(bool b) { return b ? "true" : "false"; }
+// fn(NF): the threads per row of a forward with a top-K teacher, one thread per entry in its epilogue -- 512, and 1024
+// only where the K entries do not fit one thread each at 512
+typedef std::integral_constant<int, 512> Threads512;
+template <typename F> void by_threads(int K, F&& fn) {
+  if (K > 512) fn(std::integral_constant<int, 1024>{}); else fn(Threads512{});
+}
+
+// What every rows entry asks of its rows, in this order: V a multiple of 8, S (and the dense teacher S2, if there is
+// one) 16-byte aligned, bf16 or fp32.  Each family's check puts its own conditions before and after.
+int rows_check(int V, int dtype, const void* S, const void* S2 = nullptr) {
+  if (V & 7) return SD_ERR_ALIGN;
+  if (((uintptr_t)S & 15) || ((uintptr_t)S2 & 15)) return SD_ERR_ALIGN;
+  if (dtype != SD_DTYPE_BF16 && dtype != SD_DTYPE_F32) return SD_ERR_UNSUPPORTED;
+  return 0;
+}
+
+// The launch path of every rows entry: the dtype becomes the element type T, `launch(tag of T)` runs inside a profiler
+// record of `kind` over elems x sizeof(T) bytes and is checked; then `fin()`, a forward's finalize launch, is run and
+// checked -- after the record has ended, or (fin_in_scope: sd_kdloss_fwd*, whose record has always covered both) inside.
+template <typename L, typename F>
+int rows_launch(int dtype, int kind, double elems, hipStream_t st, bool fin_in_scope, L&& launch, F&& fin) {
+  return by_dtype(dtype, [&](auto tt) -> int {
+    SdProfScope prof(kind, elems * sizeof(SD_TAG_TYPE(tt)), st);
+    launch(tt);
+    SD_CHECK_LAUNCH();
+    if (!fin_in_scope) prof.close();
+    fin();
+    SD_CHECK_LAUNCH();
+    return 0;
+  });
+}
+template <typename L> int rows_launch(int dtype, int kind, double elems, hipStream_t st, L&& launch) {  // a backward
+  return rows_launch(dtype, kind, elems, st, true, launch, [] {});
+}
+
+// the exit of a forward kernel on a masked row: its stats are all zeros (valid = 0)
+template <typename Stats> SD_DEV void masked_row(Stats* stats, int row) {
+  if (threadIdx.x == 0) stats[row] = Stats{};
+}
 
 // row -> (b, t); label / mask are taken at t+1 (the causal shift).  T == 0: the caller already selected and
 // shifted the rows (sd_kdloss_fwd_rows): label / mask are taken at `row` itself.
@@ -75,10 +114,7 @@ __global__ __launch_bounds__(NF, (NF == 1024 && sizeof(T) == 2) ? 8 : 1) void kd
   const int row = blockIdx.x;
   long y = 0;
   const bool valid = row_valid(labels, mask, row, Tlen, &y);
-  if (!valid || y < 0 || y >= V) {
-    if (threadIdx.x == 0) stats[row] = RowStats{0, 0, 0, 0, 0, 0, 0, 0};
-    return;
-  }
+  if (!valid || y < 0 || y >= V) return masked_row(stats, row);
   const float invT = 1.f / temperature;
   const float k1 = 1.4426950408889634f, kT = invT * k1;  // log2(e), log2(e) / T
   const T* s = S + (long)row * V;
@@ -265,12 +301,19 @@ __global__ __launch_bounds__(NT) void kd_bwd_kernel(const T* S, const T* __restr
 
 int check(const void* S, const void* Tl, const void* topv, const void* topi, int B, int Tlen, int V, int K, int dtype) {
   if (B <= 0 || Tlen < 0 || V <= 0) return SD_ERR_SHAPE;
-  if (V & 7) return SD_ERR_ALIGN;
-  if ((uintptr_t)S & 15) return SD_ERR_ALIGN;
-  if (dtype != SD_DTYPE_BF16 && dtype != SD_DTYPE_F32) return SD_ERR_UNSUPPORTED;
+  if (int e = rows_check(V, dtype, S)) return e;
   if (!Tl && !(topv && topi)) return SD_ERR_NO_TEACHER;
   if (!Tl && (K <= 0 || K > KMAX)) return SD_ERR_SHAPE;
   return 0;
+}
+
+// a forward's finalize launch over the family's stats (rows_launch's `fin`)
+template <typename Stats, bool HITS>
+auto finalize(const void* stats, float* out, int rows, float temperature, float alpha, int dense, hipStream_t st) {
+  return [=] {
+    hipLaunchKernelGGL((kd_finalize_kernel<Stats, HITS>), dim3(1), dim3(NT), 0, st, (const Stats*)stats, out, rows,
+                       temperature, alpha, dense);
+  };
 }
 
 // Both forward entries: B sequences of Tlen positions, shifted and masked by the kernel (sd_kdloss_fwd), or Tlen == 0 and
@@ -280,28 +323,21 @@ int kd_fwd(const void* S, const void* Tl, const void* topv, const void* topi, co
   if (int e = check(S, Tl, topv, topi, B, Tlen, V, K, dtype)) return e;
   hipStream_t st = (hipStream_t)stream;
   const int rows = Tlen ? B * Tlen : B;
-  return by_dtype(dtype, [&](auto tt) -> int {
+  return rows_launch(dtype, SD_K_LOSS_FWD, (double)rows * V * (Tl ? 2 : 1), st, true, [&](auto tt) {
     typedef SD_TAG_TYPE(tt) T;
-    SdProfScope prof(SD_K_LOSS_FWD, (double)rows * V * sizeof(T) * (Tl ? 2 : 1), st);
-    auto launch = [&](auto t2, auto wide, auto dense) {
-      constexpr int NF = SD_FLAG(wide) ? 1024 : 512;
+    auto launch = [&](auto t2, auto nf, auto dense) {
+      constexpr int NF = SD_FLAG(nf);
       // the symbol as rocprofv3 --kernel-trace prints it
       SD_PROF_LABEL("kd_fwd_kernel<%s, %s, %d, %s>", type_name(sizeof(T)), flag_name(SD_FLAG(t2)), NF, flag_name(SD_FLAG(dense)));
       hipLaunchKernelGGL((kd_fwd_kernel<T, SD_FLAG(t2), NF, SD_FLAG(dense)>), dim3(rows), dim3(NF), 0, st, (const T*)S,
                          (const T*)Tl, (const _Float16*)topv, (const int32_t*)topi, labels, mask, (RowStats*)stats, rows, Tlen,
                          V, K, temperature);
     };
-    // 1024 threads only where the K teacher entries do not fit one thread each at 512
     by_flag(temperature == 2.0f, [&](auto t2) {
-      if (Tl) launch(t2, std::false_type{}, std::true_type{});
-      else by_flag(K > 512, [&](auto wide) { launch(t2, wide, std::false_type{}); });
+      if (Tl) launch(t2, Threads512{}, std::true_type{});
+      else by_threads(K, [&](auto nf) { launch(t2, nf, std::false_type{}); });
     });
-    SD_CHECK_LAUNCH();
-    hipLaunchKernelGGL((kd_finalize_kernel<RowStats, true>), dim3(1), dim3(NT), 0, st, (const RowStats*)stats, out, rows,
-                       temperature, alpha, Tl ? 1 : 0);
-    SD_CHECK_LAUNCH();
-    return 0;
-  });
+  }, finalize<RowStats, true>(stats, out, rows, temperature, alpha, Tl ? 1 : 0, st));
 }
 
 int kd_bwd(const void* S, const void* Tl, const void* topv, const void* topi, const int64_t* labels, const void* stats,
@@ -311,15 +347,12 @@ int kd_bwd(const void* S, const void* Tl, const void* topv, const void* topi, co
   if ((uintptr_t)G & 15) return SD_ERR_ALIGN;
   hipStream_t st = (hipStream_t)stream;
   const int rows = Tlen ? B * Tlen : B;
-  return by_dtype(dtype, [&](auto tt) -> int {
+  return rows_launch(dtype, SD_K_LOSS_BWD, (double)rows * V * (Tl ? 3 : 2), st, [&](auto tt) {
     typedef SD_TAG_TYPE(tt) T;
-    SdProfScope prof(SD_K_LOSS_BWD, (double)rows * V * sizeof(T) * (Tl ? 3 : 2), st);
     SD_PROF_LABEL("kd_bwd_kernel<%s>", type_name(sizeof(T)));
     hipLaunchKernelGGL((kd_bwd_kernel<T>), dim3(rows), dim3(NT), 0, st, (const T*)S, (const T*)Tl, (const _Float16*)topv,
                        (const int32_t*)topi, labels, (const RowStats*)stats, out, go, (T*)G, rows, Tlen, V, K, temperature,
                        alpha);
-    SD_CHECK_LAUNCH();
-    return 0;
   });
 }
 
@@ -375,10 +408,7 @@ __global__ __launch_bounds__(NF) void ce_fwd_kernel(const T* __restrict__ S, con
   __shared__ float sc[32];
   const int row = blockIdx.x;
   const long y = labels[row];
-  if (y < 0 || y >= V) {  // -100 (and anything outside the vocabulary) masks the row
-    if (threadIdx.x == 0) stats[row] = CeStats{0.f, 0.f, 0.f, 0.f};
-    return;
-  }
+  if (y < 0 || y >= V) return masked_row(stats, row);  // -100 (and anything outside the vocabulary) masks the row
   const float k1 = 1.4426950408889634f;  // log2(e)
   const T* s = S + (long)row * V;
   float m = -INFINITY, s1 = 0.f;
@@ -444,10 +474,7 @@ __global__ __launch_bounds__(NT) void ce_bwd_kernel(const T* S, const int64_t* _
 
 int ce_check(const void* S, const int64_t* labels, int R, int V, int dtype) {
   if (R <= 0 || V <= 0 || !labels) return SD_ERR_SHAPE;
-  if (V & 7) return SD_ERR_ALIGN;
-  if ((uintptr_t)S & 15) return SD_ERR_ALIGN;
-  if (dtype != SD_DTYPE_BF16 && dtype != SD_DTYPE_F32) return SD_ERR_UNSUPPORTED;
-  return 0;
+  return rows_check(V, dtype, S);
 }
 
 }  // namespace
@@ -458,19 +485,14 @@ extern "C" int sd_celoss_fwd_rows(const void* logits, const int64_t* row_labels,
                                   float* loss_out, int R, int V, int dtype, void* stream) {
   if (int e = ce_check(logits, row_labels, R, V, dtype)) return e;
   hipStream_t st = (hipStream_t)stream;
-  if (int e = by_dtype(dtype, [&](auto tt) -> int {
-        typedef SD_TAG_TYPE(tt) T;
-        SdProfScope prof(SD_K_LOSS_FWD, (double)R * V * sizeof(T), st);
-        SD_PROF_LABEL("ce_fwd_kernel<%s, 512>", type_name(sizeof(T)));
-        hipLaunchKernelGGL((ce_fwd_kernel<T, 512>), dim3(R), dim3(512), 0, st, (const T*)logits, row_labels,
-                           (CeStats*)row_stats, V);
-        SD_CHECK_LAUNCH();
-        return 0;
-      }))
-    return e;
-  hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(NT), 0, st, (const CeStats*)row_stats, divisor, loss_out, R);
-  SD_CHECK_LAUNCH();
-  return 0;
+  return rows_launch(dtype, SD_K_LOSS_FWD, (double)R * V, st, false, [&](auto tt) {
+    typedef SD_TAG_TYPE(tt) T;
+    SD_PROF_LABEL("ce_fwd_kernel<%s, 512>", type_name(sizeof(T)));
+    hipLaunchKernelGGL((ce_fwd_kernel<T, 512>), dim3(R), dim3(512), 0, st, (const T*)logits, row_labels,
+                       (CeStats*)row_stats, V);
+  }, [&] {
+    hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(NT), 0, st, (const CeStats*)row_stats, divisor, loss_out, R);
+  });
 }
 
 extern "C" int sd_celoss_bwd_rows(const void* logits, const int64_t* row_labels, const void* row_stats,
@@ -479,14 +501,11 @@ extern "C" int sd_celoss_bwd_rows(const void* logits, const int64_t* row_labels,
   if (int e = ce_check(logits, row_labels, R, V, dtype)) return e;
   if ((uintptr_t)grad_logits & 15) return SD_ERR_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-  return by_dtype(dtype, [&](auto tt) -> int {
+  return rows_launch(dtype, SD_K_LOSS_BWD, (double)R * V * 2, st, [&](auto tt) {
     typedef SD_TAG_TYPE(tt) T;
-    SdProfScope prof(SD_K_LOSS_BWD, (double)R * V * sizeof(T) * 2, st);
     SD_PROF_LABEL("ce_bwd_kernel<%s>", type_name(sizeof(T)));
     hipLaunchKernelGGL((ce_bwd_kernel<T>), dim3(R), dim3(NT), 0, st, (const T*)logits, row_labels, (const CeStats*)row_stats,
                        loss_out, grad_total, (T*)grad_logits, V);
-    SD_CHECK_LAUNCH();
-    return 0;
   });
 }
 
@@ -498,6 +517,31 @@ extern "C" int sd_celoss_bwd_rows(const void* logits, const int64_t* row_labels,
 // launch and one 8-byte read instead of ~15 tiny torch kernels.
 namespace {
 
+// One chunk of 1024 candidates of a 1024-thread workgroup, compacted IN ORDER: thread tid's candidate e (with its label)
+// is appended to rows / row_labels iff `valid`, behind the *base_s rows of the chunks before -- ballot prefix inside a
+// wave, the 16 wave totals through LDS -- and *base_s moves on.  Its three barriers included: every thread calls it.
+SD_DEV void compact_chunk(bool valid, long long e, long long lab, long long* __restrict__ rows,
+                          long long* __restrict__ row_labels, int* wave_tot, int* base_s) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const unsigned long long bal = __ballot(valid);
+  const int before = __popcll(bal & ((1ull << lane) - 1ull));
+  if (lane == 0) wave_tot[wv] = __popcll(bal);
+  __syncthreads();
+  int off = *base_s;
+  for (int w = 0; w < wv; ++w) off += wave_tot[w];
+  if (valid) {
+    rows[off + before] = e;
+    row_labels[off + before] = lab;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int tot = 0;
+    for (int w = 0; w < 16; ++w) tot += wave_tot[w];
+    *base_s += tot;
+  }
+  __syncthreads();
+}
+
 __global__ __launch_bounds__(1024) void loss_rows_kernel(const long long* __restrict__ labels,
                                                          const long long* __restrict__ speech_mask,
                                                          const long long* __restrict__ mask_a,
@@ -506,7 +550,7 @@ __global__ __launch_bounds__(1024) void loss_rows_kernel(const long long* __rest
                                                          int T) {
   __shared__ int wave_tot[16];
   __shared__ int base_s, bad_s;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int tid = threadIdx.x;
   if (tid == 0) { base_s = 0; bad_s = 0; }
   __syncthreads();
   const long n = (long)B * T;
@@ -526,23 +570,7 @@ __global__ __launch_bounds__(1024) void loss_rows_kernel(const long long* __rest
         if (mask_b && mask_b[e] != 0 && mask_b[e - 1] == 0) bad = 1;
       }
     }
-    const unsigned long long bal = __ballot(valid);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wv] = __popcll(bal);
-    __syncthreads();
-    int off = base_s;
-    for (int w = 0; w < wv; ++w) off += wave_tot[w];
-    if (valid) {
-      rows[off + before] = e;
-      row_labels[off + before] = lab;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int tot = 0;
-      for (int w = 0; w < 16; ++w) tot += wave_tot[w];
-      base_s += tot;
-    }
-    __syncthreads();
+    compact_chunk(valid, e, lab, rows, row_labels, wave_tot, &base_s);
   }
   if (bad) atomicOr(&bad_s, 1);
   __syncthreads();
@@ -574,7 +602,7 @@ extern "C" int sd_loss_rows(const int64_t* labels, const int64_t* speech_mask, c
 // the segment array and reduces what the host needs to build the varlen descriptor and the RoPE gather without reading
 // anything else: the longest document and the largest position.  A chunk of 1024 tokens marks its document starts in LDS
 // from cu_seqlens (every offset is range-checked against the chunk before it indexes anything, so a malformed array gives
-// wrong rows and meta[1] bit 0, never an access outside [0, M)); the compaction is loss_rows_kernel's.
+// wrong rows and meta[1] bit 0, never an access outside [0, M)); the compaction is compact_chunk, as in loss_rows_kernel.
 namespace {
 
 __global__ __launch_bounds__(1024) void packed_rows_kernel(const long long* __restrict__ labels,
@@ -586,7 +614,7 @@ __global__ __launch_bounds__(1024) void packed_rows_kernel(const long long* __re
   __shared__ int wave_tot[16];
   __shared__ int base_s, bad_s, longest_s, maxpos_s;
   __shared__ unsigned char next_starts[1024];  // next_starts[i]: token c0 + i + 1 opens a document
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int tid = threadIdx.x;
   if (tid == 0) { base_s = 0; bad_s = 0; longest_s = 0; maxpos_s = 0; }
   __syncthreads();
   int bad = 0, longest = 0, maxpos = 0;
@@ -617,23 +645,7 @@ __global__ __launch_bounds__(1024) void packed_rows_kernel(const long long* __re
         maxpos = max(maxpos, (int)min(p, 0x7fffffffll));
       }
     }
-    const unsigned long long bal = __ballot(valid);
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wv] = __popcll(bal);
-    __syncthreads();
-    int off = base_s;
-    for (int w = 0; w < wv; ++w) off += wave_tot[w];
-    if (valid) {
-      rows[off + before] = e;
-      row_labels[off + before] = lab;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int tot = 0;
-      for (int w = 0; w < 16; ++w) tot += wave_tot[w];
-      base_s += tot;
-    }
-    __syncthreads();
+    compact_chunk(valid, e, lab, rows, row_labels, wave_tot, &base_s);
   }
   if (bad) atomicOr(&bad_s, bad);
   atomicMax(&longest_s, longest);
@@ -694,6 +706,19 @@ struct GjsdStats {  // 12 floats per row; m .. c are what the backward reads: ls
 constexpr int GJ_NF = 512;  // threads per row, as kd_fwd_kernel's dense variant (here 2 to 4 workgroups per CU by VGPRs)
 constexpr float GJ_LN2 = 0.6931471805599453f, GJ_LOG2E = 1.4426950408889634f, GJ_FLT_MIN = 1.17549435e-38f;
 
+// One element x of a normaliser sweep after online_raise: sT += exp((x - m) / T), s1 += exp(x - m), UNFOLDED --
+// exp2((x - m) kT), NOT kd_fwd_kernel's folded exp2(x kT - m kT): the fold leaves the rounding error of m kT in every
+// exponent (the maximum itself gives 1 + 1e-6 instead of 1).  A forward KL forgives that, it shifts lse(s) and the
+// cross term alike; here log q and log p each take their own shift, which on a peaked row near its teacher is
+// ten thousand times D.  One subtraction more per logit, next to exponentials at a quarter of the vector rate.
+template <bool T2>
+SD_DEV void unfolded_step(float x, float m, float kT, float k1, float& s1, float& sT) {
+  const float d = x - m;
+  const float q = __builtin_amdgcn_exp2f(d * kT);
+  sT += q;
+  s1 += T2 ? q * q : __builtin_amdgcn_exp2f(d * k1);
+}
+
 // one element of sweep 2 / of the backward: q and (in log2 units) log q - log p, or log q - log m.
 // m, mt: the row maxima; A0, B0: -log2 of the max-subtracted sums at T
 template <bool JSD>
@@ -720,10 +745,7 @@ __global__ __launch_bounds__(GJ_NF) void gjsd_fwd_kernel(const T* __restrict__ S
   __shared__ float sc[32];
   const int row = blockIdx.x;
   const long y = labels[row];
-  if (y < 0 || y >= V) {  // -100 (and anything outside the vocabulary) masks the row
-    if (threadIdx.x == 0) stats[row] = GjsdStats{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    return;
-  }
+  if (y < 0 || y >= V) return masked_row(stats, row);  // -100 (and anything outside the vocabulary) masks the row
   const float invT = 1.f / temperature;
   const float k1 = GJ_LOG2E, kT = invT * k1;
   const T* s = S + (long)row * V;
@@ -733,19 +755,10 @@ __global__ __launch_bounds__(GJ_NF) void gjsd_fwd_kernel(const T* __restrict__ S
   row_sweep<T, GJ_NF, true>(s, tl, V, [&](int, const float* f, const float* g) {
     online_raise<T2>(chunk_max8(f), invT, m, s1, sT);
     online_raise<T2>(chunk_max8(g), invT, mt, t1, tT);
-    // exp2((f - m) kT), NOT kd_fwd_kernel's folded exp2(f kT - m kT): the fold leaves the rounding error of m kT in every
-    // exponent (the maximum itself gives 1 + 1e-6 instead of 1).  A forward KL forgives that, it shifts lse(s) and the
-    // cross term alike; here log q and log p each take their own shift, which on a peaked row near its teacher is
-    // ten thousand times D.  One subtraction more per logit, next to exponentials at a quarter of the vector rate.
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float df = f[e] - m, dg = g[e] - mt;
-      const float q = __builtin_amdgcn_exp2f(df * kT);
-      const float w = __builtin_amdgcn_exp2f(dg * kT);
-      sT += q;
-      tT += w;
-      s1 += T2 ? q * q : __builtin_amdgcn_exp2f(df * k1);
-      t1 += T2 ? w * w : __builtin_amdgcn_exp2f(dg * k1);
+      unfolded_step<T2>(f[e], m, kT, k1, s1, sT);
+      unfolded_step<T2>(g[e], mt, kT, k1, t1, tT);
     }
   });
   block_merge<GJ_NF>(m, s1, sT, invT, sc);
@@ -811,22 +824,31 @@ __global__ __launch_bounds__(GJ_NF) void gjsd_bwd_kernel(const T* S, const T* __
   });
 }
 
-int gjsd_check(const void* S, const void* Tl, const int64_t* labels, const void* stats, const float* out, int R, int V,
-               float temperature, float beta, int mode, int dtype) {
+// The check of the three sd_gjsd*_rows families, in its one order: the row arrays, the family's teacher form (`teacher`: the
+// code its own conditions gave, or 0), rows_check, the family's modes (`modes`, likewise), temperature, and the beta of a JSD.
+// S2: a dense teacher, else null.  The backward's (G: true) gradient pointer comes last.
+int gjsd_check(const void* S, const void* S2, const int64_t* labels, const void* stats, const float* out, int R, int V,
+               float temperature, float beta, bool jsd, int dtype, int teacher, int modes, bool G, const void* grad) {
   if (R <= 0 || V <= 0 || !S || !labels || !stats || !out) return SD_ERR_SHAPE;
-  if (!Tl) return SD_ERR_NO_TEACHER;
-  if (V & 7) return SD_ERR_ALIGN;
-  if (((uintptr_t)S & 15) || ((uintptr_t)Tl & 15)) return SD_ERR_ALIGN;
-  if (dtype != SD_DTYPE_BF16 && dtype != SD_DTYPE_F32) return SD_ERR_UNSUPPORTED;
-  if (mode != SD_DIV_REVERSE_KL && mode != SD_DIV_JSD) return SD_ERR_UNSUPPORTED;
-  if (!(temperature > 0.f) || !(temperature < INFINITY)) return SD_ERR_SHAPE;       // NaN fails both comparisons
-  if (mode == SD_DIV_JSD && !(beta > 0.f && beta < 1.f)) return SD_ERR_SHAPE;    // likewise
+  if (teacher) return teacher;
+  if (int e = rows_check(V, dtype, S, S2)) return e;
+  if (modes) return modes;
+  if (!(temperature > 0.f) || !(temperature < INFINITY)) return SD_ERR_SHAPE;  // NaN fails both comparisons
+  if (jsd && !(beta > 0.f && beta < 1.f)) return SD_ERR_SHAPE;                  // likewise
+  if (G && !grad) return SD_ERR_SHAPE;
+  if (G && ((uintptr_t)grad & 15)) return SD_ERR_ALIGN;
   return 0;
 }
 
 // fn(T2, JSD): the two flags every gjsd kernel is instantiated over
 template <typename F> void gjsd_flags(float temperature, int mode, F&& fn) {
   by_flag(temperature == 2.0f, [&](auto t2) { by_flag(mode == SD_DIV_JSD, [&](auto jsd) { fn(t2, jsd); }); });
+}
+
+int gjsd_dense_check(const void* S, const void* Tl, const int64_t* labels, const void* stats, const float* out, int R, int V,
+                     float temperature, float beta, int mode, int dtype, bool G = false, const void* grad = nullptr) {
+  return gjsd_check(S, Tl, labels, stats, out, R, V, temperature, beta, mode == SD_DIV_JSD, dtype,
+                    !Tl ? SD_ERR_NO_TEACHER : 0, mode != SD_DIV_REVERSE_KL && mode != SD_DIV_JSD ? SD_ERR_UNSUPPORTED : 0, G, grad);
 }
 
 }  // namespace
@@ -836,47 +858,35 @@ extern "C" int64_t sd_gjsd_stats_bytes(int R) { return (int64_t)R * sizeof(GjsdS
 extern "C" int sd_gjsd_fwd_rows(const void* student_logits, const void* teacher_logits, const int64_t* row_labels,
                                 void* row_stats, float* loss_out, int R, int V, float temperature, float alpha, float beta,
                                 int mode, int dtype, void* stream) {
-  if (int e = gjsd_check(student_logits, teacher_logits, row_labels, row_stats, loss_out, R, V, temperature, beta, mode, dtype))
+  if (int e = gjsd_dense_check(student_logits, teacher_logits, row_labels, row_stats, loss_out, R, V, temperature, beta, mode, dtype))
     return e;
   hipStream_t st = (hipStream_t)stream;
-  if (int e = by_dtype(dtype, [&](auto tt) -> int {
-        typedef SD_TAG_TYPE(tt) T;
-        SdProfScope prof(SD_K_LOSS_FWD, (double)R * V * sizeof(T) * 2, st);
-        gjsd_flags(temperature, mode, [&](auto t2, auto jsd) {
-          SD_PROF_LABEL("gjsd_fwd_kernel<%s, %s, %s>", type_name(sizeof(T)), flag_name(SD_FLAG(t2)), flag_name(SD_FLAG(jsd)));
-          hipLaunchKernelGGL((gjsd_fwd_kernel<T, SD_FLAG(t2), SD_FLAG(jsd)>), dim3(R), dim3(GJ_NF), 0, st,
-                             (const T*)student_logits, (const T*)teacher_logits, row_labels, (GjsdStats*)row_stats, V,
-                             temperature, beta);
-        });
-        SD_CHECK_LAUNCH();
-        return 0;
-      }))
-    return e;
-  hipLaunchKernelGGL((kd_finalize_kernel<GjsdStats, false>), dim3(1), dim3(NT), 0, st, (const GjsdStats*)row_stats, loss_out,
-                     R, temperature, alpha, 1);
-  SD_CHECK_LAUNCH();
-  return 0;
+  return rows_launch(dtype, SD_K_LOSS_FWD, (double)R * V * 2, st, false, [&](auto tt) {
+    typedef SD_TAG_TYPE(tt) T;
+    gjsd_flags(temperature, mode, [&](auto t2, auto jsd) {
+      SD_PROF_LABEL("gjsd_fwd_kernel<%s, %s, %s>", type_name(sizeof(T)), flag_name(SD_FLAG(t2)), flag_name(SD_FLAG(jsd)));
+      hipLaunchKernelGGL((gjsd_fwd_kernel<T, SD_FLAG(t2), SD_FLAG(jsd)>), dim3(R), dim3(GJ_NF), 0, st,
+                         (const T*)student_logits, (const T*)teacher_logits, row_labels, (GjsdStats*)row_stats, V,
+                         temperature, beta);
+    });
+  }, finalize<GjsdStats, false>(row_stats, loss_out, R, temperature, alpha, 1, st));
 }
 
 extern "C" int sd_gjsd_bwd_rows(const void* student_logits, const void* teacher_logits, const int64_t* row_labels,
                                 const void* row_stats, const float* loss_out, const float* grad_total, void* grad_logits,
                                 int R, int V, float temperature, float alpha, float beta, int mode, int dtype, void* stream) {
-  if (int e = gjsd_check(student_logits, teacher_logits, row_labels, row_stats, loss_out, R, V, temperature, beta, mode, dtype))
+  if (int e = gjsd_dense_check(student_logits, teacher_logits, row_labels, row_stats, loss_out, R, V, temperature, beta, mode,
+                               dtype, true, grad_logits))
     return e;
-  if (!grad_logits) return SD_ERR_SHAPE;
-  if ((uintptr_t)grad_logits & 15) return SD_ERR_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-  return by_dtype(dtype, [&](auto tt) -> int {
+  return rows_launch(dtype, SD_K_LOSS_BWD, (double)R * V * 3, st, [&](auto tt) {
     typedef SD_TAG_TYPE(tt) T;
-    SdProfScope prof(SD_K_LOSS_BWD, (double)R * V * sizeof(T) * 3, st);
     gjsd_flags(temperature, mode, [&](auto t2, auto jsd) {
       SD_PROF_LABEL("gjsd_bwd_kernel<%s, %s, %s>", type_name(sizeof(T)), flag_name(SD_FLAG(t2)), flag_name(SD_FLAG(jsd)));
       hipLaunchKernelGGL((gjsd_bwd_kernel<T, SD_FLAG(t2), SD_FLAG(jsd)>), dim3(R), dim3(GJ_NF), 0, st,
                          (const T*)student_logits, (const T*)teacher_logits, row_labels, (const GjsdStats*)row_stats, loss_out,
                          grad_total, (T*)grad_logits, V, temperature, alpha, beta);
     });
-    SD_CHECK_LAUNCH();
-    return 0;
   });
 }
 
@@ -979,6 +989,16 @@ SD_DEV void tk_term(float sj, float P, float m, float kT, float A0, float beta, 
   lm = __builtin_amdgcn_logf(fmaxf(__builtin_fmaf(1.f - beta, q, beta * P), GJ_FLT_MIN));  // v_log_f32 = log2
 }
 
+// Entry k of a row: its index (-1: none, or dropped) and the mass of that index, P = scale x tk_mass (scale: 1, or
+// 1 - tau where the teacher has a tail bucket).  true: this entry owns the element -- it is the first one that holds
+// the index, and P is a normal number (the support S of both families).
+SD_DEV bool tk_entry(const int* k_i, const float* k_p, int K, int k, float scale, int& idx, float& P) {
+  bool first = false;
+  idx = k < K ? k_i[k] : -1;
+  P = scale * tk_mass(k_i, k_p, K, k, idx, first);
+  return first && P >= GJ_FLT_MIN;
+}
+
 // No register cap (kd_fwd_kernel's 8 waves per SIMD): held to 64 VGPRs every bf16 instantiation spills (20 / 108 bytes of
 // scratch per lane); left alone they take 68 (NF = 512: three workgroups per CU) and 93-95 (NF = 1024: one).
 template <typename T, bool T2, int NF>
@@ -996,32 +1016,22 @@ __global__ __launch_bounds__(NF) void gjsd_topk_fwd_kernel(const T* __restrict__
   const float k1 = GJ_LOG2E, kT = invT * k1;
   float hv = 0.f, hc = 0.f, mv = 0.f, sv = 0.f;
   // -100 (and anything outside the vocabulary) masks the row, and so does a teacher without a single kept entry
-  if (y < 0 || y >= V || !tk_renorm<NF, 1, false>(topv, topi, (long)row * K, K, V, kT, y, sc, k_i, k_p, hv, hc, mv, sv)) {
-    if (threadIdx.x == 0) stats[row] = GjsdTopkStats{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    return;
-  }
+  if (y < 0 || y >= V || !tk_renorm<NF, 1, false>(topv, topi, (long)row * K, K, V, kT, y, sc, k_i, k_p, hv, hc, mv, sv))
+    return masked_row(stats, row);
   const T* s = S + (long)row * V;
-  // ---- the one sweep: the student's normalisers at 1 and at T, exponent unfolded (see gjsd_fwd_kernel)
+  // ---- the one sweep: the student's normalisers at 1 and at T, exponent unfolded
   float m = -INFINITY, s1 = 0.f, sT = 0.f;
   row_sweep<T, NF, false>(s, (const T*)nullptr, V, [&](int, const float* f, const float*) {
     online_raise<T2>(chunk_max8(f), invT, m, s1, sT);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float df = f[e] - m;
-      const float q = __builtin_amdgcn_exp2f(df * kT);
-      sT += q;
-      s1 += T2 ? q * q : __builtin_amdgcn_exp2f(df * k1);
-    }
+    for (int e = 0; e < 8; ++e) unfolded_step<T2>(f[e], m, kT, k1, s1, sT);
   });
   block_merge<NF>(m, s1, sT, invT, sc);
   const float ls1 = __builtin_amdgcn_logf(s1), lsT = __builtin_amdgcn_logf(sT);  // v_log_f32: log2
   // ---- epilogue: one thread per entry; the first entry of an index owns its element of S
-  const int k = threadIdx.x;
-  bool first = false;
-  const int idx = k < K ? k_i[k] : -1;
-  const float P = tk_mass(k_i, k_p, K, k, idx, first);
-  float tp = 0.f, tq = 0.f, qs = 0.f;
-  if (first && P >= GJ_FLT_MIN) {
+  int idx;
+  float P, tp = 0.f, tq = 0.f, qs = 0.f;
+  if (tk_entry(k_i, k_p, K, threadIdx.x, 1.f, idx, P)) {
     float q, a2, lm;
     tk_term((float)s[idx], P, m, kT, -lsT, beta, q, a2, lm);
     tp = P * (__builtin_amdgcn_logf(P) - lm);
@@ -1038,30 +1048,34 @@ __global__ __launch_bounds__(NF) void gjsd_topk_fwd_kernel(const T* __restrict__
     stats[row] = GjsdTopkStats{m, ls1, lsT, c, 1.f, (m - (float)s[y]) + ls1 * GJ_LN2, D, hv, hc, mv, sv, 0.f};
 }
 
-// One read of the student row, one write of the gradient; G may alias S: the on-support values are formed from s
-// BEFORE the dense pass, with a workgroup barrier between the two, and stored after it.
-template <typename T, bool T2>
-__global__ __launch_bounds__(GJ_NF) void gjsd_topk_bwd_kernel(const T* S, const _Float16* __restrict__ topv,
-                                                              const int32_t* __restrict__ topi,
-                                                              const int64_t* __restrict__ labels,
-                                                              const GjsdTopkStats* __restrict__ stats,
-                                                              const float* __restrict__ loss_out,
-                                                              const float* __restrict__ grad_out, T* G, int V, int K,
-                                                              float temperature, float alpha, float beta) {
+// The backward of a row against a top-K teacher (both families; Stats: GjsdTopkStats or GjsdTailStats, `st` the row's):
+// one read of the student row, one write of the gradient.  Every element is a1 (softmax(s)_j - e_y) plus
+//   on S:  aT on_w(q_j, log2 q_j, log2 m_j, P_j),   off S:  aT d0c off(s_j, q_j, log2 q_j),
+// aT = go (1 - alpha) T / N x gs.  The family gives gs (the units of on_w and d0c), the scale of P (tk_entry), d0c (what
+// every off-support element of the row shares) and the two callables.
+// G may alias S.  The on-support values fo[] are formed from gathers of s BEFORE the dense pass, and the first barrier
+// stands between the two: every gather has returned (fo[] is computed from it) in EVERY wave before any wave stores,
+// because with G == S the dense pass overwrites logits that another wave's entries point at (kd_bwd_kernel's barrier,
+// same place).  The dense pass itself is row_sweep's case of a body that stores to its own chunk.  The second barrier
+// (with its vmcnt(0)) completes every dense store of the row before the fix-up stores the at most K on-support elements.
+template <typename T, bool T2, typename Stats, typename OnW, typename Off>
+SD_DEV void tk_bwd_row(const T* S, const _Float16* __restrict__ topv, const int32_t* __restrict__ topi,
+                       const int64_t* __restrict__ labels, const Stats& st, const float* __restrict__ loss_out,
+                       const float* __restrict__ grad_out, T* G, int V, int K, float temperature, float alpha, float beta,
+                       float gs, float scale, float d0c, OnW&& on_w, Off&& off) {
   constexpr int E = KMAX / GJ_NF;  // entries per thread
   __shared__ float sc[32];
   __shared__ __attribute__((aligned(16))) float k_p[KMAX];
   __shared__ __attribute__((aligned(16))) int k_i[KMAX];
   const int row = blockIdx.x;
-  const GjsdTopkStats st = stats[row];
   T* gr = G + (long)row * V;
   if (st.valid == 0.f) return zero_row<T, GJ_NF>(gr, V);
   const float invT = 1.f / temperature;
   const float k1 = GJ_LOG2E, kT = invT * k1;
   const float N = loss_out[4];
   const float go = grad_out ? grad_out[0] : 1.f;
-  const float a1 = go * alpha / N;                                                      // * (softmax(s) - e_y)
-  const float aT = go * (1.f - alpha) * temperature / N * ((1.f - beta) * GJ_LN2);  // * q (d - c), d - c in log2 units
+  const float a1 = go * alpha / N;  // * (softmax(s) - e_y)
+  const float aT = go * (1.f - alpha) * temperature / N * gs;
   const long y = labels[row];
   const T* s = S + (long)row * V;
   const float A0 = -st.lsT, L1 = -st.ls1;
@@ -1073,52 +1087,59 @@ __global__ __launch_bounds__(GJ_NF) void gjsd_topk_bwd_kernel(const T* S, const 
   float fo[E];
 #pragma unroll
   for (int u = 0; u < E; ++u) {
-    const int k = threadIdx.x + u * GJ_NF;
-    bool first = false;
-    const int idx = k < K ? k_i[k] : -1;
-    const float P = tk_mass(k_i, k_p, K, k, idx, first);
+    int idx;
+    float P;
     fi[u] = -1;
     fo[u] = 0.f;
-    if (first && P >= GJ_FLT_MIN) {
+    if (tk_entry(k_i, k_p, K, threadIdx.x + u * GJ_NF, scale, idx, P)) {
       const float sj = (float)s[idx];
       float q, a2, lm;
       tk_term(sj, P, st.m, kT, A0, beta, q, a2, lm);
-      const float w = q > 0.f ? q * ((a2 - lm) - st.c) : 0.f;
       fi[u] = idx;
-      fo[u] = __builtin_fmaf(a1, soft1(sj, q), aT * w) - ((long)idx == y ? a1 : 0.f);
+      fo[u] = __builtin_fmaf(a1, soft1(sj, q), aT * on_w(q, a2, lm, P)) - ((long)idx == y ? a1 : 0.f);
     }
   }
-  // Every gather of s above has returned (fo[] is computed from it) in EVERY wave before any wave stores: with G == S the
-  // dense pass below overwrites logits that another wave's entries point at (kd_bwd_kernel's barrier, same place).
   __syncthreads();
-  const float w0 = aT * (-__builtin_amdgcn_logf(1.f - beta) - st.c);  // off S: d_j = d0 = -log2(1 - beta)
+  const float w0 = aT * d0c;
   row_sweep<T, GJ_NF, false>(s, (const T*)nullptr, V, [&](int c, const float* f, const float*) {
     float o[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      const float q = __builtin_amdgcn_exp2f(__builtin_fmaf(f[e] - st.m, kT, A0));
-      o[e] = __builtin_fmaf(a1, soft1(f[e], q), w0 * q);
+      const float a2 = __builtin_fmaf(f[e] - st.m, kT, A0);
+      const float q = __builtin_amdgcn_exp2f(a2);
+      o[e] = __builtin_fmaf(a1, soft1(f[e], q), w0 * off(f[e], q, a2));
     }
     if (y >= c && y < c + 8) o[y - c] -= a1;
     Ld8<T>::store(gr + c, o);
   });
-  __syncthreads();  // every dense store of this row is complete (vmcnt(0) + barrier) before the fix-up
+  __syncthreads();
 #pragma unroll
   for (int u = 0; u < E; ++u)
     if (fi[u] >= 0) gr[fi[u]] = (T)fo[u];
 }
 
+// tk_bwd_row with the JSD's weights, in log2 units: on S q (d - c), d = log2 q - log2 m; off S every element has
+// d_0 = -log2(1 - beta)
+template <typename T, bool T2>
+__global__ __launch_bounds__(GJ_NF) void gjsd_topk_bwd_kernel(const T* S, const _Float16* __restrict__ topv,
+                                                              const int32_t* __restrict__ topi,
+                                                              const int64_t* __restrict__ labels,
+                                                              const GjsdTopkStats* __restrict__ stats,
+                                                              const float* __restrict__ loss_out,
+                                                              const float* __restrict__ grad_out, T* G, int V, int K,
+                                                              float temperature, float alpha, float beta) {
+  const GjsdTopkStats st = stats[blockIdx.x];
+  tk_bwd_row<T, T2>(S, topv, topi, labels, st, loss_out, grad_out, G, V, K, temperature, alpha, beta, (1.f - beta) * GJ_LN2,
+                    1.f, -__builtin_amdgcn_logf(1.f - beta) - st.c,
+                    [&](float q, float a2, float lm, float) { return q > 0.f ? q * ((a2 - lm) - st.c) : 0.f; },
+                    [](float, float q, float) { return q; });
+}
+
 int gjsd_topk_check(const void* S, const void* topv, const void* topi, const int64_t* labels, const void* stats,
-                    const float* out, int R, int V, int K, float temperature, float beta, int dtype) {
-  if (R <= 0 || V <= 0 || !S || !labels || !stats || !out) return SD_ERR_SHAPE;
-  if (!topv || !topi) return SD_ERR_NO_TEACHER;
-  if (K <= 0 || K > KMAX) return SD_ERR_SHAPE;
-  if (V & 7) return SD_ERR_ALIGN;
-  if ((uintptr_t)S & 15) return SD_ERR_ALIGN;
-  if (dtype != SD_DTYPE_BF16 && dtype != SD_DTYPE_F32) return SD_ERR_UNSUPPORTED;
-  if (!(temperature > 0.f) || !(temperature < INFINITY)) return SD_ERR_SHAPE;  // NaN fails both comparisons
-  if (!(beta > 0.f && beta < 1.f)) return SD_ERR_SHAPE;                          // likewise
-  return 0;
+                    const float* out, int R, int V, int K, float temperature, float beta, int dtype, bool G = false,
+                    const void* grad = nullptr) {
+  return gjsd_check(S, nullptr, labels, stats, out, R, V, temperature, beta, true, dtype,
+                    (!topv || !topi) ? SD_ERR_NO_TEACHER : (K <= 0 || K > KMAX) ? SD_ERR_SHAPE : 0, 0, G, grad);
 }
 
 }  // namespace
@@ -1131,49 +1152,36 @@ extern "C" int sd_gjsd_topk_fwd_rows(const void* student_logits, const void* top
   if (int e = gjsd_topk_check(student_logits, top_k_v, top_k_i, row_labels, row_stats, loss_out, R, V, K, temperature, beta, dtype))
     return e;
   hipStream_t st = (hipStream_t)stream;
-  if (int e = by_dtype(dtype, [&](auto tt) -> int {
-        typedef SD_TAG_TYPE(tt) T;
-        SdProfScope prof(SD_K_LOSS_FWD, (double)R * V * sizeof(T), st);
-        // 1024 threads only where the K teacher entries do not fit one thread each at 512 (kd_fwd_kernel's rule)
-        by_flag(temperature == 2.0f, [&](auto t2) {
-          by_flag(K > 512, [&](auto wide) {
-            constexpr int NF = SD_FLAG(wide) ? 1024 : 512;
-            SD_PROF_LABEL("gjsd_topk_fwd_kernel<%s, %s, %d>", type_name(sizeof(T)), flag_name(SD_FLAG(t2)), NF);
-            hipLaunchKernelGGL((gjsd_topk_fwd_kernel<T, SD_FLAG(t2), NF>), dim3(R), dim3(NF), 0, st, (const T*)student_logits,
-                               (const _Float16*)top_k_v, (const int32_t*)top_k_i, row_labels, (GjsdTopkStats*)row_stats, V, K,
-                               temperature, beta);
-          });
-        });
-        SD_CHECK_LAUNCH();
-        return 0;
-      }))
-    return e;
-  hipLaunchKernelGGL((kd_finalize_kernel<GjsdTopkStats, true>), dim3(1), dim3(NT), 0, st, (const GjsdTopkStats*)row_stats,
-                     loss_out, R, temperature, alpha, 0);
-  SD_CHECK_LAUNCH();
-  return 0;
+  return rows_launch(dtype, SD_K_LOSS_FWD, (double)R * V, st, false, [&](auto tt) {
+    typedef SD_TAG_TYPE(tt) T;
+    by_flag(temperature == 2.0f, [&](auto t2) {
+      by_threads(K, [&](auto nf) {
+        constexpr int NF = SD_FLAG(nf);
+        SD_PROF_LABEL("gjsd_topk_fwd_kernel<%s, %s, %d>", type_name(sizeof(T)), flag_name(SD_FLAG(t2)), NF);
+        hipLaunchKernelGGL((gjsd_topk_fwd_kernel<T, SD_FLAG(t2), NF>), dim3(R), dim3(NF), 0, st, (const T*)student_logits,
+                           (const _Float16*)top_k_v, (const int32_t*)top_k_i, row_labels, (GjsdTopkStats*)row_stats, V, K,
+                           temperature, beta);
+      });
+    });
+  }, finalize<GjsdTopkStats, true>(row_stats, loss_out, R, temperature, alpha, 0, st));
 }
 
 extern "C" int sd_gjsd_topk_bwd_rows(const void* student_logits, const void* top_k_v, const void* top_k_i,
                                      const int64_t* row_labels, const void* row_stats, const float* loss_out,
                                      const float* grad_total, void* grad_logits, int R, int V, int K, float temperature,
                                      float alpha, float beta, int dtype, void* stream) {
-  if (int e = gjsd_topk_check(student_logits, top_k_v, top_k_i, row_labels, row_stats, loss_out, R, V, K, temperature, beta, dtype))
+  if (int e = gjsd_topk_check(student_logits, top_k_v, top_k_i, row_labels, row_stats, loss_out, R, V, K, temperature, beta, dtype,
+                              true, grad_logits))
     return e;
-  if (!grad_logits) return SD_ERR_SHAPE;
-  if ((uintptr_t)grad_logits & 15) return SD_ERR_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-  return by_dtype(dtype, [&](auto tt) -> int {
+  return rows_launch(dtype, SD_K_LOSS_BWD, (double)R * V * 2, st, [&](auto tt) {
     typedef SD_TAG_TYPE(tt) T;
-    SdProfScope prof(SD_K_LOSS_BWD, (double)R * V * sizeof(T) * 2, st);
     by_flag(temperature == 2.0f, [&](auto t2) {
       SD_PROF_LABEL("gjsd_topk_bwd_kernel<%s, %s>", type_name(sizeof(T)), flag_name(SD_FLAG(t2)));
       hipLaunchKernelGGL((gjsd_topk_bwd_kernel<T, SD_FLAG(t2)>), dim3(R), dim3(GJ_NF), 0, st, (const T*)student_logits,
                          (const _Float16*)top_k_v, (const int32_t*)top_k_i, row_labels, (const GjsdTopkStats*)row_stats,
                          loss_out, grad_total, (T*)grad_logits, V, K, temperature, alpha, beta);
     });
-    SD_CHECK_LAUNCH();
-    return 0;
   });
 }
 
@@ -1230,19 +1238,15 @@ __global__ __launch_bounds__(NF) void gjsd_tail_fwd_kernel(const T* __restrict__
   const float tau_in = tail[row];
   float hv = 0.f, hc = 0.f, mv = 0.f, sv = 0.f;
   if (y < 0 || y >= V || !tail_ok(tau_in) ||
-      !tk_renorm<NF, 1, false>(topv, topi, (long)row * K, K, V, kT, y, sc, k_i, k_p, hv, hc, mv, sv)) {
-    if (threadIdx.x == 0) stats[row] = GjsdTailStats{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    return;
-  }
+      !tk_renorm<NF, 1, false>(topv, topi, (long)row * K, K, V, kT, y, sc, k_i, k_p, hv, hc, mv, sv))
+    return masked_row(stats, row);
   const float tau = fmaxf(tau_in, GJ_TAIL_MIN);
   const T* s = S + (long)row * V;
   // ---- the support: one thread per entry; the first entry of an index owns its element of S and marks it
   row_bits_clear<NF>(row_bits, V);
-  const int k = threadIdx.x;
-  bool first = false;
-  const int idx = k < K ? k_i[k] : -1;
-  const float P = (1.f - tau) * tk_mass(k_i, k_p, K, k, idx, first);
-  const bool on = first && P >= GJ_FLT_MIN;
+  int idx;
+  float P;
+  const bool on = tk_entry(k_i, k_p, K, threadIdx.x, 1.f - tau, idx, P);
   __syncthreads();
   if (on) row_bits_set(row_bits, idx);
   __syncthreads();
@@ -1257,12 +1261,7 @@ __global__ __launch_bounds__(NF) void gjsd_tail_fwd_kernel(const T* __restrict__
     if (cm == -INFINITY) return;  // a chunk of members only
     online_raise<T2>(cm, invT, m0, s1, sT);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float df = g[e] - m0;
-      const float q = __builtin_amdgcn_exp2f(df * kT);
-      sT += q;
-      s1 += T2 ? q * q : __builtin_amdgcn_exp2f(df * k1);
-    }
+    for (int e = 0; e < 8; ++e) unfolded_step<T2>(g[e], m0, kT, k1, s1, sT);
   });
   block_merge<NF>(m0, s1, sT, invT, sc);
   const float ls0 = __builtin_amdgcn_logf(sT);  // v_log_f32: log2
@@ -1311,7 +1310,9 @@ __global__ __launch_bounds__(NF) void gjsd_tail_fwd_kernel(const T* __restrict__
     stats[row] = GjsdTailStats{m, ls1, lsT, Sq, 1.f, (m - (float)s[y]) + ls1 * GJ_LN2, D, hv, hc, mv, sv, lq0};
 }
 
-// One read of the student row, one write of the gradient; G may alias S (gjsd_topk_bwd_kernel's two barriers).
+// tk_bwd_row with P scaled by 1 - tau and the weights of the K + 1 outcomes.  Forward KL: q - P on S, and off S
+// q_j - tau q_j / q_0 = q_j - exp2(log2 q_j + dl), in natural units.  The others, in log2 units: q (d - c) on S with
+// d = log2 q - log2 P (reverse KL) or log2 q - log2 m (JSD), and the row's d_0 - c times q_j off S.
 template <typename T, bool T2, int MODE>
 __global__ __launch_bounds__(GJ_NF) void gjsd_tail_bwd_kernel(const T* S, const _Float16* __restrict__ topv,
                                                               const int32_t* __restrict__ topi,
@@ -1321,97 +1322,35 @@ __global__ __launch_bounds__(GJ_NF) void gjsd_tail_bwd_kernel(const T* S, const 
                                                               const float* __restrict__ loss_out,
                                                               const float* __restrict__ grad_out, T* G, int V, int K,
                                                               float temperature, float alpha, float beta) {
-  constexpr int E = KMAX / GJ_NF;  // entries per thread
   constexpr bool FKL = MODE == SD_DIV_FORWARD_KL, JSD = MODE == SD_DIV_JSD;
-  __shared__ float sc[32];
-  __shared__ __attribute__((aligned(16))) float k_p[KMAX];
-  __shared__ __attribute__((aligned(16))) int k_i[KMAX];
-  const int row = blockIdx.x;
-  const GjsdTailStats st = stats[row];
-  T* gr = G + (long)row * V;
-  if (st.valid == 0.f) return zero_row<T, GJ_NF>(gr, V);
-  const float invT = 1.f / temperature;
-  const float k1 = GJ_LOG2E, kT = invT * k1;
-  const float N = loss_out[4];
-  const float go = grad_out ? grad_out[0] : 1.f;
-  const float a1 = go * alpha / N;  // * (softmax(s) - e_y)
-  // * q (d - c), d - c in log2 units (the forward KL: * (q - P))
-  const float aT = go * (1.f - alpha) * temperature / N * (FKL ? 1.f : (JSD ? (1.f - beta) * GJ_LN2 : GJ_LN2));
-  const long y = labels[row];
-  const T* s = S + (long)row * V;
-  const float A0 = -st.lsT, L1 = -st.ls1;
-  const float r1 = T2 ? __builtin_amdgcn_exp2f(2.f * st.lsT - st.ls1) : 0.f;  // softmax(s) = q^2 r1 at T == 2
-  auto soft1 = [&](float f, float q) { return T2 ? q * q * r1 : __builtin_amdgcn_exp2f(__builtin_fmaf(f - st.m, k1, L1)); };
-  const float tau = fmaxf(tail[row], GJ_TAIL_MIN);  // (a valid row's tau passed tail_ok in the forward)
+  const GjsdTailStats st = stats[blockIdx.x];
+  const float tau = fmaxf(tail[blockIdx.x], GJ_TAIL_MIN);  // (a valid row's tau passed tail_ok in the forward)
   const float lt = __builtin_amdgcn_logf(tau);
-  float hv, hc, mv = st.mv, sv = st.sv;  // the forward's renormalisation (a valid row keeps an entry)
-  tk_renorm<GJ_NF, E, true>(topv, topi, (long)row * K, K, V, kT, y, sc, k_i, k_p, hv, hc, mv, sv);
-  int fi[E];
-  float fo[E];
-#pragma unroll
-  for (int u = 0; u < E; ++u) {
-    const int k = threadIdx.x + u * GJ_NF;
-    bool first = false;
-    const int idx = k < K ? k_i[k] : -1;
-    const float P = (1.f - tau) * tk_mass(k_i, k_p, K, k, idx, first);
-    fi[u] = -1;
-    fo[u] = 0.f;
-    if (first && P >= GJ_FLT_MIN) {
-      const float sj = (float)s[idx];
-      float q, a2, lm;
-      tk_term(sj, P, st.m, kT, A0, beta, q, a2, lm);
-      float w;
-      if constexpr (FKL) {
-        w = q - P;
-      } else {
-        const float ref = JSD ? lm : __builtin_amdgcn_logf(P);
-        w = q > 0.f ? q * ((a2 - ref) - st.c) : 0.f;
-      }
-      fi[u] = idx;
-      fo[u] = __builtin_fmaf(a1, soft1(sj, q), aT * w) - ((long)idx == y ? a1 : 0.f);
-    }
-  }
-  // Every gather of s above has returned in EVERY wave before any wave stores (gjsd_topk_bwd_kernel's barrier, same place)
-  __syncthreads();
-  // off S: the forward KL subtracts tau q_j / q_0 = exp2(log2 q_j + dl); the others scale q_j by the row's d_0 - c
   const float dl = lt - st.lq0;
-  const float w0 = FKL ? 0.f : aT * ((st.lq0 - (JSD ? tail_lm0(st.lq0, lt, beta) : lt)) - st.c);
-  row_sweep<T, GJ_NF, false>(s, (const T*)nullptr, V, [&](int c, const float* f, const float*) {
-    float o[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float a2 = __builtin_fmaf(f[e] - st.m, kT, A0);
-      const float q = __builtin_amdgcn_exp2f(a2);
-      if constexpr (FKL)
-        o[e] = __builtin_fmaf(a1, soft1(f[e], q), aT * (q - __builtin_amdgcn_exp2f(a2 + dl)));
-      else
-        o[e] = __builtin_fmaf(a1, soft1(f[e], q), w0 * q);
-    }
-    if (y >= c && y < c + 8) o[y - c] -= a1;
-    Ld8<T>::store(gr + c, o);
-  });
-  __syncthreads();  // every dense store of this row is complete (vmcnt(0) + barrier) before the fix-up
-#pragma unroll
-  for (int u = 0; u < E; ++u)
-    if (fi[u] >= 0) gr[fi[u]] = (T)fo[u];
+  tk_bwd_row<T, T2>(S, topv, topi, labels, st, loss_out, grad_out, G, V, K, temperature, alpha, beta,
+                    FKL ? 1.f : (JSD ? (1.f - beta) * GJ_LN2 : GJ_LN2), 1.f - tau,
+                    FKL ? 1.f : (st.lq0 - (JSD ? tail_lm0(st.lq0, lt, beta) : lt)) - st.c,
+                    [&](float q, float a2, float lm, float P) {
+                      if constexpr (FKL) {
+                        return q - P;
+                      } else {
+                        const float ref = JSD ? lm : __builtin_amdgcn_logf(P);
+                        return q > 0.f ? q * ((a2 - ref) - st.c) : 0.f;
+                      }
+                    },
+                    [&](float, float q, float a2) { return FKL ? q - __builtin_amdgcn_exp2f(a2 + dl) : q; });
 }
 
 constexpr int GJ_TAIL_VMAX = 458752;  // the forward's V-bit bitmap beside its other LDS: 56 KB of the 64 KB
 
 int gjsd_tail_check(const void* S, const void* topv, const void* topi, const float* tail, const int64_t* labels,
                     const void* stats, const float* out, int R, int V, int K, float temperature, float beta, int mode,
-                    int dtype) {
-  if (R <= 0 || V <= 0 || !S || !labels || !stats || !out) return SD_ERR_SHAPE;
-  if (!topv || !topi || !tail) return SD_ERR_NO_TEACHER;
-  if (K <= 0 || K > KMAX || K >= V) return SD_ERR_SHAPE;  // K < V: an off-support element always exists
-  if (V & 7) return SD_ERR_ALIGN;
-  if ((uintptr_t)S & 15) return SD_ERR_ALIGN;
-  if (dtype != SD_DTYPE_BF16 && dtype != SD_DTYPE_F32) return SD_ERR_UNSUPPORTED;
-  if (mode != SD_DIV_FORWARD_KL && mode != SD_DIV_REVERSE_KL && mode != SD_DIV_JSD) return SD_ERR_UNSUPPORTED;
-  if (V > GJ_TAIL_VMAX) return SD_ERR_UNSUPPORTED;
-  if (!(temperature > 0.f) || !(temperature < INFINITY)) return SD_ERR_SHAPE;   // NaN fails both comparisons
-  if (mode == SD_DIV_JSD && !(beta > 0.f && beta < 1.f)) return SD_ERR_SHAPE;    // likewise
-  return 0;
+                    int dtype, bool G = false, const void* grad = nullptr) {
+  const bool known = mode == SD_DIV_FORWARD_KL || mode == SD_DIV_REVERSE_KL || mode == SD_DIV_JSD;
+  return gjsd_check(S, nullptr, labels, stats, out, R, V, temperature, beta, mode == SD_DIV_JSD, dtype,
+                    (!topv || !topi || !tail) ? SD_ERR_NO_TEACHER
+                    : (K <= 0 || K > KMAX || K >= V) ? SD_ERR_SHAPE : 0,  // K < V: an off-support element always exists
+                    (!known || V > GJ_TAIL_VMAX) ? SD_ERR_UNSUPPORTED : 0, G, grad);
 }
 
 }  // namespace
@@ -1426,27 +1365,18 @@ extern "C" int sd_gjsd_tail_fwd_rows(const void* student_logits, const void* top
                               temperature, beta, mode, dtype))
     return e;
   hipStream_t st = (hipStream_t)stream;
-  if (int e = by_dtype(dtype, [&](auto tt) -> int {
-        typedef SD_TAG_TYPE(tt) T;
-        SdProfScope prof(SD_K_LOSS_FWD, (double)R * V * sizeof(T), st);
-        // 1024 threads only where the K teacher entries do not fit one thread each at 512 (kd_fwd_kernel's rule)
-        by_flag(temperature == 2.0f, [&](auto t2) {
-          by_flag(K > 512, [&](auto wide) {
-            constexpr int NF = SD_FLAG(wide) ? 1024 : 512;
-            SD_PROF_LABEL("gjsd_tail_fwd_kernel<%s, %s, %d>", type_name(sizeof(T)), flag_name(SD_FLAG(t2)), NF);
-            hipLaunchKernelGGL((gjsd_tail_fwd_kernel<T, SD_FLAG(t2), NF>), dim3(R), dim3(NF), row_bits_bytes(V), st,
-                               (const T*)student_logits, (const _Float16*)top_k_v, (const int32_t*)top_k_i, top_k_tail,
-                               row_labels, (GjsdTailStats*)row_stats, V, K, temperature, beta, mode);
-          });
-        });
-        SD_CHECK_LAUNCH();
-        return 0;
-      }))
-    return e;
-  hipLaunchKernelGGL((kd_finalize_kernel<GjsdTailStats, true>), dim3(1), dim3(NT), 0, st, (const GjsdTailStats*)row_stats,
-                     loss_out, R, temperature, alpha, 0);
-  SD_CHECK_LAUNCH();
-  return 0;
+  return rows_launch(dtype, SD_K_LOSS_FWD, (double)R * V, st, false, [&](auto tt) {
+    typedef SD_TAG_TYPE(tt) T;
+    by_flag(temperature == 2.0f, [&](auto t2) {
+      by_threads(K, [&](auto nf) {
+        constexpr int NF = SD_FLAG(nf);
+        SD_PROF_LABEL("gjsd_tail_fwd_kernel<%s, %s, %d>", type_name(sizeof(T)), flag_name(SD_FLAG(t2)), NF);
+        hipLaunchKernelGGL((gjsd_tail_fwd_kernel<T, SD_FLAG(t2), NF>), dim3(R), dim3(NF), row_bits_bytes(V), st,
+                           (const T*)student_logits, (const _Float16*)top_k_v, (const int32_t*)top_k_i, top_k_tail,
+                           row_labels, (GjsdTailStats*)row_stats, V, K, temperature, beta, mode);
+      });
+    });
+  }, finalize<GjsdTailStats, true>(row_stats, loss_out, R, temperature, alpha, 0, st));
 }
 
 extern "C" int sd_gjsd_tail_bwd_rows(const void* student_logits, const void* top_k_v, const void* top_k_i,
@@ -1454,14 +1384,11 @@ extern "C" int sd_gjsd_tail_bwd_rows(const void* student_logits, const void* top
                                      const float* loss_out, const float* grad_total, void* grad_logits, int R, int V, int K,
                                      float temperature, float alpha, float beta, int mode, int dtype, void* stream) {
   if (int e = gjsd_tail_check(student_logits, top_k_v, top_k_i, top_k_tail, row_labels, row_stats, loss_out, R, V, K,
-                              temperature, beta, mode, dtype))
+                              temperature, beta, mode, dtype, true, grad_logits))
     return e;
-  if (!grad_logits) return SD_ERR_SHAPE;
-  if ((uintptr_t)grad_logits & 15) return SD_ERR_ALIGN;
   hipStream_t st = (hipStream_t)stream;
-  return by_dtype(dtype, [&](auto tt) -> int {
+  return rows_launch(dtype, SD_K_LOSS_BWD, (double)R * V * 2, st, [&](auto tt) {
     typedef SD_TAG_TYPE(tt) T;
-    SdProfScope prof(SD_K_LOSS_BWD, (double)R * V * sizeof(T) * 2, st);
     by_flag(temperature == 2.0f, [&](auto t2) {
       auto go = [&](auto md) {
         constexpr int MODE = decltype(md)::value;
@@ -1475,7 +1402,6 @@ extern "C" int sd_gjsd_tail_bwd_rows(const void* student_logits, const void* top
       else if (mode == SD_DIV_REVERSE_KL) go(std::integral_constant<int, SD_DIV_REVERSE_KL>{});
       else go(std::integral_constant<int, SD_DIV_JSD>{});
     });
-    SD_CHECK_LAUNCH();
-    return 0;
   });
 }
+

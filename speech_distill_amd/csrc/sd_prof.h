@@ -20,7 +20,9 @@ struct SdProfScope {
   SdProfScope(int kind, double work, hipStream_t s) : st(s) {
     if (sd_prof_enabled) sd_prof_open(kind, work, s, &slot);
   }
-  ~SdProfScope() {
+  void close() {  // ends the record before the scope does (a second call, and the destructor after one, do nothing)
     if (slot >= 0) sd_prof_close(slot, st);
+    slot = -1;
   }
+  ~SdProfScope() { close(); }
 };

@@ -1,6 +1,6 @@
 // Device functions shared by the kernels that stream whole vocabulary rows (sd_loss.hip, sd_topk.hip): the 8-element
 // load / convert / store, the prefetched row sweep, the online max / sum-exp step and its cross-thread merge, and the
-// zero fill of a masked row's gradient.  Each is stated once; DESIGN.md section 12d lists who calls what.
+// zero fill of a masked row's gradient.  Each is stated once; DESIGN.md sections 12a and 12e list who calls what.
 #pragma once
 #include "sd_common.cuh"
 

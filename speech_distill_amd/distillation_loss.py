@@ -48,24 +48,20 @@ class DistillationLoss(nn.Module):
                 speech_token_mask=None, teacher_top_k_tail=None):
         if teacher_logits is None and (teacher_top_k_v is None or teacher_top_k_i is None):
             raise ValueError("Either teacher_logits or top_k must be provided")
-        if self.divergence == ops.TOPK_DIVERGENCE or self.divergence in ops.TAIL_DIVERGENCES:
-            # as below, with the top-K rows selected the way the trainer selects them for the forward KL
-            self._need_topk(teacher_logits, teacher_top_k_v, teacher_top_k_i)
+        if self.divergence != "forward_kl":
+            # eval / return_outputs path: select the rows as the trainer does and gather them (one copy of R rows)
+            self._need_form(teacher_logits, teacher_top_k_v, teacher_top_k_i)
             rows, row_labels = ops.loss_rows(labels, speech_token_mask)
             V = student_logits.shape[-1]
+            if ops.takes_dense_teacher(self.divergence):
+                return self.forward_rows(student_logits.reshape(-1, V)[rows], row_labels,
+                                         teacher_logits=teacher_logits.detach().reshape(-1, V)[rows])
             pick = (lambda x: x.to(rows.device).reshape(-1, x.size(-1))[rows])
             tail = {}
             if self.divergence in ops.TAIL_DIVERGENCES:
                 tail = {"teacher_top_k_tail": self._tail(teacher_top_k_v, teacher_top_k_tail).to(rows.device).reshape(-1)[rows]}
             return self.forward_rows(student_logits.reshape(-1, V)[rows], row_labels,
                                      teacher_top_k_v=pick(teacher_top_k_v), teacher_top_k_i=pick(teacher_top_k_i), **tail)
-        if self.divergence != "forward_kl":
-            # eval / return_outputs path: select the rows as the trainer does and gather them (one copy of R rows)
-            self._need_dense(teacher_logits)
-            rows, row_labels = ops.loss_rows(labels, speech_token_mask)
-            V = student_logits.shape[-1]
-            return self.forward_rows(student_logits.reshape(-1, V)[rows], row_labels,
-                                     teacher_logits=teacher_logits.detach().reshape(-1, V)[rows])
         if not student_logits.is_contiguous():
             student_logits = student_logits.contiguous()
         if teacher_logits is not None:
@@ -84,40 +80,33 @@ class DistillationLoss(nn.Module):
             raise ValueError("Either teacher_logits or top_k must be provided")
         if teacher_logits is not None:
             teacher_logits = teacher_logits.detach()
-        if self.divergence == ops.TOPK_DIVERGENCE:
-            self._need_topk(teacher_logits, teacher_top_k_v, teacher_top_k_i)
-            total, out = GJSDTopKLossRowsFn.apply(student_logits.contiguous(), row_labels, teacher_top_k_v, teacher_top_k_i,
-                                                  self.temperature, self.alpha, self.beta,
-                                                  self.inplace_grad and student_logits.requires_grad)
-            return total, out[1], out[2], out[3]
-        if self.divergence in ops.TAIL_DIVERGENCES:
-            self._need_topk(teacher_logits, teacher_top_k_v, teacher_top_k_i)
-            total, out = GJSDTailLossRowsFn.apply(student_logits.contiguous(), row_labels, teacher_top_k_v, teacher_top_k_i,
+        self._need_form(teacher_logits, teacher_top_k_v, teacher_top_k_i)
+        s, inplace = student_logits.contiguous(), self.inplace_grad and student_logits.requires_grad
+        form = ops.DIVERGENCE_TABLE[self.divergence].teacher
+        if form == "topk":
+            total, out = GJSDTopKLossRowsFn.apply(s, row_labels, teacher_top_k_v, teacher_top_k_i, self.temperature,
+                                                  self.alpha, self.beta, inplace)
+        elif form == "topk_tail":
+            total, out = GJSDTailLossRowsFn.apply(s, row_labels, teacher_top_k_v, teacher_top_k_i,
                                                   self._tail(teacher_top_k_v, teacher_top_k_tail), self.temperature,
-                                                  self.alpha, self.beta, self.divergence,
-                                                  self.inplace_grad and student_logits.requires_grad)
-            return total, out[1], out[2], out[3]
-        if self.divergence != "forward_kl":
-            self._need_dense(teacher_logits)
-            total, out = GJSDLossRowsFn.apply(student_logits.contiguous(), row_labels, teacher_logits, self.temperature,
-                                              self.alpha, self.beta, self.divergence,
-                                              self.inplace_grad and student_logits.requires_grad)
-            return total, out[1], out[2], out[3]
-        total, out = KDLossRowsFn.apply(student_logits.contiguous(), row_labels, teacher_logits, teacher_top_k_v,
-                                        teacher_top_k_i, self.temperature, self.alpha,
-                                        self.inplace_grad and student_logits.requires_grad)
+                                                  self.alpha, self.beta, self.divergence, inplace)
+        elif form == "dense":
+            total, out = GJSDLossRowsFn.apply(s, row_labels, teacher_logits, self.temperature, self.alpha, self.beta,
+                                              self.divergence, inplace)
+        else:
+            total, out = KDLossRowsFn.apply(s, row_labels, teacher_logits, teacher_top_k_v, teacher_top_k_i,
+                                            self.temperature, self.alpha, inplace)
         return total, out[1], out[2], out[3]
 
-    def _need_dense(self, teacher_logits):
-        if teacher_logits is None:
+    def _need_form(self, teacher_logits, teacher_top_k_v, teacher_top_k_i):
+        """ValueError unless the teacher comes in the form the divergence is defined on (``forward_kl`` takes either)."""
+        if ops.takes_dense_teacher(self.divergence) and teacher_logits is None:
             raise ValueError(f"divergence={self.divergence!r} needs dense teacher_logits: a top-K teacher defines the "
                              "teacher distribution on K entries only")
-
-    def _need_topk(self, teacher_logits, teacher_top_k_v, teacher_top_k_i):
-        if teacher_logits is not None or teacher_top_k_v is None or teacher_top_k_i is None:
-            dense = self.divergence[:-len("_tail")] if self.divergence in ops.TAIL_DIVERGENCES else "jsd"
+        if ops.takes_topk_teacher(self.divergence) and (teacher_logits is not None or teacher_top_k_v is None
+                                                         or teacher_top_k_i is None):
             raise ValueError(f"divergence={self.divergence!r} takes a top-K teacher (teacher_top_k_v, teacher_top_k_i); "
-                             f"for dense teacher_logits use divergence={dense!r}")
+                             f"for dense teacher_logits use divergence={ops.dense_name(self.divergence)!r}")
 
     def _tail(self, teacher_top_k_v, teacher_top_k_tail):
         """The tail of a ``_tail`` divergence: the caller's, or at T = 1 the one the stored log-probs imply."""

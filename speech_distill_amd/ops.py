@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -348,6 +349,65 @@ def tail_from_logprobs(top_v):
     return (1.0 - top_v.to(torch.float32).exp().sum(-1)).clamp_(0.0, 1.0)
 
 
+# The loss autograd functions below are declarations over one forward and one backward body.  Every C entry takes
+#   <stem>_fwd<suffix>(student, *teacher, labels, *forward-only pointers, stats, out, *dims, *scalars, dtype, stream)
+#   <stem>_bwd<suffix>(student, *teacher, labels, stats, out, grad_total, grad_logits, *dims, *scalars, dtype, stream)
+def _loss_forward(ctx, stem, suffix, s, dt, labels, teacher, fwd_only, dims, scalars, inplace_grad, stats_dims, n_out=8,
+                  zeros_without_rows=False):
+    """``teacher``: the tensors of the teacher form (None where the form has none), ``fwd_only``: what only the forward
+    reads (a speech mask, a divisor).  ``zeros_without_rows``: with dims[0] == 0 nothing is launched and the zeros returned
+    are connected to autograd (the C entries refuse R <= 0; the loss of no row is 0 and so is its (empty) gradient)."""
+    lib = load_lib()
+    launch = not (zeros_without_rows and dims[0] == 0)
+    ctx.cfg = (stem, suffix, dims, scalars, dt, bool(inplace_grad), launch)
+    if launch:
+        stats = torch.empty(getattr(lib, stem + "_stats_bytes")(*stats_dims), dtype=torch.uint8, device=s.device)
+        out = torch.empty(n_out, dtype=torch.float32, device=s.device)
+        name = f"{stem}_fwd{suffix}"
+        check(getattr(lib, name)(s.data_ptr(), *map(_p, teacher), labels.data_ptr(), *map(_p, fwd_only), stats.data_ptr(),
+                                 out.data_ptr(), *dims, *scalars, dt, _stream()), name)
+    else:
+        stats = out = torch.zeros(n_out, dtype=torch.float32, device=s.device)
+    ctx.save_for_backward(s, labels, stats, out, *teacher)
+    ctx.mark_non_differentiable(out)
+    return out[0].clone(), out
+
+
+def _loss_backward(ctx, g_total, n_inputs):
+    """-> (the gradient of the logits, written over them if the forward was told so, None for every other input)."""
+    s, labels, stats, out, *teacher = ctx.saved_tensors
+    stem, suffix, dims, scalars, dt, inplace, launch = ctx.cfg
+    grad = s if inplace else torch.empty_like(s)
+    if launch:
+        go = g_total.to(torch.float32).reshape(1).contiguous()
+        name = f"{stem}_bwd{suffix}"
+        check(getattr(load_lib(), name)(s.data_ptr(), *map(_p, teacher), labels.data_ptr(), stats.data_ptr(), out.data_ptr(),
+                                        go.data_ptr(), grad.data_ptr(), *dims, *scalars, dt, _stream()), name)
+    return (grad,) + (None,) * (n_inputs - 1)
+
+
+def _dense_teacher(s, teacher_logits):
+    teacher_logits = _need(teacher_logits.to(s.dtype), None, "teacher_logits")
+    if teacher_logits.shape != s.shape:
+        raise ValueError(f"teacher_logits {tuple(teacher_logits.shape)} != student_logits {tuple(s.shape)}")
+    return teacher_logits
+
+
+def _topk_teacher(s, *arrays):
+    """(top_v, top_i[, top_tail]) on the student's device as fp16, int32[, fp32] (distillation_loss.py:78-91 moves the
+    pre-extracted arrays there)."""
+    return tuple(a.to(device=s.device, dtype=d).contiguous() for a, d in zip(arrays, (torch.float16, torch.int32, torch.float32)))
+
+
+def _kd_teacher(s, teacher_logits, top_v, top_i):
+    """The forward KL takes either form -> ((teacher_logits, top_v, top_i) with None for the absent form, K)."""
+    if teacher_logits is not None:
+        return (_dense_teacher(s, teacher_logits), None, None), 0
+    if top_v is not None and top_i is not None:
+        return (None,) + _topk_teacher(s, top_v, top_i), top_v.shape[-1]
+    raise ValueError("Either teacher_logits or top_k must be provided")  # distillation_loss.py:120
+
+
 class KDLossFn(torch.autograd.Function):
     """DistillationLoss.forward + its backward on the HIP kernels (distillation_loss.py:14-128)."""
 
@@ -356,44 +416,17 @@ class KDLossFn(torch.autograd.Function):
         s = _need(student_logits, None, "student_logits")
         B, T, V = s.shape
         dt = _dt(s)
-        lib = load_lib()
         labels = _need(labels.to(torch.int64), torch.int64, "labels")
-        K = 0
-        if teacher_logits is not None:
-            teacher_logits = _need(teacher_logits.to(s.dtype), None, "teacher_logits")
-            if teacher_logits.shape != s.shape:
-                raise ValueError(f"teacher_logits {tuple(teacher_logits.shape)} != student_logits {tuple(s.shape)}")
-            top_v = top_i = None
-        elif top_v is not None and top_i is not None:
-            K = top_v.shape[-1]
-            # distillation_loss.py:78-91 moves the pre-extracted arrays to the student's device
-            top_v = top_v.to(device=s.device, dtype=torch.float16).contiguous()
-            top_i = top_i.to(device=s.device, dtype=torch.int32).contiguous()
-        else:
-            raise ValueError("Either teacher_logits or top_k must be provided")  # distillation_loss.py:120
+        teacher, K = _kd_teacher(s, teacher_logits, top_v, top_i)
         mask = None
         if speech_mask is not None:
             mask = (speech_mask.to(s.device) != 0).to(torch.uint8).contiguous()
-        stats = torch.empty(lib.sd_kdloss_stats_bytes(B, T), dtype=torch.uint8, device=s.device)
-        out = torch.empty(8, dtype=torch.float32, device=s.device)
-        check(lib.sd_kdloss_fwd(s.data_ptr(), _p(teacher_logits), _p(top_v), _p(top_i), labels.data_ptr(), _p(mask),
-                                stats.data_ptr(), out.data_ptr(), B, T, V, K, float(temperature), float(alpha), dt,
-                                _stream()), "sd_kdloss_fwd")
-        ctx.save_for_backward(s, labels, teacher_logits, top_v, top_i, stats, out)
-        ctx.cfg = (B, T, V, K, float(temperature), float(alpha), dt, bool(inplace_grad))
-        ctx.mark_non_differentiable(out)
-        return out[0].clone(), out
+        return _loss_forward(ctx, "sd_kdloss", "", s, dt, labels, teacher, (mask,), (B, T, V, K),
+                             (float(temperature), float(alpha)), inplace_grad, (B, T))
 
     @staticmethod
     def backward(ctx, g_total, _g_out):
-        s, labels, teacher_logits, top_v, top_i, stats, out = ctx.saved_tensors
-        B, T, V, K, temperature, alpha, dt, inplace = ctx.cfg
-        grad = s if inplace else torch.empty_like(s)
-        go = g_total.to(torch.float32).reshape(1).contiguous()
-        check(load_lib().sd_kdloss_bwd(s.data_ptr(), _p(teacher_logits), _p(top_v), _p(top_i), labels.data_ptr(),
-                                       stats.data_ptr(), out.data_ptr(), go.data_ptr(), grad.data_ptr(), B, T, V, K,
-                                       temperature, alpha, dt, _stream()), "sd_kdloss_bwd")
-        return grad, None, None, None, None, None, None, None, None
+        return _loss_backward(ctx, g_total, 9)
 
 
 def gemm_grouped_tn(pairs, accumulate_into=None):
@@ -450,59 +483,64 @@ class KDLossRowsFn(torch.autograd.Function):
         s = _need(student_logits, None, "student_logits")
         R, V = s.shape
         dt = _dt(s)
-        lib = load_lib()
         row_labels = _need(row_labels.to(torch.int64), torch.int64, "row_labels")
-        K = 0
-        if teacher_logits is not None:
-            teacher_logits = _need(teacher_logits.to(s.dtype), None, "teacher_logits")
-            if teacher_logits.shape != s.shape:
-                raise ValueError(f"teacher_logits {tuple(teacher_logits.shape)} != student_logits {tuple(s.shape)}")
-            top_v = top_i = None
-        elif top_v is not None and top_i is not None:
-            K = top_v.shape[-1]
-            top_v = top_v.to(device=s.device, dtype=torch.float16).contiguous()
-            top_i = top_i.to(device=s.device, dtype=torch.int32).contiguous()
-        else:
-            raise ValueError("Either teacher_logits or top_k must be provided")  # distillation_loss.py:120
-        stats = torch.empty(lib.sd_kdloss_stats_bytes(R, 1), dtype=torch.uint8, device=s.device)
-        out = torch.empty(8, dtype=torch.float32, device=s.device)
-        check(lib.sd_kdloss_fwd_rows(s.data_ptr(), _p(teacher_logits), _p(top_v), _p(top_i), row_labels.data_ptr(),
-                                     stats.data_ptr(), out.data_ptr(), R, V, K, float(temperature), float(alpha), dt,
-                                     _stream()), "sd_kdloss_fwd_rows")
-        ctx.save_for_backward(s, row_labels, teacher_logits, top_v, top_i, stats, out)
-        ctx.cfg = (R, V, K, float(temperature), float(alpha), dt, bool(inplace_grad))
-        ctx.mark_non_differentiable(out)
-        return out[0].clone(), out
+        teacher, K = _kd_teacher(s, teacher_logits, top_v, top_i)
+        return _loss_forward(ctx, "sd_kdloss", "_rows", s, dt, row_labels, teacher, (), (R, V, K),
+                             (float(temperature), float(alpha)), inplace_grad, (R, 1))
 
     @staticmethod
     def backward(ctx, g_total, _g_out):
-        s, row_labels, teacher_logits, top_v, top_i, stats, out = ctx.saved_tensors
-        R, V, K, temperature, alpha, dt, inplace = ctx.cfg
-        grad = s if inplace else torch.empty_like(s)
-        go = g_total.to(torch.float32).reshape(1).contiguous()
-        check(load_lib().sd_kdloss_bwd_rows(s.data_ptr(), _p(teacher_logits), _p(top_v), _p(top_i), row_labels.data_ptr(),
-                                            stats.data_ptr(), out.data_ptr(), go.data_ptr(), grad.data_ptr(), R, V, K,
-                                            temperature, alpha, dt, _stream()), "sd_kdloss_bwd_rows")
-        return grad, None, None, None, None, None, None, None
+        return _loss_backward(ctx, g_total, 8)
 
 
-DIVERGENCES = {"reverse_kl": 1, "jsd": 2}  # include/sd_hip.h SD_DIV_*; "forward_kl" is KDLossRowsFn
-TOPK_DIVERGENCE = "jsd_topk"               # the jsd against a top-K teacher: GJSDTopKLossRowsFn (sd_gjsd_topk_*_rows)
+# ------------------------------------------------------------------------------------------ the divergences
+class Divergence(NamedTuple):
+    """One row of the table: what a ``divergence`` name means to the kernels, the loss module and the trainer."""
+    stem: str       # its C entries are <stem>_fwd_rows / <stem>_bwd_rows (forward_kl also has the shifted <stem>_fwd / _bwd)
+    mode: object    # the SD_DIV_* of include/sd_hip.h that the entries take, None where they take none
+    teacher: str    # the teacher form: "dense" logits, a "topk" teacher, "topk_tail" (with its tail), or "either"
+    beta01: bool    # beta must lie in (0, 1)
+    dense: str      # the divergence that takes the dense teacher distribution where this one takes a top-K teacher
 
 
-TAIL_DIVERGENCES = {"forward_kl_tail": 0, "reverse_kl_tail": 1, "jsd_tail": 2}  # a top-K teacher with a tail bucket:
-#                                                       GJSDTailLossRowsFn (sd_gjsd_tail_*_rows), SD_DIV_* of the same kind
-ALL_DIVERGENCES = ("forward_kl", *DIVERGENCES, TOPK_DIVERGENCE, *TAIL_DIVERGENCES)
+DIVERGENCE_TABLE = {
+    "forward_kl":      Divergence("sd_kdloss", None, "either", False, "forward_kl"),   # KDLossFn / KDLossRowsFn
+    "reverse_kl":      Divergence("sd_gjsd", 1, "dense", False, "reverse_kl"),         # GJSDLossRowsFn
+    "jsd":             Divergence("sd_gjsd", 2, "dense", True, "jsd"),
+    "jsd_topk":        Divergence("sd_gjsd_topk", None, "topk", True, "jsd"),          # GJSDTopKLossRowsFn
+    "forward_kl_tail": Divergence("sd_gjsd_tail", 0, "topk_tail", False, "forward_kl"),  # GJSDTailLossRowsFn
+    "reverse_kl_tail": Divergence("sd_gjsd_tail", 1, "topk_tail", False, "reverse_kl"),
+    "jsd_tail":        Divergence("sd_gjsd_tail", 2, "topk_tail", True, "jsd"),
+}
+ALL_DIVERGENCES = tuple(DIVERGENCE_TABLE)
+DIVERGENCES = {n: d.mode for n, d in DIVERGENCE_TABLE.items() if d.stem == "sd_gjsd"}            # dense reverse KL / JSD
+TOPK_DIVERGENCE, = (n for n, d in DIVERGENCE_TABLE.items() if d.stem == "sd_gjsd_topk")         # the jsd on a top-K teacher
+TAIL_DIVERGENCES = {n: d.mode for n, d in DIVERGENCE_TABLE.items() if d.stem == "sd_gjsd_tail"}  # top-K teacher + tail bucket
 
 
 def check_divergence(divergence, beta):
     """ValueError for a divergence the loss does not know, or a ``jsd`` / ``jsd_topk`` / ``jsd_tail`` whose beta is outside
     (0, 1) (NaN included): the jsd formula tends to 0 at both ends, TRL's beta = 0 / 1 are ``forward_kl`` / ``reverse_kl``."""
-    if divergence not in ALL_DIVERGENCES:
+    if divergence not in DIVERGENCE_TABLE:
         raise ValueError(f"unknown divergence {divergence!r}: one of " + ", ".join(repr(d) for d in ALL_DIVERGENCES))
-    if divergence in ("jsd", TOPK_DIVERGENCE, "jsd_tail") and not 0.0 < float(beta) < 1.0:
+    if DIVERGENCE_TABLE[divergence].beta01 and not 0.0 < float(beta) < 1.0:
         raise ValueError(f"divergence={divergence!r} needs 0 < beta < 1, got {beta!r} (beta = 0 is 'forward_kl', beta = 1 is "
                          "'reverse_kl')")
+
+
+def takes_topk_teacher(divergence):
+    """The divergence is defined on a top-K teacher only (``jsd_topk`` and the ``_tail`` names)."""
+    return DIVERGENCE_TABLE[divergence].teacher in ("topk", "topk_tail")
+
+
+def takes_dense_teacher(divergence):
+    """The divergence is defined on the dense teacher distribution only (``reverse_kl``, ``jsd``)."""
+    return DIVERGENCE_TABLE[divergence].teacher == "dense"
+
+
+def dense_name(divergence):
+    """The divergence that takes the dense teacher distribution where ``divergence`` takes a top-K teacher."""
+    return DIVERGENCE_TABLE[divergence].dense
 
 
 class GJSDLossRowsFn(torch.autograd.Function):
@@ -521,39 +559,14 @@ class GJSDLossRowsFn(torch.autograd.Function):
         s = _need(student_logits, None, "student_logits")
         R, V = s.shape
         dt = _dt(s)
-        lib = load_lib()
         row_labels = _need(row_labels.to(torch.int64), torch.int64, "row_labels")
-        teacher_logits = _need(teacher_logits.to(s.dtype), None, "teacher_logits")
-        if teacher_logits.shape != s.shape:
-            raise ValueError(f"teacher_logits {tuple(teacher_logits.shape)} != student_logits {tuple(s.shape)}")
-        mode = DIVERGENCES[divergence]
-        ctx.cfg = (R, V, float(temperature), float(alpha), float(beta), mode, dt, bool(inplace_grad))
-        if R == 0:   # the C entry refuses R <= 0; the loss of no row is 0 and so is its (empty) gradient
-            out = torch.zeros(8, dtype=torch.float32, device=s.device)
-            ctx.save_for_backward(s, row_labels, teacher_logits, out, out)
-            ctx.mark_non_differentiable(out)
-            return out[0].clone(), out
-        stats = torch.empty(lib.sd_gjsd_stats_bytes(R), dtype=torch.uint8, device=s.device)
-        out = torch.empty(8, dtype=torch.float32, device=s.device)
-        check(lib.sd_gjsd_fwd_rows(s.data_ptr(), teacher_logits.data_ptr(), row_labels.data_ptr(), stats.data_ptr(),
-                                   out.data_ptr(), R, V, float(temperature), float(alpha), float(beta), mode, dt, _stream()),
-              "sd_gjsd_fwd_rows")
-        ctx.save_for_backward(s, row_labels, teacher_logits, stats, out)
-        ctx.mark_non_differentiable(out)
-        return out[0].clone(), out
+        return _loss_forward(ctx, "sd_gjsd", "_rows", s, dt, row_labels, (_dense_teacher(s, teacher_logits),), (), (R, V),
+                             (float(temperature), float(alpha), float(beta), DIVERGENCES[divergence]), inplace_grad, (R,),
+                             zeros_without_rows=True)
 
     @staticmethod
     def backward(ctx, g_total, _g_out):
-        s, row_labels, teacher_logits, stats, out = ctx.saved_tensors
-        R, V, temperature, alpha, beta, mode, dt, inplace = ctx.cfg
-        grad = s if inplace else torch.empty_like(s)
-        if R == 0:
-            return grad, None, None, None, None, None, None, None
-        go = g_total.to(torch.float32).reshape(1).contiguous()
-        check(load_lib().sd_gjsd_bwd_rows(s.data_ptr(), teacher_logits.data_ptr(), row_labels.data_ptr(), stats.data_ptr(),
-                                          out.data_ptr(), go.data_ptr(), grad.data_ptr(), R, V, temperature, alpha, beta,
-                                          mode, dt, _stream()), "sd_gjsd_bwd_rows")
-        return grad, None, None, None, None, None, None, None
+        return _loss_backward(ctx, g_total, 8)
 
 
 class GJSDTopKLossRowsFn(torch.autograd.Function):
@@ -573,40 +586,16 @@ class GJSDTopKLossRowsFn(torch.autograd.Function):
         s = _need(student_logits, None, "student_logits")
         R, V = s.shape
         dt = _dt(s)
-        lib = load_lib()
         row_labels = _need(row_labels.to(torch.int64), torch.int64, "row_labels")
         K = int(top_v.shape[-1])
         if tuple(top_v.shape) != (R, K) or tuple(top_i.shape) != (R, K):
             raise ValueError(f"top-K teacher {tuple(top_v.shape)} / {tuple(top_i.shape)} for {R} rows: expected [R, K] twice")
-        top_v = top_v.to(device=s.device, dtype=torch.float16).contiguous()
-        top_i = top_i.to(device=s.device, dtype=torch.int32).contiguous()
-        ctx.cfg = (R, V, K, float(temperature), float(alpha), float(beta), dt, bool(inplace_grad))
-        if R == 0:   # the C entry refuses R <= 0; the loss of no row is 0 and so is its (empty) gradient
-            out = torch.zeros(8, dtype=torch.float32, device=s.device)
-            ctx.save_for_backward(s, row_labels, top_v, top_i, out, out)
-            ctx.mark_non_differentiable(out)
-            return out[0].clone(), out
-        stats = torch.empty(lib.sd_gjsd_topk_stats_bytes(R), dtype=torch.uint8, device=s.device)
-        out = torch.empty(8, dtype=torch.float32, device=s.device)
-        check(lib.sd_gjsd_topk_fwd_rows(s.data_ptr(), top_v.data_ptr(), top_i.data_ptr(), row_labels.data_ptr(),
-                                        stats.data_ptr(), out.data_ptr(), R, V, K, float(temperature), float(alpha),
-                                        float(beta), dt, _stream()), "sd_gjsd_topk_fwd_rows")
-        ctx.save_for_backward(s, row_labels, top_v, top_i, stats, out)
-        ctx.mark_non_differentiable(out)
-        return out[0].clone(), out
+        return _loss_forward(ctx, "sd_gjsd_topk", "_rows", s, dt, row_labels, _topk_teacher(s, top_v, top_i), (), (R, V, K),
+                             (float(temperature), float(alpha), float(beta)), inplace_grad, (R,), zeros_without_rows=True)
 
     @staticmethod
     def backward(ctx, g_total, _g_out):
-        s, row_labels, top_v, top_i, stats, out = ctx.saved_tensors
-        R, V, K, temperature, alpha, beta, dt, inplace = ctx.cfg
-        grad = s if inplace else torch.empty_like(s)
-        if R == 0:
-            return grad, None, None, None, None, None, None, None
-        go = g_total.to(torch.float32).reshape(1).contiguous()
-        check(load_lib().sd_gjsd_topk_bwd_rows(s.data_ptr(), top_v.data_ptr(), top_i.data_ptr(), row_labels.data_ptr(),
-                                               stats.data_ptr(), out.data_ptr(), go.data_ptr(), grad.data_ptr(), R, V, K,
-                                               temperature, alpha, beta, dt, _stream()), "sd_gjsd_topk_bwd_rows")
-        return grad, None, None, None, None, None, None, None
+        return _loss_backward(ctx, g_total, 8)
 
 
 class GJSDTailLossRowsFn(torch.autograd.Function):
@@ -630,45 +619,18 @@ class GJSDTailLossRowsFn(torch.autograd.Function):
         s = _need(student_logits, None, "student_logits")
         R, V = s.shape
         dt = _dt(s)
-        lib = load_lib()
         row_labels = _need(row_labels.to(torch.int64), torch.int64, "row_labels")
         K = int(top_v.shape[-1])
         if tuple(top_v.shape) != (R, K) or tuple(top_i.shape) != (R, K) or tuple(top_tail.shape) != (R,):
             raise ValueError(f"top-K teacher {tuple(top_v.shape)} / {tuple(top_i.shape)} / tail {tuple(top_tail.shape)} for "
                              f"{R} rows: expected [R, K] twice and [R]")
-        top_v = top_v.to(device=s.device, dtype=torch.float16).contiguous()
-        top_i = top_i.to(device=s.device, dtype=torch.int32).contiguous()
-        top_tail = top_tail.to(device=s.device, dtype=torch.float32).contiguous()
-        ctx.cfg = (R, V, K, float(temperature), float(alpha), float(beta), TAIL_DIVERGENCES[divergence], dt, bool(inplace_grad))
-        if R == 0:   # the C entry refuses R <= 0; the loss of no row is 0 and so is its (empty) gradient
-            out = torch.zeros(8, dtype=torch.float32, device=s.device)
-            ctx.save_for_backward(s, row_labels, top_v, top_i, top_tail, out, out)
-            ctx.mark_non_differentiable(out)
-            return out[0].clone(), out
-        stats = torch.empty(lib.sd_gjsd_tail_stats_bytes(R), dtype=torch.uint8, device=s.device)
-        out = torch.empty(8, dtype=torch.float32, device=s.device)
-        check(lib.sd_gjsd_tail_fwd_rows(s.data_ptr(), top_v.data_ptr(), top_i.data_ptr(), top_tail.data_ptr(),
-                                        row_labels.data_ptr(), stats.data_ptr(), out.data_ptr(), R, V, K, float(temperature),
-                                        float(alpha), float(beta), TAIL_DIVERGENCES[divergence], dt, _stream()),
-              "sd_gjsd_tail_fwd_rows")
-        ctx.save_for_backward(s, row_labels, top_v, top_i, top_tail, stats, out)
-        ctx.mark_non_differentiable(out)
-        return out[0].clone(), out
+        return _loss_forward(ctx, "sd_gjsd_tail", "_rows", s, dt, row_labels, _topk_teacher(s, top_v, top_i, top_tail), (),
+                             (R, V, K), (float(temperature), float(alpha), float(beta), TAIL_DIVERGENCES[divergence]),
+                             inplace_grad, (R,), zeros_without_rows=True)
 
     @staticmethod
     def backward(ctx, g_total, _g_out):
-        s, row_labels, top_v, top_i, top_tail, stats, out = ctx.saved_tensors
-        R, V, K, temperature, alpha, beta, mode, dt, inplace = ctx.cfg
-        grad = s if inplace else torch.empty_like(s)
-        none = (None,) * 9
-        if R == 0:
-            return (grad,) + none
-        go = g_total.to(torch.float32).reshape(1).contiguous()
-        check(load_lib().sd_gjsd_tail_bwd_rows(s.data_ptr(), top_v.data_ptr(), top_i.data_ptr(), top_tail.data_ptr(),
-                                               row_labels.data_ptr(), stats.data_ptr(), out.data_ptr(), go.data_ptr(),
-                                               grad.data_ptr(), R, V, K, temperature, alpha, beta, mode, dt, _stream()),
-              "sd_gjsd_tail_bwd_rows")
-        return (grad,) + none
+        return _loss_backward(ctx, g_total, 10)
 
 
 class CELossRowsFn(torch.autograd.Function):
@@ -681,28 +643,14 @@ class CELossRowsFn(torch.autograd.Function):
         s = _need(logits, None, "logits")
         R, V = s.shape
         dt = _dt(s)
-        lib = load_lib()
         row_labels = _need(row_labels.to(torch.int64), torch.int64, "row_labels")
         if divisor is not None:
             divisor = _need(divisor.to(device=s.device, dtype=torch.float32).reshape(1), torch.float32, "divisor")
-        stats = torch.empty(lib.sd_celoss_stats_bytes(R), dtype=torch.uint8, device=s.device)
-        out = torch.empty(4, dtype=torch.float32, device=s.device)
-        check(lib.sd_celoss_fwd_rows(s.data_ptr(), row_labels.data_ptr(), _p(divisor), stats.data_ptr(), out.data_ptr(), R, V,
-                                     dt, _stream()), "sd_celoss_fwd_rows")
-        ctx.save_for_backward(s, row_labels, stats, out)
-        ctx.cfg = (R, V, dt, bool(inplace_grad))
-        ctx.mark_non_differentiable(out)
-        return out[0].clone(), out
+        return _loss_forward(ctx, "sd_celoss", "_rows", s, dt, row_labels, (), (divisor,), (R, V), (), inplace_grad, (R,), n_out=4)
 
     @staticmethod
     def backward(ctx, g_total, _g_out):
-        s, row_labels, stats, out = ctx.saved_tensors
-        R, V, dt, inplace = ctx.cfg
-        grad = s if inplace else torch.empty_like(s)
-        go = g_total.to(torch.float32).reshape(1).contiguous()
-        check(load_lib().sd_celoss_bwd_rows(s.data_ptr(), row_labels.data_ptr(), stats.data_ptr(), out.data_ptr(),
-                                            go.data_ptr(), grad.data_ptr(), R, V, dt, _stream()), "sd_celoss_bwd_rows")
-        return grad, None, None, None
+        return _loss_backward(ctx, g_total, 4)
 
 
 def celoss_rows(logits, row_labels, divisor=None, inplace_grad=False):

@@ -146,12 +146,11 @@ class DistillationTrainer(FlatStudentTrainer):
                  on_policy_engine=None, **kwargs):
         # everything that can be refused without a model is refused before HF's constructor touches one
         ops.check_divergence(divergence, beta)
-        if divergence == ops.TOPK_DIVERGENCE or divergence in ops.TAIL_DIVERGENCES:
-            if top_k <= 0 or is_quantized_teacher:
-                raise ValueError(f"divergence={divergence!r} needs a top-K teacher (top_k > 0, not a quantised teacher), got "
-                                 f"top_k={top_k}, is_quantized_teacher={is_quantized_teacher}: the dense teacher "
-                                 f"distribution goes with divergence={self._dense_name(divergence)!r}")
-        elif divergence != "forward_kl" and not (top_k <= 0 or is_quantized_teacher):
+        if ops.takes_topk_teacher(divergence) and (top_k <= 0 or is_quantized_teacher):
+            raise ValueError(f"divergence={divergence!r} needs a top-K teacher (top_k > 0, not a quantised teacher), got "
+                             f"top_k={top_k}, is_quantized_teacher={is_quantized_teacher}: the dense teacher "
+                             f"distribution goes with divergence={ops.dense_name(divergence)!r}")
+        if ops.takes_dense_teacher(divergence) and not (top_k <= 0 or is_quantized_teacher):
             raise ValueError(f"divergence={divergence!r} needs the dense teacher distribution: pass top_k=0 (a top-K "
                              f"teacher defines it on K entries only), got top_k={top_k}")
         if not 0.0 <= float(lmbda) <= 1.0:
@@ -219,11 +218,6 @@ class DistillationTrainer(FlatStudentTrainer):
         # The optimizer HF would build by default (AdamW over ~310 HF-named tensors, HF trainer.py:1778-1796) is replaced
         # by the one-launch FlatAdamW over the flat buffers when the student offers them; set False to keep HF's.
         self.fused_optimizer = True
-
-    @staticmethod
-    def _dense_name(divergence):
-        """The divergence that takes the dense teacher distribution where ``divergence`` takes a top-K teacher."""
-        return divergence[:-len("_tail")] if divergence in ops.TAIL_DIVERGENCES else "jsd"
 
     # ------------------------------------------------------------------------------ on-policy window rollouts
     @staticmethod
@@ -616,8 +610,7 @@ class DistillationTrainer(FlatStudentTrainer):
         teacher_top_k_i = inputs.pop("teacher_top_k_i", None)
         teacher_top_k_tail = inputs.pop("teacher_top_k_tail", None)   # (read by the _tail divergences only)
 
-        if (self.divergence not in ("forward_kl", ops.TOPK_DIVERGENCE) and self.divergence not in ops.TAIL_DIVERGENCES
-                and teacher_top_k_v is not None):
+        if ops.takes_dense_teacher(self.divergence) and teacher_top_k_v is not None:
             raise ValueError(f"divergence={self.divergence!r} needs the dense teacher distribution; this batch carries "
                              "pre-extracted teacher_top_k_v (K entries per position)")
         need_teacher = teacher_top_k_v is None and self.teacher_model is not None

@@ -12,6 +12,13 @@ library's launch profiler (an event pair around every launch), forward + backwar
   - sd_celoss_fwd_rows + sd_celoss_bwd_rows;
   - sd_gjsd_fwd_rows + sd_gjsd_bwd_rows, reverse KL and JSD beta = 0.5, at T = 2;
   - sd_logsoftmax_topk, K = 128.
+--rows sparse (default --out profiles/loss_sparse_refactor_bench.json) measures instead what DESIGN.md section 12e moved,
+same method, T = 2, beta = 0.5:
+  - sd_gjsd_topk_fwd_rows + _bwd_rows at K = 128 and K = 1024; sd_gjsd_tail_fwd_rows + _bwd_rows in its three modes at
+    K = 128 and jsd_tail at K = 1024 (the tails are sd_topk_tail's);
+  - sd_gjsd_*_rows reverse KL and JSD (sweep 1 is on the shared normaliser step) and sd_kdloss_*_rows at top-128 (the host
+    path alone moved);
+  - sd_loss_rows at B = 4, T = 512 and sd_packed_rows at M = 2048 with four documents (the shared compaction).
 Criterion per row: the new build's median may exceed the parent's maximum by no more than the parent's own spread
 (max - min) of this call.  Exit status 1 if a row misses it."""
 import argparse
@@ -28,7 +35,7 @@ WARM = 3
 R, V = 1536, 159488
 
 
-def child():
+def child(which):
     sys.path.insert(0, ROOT)
     import torch
     from speech_distill_amd import ops
@@ -41,8 +48,8 @@ def child():
     labels = torch.randint(0, V, (R,), device=dev, generator=g)
     go = torch.ones(1, dtype=torch.float32, device=dev)
     out = torch.empty(8, dtype=torch.float32, device=dev)
-    stats = torch.empty(max(lib.sd_kdloss_stats_bytes(R, 1), lib.sd_gjsd_stats_bytes(R), lib.sd_celoss_stats_bytes(R)),
-                        dtype=torch.uint8, device=dev)
+    stats = torch.empty(max(lib.sd_kdloss_stats_bytes(R, 1), lib.sd_gjsd_stats_bytes(R), lib.sd_celoss_stats_bytes(R),
+                            lib.sd_gjsd_topk_stats_bytes(R), lib.sd_gjsd_tail_stats_bytes(R)), dtype=torch.uint8, device=dev)
     tv, ti = ops.logsoftmax_topk(t, 1024)
     top = {128: (tv[:, :128].contiguous(), ti[:, :128].contiguous()), 1024: (tv, ti)}
     tv128, ti128 = torch.empty_like(top[128][0]), torch.empty_like(top[128][1])
@@ -75,9 +82,60 @@ def child():
     def topk():
         assert lib.sd_logsoftmax_topk(t.data_ptr(), tv128.data_ptr(), ti128.data_ptr(), None, R, V, V, 128, 0, st) == 0
 
-    rows = {"kd fwd+bwd, top-128, T=2": kd(None, 128, 2.0), "kd fwd+bwd, top-1024, T=2": kd(None, 1024, 2.0),
-            "kd fwd+bwd, dense, T=2": kd(t, 0, 2.0), "kd fwd+bwd, dense, T=3": kd(t, 0, 3.0), "ce fwd+bwd": ce,
-            "gjsd fwd+bwd, reverse KL, T=2": gjsd(1), "gjsd fwd+bwd, JSD beta=0.5, T=2": gjsd(2), "top-K, K=128": topk}
+    def gjsd_topk(K):
+        v, i = top[K]
+
+        def run():
+            assert lib.sd_gjsd_topk_fwd_rows(s.data_ptr(), v.data_ptr(), i.data_ptr(), labels.data_ptr(), stats.data_ptr(),
+                                             out.data_ptr(), R, V, K, 2.0, 0.5, 0.5, 0, st) == 0
+            assert lib.sd_gjsd_topk_bwd_rows(s.data_ptr(), v.data_ptr(), i.data_ptr(), labels.data_ptr(), stats.data_ptr(),
+                                             out.data_ptr(), go.data_ptr(), grad.data_ptr(), R, V, K, 2.0, 0.5, 0.5, 0, st) == 0
+        return run
+
+    def gjsd_tail(K, mode):
+        v, i = top[K]
+        tau = ops.topk_tail(t, i, 2.0)
+
+        def run():
+            assert lib.sd_gjsd_tail_fwd_rows(s.data_ptr(), v.data_ptr(), i.data_ptr(), tau.data_ptr(), labels.data_ptr(),
+                                             stats.data_ptr(), out.data_ptr(), R, V, K, 2.0, 0.5, 0.5, mode, 0, st) == 0
+            assert lib.sd_gjsd_tail_bwd_rows(s.data_ptr(), v.data_ptr(), i.data_ptr(), tau.data_ptr(), labels.data_ptr(),
+                                             stats.data_ptr(), out.data_ptr(), go.data_ptr(), grad.data_ptr(), R, V, K, 2.0, 0.5,
+                                             0.5, mode, 0, st) == 0
+        return run
+
+    def selection():
+        """-> (sd_loss_rows at B = 4, T = 512, sd_packed_rows at M = 2048 with four documents): a quarter of the labels masked."""
+        B, T, M = 4, 512, 2048
+        lab = torch.randint(0, V, (B, T), device=dev, generator=g)
+        lab[torch.rand(B, T, device=dev, generator=g) < 0.25] = -100
+        sel, sel_labels = torch.empty(M, dtype=torch.int64, device=dev), torch.empty(M, dtype=torch.int64, device=dev)
+        meta = torch.empty(4, dtype=torch.int32, device=dev)
+        cu = torch.tensor([0, 300, 1000, 1900, M], dtype=torch.int32, device=dev)
+        pos = torch.cat([torch.arange(int(b - a), device=dev) for a, b in zip(cu[:-1], cu[1:])])
+
+        def padded():
+            assert lib.sd_loss_rows(lab.data_ptr(), None, None, None, sel.data_ptr(), sel_labels.data_ptr(), meta.data_ptr(), B, T,
+                                    st) == 0
+
+        def packed():
+            assert lib.sd_packed_rows(lab.data_ptr(), None, cu.data_ptr(), 4, pos.data_ptr(), sel.data_ptr(), sel_labels.data_ptr(),
+                                      meta.data_ptr(), M, st) == 0
+        return padded, packed
+
+    if which == "sparse":
+        padded, packed = selection()
+        rows = {"gjsd_topk fwd+bwd, K=128": gjsd_topk(128), "gjsd_topk fwd+bwd, K=1024": gjsd_topk(1024),
+                "gjsd_tail fwd+bwd, forward_kl_tail, K=128": gjsd_tail(128, 0),
+                "gjsd_tail fwd+bwd, reverse_kl_tail, K=128": gjsd_tail(128, 1),
+                "gjsd_tail fwd+bwd, jsd_tail, K=128": gjsd_tail(128, 2), "gjsd_tail fwd+bwd, jsd_tail, K=1024": gjsd_tail(1024, 2),
+                "gjsd fwd+bwd, reverse KL, T=2": gjsd(1), "gjsd fwd+bwd, JSD beta=0.5, T=2": gjsd(2),
+                "kd fwd+bwd, top-128, T=2": kd(None, 128, 2.0), "loss_rows, B=4, T=512": padded,
+                "packed_rows, M=2048, 4 documents": packed}
+    else:
+        rows = {"kd fwd+bwd, top-128, T=2": kd(None, 128, 2.0), "kd fwd+bwd, top-1024, T=2": kd(None, 1024, 2.0),
+                "kd fwd+bwd, dense, T=2": kd(t, 0, 2.0), "kd fwd+bwd, dense, T=3": kd(t, 0, 3.0), "ce fwd+bwd": ce,
+                "gjsd fwd+bwd, reverse KL, T=2": gjsd(1), "gjsd fwd+bwd, JSD beta=0.5, T=2": gjsd(2), "top-K, K=128": topk}
     res = {}
     for name, fn in rows.items():
         for _ in range(WARM):
@@ -94,10 +152,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent_lib")
     ap.add_argument("--child", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "loss_refactor_bench.json"))
+    ap.add_argument("--rows", choices=("dense", "sparse"), default="dense", help="the row set (see the module docstring)")
+    ap.add_argument("--out", help="default: profiles/loss_refactor_bench.json, for --rows sparse loss_sparse_refactor_bench.json")
     args = ap.parse_args()
     if args.child:
-        return child()
+        return child(args.rows)
+    if not args.out:
+        args.out = os.path.join(ROOT, "profiles", "loss_sparse_refactor_bench.json" if args.rows == "sparse" else "loss_refactor_bench.json")
     if not args.parent_lib or not os.path.exists(args.parent_lib):
         sys.exit("--parent_lib: the other build's libsd_hip.so")
     runs = {"parent": [], "new": []}
@@ -108,8 +169,8 @@ def main():
             if build == "parent":
                 env["SD_HIP_LIB"] = os.path.abspath(args.parent_lib)
             try:
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, capture_output=True,
-                                   text=True, timeout=180)
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--rows", args.rows], env=env, capture_output=True,
+                                   text=True, timeout=240)
             except subprocess.TimeoutExpired:
                 print(f"{build} child {rep} ran into its time limit")
                 return 3

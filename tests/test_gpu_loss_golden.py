@@ -21,7 +21,19 @@ Cases (eight rows each unless the family says otherwise):
         shifted sd_kdloss_fwd / sd_kdloss_bwd entry with a speech mask;
   ce    sd_celoss_*_rows, both dtypes, V = 40008 and the four edges, with and without a divisor;
   gjsd  the table, near and underflow families of tests/gjsd_ref.py;
-  topk  P.topk_case_list((256, 512, 1024))."""
+  topk  P.topk_case_list((256, 512, 1024)).
+
+The sparse families were recorded later, from commit 7b5e9af ("On-policy: roll out the accumulation window through the
+engine"), the commit before gjsd_topk_bwd_kernel and gjsd_tail_bwd_kernel became wrappers of one tk_bwd_row and the
+top-K forwards took their normaliser step, masked-row exit and entry epilogue from shared functions (DESIGN.md section
+12e), into ONE file of their own (arrays_sparse.npz; `--record DIR sparse`), which holds the digests as well: the JSON
+text of what digests.json holds for the older cases, as a byte array under the key DIGESTS_KEY:
+  tk    sd_gjsd_topk_*_rows on every entry of gjsd_topk_ref.family_cases(f), f = table, peaked, underflow (V = 8 / 4096 /
+        16384 / 16392 / 40008, K = 4 / 32 / 100 / 512 / 513 / 1024, duplicates, ends, no hit, dropped entries);
+  tail  sd_gjsd_tail_*_rows on every entry of gjsd_tail_ref.family_cases(f) (the same, and bad tails) for each of the three
+        divergences.
+For each of the two backward kernels the in-place cases are one at K = 100, one at K = 1024 (two entries per thread) and
+the "duplicates" extra; the tail kernel runs them in all three modes."""
 import hashlib
 import json
 import os
@@ -33,6 +45,8 @@ import torch
 
 from conftest import GOLDEN  # first: as a script (--record) this is what puts the repository root on sys.path
 import gjsd_ref as G
+import gjsd_tail_ref as TL
+import gjsd_topk_ref as TK
 import parity_ref as P
 from gpu_util import dev, to_dev
 from parity_ref import BF, F32
@@ -198,6 +212,40 @@ def _run_gjsd(lib, c):
     return ins, {"loss_out": out.cpu().numpy()}, {"stats": _digest(stats, R), "grad": grad}
 
 
+def _run_sparse(lib, c):
+    """sd_gjsd_topk_*_rows (c["div"] None) or sd_gjsd_tail_*_rows (c["div"]: the SD_DIV_* mode, c["tau"] the tails)."""
+    s, tv, ti, tau, labels, dtype, (beta, T), div = c["s"], c["tv"], c["ti"], c.get("tau"), c["labels"], c["dtype"], c["mode"], c["div"]
+    R, V = s.shape
+    K = tv.shape[-1]
+    ins = _inputs_digest([s, tv, ti, tau, labels], ("sparse", div, beta, T, TK.ALPHA, GO))
+    sd, ld = to_dev(s), to_dev(labels)
+    tvd, tid = to_dev(tv.to(torch.float16)), to_dev(ti.to(torch.int32))
+    go = torch.tensor([GO], dtype=torch.float32, device=dev())
+    out = _scalars()
+    if div is None:
+        stats = _stats(lib.sd_gjsd_topk_stats_bytes(R))
+        rc = lib.sd_gjsd_topk_fwd_rows(sd.data_ptr(), tvd.data_ptr(), tid.data_ptr(), ld.data_ptr(), stats.data_ptr(),
+                                       out.data_ptr(), R, V, K, T, TK.ALPHA, beta, _dt(dtype), _stream())
+    else:
+        taud = to_dev(tau.to(torch.float32))
+        stats = _stats(lib.sd_gjsd_tail_stats_bytes(R))
+        rc = lib.sd_gjsd_tail_fwd_rows(sd.data_ptr(), tvd.data_ptr(), tid.data_ptr(), taud.data_ptr(), ld.data_ptr(),
+                                       stats.data_ptr(), out.data_ptr(), R, V, K, T, TK.ALPHA, beta, div, _dt(dtype), _stream())
+    assert rc == 0, rc
+
+    def bwd(sp, gp):
+        if div is None:
+            rc = lib.sd_gjsd_topk_bwd_rows(sp, tvd.data_ptr(), tid.data_ptr(), ld.data_ptr(), stats.data_ptr(), out.data_ptr(),
+                                           go.data_ptr(), gp, R, V, K, T, TK.ALPHA, beta, _dt(dtype), _stream())
+        else:
+            rc = lib.sd_gjsd_tail_bwd_rows(sp, tvd.data_ptr(), tid.data_ptr(), taud.data_ptr(), ld.data_ptr(), stats.data_ptr(),
+                                           out.data_ptr(), go.data_ptr(), gp, R, V, K, T, TK.ALPHA, beta, div, _dt(dtype),
+                                           _stream())
+        assert rc == 0, rc
+    grad = _backward(bwd, sd, R, dtype, c.get("inplace", False))
+    return ins, {"loss_out": out.cpu().numpy()}, {"stats": _digest(stats, R), "grad": grad}
+
+
 def _run_topk(lib, c):
     from speech_distill_amd import _lib
     tc, dtype, nt = P.TOPK_CASES[c["name"]], c["dtype"], c["nt"]
@@ -293,35 +341,73 @@ def _cases():
     return c
 
 
+def _sparse_cases():
+    """-> (cases, names of the in-place ones).  The in-place inputs are picked by identity: the ref modules cache them."""
+    c, inplace = {}, []
+    marks = [(TK.table_inputs(TK.TABLE_V, BF), TK.MODES[0]), (TK.table_inputs(TK.TABLE_V, F32, 1024), TK.MODES[0]),
+             (TK.extras_inputs(TK.TABLE_V, BF, "duplicates"), TK.MODES[0])]
+    marks += [(TL.table_inputs(TL.TABLE_V, BF, TL.MODES[0][1]), TL.MODES[0]),
+              (TL.table_inputs(TL.TABLE_V, F32, TL.MODES[0][1], 1024), TL.MODES[0]),
+              (TL.extras_inputs(TL.TABLE_V, BF, TL.MODES[0][1], "duplicates"), TL.MODES[0])]
+
+    def add(name, inputs, mode, case):
+        c[name] = (_run_sparse, lambda: dict(case, dtype=inputs[0].dtype, mode=mode))
+        if any(inputs is i and mode == m for i, m in marks):
+            inplace.append(name)
+
+    for family in ("table", "peaked", "underflow"):
+        for n, (inputs, mode) in enumerate(TK.family_cases(family)):
+            s, tv, ti, labels = inputs
+            add(f"tk_{family}_{n:02d}_V{s.shape[1]}_K{tv.shape[1]}_{_dt_name(s.dtype)}_{TK.mode_id(mode)}", inputs, mode,
+                dict(s=s, tv=tv, ti=ti, labels=labels, div=None))
+        for n, (inputs, mode) in enumerate(TL.family_cases(family)):
+            s, tv, ti, tau, labels = inputs
+            for d, div in enumerate(TL.DIVERGENCES):   # d: SD_DIV_FORWARD_KL, SD_DIV_REVERSE_KL, SD_DIV_JSD
+                add(f"tail_{family}_{n:02d}_V{s.shape[1]}_K{tv.shape[1]}_{_dt_name(s.dtype)}_{TL.case_id(div, mode)}", inputs,
+                    mode, dict(s=s, tv=tv, ti=ti, tau=tau, labels=labels, div=d))
+    assert len([n for n in inplace if n.startswith("tk_")]) == 3 and len([n for n in inplace if n.startswith("tail_")]) == 9
+    return c, tuple(inplace)
+
+
 CASES = _cases()
+SPARSE_CASES, SPARSE_INPLACE = _sparse_cases()
+# which recording holds which cases: suffix of digests*.json / arrays*.npz -> cases
+SETS = {"": CASES, "_sparse": SPARSE_CASES}
+DIGESTS_KEY = "digests.json"   # a set with a suffix keeps its digests inside its arrays*.npz, under this key
 _GOLDEN = {}
 
 
 def _run(lib, name):
-    run, make = CASES[name]
+    run, make = CASES[name] if name in CASES else SPARSE_CASES[name]
     case = make()
-    case["inplace"] = name in INPLACE
+    case["inplace"] = name in INPLACE or name in SPARSE_INPLACE
     return run(lib, case)
 
 
-def _golden():
-    if not _GOLDEN:
-        with open(os.path.join(GOLDEN_DIR, "digests.json")) as f:
-            _GOLDEN["digests"] = json.load(f)
-        _GOLDEN["arrays"] = np.load(os.path.join(GOLDEN_DIR, "arrays.npz"), allow_pickle=False)
-    return _GOLDEN["digests"], _GOLDEN["arrays"]
+def _golden(suffix=""):
+    if suffix not in _GOLDEN:
+        arrays = np.load(os.path.join(GOLDEN_DIR, f"arrays{suffix}.npz"), allow_pickle=False)
+        if suffix:
+            digests = json.loads(arrays[DIGESTS_KEY].tobytes())
+        else:
+            with open(os.path.join(GOLDEN_DIR, "digests.json")) as f:
+                digests = json.load(f)
+        _GOLDEN[suffix] = (digests, arrays)
+    return _GOLDEN[suffix]
 
 
 # ------------------------------------------------------------------------------------------------------ the tests
 def test_the_recording_holds_exactly_these_cases():
-    want, arrays = _golden()
-    assert sorted(want) == sorted(CASES)
-    assert sorted({k.split("/")[0] for k in arrays.files}) == sorted(CASES)
+    assert not set(CASES) & set(SPARSE_CASES)
+    for suffix, cases in SETS.items():
+        want, arrays = _golden(suffix)
+        assert sorted(want) == sorted(cases)
+        assert sorted({k.split("/")[0] for k in arrays.files} - {DIGESTS_KEY}) == sorted(cases)
 
 
-@pytest.mark.parametrize("name", sorted(CASES))
+@pytest.mark.parametrize("name", sorted(CASES) + sorted(SPARSE_CASES))
 def test_outputs_equal_the_recorded_ones(lib, name):
-    want, want_arrays = _golden()
+    want, want_arrays = _golden("" if name in CASES else "_sparse")
     ins, arrays, digests = _run(lib, name)
     assert ins == want[name]["inputs"], f"{name}: the INPUTS differ from the recording (the seeded generators or the " \
                                         f"case tables moved): this says nothing about the kernels"
@@ -342,26 +428,28 @@ def test_outputs_equal_the_recorded_ones(lib, name):
     assert not bad, f"{name}: the KERNEL's output differs from the recorded one (inputs equal): {bad}"
 
 
-def _record(out_dir):
+def _record(out_dir, suffix):
     import speech_distill_amd as sda
     lib = sda.load_lib()
     os.makedirs(out_dir, exist_ok=True)
     all_dig, all_arr = {}, {}
-    for name in sorted(CASES):
+    for name in sorted(SETS[suffix]):
         ins, arrays, digests = _run(lib, name)
         all_dig[name] = {"inputs": ins, "digests": digests}
         all_arr.update({f"{name}/{k}": v for k, v in arrays.items()})
-    path = os.path.join(out_dir, "arrays.npz")
+    path = os.path.join(out_dir, f"arrays{suffix}.npz")
+    if suffix:
+        all_arr[DIGESTS_KEY] = np.frombuffer(json.dumps(all_dig, sort_keys=True).encode(), dtype=np.uint8)
+    else:
+        with open(os.path.join(out_dir, "digests.json"), "w") as f:
+            json.dump(all_dig, f, indent=0, sort_keys=True)
+            f.write("\n")
     np.savez_compressed(path, **all_arr)
-    with open(os.path.join(out_dir, "digests.json"), "w") as f:
-        json.dump(all_dig, f, indent=0, sort_keys=True)
-        f.write("\n")
-    print("recorded", len(CASES), "cases from", sda.lib_path(), os.path.getsize(path), "+",
-          os.path.getsize(os.path.join(out_dir, "digests.json")), "bytes")
+    print("recorded", len(SETS[suffix]), "cases from", sda.lib_path(), os.path.getsize(path), "bytes of arrays")
 
 
 if __name__ == "__main__":
-    if len(sys.argv) == 3 and sys.argv[1] == "--record":
-        _record(sys.argv[2])
+    if len(sys.argv) in (3, 4) and sys.argv[1] == "--record" and sys.argv[3:] in ([], ["sparse"]):
+        _record(sys.argv[2], "_sparse" if sys.argv[3:] else "")
     else:
-        sys.exit("usage: python tests/test_gpu_loss_golden.py --record DIR")
+        sys.exit("usage: python tests/test_gpu_loss_golden.py --record DIR [sparse]")
