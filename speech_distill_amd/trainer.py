@@ -10,9 +10,15 @@ DistillationLoss  ->  log {student_loss, teacher_loss, distill_loss} when
 Beyond the reference: ``divergence`` / ``beta`` choose the distillation term (``DistillationLoss``),
 and ``lmbda`` makes a share of the training micro-batches on-policy (``on_policy.py``): the student's own sampled
 continuation replaces the completion before the step.  The defaults (``"forward_kl"``, ``lmbda=0``) are the reference's loop.
+
+What makes a step fast is decided once per micro-batch, in a ``StepPlan`` (``DistillationTrainer._plan_step``, when HF fetches
+the accumulation window or else in ``compute_loss``): the rows the loss reads and what the two models may skip.
 """
 import os
 import time
+from dataclasses import dataclass
+from types import MappingProxyType
+from typing import NamedTuple
 
 import torch
 from transformers import Trainer
@@ -26,10 +32,54 @@ ENGINE_KEYS = ("max_batch", "n_pages", "sync_every", "admission")   # of Distill
 WINDOW_MAX_ROWS = 64   # the rows of the widest batch-invariant decode step (decode_kernels="wide")
 
 
+class StepPlan(NamedTuple):
+    """What the selection of one micro-batch produced (``DistillationTrainer._plan_step``, its only maker): which rows the
+    loss reads and what each model may skip because the selection's one host read has checked it."""
+    rows: object = None          # flat indices of the loss rows (None: nothing was selected, the full [B, T, V] path)
+    row_labels: object = None    # the label each of them predicts
+    packed: object = None        # (student's PackedBatch, teacher's) of a batch packed with cu_seq_lens_q, else None
+    student_kw: object = MappingProxyType({})   # forward keywords of the student: padding_checked / packed_batch
+    teacher_kw: object = MappingProxyType({})   # ... of a HipQwen3ForCausalLM teacher
+    event: object = None         # after it the batch and the rows are on the device (None: planned in place)
+    key: object = None           # what a stored plan is validated by: the addresses of the tensors it was made from
+    full_labels: object = None   # packed by position_ids alone: the labels with -100 at every document start
+
+
+@dataclass
+class _Ahead:
+    """What was done ahead for one micro-batch: its plan and, once enqueued, the teacher's result (``_teacher_pass``)."""
+    plan: StepPlan
+    teacher: tuple = None
+
+
 class FlatStudentTrainer(Trainer):
     """HF Trainer plumbing shared by the trainers of a flat-buffer student (``HipQwen3ForCausalLM``): the data-parallel
     wrapper, tokens/sec in the training log, the fused optimizer and its one-reduction gradient clip, and
-    ``save_pretrained`` checkpoints.  Subclasses set ``tokens_seen``, ``_tps_mark``, ``_hip_dp`` and ``fused_optimizer``."""
+    ``save_pretrained`` checkpoints."""
+
+    PACKED_KEYS = ("position_ids", "cu_seq_lens_q", "cu_seq_lens_k", "max_length_q", "max_length_k")
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        # throughput of the loop: positions (B*T of every training micro-batch, padding included -- what the kernels
+        # process and what bench.py counts) seen by THIS rank; `log` turns it into whole-job tokens/sec
+        self.tokens_seen = 0
+        self._tps_mark = None  # (perf_counter, tokens_seen) at the previous training log
+        self._hip_dp = None
+        # The optimizer HF would build by default (AdamW over ~310 HF-named tensors, HF trainer.py:1778-1796) is replaced
+        # by the one-launch FlatAdamW over the flat buffers when the student offers them; set False to keep HF's.
+        self.fused_optimizer = True
+
+    def _count_tokens(self, model, ids):
+        """A training micro-batch's positions; the first one starts the clock of the first tokens/sec figure."""
+        if model.training and ids is not None:
+            self.tokens_seen += ids.numel()
+            if self._tps_mark is None:
+                self._tps_mark = (time.perf_counter(), self.tokens_seen - ids.numel())
+
+    def _default_adamw(self):
+        """TrainingArguments asks for HF's default AdamW (the reference passes no ``optim``, train.py:331-354)."""
+        return str(getattr(self.args.optim, "value", self.args.optim)).startswith("adamw_torch")
 
     # ------------------------------------------------------------------------------ HF Trainer plumbing
     def _wrap_model(self, model, training=True, dataloader=None):
@@ -193,31 +243,22 @@ class DistillationTrainer(FlatStudentTrainer):
         # compute back-ends; the product ones are the HIP kernels (tests may inject a checker here)
         self._extract_topk = ops.logsoftmax_topk
         self._extract_tail = ops.topk_tail
-        # throughput of the loop: positions (B*T of every training micro-batch, padding included -- what the kernels
-        # process and what bench.py counts) seen by THIS rank; `log` turns it into whole-job tokens/sec
-        self.tokens_seen = 0
-        self._tps_mark = None  # (perf_counter, tokens_seen) at the previous training log
         # The frozen teacher does not depend on the student: on GPUs its forward (+ top-K) runs on a second HIP
         # stream beside the student forward (+4.5 % step throughput on MI355X); results are identical.
         self.overlap_teacher = True
         self._teacher_stream = None
-        self._rows_ahead = {}  # id(labels) -> (key, (rows, row_labels), event) selected in get_batch_samples for this optimizer step
         self._copy_stream = None
         # The teacher's pass of micro-batch i+1 of an accumulation window is enqueued at the END of training_step(i): HF's
         # per-micro-batch host read (logging_nan_inf_filter, on by default) drains the main stream after every backward,
         # and the GPU then has the next teacher pass to run while the host walks back to compute_loss (+1.6-2.1 % loop
         # throughput; with HF's read off the host is ahead anyway and it measured -0.5 %, so "auto" follows that flag).
         # SD_TEACHER_AHEAD=0 / 1 forces it.
-        self._window, self._window_next, self._ahead_results, self._prefetched = [], [], {}, None
+        self._drop_lookahead()
         # Training steps apply both lm_heads, the top-K and the loss only to the rows the loss reads (positions whose
         # NEXT label is not -100, distillation_loss.py:31-45) instead of computing all B*T rows and masking them
         # afterwards; loss and gradients are the same, the head is ~(masked fraction) cheaper.  Needs one host sync
         # per step for the row count.  Off: the full [B,T,V] path; return_outputs=True always uses the full path.
         self.compact_head = True
-        self._hip_dp = None
-        # The optimizer HF would build by default (AdamW over ~310 HF-named tensors, HF trainer.py:1778-1796) is replaced
-        # by the one-launch FlatAdamW over the flat buffers when the student offers them; set False to keep HF's.
-        self.fused_optimizer = True
 
     # ------------------------------------------------------------------------------ on-policy window rollouts
     @staticmethod
@@ -328,8 +369,7 @@ class DistillationTrainer(FlatStudentTrainer):
         fused launch over the flat parameter / gradient / moment buffers (``sd_adamw_bf16``).  HF keeps clipping
         (``max_grad_norm``) and the learning-rate schedule: the scheduler writes ``param_groups[0]["lr"]``."""
         core = ddp.unwrap(self.model)
-        default_adamw = str(getattr(self.args.optim, "value", self.args.optim)).startswith("adamw_torch")
-        if (self.optimizer is None and self.fused_optimizer and default_adamw and isinstance(core, HipQwen3ForCausalLM)
+        if (self.optimizer is None and self.fused_optimizer and self._default_adamw() and isinstance(core, HipQwen3ForCausalLM)
                 and core.flat.is_cuda and (core._lora is not None or all(p.requires_grad for p in core.parameters()))):
             self.optimizer = self._flat_adamw(core)
             return self.optimizer
@@ -340,15 +380,7 @@ class DistillationTrainer(FlatStudentTrainer):
         # (HF calls create_optimizer(model) on its delay_optimizer_creation path: FSDP / SageMaker model parallel)
         return super().create_optimizer(model) if model is not None else super().create_optimizer()
 
-    @staticmethod
-    def _rows_key(lab, speech_mask, am, tam, cu=None):
-        return (id(lab), lab.data_ptr(), tuple(lab.shape), None if speech_mask is None else speech_mask.data_ptr(),
-                None if am is None else am.data_ptr(), None if tam is None else tam.data_ptr(),
-                None if cu is None else cu.data_ptr())
-
     # ------------------------------------------------------------------------------ packed (padding-free) batches
-    PACKED_KEYS = ("position_ids", "cu_seq_lens_q", "cu_seq_lens_k", "max_length_q", "max_length_k")
-
     @staticmethod
     def _is_packed(batch):
         """A batch is packed by its keys, exactly when HF Qwen3 and HipQwen3ForCausalLM pack: ``position_ids`` present and
@@ -411,6 +443,73 @@ class DistillationTrainer(FlatStudentTrainer):
             start[:, 1:] = pos[:, 1:] != pos[:, :-1] + 1
         return torch.where(start, torch.full_like(labels, -100), labels)
 
+    # ------------------------------------------------------------------------------ the step plan and what is done ahead
+    def _plan_step(self, core, batch, lab, speech_mask, teacher_mask, need_teacher, select=True, event=None, stored=None):
+        """The ``StepPlan`` of one micro-batch: the step's ONE host read (the row count and, in the same read, the segment
+        or padding checks) and the forward keywords that follow from it.  ``event``: planned ahead, on the copy stream
+        that records it; ``stored``: a plan made ahead for these labels, returned when its key still matches (else the
+        selection is redone); ``select=False``: the caller takes the full [B, T, V] path, only what the models need is made.
+        * packed with ``cu_seq_lens_q``: always selected -- the descriptors come out of the same read;
+        * packed by ``position_ids`` alone: the models read the segments themselves, and the rows come from the labels with
+          every document start masked, so that none crosses a document boundary.  Never planned ahead (-> None);
+        * padded: only masks laid out on the labels' [B, T] grid go into the fused right-padding check (the teacher's only
+          for a HIP teacher that will run); any other keeps its own validation in the model's forward (no ``padding_checked``)."""
+        if lab is None:
+            return StepPlan()
+        packed = self._is_packed(batch)
+        cu = batch.get("cu_seq_lens_q") if packed else None
+        hip_teacher = isinstance(self.teacher_model, HipQwen3ForCausalLM)
+        full_labels = am = tam = None
+        if cu is not None and event is not None:   # planned ahead: refused before its first launch (compute_loss refuses its own)
+            self._check_packed(batch, batch.get("teacher_input_ids"), teacher_mask)
+        if cu is None:
+            if packed:
+                if event is not None:
+                    return None
+                full_labels = self._document_start_labels(lab, batch)
+            if not select:
+                return StepPlan(full_labels=full_labels)
+            am, tam = batch.get("attention_mask"), (teacher_mask if hip_teacher and need_teacher else None)
+            am, tam = (m if m is not None and tuple(m.shape) == tuple(lab.shape) else None for m in (am, tam))
+        key = (id(lab), lab.data_ptr(), tuple(lab.shape)) + tuple(None if t is None else t.data_ptr()
+                                                                  for t in (speech_mask, am, tam, cu))
+        if stored is not None and stored.key == key:
+            return stored
+        if cu is not None:
+            rows, row_labels, pbs = self._select_packed(core, batch, lab, speech_mask)
+            student_kw, teacher_kw = ({"packed_batch": pb} if pb is not None else {} for pb in pbs)
+        else:
+            rows, row_labels = ops.loss_rows(lab if full_labels is None else full_labels, speech_mask, right_padded=(am, tam))
+            pbs = None
+            student_kw = {"padding_checked": True} if am is not None or batch.get("attention_mask") is None else {}
+            teacher_kw = {"padding_checked": True} if hip_teacher and (tam is not None or teacher_mask is None) else {}
+        return StepPlan(rows, row_labels, pbs, student_kw, teacher_kw, event, key, full_labels)
+
+    def _drop_lookahead(self):
+        """Nothing is planned, fetched or enqueued ahead."""
+        self._ahead = {}   # id(labels) -> _Ahead, of the micro-batches of this accumulation window and the next
+        self._window, self._prefetched = [], None
+
+    def _start_teacher(self, core, batch, teacher_input_ids, teacher_mask, plan):
+        """``_teacher_pass`` on the teacher's own stream.  It waits for the batch -- the plan's event, not whatever else the
+        main stream still has queued -- or, for a batch planned in place, for the main stream.  Two passes then share the
+        GPU and both are told (``concurrent``: SD_FWD_CONCURRENT, include/sd_hip.h)."""
+        ids = batch.get("input_ids")
+        if self._teacher_stream is None:
+            self._teacher_stream = ops.concurrent_stream(ids.device, "teacher")
+        side = self._teacher_stream
+        if plan.event is not None:
+            side.wait_event(plan.event)
+            for t in [ids, teacher_input_ids, teacher_mask, batch.get("attention_mask"), plan.rows,
+                      batch.get("position_ids")] + self._packed_tensors(plan.packed):
+                if torch.is_tensor(t) and t.is_cuda:
+                    t.record_stream(side)
+        else:
+            side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            return self._teacher_pass(batch, teacher_input_ids, teacher_mask, core.dims.vocab_size, plan.rows,
+                                      dict(plan.teacher_kw, concurrent=True))
+
     def get_batch_samples(self, epoch_iterator, num_batches, device):
         """HF fetches the micro-batches of one optimizer step here, together, right after it has enqueued the previous
         optimizer step.  Two things are done with that (``SD_ROWS_AHEAD=0`` turns both off):
@@ -428,77 +527,60 @@ class DistillationTrainer(FlatStudentTrainer):
         ahead = (self.compact_head and os.environ.get("SD_ROWS_AHEAD", "1") != "0" and isinstance(core, HipQwen3ForCausalLM)
                  and core.flat.is_cuda and isinstance(self.distill_loss_fn, DistillationLoss) and self.lmbda == 0)
         if not ahead:
-            self._rows_ahead.clear()
-            self._window, self._window_next, self._ahead_results, self._prefetched = [], [], {}, None
+            self._drop_lookahead()
             batch_samples, num_items = super().get_batch_samples(epoch_iterator, num_batches, device)
             if self.lmbda > 0 and self.on_policy_rollout == "window":   # the whole window's rollouts, before its first step
                 batch_samples = self._roll_out_window(batch_samples)
             return batch_samples, num_items
         # window k comes from the previous call's lookahead when there is one (same iterator object = same epoch)
         pre, self._prefetched = self._prefetched, None
-        if pre is not None and pre[0] is epoch_iterator:
-            batch_samples, num_items, selected, ready = pre[1]
+        if pre is not None and pre[0] is epoch_iterator:   # (its plans, and a teacher's result, are in the table already)
+            batch_samples, num_items, ready = pre[1]
         else:
-            batch_samples, num_items, selected, ready = self._fetch_window(core, epoch_iterator, num_batches, device)
+            batch_samples, num_items, ready = self._fetch_window(core, epoch_iterator, num_batches, device)
         main = torch.cuda.current_stream(core.flat.device)
         main.wait_event(ready)
         live = {id(b.get("labels")) for b in batch_samples if isinstance(b, dict)}
-        self._rows_ahead = {k: v for k, v in self._rows_ahead.items() if k in live}
-        self._ahead_results = {k: v for k, v in self._ahead_results.items() if k in live}
-        for key, rr in selected:
-            self._rows_ahead[key[0]] = (key, rr, ready)
-        self._window, self._window_next = list(batch_samples), []
+        self._ahead = {k: v for k, v in self._ahead.items() if k in live}
+        self._window = list(batch_samples)   # the micro-batches in the order they are trained on: this window, then the next
         # ... and window k+1 is fetched NOW (lock-step host only: HF's per-micro-batch read on), so that the last
         # training_step of window k can enqueue the teacher's pass for its first micro-batch beside the optimizer step
         mode = os.environ.get("SD_WINDOW_AHEAD", "auto")
         if batch_samples and (mode == "1" or (mode == "auto" and self.args.logging_nan_inf_filter)):
             nxt = self._fetch_window(core, epoch_iterator, num_batches, device)
             self._prefetched = (epoch_iterator, nxt)
-            self._window_next = list(nxt[0])
-            for key, rr in nxt[2]:
-                self._rows_ahead[key[0]] = (key, rr, nxt[3])
+            self._window += list(nxt[0])
         return batch_samples, num_items
 
     def _fetch_window(self, core, epoch_iterator, num_batches, device):
-        """HF's fetch of one accumulation window + the loss-row selection of its micro-batches, on the copy stream.
-        Returns (batch_samples, num_items_in_batch, [(key, (rows, row_labels, packed descriptors or None))], event)."""
+        """HF's fetch of one accumulation window + the plans of its micro-batches (CUDA tensor labels only), on the copy
+        stream; the plans go into the table.  Returns (batch_samples, num_items_in_batch, event)."""
         main = torch.cuda.current_stream(core.flat.device)
         if self._copy_stream is None:
             self._copy_stream = ops.concurrent_stream(core.flat.device, "h2d")
         cs = self._copy_stream
-        hip_teacher = isinstance(self.teacher_model, HipQwen3ForCausalLM)
+        ready = torch.cuda.Event()
         with torch.cuda.stream(cs):
             batch_samples, num_items = super().get_batch_samples(epoch_iterator, num_batches, device)
-            selected = []
+            plans = []
             for b in batch_samples:
                 lab = b.get("labels") if isinstance(b, dict) else None
-                if lab is None or not torch.is_tensor(lab) or not lab.is_cuda:
-                    continue
-                need_teacher = b.get("teacher_top_k_v") is None and self.teacher_model is not None
-                sm = b.get("speech_token_mask")
-                if self._is_packed(b) and b.get("cu_seq_lens_q") is None:
-                    continue   # segments by position_ids alone: selected in compute_loss, after the document starts are masked
-                if self._is_packed(b):
-                    self._check_packed(b, b.get("teacher_input_ids"), b.get("teacher_attention_mask"))
-                    selected.append((self._rows_key(lab, sm, None, None, b["cu_seq_lens_q"]),
-                                     self._select_packed(core, b, lab, sm)))
-                    continue
-                am = b.get("attention_mask")
-                tam = b.get("teacher_attention_mask") if hip_teacher and need_teacher else None
-                am = am if am is not None and tuple(am.shape) == tuple(lab.shape) else None
-                tam = tam if tam is not None and tuple(tam.shape) == tuple(lab.shape) else None
-                selected.append((self._rows_key(lab, sm, am, tam), ops.loss_rows(lab, sm, right_padded=(am, tam)) + (None,)))
-            ready = torch.cuda.Event()
+                if torch.is_tensor(lab) and lab.is_cuda:
+                    need_teacher = b.get("teacher_top_k_v") is None and self.teacher_model is not None
+                    plans.append(self._plan_step(core, b, lab, b.get("speech_token_mask"), b.get("teacher_attention_mask"),
+                                                 need_teacher, event=ready))
             ready.record(cs)
+        plans = [p for p in plans if p is not None]
+        self._ahead.update((p.key[0], _Ahead(p)) for p in plans)
         # the tensors were allocated on the copy stream and are used on the main and the teacher's stream
         users = [main] + ([self._teacher_stream] if self._teacher_stream is not None else [])
         held = [t for b in batch_samples if isinstance(b, dict) for t in b.values() if torch.is_tensor(t) and t.is_cuda]
-        held += [t for _, rr in selected for t in list(rr[:2]) + self._packed_tensors(rr[2])]
+        held += [t for p in plans for t in [p.rows, p.row_labels] + self._packed_tensors(p.packed)]
         held += [num_items] if torch.is_tensor(num_items) and num_items.is_cuda else []
         for t in held:
             for st in users:
                 t.record_stream(st)
-        return batch_samples, num_items, selected, ready
+        return batch_samples, num_items, ready
 
     _TEACHER_SIDE_KEYS = ("teacher_input_ids", "teacher_attention_mask", "speech_token_mask", "teacher_top_k_v", "teacher_top_k_i",
                           "teacher_top_k_tail")
@@ -533,35 +615,21 @@ class DistillationTrainer(FlatStudentTrainer):
 
     def _launch_teacher_ahead(self, cur_id):
         """Enqueue the frozen teacher's pass for the micro-batch that follows ``cur_id`` in this accumulation window."""
-        seq = self._window + self._window_next   # (the next window's first micro-batch follows this window's last)
+        seq = self._window   # (the next window's first micro-batch follows this window's last)
         idx = next((i for i, b in enumerate(seq) if isinstance(b, dict) and id(b.get("labels")) == cur_id), None)
         if idx is None or idx + 1 >= len(seq):
             return
         nxt = seq[idx + 1]
         lab = nxt.get("labels")
-        entry = self._rows_ahead.get(id(lab))
+        entry = self._ahead.get(id(lab))
         core = ddp.unwrap(self.model)
         ids, tids = nxt.get("input_ids"), nxt.get("teacher_input_ids")
-        if (entry is None or entry[1][0].numel() == 0 or not self.overlap_teacher or nxt.get("teacher_top_k_v") is not None
+        if (entry is None or entry.plan.rows.numel() == 0 or not self.overlap_teacher or nxt.get("teacher_top_k_v") is not None
                 or not isinstance(self.teacher_model, HipQwen3ForCausalLM) or not isinstance(core, HipQwen3ForCausalLM)
                 or ids is None or (tids is not None and tuple(tids.shape) != tuple(ids.shape))):
             return
-        _, (rows, _, pbs), fetched = entry
-        tam = nxt.get("teacher_attention_mask")
-        aligned = tam is not None and tuple(tam.shape) == tuple(lab.shape)
-        kw = dict({"padding_checked": True} if aligned or tam is None else {}, concurrent=True)
-        if pbs is not None:
-            kw = dict(concurrent=True, packed_batch=pbs[1])
-        if self._teacher_stream is None:
-            self._teacher_stream = ops.concurrent_stream(ids.device, "teacher")
-        side = self._teacher_stream
-        side.wait_event(fetched)
-        for t in [ids, tids, tam, nxt.get("attention_mask"), rows, nxt.get("position_ids")] + self._packed_tensors(pbs):
-            if torch.is_tensor(t) and t.is_cuda:
-                t.record_stream(side)
         base = {k: v for k, v in nxt.items() if k not in self._TEACHER_SIDE_KEYS}
-        with torch.cuda.stream(side):
-            self._ahead_results[id(lab)] = self._teacher_pass(base, tids, tam, core.dims.vocab_size, rows, kw)
+        entry.teacher = self._start_teacher(core, base, tids, nxt.get("teacher_attention_mask"), entry.plan)
 
     def _load_best_model(self):
         """HF's loader looks for ``model.safetensors``; a LoRA student's checkpoints hold the adapter (``_save`` above)."""
@@ -603,142 +671,82 @@ class DistillationTrainer(FlatStudentTrainer):
         return teacher_logits, None, None, None
 
     def compute_loss(self, model, inputs, return_outputs=False, **kwargs):
-        teacher_input_ids = inputs.pop("teacher_input_ids", None)
-        teacher_attention_mask = inputs.pop("teacher_attention_mask", None)
-        speech_mask = inputs.pop("speech_token_mask", None)
-        teacher_top_k_v = inputs.pop("teacher_top_k_v", None)
-        teacher_top_k_i = inputs.pop("teacher_top_k_i", None)
-        teacher_top_k_tail = inputs.pop("teacher_top_k_tail", None)   # (read by the _tail divergences only)
-
+        """Pop the teacher's keys and refuse what cannot be computed  ->  count the tokens  ->  the plan (made ahead, or
+        here)  ->  the teacher's result (enqueued ahead, on its stream now, gathered from the pre-extracted top-K, or after
+        the student as in the reference)  ->  student forward  ->  join  ->  loss on the plan's rows  ->  log."""
+        (teacher_input_ids, teacher_attention_mask, speech_mask, teacher_top_k_v, teacher_top_k_i,
+         teacher_top_k_tail) = (inputs.pop(k, None) for k in self._TEACHER_SIDE_KEYS)   # (the tail: the _tail divergences only)
         if ops.takes_dense_teacher(self.divergence) and teacher_top_k_v is not None:
             raise ValueError(f"divergence={self.divergence!r} needs the dense teacher distribution; this batch carries "
                              "pre-extracted teacher_top_k_v (K entries per position)")
         need_teacher = teacher_top_k_v is None and self.teacher_model is not None
-        ids0 = inputs.get("input_ids")
+        ids = inputs.get("input_ids")
         packed = self._check_packed(inputs, teacher_input_ids, teacher_attention_mask)
-        if (need_teacher and teacher_input_ids is not None and ids0 is not None
-                and tuple(teacher_input_ids.shape) != tuple(ids0.shape)):
+        if (need_teacher and teacher_input_ids is not None and ids is not None
+                and tuple(teacher_input_ids.shape) != tuple(ids.shape)):
             # The collator pads teacher and student separately (data.py:219-278) and the loss indexes both with ONE
             # [B, T-1] row mask (distillation_loss.py:31-45): the reference dies there with an IndexError.  Same
             # condition, named, before any kernel indexes a [B, T_teacher] tensor with the student's T.
-            raise ValueError(f"teacher_input_ids {tuple(teacher_input_ids.shape)} and input_ids {tuple(ids0.shape)} must be "
+            raise ValueError(f"teacher_input_ids {tuple(teacher_input_ids.shape)} and input_ids {tuple(ids.shape)} must be "
                              "position-aligned (data.py:20-60 align_prefixes): the loss selects rows of both with one mask")
-        if model.training and ids0 is not None:
-            self.tokens_seen += ids0.numel()
-            if self._tps_mark is None:
-                self._tps_mark = (time.perf_counter(), self.tokens_seen - ids0.numel())
+        self._count_tokens(model, ids)
+
         # `model` is what the loop trains (HipDataParallel / torch DDP / the bare module); `core` is the module itself
         core = ddp.unwrap(model)
         hip_student = isinstance(core, HipQwen3ForCausalLM)
-        hip_teacher = isinstance(self.teacher_model, HipQwen3ForCausalLM)
-        vocab = getattr(getattr(core, "dims", None), "vocab_size", None)  # only our own model type is overlapped
-        side = None
-        fetched = None
-        ids = inputs.get("input_ids")
-        rows = row_labels = None
         lab = inputs.get("labels")
-        checked = {}
-        pbs = None
-        full_labels = None   # packed: the labels with -100 at every document start, where this step needs them
-        if packed and lab is not None and inputs.get("cu_seq_lens_q") is None:
-            full_labels = self._document_start_labels(lab, inputs)
-        if packed and lab is not None and inputs.get("cu_seq_lens_q") is not None:
-            # the one host read of a packed step: row count, segment check, longest document, largest position
-            key = self._rows_key(lab, speech_mask, None, None, inputs["cu_seq_lens_q"])
-            hit = self._rows_ahead.pop(key[0], None)
-            if hit is not None and hit[0] == key:
-                (rows, row_labels, pbs), fetched = hit[1], hit[2]
-            else:
-                rows, row_labels, pbs = self._select_packed(core, inputs, lab, speech_mask)
-            if pbs[0] is not None:
-                checked = {"packed_batch": pbs[0]}
-            teacher_checked = {"packed_batch": pbs[1]} if pbs[1] is not None else {}
-            if (rows.numel() == 0 or not self.compact_head or return_outputs or not hip_student or not lab.is_cuda
-                    or not isinstance(self.distill_loss_fn, DistillationLoss)):
-                rows = row_labels = None     # the full path; the descriptors still serve both models
-                fetched = None
-        elif (self.compact_head and not return_outputs and hip_student and lab is not None
-                and lab.is_cuda and isinstance(self.distill_loss_fn, DistillationLoss)):
-            # the one host read of the step: the row count, and (same read) that the masks are right-padded
-            # only masks laid out on the labels' [B, T] grid go into the fused check; any other keeps its own validation
-            # in the model's forward (padding_checked stays unset for it)
-            am, tam = inputs.get("attention_mask"), (teacher_attention_mask if hip_teacher and need_teacher else None)
-            am = am if am is not None and tuple(am.shape) == tuple(lab.shape) else None
-            tam = tam if tam is not None and tuple(tam.shape) == tuple(lab.shape) else None
-            key = self._rows_key(lab, speech_mask, am, tam)
-            hit = self._rows_ahead.pop(key[0], None)
-            if hit is not None and hit[0] == key:   # selected with the accumulation window's other batches (get_batch_samples)
-                rows, row_labels = hit[1][:2]
-                fetched = hit[2]                    # event: this batch (and its rows) are on the device
-            else:   # (position_ids without cu_seq_lens: the models read the segments themselves, and the rows come from
-                # the labels with every document start masked, so that none crosses a document boundary)
-                rows, row_labels = ops.loss_rows(full_labels if packed else lab, speech_mask, right_padded=(am, tam))
-            checked = {"padding_checked": True} if am is not None or inputs.get("attention_mask") is None else {}
-            teacher_checked = {"padding_checked": True} if tam is not None or teacher_attention_mask is None else {}
-            if rows.numel() == 0:  # N == 0: the full path returns the reference's zeros (distillation_loss.py:47-53)
-                rows = row_labels = None
-        else:
-            teacher_checked = {}
-        teacher_kw = teacher_checked if hip_teacher else {}
-        ahead = self._ahead_results.pop(id(lab), None) if fetched is not None and rows is not None else None
-        if ahead is not None:   # SD_TEACHER_AHEAD: this batch's teacher pass was enqueued at the end of the previous micro-step
-            side = self._teacher_stream
-            teacher_logits, teacher_top_k_v, teacher_top_k_i, teacher_top_k_tail = ahead
-            if hip_student:
-                checked = dict(checked, concurrent=True)
-        elif (need_teacher and self.overlap_teacher and vocab is not None and ids is not None and ids.is_cuda
-                and hip_teacher):
-            if self._teacher_stream is None:
-                self._teacher_stream = ops.concurrent_stream(ids.device, "teacher")
-            side = self._teacher_stream
-            if fetched is not None:   # the teacher needs the batch, not whatever else the main stream still has queued
-                side.wait_event(fetched)
-                for t in [ids, teacher_input_ids, teacher_attention_mask, inputs.get("attention_mask"), rows,
-                          inputs.get("position_ids")] + self._packed_tensors(pbs):
-                    if torch.is_tensor(t) and t.is_cuda:
-                        t.record_stream(side)
-            else:
-                side.wait_stream(torch.cuda.current_stream())
-            # two passes share the GPU from here to the loss: both are told (SD_FWD_CONCURRENT, include/sd_hip.h)
-            teacher_kw = dict(teacher_kw, concurrent=True)
-            if hip_student:
-                checked = dict(checked, concurrent=True)
-            with torch.cuda.stream(side):
-                teacher_logits, teacher_top_k_v, teacher_top_k_i, teacher_top_k_tail = self._teacher_pass(
-                    inputs, teacher_input_ids, teacher_attention_mask, vocab, rows, teacher_kw)
-        elif rows is not None and teacher_top_k_v is not None:  # pre-extracted top-K: keep the same rows
-            dev = lab.device
-            teacher_top_k_v = teacher_top_k_v.to(dev).reshape(-1, teacher_top_k_v.size(-1))[rows]
-            teacher_top_k_i = teacher_top_k_i.to(dev).reshape(-1, teacher_top_k_i.size(-1))[rows]
-            if teacher_top_k_tail is not None:
-                teacher_top_k_tail = teacher_top_k_tail.to(dev).reshape(-1)[rows]
+        compact = (self.compact_head and not return_outputs and hip_student and lab is not None and lab.is_cuda
+                   and isinstance(self.distill_loss_fn, DistillationLoss))
+        ahead = self._ahead.pop(id(lab), None)   # planned with the accumulation window's other batches (get_batch_samples)
+        plan = self._plan_step(core, inputs, lab, speech_mask, teacher_attention_mask, need_teacher, select=compact,
+                               stored=None if ahead is None else ahead.plan)
+        if ahead is not None and ahead.plan is not plan:   # made from other tensors: discarded with what was enqueued for it
+            ahead = None
+        if not compact or plan.rows.numel() == 0:
+            # The full [B, T, V] path (with no row it returns the reference's zeros, distillation_loss.py:47-53).  What the
+            # plan has checked still serves both models; a packed batch is then taken as made in place.
+            plan = plan._replace(rows=None, row_labels=None, event=None if plan.packed is not None else plan.event)
+            ahead = None
 
-        outputs = model(**inputs, **checked) if rows is None else model(**inputs, logit_rows=rows, **checked)  # train.py:54
+        side, teacher = None, (None, teacher_top_k_v, teacher_top_k_i, teacher_top_k_tail)
+        if ahead is not None and ahead.teacher is not None:   # SD_TEACHER_AHEAD: enqueued at the end of the previous micro-step
+            side, teacher = self._teacher_stream, ahead.teacher
+        elif (need_teacher and self.overlap_teacher and ids is not None and ids.is_cuda
+                and isinstance(self.teacher_model, HipQwen3ForCausalLM)
+                and getattr(getattr(core, "dims", None), "vocab_size", None) is not None):   # only our own model type is overlapped
+            teacher = self._start_teacher(core, inputs, teacher_input_ids, teacher_attention_mask, plan)
+            side = self._teacher_stream
+        elif plan.rows is not None and teacher_top_k_v is not None:  # pre-extracted top-K: keep the same rows
+            v, i, tail = ((None if t is None else t.to(lab.device)) for t in teacher[1:])
+            teacher = (None, v.reshape(-1, v.size(-1))[plan.rows], i.reshape(-1, i.size(-1))[plan.rows],
+                       None if tail is None else tail.reshape(-1)[plan.rows])
+
+        student_kw = dict(plan.student_kw, concurrent=True) if side is not None and hip_student else plan.student_kw
+        if plan.rows is not None:
+            student_kw = dict(student_kw, logit_rows=plan.rows)
+        outputs = model(**inputs, **student_kw)  # train.py:54
         student_logits = outputs.logits
         labels = inputs.pop("labels", None)
-        if packed and rows is None and labels is not None:   # the full [1, M, V] path shifts across the flat row itself
-            labels = full_labels if full_labels is not None else self._document_start_labels(labels, inputs)
+        if packed and plan.rows is None and labels is not None:   # the full [1, M, V] path shifts across the flat row itself
+            labels = plan.full_labels if plan.full_labels is not None else self._document_start_labels(labels, inputs)
 
-        teacher_logits_local = None
         if side is not None:
             torch.cuda.current_stream().wait_stream(side)
-            # allocated on the teacher's stream, read on this one
-            for t in (teacher_logits, teacher_top_k_v, teacher_top_k_i, teacher_top_k_tail):
+            for t in teacher:   # allocated on the teacher's stream, read on this one
                 if torch.is_tensor(t) and t.is_cuda:
                     t.record_stream(torch.cuda.current_stream())
-            teacher_logits_local = teacher_logits
         elif need_teacher:  # reference order: student first, then teacher (train.py:60-94)
-            teacher_logits_local, teacher_top_k_v, teacher_top_k_i, teacher_top_k_tail = self._teacher_pass(
-                inputs, teacher_input_ids, teacher_attention_mask, student_logits.size(-1), rows, teacher_kw)
-        teacher_logits = teacher_logits_local
+            teacher = self._teacher_pass(inputs, teacher_input_ids, teacher_attention_mask, student_logits.size(-1),
+                                         plan.rows, plan.teacher_kw)
+        teacher_logits, teacher_top_k_v, teacher_top_k_i, teacher_top_k_tail = teacher
 
         if isinstance(self.distill_loss_fn, DistillationLoss):
             self.distill_loss_fn.inplace_grad = (not return_outputs) and hip_student
         # (the tail goes to the _tail divergences only: any other loss, a caller's own included, keeps its signature)
         tail_kw = {"teacher_top_k_tail": teacher_top_k_tail} if self.divergence in ops.TAIL_DIVERGENCES else {}
-        if rows is not None:
+        if plan.rows is not None:
             loss, task_loss, distill_loss, teacher_loss = self.distill_loss_fn.forward_rows(
-                student_logits, row_labels, teacher_logits=teacher_logits, teacher_top_k_v=teacher_top_k_v,
+                student_logits, plan.row_labels, teacher_logits=teacher_logits, teacher_top_k_v=teacher_top_k_v,
                 teacher_top_k_i=teacher_top_k_i, **tail_kw)
         else:
             loss, task_loss, distill_loss, teacher_loss = self.distill_loss_fn(
@@ -765,14 +773,8 @@ class Stage1Trainer(FlatStudentTrainer):
     tokens/sec in the training log.  Single GPU.  Batches: ``stage1.Stage1Collator`` (input_ids, attention_mask, labels; or,
     with ``padding_free=True``, input_ids, labels, position_ids and the flash-attn varlen keys, passed through)."""
 
-    PACKED_KEYS = ("position_ids", "cu_seq_lens_q", "cu_seq_lens_k", "max_length_q", "max_length_k")
-
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
-        self.tokens_seen = 0
-        self._tps_mark = None
-        self._hip_dp = None
-        self.fused_optimizer = True
         if self.args.world_size > 1:
             raise NotImplementedError("Stage-1 alignment runs on one GPU (multi-GPU Stage-1 is not implemented)")
         # compute_loss passes num_items_in_batch to the model itself; HF must then neither drop the count nor divide the
@@ -781,8 +783,7 @@ class Stage1Trainer(FlatStudentTrainer):
 
     def create_optimizer(self, model=None):
         core = ddp.unwrap(self.model)
-        default_adamw = str(getattr(self.args.optim, "value", self.args.optim)).startswith("adamw_torch")
-        if (self.optimizer is None and self.fused_optimizer and default_adamw and isinstance(core, HipQwen3ForCausalLM)
+        if (self.optimizer is None and self.fused_optimizer and self._default_adamw() and isinstance(core, HipQwen3ForCausalLM)
                 and core.flat.is_cuda and core.stage1_row_lo is not None):
             core.check_stage1()
             self.optimizer = self._flat_adamw(core)
@@ -791,10 +792,7 @@ class Stage1Trainer(FlatStudentTrainer):
 
     def compute_loss(self, model, inputs, return_outputs=False, num_items_in_batch=None, **kwargs):
         ids = inputs["input_ids"]
-        if model.training:
-            self.tokens_seen += ids.numel()
-            if self._tps_mark is None:  # first training micro-batch: the clock of the first tokens/sec figure starts here
-                self._tps_mark = (time.perf_counter(), self.tokens_seen - ids.numel())
+        self._count_tokens(model, ids)
         packed = {k: inputs[k] for k in self.PACKED_KEYS if inputs.get(k) is not None}
         out = model(input_ids=ids, attention_mask=inputs.get("attention_mask"), labels=inputs["labels"],
                     num_items_in_batch=num_items_in_batch, stage1_inplace_grad=not return_outputs, **packed)

@@ -390,26 +390,47 @@ def test_real_train_loop_packed_with_and_without_the_lookaheads(sda, c1, monkeyp
     """Three optimizer steps of a real ``Trainer.train()`` (two samples per packed micro-batch, accumulation 2) with the
     lookaheads on (rows ahead, teacher ahead, window ahead) and with SD_ROWS_AHEAD=0: the same micro-batches in the same
     order, by the method of test_window_lookahead_serves_the_same_batches_in_the_same_order, finite logged losses, and the
-    bound that test uses for the two runs' losses: equality (both runs launch the same kernels on the same data)."""
+    bound that test uses for the two runs' losses: equality (both runs launch the same kernels on the same data).  Also one
+    selection (``ops.loss_rows`` + ``ops.packed_rows``) per micro-batch.  With the lookaheads on this is counted per FETCHED
+    micro-batch, not per trained one as in the padded test (whose loop ends with its iterator): ``max_steps`` stops this loop
+    with the fourth window already fetched ahead, so 8 selections stand against 6 trained micro-batches."""
+    from transformers import Trainer
+    from speech_distill_amd import ops
     rows = c1["feats"] * 2
 
     def run(ahead):
         monkeypatch.setenv("SD_ROWS_AHEAD", "1" if ahead else "0")
         tr, student, _ = _trainer(sda, c1, 16, rows=rows, per_device_train_batch_size=2, max_steps=3, seed=7, data_seed=7)
-        seen, early, inner = [], [], tr.compute_loss
+        seen, early, reads, in_step, fetched, inner, hf_fetch = [], [], [], [], [], tr.compute_loss, Trainer.get_batch_samples
+
+        def fetch(self, *a, **k):    # HF's own fetch of one accumulation window, under the trainer's override
+            out = hf_fetch(self, *a, **k)
+            fetched.extend(out[0])
+            return out
 
         def spy(model, inputs, *a, **k):
             assert "attention_mask" not in inputs and inputs["input_ids"].shape[0] == 1
             seen.append(inputs["input_ids"].cpu().clone())
-            early.append(id(inputs["labels"]) in tr._ahead_results)
-            return inner(model, inputs, *a, **k)
+            early.append(getattr(tr._ahead.get(id(inputs["labels"])), "teacher", None) is not None)
+            n0 = len(reads)
+            out = inner(model, inputs, *a, **k)
+            in_step.append(len(reads) - n0)
+            return out
         tr.compute_loss = spy
-        tr.train()
-        return seen, early, [h["loss"] for h in tr.state.log_history if "loss" in h], student.flat.clone(), tr.tokens_seen
-    seen_a, early_a, loss_a, flat_a, tok_a = run(True)
-    seen_b, early_b, loss_b, flat_b, tok_b = run(False)
-    print("packed train loop losses:", loss_a, loss_b, "early:", early_a)
+        with monkeypatch.context() as mp:
+            mp.setattr(Trainer, "get_batch_samples", fetch)
+            for name in ("loss_rows", "packed_rows"):   # the selections, each with the micro-batch's one host read
+                mp.setattr(ops, name, lambda *a, _f=getattr(ops, name), **k: reads.append(1) or _f(*a, **k))
+            tr.train()
+        return (seen, early, [h["loss"] for h in tr.state.log_history if "loss" in h], student.flat.clone(), tr.tokens_seen,
+                (len(reads), in_step, len(fetched)))
+    seen_a, early_a, loss_a, flat_a, tok_a, reads_a = run(True)
+    seen_b, early_b, loss_b, flat_b, tok_b, reads_b = run(False)
+    print("packed train loop losses:", loss_a, loss_b, "early:", early_a, "selections:", reads_a, reads_b)
     assert len(seen_a) == len(seen_b) == 6 and len(loss_a) == len(loss_b) == 3
+    # One selection (one host read) per micro-batch, made ahead or in compute_loss, never both.  max_steps stops the loop
+    # with the fourth window already fetched ahead: its two micro-batches were fetched and selected, and never trained on.
+    assert reads_b == (6, [1] * 6, 6) and reads_a == (8, [0] * 6, 8)
     for a, b in zip(seen_a, seen_b):
         assert a.shape == b.shape and torch.equal(a, b)
     assert tok_a == tok_b == sum(s.numel() for s in seen_a)           # tokens_seen counts M

@@ -370,6 +370,41 @@ def test_teacher_batch_of_another_length_is_refused_on_the_gpu_path(sda):
     assert float(a) == float(b) and float(a) > 0
 
 
+def test_zero_row_batch_planned_ahead_takes_the_full_path(sda, monkeypatch):
+    """``compute_loss``'s own zero-row fall-back with a HIP student on the GPU: a padded batch without a loss row gives the
+    reference's zeros (distillation_loss.py:47-53) when it is planned in place, and the same when its plan was made ahead --
+    the stored plan is taken (no second selection) although no row of it is used, and it keeps its event, which the
+    teacher's stream then waits for."""
+    from transformers import TrainingArguments
+    from speech_distill_amd import ops
+    from speech_distill_amd.trainer import DistillationTrainer, _Ahead
+    z, st, te, sw, tw, feats, pad, bos = _c1(sda)
+    student, teacher = _build(sda, st, sw), _build(sda, te, tw)
+    teacher.eval().requires_grad_(False)
+    args = TrainingArguments(output_dir=tempfile.mkdtemp(), report_to=[], remove_unused_columns=False, label_names=["labels"],
+                             save_strategy="no", logging_steps=1, bf16=True)
+    tr = DistillationTrainer(model=student, args=args, teacher_model=teacher, temperature=2.0, alpha=0.5, top_k=16)
+    logged, reads = [], []
+    tr.log = lambda d, *a, **k: logged.append(dict(d))
+    monkeypatch.setattr(ops, "loss_rows", lambda *a, _f=ops.loss_rows, **k: reads.append(1) or _f(*a, **k))
+    ids = torch.randint(0, 640, (2, 40), generator=torch.Generator().manual_seed(0))
+    batch = {"input_ids": to_dev(ids), "attention_mask": to_dev(torch.ones_like(ids)), "labels": to_dev(torch.full_like(ids, -100)),
+             "teacher_input_ids": to_dev(ids), "teacher_attention_mask": to_dev(torch.ones_like(ids))}
+    zeros = {"student_loss": 0.0, "teacher_loss": 0.0, "distill_loss": 0.0}
+    in_place = tr.compute_loss(student, dict(batch))
+    n_in_place = len(reads)
+    assert float(in_place) == 0.0 and logged[-1] == zeros and n_in_place >= 1
+    ready = torch.cuda.Event()
+    ready.record()
+    plan = tr._plan_step(student, batch, batch["labels"], None, batch["teacher_attention_mask"], True, event=ready)
+    assert plan.rows.numel() == 0 and plan.event is ready and plan.student_kw == plan.teacher_kw == {"padding_checked": True}
+    tr._ahead[id(batch["labels"])] = _Ahead(plan)
+    del reads[:]
+    ahead = tr.compute_loss(student, dict(batch))
+    assert float(ahead) == 0.0 and logged[-1] == zeros and not tr._ahead
+    assert len(reads) == n_in_place - 1      # the selection was not made again
+
+
 def test_window_lookahead_serves_the_same_batches_in_the_same_order(sda, monkeypatch):
     """DistillationTrainer.get_batch_samples fetches one accumulation window ahead and training_step enqueues the next
     micro-batch's teacher pass early (both only re-order host work).  Over two epochs whose last window is a remainder
@@ -378,6 +413,7 @@ def test_window_lookahead_serves_the_same_batches_in_the_same_order(sda, monkeyp
     same parameters as with the plain HF order (SD_ROWS_AHEAD=0)."""
     import tempfile
     from transformers import TrainingArguments
+    from speech_distill_amd import ops
     from speech_distill_amd.collator import ProcessedDataCollator
     from speech_distill_amd.trainer import DistillationTrainer
     z, st, te, sw, tw, feats, pad, bos = _c1(sda)
@@ -401,19 +437,23 @@ def test_window_lookahead_serves_the_same_batches_in_the_same_order(sda, monkeyp
             warmup_steps=0, max_grad_norm=1.0, dataloader_num_workers=0, bf16=True)
         tr = DistillationTrainer(model=student, args=args, train_dataset=DS(), teacher_model=teacher, temperature=2.0,
                                  alpha=0.5, top_k=16, data_collator=ProcessedDataCollator(_Tok(pad, bos), pad_token_id=pad))
-        seen, early = [], []
+        seen, early, reads = [], [], []
         inner = tr.compute_loss
 
         def spy(model, inputs, *a, **k):
             seen.append(inputs["input_ids"].cpu().clone())
-            early.append(id(inputs["labels"]) in tr._ahead_results)
+            early.append(getattr(tr._ahead.get(id(inputs["labels"])), "teacher", None) is not None)
             return inner(model, inputs, *a, **k)
         tr.compute_loss = spy
-        tr.train()
-        return seen, early, [h["loss"] for h in tr.state.log_history if "loss" in h], student.flat.clone()
-    seen_a, early_a, loss_a, flat_a = run(True)
-    seen_b, early_b, loss_b, flat_b = run(False)
+        with monkeypatch.context() as mp:
+            for name in ("loss_rows", "packed_rows"):   # the selections, each with the micro-batch's one host read
+                mp.setattr(ops, name, lambda *a, _f=getattr(ops, name), **k: reads.append(1) or _f(*a, **k))
+            tr.train()
+        return seen, early, [h["loss"] for h in tr.state.log_history if "loss" in h], student.flat.clone(), len(reads)
+    seen_a, early_a, loss_a, flat_a, reads_a = run(True)
+    seen_b, early_b, loss_b, flat_b, reads_b = run(False)
     assert len(seen_a) == len(seen_b) == 14 and len(loss_a) == 8
+    assert reads_a == reads_b == 14      # one selection per micro-batch, made ahead or in compute_loss, never both
     for a, b in zip(seen_a, seen_b):
         assert a.shape == b.shape and torch.equal(a, b)
     assert loss_a == loss_b and torch.equal(flat_a, flat_b)

@@ -201,6 +201,126 @@ def test_tokens_per_second_is_logged_by_the_real_loop():
     assert sub and all("tokens_per_second" not in d for d in sub)
 
 
+# ------------------------------------------------------------------------------------------------------ the step plan
+@pytest.fixture(scope="module")
+def hip_trainer():
+    """A DistillationTrainer over two HipQwen3ForCausalLM on the CPU: ``_plan_step`` runs no model, and on CPU tensors
+    ``ops.loss_rows`` / ``ops.packed_rows`` take their torch paths."""
+    import speech_distill_amd as sda
+    from transformers import TrainingArguments
+    from speech_distill_amd.trainer import DistillationTrainer
+    dims = sda.Qwen3Dims(640, 128, 256, 2, 2, 1)
+    student, teacher = sda.HipQwen3ForCausalLM(dims, device="cpu", seed=0), sda.HipQwen3ForCausalLM(dims, device="cpu", seed=1)
+    args = TrainingArguments(output_dir=tempfile.mkdtemp(), use_cpu=True, report_to=[], remove_unused_columns=False,
+                             label_names=["labels"], save_strategy="no")
+    return DistillationTrainer(model=student, args=args, teacher_model=teacher, top_k=4), student
+
+
+def _grid_rows(labels, speech_mask=None, same_doc=None):
+    """The rule, written out: flat position m = b*T+t with t < T-1 is a loss row iff the NEXT label is not -100 (and the
+    next speech bit is set, and -- packed -- the next token lies in the same document); it predicts that label."""
+    B, T = labels.shape
+    rows, labs = [], []
+    for b in range(B):
+        for t in range(T - 1):
+            if (int(labels[b, t + 1]) != -100 and (speech_mask is None or int(speech_mask[b, t + 1]) != 0)
+                    and (same_doc is None or same_doc(b * T + t, b * T + t + 1))):
+                rows.append(b * T + t)
+                labs.append(int(labels[b, t + 1]))
+    return rows, labs
+
+
+def _plan(tr, core, b, need_teacher=True, **kw):
+    return tr._plan_step(core, b, b.get("labels"), b.get("speech_token_mask"), b.get("teacher_attention_mask"), need_teacher, **kw)
+
+
+def test_step_plan_of_padded_batches(hip_trainer):
+    tr, core = hip_trainer
+    checked = {"padding_checked": True}
+    b = batch()
+    b["attention_mask"][1, 4:] = 0
+    b["teacher_attention_mask"][1, 5:] = 0
+    b["speech_token_mask"] = torch.tensor([[1, 1, 1, 0, 1, 1], [1, 1, 1, 1, 1, 0]])
+    plan = _plan(tr, core, b)
+    want = _grid_rows(b["labels"], b["speech_token_mask"])
+    assert want[0] == [1, 3, 4, 7, 8, 9] and (plan.rows.tolist(), plan.row_labels.tolist()) == want
+    assert plan.student_kw == checked and plan.teacher_kw == checked
+    assert plan.packed is None and plan.event is None and plan.full_labels is None
+    # the key: equal for the same tensors, another for an equal copy of any keyed tensor at another address
+    assert _plan(tr, core, b).key == plan.key and _plan(tr, core, b, stored=plan) is plan
+    for k in ("labels", "speech_token_mask", "attention_mask", "teacher_attention_mask"):
+        other = _plan(tr, core, dict(b, **{k: b[k].clone()}), stored=plan)
+        assert other is not plan and other.key != plan.key and other.rows.tolist() == want[0], k
+    # a teacher mask of another width: not this batch's grid, so the teacher keeps its own validation; nothing is raised here
+    wide = dict(b, teacher_attention_mask=torch.ones(2, 8, dtype=torch.long))
+    plan = _plan(tr, core, wide)
+    assert plan.student_kw == checked and plan.teacher_kw == {} and plan.rows.tolist() == want[0]
+    # ... and a teacher that will not run (pre-extracted top-K) has its mask neither checked nor keyed
+    idle = _plan(tr, core, b, need_teacher=False)
+    assert idle.teacher_kw == {} and idle.key[5] is None and idle.key[:5] == _plan(tr, core, b).key[:5]
+    with pytest.raises(ValueError, match="right-padded"):
+        _plan(tr, core, dict(b, teacher_attention_mask=torch.tensor([[1] * 6, [0, 1, 1, 1, 1, 1]])))
+    _plan(tr, core, dict(b, teacher_attention_mask=torch.tensor([[1] * 6, [0, 1, 1, 1, 1, 1]])), need_teacher=False)
+    # no attention mask at all: nothing to check, both models may skip it
+    bare = {k: v for k, v in b.items() if not k.endswith("attention_mask")}
+    plan = _plan(tr, core, bare)
+    assert plan.student_kw == checked and plan.teacher_kw == checked and plan.key[4:] == (None, None, None)
+    assert (plan.rows.tolist(), plan.row_labels.tolist()) == want
+    # the caller takes the full path: nothing is selected, nothing is read
+    assert _plan(tr, core, b, select=False) == type(plan)() and _plan(tr, core, dict(b, labels=None)) == type(plan)()
+
+
+def test_step_plan_without_a_loss_row_and_the_full_path_zeros(hip_trainer):
+    """The plan of a batch without a loss row, and the reference's zeros from ``compute_loss``.  The stand-in student below
+    takes the full path whatever the plan says; ``compute_loss``'s own zero-row fall-back (a HIP student, a plan that keeps
+    its event) is test_gpu_trainer.py::test_zero_row_batch_planned_ahead_takes_the_full_path."""
+    tr, core = hip_trainer
+    b = batch()
+    b["labels"] = torch.full_like(b["labels"], -100)
+    plan = _plan(tr, core, b)
+    assert plan.rows.numel() == 0 and plan.row_labels.numel() == 0 and plan.student_kw == {"padding_checked": True}
+    # compute_loss on that batch: the full path, the reference's zeros (distillation_loss.py:47-53)
+    tr2, student, teacher, logged = make(top_k=4)
+    loss = tr2.compute_loss(student, b)
+    assert float(loss.detach()) == 0.0 and tr2.distill_loss_fn.seen == ["sparse"] and student.calls == teacher.calls == 1
+    assert logged[-1] == {"student_loss": 0.0, "teacher_loss": 0.0, "distill_loss": 0.0}
+
+
+def test_step_plan_of_packed_batches(hip_trainer):
+    tr, core = hip_trainer
+    #                        doc 0: 0..3          doc 1: 4   doc 2: 5..9
+    labels = torch.tensor([[-100, 7, 8, -100,     21,        9, -100, 31, 32, 33]])    # (real labels at two document starts)
+    cu = torch.tensor([0, 4, 5, 10], dtype=torch.int32)
+    pos = torch.tensor([[0, 1, 2, 3, 0, 0, 1, 2, 3, 4]])
+    doc = [0, 0, 0, 0, 1, 2, 2, 2, 2, 2]
+    want = _grid_rows(labels, same_doc=lambda m, n: doc[m] == doc[n])
+    assert want == ([0, 1, 6, 7, 8], [7, 8, 31, 32, 33])
+    b = {"input_ids": torch.zeros_like(labels), "labels": labels, "position_ids": pos, "cu_seq_lens_q": cu, "cu_seq_lens_k": cu,
+         "max_length_q": 5, "max_length_k": 5, "teacher_input_ids": torch.zeros_like(labels)}
+    plan = _plan(tr, core, b)
+    assert (plan.rows.tolist(), plan.row_labels.tolist()) == want and plan.full_labels is None
+    # (on the CPU no model takes a descriptor: both get the packed keys themselves)
+    assert plan.packed == (None, None) and plan.student_kw == {} and plan.teacher_kw == {}
+    assert _plan(tr, core, b).key == plan.key and _plan(tr, core, b, select=False).rows.tolist() == want[0]
+    for k in ("labels", "cu_seq_lens_q"):
+        assert _plan(tr, core, dict(b, **{k: b[k].clone()})).key != plan.key, k
+    with pytest.raises(ValueError, match="attention_mask"):      # a batch planned ahead is refused by the plan
+        _plan(tr, core, dict(b, teacher_attention_mask=torch.ones_like(labels)), event="e")
+    with pytest.raises(ValueError, match="position-aligned"):
+        _plan(tr, core, dict(b, teacher_input_ids=torch.zeros(1, 9, dtype=torch.long)), event="e")
+    # the same batch by position_ids alone: the same rows, from the labels with every document start masked
+    bare = {k: v for k, v in b.items() if not k.startswith(("cu_seq_lens", "max_length"))}
+    plan = _plan(tr, core, bare)
+    masked = labels.clone()
+    masked[0, [0, 4, 5]] = -100
+    assert torch.equal(plan.full_labels, masked) and (plan.rows.tolist(), plan.row_labels.tolist()) == want
+    assert plan.packed is None and plan.student_kw == plan.teacher_kw == {"padding_checked": True}
+    assert _plan(tr, core, bare).key == plan.key and plan.key[-1] is None
+    off = _plan(tr, core, bare, select=False)
+    assert off.rows is None and torch.equal(off.full_labels, masked) and off.student_kw == {}
+    assert _plan(tr, core, bare, event=object()) is None and _plan(tr, core, b, event="e").event == "e"   # never planned ahead
+
+
 def test_rs_ag_fallback_is_loud_and_counted(monkeypatch):
     """algo='rs_ag' on a bucket that does not divide by the world size falls back to all_reduce with ONE
     warning per bucket size and a count in stats -- never silently."""
